@@ -12,9 +12,11 @@ ROIHeads3DGDINO's native GroundingDINO network (Swin-B + BERT-base + 6/6 deforma
 random-init weights, 6 prompted categories) -> phrase scores -> NMS; `--proposals oracle2d` measures the
 oracle-2D branch instead (32 given boxes/image, SURVEY.md §8d mode A).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel, HIP
-events on the launch stream) and `cpu_baseline` (the fp32 torch CPU oracle on the host cores, rank 0,
-N=1 only, bounded sample).
+Prints ONE JSON line on rank 0. A plain run sets up, warms up, times --steps steps and prints the headline
+(`value`, `ms_per_step`). `--full` adds what takes measurements or runs of its own: `roofline` and `kernels`
+(HIP events on the launch stream), the detector alone, `alt_precision` / `alt_canvas` (child processes),
+`mixed_shapes`, `cpu_baseline` (the fp32 torch CPU oracle on the host cores, rank 0, N=1 only, bounded
+sample) and `parity`. `--dump-outputs DIR` writes rank 0's outputs of the last timed step as .npy files.
 """
 import argparse
 import json
@@ -42,6 +44,33 @@ def kernel_flops(T, D):
             "fc1": 8.0 * T * D * D, "fc2": 8.0 * T * D * D}
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out, dirname):
+    """Every field of every image's Instances as DIR/image<i>_<field>.npy: floating fields as float32 (float64 stays float64),
+    integer and bool fields as float64 (exact). Above DUMP_CAP_BYTES in all, each image keeps the same fixed, seeded sample of
+    its detections in every field."""
+    import numpy as np
+    arrays = {}
+    for i, o in enumerate(out):
+        for name, v in o["instances"].get_fields().items():
+            t = torch.as_tensor(v.tensor if hasattr(v, "tensor") else v).detach().cpu()
+            arrays[(i, name)] = t.float() if t.is_floating_point() and t.dtype != torch.float64 else t.double()
+    total = sum(t.numel() * t.element_size() for t in arrays.values())
+    if total > DUMP_CAP_BYTES:
+        frac = DUMP_CAP_BYTES / total
+        keep = {}
+        for (i, name), t in arrays.items():
+            if i not in keep:
+                n = t.shape[0]
+                keep[i] = torch.randperm(n, generator=torch.Generator().manual_seed(i))[:int(n * frac)].sort().values
+            arrays[(i, name)] = t[keep[i]]
+    os.makedirs(dirname, exist_ok=True)
+    for (i, name), t in arrays.items():
+        np.save(os.path.join(dirname, f"image{i}_{name}.npy"), t.numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -61,9 +90,14 @@ def main():
                     help="gdino: ROIHeads3DGDINO (the headline); oracle2d: given boxes; rpn: the route the reference's --eval-only takes without "
                          "oracle boxes (RPN -> box head -> Fast R-CNN inference -> cube head, rcnn3d.py:105-111; its published number, "
                          "nohup.out:939, is ViT-B: --model vitb14)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-alt", action="store_true", help="skip the extra measurements (one-pass fp16; tight 518 canvas)")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline (roofline, per-kernel "
+                                                        "figures, detector alone, one-pass fp16, tight canvas, mixed shapes, CPU baseline, parity)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and parity")
+    ap.add_argument("--no-alt", action="store_true", help="with --full: skip the extra measurements (one-pass fp16; tight 518 canvas; mixed shapes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write rank 0's outputs of the last timed step to DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start one rank per GPU through torch.distributed.run as a CHILD process,
@@ -215,6 +249,8 @@ def main():
         if world > 1:
             dist.barrier()
         dt = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:
+            dump_outputs(out, args.dump_outputs)
         if os.environ.get("OVM_BENCH_HOSTTIME") == "1" and use_gdino and profile:
             print(f"[hosttime] step {dt / steps * 1e3:.3f} ms, inside ovm_infer {c_time[0] / steps * 1e3:.3f} ms", file=sys.stderr)
         prof = model.engine.profile_read() if profile else None
@@ -241,67 +277,69 @@ def main():
             dt = float(t.item())
         return dt, prof, ndet, model, host_inputs, cfg, out, inputs
 
-    dt, prof, ndet, model, host_inputs, cfg, last_out, inputs_dev = run(args.precision, args.steps, args.warmup, True)
+    dt, prof, ndet, model, host_inputs, cfg, last_out, inputs_dev = run(args.precision, args.steps, args.warmup, args.full)
     ms_per_step = dt / args.steps * 1e3
     value = world * B * args.steps / dt
 
     # ---- roofline of the dominant kernel (HIP events, launch stream) ----
-    kf = kernel_flops(T, D)
-    dominant = max((k for k in kf), key=lambda k: prof[k][0])
-    tot_ms, launches = prof[dominant]
-    avg_ms = tot_ms / max(launches, 1)
-    flops_launch = kf[dominant] * B
-    achieved = flops_launch / (avg_ms * 1e-3) / 1e12 if avg_ms > 0 else 0.0
-    # HBM-side bytes per launch of the dominant kernel come from a separate rocprofv3 --pmc pass over this same command
-    # (profiles/rNN/pmc_traffic_*.json documents the command and the gfx950 FETCH_SIZE correction; newest round first); null if none matches
-    traffic = traffic_source = None
-    for tdir in ("r03", "r02", "r01"):
-        try:
-            tj = json.load(open(os.path.join(ROOT, "profiles", tdir, "pmc_traffic_f16x3_vitl14_T4097_b1.json")))
-            wl = tj["workload"]
-            # per-launch HBM bytes of a kernel do not depend on what runs beside it, but the figure is only quoted for the same
-            # model / canvas / precision / batch, and its provenance is stated next to it
-            if (wl["model"], wl["canvas"], wl["precision"], wl["batch"]) == (args.model, args.canvas, args.precision, B):
-                key = {"attn": "attn_kernel"}.get(dominant)
-                for kn, kv in tj["kernels"].items():
-                    if key and key in kn:
-                        traffic = kv["traffic_bytes_per_launch"]
-                        traffic_source = (f"profiles/{tdir}/pmc_traffic_f16x3_vitl14_T4097_b1.json: separate rocprofv3 --pmc FETCH_SIZE / "
-                                          f"WRITE_SIZE passes over bench.py --proposals {wl.get('proposals', 'oracle2d')} (per-launch bytes of the "
-                                          "same kernel at the same shapes, counters-only run of its own: PMC collection cannot share the timed run)")
-                if traffic is not None:
-                    break
-        except (OSError, KeyError, ValueError):
-            continue
-    roofline = {"bound": "mfma", "kernel": dominant, "achieved": round(achieved, 2), "peak": PEAK_F16_TFLOPS,
-                "unit": "TFLOP/s", "frac": round(achieved / PEAK_F16_TFLOPS, 4), "traffic": traffic,
-                "traffic_source": traffic_source,
-                "avg_launch_ms": round(avg_ms, 4), "launches": launches,
-                "algorithmic_flops_per_launch": flops_launch,
-                "mfma_passes_per_product": 3 if args.precision == "f16x3" else 1}
-    if args.tower == "sam":
-        roofline["note"] = ("the per-launch FLOP model assumes global attention over all T tokens; 8 of SAM's 12 blocks attend inside 14 x 14 "
-                            "windows and all of them run on the fp32-MFMA attention kernel: read `value`, not this fraction")
-    if use_gdino:
-        roofline["note"] = ("launch durations are measured while the GroundingDINO graph runs concurrently on a side stream "
-                            "(the kernels share the CUs); --proposals oracle2d gives the uncontended figure")
-    kernels = {k: {"ms_per_step": round(prof[k][0] / args.steps, 4), "launches_per_step": prof[k][1] // args.steps,
-                   **({"tflops": round(kf[k] * B * prof[k][1] / (prof[k][0] * 1e-3) / 1e12, 2)} if k in kf and prof[k][0] > 0 else {})}
-               for k in prof}
-    if use_gdino and gd_events:
-        kernels["gdino_network_alone"] = {"ms_per_forward": round(gd_events[0][0], 4), "launches_per_forward": gd_events[0][1],
-                                          "note": "the C++ GroundingDINO engine by itself (graph replay), measured after the timed region; "
-                                                  "inside a step it runs on a side stream beside the ViT"}
+    roofline = kernels = None
+    if args.full:
+        kf = kernel_flops(T, D)
+        dominant = max((k for k in kf), key=lambda k: prof[k][0])
+        tot_ms, launches = prof[dominant]
+        avg_ms = tot_ms / max(launches, 1)
+        flops_launch = kf[dominant] * B
+        achieved = flops_launch / (avg_ms * 1e-3) / 1e12 if avg_ms > 0 else 0.0
+        # HBM-side bytes per launch of the dominant kernel come from a separate rocprofv3 --pmc pass over this same command
+        # (profiles/rNN/pmc_traffic_*.json documents the command and the gfx950 FETCH_SIZE correction; newest round first); null if none matches
+        traffic = traffic_source = None
+        for tdir in ("r03", "r02", "r01"):
+            try:
+                tj = json.load(open(os.path.join(ROOT, "profiles", tdir, "pmc_traffic_f16x3_vitl14_T4097_b1.json")))
+                wl = tj["workload"]
+                # per-launch HBM bytes of a kernel do not depend on what runs beside it, but the figure is only quoted for the same
+                # model / canvas / precision / batch, and its provenance is stated next to it
+                if (wl["model"], wl["canvas"], wl["precision"], wl["batch"]) == (args.model, args.canvas, args.precision, B):
+                    key = {"attn": "attn_kernel"}.get(dominant)
+                    for kn, kv in tj["kernels"].items():
+                        if key and key in kn:
+                            traffic = kv["traffic_bytes_per_launch"]
+                            traffic_source = (f"profiles/{tdir}/pmc_traffic_f16x3_vitl14_T4097_b1.json: separate rocprofv3 --pmc FETCH_SIZE / "
+                                              f"WRITE_SIZE passes over bench.py --proposals {wl.get('proposals', 'oracle2d')} (per-launch bytes of the "
+                                              "same kernel at the same shapes, counters-only run of its own: PMC collection cannot share the timed run)")
+                    if traffic is not None:
+                        break
+            except (OSError, KeyError, ValueError):
+                continue
+        roofline = {"bound": "mfma", "kernel": dominant, "achieved": round(achieved, 2), "peak": PEAK_F16_TFLOPS,
+                    "unit": "TFLOP/s", "frac": round(achieved / PEAK_F16_TFLOPS, 4), "traffic": traffic,
+                    "traffic_source": traffic_source,
+                    "avg_launch_ms": round(avg_ms, 4), "launches": launches,
+                    "algorithmic_flops_per_launch": flops_launch,
+                    "mfma_passes_per_product": 3 if args.precision == "f16x3" else 1}
+        if args.tower == "sam":
+            roofline["note"] = ("the per-launch FLOP model assumes global attention over all T tokens; 8 of SAM's 12 blocks attend inside 14 x 14 "
+                                "windows and all of them run on the fp32-MFMA attention kernel: read `value`, not this fraction")
+        if use_gdino:
+            roofline["note"] = ("launch durations are measured while the GroundingDINO graph runs concurrently on a side stream "
+                                "(the kernels share the CUs); --proposals oracle2d gives the uncontended figure")
+        kernels = {k: {"ms_per_step": round(prof[k][0] / args.steps, 4), "launches_per_step": prof[k][1] // args.steps,
+                       **({"tflops": round(kf[k] * B * prof[k][1] / (prof[k][0] * 1e-3) / 1e12, 2)} if k in kf and prof[k][0] > 0 else {})}
+                   for k in prof}
+        if use_gdino and gd_events:
+            kernels["gdino_network_alone"] = {"ms_per_forward": round(gd_events[0][0], 4), "launches_per_forward": gd_events[0][1],
+                                              "note": "the C++ GroundingDINO engine by itself (graph replay), measured after the timed region; "
+                                                      "inside a step it runs on a side stream beside the ViT"}
     total_flops = vit_flops(T, D, L, G * G) * B
     e2e_tflops = total_flops * args.steps / dt / 1e12
 
     alt = None
-    if not args.no_alt and args.precision == "f16x3" and world == 1:
+    if args.full and not args.no_alt and args.precision == "f16x3" and world == 1:
         # the one-pass fp16 mode is measured in a child process of its own (fresh handle, graphs and allocator state), after
         # this process has finished its timed region
         import subprocess
         torch.cuda.synchronize()
-        cmd = [sys.executable, os.path.abspath(__file__), "--precision", "f16", "--no-alt", "--no-cpu-baseline", "--steps", str(args.steps),
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--precision", "f16", "--no-alt", "--no-cpu-baseline", "--steps", str(args.steps),
                "--warmup", str(args.warmup), "--proposals", args.proposals, "--model", args.model, "--canvas", str(args.canvas),
                "--net-res", str(args.net_res), "--boxes", str(args.boxes), "--batch", str(args.batch)]
         try:
@@ -313,11 +351,11 @@ def main():
         except Exception as e:                                   # the extra measurement must never break the contract line
             alt = {"precision": "f16", "error": repr(e)[:200]}
     alt_canvas = None
-    if not args.no_alt and world == 1 and args.canvas == 896 and args.net_res == 532:
+    if args.full and not args.no_alt and world == 1 and args.canvas == 896 and args.net_res == 532:
         # SURVEY.md 8(d) second canvas mode, a declared deviation from the reference's plumbing: 512x512 fed unresized on a
         # tight 518x518 canvas (G = 37, T = 1370) instead of ResizeShortestEdge(532) on SQUARE_PAD 896
         import subprocess
-        cmd = [sys.executable, os.path.abspath(__file__), "--precision", args.precision, "--no-alt", "--no-cpu-baseline", "--steps",
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--precision", args.precision, "--no-alt", "--no-cpu-baseline", "--steps",
                str(args.steps), "--warmup", str(args.warmup), "--proposals", args.proposals, "--model", args.model, "--canvas", "518",
                "--net-res", "512", "--boxes", str(args.boxes), "--batch", str(args.batch)]
         try:
@@ -335,7 +373,7 @@ def main():
     # timed beside the mixed order: their ratio is what switching plans costs. Larger images carry more detector work than the
     # 532 x 532 headline, so neither figure is comparable with `value`; reported next to it, never as `value`.
     mixed = None
-    if not args.no_alt and world == 1 and args.canvas == 896 and args.net_res == 532:
+    if args.full and not args.no_alt and world == 1 and args.canvas == 896 and args.net_res == 532:
         try:
             shapes = [(532, w) for w in range(532, 897, 16)] + [(h, 532) for h in range(548, 897, 16)]
             g = torch.Generator().manual_seed(77)
@@ -377,7 +415,7 @@ def main():
             mixed = {"error": repr(e)[:300]}
 
     cpu_baseline = parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle.pipeline import inference
         from parity import parity_ok, parity_report
         try:

@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/r02
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py"
+B="python3 $R/bench.py --full"
 timeout -k 10 500 $B > $O/bench_final.json 2> $O/bench_final.err; echo "bench rc=$?"
 timeout -k 10 200 $B --proposals oracle2d --no-alt --no-cpu-baseline > $O/bench_oracle2d.json 2> $O/bench_oracle2d.err; echo "oracle2d rc=$?"
 timeout -k 10 300 $B --proposals oracle2d --no-alt --no-cpu-baseline --batch 16 --steps 10 > $O/bench_oracle2d_b16.json 2> $O/bench_oracle2d_b16.err; echo "b16 rc=$?"

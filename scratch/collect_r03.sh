@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/r03
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py"
+B="python3 $R/bench.py --full"
 PART=${1:-all}      # "bench": the bench lines; "prof": kernel trace + PMC passes (two gpurun calls: together they exceed one call's limit)
 if [ "$PART" != "prof" ]; then
 timeout -k 10 500 $B > $O/bench_final.json 2> $O/bench_final.err || { echo "bench FAILED rc=$?"; exit 1; }; echo "bench ok"

@@ -17,7 +17,7 @@ if os.path.exists(os.path.join(O, "bench_jpeg.json")):
 # kernel statistics: top 60 rows
 rows = open(os.path.join(O, "kernel_stats.csv")).read().splitlines()
 open(os.path.join(P, "kernel_stats_f16x3_vitl14_gdino_T4097_b1.csv"), "w").write("\n".join(rows[:61]) + "\n")
-CMD = "python3 bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-alt   (default workload: ROIHeads3DGDINO, the configuration the bench line prints)"
+CMD = "python3 bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-alt   (default workload: ROIHeads3DGDINO, the configuration the bench line prints)"
 sq = json.load(open(os.path.join(O, "pmc_sq.summary.json")))
 out = {"note": "rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS "
                "GRBM_GUI_ACTIVE --output-format csv -- " + CMD + "; counters only (no trace domains); per-dispatch means. mfma_util = MFMA busy cycles / "

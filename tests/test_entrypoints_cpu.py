@@ -225,3 +225,28 @@ def test_category_map_of_the_eval_entry_point(tmp_path):
     meta = tmp_path / "category_meta.json"
     meta.write_text(json.dumps({"thing_classes": ["chair", "sofa"], "thing_dataset_id_to_contiguous_id": {"18": 0, "40": 1}}))
     assert category_map_for(cfg, "base", gt, str(meta)).contiguous_to_dataset_id == {0: 18, 1: 40}
+
+
+def test_bench_dump_outputs_dtypes_and_seeded_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every field of every image's Instances as a float32 / float64 .npy (class ids exact). Above the
+    size cap each image keeps one seeded sample of its detections: the same rows in every field, and the same from run to run."""
+    import bench
+    out = [{"instances": _fake_instances(40, 1)}, {"instances": _fake_instances(7, 2)}]
+    bench.dump_outputs(out, str(tmp_path / "a"))
+    a = {f: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert len(a) == 2 * 8 and all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert a["image0_pred_classes.npy"].dtype == np.float64 and a["image0_scores.npy"].dtype == np.float32
+    assert np.array_equal(a["image0_pred_classes.npy"], out[0]["instances"].pred_classes.numpy())
+    assert np.array_equal(a["image1_pred_boxes.npy"], out[1]["instances"].pred_boxes.tensor.numpy())
+    full = sum(v.nbytes for v in a.values())
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", full // 2)
+    bench.dump_outputs(out, str(tmp_path / "b"))
+    bench.dump_outputs(out, str(tmp_path / "c"))
+    b = {f: np.load(tmp_path / "b" / f) for f in a}
+    c = {f: np.load(tmp_path / "c" / f) for f in a}
+    assert 0 < sum(v.nbytes for v in b.values()) <= full // 2
+    assert all(np.array_equal(b[f], c[f]) for f in a)
+    for i in range(2):
+        rows = [int(np.flatnonzero(a[f"image{i}_scores.npy"] == s)[0]) for s in b[f"image{i}_scores.npy"]]
+        for f in ("pred_pose", "pred_boxes", "pred_classes"):
+            assert np.array_equal(b[f"image{i}_{f}.npy"], a[f"image{i}_{f}.npy"][rows])

@@ -184,3 +184,27 @@ def test_bench_gpus2_real_steps_gloo(device):
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["value"] > 0 and abs(d["value"] - 2 * 3 / (d["ms_per_step"] * 3e-3)) / d["value"] < 1e-2
     assert d["scaling"] == "weak" and "dry_run" not in d
+
+
+def test_bench_plain_and_full_runs_dump_the_same_outputs(device, tmp_path):
+    """A plain `bench.py` run prints the headline of exactly --steps timed steps and none of the --full figures; `--full` adds
+    them. With the same arguments both runs compute the same outputs in their last timed step (--dump-outputs)."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--model", "vittest14", "--canvas", "224",
+           "--net-res", "140", "--proposals", "oracle2d", "--boxes", "8"]
+    lines, dumps = [], []
+    for k, extra in enumerate(([], ["--full", "--no-alt"])):
+        r = subprocess.run(cmd + extra + ["--dump-outputs", str(tmp_path / f"o{k}")], capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        js = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(js) == 1, r.stdout
+        d = json.loads(js[0])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and abs(d["value"] - 3 / (d["ms_per_step"] * 3e-3)) / d["value"] < 1e-2
+        lines.append(d)
+        dumps.append({f: np.load(tmp_path / f"o{k}" / f) for f in sorted(os.listdir(tmp_path / f"o{k}"))})
+    plain, full = lines
+    assert all(plain[k] is None for k in ("roofline", "kernels", "cpu_baseline", "parity"))
+    assert full["roofline"]["kernel"] in full["kernels"] and "ok_1e-3" in full["parity"] and full["cpu_baseline"]["value"] > 0
+    assert "image0_pred_bbox3D.npy" in dumps[0] and dumps[0].keys() == dumps[1].keys()
+    for f, a in dumps[0].items():
+        assert a.dtype in (np.float32, np.float64), f
+        np.testing.assert_allclose(dumps[1][f], a, rtol=1e-6, atol=1e-6, err_msg=f)
