@@ -3,8 +3,10 @@
 
 Per image: read -> K from the focal-length convention of the reference (:63-76, including its quirk that the
 first image's focal length sticks) -> ResizeShortestEdge -> model([{image, height,
-width, K, category_list}]) -> threshold on score (:99). Drawing (vis.draw_scene_view, :107-118) is
-presentation and out of scope: detections are written as JSON next to where the reference writes its JPEGs.
+width, K, category_list}]) -> threshold on score (:99) -> ``<name>_dets.json`` with the kept detections, and, as the reference
+(:89-121), ``<name>_combine.jpg``: the image with the kept boxes rendered and outlined beside a top-down view of them
+(``ovmono3d_amd.vis.draw_scene_view``, drawn on the device; encoded with Pillow at quality 95), or ``<name>_boxes.jpg`` (the input)
+when no detection is kept. ``MODEL.AMD.VIS False`` writes the JSON only.
 
 2D boxes: the reference's demo always goes through ROIHeads3DGDINO (category_list is set, :84). Select it with
 ``MODEL.ROI_HEADS.NAME ROIHeads3DGDINO``: the native GroundingDINO network (``ovmono3d_amd/gdino``) is built from
@@ -48,6 +50,7 @@ def do_test(args, cfg, model):
         gpu_resize = ResizeShortestEdgeGPU(cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST)
     gpu_jpeg = gpu_resize is not None and bool(cfg.MODEL.AMD.get("GPU_JPEG", False))
     use_gdino_head = cfg.MODEL.ROI_HEADS.NAME == "ROIHeads3DGDINO"
+    vis_on = bool(cfg.MODEL.AMD.get("VIS", True))
     for name in ims:
         im_name = os.path.splitext(name)[0]
         cats = cats_per_img.get(im_name, [])
@@ -78,12 +81,13 @@ def do_test(args, cfg, model):
             d["category_list"] = cats
         dets = model([d])[0]["instances"]
         n_det = len(dets) if dets.get_fields() else 0
-        out = []
+        out, kept_idx = [], []
         if n_det > 0 and dets.has("pred_bbox3D"):
             for idx in range(n_det):
                 score = float(dets.scores[idx])
                 if score < thres:
                     continue
+                kept_idx.append(idx)
                 ci = int(dets.pred_classes[idx])
                 out.append({"category": cats[ci] if ci < len(cats) else ci, "score": score,
                             "bbox3D": dets.pred_center_cam[idx].tolist() + dets.pred_dimensions[idx].tolist(),
@@ -92,6 +96,24 @@ def do_test(args, cfg, model):
         print("File: {} with {} dets".format(im_name, len(out)))
         with open(os.path.join(cfg.OUTPUT_DIR, im_name + "_dets.json"), "w") as f:
             json.dump({"K": K.tolist(), "detections": out}, f)
+        if vis_on:
+            write_views(im, K, out, kept_idx, cfg.OUTPUT_DIR, im_name)
+
+
+def write_views(im, K, dets, kept_idx, output_dir, im_name):
+    """demo.py:89-121: the kept boxes drawn (front + novel view, scale = H) into <name>_combine.jpg, else <name>_boxes.jpg."""
+    from PIL import Image
+    from ovmono3d_amd import vis
+    if len(dets) > 0:
+        corners = np.asarray([d["corners3D"] for d in dets], np.float64)
+        colors = np.asarray([[c / 255.0 for c in vis.get_color(i)] for i in kept_idx], np.float32)
+        text = ["{} {:.2f}".format(d["category"], d["score"]) for d in dets]
+        front, novel = vis.draw_scene_view(im, K, corners, colors, text=text, scale=int(im.shape[0]), blend_weight=0.5,
+                                           blend_weight_overlay=0.85)
+        bgr, name = vis.concat_views(front, novel).cpu().numpy(), im_name + "_combine.jpg"
+    else:
+        bgr, name = (im.cpu().numpy() if torch.is_tensor(im) else np.asarray(im)), im_name + "_boxes.jpg"
+    Image.fromarray(np.ascontiguousarray(bgr[:, :, ::-1])).save(os.path.join(output_dir, name), quality=95)
 
 
 def setup(args):
@@ -115,7 +137,7 @@ if __name__ == "__main__":
     parser.add_argument("--focal-length", type=float, default=0, help="focal length for image inputs (in px)")
     parser.add_argument("--principal-point", type=float, default=[], nargs=2, help="principal point for image inputs (in px)")
     parser.add_argument("--threshold", type=float, default=0.25, help="threshold on score for visualizing")
-    parser.add_argument("--display", default=False, action="store_true", help="unused (no drawing in the native build)")
+    parser.add_argument("--display", default=False, action="store_true", help="no-op: there is no GUI on the target (the views are written to <name>_combine.jpg)")
     parser.add_argument("--eval-only", default=True, action="store_true", help="perform evaluation only")
     parser.add_argument("--num-gpus", type=int, default=1, help="number of gpus *per machine*")
     parser.add_argument("--num-machines", type=int, default=1, help="total number of machines")

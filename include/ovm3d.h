@@ -141,7 +141,7 @@ int ovm_destroy(OvmHandle* h);
 const char* ovm_last_error(const OvmHandle* h);
 const char* ovm_version(void);
 /* sizeof() of a struct of this header as the library was compiled ("OvmConfig", "OvmTensor", "OvmImage", "OvmDet3D",
- * "OvmGdinoConfig"), -1 for an unknown name: lets a binding check its mirror of the layout before the first call. */
+ * "OvmGdinoConfig", "OvmJpegInfo", "OvmSceneInput", "OvmSceneLayout", "OvmSceneSegment"), -1 for an unknown name: lets a binding check its mirror of the layout before the first call. */
 int ovm_abi_sizeof(const char* struct_name);
 
 /* --- backbone: build_dino_backbone(...).forward(x, prompt_depth) -> {p2,p3,p4}
@@ -416,6 +416,87 @@ typedef struct OvmJpegInfo {
 int ovm_host_jpeg_info(const uint8_t* data, size_t n, OvmJpegInfo* info);
 int ovm_host_jpeg_entropy_decode(const uint8_t* data, size_t n, int16_t* coef, int64_t coef_capacity, OvmJpegInfo* info);
 int ovm_jpeg_reconstruct(const int16_t* coef, const OvmJpegInfo* info, uint8_t* planes, uint8_t* rgb, ovm_stream_t stream);
+
+/* ---- Visualisation ----------------------------------------------------------------------------------------------------------
+ * draw_scene_view(mode in {front, novel, front_and_novel}) of the reference (cubercnn/vis/vis.py:309-640, edges :673-748, labels
+ * :755-784): the input image with the boxes rendered, blended and outlined, and a top-down "novel" view of the same boxes over a
+ * ground grid. The reference draws with pytorch3d (MeshRasterizer + SoftPhongShader) and cv2; the rules below restate those calls
+ * and are pinned by the numpy restatement tests/scene_oracle.py, not by the two libraries (neither is available to compare).
+ *
+ * ovm_host_scene_layout (host, fp64, no GPU): per-view box frames, depth order, the zoom search (:442-478), the ground bounds
+ * (:488-533, with the reference's quirks), the deduplicated grid segment set (:557-579), edge endpoints after zplane clipping and
+ * the label rectangles. ovm_render_scene (device, one stream-ordered call): triangle setup, per-tile culling, rasterisation,
+ * Phong shading, softmax blend, grid, edges, labels and the overlay, written once as BGR uint8.
+ *
+ * Declared deviations from the reference:
+ *  - triangles are clipped against z = zplane before projection (pytorch3d does not clip); a clipped triangle becomes up to two;
+ *  - a pixel (row i, col j) samples the image point (j + 0.5, i + 0.5) under K; covered = edge functions all >= 0 or all <= 0;
+ *  - thick lines: a pixel is covered when its integer centre lies within thickness / 2 of the segment (cv2 draws a polygon with
+ *    round caps); the segment is clipped to the canvas grown by that radius, which leaves the covered set unchanged;
+ *  - label glyphs are a coverage mask made by the caller (Pillow's built-in font, not cv2's Hershey font); the text size used
+ *    for the background rectangle is that mask's size;
+ *  - box colours come from the caller (the reference jitters them with an unseeded RNG);
+ *  - the depth order is a stable sort of the mean corner y (the reference's default argsort is not stable for > 16 boxes);
+ *  - host geometry is fp64 throughout (the reference's torch part is fp32); shading is fp32 as in pytorch3d. */
+#define OVM_SCENE_MAX_BOXES 1024
+#define OVM_SCENE_FRONT 1   /* mode bits */
+#define OVM_SCENE_NOVEL 2
+
+typedef struct OvmSceneInput {
+  int32_t n_boxes, mode;            /* 0..OVM_SCENE_MAX_BOXES; OVM_SCENE_FRONT | OVM_SCENE_NOVEL */
+  int32_t height, width, scale;     /* front image height x width; novel canvas scale x scale */
+  int32_t has_T, has_ground_bounds, has_labels;
+  double K[9], R[9], T[3];          /* row-major K; novel view rotation R (euler2mat([pi/3, 0, 0]) in the reference); T */
+  double ground_bounds[5];          /* max_y3d, x3d_start, x3d_end, z3d_start, z3d_end */
+  double blend_weight, blend_weight_overlay, zplane;
+  const double* corners;            /* [n_boxes][8][3] camera-space corners, pred_bbox3D order */
+  const float* colors;              /* [n_boxes][3] in [0, 1]; component k lands in image channel k */
+  const int32_t* label_size;        /* [2 views][n_boxes][2] glyph mask (width, height); read when has_labels */
+} OvmSceneInput;
+
+typedef struct OvmSceneBox {        /* one box in one view */
+  double verts[8][3];               /* corners in the view's camera frame */
+  int64_t edge[12][4];              /* int() of the projected endpoints after zplane clipping: u0, v0, u1, v1 */
+  int32_t edge_drawn[12];           /* 0 when both endpoints are behind zplane */
+  int32_t rect[4];                  /* label background, half-open x0, y0, x1, y1 on the canvas (empty when x1 <= x0 or y1 <= y0) */
+  int32_t text_org[2];              /* bottom-left corner of the glyph mask: the mask covers rows [y - h, y), cols [x, x + w) */
+  int32_t label_w, label_h;         /* glyph mask size (0 x 0: no label) */
+} OvmSceneBox;
+
+typedef struct OvmSceneView {
+  int32_t height, width, thickness, drawn;    /* drawn = 0: the view is not produced */
+  double K[9];
+  int32_t order[OVM_SCENE_MAX_BOXES];         /* draw order: reversed stable argsort of the mean corner y */
+  OvmSceneBox box[OVM_SCENE_MAX_BOXES];
+} OvmSceneView;
+
+typedef struct OvmSceneLayout {
+  int32_t n_boxes, mode, early_return;        /* early_return: empty grid mask (:522-526) - front = the input, novel = the bare render */
+  int32_t grid_thickness, n_grid, reserved;
+  double zoom_factor, zoom_bias, center[3];
+  double ground[5];                           /* max_y3d, x3d_start, x3d_end, z3d_start, z3d_end of the drawn grid */
+  double blend_weight, blend_weight_overlay, zplane;
+  double edge_color[OVM_SCENE_MAX_BOXES][3];  /* min(255, c * 255 * 1.25): the label background */
+  uint8_t edge_u8[OVM_SCENE_MAX_BOXES][4];    /* [0..2] edge colour rounded half to even, [3] text colour (0 or 255) */
+  float color[OVM_SCENE_MAX_BOXES][3];        /* texel colour c */
+  OvmSceneView view[2];                       /* 0 front, 1 novel */
+} OvmSceneLayout;
+
+typedef struct OvmSceneSegment { int64_t x0, y0, x1, y1; } OvmSceneSegment;
+
+/* Fills *out and grid[0 .. out->n_grid) (sorted ascending). OVM_ERR_CAPACITY, with out->n_grid set to the count needed, when
+ * grid_capacity is too small; OVM_ERR_INVALID for null, non-finite or out-of-range arguments. */
+int ovm_host_scene_layout(const OvmSceneInput* in, OvmSceneLayout* out, OvmSceneSegment* grid, int32_t grid_capacity);
+/* Device workspace bytes ovm_render_scene needs for this layout and glyph buffer. */
+int ovm_render_scene_workspace(const OvmSceneLayout* layout, int64_t glyph_bytes, int64_t* bytes);
+/* layout, grid, glyphs: host. glyphs: the masks of view 0 boxes 0..n-1, then view 1 boxes 0..n-1, each label_h x label_w bytes
+ * row-major, nonzero = ink; glyph_bytes must equal their total. image: device BGR uint8 [height][width][3] with a row pitch in
+ * bytes; front / novel: device outputs of the views the layout draws (null otherwise), row pitches in bytes - front and novel may
+ * be the two halves of one height x (width + scale) x 3 buffer. Too small a workspace -> OVM_ERR_CAPACITY; null or inconsistent
+ * arguments -> OVM_ERR_INVALID, both before any device work. */
+int ovm_render_scene(const OvmSceneLayout* layout, const OvmSceneSegment* grid, const uint8_t* glyphs, int64_t glyph_bytes,
+                     const uint8_t* image, int64_t image_pitch, uint8_t* front, int64_t front_pitch, uint8_t* novel, int64_t novel_pitch,
+                     void* workspace, int64_t workspace_bytes, ovm_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -307,5 +307,7 @@ def get_cfg_defaults(cfg: CfgNode) -> CfgNode:
                                  FUSED_INFER=True,
                                  # GPU_JPEG: baseline JPEGs are entropy-decoded on the host and reconstructed on the device (data/gpu_jpeg.py)
                                  # ResizeShortestEdge on the device (bit-identical to the host's Pillow resize)
-                                 GPU_RESIZE=True, GPU_JPEG=True))
+                                 GPU_RESIZE=True, GPU_JPEG=True,
+                                 # demo.py draws <name>_combine.jpg on the device (ovmono3d_amd/vis); False: detections JSON only
+                                 VIS=True))
     return cfg

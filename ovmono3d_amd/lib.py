@@ -69,6 +69,51 @@ class OvmJpegInfo(C.Structure):
     ]
 
 
+OVM_SCENE_MAX_BOXES = 1024
+OVM_SCENE_FRONT, OVM_SCENE_NOVEL = 1, 2
+
+
+class OvmSceneInput(C.Structure):
+    """Mirror of include/ovm3d.h OvmSceneInput."""
+    _fields_ = [
+        ("n_boxes", C.c_int32), ("mode", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("scale", C.c_int32),
+        ("has_T", C.c_int32), ("has_ground_bounds", C.c_int32), ("has_labels", C.c_int32),
+        ("K", C.c_double * 9), ("R", C.c_double * 9), ("T", C.c_double * 3), ("ground_bounds", C.c_double * 5),
+        ("blend_weight", C.c_double), ("blend_weight_overlay", C.c_double), ("zplane", C.c_double),
+        ("corners", C.c_void_p), ("colors", C.c_void_p), ("label_size", C.c_void_p),
+    ]
+
+
+class OvmSceneBox(C.Structure):
+    _fields_ = [
+        ("verts", (C.c_double * 3) * 8), ("edge", (C.c_int64 * 4) * 12), ("edge_drawn", C.c_int32 * 12),
+        ("rect", C.c_int32 * 4), ("text_org", C.c_int32 * 2), ("label_w", C.c_int32), ("label_h", C.c_int32),
+    ]
+
+
+class OvmSceneView(C.Structure):
+    _fields_ = [
+        ("height", C.c_int32), ("width", C.c_int32), ("thickness", C.c_int32), ("drawn", C.c_int32),
+        ("K", C.c_double * 9), ("order", C.c_int32 * OVM_SCENE_MAX_BOXES), ("box", OvmSceneBox * OVM_SCENE_MAX_BOXES),
+    ]
+
+
+class OvmSceneLayout(C.Structure):
+    """Mirror of include/ovm3d.h OvmSceneLayout."""
+    _fields_ = [
+        ("n_boxes", C.c_int32), ("mode", C.c_int32), ("early_return", C.c_int32),
+        ("grid_thickness", C.c_int32), ("n_grid", C.c_int32), ("reserved", C.c_int32),
+        ("zoom_factor", C.c_double), ("zoom_bias", C.c_double), ("center", C.c_double * 3), ("ground", C.c_double * 5),
+        ("blend_weight", C.c_double), ("blend_weight_overlay", C.c_double), ("zplane", C.c_double),
+        ("edge_color", (C.c_double * 3) * OVM_SCENE_MAX_BOXES), ("edge_u8", (C.c_uint8 * 4) * OVM_SCENE_MAX_BOXES),
+        ("color", (C.c_float * 3) * OVM_SCENE_MAX_BOXES), ("view", OvmSceneView * 2),
+    ]
+
+
+class OvmSceneSegment(C.Structure):
+    _fields_ = [("x0", C.c_int64), ("y0", C.c_int64), ("x1", C.c_int64), ("y1", C.c_int64)]
+
+
 EXPORTS = [
     "ovm_create", "ovm_destroy", "ovm_last_error", "ovm_version", "ovm_abi_sizeof", "ovm_backbone_forward", "ovm_cube_forward",
     "ovm_rpn_box_forward", "ovm_gather_records", "ovm_gather_counts", "ovm_host_interp_pos_embed", "ovm_host_resize_pos_embed_aa", "ovm_host_sincos_pos_embed", "ovm_host_shard_range",
@@ -81,6 +126,7 @@ EXPORTS = [
     "ovm_gdino_create", "ovm_gdino_destroy", "ovm_gdino_last_error", "ovm_gdino_forward", "ovm_gdino_detect", "ovm_gdino_set_force_topk",
     "ovm_gdino_debug_copy", "ovm_debug_set_ptr", "ovm_gdino_num_queries", "ovm_gdino_last_outputs", "ovm_infer",
     "ovm_host_jpeg_info", "ovm_host_jpeg_entropy_decode", "ovm_jpeg_reconstruct",
+    "ovm_host_scene_layout", "ovm_render_scene_workspace", "ovm_render_scene",
 ]
 PROF_NAMES = ("attn", "qkv", "proj", "fc1", "fc2", "ln")
 
@@ -105,13 +151,17 @@ def load() -> C.CDLL:
     lib.ovm_version.restype = C.c_char_p
     lib.ovm_abi_sizeof.argtypes = [C.c_char_p]
     for name, mirror in (("OvmConfig", OvmConfig), ("OvmTensor", OvmTensor), ("OvmImage", OvmImage), ("OvmGdinoConfig", OvmGdinoConfig),
-                         ("OvmJpegInfo", OvmJpegInfo)):
+                         ("OvmJpegInfo", OvmJpegInfo), ("OvmSceneInput", OvmSceneInput), ("OvmSceneLayout", OvmSceneLayout),
+                         ("OvmSceneSegment", OvmSceneSegment)):
         if lib.ovm_abi_sizeof(name.encode()) != C.sizeof(mirror):
             raise RuntimeError(f"{LIB_PATH}: sizeof({name}) = {lib.ovm_abi_sizeof(name.encode())} but the ctypes mirror has "
                                f"{C.sizeof(mirror)} bytes - rebuild the library (ovmono3d_amd/csrc/build.sh) or update lib.py")
     lib.ovm_host_jpeg_info.argtypes = [vp, C.c_size_t, C.POINTER(OvmJpegInfo)]
     lib.ovm_host_jpeg_entropy_decode.argtypes = [vp, C.c_size_t, vp, i64, C.POINTER(OvmJpegInfo)]
     lib.ovm_jpeg_reconstruct.argtypes = [vp, C.POINTER(OvmJpegInfo), vp, vp, vp]
+    lib.ovm_host_scene_layout.argtypes = [C.POINTER(OvmSceneInput), C.POINTER(OvmSceneLayout), vp, i32]
+    lib.ovm_render_scene_workspace.argtypes = [C.POINTER(OvmSceneLayout), i64, C.POINTER(i64)]
+    lib.ovm_render_scene.argtypes = [C.POINTER(OvmSceneLayout), vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
     lib.ovm_backbone_forward.argtypes = [vp, C.POINTER(OvmImage), i32, vp, i32, i32, vp, vp, vp, vp]
     lib.ovm_cube_forward.argtypes = [vp, C.POINTER(OvmImage), i32, vp, vp, vp, vp, i32, i32, vp, vp, vp]
     lib.ovm_rpn_box_forward.argtypes = [vp, C.POINTER(OvmImage), i32, vp, vp, vp, vp, vp, vp, vp]
