@@ -141,7 +141,7 @@ int ovm_destroy(OvmHandle* h);
 const char* ovm_last_error(const OvmHandle* h);
 const char* ovm_version(void);
 /* sizeof() of a struct of this header as the library was compiled ("OvmConfig", "OvmTensor", "OvmImage", "OvmDet3D",
- * "OvmGdinoConfig", "OvmJpegInfo", "OvmSceneInput", "OvmSceneLayout", "OvmSceneSegment"), -1 for an unknown name: lets a binding check its mirror of the layout before the first call. */
+ * "OvmGdinoConfig", "OvmJpegInfo", "OvmSceneInput", "OvmSceneLayout", "OvmSceneSegment", "OvmEvalCell"), -1 for an unknown name: lets a binding check its mirror of the layout before the first call. */
 int ovm_abi_sizeof(const char* struct_name);
 
 /* --- backbone: build_dino_backbone(...).forward(x, prompt_depth) -> {p2,p3,p4}
@@ -376,6 +376,37 @@ int64_t ovm_debug_copy(OvmHandle* h, const char* name, float* dst, int64_t capac
  * `vol` (optional) receives the intersection volumes. */
 int ovm_box3d_iou(const float* boxes_dt, const float* boxes_gt, int32_t N, int32_t M, float eps_coplanar, float eps_nonzero, float* iou,
                   float* vol, ovm_stream_t stream);
+
+/* One (image, category) cell of the COCO-style evaluation, packed CSR-style: its detections are rows dt_off .. dt_off+n_dt-1
+ * of the detection arrays (descending score, cut to the largest maxDets), its ground truth rows gt_off .. gt_off+n_gt-1 of the
+ * ground-truth arrays (file order), its IoU the row-major [n_dt][n_gt] block at iou_off. prox != 0: the proximity rules of
+ * upstream Omni3D's evaluateImg apply to the cell (reference Omni3Deval(eval_prox=...) :1472-1485, threshold :1459-1461). */
+typedef struct OvmEvalCell {
+  int64_t iou_off;
+  int32_t dt_off, n_dt;
+  int32_t gt_off, n_gt;
+  int32_t prox;
+  int32_t reserved;
+} OvmEvalCell;
+
+/* fp64 xywh box IoU of every cell, bit-equal to pycocotools maskUtils.iou without crowd regions (the IoU of COCOeval.computeIoU
+ * that Omni3Deval inherits, reference :1467). dt_cell [n_dt_total]: the cell of each detection row. dt_box / gt_box [.][4] xywh.
+ * iou (optional) receives each cell's block; in_prox (optional, uint8 [n_dt_total]) = any IoU of the row > prox_thresh. All device. */
+int ovm_eval_iou2d(const OvmEvalCell* cells, const int32_t* dt_cell, int32_t n_dt_total, const double* dt_box, const double* gt_box,
+                   double prox_thresh, double* iou, uint8_t* in_prox, ovm_stream_t stream);
+
+/* Greedy COCO matching of every cell x range x IoU threshold in one launch: COCOeval.evaluateImg as Omni3Deval runs it (reference
+ * :1467-1545 on pycocotools), with upstream Omni3D's proximity rules for cells with prox set. Per range the ground truth is ordered
+ * not-ignored first (stable); per threshold the detections pick in score order the free ground truth of highest IoU >= floor (the
+ * later one on equal IoU), among the ignored ones only when no not-ignored one qualifies; crowd ground truth is never taken; a NaN
+ * IoU counts as 0. iou: the [n_dt][n_gt] blocks (fp64). dt_rng / gt_rng: area (2D) or depth (3D); gt_flag / gt_crowd uint8;
+ * in_prox: uint8 per detection (read for prox cells only, may be NULL when none is). ranges [n_rng][2] = lo, hi; floors [n_thr]
+ * = min(threshold, 1 - 1e-10). Outputs, cell c at detection offset o = dt_off * n_rng * n_thr: pick int32 [o + (r*n_thr + t)*n_dt + d]
+ * (index into the ORDERED ground truth, -1 = none), ignored uint8 (same index), n_gt int32 [c*n_rng + r]. All device. max_gt: the
+ * largest n_gt of any cell; a cell holds at most 4096 ground-truth boxes (OVM_ERR_CAPACITY otherwise). */
+int ovm_eval_match(const OvmEvalCell* cells, int32_t n_cells, int32_t max_gt, const double* iou, const double* dt_rng, const double* gt_rng,
+                   const uint8_t* gt_flag, const uint8_t* gt_crowd, const uint8_t* in_prox, const double* ranges, int32_t n_rng,
+                   const double* floors, int32_t n_thr, int32_t* pick, uint8_t* ignored, int32_t* n_gt, ovm_stream_t stream);
 
 /* ---- data feeding ("next" row 2 of SURVEY.md 8f) ---------------------------------------------------------------------------
  * uint8 bilinear resize bit-identical to Pillow's Image.resize(size, BILINEAR), i.e. to detectron2's ResizeShortestEdge on

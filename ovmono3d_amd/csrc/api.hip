@@ -390,6 +390,7 @@ int ovm_abi_sizeof(const char* name) {
   if (n == "OvmSceneInput") return (int)sizeof(OvmSceneInput);
   if (n == "OvmSceneLayout") return (int)sizeof(OvmSceneLayout);
   if (n == "OvmSceneSegment") return (int)sizeof(OvmSceneSegment);
+  if (n == "OvmEvalCell") return (int)sizeof(OvmEvalCell);
   return -1;
 }
 

@@ -13,6 +13,10 @@ The reference FORK lost its ``computeIoU`` override, so its "3D" AP is really co
 pycocotools is not a dependency (and not importable here, so AP values are pinned by cases with a known answer and by
 a by-definition restatement in tests/test_eval.py, not by running the reference's evaluator: "parity unpinned" for
 real-data AP).
+
+``eval_prox`` restores upstream Omni3D's proximity evaluation (reference :263 turns it on for Objectron and SUNRGBD, option
+:1483-1485, threshold :1459-1461), whose ``evaluateImg`` / ``computeIoU`` overrides the fork lost; ``matcher="device"`` runs the
+2D IoU and the greedy matching of every cell in HIP (``csrc/eval_match.hip``) with results equal to the host's.
 """
 from __future__ import annotations
 
@@ -82,8 +86,32 @@ class Omni3DParams:
 
 class _Cell:
     """One (image, category) cell: detections in descending score order (stable), cut to the largest maxDets; ground truth
-    in file order; ``iou`` [D,G] between them."""
-    __slots__ = ("dt", "gt", "iou", "score", "dt_rng", "gt_rng", "gt_flag", "gt_crowd")
+    in file order; ``iou`` [D,G] between them. ``prox``: the proximity rules apply to the cell; ``in_prox`` [D]: some 2D IoU
+    with the cell's ground truth (any of it) exceeds ``proximity_thresh``."""
+    __slots__ = ("dt", "gt", "iou", "score", "dt_rng", "gt_rng", "gt_flag", "gt_crowd", "dt_box", "gt_box", "prox", "in_prox")
+
+
+# numpy mirror of include/ovm3d.h OvmEvalCell
+_CELL_DTYPE = np.dtype([("iou_off", "<i8"), ("dt_off", "<i4"), ("n_dt", "<i4"), ("gt_off", "<i4"), ("n_gt", "<i4"), ("prox", "<i4"),
+                        ("reserved", "<i4")])
+
+
+def _exclusive_cumsum(n: np.ndarray) -> np.ndarray:
+    out = np.zeros(len(n), dtype=np.int64)
+    np.cumsum(n[:-1], out=out[1:])
+    return out
+
+
+def _pack_segments(arrays):
+    """One contiguous byte buffer holding every array, each at an 8-byte aligned offset: (buffer, offsets)."""
+    offs, pos = [], 0
+    for a in arrays:
+        offs.append(pos)
+        pos += (a.nbytes + 7) // 8 * 8
+    buf = np.zeros(max(pos, 8), dtype=np.uint8)
+    for a, o in zip(arrays, offs):
+        buf[o:o + a.nbytes] = np.ascontiguousarray(a).view(np.uint8).ravel()
+    return buf, offs
 
 
 class Omni3Deval:
@@ -97,14 +125,25 @@ class Omni3Deval:
 
     The evaluation is the published COCOeval procedure (greedy matching per IoU threshold in score order, ignore rules,
     101-point interpolated precision); it is organised here as array operations over the thresholds rather than the
-    per-threshold loops of pycocotools, and ``tests/test_eval.py`` holds it against a by-definition restatement."""
+    per-threshold loops of pycocotools, and ``tests/test_eval.py`` holds it against a by-definition restatement.
+
+    ``eval_prox``: upstream Omni3D's proximity evaluation for datasets that are not exhaustively annotated (reference
+    :1483-1485) - True / False for every cell, or a collection of image ids whose cells it applies to. In such a cell, per range,
+    a detection whose 2D IoU with every ground truth of the cell (ignored, out-of-range and crowd boxes included) is at most
+    ``proximity_thresh`` is ignored, and when every ground truth is ignored in the range (or there is none) every detection is.
+    ``matcher``: "host" (numpy) or "device" (HIP kernels ``ovm_eval_iou2d`` / ``ovm_eval_match``, same results; no CPU
+    fallback)."""
 
     def __init__(self, gts: Sequence[Dict], dts: Sequence[Dict], mode: str = "3D", device: Optional[torch.device] = None,
                  fork_compat_2d_iou: bool = False, img_ids: Optional[Sequence] = None, cat_ids: Optional[Sequence] = None,
-                 nhd_iou_threshold: float = 0.5):
+                 nhd_iou_threshold: float = 0.5, eval_prox=False, matcher: str = "host"):
+        if matcher not in ("host", "device"):
+            raise ValueError(f"matcher must be 'host' or 'device', not {matcher!r}")
         self.mode = mode
         self.params = Omni3DParams(mode)
         self.device = device
+        self.matcher = matcher
+        self.eval_prox = bool(eval_prox) if isinstance(eval_prox, (bool, np.bool_)) else frozenset(eval_prox)
         self.fork_compat_2d_iou = fork_compat_2d_iou
         self.nhd_iou_threshold = nhd_iou_threshold
         self._gts_all, self._dts_all = [dict(g) for g in gts], [dict(d) for d in dts]
@@ -127,10 +166,11 @@ class Omni3Deval:
         self.nhd_pairs: List[Dict] = []
 
     # ---- cells and their IoU ------------------------------------------------------------------------------------------
-    def _iou_2d(self, dt, gt):
-        return iou2d_xywh(np.array([d["bbox"] for d in dt]), np.array([g["bbox"] for g in gt]))
+    def _prox_applies(self, img) -> bool:
+        return self.eval_prox if isinstance(self.eval_prox, bool) else img in self.eval_prox
 
-    def _build_cells(self):
+    def _build_cells(self, with_iou: bool = True):
+        """``with_iou=False``: leave the 2D IoU (and the proximity flags) to the device matcher."""
         p = self.params
         flag = "ignore2D" if self.mode == "2D" else "ignore3D"                  # _prepare :1515-1545
         rng_key = "area" if self.mode == "2D" else "depth"
@@ -155,13 +195,27 @@ class Omni3Deval:
             c.gt_rng = np.array([g[rng_key] for g in c.gt], dtype=np.float64)
             c.gt_flag = np.array([bool(g.get(flag, 0)) for g in c.gt], dtype=bool)
             c.gt_crowd = np.array([bool(g["iscrowd"]) for g in c.gt], dtype=bool)
-            c.iou = None
+            c.dt_box = np.array([d["bbox"] for d in c.dt], dtype=np.float64).reshape(-1, 4)
+            c.gt_box = np.array([g["bbox"] for g in c.gt], dtype=np.float64).reshape(-1, 4)
+            c.prox = self._prox_applies(key[0])
+            c.iou = c.in_prox = None
             self.cells[key] = c
         true_3d = self.mode == "3D" and not self.fork_compat_2d_iou
-        if not true_3d:
-            for c in self.cells.values():
-                c.iou = self._iou_2d(c.dt, c.gt) if c.dt and c.gt else np.zeros((len(c.dt), len(c.gt)))
+        if not with_iou:
+            if true_3d:
+                self._build_iou_3d()
             return
+        for c in self.cells.values():
+            if c.prox or not true_3d:
+                iou2 = iou2d_xywh(c.dt_box, c.gt_box) if c.dt and c.gt else np.zeros((len(c.dt), len(c.gt)))
+                if not true_3d:
+                    c.iou = iou2
+                if c.prox:
+                    c.in_prox = (iou2 > self.params.proximity_thresh).any(axis=1)
+        if true_3d:
+            self._build_iou_3d()
+
+    def _build_iou_3d(self):
         # true 3D IoU: one kernel call per IMAGE (all its detections x all its ground truth), sliced per category
         dev = self.device if self.device is not None else torch.device("cuda", torch.cuda.current_device())
         per_image = defaultdict(list)
@@ -217,15 +271,105 @@ class Omni3Deval:
                                        c.gt_crowd[order], self.params.iouThrs)
         matched = pick >= 0
         outside = (c.dt_rng < lo) | (c.dt_rng > hi)
-        return {"score": c.score, "matched": matched, "ignored": on_ignored | (~matched & outside[None, :]),
-                "n_gt": int(np.count_nonzero(~gt_ign)), "gt_order": order, "pick": pick}
+        ignored = on_ignored | (~matched & outside[None, :])
+        if c.prox:                                                             # proximity evaluation: far detections, and every
+            far = np.ones(len(c.dt), dtype=bool) if np.all(gt_ign) else ~c.in_prox     # detection of a cell without countable GT
+            ignored = ignored | far[None, :]
+        return {"score": c.score, "matched": matched, "ignored": ignored, "n_gt": int(np.count_nonzero(~gt_ign)), "gt_order": order,
+                "pick": pick}
 
     def evaluate(self):
-        p = self.params
-        self._build_cells()
-        self.per_cell = {(key, a): self._evaluate_cell(c, rng) for key, c in self.cells.items() for a, rng in enumerate(p.areaRng)}
+        self._build_cells(with_iou=self.matcher == "host")
+        self._match_cells()
         if self.mode == "3D":
             self._collect_nhd()
+
+    def _match_cells(self):
+        """Fills ``per_cell``: one entry per (cell, range) with the per-threshold picks and ignore flags."""
+        if self.matcher == "device":
+            self._match_device()
+        else:
+            self.per_cell = {(key, a): self._evaluate_cell(c, rng) for key, c in self.cells.items() for a, rng in enumerate(self.params.areaRng)}
+
+    def _match_device(self):
+        """Every cell packed CSR-style (vectorised, no loop per detection), one upload, the 2D IoU launch when the IoU or the
+        proximity flags are needed, one matcher launch, one download; ``per_cell`` in the host's format."""
+        if not torch.cuda.is_available():
+            raise RuntimeError("matcher='device' needs a HIP device (no CPU fallback)")
+        L = _lib.load()
+        p = self.params
+        dev = self.device if self.device is not None else torch.device("cuda", torch.cuda.current_device())
+        keys = list(self.cells)
+        cs = [self.cells[k] for k in keys]
+        n, A, T = len(cs), len(p.areaRng), len(p.iouThrs)
+        true_3d = self.mode == "3D" and not self.fork_compat_2d_iou
+        nd = np.array([len(c.score) for c in cs], dtype=np.int64)
+        ng = np.array([len(c.gt_rng) for c in cs], dtype=np.int64)
+        cells = np.zeros(n, dtype=_CELL_DTYPE)
+        assert cells.itemsize == C.sizeof(_lib.OvmEvalCell)
+        dt_off, gt_off, iou_off = _exclusive_cumsum(nd), _exclusive_cumsum(ng), _exclusive_cumsum(nd * ng)
+        n_dt, n_gtb, n_iou = int(nd.sum()), int(ng.sum()), int((nd * ng).sum())
+        if max(n_dt, n_gtb) >= 2 ** 31 or n_dt * A * T >= 2 ** 62:
+            raise RuntimeError("too many boxes for the device matcher")
+        cells["iou_off"], cells["dt_off"], cells["n_dt"], cells["gt_off"], cells["n_gt"] = iou_off, dt_off, nd, gt_off, ng
+        cells["prox"] = [c.prox for c in cs]
+        any_prox = bool(cells["prox"].any())
+
+        def cat(parts, dtype, shape=(-1,)):
+            return np.concatenate([np.asarray(x, dtype=dtype).reshape(shape) for x in parts]) if parts else np.zeros(0, dtype)
+        ins = [cells, np.repeat(np.arange(n, dtype=np.int32), nd), cat([c.dt_box for c in cs], np.float64, (-1, 4)),
+               cat([c.gt_box for c in cs], np.float64, (-1, 4)), cat([c.dt_rng for c in cs], np.float64), cat([c.gt_rng for c in cs], np.float64),
+               cat([c.gt_flag for c in cs], np.uint8), cat([c.gt_crowd for c in cs], np.uint8),
+               np.asarray(p.areaRng, dtype=np.float64).reshape(-1), np.minimum(p.iouThrs, 1 - 1e-10).astype(np.float64)]
+        if true_3d:
+            ins.append(cat([c.iou for c in cs], np.float64))
+        buf, io = _pack_segments(ins)
+        # outputs: pick int32, ignored uint8, n_gt int32, in_prox uint8, and the 2D IoU when it is computed here
+        outs = [np.zeros(n_dt * A * T, np.int32), np.zeros(n_dt * A * T, np.uint8), np.zeros(n * A, np.int32), np.zeros(n_dt, np.uint8)]
+        if not true_3d:
+            outs.append(np.zeros(n_iou, np.float64))
+        obytes, oo = _pack_segments(outs)
+        d_in = torch.from_numpy(buf).to(dev)
+        d_out = torch.empty(len(obytes), dtype=torch.uint8, device=dev)
+        bi, bo = d_in.data_ptr(), d_out.data_ptr()
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        iou_ptr = (bi + io[10]) if true_3d else (bo + oo[4])
+        prox_ptr = (bo + oo[3]) if any_prox else None
+        if not true_3d or any_prox:
+            _lib.check(L.ovm_eval_iou2d(bi + io[0], bi + io[1], n_dt, bi + io[2], bi + io[3], float(p.proximity_thresh),
+                                        None if true_3d else iou_ptr, prox_ptr, stream), what="ovm_eval_iou2d")
+        _lib.check(L.ovm_eval_match(bi + io[0], n, int(ng.max()) if n else 0, iou_ptr, bi + io[4], bi + io[5], bi + io[6], bi + io[7], prox_ptr,
+                                    bi + io[8], A, bi + io[9], T, bo + oo[0], bo + oo[1], bo + oo[2], stream), what="ovm_eval_match")
+        host = d_out.cpu().numpy()
+        pick = host[oo[0]:oo[0] + outs[0].nbytes].view(np.int32).astype(np.int64)
+        ignored = host[oo[1]:oo[1] + outs[1].nbytes].view(np.bool_)
+        matched = pick >= 0
+        n_gt = host[oo[2]:oo[2] + outs[2].nbytes].view(np.int32).reshape(n, A)
+        if not true_3d:
+            iou = host[oo[4]:oo[4] + outs[4].nbytes].view(np.float64)
+            for i, c in enumerate(cs):
+                c.iou = iou[iou_off[i]:iou_off[i] + nd[i] * ng[i]].reshape(nd[i], ng[i])
+        if any_prox:
+            in_prox = host[oo[3]:oo[3] + outs[3].nbytes].view(np.bool_)
+            for i, c in enumerate(cs):
+                if c.prox:
+                    c.in_prox = in_prox[dt_off[i]:dt_off[i] + nd[i]]
+        # the ordered ground truth of every (cell, range): not ignored first, file order within
+        gt_cell = np.repeat(np.arange(n), ng)
+        gt_local = np.arange(n_gtb) - np.repeat(gt_off, ng)
+        flag, rng = ins[6].astype(bool), ins[5]
+        orders = []
+        for lo, hi in p.areaRng:
+            ign = flag | (rng < lo) | (rng > hi)
+            orders.append(gt_local[np.lexsort((ign, gt_cell))])
+        self.per_cell = {}
+        for i, (key, c) in enumerate(zip(keys, cs)):
+            b, e = dt_off[i] * A * T, (dt_off[i] + nd[i]) * A * T
+            pk, mt, ig = pick[b:e].reshape(A, T, nd[i]), matched[b:e].reshape(A, T, nd[i]), ignored[b:e].reshape(A, T, nd[i])
+            g0, g1 = gt_off[i], gt_off[i] + ng[i]
+            for a in range(A):
+                self.per_cell[key, a] = {"score": c.score, "matched": mt[a], "ignored": ig[a], "n_gt": int(n_gt[i, a]), "gt_order": orders[a][g0:g1],
+                                         "pick": pk[a]}
 
     # ---- precision / recall tables ----------------------------------------------------------------------------------------
     def accumulate(self):
@@ -361,8 +505,9 @@ class Omni3Deval:
 
 
 def evaluate_omni3d(gts, dts: Sequence[Dict], device=None, only_2d: bool = False, fork_compat_2d_iou: bool = False,
-                    category_map=None, passthrough_dataset_ids: bool = False) -> Dict:
+                    category_map=None, passthrough_dataset_ids: bool = False, eval_prox=False, matcher: str = "host") -> Dict:
     """AP2D and AP3D dictionaries for one dataset (reference _evaluate_predictions_on_omni :1255-1391 without the file plumbing).
+    ``eval_prox`` (a bool, or the image ids whose cells it applies to) and ``matcher``: as ``Omni3Deval``.
 
     ``gts``: an ``Omni3DGroundTruth`` (images and categories evaluated = the dataset's, as the reference; detections on unknown
     images or categories are dropped :1319-1334) or a plain list of ground-truth dicts. ``category_map`` (``CategoryMap``): the
@@ -379,7 +524,7 @@ def evaluate_omni3d(gts, dts: Sequence[Dict], device=None, only_2d: bool = False
         known_i, known_c = set(img_ids), set(cat_ids)
         dts = [d for d in dts if d["image_id"] in known_i and d["category_id"] in known_c]
     res = {}
-    e2 = Omni3Deval(gts, dts, "2D", img_ids=img_ids, cat_ids=cat_ids)
+    e2 = Omni3Deval(gts, dts, "2D", device=device, img_ids=img_ids, cat_ids=cat_ids, eval_prox=eval_prox, matcher=matcher)
     e2.evaluate(); e2.accumulate()
     res["bbox_2D"] = e2.summarize()
     if names is not None:
@@ -387,7 +532,8 @@ def evaluate_omni3d(gts, dts: Sequence[Dict], device=None, only_2d: bool = False
         res["bbox_2D_per_category_AR"] = e2.per_category_ar(names)
     if not only_2d:
         d3 = [d for d in dts if "bbox3D" in d]
-        e3 = Omni3Deval(gts, d3, "3D", device=device, fork_compat_2d_iou=fork_compat_2d_iou, img_ids=img_ids, cat_ids=cat_ids)
+        e3 = Omni3Deval(gts, d3, "3D", device=device, fork_compat_2d_iou=fork_compat_2d_iou, img_ids=img_ids, cat_ids=cat_ids,
+                        eval_prox=eval_prox, matcher=matcher)
         e3.evaluate(); e3.accumulate()
         res["bbox_3D"] = e3.summarize()
         if names is not None:
@@ -409,6 +555,10 @@ OMNI3D_IN = frozenset(["chair", "table", "cabinet", "lamp", "books", "sofa", "pi
                        "television", "shoes", "cup", "bottle", "bookcase", "laptop", "desk", "floor mat", "mirror", "counter", "bicycle", "toilet", "bed",
                        "refrigerator", "box", "oven", "clothes", "towel", "night stand", "stove", "machine", "stationery", "bathtub", "curtain", "bin"])
 OMNI3D_ALL = OMNI3D_OUT | OMNI3D_IN | frozenset(["camera", "cereal box"])      # the benchmark's 50 categories (builtin.py:12-14)
+# the novel split's 22 categories and its easy ones (reference summarize_all :602-603)
+OMNI3D_NOVEL = frozenset(["monitor", "bag", "dresser", "board", "printer", "keyboard", "painting", "drawers", "microwave", "computer", "kitchen pan",
+                          "potted plant", "tissues", "rack", "tray", "toys", "phone", "podium", "cart", "soundsystem", "fireplace", "tram"])
+OMNI3D_NOVEL_EASY = frozenset(["board", "printer", "painting", "microwave", "tray", "podium", "cart", "tram"])
 
 
 def collective_summary(results: Dict) -> Dict:
@@ -416,7 +566,9 @@ def collective_summary(results: Dict) -> Dict:
     over the concatenation of the datasets (re-accumulating the cached per-image results of every dataset, as the reference does, is the
     same computation: a cell's matching depends on its own image and category only). ``<Concat>`` averages the per-category AP / AR
     over the categories that have ground truth; ``Omni3D_Out`` / ``Omni3D_In`` / ``Omni3D`` over the benchmark's outdoor / indoor / all 50
-    categories, NaN unless every one of them was evaluated."""
+    categories, NaN unless every one of them was evaluated. When the categories with any result (AP2D, AP3D, AR2D or AR3D not NaN,
+    :598) are exactly the novel split's 22, ``Novel_Easy`` / ``Novel_Hard`` hold the plain means over its 8 easy and 14 hard ones
+    (``calculate_metrics`` :171-191, a NaN propagates; :601-613)."""
     def mean_over(table, cats):
         vals = [table[c] for c in cats]
         return float(np.mean(vals)) if vals and not any(np.isnan(v) for v in vals) else float("nan")
@@ -436,4 +588,10 @@ def collective_summary(results: Dict) -> Dict:
         out[label] = {"AP2D": mean_over(ap2, sorted(group)) if full else float("nan"), "AR2D": mean_over(ar2, sorted(group)) if full else float("nan"),
                       "AP3D": mean_over(ap3, sorted(group)) if full and ap3 else float("nan"),
                       "AR3D": mean_over(ar3, sorted(group)) if full and ar3 else float("nan")}
+    nan = float("nan")
+    results_cat = {c: {"AP2D": ap2[c], "AP3D": (ap3 or {}).get(c, nan), "AR2D": ar2.get(c, nan), "AR3D": (ar3 or {}).get(c, nan)} for c in ap2}
+    results_cat = {c: m for c, m in results_cat.items() if not all(np.isnan(v) for v in m.values())}
+    if set(results_cat) == OMNI3D_NOVEL:
+        for label, group in (("Novel_Easy", OMNI3D_NOVEL_EASY), ("Novel_Hard", OMNI3D_NOVEL - OMNI3D_NOVEL_EASY)):
+            out[label] = {k: sum(results_cat[c][k] for c in sorted(group)) / len(group) for k in ("AP2D", "AP3D", "AR2D", "AR3D")}
     return out

@@ -13,6 +13,10 @@ next to the ``category_meta.json`` that was applied. Training (``do_train``) is 
 
 Deviations from the fork, both restoring upstream intent: oracle-2D boxes are
 forwarded to the model when TEST.ORACLE2D is set and the oracle file exists, and TEST.CAT_MODE selects the mode.
+
+``--eval-prox`` turns on upstream Omni3D's proximity evaluation for the datasets whose name contains Objectron or SUNRGBD
+(reference omni3d_evaluation.py:263), in their own evaluation and for their images in the collective pass; ``--eval-matcher
+device`` runs the evaluator's matching on the GPU (same results as ``host``).
 """
 import argparse
 import json
@@ -51,7 +55,13 @@ def oracle2d_file(cfg, mode, name, datasets_root):
     return None
 
 
-def do_test(cfg, model, mode="base", datasets_root="datasets/Omni3D", image_root="datasets", depth_dir=None, category_meta=None):
+def uses_proximity(name):
+    """The reference builds each dataset's evaluator with eval_prox=('Objectron' in name or 'SUNRGBD' in name) (omni3d_evaluation.py:263)."""
+    return "Objectron" in name or "SUNRGBD" in name
+
+
+def do_test(cfg, model, mode="base", datasets_root="datasets/Omni3D", image_root="datasets", depth_dir=None, category_meta=None,
+            eval_prox=False, matcher="host"):
     if mode == "novel":
         names = cfg.DATASETS.TEST_NOVEL
     elif mode == "base":
@@ -59,7 +69,7 @@ def do_test(cfg, model, mode="base", datasets_root="datasets/Omni3D", image_root
     else:
         raise ValueError("wrong mode")
     out_dir = os.path.join(cfg.OUTPUT_DIR, "inference", "iter_final")
-    all_files, all_dets = [], []
+    all_files, all_dets, prox_images = [], [], set()
     for name in names:
         dicts = load_omni3d_json(os.path.join(datasets_root, name + ".json"), image_root)
         if cfg.TEST.ORACLE2D:
@@ -82,9 +92,12 @@ def do_test(cfg, model, mode="base", datasets_root="datasets/Omni3D", image_root
             gt = Omni3DGroundTruth(os.path.join(datasets_root, name + ".json"), eval_filter_settings(cfg, mode))
             all_files.append(os.path.join(datasets_root, name + ".json"))
             all_dets += [inst for r in results for inst in r["instances"]]
+            prox = eval_prox and uses_proximity(name)
+            if prox:
+                prox_images |= set(gt.image_ids)
             if len(gt):
                 cmap = category_map_for(cfg, mode, gt, category_meta)
-                ap = evaluate_omni3d(gt, [inst for r in results for inst in r["instances"]], category_map=cmap)
+                ap = evaluate_omni3d(gt, [inst for r in results for inst in r["instances"]], category_map=cmap, eval_prox=prox, matcher=matcher)
                 with open(os.path.join(out_dir, name, "omni_ap.json"), "w") as f:
                     json.dump(ap, f)
                 with open(os.path.join(out_dir, name, "category_meta.json"), "w") as f:
@@ -98,11 +111,16 @@ def do_test(cfg, model, mode="base", datasets_root="datasets/Omni3D", image_root
         # datasets' images, per category, and averaged over the Omni3D outdoor / indoor / all-50 category groups
         gt = Omni3DGroundTruth(all_files, eval_filter_settings(cfg, mode))
         if len(gt):
-            ap = evaluate_omni3d(gt, all_dets, category_map=category_map_for(cfg, mode, gt, category_meta))
+            # a cell's matching depends on its own image only: the proximity rule goes with the images of its datasets
+            ap = evaluate_omni3d(gt, all_dets, category_map=category_map_for(cfg, mode, gt, category_meta), eval_prox=prox_images,
+                                 matcher=matcher)
             ap["collective"] = collective_summary(ap)
             with open(os.path.join(out_dir, "omni_ap_all.json"), "w") as f:
                 json.dump(ap, f)
             logger.info("all %d datasets: %s", len(all_files), json.dumps(ap["collective"]))
+            for label in ("Novel_Easy", "Novel_Hard"):
+                if label in ap["collective"]:
+                    logger.info("%s categories: %s", label, json.dumps({k: f"{v:.2f}" for k, v in ap["collective"][label].items()}))
 
 
 def category_map_for(cfg, mode, gt, category_meta=None):
@@ -138,10 +156,11 @@ def main(args):
         set_native_comm(NativeComm.from_torch_distributed(torch.device("cuda", local_rank)))
     DetectionCheckpointer(model, save_dir=cfg.OUTPUT_DIR).resume_or_load(cfg.MODEL.WEIGHTS, resume=args.resume)
     if cfg.TEST.CAT_MODE == "all":
-        do_test(cfg, model, "novel", args.datasets_root, args.image_root, args.depth_dir, args.category_meta)
-        do_test(cfg, model, "base", args.datasets_root, args.image_root, args.depth_dir, args.category_meta)
+        do_test(cfg, model, "novel", args.datasets_root, args.image_root, args.depth_dir, args.category_meta, args.eval_prox, args.eval_matcher)
+        do_test(cfg, model, "base", args.datasets_root, args.image_root, args.depth_dir, args.category_meta, args.eval_prox, args.eval_matcher)
     else:
-        do_test(cfg, model, cfg.TEST.CAT_MODE, args.datasets_root, args.image_root, args.depth_dir, args.category_meta)
+        do_test(cfg, model, cfg.TEST.CAT_MODE, args.datasets_root, args.image_root, args.depth_dir, args.category_meta, args.eval_prox,
+                args.eval_matcher)
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()
@@ -161,6 +180,10 @@ def default_argument_parser():
     p.add_argument("--depth-dir", default=None, help="(native build) folder of depth-prompt .npz files")
     p.add_argument("--category-meta", default=None, help="(native build) category_meta.json-style file: thing_classes + "
                    "thing_dataset_id_to_contiguous_id of the model's class index; default: derived from the annotation file")
+    p.add_argument("--eval-prox", action="store_true", help="(native build) proximity evaluation for the Objectron and SUNRGBD datasets "
+                   "(upstream Omni3D's eval_prox)")
+    p.add_argument("--eval-matcher", choices=("host", "device"), default="host", help="(native build) where the evaluator matches "
+                   "detections to ground truth: host (numpy) or device (HIP kernel); the results are the same")
     p.add_argument("opts", default=None, nargs=argparse.REMAINDER)
     return p
 
