@@ -373,7 +373,8 @@ int64_t ovm_debug_copy(OvmHandle* h, const char* name, float* dst, int64_t capac
  * Exact IoU of oriented 3D boxes, iou[i*M + j] for detection i and ground truth j; boxes are 8 corners x 3 floats in
  * pytorch3d's corner order. Replaces `box3d_overlap` -> pytorch3d `_C.iou_box3d` (cubercnn/evaluation/omni3d_evaluation.py:109-169)
  * including the screening of the detections: rows of non-coplanar (:68-87) or zero-area (:90-107) detections are 0.
- * `vol` (optional) receives the intersection volumes. */
+ * A box without volume (a face without a normal, or volume <= 0: all -1 or all 0 corners, flat boxes) intersects nothing:
+ * IoU and volume 0. `vol` (optional) receives the intersection volumes. */
 int ovm_box3d_iou(const float* boxes_dt, const float* boxes_gt, int32_t N, int32_t M, float eps_coplanar, float eps_nonzero, float* iou,
                   float* vol, ovm_stream_t stream);
 

@@ -10,13 +10,24 @@ from scipy.spatial import ConvexHull, HalfspaceIntersection, QhullError
 _FACES = [[0, 1, 2, 3], [3, 2, 6, 7], [0, 1, 5, 4], [0, 3, 7, 4], [1, 2, 6, 5], [4, 5, 6, 7]]      # pytorch3d `_box_planes`
 
 
-def _halfspaces(c: np.ndarray) -> np.ndarray:
+def _local(*boxes) -> list:
+    """The boxes in a frame centred on the first one's corner centroid: the geometry then does not cancel against the
+    distance from the camera, and the result is the same wherever the pair sits."""
+    o = np.asarray(boxes[0], np.float64).mean(0)
+    return [np.asarray(b, np.float64) - o for b in boxes]
+
+
+def _halfspaces(c: np.ndarray):
+    """The six outward half-spaces of a box, or None when a face has no normal (a flat box, a segment, a point)."""
     ctr = c.mean(0)
     hs = []
     for f in _FACES:
         v = c[f]
         n = np.cross(v[1] - v[0], v[3] - v[0])
-        n = n / np.linalg.norm(n)
+        ln = np.linalg.norm(n)
+        if not ln > 0:
+            return None
+        n = n / ln
         fc = v.mean(0)
         if np.dot(n, fc - ctr) < 0:
             n = -n
@@ -25,12 +36,24 @@ def _halfspaces(c: np.ndarray) -> np.ndarray:
 
 
 def box_volume(c: np.ndarray) -> float:
-    return float(ConvexHull(np.asarray(c, np.float64)).volume)
+    """Volume of the corners' convex hull; 0 for a degenerate box (a face without a normal: flat, a segment, a point; or
+    non-finite corners)."""
+    c = _local(c)[0]
+    if _halfspaces(c) is None:
+        return 0.0
+    try:
+        return float(ConvexHull(c).volume)
+    except (QhullError, ValueError):
+        return 0.0
 
 
 def intersection_volume(a: np.ndarray, b: np.ndarray) -> float:
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    hs = np.concatenate([_halfspaces(a), _halfspaces(b)], 0)
+    """0 when either box is degenerate: nothing has volume inside a box without volume."""
+    a, b = _local(a, b)
+    ha, hb = _halfspaces(a), _halfspaces(b)
+    if ha is None or hb is None or not (box_volume(a) > 0 and box_volume(b) > 0):
+        return 0.0
+    hs = np.concatenate([ha, hb], 0)
     # an interior point: Chebyshev centre by linear programming
     from scipy.optimize import linprog
     A = np.hstack([hs[:, :3], np.linalg.norm(hs[:, :3], axis=1, keepdims=True)])
@@ -45,12 +68,14 @@ def intersection_volume(a: np.ndarray, b: np.ndarray) -> float:
 
 
 def iou_matrix(dt: np.ndarray, gt: np.ndarray) -> np.ndarray:
+    """IoU of every pair; 0 where the union is empty (two degenerate boxes)."""
     out = np.zeros((len(dt), len(gt)))
     vd, vg = [box_volume(d) for d in dt], [box_volume(g) for g in gt]
     for i, d in enumerate(dt):
         for j, g in enumerate(gt):
             v = intersection_volume(d, g)
-            out[i, j] = v / (vd[i] + vg[j] - v)
+            u = vd[i] + vg[j] - v
+            out[i, j] = v / u if u > 0 else 0.0
     return out
 
 

@@ -8,7 +8,15 @@
 //     V = 1/3 * sum_{faces f of A} (p_f . n_f) * area(f clipped to B)  +  1/3 * sum_{faces g of B} (p_g . n_g) * area(g clipped to A)
 // with outward unit normals n and any point p on the face. Each quad face is clipped against the other box's six
 // half-spaces (Sutherland-Hodgman, at most 10 vertices). A's faces are clipped against B's CLOSED half-spaces and B's faces
-// against A's OPEN ones, so a coincident face pair is counted once (IoU of a box with itself is exactly 1).
+// against A's OPEN ones, so a coincident face pair is counted once (IoU of a box with itself is exactly 1). A face of A
+// lying in a plane of B whose outward normal points the other way (two boxes touching face to face) bounds no volume
+// of the intersection, so that plane is open for A's faces too.
+//
+// The pair is handled in a frame centred on the detection's corner centroid. In camera coordinates every face term
+// p_f . n_f is about distance x area and the terms cancel down to the volume, which loses most of the fp32 precision of
+// a small box far from the camera; in the local frame they are of the box's own size, and so is the snapping tolerance.
+// A box without volume (a flat box, a segment, a point: ground truth the evaluator keeps as ignored) intersects
+// nothing: such a pair gets volume 0 and IoU 0. The intersection is clamped to the smaller volume, so IoU <= 1.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "common.hpp"
@@ -35,6 +43,7 @@ struct Box {
   float d[6];     // plane offsets: inside <=> n . x <= d
   float vol;
   float scale;    // largest |coordinate|: sets the snapping tolerance of the plane tests
+  bool solid;     // every face has a normal and the volume is positive
 };
 
 __device__ void load_box(const float* p, Box& b) {
@@ -45,14 +54,28 @@ __device__ void load_box(const float* p, Box& b) {
     b.scale = fmaxf(b.scale, fmaxf(fabsf(b.c[i].x), fmaxf(fabsf(b.c[i].y), fabsf(b.c[i].z))));
   }
   ctr = ctr * 0.125f;
+  b.solid = true;
   for (int f = 0; f < 6; ++f) {
     const V3 v0 = b.c[kFace[f][0]], v1 = b.c[kFace[f][1]], v2 = b.c[kFace[f][2]], v3 = b.c[kFace[f][3]];
     V3 n = cross(v1 - v0, v3 - v0);
     const float l = norm(n);
+    if (!(l > 0.f)) b.solid = false;
     n = l > 0.f ? n * (1.f / l) : V3{0.f, 0.f, 0.f};
     const V3 fc = (v0 + v1 + v2 + v3) * 0.25f;
     if (dot(n, fc - ctr) < 0.f) n = n * -1.f;
     b.n[f] = n; b.d[f] = dot(n, fc);
+  }
+  // Corners rounded to fp32 far from the camera are off their face planes by up to half an ulp of the distance; clipped
+  // as given, faces of A and of B then do not close up into one surface, which costs an IoU error of several times that
+  // rounding on a small box. Every corner is therefore moved to where its three face planes meet: the box becomes the
+  // intersection of its six half-spaces, as the plane tests already take it.
+  if (b.solid) {
+    for (int k = 0; k < 8; ++k) {
+      const int fx = (k == 0 || k == 3 || k == 4 || k == 7) ? 3 : 4, fy = (k == 0 || k == 1 || k == 4 || k == 5) ? 2 : 1, fz = k < 4 ? 0 : 5;
+      const V3 c23 = cross(b.n[fy], b.n[fz]), c31 = cross(b.n[fz], b.n[fx]), c12 = cross(b.n[fx], b.n[fy]);
+      const float det = dot(b.n[fx], c23);
+      if (fabsf(det) > 1e-3f) b.c[k] = (c23 * b.d[fx] + c31 * b.d[fy] + c12 * b.d[fz]) * (1.f / det);
+    }
   }
   // volume of the hexahedron: the same face sum with unclipped faces
   float v = 0.f;
@@ -62,18 +85,20 @@ __device__ void load_box(const float* p, Box& b) {
     v += b.d[f] * area;
   }
   b.vol = v * (1.f / 3.f);
+  if (!(b.vol > 0.f)) b.solid = false;
 }
 
-// area of face `f` of `a` inside box `o`; closed = keep points on o's planes
+// area of face `f` of `a` inside box `o`; closed = keep points on those planes of o that face the same way as the face
 __device__ float clipped_face_area(const Box& a, int f, const Box& o, bool closed) {
   V3 poly[12], tmp[12];
   int n = 4;
   for (int i = 0; i < 4; ++i) poly[i] = a.c[kFace[f][i]];
   for (int pl = 0; pl < 6 && n > 0; ++pl) {
     const V3 pn = o.n[pl]; const float pd = o.d[pl];
+    const bool keep_on = closed && dot(pn, a.n[f]) > 0.f;
     // Signed distances within rounding noise of the plane are snapped to "on the plane" (a few fp32 ulps of the coordinate
-    // magnitude, ~1e-5 m at 10 m): a face of `a` lying in a plane of `o` is then inside for the closed test and outside for
-    // the open one, whichever way the noise fell.
+    // magnitude in the local frame, i.e. of the boxes' size and separation): a face of `a` lying in a plane of `o` is then
+    // inside for the closed test and outside for the open one, whichever way the noise fell.
     const float eps = 4e-6f * (fmaxf(a.scale, o.scale) + fabsf(pd));
     int m = 0;
     for (int i = 0; i < n; ++i) {
@@ -81,8 +106,8 @@ __device__ float clipped_face_area(const Box& a, int f, const Box& o, bool close
       float sc = dot(pn, cur) - pd, sn = dot(pn, nxt) - pd;
       if (fabsf(sc) <= eps) sc = 0.f;
       if (fabsf(sn) <= eps) sn = 0.f;
-      const bool in_c = closed ? (sc <= 0.f) : (sc < 0.f);
-      const bool in_n = closed ? (sn <= 0.f) : (sn < 0.f);
+      const bool in_c = keep_on ? (sc <= 0.f) : (sc < 0.f);
+      const bool in_n = keep_on ? (sn <= 0.f) : (sn < 0.f);
       if (in_c) tmp[m++] = cur;
       if (in_c != in_n) {
         const float t = sc / (sc - sn);
@@ -98,11 +123,14 @@ __device__ float clipped_face_area(const Box& a, int f, const Box& o, bool close
   return 0.5f * fabsf(dot(acc, a.n[f]));
 }
 
-__device__ bool box_valid(const Box& b, float eps_coplanar, float eps_nonzero) {
+__device__ __forceinline__ V3 corner(const float* p, int k) { return {p[3 * k], p[3 * k + 1], p[3 * k + 2]}; }
+
+// on the detection's corners as given (camera coordinates), as the reference screens them
+__device__ bool box_valid(const float* p, float eps_coplanar, float eps_nonzero) {
   // reference _check_coplanar: |(v3 - v0) . normalize(cross(normalize(v1 - v0), normalize(v2 - v0)))| summed over the 6 planes < eps
   float s = 0.f;
   for (int f = 0; f < 6; ++f) {
-    const V3 v0 = b.c[kFace[f][0]], v1 = b.c[kFace[f][1]], v2 = b.c[kFace[f][2]], v3 = b.c[kFace[f][3]];
+    const V3 v0 = corner(p, kFace[f][0]), v1 = corner(p, kFace[f][1]), v2 = corner(p, kFace[f][2]), v3 = corner(p, kFace[f][3]);
     V3 e0 = v1 - v0, e1 = v2 - v0;
     const float l0 = fmaxf(norm(e0), 1e-12f), l1 = fmaxf(norm(e1), 1e-12f);
     e0 = e0 * (1.f / l0); e1 = e1 * (1.f / l1);
@@ -114,7 +142,7 @@ __device__ bool box_valid(const Box& b, float eps_coplanar, float eps_nonzero) {
   if (!(fabsf(s) < eps_coplanar)) return false;
   // reference _check_nonzero: every triangle area > eps
   for (int t = 0; t < 12; ++t) {
-    const V3 v0 = b.c[kTri[t][0]], v1 = b.c[kTri[t][1]], v2 = b.c[kTri[t][2]];
+    const V3 v0 = corner(p, kTri[t][0]), v1 = corner(p, kTri[t][1]), v2 = corner(p, kTri[t][2]);
     if (!(0.5f * norm(cross(v1 - v0, v2 - v0)) > eps_nonzero)) return false;
   }
   return true;
@@ -125,16 +153,29 @@ __global__ __launch_bounds__(128) void box3d_iou_kernel(const float* __restrict_
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (long)N * M) return;
   const int i = (int)(idx / M), j = (int)(idx % M);
+  const float* pa = dt + (size_t)i * 24;
+  const float* pb = gt + (size_t)j * 24;
+  // the local frame: both boxes minus the detection's corner centroid
+  V3 o = {0.f, 0.f, 0.f};
+  for (int k = 0; k < 8; ++k) o = o + corner(pa, k);
+  o = o * 0.125f;
+  float la[24], lb[24];
+  for (int k = 0; k < 8; ++k) {
+    la[3 * k] = pa[3 * k] - o.x; la[3 * k + 1] = pa[3 * k + 1] - o.y; la[3 * k + 2] = pa[3 * k + 2] - o.z;
+    lb[3 * k] = pb[3 * k] - o.x; lb[3 * k + 1] = pb[3 * k + 1] - o.y; lb[3 * k + 2] = pb[3 * k + 2] - o.z;
+  }
   Box a, b;
-  load_box(dt + (size_t)i * 24, a);
-  load_box(gt + (size_t)j * 24, b);
-  float v = 0.f;
-  for (int f = 0; f < 6; ++f) v += a.d[f] * clipped_face_area(a, f, b, true);
-  for (int f = 0; f < 6; ++f) v += b.d[f] * clipped_face_area(b, f, a, false);
-  v = fmaxf(v * (1.f / 3.f), 0.f);
-  float u = a.vol + b.vol - v;
-  float r = (u > 0.f) ? v / u : 0.f;
-  if (!box_valid(a, eps_coplanar, eps_nonzero)) { r = 0.f; }             // offending detections get IoU 0 (:160-167)
+  load_box(la, a);
+  load_box(lb, b);
+  float v = 0.f, r = 0.f;
+  if (a.solid && b.solid) {
+    for (int f = 0; f < 6; ++f) v += a.d[f] * clipped_face_area(a, f, b, true);
+    for (int f = 0; f < 6; ++f) v += b.d[f] * clipped_face_area(b, f, a, false);
+    v = fminf(fmaxf(v * (1.f / 3.f), 0.f), fminf(a.vol, b.vol));
+    const float u = a.vol + b.vol - v;
+    r = (u > 0.f) ? fminf(v / u, 1.f) : 0.f;
+  }
+  if (!box_valid(pa, eps_coplanar, eps_nonzero)) { r = 0.f; }            // offending detections get IoU 0 (:160-167)
   iou[idx] = r;
   if (vol) vol[idx] = v;
 }
