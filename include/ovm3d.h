@@ -530,6 +530,103 @@ int ovm_render_scene(const OvmSceneLayout* layout, const OvmSceneSegment* grid, 
                      const uint8_t* image, int64_t image_pitch, uint8_t* front, int64_t front_pitch, uint8_t* novel, int64_t novel_pitch,
                      void* workspace, int64_t workspace_bytes, ovm_stream_t stream);
 
+/* ---- OVMono3D-GEO -----------------------------------------------------------------------------------------------------------
+ * The training-free baseline of the reference (tools/ovmono3d_geo.py:127-258): a 2D box's mask pixels are un-projected with a
+ * metric depth map, the cloud is yaw-aligned by the first principal direction of its (x, z) columns, outliers are removed with
+ * DBSCAN (up to `trials` runs, eps doubling), and the box is the extent of the kept points. The two networks in front of it
+ * (Depth Pro, SAM's prompt encoder / mask decoder) are NOT part of this library: depth and masks arrive as arrays.
+ *
+ * Steps, all in fp64 as the reference (the numpy restatement is tests/geo_oracle.py):
+ *  1. points, row-major over the mask pixels: z = depth[y][x]; p = (z (x - cx) / fx, -(z (y - cy) / fy), -z)
+ *  2. offset = mean(p), X = p - offset
+ *  3. yaw = atan2(v[1], v[0]), v the unit eigenvector of the larger eigenvalue of the 2 x 2 covariance of X's (x, z) columns, its
+ *     sign scikit-learn's (the entry of larger magnitude is positive; on equal magnitudes the first)
+ *  4. T = Ry(-yaw) X + offset, Ry(a) = [[cos a, 0, -sin a], [0, 1, 0], [sin a, 0, cos a]]
+ *  5. more than max_points rows: keep rows perm[0 .. max_points) (perm: the caller's permutation of 0 .. n-1; the reference's is
+ *     numpy.random.RandomState(42).shuffle(arange(n)))
+ *  6. trial t = 1 .. trials at eps = eps0 * 2^(t-1): DBSCAN(eps, min_samples), Euclidean, a point counts itself, d <= eps; a
+ *     cluster is kept unless size / n < min_cluster_frac or size <= min_cluster; the trial is accepted when kept > accept_frac * n;
+ *     no trial accepted: every point is kept (trial 0)
+ *  7. the extents are the kept points' min / max per axis of the rotated frame.
+ * ovm_host_geo_box turns the result into the reference's box (its gen_8corners order, rotation back, y / z flip, center, (W, H, L),
+ * pose, float32 corners).
+ *
+ * Cluster numbering is scikit-learn's: clusters in the order of their smallest core-point index, a border point takes the smallest
+ * label among the clusters of its core neighbours, noise is -1.
+ *
+ * Declared deviations from the reference:
+ *  - instances for which the reference divides by zero or raises are not lifted; they get a status and no box: an empty mask
+ *    (OVM_GEO_EMPTY), fewer than 2 points (OVM_GEO_TOO_FEW), a non-finite depth under the mask (OVM_GEO_NONFINITE), a rectangle
+ *    that misses the image (OVM_GEO_RECT_OUTSIDE);
+ *  - "the box is the mask" (mask == NULL) is ours, the reference always runs SAM: the pixels x0 <= x < x1, y0 <= y < y1 of `rect`
+ *    clipped to the image; the tools derive rect from an xyxy box as (ceil(x0), ceil(y0), ceil(x1), ceil(y1));
+ *  - pose is the closed form Ry(-yaw) = [[cos yaw, 0, sin yaw], [0, 1, 0], [-sin yaw, 0, cos yaw]]; the reference's Kabsch / SVD
+ *    (get_pose) gives the same matrix to 4e-16. */
+enum { OVM_GEO_OK = 0, OVM_GEO_EMPTY = 1, OVM_GEO_TOO_FEW = 2, OVM_GEO_NONFINITE = 3, OVM_GEO_RECT_OUTSIDE = 4,
+       OVM_GEO_COUNT_MISMATCH = 5, /* a mask plane holds another number of pixels than n_points declares */
+       OVM_GEO_BAD_PERM = 6 };     /* a perm entry outside 0 .. n_points-1 */
+
+typedef struct OvmGeoParams {       /* reference defaults: 0.01, 0.1, 0.5, 100, 40000, 4, 100 */
+  double eps0;                      /* eps of the first trial, metres; doubled per trial */
+  double min_cluster_frac;          /* a cluster with size / n below this is dropped */
+  double accept_frac;               /* a trial is accepted when kept > accept_frac * n */
+  int32_t min_samples;              /* DBSCAN core threshold, the point itself included */
+  int32_t max_points;               /* down-sampling cap */
+  int32_t trials;                   /* 1 .. 8 */
+  int32_t min_cluster;              /* a cluster with size <= this is dropped */
+  int32_t last_stage;               /* 0: everything. Timing aid: stop after 1 points, 2 mean + yaw, 3 rotate + gather, 3 + t trial t */
+  int32_t reserved;
+} OvmGeoParams;
+
+typedef struct OvmGeoInstance {
+  const uint8_t* mask;              /* device [H][W] plane, nonzero = inside; NULL: the rectangle is the mask */
+  const int32_t* perm;              /* device [n_points] or NULL; required when n_points > max_points */
+  int32_t rect[4];                  /* x0, y0, x1, y1, half-open, read when mask == NULL */
+  int32_t n_points;                 /* mask: the number of nonzero pixels (the caller counts them); rectangle: ignored */
+  int32_t reserved;
+} OvmGeoInstance;
+
+typedef struct OvmGeoResult {
+  double offset[3];                 /* mean of the un-projected points */
+  double yaw;
+  double ext_min[3], ext_max[3];    /* kept points' min / max in the rotated frame */
+  double eps;                       /* eps of the accepted trial (of the last one run when none was) */
+  int32_t n_points, n_used, n_kept; /* points, points after down-sampling, points the extents cover */
+  int32_t trial;                    /* accepted trial 1 .. trials, 0 = fallback to all points */
+  int32_t status;                   /* OVM_GEO_*; anything but OVM_GEO_OK: the other fields except n_points are zero */
+  int32_t reserved;
+} OvmGeoResult;
+
+typedef struct OvmGeoBox {
+  double center_cam[3], dimensions[3], pose[9], center_2D[2], depth;
+  float bbox3D[8][3];
+} OvmGeoBox;
+
+/* The reference's parameters. */
+int ovm_geo_default_params(OvmGeoParams* params);
+/* Message of the last OVM_ERR_* a GEO call returned on this thread (these calls take no handle). */
+const char* ovm_geo_last_error(void);
+/* Workspace bytes for ovm_geo_lift on these instances; label_offsets (host, [n_inst + 1], may be NULL) receives where each
+ * instance's n_used labels start in the `labels` array. inst is host memory; nothing touches the device. */
+int ovm_geo_lift_workspace(const OvmGeoInstance* inst, int32_t n_inst, int32_t H, int32_t W, const OvmGeoParams* params, int64_t* bytes,
+                           int64_t* label_offsets);
+/* Lifts all instances of one image: one stream-ordered launch sequence, no device-to-host read and no wait for the device
+ * other than for the previous call's descriptor upload, whose pinned staging buffer is reused (a per-instance flag on the device ends
+ * the later trials of an accepted instance early). depth: device fp32 [H][W]; K: host,
+ * row-major 3 x 3; inst: host; results: device [n_inst]; labels: device int32, the last trial's labels per instance at
+ * label_offsets (all -1 for an instance that is not lifted), or NULL. OVM_ERR_INVALID for null / inconsistent arguments, OVM_ERR_UNSUPPORTED when an instance has more than
+ * max_points points and no perm, OVM_ERR_CAPACITY for too small a workspace - all before any device work. */
+int ovm_geo_lift(const float* depth, int32_t H, int32_t W, const double* K, const OvmGeoInstance* inst, int32_t n_inst,
+                 const OvmGeoParams* params, OvmGeoResult* results, int32_t* labels, void* workspace, int64_t workspace_bytes,
+                 ovm_stream_t stream);
+/* The clustering alone: labels of sklearn.cluster.DBSCAN(eps, min_samples).fit(points).labels_ for device fp64 points [n][3]. */
+int ovm_geo_dbscan_workspace(int32_t n, int64_t* bytes);
+int ovm_geo_dbscan(const double* points, int32_t n, double eps, int32_t min_samples, int32_t* labels, void* workspace,
+                   int64_t workspace_bytes, ovm_stream_t stream);
+/* Host, fp64, no GPU: steps 7's corners and the box of a lifted instance (status OVM_GEO_OK, else OVM_ERR_INVALID). bbox3D is
+ * get_cuboid_verts_faces of the float32-rounded center, dimensions and pose, computed in float32 as the reference does. */
+int ovm_host_geo_box(const OvmGeoResult* result, const double* K, OvmGeoBox* box);
+
 #ifdef __cplusplus
 }
 #endif

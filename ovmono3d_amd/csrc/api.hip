@@ -391,6 +391,10 @@ int ovm_abi_sizeof(const char* name) {
   if (n == "OvmSceneLayout") return (int)sizeof(OvmSceneLayout);
   if (n == "OvmSceneSegment") return (int)sizeof(OvmSceneSegment);
   if (n == "OvmEvalCell") return (int)sizeof(OvmEvalCell);
+  if (n == "OvmGeoParams") return (int)sizeof(OvmGeoParams);
+  if (n == "OvmGeoInstance") return (int)sizeof(OvmGeoInstance);
+  if (n == "OvmGeoResult") return (int)sizeof(OvmGeoResult);
+  if (n == "OvmGeoBox") return (int)sizeof(OvmGeoBox);
   return -1;
 }
 

@@ -120,6 +120,31 @@ class OvmEvalCell(C.Structure):
                 ("prox", C.c_int32), ("reserved", C.c_int32)]
 
 
+OVM_GEO_OK, OVM_GEO_EMPTY, OVM_GEO_TOO_FEW, OVM_GEO_NONFINITE, OVM_GEO_RECT_OUTSIDE, OVM_GEO_COUNT_MISMATCH, OVM_GEO_BAD_PERM = range(7)
+
+
+class OvmGeoParams(C.Structure):
+    """Mirror of include/ovm3d.h OvmGeoParams."""
+    _fields_ = [("eps0", C.c_double), ("min_cluster_frac", C.c_double), ("accept_frac", C.c_double),
+                ("min_samples", C.c_int32), ("max_points", C.c_int32), ("trials", C.c_int32), ("min_cluster", C.c_int32),
+                ("last_stage", C.c_int32), ("reserved", C.c_int32)]
+
+
+class OvmGeoInstance(C.Structure):
+    _fields_ = [("mask", C.c_void_p), ("perm", C.c_void_p), ("rect", C.c_int32 * 4), ("n_points", C.c_int32), ("reserved", C.c_int32)]
+
+
+class OvmGeoResult(C.Structure):
+    _fields_ = [("offset", C.c_double * 3), ("yaw", C.c_double), ("ext_min", C.c_double * 3), ("ext_max", C.c_double * 3),
+                ("eps", C.c_double), ("n_points", C.c_int32), ("n_used", C.c_int32), ("n_kept", C.c_int32), ("trial", C.c_int32),
+                ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
+class OvmGeoBox(C.Structure):
+    _fields_ = [("center_cam", C.c_double * 3), ("dimensions", C.c_double * 3), ("pose", C.c_double * 9), ("center_2D", C.c_double * 2),
+                ("depth", C.c_double), ("bbox3D", (C.c_float * 3) * 8)]
+
+
 EXPORTS = [
     "ovm_create", "ovm_destroy", "ovm_last_error", "ovm_version", "ovm_abi_sizeof", "ovm_backbone_forward", "ovm_cube_forward",
     "ovm_rpn_box_forward", "ovm_gather_records", "ovm_gather_counts", "ovm_host_interp_pos_embed", "ovm_host_resize_pos_embed_aa", "ovm_host_sincos_pos_embed", "ovm_host_shard_range",
@@ -133,6 +158,8 @@ EXPORTS = [
     "ovm_gdino_debug_copy", "ovm_debug_set_ptr", "ovm_gdino_num_queries", "ovm_gdino_last_outputs", "ovm_infer",
     "ovm_host_jpeg_info", "ovm_host_jpeg_entropy_decode", "ovm_jpeg_reconstruct",
     "ovm_host_scene_layout", "ovm_render_scene_workspace", "ovm_render_scene",
+    "ovm_geo_default_params", "ovm_geo_last_error", "ovm_geo_lift_workspace", "ovm_geo_lift", "ovm_geo_dbscan_workspace", "ovm_geo_dbscan",
+    "ovm_host_geo_box",
 ]
 PROF_NAMES = ("attn", "qkv", "proj", "fc1", "fc2", "ln")
 
@@ -158,7 +185,8 @@ def load() -> C.CDLL:
     lib.ovm_abi_sizeof.argtypes = [C.c_char_p]
     for name, mirror in (("OvmConfig", OvmConfig), ("OvmTensor", OvmTensor), ("OvmImage", OvmImage), ("OvmGdinoConfig", OvmGdinoConfig),
                          ("OvmJpegInfo", OvmJpegInfo), ("OvmSceneInput", OvmSceneInput), ("OvmSceneLayout", OvmSceneLayout),
-                         ("OvmSceneSegment", OvmSceneSegment), ("OvmEvalCell", OvmEvalCell)):
+                         ("OvmSceneSegment", OvmSceneSegment), ("OvmEvalCell", OvmEvalCell), ("OvmGeoParams", OvmGeoParams),
+                         ("OvmGeoInstance", OvmGeoInstance), ("OvmGeoResult", OvmGeoResult), ("OvmGeoBox", OvmGeoBox)):
         if lib.ovm_abi_sizeof(name.encode()) != C.sizeof(mirror):
             raise RuntimeError(f"{LIB_PATH}: sizeof({name}) = {lib.ovm_abi_sizeof(name.encode())} but the ctypes mirror has "
                                f"{C.sizeof(mirror)} bytes - rebuild the library (ovmono3d_amd/csrc/build.sh) or update lib.py")
@@ -203,6 +231,14 @@ def load() -> C.CDLL:
     lib.ovm_box3d_iou.argtypes = [vp, vp, i32, i32, f32, f32, vp, vp, vp]
     lib.ovm_eval_iou2d.argtypes = [vp, vp, i32, vp, vp, C.c_double, vp, vp, vp]
     lib.ovm_eval_match.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp]
+    lib.ovm_geo_default_params.argtypes = [C.POINTER(OvmGeoParams)]
+    lib.ovm_geo_last_error.argtypes = []
+    lib.ovm_geo_last_error.restype = C.c_char_p
+    lib.ovm_geo_lift_workspace.argtypes = [C.POINTER(OvmGeoInstance), i32, i32, i32, C.POINTER(OvmGeoParams), C.POINTER(i64), C.POINTER(i64)]
+    lib.ovm_geo_lift.argtypes = [vp, i32, i32, C.POINTER(C.c_double), C.POINTER(OvmGeoInstance), i32, C.POINTER(OvmGeoParams), vp, vp, vp, i64, vp]
+    lib.ovm_geo_dbscan_workspace.argtypes = [i32, C.POINTER(i64)]
+    lib.ovm_geo_dbscan.argtypes = [vp, i32, C.c_double, i32, vp, vp, i64, vp]
+    lib.ovm_host_geo_box.argtypes = [C.POINTER(OvmGeoResult), C.POINTER(C.c_double), C.POINTER(OvmGeoBox)]
     lib.ovm_g_pack_weight.argtypes = [vp, i32, i32, i32, vp, vp, vp]
     lib.ovm_g_linear.argtypes = [vp, i32, i32, i32, vp, vp, i32, i32, vp, i32, vp, i32, vp, i32, i32, vp]
     lib.ovm_g_layernorm.argtypes = [vp, vp, i32, i32, vp, vp, f32, vp, vp]
@@ -232,7 +268,7 @@ def load() -> C.CDLL:
     lib.ovm_gdino_last_outputs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32)]
     lib.ovm_infer.argtypes = [vp, vp, C.POINTER(OvmImage), C.POINTER(i32), i32, C.POINTER(i32), i32, f32, f32, vp, i32, C.POINTER(i32), vp]
     for name in EXPORTS:
-        if name not in ("ovm_last_error", "ovm_version", "ovm_debug_copy", "ovm_gdino_last_error", "ovm_gdino_debug_copy"):
+        if name not in ("ovm_last_error", "ovm_version", "ovm_debug_copy", "ovm_gdino_last_error", "ovm_gdino_debug_copy", "ovm_geo_last_error"):
             getattr(lib, name).restype = i32
     # experiment knobs, e.g. OVM_TUNE="gemm_bm=256,attn_tail=0"
     for kv in filter(None, os.environ.get("OVM_TUNE", "").split(",")):

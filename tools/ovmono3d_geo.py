@@ -1,0 +1,158 @@
+#!/usr/bin/env python3
+"""OVMono3D-GEO, the training-free baseline (reference tools/ovmono3d_geo.py): lifts the 2D boxes of an oracle-2D file to 3D from
+a metric depth map and a mask per box - un-projection, PCA yaw, DBSCAN outlier removal, extent fit - on the device
+(ovmono3d_amd.geo, csrc/geo.hip), and writes the reference's per-image records for tools/eval_ovmono3d_geo.py.
+
+    python tools/ovmono3d_geo.py --oracle2d gdino_kitti_novel_oracle_2d.json --dataset datasets/Omni3D/KITTI_test_novel.json \\
+        --depth-dir datasets/depth --mask-dir datasets/masks --output output/ovmono3d_geo/KITTI_test_novel.pth
+
+What is NOT here: the two networks the reference runs in front of the lifting. Depth (Depth Pro there) is read from
+``<depth-dir>/test/<image base name>.npz`` (or ``<depth-dir>/<image base name>.npz``), key ``depth``, metres, at the image's own
+resolution - a map of another shape is refused, the reference never resizes it. Masks (SAM's largest mask there) are read from
+``<mask-dir>/<image_id>.npz``: ``masks`` uint8 [n, H, W] (nonzero = inside) and ``index`` int [n], the positions of the masked
+instances in the image's instance list. With ``--mask box`` the 2D box itself is the mask: the pixels ceil(x0) <= x < ceil(x1),
+ceil(y0) <= y < ceil(y1) of the xyxy box, clipped to the image (the reference has no such mode; the rule is this project's).
+
+Instances below ``--score-threshold`` are dropped as in the reference. Instances the reference has no answer for (an empty mask,
+fewer than 2 points, a non-finite depth under the mask, a box outside the image, no mask in the mask file) are skipped, counted
+and logged.
+"""
+import argparse
+import json
+import logging
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from ovmono3d_amd.geo import GeoParams, lift_boxes  # noqa: E402
+
+logger = logging.getLogger("ovmono3d_geo")
+KEPT_KEYS = ("category_id", "bbox", "score", "category_name")
+
+
+def xywh_to_xyxy(b):
+    x, y, w, h = b
+    return [x, y, x + w, y + h]
+
+
+def lift_image(depth, K, boxes_xyxy, masks, params):
+    """depth: float32 [H, W] numpy; masks: a list of uint8 [H, W] arrays or None (the box is the mask). One device call."""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    d = torch.from_numpy(depth).to(dev)
+    m = None if masks is None else [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in masks]
+    return lift_boxes(d, K, boxes_xyxy=boxes_xyxy, masks=m, params=params)
+
+
+def load_depth(depth_dir, file_path, height, width):
+    base = os.path.splitext(os.path.basename(file_path))[0]
+    for cand in (os.path.join(depth_dir, "test", base + ".npz"), os.path.join(depth_dir, base + ".npz")):
+        if os.path.exists(cand):
+            depth = np.load(cand)["depth"]
+            if depth.ndim == 3 and depth.shape[0] == 1:
+                depth = depth[0]
+            if tuple(depth.shape) != (height, width):
+                raise SystemExit(f"{cand}: depth map is {tuple(depth.shape)} but the image is {(height, width)}; GEO needs the depth at "
+                                 "the image's own resolution (the reference never resizes it)")
+            return np.ascontiguousarray(depth, dtype=np.float32)
+    raise SystemExit(f"no depth file for {file_path} under {depth_dir}")
+
+
+def load_masks(mask_dir, image_id, height, width):
+    """{position in the instance list: uint8 [H, W]} of one image; empty when the image has no mask file."""
+    path = os.path.join(mask_dir, f"{image_id}.npz")
+    if not os.path.exists(path):
+        return {}
+    z = np.load(path)
+    masks, index = z["masks"], z["index"]
+    if masks.ndim != 3 or tuple(masks.shape[1:]) != (height, width) or len(index) != len(masks):
+        raise SystemExit(f"{path}: masks {tuple(masks.shape)} / index {tuple(index.shape)} do not fit a {height} x {width} image")
+    return {int(i): (masks[k] != 0).astype(np.uint8) for k, i in enumerate(index)}
+
+
+def run(args):
+    with open(args.oracle2d) as f:
+        oracle = json.load(f)
+    with open(args.dataset) as f:
+        images = {im["id"]: im for im in json.load(f)["images"]}
+    params = GeoParams()
+    use_box = args.mask == "box"
+    if not use_box and not args.mask_dir:
+        raise SystemExit("give --mask-dir DIR or --mask box")
+    out, n_in, n_low, n_skip, n_lifted = [], 0, 0, 0, 0
+    for rec in oracle:
+        im = images.get(rec["image_id"])
+        if im is None:
+            raise SystemExit(f"image_id {rec['image_id']} of {args.oracle2d} is not in {args.dataset}")
+        H, W = int(im["height"]), int(im["width"])
+        K = np.asarray(rec.get("K", im["K"]), np.float64).reshape(3, 3)
+        cand = [(pos, ins) for pos, ins in enumerate(rec["instances"]) if not ins["score"] < args.score_threshold]
+        n_in += len(rec["instances"])
+        n_low += len(rec["instances"]) - len(cand)
+        new_instances = []
+        if cand:
+            depth = load_depth(args.depth_dir, im["file_path"], H, W)
+            planes = None
+            if not use_box:
+                have = load_masks(args.mask_dir, rec["image_id"], H, W)
+                missing = [pos for pos, _ in cand if pos not in have]
+                if missing:
+                    logger.warning("image %s: no mask for instances %s - skipped", rec["image_id"], missing)
+                    n_skip += len(missing)
+                cand = [(pos, ins) for pos, ins in cand if pos in have]
+                planes = [have[pos] for pos, _ in cand]
+            if cand:
+                boxes = np.asarray([xywh_to_xyxy(ins["bbox"]) for _, ins in cand], np.float64)
+                lifted = lift_image(depth, K, boxes, planes, params)
+                for (pos, ins), box in zip(cand, lifted):
+                    if box is None:
+                        logger.warning("image %s: instance %d has no 3D box (empty mask, < 2 points, non-finite depth or a box outside "
+                                       "the image) - skipped", rec["image_id"], pos)
+                        n_skip += 1
+                        continue
+                    new = {k: v for k, v in ins.items() if k in KEPT_KEYS}
+                    new["image_id"] = rec["image_id"]
+                    for k in ("bbox3D", "depth", "center_cam", "dimensions", "pose", "center_2D"):
+                        new[k] = box[k]
+                    new_instances.append(new)
+        n_lifted += len(new_instances)
+        new_rec = dict(rec)
+        new_rec["instances"] = new_instances
+        out.append(new_rec)
+    os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
+    if args.output.endswith(".json"):
+        with open(args.output, "w") as f:
+            json.dump(out, f)
+    else:
+        torch.save(out, args.output)
+    stats = {"images": len(out), "instances": n_in, "below_threshold": n_low, "skipped": n_skip, "lifted": n_lifted}
+    logger.info("wrote %s: %s", args.output, json.dumps(stats))
+    return stats
+
+
+def argument_parser():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--oracle2d", required=True, help="oracle-2D file (tools/make_oracle2d.py): [{image_id, instances[{bbox xywh, category_id, score}]}]")
+    ap.add_argument("--dataset", required=True, help="Omni3D annotation json of the same images (file_path, height, width, K)")
+    ap.add_argument("--depth-dir", required=True, help="metric depth .npz files (key 'depth'), the ones DatasetMapper3D reads")
+    ap.add_argument("--mask-dir", default=None, help="<image_id>.npz with 'masks' uint8 [n, H, W] and 'index' int [n]")
+    ap.add_argument("--mask", choices=("box",), default=None,
+                    help="box: the 2D box is the mask - pixels ceil(x0) <= x < ceil(x1), ceil(y0) <= y < ceil(y1), clipped to the image")
+    ap.add_argument("--score-threshold", type=float, default=0.30)
+    ap.add_argument("--output", required=True, help=".pth (torch.save, as the reference) or .json")
+    return ap
+
+
+def main():
+    logging.basicConfig(level=logging.INFO)
+    args = argument_parser().parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("OVMono3D-GEO runs on the HIP device (there is no CPU path)")
+    print(json.dumps(run(args)))
+
+
+if __name__ == "__main__":
+    main()
