@@ -141,7 +141,7 @@ int ovm_destroy(OvmHandle* h);
 const char* ovm_last_error(const OvmHandle* h);
 const char* ovm_version(void);
 /* sizeof() of a struct of this header as the library was compiled ("OvmConfig", "OvmTensor", "OvmImage", "OvmDet3D",
- * "OvmGdinoConfig", "OvmJpegInfo", "OvmSceneInput", "OvmSceneLayout", "OvmSceneSegment", "OvmEvalCell"), -1 for an unknown name: lets a binding check its mirror of the layout before the first call. */
+ * "OvmGdinoConfig", "OvmJpegInfo", "OvmSceneInput", "OvmSceneLayout", "OvmSceneSegment", "OvmEvalCell", "OvmSamConfig"), -1 for an unknown name: lets a binding check its mirror of the layout before the first call. */
 int ovm_abi_sizeof(const char* struct_name);
 
 /* --- backbone: build_dino_backbone(...).forward(x, prompt_depth) -> {p2,p3,p4}
@@ -533,8 +533,8 @@ int ovm_render_scene(const OvmSceneLayout* layout, const OvmSceneSegment* grid, 
 /* ---- OVMono3D-GEO -----------------------------------------------------------------------------------------------------------
  * The training-free baseline of the reference (tools/ovmono3d_geo.py:127-258): a 2D box's mask pixels are un-projected with a
  * metric depth map, the cloud is yaw-aligned by the first principal direction of its (x, z) columns, outliers are removed with
- * DBSCAN (up to `trials` runs, eps doubling), and the box is the extent of the kept points. The two networks in front of it
- * (Depth Pro, SAM's prompt encoder / mask decoder) are NOT part of this library: depth and masks arrive as arrays.
+ * DBSCAN (up to `trials` runs, eps doubling), and the box is the extent of the kept points. Of the two networks in front of it,
+ * SAM is in this library (OvmSam below: its planes are what `mask` takes); Depth Pro is not: depth arrives as an array.
  *
  * Steps, all in fp64 as the reference (the numpy restatement is tests/geo_oracle.py):
  *  1. points, row-major over the mask pixels: z = depth[y][x]; p = (z (x - cx) / fx, -(z (y - cy) / fy), -z)
@@ -626,6 +626,55 @@ int ovm_geo_dbscan(const double* points, int32_t n, double eps, int32_t min_samp
 /* Host, fp64, no GPU: steps 7's corners and the box of a lifted instance (status OVM_GEO_OK, else OVM_ERR_INVALID). bbox3D is
  * get_cuboid_verts_faces of the float32-rounded center, dimensions and pose, computed in float32 as the reference does. */
 int ovm_host_geo_box(const OvmGeoResult* result, const double* K, OvmGeoBox* box);
+
+/* ---- Segment Anything, box-prompted ------------------------------------------------------------------------------------------
+ * The mask source of OVMono3D-GEO (reference tools/ovmono3d_geo.py:213-217,270-272,308-309): segment_anything's
+ * SamPredictor.set_image(image) once, then predict(box=xyxy) per instance, of which the reference keeps plane [2] of the three
+ * multimask outputs. Weights carry segment_anything's own key names (image_encoder.*, prompt_encoder.*, mask_decoder.*).
+ *
+ * The image encoder's blocks are the OVM_TOWER_SAM code of ovm_create (same packing, same kernels); the neck, the prompt encoder
+ * for boxes, the two-way transformer, the upscaling / hypernetwork heads and postprocess_masks are sequenced here. GEMMs follow
+ * `precision` (1: fp16 operands, 3: split fp16 x 3); softmax, LayerNorm, sin / cos and the resampling are fp32.
+ *
+ * Scope: head dimension 64 in the image encoder (vit_b, vit_l). vit_h (1280 wide, 16 heads: head dimension 80) is refused with
+ * OVM_ERR_UNSUPPORTED. Box prompts only (no points, no mask input: the dense prompt is no_mask_embed). */
+typedef struct OvmSam OvmSam;
+typedef struct OvmSamConfig {
+  int32_t embed_dim, depth, heads, patch;   /* image encoder: vit_b 768 / 12 / 12 / 16, vit_l 1024 / 24 / 16 / 16 */
+  int32_t pos_grid;                         /* side of the checkpoint's position table (64) */
+  int32_t window;                           /* window side of the windowed blocks (14) */
+  uint32_t global_mask;                     /* bit i set = block i attends globally */
+  int32_t image_size;                       /* ResizeLongestSide target and encoder input side (1024) */
+  int32_t prompt_dim;                       /* prompt / decoder width (256) */
+  int32_t dec_depth, dec_heads, dec_mlp;    /* two-way transformer: 2, 8, 2048 */
+  int32_t attn_downsample;                  /* internal width of the cross attentions = prompt_dim / this (2) */
+  int32_t num_mask_tokens;                  /* 4 (multimask outputs + 1) */
+  int32_t iou_depth, iou_hidden;            /* IoU head: 3 layers, 256 wide */
+  float pixel_mean[3], pixel_std[3];        /* in the network's channel order (segment_anything: 123.675 116.28 103.53 / 58.395 57.12 57.375) */
+  int32_t precision;                        /* 1 or 3 */
+  int32_t max_boxes;                        /* most boxes one decoder pass takes; a call with more runs in chunks */
+} OvmSamConfig;
+int ovm_sam_create(const OvmSamConfig* cfg, const OvmTensor* weights, int32_t n_weights, int32_t device, OvmSam** out);
+int ovm_sam_destroy(OvmSam* sam);
+const char* ovm_sam_last_error(const OvmSam* sam);
+/* SamPredictor.set_image: image = uint8 device image at its own resolution (height x width; any element strides). ResizeLongestSide
+ * (target sides int(side * image_size / max(h, w) + 0.5), Pillow-exact bilinear), flip_bgr != 0: channels reversed first (the
+ * predictor's image_format != "RGB" branch), (x - mean) / std, zero padding to the square, encoder, neck. The [G][G][prompt_dim]
+ * embedding and the dense positional encoding stay in the handle. */
+int ovm_sam_set_image(OvmSam* sam, const OvmImage* image, int32_t flip_bgr, ovm_stream_t stream);
+/* Device workspace bytes of ovm_sam_predict_boxes for n boxes (chunks of min(n, max_boxes) boxes); a smaller workspace that still
+ * holds one box is accepted and means smaller chunks. */
+int ovm_sam_predict_boxes_workspace(const OvmSam* sam, int32_t n, int64_t* bytes);
+/* SamPredictor.predict(box=..., multimask_output=True) for n boxes of the image of the last ovm_sam_set_image. boxes_xyxy: device
+ * fp32 [n][4] in original pixels. mask_index 0..2: which multimask plane masks_u8 (device uint8 [n][H][W], 1 = logit > 0 after
+ * postprocess_masks) receives. iou: device fp32 [n][3] or NULL. lowres: device fp32 [n][3][4G][4G] low-resolution logits or NULL
+ * (NULL: only the requested mask token's product is computed). Stream-ordered, no synchronisation. */
+int ovm_sam_predict_boxes(OvmSam* sam, const float* boxes_xyxy, int32_t n, int32_t mask_index, uint8_t* masks_u8, float* iou,
+                          float* lowres, void* workspace, int64_t workspace_bytes, ovm_stream_t stream);
+/* tests: copy an intermediate into dst (device fp32); returns the element count or a negative error. names: "preprocessed"
+ * [3][S][S] (the encoder's input as its patch rows hold it), "neck" [G][G][C], "dense_pe" [G][G][C]; of the last chunk of the
+ * last predict call: "sparse" [n][2][C], "tokens_out" [n][3 + num_mask_tokens][C]. */
+int64_t ovm_sam_debug_copy(OvmSam* sam, const char* name, float* dst, int64_t capacity, ovm_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -13,6 +13,7 @@
 #include "kernels.hpp"
 #include "det2d.hpp"
 #include "gdino.hpp"
+#include "sam.hpp"
 
 using namespace ovm;
 
@@ -52,6 +53,7 @@ struct FpnLevel {              // one output level of the simple feature pyramid
 struct OvmHandle {
   OvmConfig cfg;
   int device = 0;
+  bool tower_only = false;          // ovm::tower_create: the ViT blocks alone (no pyramid, no heads) - the SAM predictor's image encoder
   std::string err;
   std::vector<void*> allocs;
   int G = 0, G2 = 0, T = 0, Tpad = 0, D = 0, C = 0, Kpe = 640, npass = 1;
@@ -395,6 +397,7 @@ int ovm_abi_sizeof(const char* name) {
   if (n == "OvmGeoInstance") return (int)sizeof(OvmGeoInstance);
   if (n == "OvmGeoResult") return (int)sizeof(OvmGeoResult);
   if (n == "OvmGeoBox") return (int)sizeof(OvmGeoBox);
+  if (n == "OvmSamConfig") return (int)sizeof(OvmSamConfig);
   return -1;
 }
 
@@ -606,11 +609,15 @@ int ovm_host_sincos_pos_embed(int32_t D, int32_t G, float* out) {
   return OVM_OK;
 }
 
-int ovm_create(const OvmConfig* cfg, const OvmTensor* weights, int32_t n_weights, int32_t device, OvmHandle** out) {
+}  // extern "C"
+
+// vit_prefix: key prefix of the ViT's tensors (null: the tower's own, backbone.net.vit. / backbone.net.visual.); tower_only: see OvmHandle
+static int create_impl(const OvmConfig* cfg, const OvmTensor* weights, int32_t n_weights, int32_t device, const char* vit_prefix, bool tower_only,
+                       OvmHandle** out) {
   if (!cfg || !out) return OVM_ERR_INVALID;
   OvmHandle* h = new OvmHandle();
   *out = h;
-  h->cfg = *cfg; h->device = device;
+  h->cfg = *cfg; h->device = device; h->tower_only = tower_only;
   const OvmConfig& c = h->cfg;
   const bool clip = c.tower == OVM_TOWER_CLIP, mae = c.tower == OVM_TOWER_MAE, midas = c.tower == OVM_TOWER_MIDAS, sam = c.tower == OVM_TOWER_SAM;
   const bool p16 = clip || mae || midas || sam;           // patch-16 towers behind the 4-level pyramid
@@ -650,7 +657,7 @@ int ovm_create(const OvmConfig* cfg, const OvmTensor* weights, int32_t n_weights
   for (int i = 0; i < n_weights; ++i) wm.m[weights[i].name] = &weights[i];
   int r;
   const int P = h->patch, PP = P * P;
-  const std::string V = clip ? "backbone.net.visual." : "backbone.net.vit.";
+  const std::string V = vit_prefix ? vit_prefix : (clip ? "backbone.net.visual." : "backbone.net.vit.");
   const std::string PEW = clip ? "conv1.weight" : (mae ? "embeddings.patch_embeddings.projection.weight" : "patch_embed.proj.weight");
   // ---- patch embed: [D][3][P][P] -> [D][(py*P+px)*3 + c]; P = 14: K padded 588 -> 640
   {
@@ -755,6 +762,9 @@ int ovm_create(const OvmConfig* cfg, const OvmTensor* weights, int32_t n_weights
     if ((r = pack_linear(h, wm, P + "mlp.fc1", 4 * D, D, &y.fc1))) return r;
     if ((r = pack_linear(h, wm, P + "mlp.fc2", D, 4 * D, &y.fc2))) return r;
   }
+  const int res = c.pooler_res, F = c.fc_dim;
+  if (tower_only) h->nlev = 0;
+  if (!tower_only) {
   h->has_dfuse = !p16 && c.use_depth_fusion && wm.get("backbone.net.depth_fusion.weight");
   if (h->has_dfuse) {
     if ((r = pack_linear(h, wm, "backbone.net.depth_fusion", D, D + 1, &h->dfuse, true, D + 64))) return r;
@@ -785,7 +795,6 @@ int ovm_create(const OvmConfig* cfg, const OvmTensor* weights, int32_t n_weights
     h->lv[li].side = G / 2; h->lv[li].stride = (float)P * 2.f; ++li;
   }
   // ---- heads
-  const int res = c.pooler_res, F = c.fc_dim;
   h->roiK = C * res * res;
   const std::string Q = "roi_heads.cube_head.";
   if ((r = pack_roi_fc(h, wm, Q + "feature_generator.fc1", F, C, res, &h->cube_fc1))) return r;
@@ -806,6 +815,7 @@ int ovm_create(const OvmConfig* cfg, const OvmTensor* weights, int32_t n_weights
     // 1x1 convs: objectness [A][C] then deltas [4A][C]
     if ((r = pack_concat(h, wm, {{P + "objectness_logits", 3}, {P + "anchor_deltas", 12}}, C, &h->rpn_out))) return r;
   }
+  }
   // ---- workspace
   const size_t MT = (size_t)B * T, MP = (size_t)B * G2;
   if ((r = dalloc(h, &h->X, MT * D))) return r;
@@ -820,8 +830,10 @@ int ovm_create(const OvmConfig* cfg, const OvmTensor* weights, int32_t n_weights
   { char* q = nullptr; if ((r = dalloc(h, &q, h->splitk_cap))) return r; h->splitk_ws = (float*)q; }
   if ((r = dalloc(h, &h->attn_tail_ws, attn_tail_ws_floats(B, c.heads)))) return r;
   if ((r = dalloc(h, &h->attn_tail_cnt, (size_t)B * c.heads * 8, true))) return r;
-  if ((r = salloc(h, &h->DT, MP * D))) return r;
-  if ((r = salloc(h, &h->DT4, (size_t)B * (G / 2) * (G / 2) * D))) return r;
+  if (!tower_only) {
+    if ((r = salloc(h, &h->DT, MP * D))) return r;
+    if ((r = salloc(h, &h->DT4, (size_t)B * (G / 2) * (G / 2) * D))) return r;
+  }
   if (h->has_dfuse) {
     if ((r = salloc(h, &h->DF, MP * (D + 64)))) return r;
     if ((r = dalloc(h, &h->dtok, MP))) return r;
@@ -849,6 +861,11 @@ int ovm_create(const OvmConfig* cfg, const OvmTensor* weights, int32_t n_weights
     if ((r = dalloc(h, &h->RELH, MW * c.heads * h->ldrel))) return r;
     if ((r = dalloc(h, &h->RELW, MW * c.heads * h->ldrel))) return r;
   }
+  if ((r = dalloc(h, &h->d_imgs, (size_t)B))) return r;
+  if ((r = dalloc(h, &h->d_meta, (size_t)B))) return r;
+  HCHECK(h, hipHostMalloc((void**)&h->h_imgs, sizeof(ImageDesc) * B));
+  HCHECK(h, hipHostMalloc((void**)&h->h_meta, sizeof(ImageMeta) * B));
+  if (tower_only) { HCHECK(h, hipDeviceSynchronize()); return OVM_OK; }
   const int G2x = 2 * G, G4 = G / 2;
   if ((r = salloc(h, &h->CT, (size_t)B * G2x * G2x * (D / 2)))) return r;
   if (p16) {
@@ -871,10 +888,6 @@ int ovm_create(const OvmConfig* cfg, const OvmTensor* weights, int32_t n_weights
   if ((r = dalloc(h, &h->rec, RR * kRecFloats))) return r;
   if ((r = dalloc(h, &h->keep, RR))) return r;
   if ((r = dalloc(h, &h->d_bidx, RR))) return r;
-  if ((r = dalloc(h, &h->d_imgs, (size_t)B))) return r;
-  if ((r = dalloc(h, &h->d_meta, (size_t)B))) return r;
-  HCHECK(h, hipHostMalloc((void**)&h->h_imgs, sizeof(ImageDesc) * B));
-  HCHECK(h, hipHostMalloc((void**)&h->h_meta, sizeof(ImageMeta) * B));
   if (h->has_rpn && h->has_box) {
     std::vector<void*> extra;
     int sides[kMaxLevels];
@@ -885,6 +898,12 @@ int ovm_create(const OvmConfig* cfg, const OvmTensor* weights, int32_t n_weights
   }
   HCHECK(h, hipDeviceSynchronize());
   return OVM_OK;
+}
+
+extern "C" {
+
+int ovm_create(const OvmConfig* cfg, const OvmTensor* weights, int32_t n_weights, int32_t device, OvmHandle** out) {
+  return create_impl(cfg, weights, n_weights, device, nullptr, false, out);
 }
 
 static int sfp_branch(OvmHandle* h, const Split& in, int lda, int Bn, const FpnLevel& f, hipStream_t s) {
@@ -947,8 +966,9 @@ int ovm_backbone_forward(OvmHandle* h, const OvmImage* images, int32_t B, const 
   return OVM_OK;
 }
 
-// every kernel launch of the backbone (patch embed .. pyramid), on stream s, shapes fixed by (B, canvas)
-static int backbone_launches(OvmHandle* h, int B, const float* prompt_depth, int depth_h, int depth_w, hipStream_t s) {
+// patch embed (+ preprocess) and the ViT blocks: the residual stream h->X [B * T][D] fp32 afterwards holds the last block's tokens.
+// Shared by the backbone below and by the SAM predictor's image encoder (ovm::tower_forward).
+static int tower_launches(OvmHandle* h, int B, hipStream_t s) {
   const OvmConfig& c = h->cfg;
   const int D = h->D, G = h->G, G2 = h->G2, T = h->T, L = c.depth;
   // ---- patch embed (+ preprocess) ----
@@ -1038,6 +1058,13 @@ static int backbone_launches(OvmHandle* h, int B, const float* prompt_depth, int
       KCHECK(h, gemm(h, p, EPI_RESID, A_ROWMAJOR, s, OVM_PROF_FC2));
     }
   }
+  return OVM_OK;
+}
+
+// every kernel launch of the backbone (patch embed .. pyramid), on stream s, shapes fixed by (B, canvas)
+static int backbone_launches(OvmHandle* h, int B, const float* prompt_depth, int depth_h, int depth_w, hipStream_t s) {
+  const int D = h->D, G = h->G, G2 = h->G2, T = h->T;
+  KCHECK(h, tower_launches(h, B, s));
   // ---- depth fusion at the last block output (reference dino.py:91-105) ----
   if (prompt_depth) {
     KCHECK(h, launch_depth_resize(prompt_depth, B, depth_h, depth_w, G, h->dtok, s));
@@ -1381,3 +1408,31 @@ int ovm_gather_records(void* comm, int32_t rank, int32_t world, const OvmDet3D* 
 }
 
 }  // extern "C"
+
+// ---- the ViT blocks alone, for the SAM predictor (sam.hip): same create / block code as the backbone, no pyramid and no heads ----
+namespace ovm {
+
+int tower_create(const OvmConfig* cfg, const OvmTensor* weights, int n_weights, int device, const char* vit_prefix, OvmHandle** out) {
+  return create_impl(cfg, weights, n_weights, device, vit_prefix, true, out);
+}
+
+int tower_forward(OvmHandle* h, const OvmImage* image, hipStream_t s) {
+  if (!h || !image || !h->tower_only) return OVM_ERR_INVALID;
+  h->err.clear();
+  const OvmConfig& c = h->cfg;
+  if (image->height > c.canvas || image->width > c.canvas || image->height < 1 || image->width < 1) {
+    h->err = "image larger than the encoder's canvas"; return OVM_ERR_SHAPE;
+  }
+  HCHECK(h, hipSetDevice(h->device));
+  HCHECK(h, hipStreamSynchronize(s));                    // the pinned descriptor below may still be read by the previous call's upload
+  fill_meta(h, image, 1);
+  HCHECK(h, hipMemcpyAsync(h->d_imgs, h->h_imgs, sizeof(ImageDesc), hipMemcpyHostToDevice, s));
+  h->lastB = 1;
+  return tower_launches(h, 1, s);
+}
+
+const float* tower_tokens(const OvmHandle* h) { return h ? h->X : nullptr; }
+
+void tower_patches(const OvmHandle* h, const half_t** hi, const half_t** lo, int* ld) { *hi = h->PA.hi; *lo = h->PA.lo; *ld = h->Kpe; }
+
+}  // namespace ovm

@@ -1,0 +1,792 @@
+// Segment Anything with box prompts (include/ovm3d.h, "Segment Anything, box-prompted"): SamPredictor.set_image / predict of
+// segment_anything as OVMono3D-GEO calls them (reference tools/ovmono3d_geo.py:213-217,270-272,308-309).
+//
+// The image encoder's blocks are the OVM_TOWER_SAM code of api.hip (ovm::tower_create / tower_forward). Everything behind them is
+// sequenced here from the generic fp32 device ops (ovm_g_linear / ovm_g_layernorm / ovm_g_bmm2 / ovm_g_softmax) plus the kernels
+// of this file:
+//   sam_i2t_attn_kernel   image -> token cross attention: G*G queries against <= 8 token keys per box, score + softmax + value sum
+//                         in registers (a tiled attention kernel would spend its key tile on 7 keys)
+//   sam_mask_out_kernel   postprocess_masks + threshold: both bilinear resamplings (4G -> S, crop, -> H x W) evaluated per output
+//                         pixel from the low-resolution logits, uint8 written at (H, W); the S x S plane never exists in HBM
+//   sam_mask_prod_kernel  hypernetwork product over the requested mask tokens
+//   small element-wise ones (box embedding, dense positional encoding, LayerNorm + GELU of the upscaling, broadcast add)
+// Layouts: every activation is fp32 row-major [rows][channels]; image-side rows are (box, y * G + x). The two transposed
+// convolutions of the upscaling are GEMMs over source pixels whose output columns are (a * 2 + b) * Cout + co, so the upscaled map is
+// kept blocked: pixel (4 i + 2 a + a2, 4 j + 2 b + b2) of box n lives at row ((n * G*G + i * G + j) * 4 + a * 2 + b), columns
+// (a2 * 2 + b2) * C8 .. + C8.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../../include/ovm3d.h"
+#include "kernels.hpp"
+#include "sam.hpp"
+
+using namespace ovm;
+
+namespace {
+
+struct Lin { half_t* hi = nullptr; half_t* lo = nullptr; float* bias = nullptr; int N = 0, K = 0, Kpad = 0; };
+struct Attn { Lin q, k, v, o; };
+struct Norm { float* g = nullptr; float* b = nullptr; };
+struct DecLayer { Attn self, t2i, i2t; Lin lin1, lin2; Norm n1, n2, n3, n4; };
+
+constexpr int kMaxTok = 8;           // tokens per box the image -> token kernel holds (1 IoU + mask tokens + 2 corners)
+constexpr float kDecEps = 1e-5f;     // nn.LayerNorm default of the two-way transformer
+constexpr float kLn2dEps = 1e-6f;    // LayerNorm2d of the neck and the upscaling
+
+}  // namespace
+
+struct OvmSam {
+  OvmSamConfig cfg;
+  int device = 0;
+  std::string err;
+  std::vector<void*> allocs;
+  OvmHandle* tower = nullptr;
+  int G = 0, G2 = 0, C = 0, S = 0, L = 0, nt = 0, I = 0;      // grid, prompt width, image size, low-res side 4G, tokens per box, cross-attention width
+  // neck
+  Lin neck1, neck3; Norm nn1, nn3;
+  half_t *pad_hi = nullptr, *pad_lo = nullptr; float *T1 = nullptr, *T2 = nullptr, *emb = nullptr, *src0 = nullptr, *pe = nullptr;
+  // prompt encoder
+  float *gauss = nullptr, *corner = nullptr /* point_embeddings 2, 3: [2][C] */, *no_mask = nullptr;
+  // decoder
+  float* out_tokens = nullptr;          // [1 + num_mask_tokens][C]: iou_token, mask_tokens
+  std::vector<DecLayer> layers; Attn fin; Norm nfin;
+  Lin up1, up2; Norm upn; std::vector<Lin> hyper; Lin iou[8]; int n_iou = 0;
+  // image state
+  bool has_image = false; int H = 0, W = 0, newh = 0, neww = 0;
+  uint8_t *rs_tmp = nullptr, *rs_dst = nullptr; size_t rs_tmp_cap = 0;
+  int *tab = nullptr; size_t tab_cap = 0; int tabH = -1, tabW = -1, xk = 0, yk = 0; size_t off_xc = 0, off_yb = 0, off_yc = 0;
+  std::vector<int> tab_host;
+  // debug copies of the last chunk
+  float *dbg_sparse = nullptr, *dbg_tokens = nullptr; int dbg_n = 0;
+};
+
+namespace {
+
+#define SCHECK(m, call)                                                                    \
+  do {                                                                                     \
+    hipError_t e_ = (call);                                                                \
+    if (e_ != hipSuccess) {                                                                \
+      (m)->err = std::string(#call) + ": " + hipGetErrorString(e_);                        \
+      return OVM_ERR_HIP;                                                                  \
+    }                                                                                      \
+  } while (0)
+
+#define SK(m, call)                                                                        \
+  do {                                                                                     \
+    int r_ = (call);                                                                       \
+    if (r_ != OVM_OK) {                                                                    \
+      if ((m)->err.empty()) (m)->err = std::string(#call) + " failed (" + std::to_string(r_) + ")"; \
+      return r_;                                                                           \
+    }                                                                                      \
+  } while (0)
+
+template <typename Tp>
+int dalloc(OvmSam* m, Tp** p, size_t count, bool zero = false) {
+  void* q = nullptr;
+  size_t bytes = count * sizeof(Tp);
+  if (bytes == 0) bytes = 16;
+  SCHECK(m, hipMalloc(&q, bytes));
+  m->allocs.push_back(q);
+  if (zero) SCHECK(m, hipMemset(q, 0, bytes));
+  *p = (Tp*)q;
+  return OVM_OK;
+}
+
+struct WMap {
+  std::map<std::string, const OvmTensor*> m;
+  const OvmTensor* get(const std::string& k) const { auto it = m.find(k); return it == m.end() ? nullptr : it->second; }
+};
+
+int64_t numel(const OvmTensor* t) { int64_t n = 1; for (int i = 0; i < t->ndim; ++i) n *= t->shape[i]; return n; }
+
+int host_of(OvmSam* m, const WMap& wm, const std::string& key, int64_t expect, const float** p) {
+  const OvmTensor* t = wm.get(key);
+  if (!t) { m->err = "missing weight: " + key; return OVM_ERR_MISSING_WEIGHT; }
+  if (numel(t) != expect) { m->err = "bad shape for " + key + " (expected " + std::to_string(expect) + " elements)"; return OVM_ERR_SHAPE; }
+  *p = t->data;
+  return OVM_OK;
+}
+
+int upload(OvmSam* m, const float* src, size_t n, float** out) {
+  int r = dalloc(m, out, n); if (r) return r;
+  SCHECK(m, hipMemcpy(*out, src, n * 4, hipMemcpyHostToDevice));
+  return OVM_OK;
+}
+
+int upload_key(OvmSam* m, const WMap& wm, const std::string& key, int64_t expect, float** out) {
+  const float* p; int r = host_of(m, wm, key, expect, &p); if (r) return r;
+  return upload(m, p, (size_t)expect, out);
+}
+
+// host [N][K] fp32 (GEMM k-order) -> the packed fp16 image ovm_g_linear / launch_gemm stream (ovm_g_pack_weight)
+int pack(OvmSam* m, const float* w, int N, int K, const float* bias, Lin* out) {
+  const int Kpad = (K + 63) / 64 * 64, Npad = (N + 127) / 128 * 128;
+  const bool split = m->cfg.precision == 3;
+  float* tmp = nullptr;
+  SCHECK(m, hipMalloc((void**)&tmp, (size_t)N * K * 4));
+  hipError_t e = hipMemcpy(tmp, w, (size_t)N * K * 4, hipMemcpyHostToDevice);
+  int r = e == hipSuccess ? dalloc(m, &out->hi, (size_t)Npad * Kpad * (split ? 2 : 1)) : OVM_ERR_HIP;
+  if (!r) {
+    out->lo = split ? out->hi + 32 : nullptr;
+    r = ovm_g_pack_weight(tmp, N, K, Kpad, (uint16_t*)out->hi, (uint16_t*)out->lo, nullptr);
+    if (!r && hipDeviceSynchronize() != hipSuccess) r = OVM_ERR_HIP;
+  }
+  (void)hipFree(tmp);
+  if (r) { if (m->err.empty()) m->err = "weight packing failed"; return r; }
+  out->N = N; out->K = K; out->Kpad = Kpad; out->bias = nullptr;
+  if (bias) return upload(m, bias, (size_t)N, &out->bias);
+  return OVM_OK;
+}
+
+int pack_linear(OvmSam* m, const WMap& wm, const std::string& prefix, int N, int K, Lin* out) {
+  const float *w, *b;
+  int r = host_of(m, wm, prefix + ".weight", (int64_t)N * K, &w); if (r) return r;
+  r = host_of(m, wm, prefix + ".bias", N, &b); if (r) return r;
+  return pack(m, w, N, K, b, out);
+}
+
+int pack_attn(OvmSam* m, const WMap& wm, const std::string& prefix, int C, int I, Attn* a) {
+  int r = pack_linear(m, wm, prefix + ".q_proj", I, C, &a->q); if (r) return r;
+  r = pack_linear(m, wm, prefix + ".k_proj", I, C, &a->k); if (r) return r;
+  r = pack_linear(m, wm, prefix + ".v_proj", I, C, &a->v); if (r) return r;
+  return pack_linear(m, wm, prefix + ".out_proj", C, I, &a->o);
+}
+
+int load_norm(OvmSam* m, const WMap& wm, const std::string& prefix, int D, Norm* n) {
+  int r = upload_key(m, wm, prefix + ".weight", D, &n->g); if (r) return r;
+  return upload_key(m, wm, prefix + ".bias", D, &n->b);
+}
+
+// ConvTranspose2d k2 s2 weight [Cin][Cout][2][2] -> GEMM rows [(a * 2 + b) * Cout + co][ci], bias tiled over the four taps
+int pack_convt(OvmSam* m, const WMap& wm, const std::string& prefix, int Cin, int Cout, Lin* out) {
+  const float *w, *b;
+  int r = host_of(m, wm, prefix + ".weight", (int64_t)Cin * Cout * 4, &w); if (r) return r;
+  r = host_of(m, wm, prefix + ".bias", Cout, &b); if (r) return r;
+  std::vector<float> v((size_t)4 * Cout * Cin), bb((size_t)4 * Cout);
+  for (int ci = 0; ci < Cin; ++ci)
+    for (int co = 0; co < Cout; ++co)
+      for (int q = 0; q < 4; ++q) v[((size_t)q * Cout + co) * Cin + ci] = w[((size_t)ci * Cout + co) * 4 + q];
+  for (int q = 0; q < 4; ++q) memcpy(&bb[(size_t)q * Cout], b, (size_t)Cout * 4);
+  return pack(m, v.data(), 4 * Cout, Cin, bb.data(), out);
+}
+
+inline dim3 g1(long n, int bs = 256) { return dim3((unsigned)((n + bs - 1) / bs)); }
+
+// ---- kernels ---------------------------------------------------------------------------------------------------------------------
+
+// out[i] = a[i] + b[i % bmod]
+__global__ void sam_add_bcast_kernel(const float4* __restrict__ a, const float4* __restrict__ b, float4* __restrict__ out, long n4, long bmod4) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n4) return;
+  const float4 x = a[i], y = b[i % bmod4];
+  out[i] = make_float4(x.x + y.x, x.y + y.y, x.z + y.z, x.w + y.w);
+}
+
+// out[i] = b[i % bmod]
+__global__ void sam_bcast_kernel(const float4* __restrict__ b, float4* __restrict__ out, long n4, long bmod4) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n4) return;
+  out[i] = b[i % bmod4];
+}
+
+// PositionEmbeddingRandom._pe_encoding of a point in [0, 1]^2: [sin | cos](2 pi ((2 c - 1) . gauss)), F = C / 2 frequencies
+__device__ __forceinline__ void pe_encode(float cx, float cy, const float* __restrict__ gauss, int F, int f, float* s, float* c) {
+  const float x = 2.f * cx - 1.f, y = 2.f * cy - 1.f;
+  const float v = 6.283185307179586f * (x * gauss[f] + y * gauss[F + f]);
+  *s = sinf(v); *c = cosf(v);
+}
+
+// get_dense_pe: pe[(i * G + j)][:] for the cell centres ((j + 0.5) / G, (i + 0.5) / G)
+__global__ void sam_dense_pe_kernel(const float* __restrict__ gauss, int G, int F, float* __restrict__ pe) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= G * G * F) return;
+  const int f = idx % F, p = idx / F, i = p / G, j = p - i * G;
+  float s, c;
+  pe_encode(((float)(j + 1) - 0.5f) / (float)G, ((float)(i + 1) - 0.5f) / (float)G, gauss, F, f, &s, &c);
+  pe[(size_t)p * 2 * F + f] = s; pe[(size_t)p * 2 * F + F + f] = c;
+}
+
+// tokens of one chunk: tok[b] = [iou_token, mask_tokens, corner 0, corner 1] with corner k = PE of the box corner (original pixels
+// -> ResizeLongestSide's frame: * new / old in fp64 as apply_coords, then + 0.5 and / S in fp32 as _embed_boxes) + point_embeddings[2 + k]
+__global__ void sam_box_tokens_kernel(const float* __restrict__ boxes, int nb, int nout, int C, const float* __restrict__ out_tokens,
+                                      const float* __restrict__ gauss, const float* __restrict__ corner, double sx, double sy, float S,
+                                      float* __restrict__ tok, float* __restrict__ sparse) {
+  const int nt = nout + 2, F = C / 2;
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long)nb * nt * F) return;
+  const int f = (int)(idx % F), t = (int)((idx / F) % nt), b = (int)(idx / ((long)F * nt));
+  float* o = tok + ((size_t)b * nt + t) * C;
+  if (t < nout) { o[f] = out_tokens[(size_t)t * C + f]; o[F + f] = out_tokens[(size_t)t * C + F + f]; return; }
+  const int k = t - nout;
+  const float px = (float)((double)boxes[b * 4 + 2 * k] * sx), py = (float)((double)boxes[b * 4 + 2 * k + 1] * sy);
+  float s, c;
+  pe_encode((px + 0.5f) / S, (py + 0.5f) / S, gauss, F, f, &s, &c);
+  s += corner[(size_t)k * C + f]; c += corner[(size_t)k * C + F + f];
+  o[f] = s; o[F + f] = c;
+  float* sp = sparse + ((size_t)b * 2 + k) * C;
+  sp[f] = s; sp[F + f] = c;
+}
+
+// rows of D channels: x = GELU(LayerNorm(x)), in place; one wave per row (D <= 256)
+__global__ __launch_bounds__(256) void sam_ln_gelu_kernel(float* __restrict__ x, long M, int D, const float* __restrict__ g,
+                                                          const float* __restrict__ b, float eps) {
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= M) return;
+  float* xr = x + (size_t)row * D;
+  float v[4]; float s = 0.f;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) { const int j = lane + 64 * t; v[t] = j < D ? xr[j] : 0.f; s += v[t]; }
+  const float mean = wave_sum(s) / (float)D;
+  float q = 0.f;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) { const int j = lane + 64 * t; const float d = j < D ? v[t] - mean : 0.f; q += d * d; }
+  const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + eps);
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int j = lane + 64 * t;
+    if (j < D) { const float y = (v[t] - mean) * rstd * g[j] + b[j]; xr[j] = 0.5f * y * (1.0f + erff(y * 0.70710678118654752440f)); }
+  }
+}
+
+// Image -> token cross attention. q [nb * G2][ldq] (heads x DH columns), k / v [nb * nt][ld] -> o [nb * G2][ldo]. One thread per
+// (pixel, head): its DH query values in registers, the box's nt keys and values in LDS, softmax over nt in registers. A workgroup
+// of 256 threads covers 256 / heads consecutive pixels of ONE box (G2 % (256 / heads) == 0 is checked by the launcher).
+template <int DH>
+__global__ __launch_bounds__(256) void sam_i2t_attn_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ k, const float* __restrict__ v,
+                                                           int ld, int nt, int heads, int G2, long rows, float scale, float* __restrict__ o, int ldo) {
+  __shared__ float ks[kMaxTok * 256], vs[kMaxTok * 256];
+  const int ppb = 256 / heads;                                  // pixels per workgroup
+  const long row0 = (long)blockIdx.x * ppb;
+  const int box = (int)(row0 / G2), width = heads * DH;
+  for (int i = threadIdx.x; i < nt * width; i += 256) {
+    const int t = i / width, c = i - t * width;
+    ks[i] = k[((size_t)box * nt + t) * ld + c]; vs[i] = v[((size_t)box * nt + t) * ld + c];
+  }
+  __syncthreads();
+  const int h = threadIdx.x % heads;
+  const long row = row0 + threadIdx.x / heads;
+  if (row >= rows) return;
+  float qr[DH];
+  const float4* qp = reinterpret_cast<const float4*>(q + (size_t)row * ldq + h * DH);
+#pragma unroll
+  for (int d = 0; d < DH / 4; ++d) { const float4 t4 = qp[d]; qr[4 * d] = t4.x; qr[4 * d + 1] = t4.y; qr[4 * d + 2] = t4.z; qr[4 * d + 3] = t4.w; }
+  float sc[kMaxTok]; float mx = -INFINITY;
+#pragma unroll
+  for (int t = 0; t < kMaxTok; ++t) {
+    float a = 0.f;
+    if (t < nt) {
+      const float* kr = ks + t * width + h * DH;
+#pragma unroll
+      for (int d = 0; d < DH; ++d) a = fmaf(qr[d], kr[d], a);
+      a *= scale; mx = fmaxf(mx, a);
+    }
+    sc[t] = a;
+  }
+  float sum = 0.f;
+#pragma unroll
+  for (int t = 0; t < kMaxTok; ++t) { sc[t] = t < nt ? expf(sc[t] - mx) : 0.f; sum += sc[t]; }
+  const float inv = 1.0f / sum;
+  float acc[DH];
+#pragma unroll
+  for (int d = 0; d < DH; ++d) acc[d] = 0.f;
+#pragma unroll
+  for (int t = 0; t < kMaxTok; ++t)
+    if (t < nt) {
+      const float p = sc[t] * inv; const float* vr = vs + t * width + h * DH;
+#pragma unroll
+      for (int d = 0; d < DH; ++d) acc[d] = fmaf(p, vr[d], acc[d]);
+    }
+  float4* op = reinterpret_cast<float4*>(o + (size_t)row * ldo + h * DH);
+#pragma unroll
+  for (int d = 0; d < DH / 4; ++d) op[d] = make_float4(acc[4 * d], acc[4 * d + 1], acc[4 * d + 2], acc[4 * d + 3]);
+}
+
+// masks[b][t][Y][X] = hyper[b][t0 + t][:] . up[b][Y][X][:] over the blocked upscaled map (layout: file header). One thread per
+// (up-row r, tap q2): 128 contiguous bytes of `up` for C8 = 32.
+__global__ void sam_mask_prod_kernel(const float* __restrict__ up, const float* __restrict__ hyper, int ld_hyper /* floats per box */, int t0, int ntk,
+                                     int C8, int G, long total, float* __restrict__ out, long out_box_stride) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const int q2 = (int)(idx & 3); const long r = idx >> 2;            // r = (box * G2 + i * G + j) * 4 + q1
+  const int q1 = (int)(r & 3); const long pix = r >> 2;
+  const int G2 = G * G; const int box = (int)(pix / G2), p = (int)(pix - (long)box * G2), i = p / G, j = p - i * G;
+  const int Y = 4 * i + 2 * (q1 >> 1) + (q2 >> 1), X = 4 * j + 2 * (q1 & 1) + (q2 & 1), L = 4 * G;
+  const float4* u = reinterpret_cast<const float4*>(up + (size_t)idx * C8);
+  for (int t = 0; t < ntk; ++t) {
+    const float4* hy = reinterpret_cast<const float4*>(hyper + (size_t)box * ld_hyper + (size_t)(t0 + t) * C8);
+    float a = 0.f;
+    for (int c = 0; c < C8 / 4; ++c) { const float4 x = u[c], w = hy[c]; a = fmaf(x.x, w.x, a); a = fmaf(x.y, w.y, a); a = fmaf(x.z, w.z, a); a = fmaf(x.w, w.w, a); }
+    out[(size_t)box * out_box_stride + (size_t)t * L * L + (size_t)Y * L + X] = a;
+  }
+}
+
+// torch's bilinear source index, align_corners = False: scale = in / out (fp32), src = max(scale * (dst + 0.5) - 0.5, 0)
+__device__ __forceinline__ void bil_tap(int dst, float scale, int in, int* i0, int* i1, float* l1) {
+  float src = scale * ((float)dst + 0.5f) - 0.5f;
+  if (src < 0.f) src = 0.f;
+  const int a = (int)src;
+  *i0 = a; *i1 = a + (a < in - 1 ? 1 : 0); *l1 = src - (float)a;
+}
+
+// the S x S plane of postprocess_masks at (Y, X), from the L x L logits
+__device__ __forceinline__ float up_sample(const float* __restrict__ lg, int L, float sc1, int Y, int X) {
+  int y0, y1, x0, x1; float ly, lx;
+  bil_tap(Y, sc1, L, &y0, &y1, &ly); bil_tap(X, sc1, L, &x0, &x1, &lx);
+  const float a = lg[y0 * L + x0], b = lg[y0 * L + x1], c = lg[y1 * L + x0], d = lg[y1 * L + x1];
+  return (1.f - ly) * ((1.f - lx) * a + lx * b) + ly * ((1.f - lx) * c + lx * d);
+}
+
+__device__ __forceinline__ uint8_t mask_pixel(const float* __restrict__ lg, int L, float sc1, int newh, int neww, float sch, float scw, int y, int x) {
+  int y0, y1, x0, x1; float ly, lx;
+  bil_tap(y, sch, newh, &y0, &y1, &ly); bil_tap(x, scw, neww, &x0, &x1, &lx);
+  const float a = up_sample(lg, L, sc1, y0, x0), b = up_sample(lg, L, sc1, y0, x1), c = up_sample(lg, L, sc1, y1, x0), d = up_sample(lg, L, sc1, y1, x1);
+  const float vv = (1.f - ly) * ((1.f - lx) * a + lx * b) + ly * ((1.f - lx) * c + lx * d);
+  return vv > 0.f ? 1 : 0;
+}
+
+// postprocess_masks + `> mask_threshold (0)`: F.interpolate(L -> S) . [:newh, :neww] . F.interpolate(-> H x W), per output pixel.
+// Four consecutive output bytes per thread, one 32-bit store where the address allows it.
+__global__ void sam_mask_out_kernel(const float* __restrict__ logits, long box_stride, int L, int S, int newh, int neww, int H, int W, long total,
+                                    uint8_t* __restrict__ out) {
+  const long i4 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (i4 >= total) return;
+  const float sc1 = (float)L / (float)S, sch = (float)newh / (float)H, scw = (float)neww / (float)W;
+  const long HW = (long)H * W;
+  uint32_t packed = 0; uint8_t px[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const long i = i4 + e;
+    px[e] = 0;
+    if (i < total) {
+      const int b = (int)(i / HW); const long r = i - (long)b * HW; const int y = (int)(r / W), x = (int)(r - (long)y * W);
+      px[e] = mask_pixel(logits + (size_t)b * box_stride, L, sc1, newh, neww, sch, scw, y, x);
+    }
+    packed |= (uint32_t)px[e] << (8 * e);
+  }
+  if (i4 + 3 < total && (((uintptr_t)(out + i4)) & 3) == 0) *reinterpret_cast<uint32_t*>(out + i4) = packed;
+  else for (int e = 0; e < 4 && i4 + e < total; ++e) out[i4 + e] = px[e];
+}
+
+// the encoder's input image back from its patch rows: out[c][y][x], S = G * P
+__global__ void sam_unpatch_kernel(const half_t* __restrict__ hi, const half_t* __restrict__ lo, int ld, int G, int P, float* __restrict__ out) {
+  const int S = G * P; const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long)3 * S * S) return;
+  const int x = (int)(idx % S), y = (int)((idx / S) % S), c = (int)(idx / ((long)S * S));
+  const size_t o = (size_t)((y / P) * G + x / P) * ld + (size_t)((y % P) * P + x % P) * 3 + c;
+  out[idx] = (float)hi[o] + (lo ? (float)lo[o] : 0.f);
+}
+
+// iou[b][0:3] = head[b][1:4]
+__global__ void sam_iou_slice_kernel(const float* __restrict__ head, int ldh, int n, float* __restrict__ iou) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * 3) return;
+  iou[i] = head[(size_t)(i / 3) * ldh + 1 + i % 3];
+}
+
+int last_launch() { return hipGetLastError() == hipSuccess ? OVM_OK : OVM_ERR_HIP; }
+
+int lin(OvmSam* m, const Lin& w, const float* x, int ldx, long M, int act, const float* res, int ldr, float* y, int ldy, hipStream_t s) {
+  return ovm_g_linear(x, ldx, (int)M, w.K, (const uint16_t*)w.hi, (const uint16_t*)w.lo, w.N, w.Kpad, w.bias, act, res, ldr, y, ldy, m->cfg.precision, s);
+}
+
+int add_bcast(const float* a, const float* b, float* out, long n, long bmod, hipStream_t s) {
+  hipLaunchKernelGGL(sam_add_bcast_kernel, g1(n / 4), dim3(256), 0, s, (const float4*)a, (const float4*)b, (float4*)out, n / 4, bmod / 4);
+  return last_launch();
+}
+
+// token queries [nb * nt][I] against Tk keys per box: scores (bmm) -> softmax -> context (bmm); heads x dh = I
+int token_attention(OvmSam* m, const float* Q, const float* K, const float* V, int nb, int Tk, int I, float* scores, float* ctx, hipStream_t s) {
+  const int nt = m->nt, hd = m->cfg.dec_heads, dh = I / hd;
+  SK(m, ovm_g_bmm2(Q, K, scores, nb, hd, nt, Tk, dh, I, I, Tk, (int64_t)nt * I, (int64_t)Tk * I, (int64_t)hd * nt * Tk, dh, dh, (int64_t)nt * Tk, 1,
+                   1.0f / sqrtf((float)dh), s));
+  SK(m, ovm_g_softmax(scores, nb * hd * nt, Tk, Tk, nullptr, 0, 0, 0, s));
+  SK(m, ovm_g_bmm2(scores, V, ctx, nb, hd, nt, dh, Tk, Tk, I, I, (int64_t)hd * nt * Tk, (int64_t)Tk * I, (int64_t)nt * I, (int64_t)nt * Tk, dh, dh, 0, 1.0f, s));
+  return OVM_OK;
+}
+
+struct Work {                       // one chunk's buffers, carved from the caller's workspace
+  float *tok0, *q, *qpe, *tq, *tk, *tv, *tctx, *tout, *mlp, *keys, *kpe, *tmp, *iA, *iB, *scores, *up2, *hyp, *h1, *h2, *iouh, *low;
+};
+
+size_t carve(Work* w, char* base, const OvmSam* m, long nb) {
+  const size_t C = m->C, nt = m->nt, G2 = m->G2, I = m->I, Mt = (size_t)nb * nt, Mi = (size_t)nb * G2;
+  const size_t hid = m->cfg.iou_hidden > m->C ? m->cfg.iou_hidden : m->C;
+  size_t off = 0;
+  auto take = [&](float** p, size_t floats) { if (w) *p = (float*)(base + off); off += (floats * 4 + 255) / 256 * 256; };
+  Work dummy; Work* x = w ? w : &dummy;
+  take(&x->tok0, Mt * C); take(&x->q, Mt * C); take(&x->qpe, Mt * C); take(&x->tq, Mt * C); take(&x->tk, Mt * C); take(&x->tv, Mt * C);
+  take(&x->tctx, Mt * C); take(&x->tout, Mt * C); take(&x->mlp, Mt * m->cfg.dec_mlp);
+  take(&x->keys, Mi * C); take(&x->kpe, Mi * C); take(&x->tmp, Mi * C); take(&x->iA, Mi * I); take(&x->iB, Mi * I);
+  take(&x->scores, (size_t)nb * m->cfg.dec_heads * nt * G2);
+  take(&x->up2, Mi * 2 * C);                                        // [nb * G2 * 4][4 * C / 8]
+  take(&x->hyp, (size_t)nb * m->cfg.num_mask_tokens * (C / 8)); take(&x->h1, (size_t)nb * hid); take(&x->h2, (size_t)nb * hid);
+  take(&x->iouh, (size_t)nb * 128); take(&x->low, (size_t)nb * m->L * m->L);
+  return off;
+}
+
+int decode_chunk(OvmSam* m, const float* boxes, int nb, int mask_index, uint8_t* masks, float* iou, float* lowres, const Work& w, hipStream_t s) {
+  const OvmSamConfig& c = m->cfg;
+  const int C = m->C, nt = m->nt, G2 = m->G2, I = m->I, nout = 1 + c.num_mask_tokens;
+  const long Mt = (long)nb * nt, Mi = (long)nb * G2;
+  // 1. tokens + sparse embeddings; src = (embedding + no_mask_embed) per box
+  hipLaunchKernelGGL(sam_box_tokens_kernel, g1(Mt * (C / 2)), dim3(256), 0, s, boxes, nb, nout, C, m->out_tokens, m->gauss, m->corner,
+                     (double)m->neww / (double)m->W, (double)m->newh / (double)m->H, (float)m->S, w.tok0, m->dbg_sparse);
+  SK(m, last_launch());
+  SCHECK(m, hipMemcpyAsync(w.q, w.tok0, (size_t)Mt * C * 4, hipMemcpyDeviceToDevice, s));
+  hipLaunchKernelGGL(sam_bcast_kernel, g1(Mi * C / 4), dim3(256), 0, s, (const float4*)m->src0, (float4*)w.keys, Mi * C / 4, (long)G2 * C / 4);
+  SK(m, last_launch());
+  auto norm = [&](const Norm& n, const float* x, long M, float* y) { return ovm_g_layernorm(x, nullptr, (int)M, C, n.g, n.b, kDecEps, y, s); };
+  // token -> image attention of one block (also the final one): q += out_proj(attn(q + pe_q, keys + pe_k, keys)), then the norm
+  auto tok_to_img = [&](const Attn& a, const Norm& n) -> int {
+    SK(m, add_bcast(w.q, w.tok0, w.qpe, Mt * C, Mt * C, s));
+    SK(m, add_bcast(w.keys, m->pe, w.kpe, Mi * C, (long)G2 * C, s));
+    SK(m, lin(m, a.q, w.qpe, C, Mt, 0, nullptr, 0, w.tq, I, s));
+    SK(m, lin(m, a.k, w.kpe, C, Mi, 0, nullptr, 0, w.iA, I, s));
+    SK(m, lin(m, a.v, w.keys, C, Mi, 0, nullptr, 0, w.iB, I, s));
+    SK(m, token_attention(m, w.tq, w.iA, w.iB, nb, G2, I, w.scores, w.tctx, s));
+    SK(m, lin(m, a.o, w.tctx, I, Mt, 0, w.q, C, w.tout, C, s));
+    return norm(n, w.tout, Mt, w.q);
+  };
+  for (int l = 0; l < c.dec_depth; ++l) {
+    const DecLayer& y = m->layers[l];
+    // self attention (layer 0: no positional encoding, and the output REPLACES the tokens)
+    const float* qin = w.q;
+    if (l > 0) { SK(m, add_bcast(w.q, w.tok0, w.qpe, Mt * C, Mt * C, s)); qin = w.qpe; }
+    SK(m, lin(m, y.self.q, qin, C, Mt, 0, nullptr, 0, w.tq, C, s));
+    SK(m, lin(m, y.self.k, qin, C, Mt, 0, nullptr, 0, w.tk, C, s));
+    SK(m, lin(m, y.self.v, w.q, C, Mt, 0, nullptr, 0, w.tv, C, s));
+    SK(m, token_attention(m, w.tq, w.tk, w.tv, nb, nt, C, w.scores, w.tctx, s));
+    SK(m, lin(m, y.self.o, w.tctx, C, Mt, 0, l > 0 ? w.q : nullptr, C, w.tout, C, s));
+    SK(m, norm(y.n1, w.tout, Mt, w.q));
+    SK(m, tok_to_img(y.t2i, y.n2));
+    // MLP
+    SK(m, lin(m, y.lin1, w.q, C, Mt, 1, nullptr, 0, w.mlp, c.dec_mlp, s));
+    SK(m, lin(m, y.lin2, w.mlp, c.dec_mlp, Mt, 0, w.q, C, w.tout, C, s));
+    SK(m, norm(y.n3, w.tout, Mt, w.q));
+    // image -> token: the image rows (keys + pe, unchanged since tok_to_img) are the queries
+    SK(m, add_bcast(w.q, w.tok0, w.qpe, Mt * C, Mt * C, s));
+    SK(m, lin(m, y.i2t.q, w.kpe, C, Mi, 0, nullptr, 0, w.iA, I, s));
+    SK(m, lin(m, y.i2t.k, w.qpe, C, Mt, 0, nullptr, 0, w.tk, I, s));
+    SK(m, lin(m, y.i2t.v, w.q, C, Mt, 0, nullptr, 0, w.tv, I, s));
+    hipLaunchKernelGGL(sam_i2t_attn_kernel<16>, dim3((unsigned)(Mi / (256 / c.dec_heads))), dim3(256), 0, s, w.iA, I, w.tk, w.tv, I, nt, c.dec_heads, G2, Mi,
+                       0.25f, w.iB, I);
+    SK(m, last_launch());
+    SK(m, lin(m, y.i2t.o, w.iB, I, Mi, 0, w.keys, C, w.tmp, C, s));
+    SK(m, norm(y.n4, w.tmp, Mi, w.keys));
+  }
+  SK(m, tok_to_img(m->fin, m->nfin));
+  SCHECK(m, hipMemcpyAsync(m->dbg_tokens, w.q, (size_t)Mt * C * 4, hipMemcpyDeviceToDevice, s));
+  m->dbg_n = nb;
+  // 4. upscaling: ConvT . LayerNorm2d . GELU . ConvT . GELU as GEMMs over source pixels (blocked layout: file header)
+  const int C4 = C / 4, C8 = C / 8;
+  SK(m, lin(m, m->up1, w.keys, C, Mi, 0, nullptr, 0, w.tmp, C, s));
+  hipLaunchKernelGGL(sam_ln_gelu_kernel, dim3((unsigned)((Mi * 4 + 3) / 4)), dim3(256), 0, s, w.tmp, Mi * 4, C4, m->upn.g, m->upn.b, kLn2dEps);
+  SK(m, last_launch());
+  SK(m, lin(m, m->up2, w.tmp, C4, Mi * 4, 2, nullptr, 0, w.up2, 4 * C8, s));
+  // hypernetwork MLPs (every mask token when the low-resolution logits are asked for, else the requested one) and the IoU head
+  const int t_first = lowres ? 0 : 1 + mask_index, t_last = lowres ? c.num_mask_tokens : 2 + mask_index;
+  for (int t = t_first; t < t_last; ++t) {
+    const Lin* hl = &m->hyper[(size_t)t * 3];
+    SK(m, lin(m, hl[0], w.q + (size_t)(1 + t) * C, nt * C, nb, 1, nullptr, 0, w.h1, C, s));
+    SK(m, lin(m, hl[1], w.h1, C, nb, 1, nullptr, 0, w.h2, C, s));
+    SK(m, lin(m, hl[2], w.h2, C, nb, 0, nullptr, 0, w.hyp + (size_t)t * C8, c.num_mask_tokens * C8, s));
+  }
+  {
+    const float* x = w.q; int ldx = nt * C; float* bufs[2] = {w.h1, w.h2};
+    for (int i = 0; i < m->n_iou; ++i) {
+      const bool last = i + 1 == m->n_iou;
+      float* y = last ? w.iouh : bufs[i & 1]; const int ldy = last ? 128 : c.iou_hidden;
+      SK(m, lin(m, m->iou[i], x, ldx, nb, last ? 0 : 1, nullptr, 0, y, ldy, s));
+      x = y; ldx = ldy;
+    }
+    if (iou) { hipLaunchKernelGGL(sam_iou_slice_kernel, g1(nb * 3), dim3(256), 0, s, w.iouh, 128, nb, iou); SK(m, last_launch()); }
+  }
+  // mask product: multimask slice 1:4 into `lowres`, or the requested token alone into the workspace
+  const long LL = (long)m->L * m->L;
+  float* planes = lowres ? lowres : w.low; const long stride = lowres ? 3 * LL : LL;
+  hipLaunchKernelGGL(sam_mask_prod_kernel, g1(Mi * 16), dim3(256), 0, s, w.up2, w.hyp, c.num_mask_tokens * C8, lowres ? 1 : 1 + mask_index, lowres ? 3 : 1, C8, m->G,
+                     Mi * 16, planes, stride);
+  SK(m, last_launch());
+  // 5. postprocess_masks + threshold
+  const long total = (long)nb * m->H * m->W;
+  hipLaunchKernelGGL(sam_mask_out_kernel, g1((total + 3) / 4), dim3(256), 0, s, planes + (lowres ? (size_t)mask_index * LL : 0), stride, m->L, m->S, m->newh,
+                     m->neww, m->H, m->W, total, masks);
+  return last_launch();
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* ovm_sam_last_error(const OvmSam* m) { return m ? m->err.c_str() : "null handle"; }
+
+int ovm_sam_destroy(OvmSam* m) {
+  if (!m) return OVM_OK;
+  (void)hipSetDevice(m->device);
+  if (m->tower) ovm_destroy(m->tower);
+  for (void* p : m->allocs) (void)hipFree(p);
+  if (m->rs_tmp) (void)hipFree(m->rs_tmp);
+  if (m->tab) (void)hipFree(m->tab);
+  delete m;
+  return OVM_OK;
+}
+
+int ovm_sam_create(const OvmSamConfig* cfg, const OvmTensor* weights, int32_t n_weights, int32_t device, OvmSam** out) {
+  if (!cfg || !out) return OVM_ERR_INVALID;
+  OvmSam* m = new OvmSam();
+  *out = m;
+  m->cfg = *cfg; m->device = device;
+  const OvmSamConfig& c = m->cfg;
+  if (c.heads > 0 && c.embed_dim != c.heads * 64) {
+    m->err = "unsupported image encoder: head dimension " + std::to_string(c.embed_dim / c.heads) + " (embed_dim " + std::to_string(c.embed_dim) +
+             " / " + std::to_string(c.heads) + " heads); the attention kernels take head dimension 64 only (vit_b, vit_l; vit_h has 80)";
+    return OVM_ERR_UNSUPPORTED;
+  }
+  m->C = c.prompt_dim; m->S = c.image_size; m->nt = 1 + c.num_mask_tokens + 2;
+  if (c.heads < 1 || c.patch != 16 || c.image_size < 16 || c.image_size % 16 != 0 || c.prompt_dim < 64 || c.prompt_dim % 64 != 0 || c.prompt_dim > 256 ||
+      c.dec_depth < 1 || c.dec_heads < 1 || c.attn_downsample < 1 || c.prompt_dim % (c.attn_downsample * c.dec_heads) != 0 ||
+      c.prompt_dim / c.attn_downsample / c.dec_heads != 16 || 256 % c.dec_heads != 0 || c.num_mask_tokens != 4 || m->nt > kMaxTok || c.iou_depth < 2 ||
+      c.iou_depth > 8 || c.iou_hidden < 4 || c.iou_hidden % 4 != 0 || c.dec_mlp % 64 != 0 || (c.precision != 1 && c.precision != 3) || c.max_boxes < 1) {
+    m->err = "invalid config (patch 16, image_size % 16, prompt_dim % 64 and <= 256, cross-attention head dimension 16, 4 mask tokens, precision in {1,3}, max_boxes >= 1)";
+    return OVM_ERR_INVALID;
+  }
+  m->G = c.image_size / c.patch; m->G2 = m->G * m->G; m->L = 4 * m->G; m->I = c.prompt_dim / c.attn_downsample;
+  if (m->G2 % (256 / c.dec_heads) != 0) { m->err = "invalid config (grid cells must fill whole workgroups of the image -> token kernel)"; return OVM_ERR_INVALID; }
+  SCHECK(m, hipSetDevice(device));
+  {
+    OvmConfig t; memset(&t, 0, sizeof(t));
+    t.embed_dim = c.embed_dim; t.depth = c.depth; t.heads = c.heads; t.pos_grid = c.pos_grid; t.canvas = c.image_size; t.fpn_channels = 256;
+    for (int i = 0; i < 3; ++i) { t.pixel_mean[i] = c.pixel_mean[i]; t.pixel_std[i] = c.pixel_std[i]; }
+    t.pooler_res = 1; t.precision = c.precision; t.max_batch = 1; t.max_rois = 1; t.tower = OVM_TOWER_SAM; t.sam_window = c.window;
+    t.sam_global_mask = c.global_mask;
+    const int r = tower_create(&t, weights, n_weights, device, "image_encoder.", &m->tower);
+    if (r) { m->err = std::string("image encoder: ") + ovm_last_error(m->tower); return r; }
+  }
+  WMap wm;
+  for (int i = 0; i < n_weights; ++i) wm.m[weights[i].name] = &weights[i];
+  const int C = m->C, D = c.embed_dim, G = m->G, G2 = m->G2, I = m->I;
+  int r;
+  // ---- neck: conv1x1 (no bias) . LayerNorm2d . conv3x3 (no bias, pad 1) . LayerNorm2d
+  {
+    const float* w;
+    if ((r = host_of(m, wm, "image_encoder.neck.0.weight", (int64_t)C * D, &w))) return r;
+    if ((r = pack(m, w, C, D, nullptr, &m->neck1))) return r;
+    if ((r = load_norm(m, wm, "image_encoder.neck.1", C, &m->nn1))) return r;
+    if ((r = host_of(m, wm, "image_encoder.neck.2.weight", (int64_t)C * C * 9, &w))) return r;
+    std::vector<float> v((size_t)C * C * 9);                         // [Cout][Cin][3][3] -> [Cout][(ky * 3 + kx) * Cin + c]
+    for (int o = 0; o < C; ++o)
+      for (int ci = 0; ci < C; ++ci)
+        for (int t = 0; t < 9; ++t) v[((size_t)o * 9 + t) * C + ci] = w[((size_t)o * C + ci) * 9 + t];
+    if ((r = pack(m, v.data(), C, 9 * C, nullptr, &m->neck3))) return r;
+    if ((r = load_norm(m, wm, "image_encoder.neck.3", C, &m->nn3))) return r;
+    const size_t pp = (size_t)(G + 2) * (G + 2) * C;
+    if ((r = dalloc(m, &m->pad_hi, pp, true))) return r;
+    if (c.precision == 3 && (r = dalloc(m, &m->pad_lo, pp, true))) return r;
+    if ((r = dalloc(m, &m->T1, (size_t)G2 * C))) return r;
+    if ((r = dalloc(m, &m->T2, (size_t)G2 * C))) return r;
+    if ((r = dalloc(m, &m->emb, (size_t)G2 * C))) return r;
+    if ((r = dalloc(m, &m->src0, (size_t)G2 * C))) return r;
+    if ((r = dalloc(m, &m->pe, (size_t)G2 * C))) return r;
+  }
+  // ---- prompt encoder (boxes): the Gaussian matrix, the two corner embeddings, no_mask_embed
+  {
+    if ((r = upload_key(m, wm, "prompt_encoder.pe_layer.positional_encoding_gaussian_matrix", (int64_t)2 * (C / 2), &m->gauss))) return r;
+    const float *p2, *p3;
+    if ((r = host_of(m, wm, "prompt_encoder.point_embeddings.2.weight", C, &p2))) return r;
+    if ((r = host_of(m, wm, "prompt_encoder.point_embeddings.3.weight", C, &p3))) return r;
+    std::vector<float> cr((size_t)2 * C);
+    memcpy(cr.data(), p2, (size_t)C * 4); memcpy(cr.data() + C, p3, (size_t)C * 4);
+    if ((r = upload(m, cr.data(), cr.size(), &m->corner))) return r;
+    if ((r = upload_key(m, wm, "prompt_encoder.no_mask_embed.weight", C, &m->no_mask))) return r;
+    hipLaunchKernelGGL(sam_dense_pe_kernel, g1((long)G2 * (C / 2)), dim3(256), 0, nullptr, m->gauss, G, C / 2, m->pe);
+    if ((r = last_launch())) { m->err = "dense positional encoding launch failed"; return r; }
+  }
+  // ---- mask decoder
+  {
+    const std::string Dp = "mask_decoder.";
+    const float *it, *mt;
+    if ((r = host_of(m, wm, Dp + "iou_token.weight", C, &it))) return r;
+    if ((r = host_of(m, wm, Dp + "mask_tokens.weight", (int64_t)c.num_mask_tokens * C, &mt))) return r;
+    std::vector<float> ot((size_t)(1 + c.num_mask_tokens) * C);
+    memcpy(ot.data(), it, (size_t)C * 4); memcpy(ot.data() + C, mt, (size_t)c.num_mask_tokens * C * 4);
+    if ((r = upload(m, ot.data(), ot.size(), &m->out_tokens))) return r;
+    m->layers.resize(c.dec_depth);
+    for (int l = 0; l < c.dec_depth; ++l) {
+      DecLayer& y = m->layers[l];
+      const std::string P = Dp + "transformer.layers." + std::to_string(l) + ".";
+      if ((r = pack_attn(m, wm, P + "self_attn", C, C, &y.self))) return r;
+      if ((r = pack_attn(m, wm, P + "cross_attn_token_to_image", C, I, &y.t2i))) return r;
+      if ((r = pack_attn(m, wm, P + "cross_attn_image_to_token", C, I, &y.i2t))) return r;
+      if ((r = pack_linear(m, wm, P + "mlp.lin1", c.dec_mlp, C, &y.lin1))) return r;
+      if ((r = pack_linear(m, wm, P + "mlp.lin2", C, c.dec_mlp, &y.lin2))) return r;
+      if ((r = load_norm(m, wm, P + "norm1", C, &y.n1))) return r;
+      if ((r = load_norm(m, wm, P + "norm2", C, &y.n2))) return r;
+      if ((r = load_norm(m, wm, P + "norm3", C, &y.n3))) return r;
+      if ((r = load_norm(m, wm, P + "norm4", C, &y.n4))) return r;
+    }
+    if ((r = pack_attn(m, wm, Dp + "transformer.final_attn_token_to_image", C, I, &m->fin))) return r;
+    if ((r = load_norm(m, wm, Dp + "transformer.norm_final_attn", C, &m->nfin))) return r;
+    if ((r = pack_convt(m, wm, Dp + "output_upscaling.0", C, C / 4, &m->up1))) return r;
+    if ((r = load_norm(m, wm, Dp + "output_upscaling.1", C / 4, &m->upn))) return r;
+    if ((r = pack_convt(m, wm, Dp + "output_upscaling.3", C / 4, C / 8, &m->up2))) return r;
+    m->hyper.resize((size_t)c.num_mask_tokens * 3);
+    for (int t = 0; t < c.num_mask_tokens; ++t) {
+      const std::string P = Dp + "output_hypernetworks_mlps." + std::to_string(t) + ".layers.";
+      if ((r = pack_linear(m, wm, P + "0", C, C, &m->hyper[(size_t)t * 3]))) return r;
+      if ((r = pack_linear(m, wm, P + "1", C, C, &m->hyper[(size_t)t * 3 + 1]))) return r;
+      if ((r = pack_linear(m, wm, P + "2", C / 8, C, &m->hyper[(size_t)t * 3 + 2]))) return r;
+    }
+    m->n_iou = c.iou_depth;
+    for (int i = 0; i < c.iou_depth; ++i) {
+      const int in = i == 0 ? C : c.iou_hidden, on = i + 1 == c.iou_depth ? c.num_mask_tokens : c.iou_hidden;
+      if ((r = pack_linear(m, wm, Dp + "iou_prediction_head.layers." + std::to_string(i), on, in, &m->iou[i]))) return r;
+    }
+  }
+  if ((r = dalloc(m, &m->rs_dst, (size_t)c.image_size * c.image_size * 3))) return r;
+  if ((r = dalloc(m, &m->dbg_sparse, (size_t)c.max_boxes * 2 * C, true))) return r;
+  if ((r = dalloc(m, &m->dbg_tokens, (size_t)c.max_boxes * m->nt * C, true))) return r;
+  SCHECK(m, hipDeviceSynchronize());
+  return OVM_OK;
+}
+
+int ovm_sam_set_image(OvmSam* m, const OvmImage* image, int32_t flip_bgr, ovm_stream_t stream) {
+  if (!m) return OVM_ERR_INVALID;
+  m->err.clear();
+  if (!m->tower) { m->err = "handle was not created"; return OVM_ERR_INVALID; }
+  if (!image || !image->data || image->height < 1 || image->width < 1) { m->err = "null or empty image"; return OVM_ERR_INVALID; }
+  hipStream_t s = (hipStream_t)stream;
+  SCHECK(m, hipSetDevice(m->device));
+  const OvmSamConfig& c = m->cfg;
+  const int H = image->height, W = image->width, S = m->S, G = m->G, G2 = m->G2, C = m->C;
+  // ResizeLongestSide.get_preprocess_shape
+  const double scale = (double)S / (double)(H > W ? H : W);
+  const int newh = (int)((double)H * scale + 0.5), neww = (int)((double)W * scale + 0.5);
+  if (newh < 1 || neww < 1 || newh > S || neww > S) { m->err = "image too elongated for ResizeLongestSide"; return OVM_ERR_SHAPE; }
+  m->has_image = false;
+  const bool need_h = neww != W, need_v = newh != H;
+  if (m->tabH != H || m->tabW != W) {
+    SCHECK(m, hipStreamSynchronize(s));                  // the previous tables may still be in use / in flight
+    const int xk = ovm_host_pil_bilinear_coeffs(W, neww, nullptr, nullptr, 0), yk = ovm_host_pil_bilinear_coeffs(H, newh, nullptr, nullptr, 0);
+    if (xk < 1 || yk < 1) { m->err = "resize coefficient size query failed"; return OVM_ERR_INVALID; }
+    m->xk = xk; m->yk = yk;
+    m->off_xc = (size_t)2 * neww; m->off_yb = m->off_xc + (size_t)neww * xk; m->off_yc = m->off_yb + (size_t)2 * newh;
+    const size_t n = m->off_yc + (size_t)newh * yk;
+    m->tab_host.assign(n, 0);
+    if (ovm_host_pil_bilinear_coeffs(W, neww, m->tab_host.data(), m->tab_host.data() + m->off_xc, neww * xk) < 0 ||
+        ovm_host_pil_bilinear_coeffs(H, newh, m->tab_host.data() + m->off_yb, m->tab_host.data() + m->off_yc, newh * yk) < 0) {
+      m->err = "resize coefficients failed"; return OVM_ERR_INVALID;
+    }
+    if (n > m->tab_cap) {
+      if (m->tab) (void)hipFree(m->tab);
+      m->tab = nullptr; m->tab_cap = 0;
+      SCHECK(m, hipMalloc((void**)&m->tab, n * sizeof(int)));
+      m->tab_cap = n;
+    }
+    SCHECK(m, hipMemcpy(m->tab, m->tab_host.data(), n * sizeof(int), hipMemcpyHostToDevice));
+    const size_t tmp_need = (size_t)H * neww * 3;
+    if (tmp_need > m->rs_tmp_cap) {
+      if (m->rs_tmp) (void)hipFree(m->rs_tmp);
+      m->rs_tmp = nullptr; m->rs_tmp_cap = 0;
+      SCHECK(m, hipMalloc((void**)&m->rs_tmp, tmp_need));
+      m->rs_tmp_cap = tmp_need;
+    }
+    m->tabH = H; m->tabW = W;
+  }
+  {
+    const int r = ovm_resize_bilinear_u8(image->data, H, W, 3, image->stride_h, image->stride_w, image->stride_c, newh, neww, need_h ? m->tab : nullptr,
+                                         need_h ? m->tab + m->off_xc : nullptr, m->xk, need_v ? m->tab + m->off_yb : nullptr,
+                                         need_v ? m->tab + m->off_yc : nullptr, m->yk, m->rs_tmp, m->rs_dst, s);
+    if (r) { m->err = "resize failed (an image whose width is not resized must be dense [H][W][3])"; return r; }
+  }
+  // encoder: (x - mean) / std and the zero padding to S x S happen in the tower's patch gather; a channel flip is a negative stride
+  OvmImage net; memset(&net, 0, sizeof(net));
+  net.data = m->rs_dst + (flip_bgr ? 2 : 0); net.height = newh; net.width = neww;
+  net.stride_c = flip_bgr ? -1 : 1; net.stride_h = (int64_t)3 * neww; net.stride_w = 3;
+  net.orig_height = H; net.orig_width = W;
+  {
+    const int r = tower_forward(m->tower, &net, s);
+    if (r) { m->err = std::string("image encoder: ") + ovm_last_error(m->tower); return r; }
+  }
+  // neck
+  SK(m, lin(m, m->neck1, tower_tokens(m->tower), c.embed_dim, G2, 0, nullptr, 0, m->T1, C, s));
+  {
+    LnOut o; memset(&o, 0, sizeof(o));
+    o.hi = m->pad_hi; o.lo = m->pad_lo; o.ld = C; o.padH = G; o.padW = G;
+    SK(m, launch_ln_rows(m->T1, C, G2, C, m->nn1.g, m->nn1.b, kLn2dEps, o, s));
+    GemmParams q; memset(&q, 0, sizeof(q));
+    q.Ahi = m->pad_hi; q.Alo = m->pad_lo; q.Whi = m->neck3.hi; q.Wlo = m->neck3.lo;
+    q.M = G2; q.N = C; q.K = 9 * C; q.cH = G; q.cW = G; q.cC = C; q.C = m->T2; q.ldc = C; q.ws_slot = 1;
+    SK(m, launch_gemm(q, c.precision, EPI_STORE, A_CONV3X3, s));
+  }
+  SK(m, ovm_g_layernorm(m->T2, nullptr, G2, C, m->nn3.g, m->nn3.b, kLn2dEps, m->emb, s));
+  SK(m, add_bcast(m->emb, m->no_mask, m->src0, (long)G2 * C, C, s));
+  m->H = H; m->W = W; m->newh = newh; m->neww = neww; m->has_image = true;
+  return OVM_OK;
+}
+
+int ovm_sam_predict_boxes_workspace(const OvmSam* m, int32_t n, int64_t* bytes) {
+  if (!m || !bytes || n < 0 || !m->tower) return OVM_ERR_INVALID;
+  const int nb = n < m->cfg.max_boxes ? n : m->cfg.max_boxes;
+  *bytes = (int64_t)carve(nullptr, nullptr, m, nb < 1 ? 1 : nb);
+  return OVM_OK;
+}
+
+int ovm_sam_predict_boxes(OvmSam* m, const float* boxes, int32_t n, int32_t mask_index, uint8_t* masks, float* iou, float* lowres, void* workspace,
+                          int64_t workspace_bytes, ovm_stream_t stream) {
+  if (!m) return OVM_ERR_INVALID;
+  m->err.clear();
+  if (!m->tower) { m->err = "handle was not created"; return OVM_ERR_INVALID; }
+  if (!m->has_image) { m->err = "ovm_sam_set_image has not been called"; return OVM_ERR_INVALID; }
+  if (n < 0 || mask_index < 0 || mask_index > 2) { m->err = "invalid arguments (n >= 0, mask_index 0..2)"; return OVM_ERR_INVALID; }
+  if (n == 0) return OVM_OK;
+  if (!boxes || !masks || !workspace) { m->err = "null boxes, masks or workspace"; return OVM_ERR_INVALID; }
+  if ((uintptr_t)workspace & 255) { m->err = "the workspace must be 256-byte aligned"; return OVM_ERR_INVALID; }
+  // the largest chunk the workspace holds (the carve is linear in the box count up to the 256-byte rounding of each buffer)
+  int nb = n < m->cfg.max_boxes ? n : m->cfg.max_boxes;
+  while (nb > 1 && (int64_t)carve(nullptr, nullptr, m, nb) > workspace_bytes) nb = (nb + 1) / 2;
+  if ((int64_t)carve(nullptr, nullptr, m, nb) > workspace_bytes) { m->err = "workspace too small for one box (ovm_sam_predict_boxes_workspace)"; return OVM_ERR_CAPACITY; }
+  SCHECK(m, hipSetDevice(m->device));
+  hipStream_t s = (hipStream_t)stream;
+  Work w; carve(&w, (char*)workspace, m, nb);
+  const size_t HW = (size_t)m->H * m->W, LL = (size_t)m->L * m->L;
+  for (int b0 = 0; b0 < n; b0 += nb) {
+    const int cnt = n - b0 < nb ? n - b0 : nb;
+    const int r = decode_chunk(m, boxes + (size_t)b0 * 4, cnt, mask_index, masks + (size_t)b0 * HW, iou ? iou + (size_t)b0 * 3 : nullptr,
+                               lowres ? lowres + (size_t)b0 * 3 * LL : nullptr, w, s);
+    if (r) return r;
+  }
+  return OVM_OK;
+}
+
+int64_t ovm_sam_debug_copy(OvmSam* m, const char* name, float* dst, int64_t capacity, ovm_stream_t stream) {
+  if (!m || !name || !dst || !m->tower) return OVM_ERR_INVALID;
+  hipStream_t s = (hipStream_t)stream;
+  const std::string n(name);
+  const int C = m->C, G2 = m->G2;
+  const float* src = nullptr; int64_t cnt = 0;
+  if (n == "preprocessed") {
+    cnt = (int64_t)3 * m->S * m->S;
+    if (cnt > capacity) return OVM_ERR_CAPACITY;
+    const half_t *hi, *lo; int ld;
+    tower_patches(m->tower, &hi, &lo, &ld);
+    hipLaunchKernelGGL(sam_unpatch_kernel, g1(cnt), dim3(256), 0, s, hi, lo, ld, m->G, m->cfg.patch, dst);
+    return last_launch() ? OVM_ERR_HIP : cnt;
+  }
+  if (n == "neck") { src = m->emb; cnt = (int64_t)G2 * C; }
+  else if (n == "dense_pe") { src = m->pe; cnt = (int64_t)G2 * C; }
+  else if (n == "sparse") { src = m->dbg_sparse; cnt = (int64_t)m->dbg_n * 2 * C; }
+  else if (n == "tokens_out") { src = m->dbg_tokens; cnt = (int64_t)m->dbg_n * m->nt * C; }
+  else return OVM_ERR_INVALID;
+  if (cnt > capacity) return OVM_ERR_CAPACITY;
+  if (cnt && hipMemcpyAsync(dst, src, (size_t)cnt * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return OVM_ERR_HIP;
+  return cnt;
+}
+
+}  // extern "C"

@@ -2,8 +2,9 @@
 
 ``lift_boxes`` runs the whole geometric part - un-projection, PCA yaw, DBSCAN outlier removal, extent fit - for all instances of
 one image in one call of ``ovm_geo_lift`` (ovmono3d_amd/csrc/geo.hip), then builds the reference's record fields on the host with
-``ovm_host_geo_box``. The two networks the reference runs in front of it are not here: the depth map (Depth Pro there) and the
-masks (SAM's mask decoder there) arrive as arrays, or the 2D box itself is the mask.
+``ovm_host_geo_box``. Of the two networks the reference runs in front of it, SAM is ``ovmono3d_amd.sam`` (its ``predict_boxes``
+planes are device tensors ``masks`` takes as they are); Depth Pro is not here: the depth map arrives as an array. Masks may also
+come from files, or the 2D box itself is the mask.
 """
 from __future__ import annotations
 

@@ -145,6 +145,17 @@ class OvmGeoBox(C.Structure):
                 ("depth", C.c_double), ("bbox3D", (C.c_float * 3) * 8)]
 
 
+class OvmSamConfig(C.Structure):
+    """Mirror of include/ovm3d.h OvmSamConfig."""
+    _fields_ = [
+        ("embed_dim", C.c_int32), ("depth", C.c_int32), ("heads", C.c_int32), ("patch", C.c_int32), ("pos_grid", C.c_int32),
+        ("window", C.c_int32), ("global_mask", C.c_uint32), ("image_size", C.c_int32), ("prompt_dim", C.c_int32),
+        ("dec_depth", C.c_int32), ("dec_heads", C.c_int32), ("dec_mlp", C.c_int32), ("attn_downsample", C.c_int32),
+        ("num_mask_tokens", C.c_int32), ("iou_depth", C.c_int32), ("iou_hidden", C.c_int32),
+        ("pixel_mean", C.c_float * 3), ("pixel_std", C.c_float * 3), ("precision", C.c_int32), ("max_boxes", C.c_int32),
+    ]
+
+
 EXPORTS = [
     "ovm_create", "ovm_destroy", "ovm_last_error", "ovm_version", "ovm_abi_sizeof", "ovm_backbone_forward", "ovm_cube_forward",
     "ovm_rpn_box_forward", "ovm_gather_records", "ovm_gather_counts", "ovm_host_interp_pos_embed", "ovm_host_resize_pos_embed_aa", "ovm_host_sincos_pos_embed", "ovm_host_shard_range",
@@ -160,6 +171,8 @@ EXPORTS = [
     "ovm_host_scene_layout", "ovm_render_scene_workspace", "ovm_render_scene",
     "ovm_geo_default_params", "ovm_geo_last_error", "ovm_geo_lift_workspace", "ovm_geo_lift", "ovm_geo_dbscan_workspace", "ovm_geo_dbscan",
     "ovm_host_geo_box",
+    "ovm_sam_create", "ovm_sam_destroy", "ovm_sam_last_error", "ovm_sam_set_image", "ovm_sam_predict_boxes_workspace", "ovm_sam_predict_boxes",
+    "ovm_sam_debug_copy",
 ]
 PROF_NAMES = ("attn", "qkv", "proj", "fc1", "fc2", "ln")
 
@@ -186,7 +199,8 @@ def load() -> C.CDLL:
     for name, mirror in (("OvmConfig", OvmConfig), ("OvmTensor", OvmTensor), ("OvmImage", OvmImage), ("OvmGdinoConfig", OvmGdinoConfig),
                          ("OvmJpegInfo", OvmJpegInfo), ("OvmSceneInput", OvmSceneInput), ("OvmSceneLayout", OvmSceneLayout),
                          ("OvmSceneSegment", OvmSceneSegment), ("OvmEvalCell", OvmEvalCell), ("OvmGeoParams", OvmGeoParams),
-                         ("OvmGeoInstance", OvmGeoInstance), ("OvmGeoResult", OvmGeoResult), ("OvmGeoBox", OvmGeoBox)):
+                         ("OvmGeoInstance", OvmGeoInstance), ("OvmGeoResult", OvmGeoResult), ("OvmGeoBox", OvmGeoBox),
+                         ("OvmSamConfig", OvmSamConfig)):
         if lib.ovm_abi_sizeof(name.encode()) != C.sizeof(mirror):
             raise RuntimeError(f"{LIB_PATH}: sizeof({name}) = {lib.ovm_abi_sizeof(name.encode())} but the ctypes mirror has "
                                f"{C.sizeof(mirror)} bytes - rebuild the library (ovmono3d_amd/csrc/build.sh) or update lib.py")
@@ -239,6 +253,15 @@ def load() -> C.CDLL:
     lib.ovm_geo_dbscan_workspace.argtypes = [i32, C.POINTER(i64)]
     lib.ovm_geo_dbscan.argtypes = [vp, i32, C.c_double, i32, vp, vp, i64, vp]
     lib.ovm_host_geo_box.argtypes = [C.POINTER(OvmGeoResult), C.POINTER(C.c_double), C.POINTER(OvmGeoBox)]
+    lib.ovm_sam_create.argtypes = [C.POINTER(OvmSamConfig), C.POINTER(OvmTensor), i32, i32, C.POINTER(vp)]
+    lib.ovm_sam_destroy.argtypes = [vp]
+    lib.ovm_sam_last_error.argtypes = [vp]
+    lib.ovm_sam_last_error.restype = C.c_char_p
+    lib.ovm_sam_set_image.argtypes = [vp, C.POINTER(OvmImage), i32, vp]
+    lib.ovm_sam_predict_boxes_workspace.argtypes = [vp, i32, C.POINTER(i64)]
+    lib.ovm_sam_predict_boxes.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, i64, vp]
+    lib.ovm_sam_debug_copy.argtypes = [vp, C.c_char_p, vp, i64, vp]
+    lib.ovm_sam_debug_copy.restype = i64
     lib.ovm_g_pack_weight.argtypes = [vp, i32, i32, i32, vp, vp, vp]
     lib.ovm_g_linear.argtypes = [vp, i32, i32, i32, vp, vp, i32, i32, vp, i32, vp, i32, vp, i32, i32, vp]
     lib.ovm_g_layernorm.argtypes = [vp, vp, i32, i32, vp, vp, f32, vp, vp]
@@ -268,7 +291,8 @@ def load() -> C.CDLL:
     lib.ovm_gdino_last_outputs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32)]
     lib.ovm_infer.argtypes = [vp, vp, C.POINTER(OvmImage), C.POINTER(i32), i32, C.POINTER(i32), i32, f32, f32, vp, i32, C.POINTER(i32), vp]
     for name in EXPORTS:
-        if name not in ("ovm_last_error", "ovm_version", "ovm_debug_copy", "ovm_gdino_last_error", "ovm_gdino_debug_copy", "ovm_geo_last_error"):
+        if name not in ("ovm_last_error", "ovm_version", "ovm_debug_copy", "ovm_gdino_last_error", "ovm_gdino_debug_copy", "ovm_geo_last_error",
+                        "ovm_sam_last_error", "ovm_sam_debug_copy"):
             getattr(lib, name).restype = i32
     # experiment knobs, e.g. OVM_TUNE="gemm_bm=256,attn_tail=0"
     for kv in filter(None, os.environ.get("OVM_TUNE", "").split(",")):

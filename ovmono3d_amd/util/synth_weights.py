@@ -57,6 +57,7 @@ SAM_ARCH = {
     # name: (width, layers, heads, patch, checkpoint grid, window, global-attention blocks)   -- reference backbone/sam.py:39-40
     # (segment_anything sam_model_registry['vit_b']: image 1024 -> 64 x 64 grid, window 14, global blocks 2 5 8 11)
     "vit_b": (768, 12, 12, 16, 64, 14, (2, 5, 8, 11)),
+    "vit_l": (1024, 24, 16, 16, 64, 14, (5, 11, 17, 23)),
     "vit_test": (256, 4, 4, 16, 8, 6, (1, 3)),      # tiny (not a published model)
 }
 

@@ -4,14 +4,26 @@ a metric depth map and a mask per box - un-projection, PCA yaw, DBSCAN outlier r
 (ovmono3d_amd.geo, csrc/geo.hip), and writes the reference's per-image records for tools/eval_ovmono3d_geo.py.
 
     python tools/ovmono3d_geo.py --oracle2d gdino_kitti_novel_oracle_2d.json --dataset datasets/Omni3D/KITTI_test_novel.json \\
-        --depth-dir datasets/depth --mask-dir datasets/masks --output output/ovmono3d_geo/KITTI_test_novel.pth
+        --depth-dir datasets/depth --mask sam --sam-weights sam_vit_l_0b3195.pth --sam-arch vit_l --image-root datasets \\
+        --output output/ovmono3d_geo/KITTI_test_novel.pth
 
-What is NOT here: the two networks the reference runs in front of the lifting. Depth (Depth Pro there) is read from
+Masks, one of:
+  ``--mask sam``   the reference's way (tools/ovmono3d_geo.py:213-217,270-272,308-309): Segment Anything prompted with each 2D box,
+                   plane [2] of the multimask outputs, on the device (ovmono3d_amd.sam, csrc/sam.hip). One ``set_image`` per image
+                   (the reference repeats it per instance, with the same result) and one ``predict_boxes`` call for all instances at
+                   or above the score threshold; the planes go straight to the lifting without leaving the device. Images are read
+                   from ``<image-root>/<file_path>`` by the device JPEG decoder (the host reader for files outside its scope) in
+                   cv2.imread's BGR order and handed over as the reference does (``set_image(im, image_format="BGR")``). vit_b
+                   and vit_l checkpoints; vit_h (head dimension 80) is refused by the library.
+  ``--mask-dir``   masks some other program wrote: ``<mask-dir>/<image_id>.npz`` with ``masks`` uint8 [n, H, W] (nonzero = inside)
+                   and ``index`` int [n], the positions of the masked instances in the image's instance list. ``--dump-masks DIR``
+                   writes exactly these files from a ``--mask sam`` run.
+  ``--mask box``   the 2D box itself is the mask: the pixels ceil(x0) <= x < ceil(x1), ceil(y0) <= y < ceil(y1) of the xyxy box,
+                   clipped to the image (the reference has no such mode; the rule is this project's).
+
+What is NOT here: Depth Pro, the network the reference takes its depth from. Depth is read from
 ``<depth-dir>/test/<image base name>.npz`` (or ``<depth-dir>/<image base name>.npz``), key ``depth``, metres, at the image's own
-resolution - a map of another shape is refused, the reference never resizes it. Masks (SAM's largest mask there) are read from
-``<mask-dir>/<image_id>.npz``: ``masks`` uint8 [n, H, W] (nonzero = inside) and ``index`` int [n], the positions of the masked
-instances in the image's instance list. With ``--mask box`` the 2D box itself is the mask: the pixels ceil(x0) <= x < ceil(x1),
-ceil(y0) <= y < ceil(y1) of the xyxy box, clipped to the image (the reference has no such mode; the rule is this project's).
+resolution - a map of another shape is refused, the reference never resizes it.
 
 Instances below ``--score-threshold`` are dropped as in the reference. Instances the reference has no answer for (an empty mask,
 fewer than 2 points, a non-finite depth under the mask, a box outside the image, no mask in the mask file) are skipped, counted
@@ -40,11 +52,34 @@ def xywh_to_xyxy(b):
 
 
 def lift_image(depth, K, boxes_xyxy, masks, params):
-    """depth: float32 [H, W] numpy; masks: a list of uint8 [H, W] arrays or None (the box is the mask). One device call."""
+    """depth: float32 [H, W] numpy; masks: a list of uint8 [H, W] planes (numpy arrays or device tensors) or None (the box is the
+    mask). One device call."""
     dev = torch.device("cuda", torch.cuda.current_device())
     d = torch.from_numpy(depth).to(dev)
-    m = None if masks is None else [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in masks]
+    m = None if masks is None else [x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in masks]
     return lift_boxes(d, K, boxes_xyxy=boxes_xyxy, masks=m, params=params)
+
+
+def sam_masks(predictor, image_root, file_path, height, width, boxes_xyxy):
+    """Device uint8 [n, H, W]: SAM's plane [2] for every box of one image (one set_image, one predict_boxes)."""
+    from ovmono3d_amd.data.gpu_jpeg import read_image_device
+    path = os.path.join(image_root, file_path)
+    if not os.path.exists(path):
+        raise SystemExit(f"no image {path} (--image-root)")
+    bgr = read_image_device(path, "BGR", predictor.engine.dev)
+    if tuple(bgr.shape[:2]) != (height, width):
+        raise SystemExit(f"{path}: image is {tuple(bgr.shape[:2])} but the dataset says {(height, width)}")
+    predictor.set_image(bgr, image_format="BGR")   # the reference's call (run_seg_anything): a cv2 BGR array, declared as such
+    return predictor.predict_boxes(boxes_xyxy, mask_index=2)
+
+
+def dump_masks(mask_dir, image_id, positions, planes):
+    """The <image_id>.npz file load_masks reads."""
+    os.makedirs(mask_dir, exist_ok=True)
+    planes = [p.cpu().numpy() if isinstance(p, torch.Tensor) else np.asarray(p) for p in planes]
+    H, W = planes[0].shape
+    np.savez_compressed(os.path.join(mask_dir, f"{image_id}.npz"), masks=np.stack(planes).astype(np.uint8).reshape(-1, H, W),
+                        index=np.asarray(positions, np.int64))
 
 
 def load_depth(depth_dir, file_path, height, width):
@@ -79,9 +114,15 @@ def run(args):
     with open(args.dataset) as f:
         images = {im["id"]: im for im in json.load(f)["images"]}
     params = GeoParams()
-    use_box = args.mask == "box"
-    if not use_box and not args.mask_dir:
-        raise SystemExit("give --mask-dir DIR or --mask box")
+    use_box, use_sam = args.mask == "box", args.mask == "sam"
+    if not use_box and not use_sam and not args.mask_dir:
+        raise SystemExit("give --mask-dir DIR, --mask sam or --mask box")
+    predictor = None
+    if use_sam:
+        if not args.sam_weights or not args.image_root:
+            raise SystemExit("--mask sam needs --sam-weights FILE and --image-root DIR")
+        from ovmono3d_amd.sam import build_sam
+        predictor = build_sam(args.sam_arch, args.sam_weights, image_size=args.sam_image_size)
     out, n_in, n_low, n_skip, n_lifted = [], 0, 0, 0, 0
     for rec in oracle:
         im = images.get(rec["image_id"])
@@ -96,7 +137,10 @@ def run(args):
         if cand:
             depth = load_depth(args.depth_dir, im["file_path"], H, W)
             planes = None
-            if not use_box:
+            if use_sam:
+                boxes = np.asarray([xywh_to_xyxy(ins["bbox"]) for _, ins in cand], np.float64)
+                planes = list(sam_masks(predictor, args.image_root, im["file_path"], H, W, boxes))
+            elif not use_box:
                 have = load_masks(args.mask_dir, rec["image_id"], H, W)
                 missing = [pos for pos, _ in cand if pos not in have]
                 if missing:
@@ -107,6 +151,8 @@ def run(args):
             if cand:
                 boxes = np.asarray([xywh_to_xyxy(ins["bbox"]) for _, ins in cand], np.float64)
                 lifted = lift_image(depth, K, boxes, planes, params)
+                if args.dump_masks and planes is not None:
+                    dump_masks(args.dump_masks, rec["image_id"], [pos for pos, _ in cand], planes)
                 for (pos, ins), box in zip(cand, lifted):
                     if box is None:
                         logger.warning("image %s: instance %d has no 3D box (empty mask, < 2 points, non-finite depth or a box outside "
@@ -139,8 +185,14 @@ def argument_parser():
     ap.add_argument("--dataset", required=True, help="Omni3D annotation json of the same images (file_path, height, width, K)")
     ap.add_argument("--depth-dir", required=True, help="metric depth .npz files (key 'depth'), the ones DatasetMapper3D reads")
     ap.add_argument("--mask-dir", default=None, help="<image_id>.npz with 'masks' uint8 [n, H, W] and 'index' int [n]")
-    ap.add_argument("--mask", choices=("box",), default=None,
-                    help="box: the 2D box is the mask - pixels ceil(x0) <= x < ceil(x1), ceil(y0) <= y < ceil(y1), clipped to the image")
+    ap.add_argument("--mask", choices=("box", "sam"), default=None,
+                    help="box: the 2D box is the mask - pixels ceil(x0) <= x < ceil(x1), ceil(y0) <= y < ceil(y1), clipped to the image; "
+                         "sam: Segment Anything prompted with the box, plane [2] of its multimask outputs (the reference's rule)")
+    ap.add_argument("--sam-weights", default=None, help="segment_anything checkpoint (.pth: image_encoder.*, prompt_encoder.*, mask_decoder.*)")
+    ap.add_argument("--sam-arch", default="vit_l", help="vit_b or vit_l (vit_h has head dimension 80: refused)")
+    ap.add_argument("--sam-image-size", type=int, default=None, help=argparse.SUPPRESS)      # tests: a small encoder input
+    ap.add_argument("--image-root", default=None, help="directory the dataset's file_path entries are relative to (--mask sam)")
+    ap.add_argument("--dump-masks", default=None, metavar="DIR", help="write the masks used as <DIR>/<image_id>.npz, the files --mask-dir reads")
     ap.add_argument("--score-threshold", type=float, default=0.30)
     ap.add_argument("--output", required=True, help=".pth (torch.save, as the reference) or .json")
     return ap
