@@ -242,8 +242,29 @@ int ovm_op_roi_align(const float* p2, const float* p3, const float* p4, const in
 int ovm_op_cube_decode(const float* head13, int32_t ld, const float* boxes, const float* scores, const int32_t* classes,
                        const int32_t* image_idx, const OvmImage* images, int32_t B, int32_t n, float virtual_focal,
                        int32_t postprocess, OvmDet3D* rec, int32_t* keep, ovm_stream_t stream);
+/* torchvision.ops.nms: keep_idx [n] in decreasing-score order (ties: lower index first), *n_keep their number. n <= 4096;
+ * a larger n returns OVM_ERR_CAPACITY before any device work and leaves keep_idx and *n_keep untouched. Synchronises. */
 int ovm_op_nms(const float* boxes, const float* scores, int32_t n, float thresh, int32_t* keep_idx, int32_t* n_keep,
                ovm_stream_t stream);
+/* The post-processing stages of ovm_rpn_box_forward on their own, with inputs the caller chooses. Both allocate their scratch,
+ * free it on every exit path and synchronise the stream. Of `images` only height / width are read (the clip size).
+ *
+ * RPN.predict_proposals + find_top_rpn_proposals. levels_o: host array of nlev (1 .. 4) device pointers, level l fp32
+ * [B * sides[l]^2][16] = 3 objectness logits then 3 x 4 anchor deltas per cell (cell = y * side + x, image-major); sides, strides,
+ * anchor_sizes [nlev] and anchor_ratios [3] host arrays. Outputs (device): prop_boxes [B][post_topk][4] and prop_scores
+ * [B][post_topk] in decreasing-score order, rows past prop_count [B] zero. pre_topk, post_topk <= 1024, else OVM_ERR_CAPACITY. */
+int ovm_op_rpn_proposals(const float* const* levels_o, int32_t nlev, const int32_t* sides, const float* strides,
+                         const float* anchor_sizes, const float* anchor_ratios, const OvmImage* images, int32_t B,
+                         int32_t pre_topk, int32_t post_topk, float nms_thresh, float* prop_boxes, float* prop_scores,
+                         int32_t* prop_count, ovm_stream_t stream);
+/* FastRCNNOutputLayers.inference. HO (device) fp32 [B*R][ldh]: K+1 class logits, then K x 4 box deltas (weights 10, 10, 5, 5);
+ * prop_boxes [B][R][4] and prop_count [B] (device): rows r >= prop_count[b] are ignored. Outputs (device, capacity B*topk rows,
+ * image-major and compact, nothing is written past the sum of out_counts): boxes [.][4], scores, classes, image_idx,
+ * scores_full [.][K] (may be NULL), out_counts [B]. R, topk <= 1024 and K <= 63, else OVM_ERR_CAPACITY. */
+int ovm_op_boxhead_post(const float* HO, int32_t ldh, const float* prop_boxes, const int32_t* prop_count, const OvmImage* images,
+                        int32_t B, int32_t R, int32_t K, float score_thresh, float nms_thresh, int32_t topk, float* boxes,
+                        float* scores, int32_t* classes, int32_t* image_idx, float* scores_full, int32_t* out_counts,
+                        ovm_stream_t stream);
 
 /* --- GroundingDINO output glue of ROIHeads3DGDINO (reference roi_heads_gdino.py:186-202,236-263,266-294):
  * pred_logits [nq][ld] (pre-sigmoid token logits, ld = 256), pred_boxes [nq][4] cxcywh in [0,1] (device);

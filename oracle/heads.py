@@ -124,15 +124,24 @@ def forward_box(sd, feats: List[torch.Tensor], proposals: List[torch.Tensor], im
     x = fc_head(x, sd, "roi_heads.box_head.")
     cls = F.linear(x, sd["roi_heads.box_predictor.cls_score.weight"], sd["roi_heads.box_predictor.cls_score.bias"])
     dlt = F.linear(x, sd["roi_heads.box_predictor.bbox_pred.weight"], sd["roi_heads.box_predictor.bbox_pred.bias"])
+    return box_inference(cls, dlt, proposals, image_sizes, score_thresh, nms_thresh, topk, bbox_weights)
+
+
+def box_inference(cls: torch.Tensor, dlt: torch.Tensor, proposals: List[torch.Tensor], image_sizes, score_thresh=0.01,
+                  nms_thresh=0.5, topk=100, bbox_weights=(10.0, 10.0, 5.0, 5.0), with_rows=False):
+    """``FastRCNNOutputLayers.inference`` from the predictor outputs: cls [sum R_i, K+1] logits, dlt [sum R_i, 4K].
+    with_rows: also return, per image, the proposal row of each detection."""
     nums = [len(p) for p in proposals]
     allp = torch.cat(proposals, dim=0)
     pred = apply_deltas(dlt, allp, bbox_weights)
     probs = F.softmax(cls, dim=-1)
-    out = []
+    out, rows = [], []
     for pb, sc, shp in zip(pred.split(nums), probs.split(nums), image_sizes):
-        r, _ = fast_rcnn_inference_single_image(pb, sc, shp, score_thresh, nms_thresh, topk)
+        valid = torch.isfinite(pb).all(dim=1) & torch.isfinite(sc).all(dim=1)
+        r, kept = fast_rcnn_inference_single_image(pb, sc, shp, score_thresh, nms_thresh, topk)
         out.append(r)
-    return out
+        rows.append(torch.where(valid)[0][kept])                         # kept indexes the rows that survived the finite filter
+    return (out, rows) if with_rows else out
 
 
 # ----------------------------------------------------------------------------- cube branch

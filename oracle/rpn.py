@@ -87,9 +87,19 @@ def rpn_inference(sd, feats: List[torch.Tensor], strides: Sequence[int], sizes: 
                   nms_thresh=0.7, min_box_size=0.0):
     """Returns per image (proposal_boxes [R,4], objectness_logits [R])."""
     logits, deltas = rpn_head(sd, feats)
-    B = feats[0].shape[0]
+    return rpn_proposals_from_head(logits, deltas, strides, sizes, ratios, image_sizes, pre_topk, post_topk, nms_thresh,
+                                   min_box_size)
+
+
+def rpn_proposals_from_head(logits: List[torch.Tensor], deltas: List[torch.Tensor], strides: Sequence[int],
+                            sizes: Sequence[float], ratios: Sequence[float], image_sizes: List[Tuple[int, int]],
+                            pre_topk=1000, post_topk=1000, nms_thresh=0.7, min_box_size=0.0, with_ids=False):
+    """``predict_proposals`` + ``find_top_rpn_proposals`` from the head outputs: per level logits [B,A,H,W] and
+    deltas [B,A*4,H,W]. Returns per image (proposal_boxes [R,4], objectness_logits [R]); with_ids adds a third entry
+    [R,2] = (level, anchor index (y*W + x)*A + a) of each proposal."""
+    B = logits[0].shape[0]
     A = len(ratios)
-    lvl_scores, lvl_boxes, lvl_ids = [], [], []
+    lvl_scores, lvl_boxes, lvl_ids, lvl_anchor = [], [], [], []
     for li, (lg, dl) in enumerate(zip(logits, deltas)):
         _, _, H, W = lg.shape
         anchors = grid_anchors(H, W, strides[li], cell_anchors(sizes[li], ratios))
@@ -104,19 +114,22 @@ def rpn_inference(sd, feats: List[torch.Tensor], strides: Sequence[int], sizes: 
         lvl_scores.append(sc)
         lvl_boxes.append(torch.stack(boxes))
         lvl_ids.append(torch.full((k,), li, dtype=torch.int64))
+        lvl_anchor.append(idx)
     scores = torch.cat(lvl_scores, dim=1)
     boxes = torch.cat(lvl_boxes, dim=1)
     lvl = torch.cat(lvl_ids)
+    anchor = torch.cat(lvl_anchor, dim=1)
     results = []
     for b in range(B):
         bx, sc, lv = boxes[b], scores[b], lvl
+        ids = torch.stack((lvl, anchor[b]), dim=1)
         valid = torch.isfinite(bx).all(dim=1) & torch.isfinite(sc)
         if not valid.all():
-            bx, sc, lv = bx[valid], sc[valid], lv[valid]
+            bx, sc, lv, ids = bx[valid], sc[valid], lv[valid], ids[valid]
         bx = clip_boxes(bx, image_sizes[b])
         keep = ((bx[:, 2] - bx[:, 0]) > min_box_size) & ((bx[:, 3] - bx[:, 1]) > min_box_size)
         if int(keep.sum()) != len(bx):
-            bx, sc, lv = bx[keep], sc[keep], lv[keep]
+            bx, sc, lv, ids = bx[keep], sc[keep], lv[keep], ids[keep]
         keep = batched_nms(bx, sc, lv, nms_thresh)[:post_topk]
-        results.append((bx[keep], sc[keep]))
+        results.append((bx[keep], sc[keep], ids[keep]) if with_ids else (bx[keep], sc[keep]))
     return results

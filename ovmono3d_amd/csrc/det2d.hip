@@ -18,8 +18,14 @@ constexpr int TILE = 2048;
 constexpr unsigned long long kInvalidKey = ~0ull;
 constexpr unsigned long long kIdMask = (1ull << 24) - 1;
 
-__device__ __forceinline__ unsigned int ord32(float f) {        // order-preserving float -> uint (ascending)
-  const unsigned int u = __float_as_uint(f);
+// torch.clamp(d, max=c): a NaN delta stays NaN (fminf would return c) and the box is then dropped as non-finite
+__device__ __forceinline__ float clamp_max(float d, float c) { return d > c ? c : d; }
+
+// order-preserving float -> uint (ascending); -0.0f maps to the key of +0.0f, so that the two tie and the lower index wins, as in
+// torch.sort(stable=True) / torch.topk
+__device__ __forceinline__ unsigned int ord32(float f) {
+  unsigned int u = __float_as_uint(f);
+  if (u == 0x80000000u) u = 0u;
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
@@ -200,7 +206,7 @@ __global__ void rpn_decode_kernel(const unsigned long long* __restrict__ keys, R
   const float widths = ax2 - ax1, heights = ay2 - ay1;
   const float ctr_x = ax1 + 0.5f * widths, ctr_y = ay1 + 0.5f * heights;
   const float dx = o[3 + a * 4 + 0], dy = o[3 + a * 4 + 1];
-  const float dw = fminf(o[3 + a * 4 + 2], scale_clamp), dh = fminf(o[3 + a * 4 + 3], scale_clamp);
+  const float dw = clamp_max(o[3 + a * 4 + 2], scale_clamp), dh = clamp_max(o[3 + a * 4 + 3], scale_clamp);
   const float pcx = dx * widths + ctr_x, pcy = dy * heights + ctr_y;
   const float pw = expf(dw) * widths, ph = expf(dh) * heights;
   float x1 = pcx - 0.5f * pw, y1 = pcy - 0.5f * ph, x2 = pcx + 0.5f * pw, y2 = pcy + 0.5f * ph;
@@ -272,7 +278,7 @@ __global__ __launch_bounds__(256) void boxhead_dense_kernel(const float* __restr
     const float widths = bx2 - bx1, heights = by2 - by1;
     const float ctr_x = bx1 + 0.5f * widths, ctr_y = by1 + 0.5f * heights;
     const float dx = d[0] / 10.f, dy = d[1] / 10.f;
-    const float dw = fminf(d[2] / 5.f, scale_clamp), dh = fminf(d[3] / 5.f, scale_clamp);
+    const float dw = clamp_max(d[2] / 5.f, scale_clamp), dh = clamp_max(d[3] / 5.f, scale_clamp);
     const float pcx = dx * widths + ctr_x, pcy = dy * heights + ctr_y;
     const float pw = expf(dw) * widths, ph = expf(dh) * heights;
     x1 = pcx - 0.5f * pw; y1 = pcy - 0.5f * ph; x2 = pcx + 0.5f * pw; y2 = pcy + 0.5f * ph;
@@ -416,17 +422,13 @@ int det2d_alloc(Det2dWorkspace* w, int B, int nlev, const int* sides, int C, int
   return OVM_OK;
 }
 
-int det2d_forward(const Det2dModel& m, Det2dWorkspace& w, float* boxes, float* scores, int* classes, int* image_idx,
-                  float* scores_full, int* out_counts, hipStream_t s) {
-  const int B = m.B, C = m.C, K = m.num_classes;
-  if (B > w.maxB || m.pre_topk != w.pre_topk || K != w.num_classes) return OVM_ERR_CAPACITY;
-  const float scale_clamp = (float)std::log(1000.0 / 16.0);
-  const int nlev = m.nlev;
-  if (nlev != w.nlev) return OVM_ERR_CAPACITY;
+namespace {
+
+RpnGeom rpn_geom(const Det2dModel& m, const Det2dWorkspace& w) {
   RpnGeom gm; memset(&gm, 0, sizeof(gm));
-  gm.nlev = nlev;
+  gm.nlev = m.nlev;
   gm.A_off[0] = 0;
-  for (int l = 0; l < nlev; ++l) {
+  for (int l = 0; l < m.nlev; ++l) {
     gm.HW[l] = w.HW[l]; gm.Wl[l] = w.Wl[l]; gm.A_off[l + 1] = gm.A_off[l] + w.HW[l] * 3;
     gm.stride[l] = m.stride[l]; gm.o[l] = w.rpn_o[l];
     for (int a = 0; a < 3; ++a) {                         // DefaultAnchorGenerator.generate_cell_anchors
@@ -437,8 +439,15 @@ int det2d_forward(const Det2dModel& m, Det2dWorkspace& w, float* boxes, float* s
       gm.base[l][a][2] = (float)(ww / 2.0);  gm.base[l][a][3] = (float)(hh / 2.0);
     }
   }
-  // ---- RPN head: conv3x3+bias+ReLU (implicit GEMM over the zero-bordered fp16 pyramid), then the 1x1s ----
-  for (int l = 0; l < nlev; ++l) {
+  return gm;
+}
+
+const float kScaleClamp = (float)std::log(1000.0 / 16.0);
+
+// ---- stage 1: RPN head: conv3x3+bias+ReLU (implicit GEMM over the zero-bordered fp16 pyramid), then the 1x1s ----
+int det2d_rpn_head(const Det2dModel& m, Det2dWorkspace& w, hipStream_t s) {
+  const int B = m.B, C = m.C;
+  for (int l = 0; l < m.nlev; ++l) {
     const int Hs = w.Wl[l], M = B * w.HW[l];
     GemmParams p; memset(&p, 0, sizeof(p));
     p.Ahi = m.rpad[l].hi; p.Alo = m.rpad[l].lo; p.Whi = m.rpn_conv_hi; p.Wlo = m.rpn_conv_lo;
@@ -452,14 +461,44 @@ int det2d_forward(const Det2dModel& m, Det2dWorkspace& w, float* boxes, float* s
     r = launch_gemm(q, m.npass, EPI_STORE, A_ROWMAJOR, s);
     if (r) return r;
   }
-  // ---- per-level top-k (sort of (level, score, index) keys), decode, clip ----
+  return OVM_OK;
+}
+
+// ---- stage 3: box head: ROIAlign -> fc1 -> fc2 -> (cls_score | bbox_pred) ----
+int det2d_box_head(const Det2dModel& m, Det2dWorkspace& w, hipStream_t s) {
+  const int K = m.num_classes, M = m.B * w.R;
+  RoiParams rp = m.roi;
+  rp.boxes = w.prop_boxes; rp.batch_idx = w.prop_bidx; rp.n = M; rp.Ohi = m.RF.hi; rp.Olo = m.RF.lo; rp.ldo = m.roiK;
+  int r = launch_roi_align(rp, s);
+  if (r) return r;
+  GemmParams p; memset(&p, 0, sizeof(p));
+  p.Ahi = m.RF.hi; p.Alo = m.RF.lo; p.lda = m.roiK; p.Whi = m.fc1_hi; p.Wlo = m.fc1_lo; p.M = M; p.N = m.F; p.K = m.roiK;
+  p.bias = m.fc1_bias; p.relu = 1; p.Ohi = m.H1.hi; p.Olo = m.H1.lo; p.ldo = m.F;
+  if ((r = launch_gemm(p, m.npass, EPI_STORE, A_ROWMAJOR, s))) return r;
+  GemmParams q; memset(&q, 0, sizeof(q));
+  q.Ahi = m.H1.hi; q.Alo = m.H1.lo; q.lda = m.F; q.Whi = m.fc2_hi; q.Wlo = m.fc2_lo; q.M = M; q.N = m.F; q.K = m.F;
+  q.bias = m.fc2_bias; q.relu = 1; q.Ohi = m.H2.hi; q.Olo = m.H2.lo; q.ldo = m.F;
+  if ((r = launch_gemm(q, m.npass, EPI_STORE, A_ROWMAJOR, s))) return r;
+  GemmParams o; memset(&o, 0, sizeof(o));
+  o.Ahi = m.H2.hi; o.Alo = m.H2.lo; o.lda = m.F; o.Whi = m.out_hi; o.Wlo = m.out_lo; o.M = M; o.N = (K + 1) + 4 * K; o.K = m.F;
+  o.bias = m.out_bias; o.C = m.HO; o.ldc = 256;
+  if (o.N > 256) return OVM_ERR_CAPACITY;
+  return launch_gemm(o, m.npass, EPI_STORE, A_ROWMAJOR, s);
+}
+
+}  // namespace
+
+// ---- stage 2: per-level top-k (sort of (level, score, index) keys), decode, clip, per-level NMS, merge by score, keep R ----
+int det2d_rpn_proposals(const Det2dModel& m, Det2dWorkspace& w, hipStream_t s) {
+  const int B = m.B, nlev = m.nlev;
+  if (B > w.maxB || m.pre_topk != w.pre_topk || nlev != w.nlev) return OVM_ERR_CAPACITY;
+  const RpnGeom gm = rpn_geom(m, w);
   const int N = w.Nrpn, NS = nlev * m.pre_topk;
   hipLaunchKernelGGL(rpn_keys_kernel, dim3((N + 255) / 256, B), dim3(256), 0, s, gm, N, w.keys);
   int r = sort_keys(w.keys, N, B, s);
   if (r) return r;
   hipLaunchKernelGGL(rpn_decode_kernel, dim3((NS + 255) / 256, B), dim3(256), 0, s, w.keys, gm, N,
-                     m.pre_topk, m.meta, scale_clamp, w.cbox, w.cscore, w.cgroup, w.gstart, w.gend);
-  // ---- per-level NMS, merge by score, keep post_topk ----
+                     m.pre_topk, m.meta, kScaleClamp, w.cbox, w.cscore, w.cgroup, w.gstart, w.gend);
   hipLaunchKernelGGL(nms_mask_kernel, dim3((NS * 16 + 127) / 128, B), dim3(128), 0, s, w.cbox, w.cgroup, w.gstart, w.gend, nlev, NS, 16,
                      m.rpn_nms, w.mask);
   hipLaunchKernelGGL(nms_scan_kernel, dim3(nlev, B), dim3(64), 0, s, w.cgroup, w.gstart, w.gend, nlev, NS, 16, w.mask, w.ckeep);
@@ -470,32 +509,19 @@ int det2d_forward(const Det2dModel& m, Det2dWorkspace& w, float* boxes, float* s
   const int R = w.R;
   hipLaunchKernelGGL(rpn_emit_kernel, dim3((R + 255) / 256, B), dim3(256), 0, s, w.mkeys, w.Nmerge, NS, w.cbox, w.cscore, R,
                      w.prop_boxes, w.prop_scores, w.prop_bidx, w.prop_count);
-  // ---- box head: ROIAlign -> fc1 -> fc2 -> (cls_score | bbox_pred) ----
-  const int M = B * R;
-  RoiParams rp = m.roi;
-  rp.boxes = w.prop_boxes; rp.batch_idx = w.prop_bidx; rp.n = M; rp.Ohi = m.RF.hi; rp.Olo = m.RF.lo; rp.ldo = m.roiK;
-  r = launch_roi_align(rp, s);
-  if (r) return r;
-  {
-    GemmParams p; memset(&p, 0, sizeof(p));
-    p.Ahi = m.RF.hi; p.Alo = m.RF.lo; p.lda = m.roiK; p.Whi = m.fc1_hi; p.Wlo = m.fc1_lo; p.M = M; p.N = m.F; p.K = m.roiK;
-    p.bias = m.fc1_bias; p.relu = 1; p.Ohi = m.H1.hi; p.Olo = m.H1.lo; p.ldo = m.F;
-    if ((r = launch_gemm(p, m.npass, EPI_STORE, A_ROWMAJOR, s))) return r;
-    GemmParams q; memset(&q, 0, sizeof(q));
-    q.Ahi = m.H1.hi; q.Alo = m.H1.lo; q.lda = m.F; q.Whi = m.fc2_hi; q.Wlo = m.fc2_lo; q.M = M; q.N = m.F; q.K = m.F;
-    q.bias = m.fc2_bias; q.relu = 1; q.Ohi = m.H2.hi; q.Olo = m.H2.lo; q.ldo = m.F;
-    if ((r = launch_gemm(q, m.npass, EPI_STORE, A_ROWMAJOR, s))) return r;
-    GemmParams o; memset(&o, 0, sizeof(o));
-    o.Ahi = m.H2.hi; o.Alo = m.H2.lo; o.lda = m.F; o.Whi = m.out_hi; o.Wlo = m.out_lo; o.M = M; o.N = (K + 1) + 4 * K; o.K = m.F;
-    o.bias = m.out_bias; o.C = m.HO; o.ldc = 256;
-    if (o.N > 256) return OVM_ERR_CAPACITY;
-    if ((r = launch_gemm(o, m.npass, EPI_STORE, A_ROWMAJOR, s))) return r;
-  }
-  // ---- softmax + decode + threshold -> per-class NMS -> top-k ----
+  return hipGetLastError() == hipSuccess ? OVM_OK : OVM_ERR_HIP;
+}
+
+// ---- stage 4: softmax + decode + threshold -> per-class NMS -> top-k ----
+int det2d_boxhead_post(const Det2dModel& m, Det2dWorkspace& w, const float* HO, int ldh, float* boxes, float* scores, int* classes,
+                       int* image_idx, float* scores_full, int* out_counts, hipStream_t s) {
+  const int B = m.B, K = m.num_classes, R = w.R, M = B * R;
+  if (B > w.maxB || K != w.num_classes || m.topk > w.topk || ldh < 5 * K + 1) return OVM_ERR_CAPACITY;
   const int Nc = w.Ncand;
+  int r;
   if (hipMemsetAsync(w.keys, 0xFF, sizeof(unsigned long long) * (size_t)B * Nc, s) != hipSuccess) return OVM_ERR_HIP;
-  hipLaunchKernelGGL(boxhead_dense_kernel, dim3((M + 3) / 4), dim3(256), 0, s, m.HO, 256, w.prop_boxes, w.prop_count, m.meta, R, K, M,
-                     m.score_thresh, scale_clamp, Nc, w.probs, w.dbox, w.keys);
+  hipLaunchKernelGGL(boxhead_dense_kernel, dim3((M + 3) / 4), dim3(256), 0, s, HO, ldh, w.prop_boxes, w.prop_count, m.meta, R, K, M,
+                     m.score_thresh, kScaleClamp, Nc, w.probs, w.dbox, w.keys);
   if ((r = sort_keys(w.keys, Nc, B, s))) return r;
   hipLaunchKernelGGL(cand_gather_kernel, dim3((Nc + 255) / 256, B), dim3(256), 0, s, w.keys, Nc, R, K, w.dbox, w.sbox, w.sgroup);
   if (hipMemsetAsync(w.gstart, 0, sizeof(int) * (size_t)B * K, s) != hipSuccess) return OVM_ERR_HIP;
@@ -509,6 +535,17 @@ int det2d_forward(const Det2dModel& m, Det2dWorkspace& w, float* boxes, float* s
   hipLaunchKernelGGL(boxhead_emit_kernel, dim3(1), dim3(1024), 0, s, w.keys, Nc, B, R, K, m.topk, w.dbox, w.probs, boxes, scores,
                      classes, image_idx, scores_full, out_counts);
   return hipGetLastError() == hipSuccess ? OVM_OK : OVM_ERR_HIP;
+}
+
+int det2d_forward(const Det2dModel& m, Det2dWorkspace& w, float* boxes, float* scores, int* classes, int* image_idx,
+                  float* scores_full, int* out_counts, hipStream_t s) {
+  if (m.B > w.maxB || m.pre_topk != w.pre_topk || m.num_classes != w.num_classes) return OVM_ERR_CAPACITY;
+  if (m.nlev != w.nlev) return OVM_ERR_CAPACITY;
+  int r;
+  if ((r = det2d_rpn_head(m, w, s))) return r;
+  if ((r = det2d_rpn_proposals(m, w, s))) return r;
+  if ((r = det2d_box_head(m, w, s))) return r;
+  return det2d_boxhead_post(m, w, m.HO, 256, boxes, scores, classes, image_idx, scores_full, out_counts, s);
 }
 
 // ------------------------------------------------------------------------------------------------

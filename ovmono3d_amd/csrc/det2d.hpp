@@ -52,8 +52,16 @@ struct Det2dModel {
 
 int det2d_alloc(Det2dWorkspace* w, int B, int nlev, const int* sides, int C, int num_classes, int maxR, int pre_topk, int post_topk, int topk,
                 std::vector<void*>* allocs);
+// RPN head GEMMs -> det2d_rpn_proposals -> ROIAlign + box-head GEMMs -> det2d_boxhead_post
 int det2d_forward(const Det2dModel& m, Det2dWorkspace& w, float* boxes, float* scores, int* classes, int* image_idx,
                   float* scores_full, int* out_counts, hipStream_t s);
+// The two post-processing stages of det2d_forward on their own (ovm_op_rpn_proposals / ovm_op_boxhead_post drive them with
+// chosen inputs). Proposals: w.rpn_o (head outputs) -> w.prop_boxes / prop_scores / prop_bidx / prop_count; reads m.B, nlev,
+// stride, anchor_sizes, anchor_ratios, pre_topk, rpn_nms, meta. Box head: HO [B*w.R][ldh] + w.prop_boxes / prop_count ->
+// image-major detections; reads m.B, num_classes, score_thresh, nms_thresh, topk, meta.
+int det2d_rpn_proposals(const Det2dModel& m, Det2dWorkspace& w, hipStream_t s);
+int det2d_boxhead_post(const Det2dModel& m, Det2dWorkspace& w, const float* HO, int ldh, float* boxes, float* scores, int* classes,
+                       int* image_idx, float* scores_full, int* out_counts, hipStream_t s);
 // Standalone class-agnostic NMS (torchvision.ops.nms semantics): keep_idx in decreasing-score order.
 int launch_nms_single(const float* boxes, const float* scores, const int* valid, int n, float thresh, int* keep_idx, int* n_keep,
                       hipStream_t s);

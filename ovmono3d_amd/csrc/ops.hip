@@ -241,6 +241,65 @@ int ovm_op_nms(const float* boxes, const float* scores, int32_t n, float thresh,
   return launch_nms_single(boxes, scores, nullptr, n, thresh, keep_idx, n_keep, (hipStream_t)stream);
 }
 
+namespace {
+// the clip sizes of `images` as a device-resident ImageMeta array (only net_h / net_w are read by the detection stages)
+ImageMeta* upload_clip_meta(Tmp& tmp, const OvmImage* images, int B) {
+  std::vector<ImageMeta> hm(B);
+  memset(hm.data(), 0, sizeof(ImageMeta) * B);
+  for (int b = 0; b < B; ++b) { hm[b].net_h = images[b].height; hm[b].net_w = images[b].width; }
+  ImageMeta* dm = tmp.get<ImageMeta>(B);
+  if (dm && hipMemcpy(dm, hm.data(), sizeof(ImageMeta) * B, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+  return dm;
+}
+}  // namespace
+
+int ovm_op_rpn_proposals(const float* const* levels_o, int32_t nlev, const int32_t* sides, const float* strides,
+                         const float* anchor_sizes, const float* anchor_ratios, const OvmImage* images, int32_t B,
+                         int32_t pre_topk, int32_t post_topk, float nms_thresh, float* prop_boxes, float* prop_scores,
+                         int32_t* prop_count, ovm_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!levels_o || !sides || !strides || !anchor_sizes || !anchor_ratios || !images || !prop_boxes || !prop_scores || !prop_count ||
+      B < 1 || pre_topk < 1 || post_topk < 1)
+    return OVM_ERR_INVALID;
+  if (nlev < 1 || nlev > kMaxLevels) return OVM_ERR_INVALID;
+  for (int l = 0; l < nlev; ++l) if (!levels_o[l] || sides[l] < 1) return OVM_ERR_INVALID;
+  Tmp tmp;                                       // frees the scratch on every exit path
+  Det2dWorkspace w;
+  int r = det2d_alloc(&w, B, nlev, sides, 0, 1, post_topk, pre_topk, post_topk, 1, &tmp.p);
+  if (r) return r;
+  Det2dModel m; memset(&m, 0, sizeof(m));
+  m.B = B; m.nlev = nlev; m.num_classes = 1; m.pre_topk = pre_topk; m.post_topk = post_topk; m.rpn_nms = nms_thresh;
+  for (int l = 0; l < nlev; ++l) { m.stride[l] = strides[l]; m.anchor_sizes[l] = anchor_sizes[l]; w.rpn_o[l] = const_cast<float*>(levels_o[l]); }
+  for (int a = 0; a < 3; ++a) m.anchor_ratios[a] = anchor_ratios[a];
+  if (!(m.meta = upload_clip_meta(tmp, images, B))) return OVM_ERR_HIP;
+  w.prop_boxes = prop_boxes; w.prop_scores = prop_scores; w.prop_count = prop_count;
+  r = det2d_rpn_proposals(m, w, s);
+  if (hipStreamSynchronize(s) != hipSuccess && !r) r = OVM_ERR_HIP;
+  return r;
+}
+
+int ovm_op_boxhead_post(const float* HO, int32_t ldh, const float* prop_boxes, const int32_t* prop_count, const OvmImage* images,
+                        int32_t B, int32_t R, int32_t K, float score_thresh, float nms_thresh, int32_t topk, float* boxes,
+                        float* scores, int32_t* classes, int32_t* image_idx, float* scores_full, int32_t* out_counts,
+                        ovm_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!HO || !prop_boxes || !prop_count || !images || !boxes || !scores || !classes || !image_idx || !out_counts || B < 1 || R < 1 ||
+      K < 1 || topk < 1 || ldh < 5 * (int64_t)K + 1)
+    return OVM_ERR_INVALID;
+  Tmp tmp;
+  Det2dWorkspace w;
+  const int side = 1;
+  int r = det2d_alloc(&w, B, 1, &side, 0, K, R, 1, R, topk, &tmp.p);
+  if (r) return r;
+  Det2dModel m; memset(&m, 0, sizeof(m));
+  m.B = B; m.nlev = 1; m.num_classes = K; m.pre_topk = 1; m.score_thresh = score_thresh; m.nms_thresh = nms_thresh; m.topk = topk;
+  if (!(m.meta = upload_clip_meta(tmp, images, B))) return OVM_ERR_HIP;
+  w.prop_boxes = const_cast<float*>(prop_boxes); w.prop_count = const_cast<int*>(prop_count);
+  r = det2d_boxhead_post(m, w, HO, ldh, boxes, scores, classes, image_idx, scores_full, out_counts, s);
+  if (hipStreamSynchronize(s) != hipSuccess && !r) r = OVM_ERR_HIP;
+  return r;
+}
+
 int ovm_gdino_postprocess(const float* pred_logits, int32_t nq, int32_t ld, const float* pred_boxes, const int32_t* spans, int32_t n_phrases,
                           int32_t img_h, int32_t img_w, float box_threshold, float nms_threshold, float* out_boxes, float* out_scores,
                           int32_t* out_classes, int32_t* n_out, ovm_stream_t stream) {

@@ -161,7 +161,7 @@ EXPORTS = [
     "ovm_rpn_box_forward", "ovm_gather_records", "ovm_gather_counts", "ovm_host_interp_pos_embed", "ovm_host_resize_pos_embed_aa", "ovm_host_sincos_pos_embed", "ovm_host_shard_range",
     "ovm_backbone_num_levels", "ovm_backbone_level",
     "ovm_op_split_f16", "ovm_op_interleave", "ovm_op_gemm", "ovm_op_layernorm", "ovm_op_attention", "ovm_op_roi_align",
-    "ovm_op_cube_decode", "ovm_op_nms", "ovm_debug_copy", "ovm_set_corun", "ovm_profile_enable", "ovm_profile_read",
+    "ovm_op_cube_decode", "ovm_op_nms", "ovm_op_rpn_proposals", "ovm_op_boxhead_post", "ovm_debug_copy", "ovm_set_corun", "ovm_profile_enable", "ovm_profile_read",
     "ovm_comm_unique_id", "ovm_comm_init", "ovm_comm_destroy", "ovm_tune_set", "ovm_gdino_postprocess", "ovm_box3d_iou", "ovm_eval_iou2d", "ovm_eval_match", "ovm_host_pil_bilinear_coeffs", "ovm_resize_bilinear_u8", "ovm_resize_bilinear_f32",
     "ovm_g_pack_weight", "ovm_g_linear", "ovm_g_layernorm", "ovm_g_bmm", "ovm_g_bmm2", "ovm_g_softmax", "ovm_g_softmax2", "ovm_g_eltwise", "ovm_g_gather_rows",
     "ovm_g_groupnorm", "ovm_g_msdeform", "ovm_g_sine_embed", "ovm_g_normalize_image", "ovm_g_topk", "ovm_g_rowmax",
@@ -229,6 +229,9 @@ def load() -> C.CDLL:
     lib.ovm_op_roi_align.argtypes = [vp, vp, vp, C.POINTER(i32), C.POINTER(f32), i32, i32, i32, i32, vp, vp, i32, vp, vp]
     lib.ovm_op_cube_decode.argtypes = [vp, i32, vp, vp, vp, vp, C.POINTER(OvmImage), i32, i32, f32, i32, vp, vp, vp]
     lib.ovm_op_nms.argtypes = [vp, vp, i32, f32, vp, vp, vp]
+    lib.ovm_op_rpn_proposals.argtypes = [C.POINTER(vp), i32, C.POINTER(i32), C.POINTER(f32), C.POINTER(f32), C.POINTER(f32),
+                                         C.POINTER(OvmImage), i32, i32, i32, f32, vp, vp, vp, vp]
+    lib.ovm_op_boxhead_post.argtypes = [vp, i32, vp, vp, C.POINTER(OvmImage), i32, i32, i32, f32, f32, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.ovm_debug_copy.argtypes = [vp, C.c_char_p, vp, i64, vp]
     lib.ovm_debug_copy.restype = i64
     lib.ovm_profile_enable.argtypes = [vp, i32]

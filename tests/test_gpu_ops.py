@@ -244,7 +244,9 @@ def test_cube_decode(device):
     assert keep[7] == 0 and keep.sum() == n - 1
 
 
-@pytest.mark.parametrize("n", [1, 7, 300, 900, 2500])
+# 2048 / 2049: either side of the sort padding; 4096: the cap, 64 mask words. Margin/discrepancy of |IoU - 0.5| over the pairs the
+# greedy pass tests (tests/det2d_oracle.py; seed = n): 2048 3.2e-06/2.0e-07, 2049 6.7e-05/1.8e-07, 4096 9.5e-06/2.0e-07
+@pytest.mark.parametrize("n", [1, 7, 300, 900, 2500, 2048, 2049, 4096])
 def test_nms_op(device, n):
     from oracle.roi_ops import nms
     g = torch.Generator().manual_seed(n)
@@ -253,6 +255,10 @@ def test_nms_op(device, n):
     boxes = torch.cat([xy, xy + wh], 1)
     scores = torch.rand(n, generator=g)
     ref = nms(boxes, scores, 0.5)
+    if n >= 2048:                      # the float32 reference is only as good as its closest call: every decision must be safe
+        import det2d_oracle as plain
+        M = plain.Margins()
+        assert plain.nms(boxes.numpy(), scores.numpy(), 0.5, M).tolist() == ref.tolist() and M.safe("iou"), M.summary(("iou",))
     db, ds = boxes.to(device), scores.to(device)
     keep = torch.full((n,), -1, dtype=torch.int32, device=device)
     nk = torch.zeros(1, dtype=torch.int32, device=device)
@@ -260,6 +266,61 @@ def test_nms_op(device, n):
     assert rc == 0
     k = int(nk.item())
     assert keep[:k].cpu().tolist() == ref.tolist()
+    assert (keep[k:] == -1).all()
+
+
+def _nms_dev(device, boxes, scores, thr):
+    n = len(boxes)
+    db = torch.from_numpy(np.ascontiguousarray(boxes, dtype=np.float32)).to(device)
+    ds = torch.from_numpy(np.ascontiguousarray(scores, dtype=np.float32)).to(device)
+    keep = torch.full((n,), -1, dtype=torch.int32, device=device)
+    nk = torch.full((1,), -3, dtype=torch.int32, device=device)
+    rc = _lib().ovm_op_nms(db.data_ptr(), ds.data_ptr(), n, thr, keep.data_ptr(), nk.data_ptr(), _stream())
+    return rc, keep.cpu().numpy(), int(nk.item())
+
+
+@pytest.mark.parametrize("thr", [0.5, 0.7])
+def test_nms_op_exact_edges(device, thr):
+    """Integer boxes: intersections and unions are exact in float32, so the only rounding is the division and the kept list must
+    equal the restatement's exactly. 200 boxes in decreasing score order except where noted."""
+    import det2d_oracle as plain
+    boxes = [[70 * (i % 14), 70 * (i // 14), 70 * (i % 14) + 64, 70 * (i // 14) + 64] for i in range(200)]   # disjoint 64 x 64 tiles
+    scores = [100.0 - i / 4.0 for i in range(200)]
+    for a, b_, c in ((63, 127, 128), (61, 64, 191)):     # A > B > C over three mask words: IoU(A,B) = IoU(B,C) = 7/9, IoU(A,C) = 3/5
+        x, y = boxes[a][0], boxes[a][1]
+        boxes[b_] = [x + 8, y, x + 72, y + 64]
+        boxes[c] = [x + 16, y, x + 80, y + 64]
+    boxes[10], boxes[11] = [2000, 0, 2064, 64], [2032, 0, 2064, 64]            # IoU exactly 1/2
+    boxes[12], boxes[13] = [2000, 100, 2040, 164], [2012, 100, 2040, 164]      # IoU exactly 7/10: 0.7f in float32, not above 0.7f
+    boxes[20] = [2000, 300, 2000, 364]                                         # zero area over box 21: kept, suppresses nothing
+    boxes[21] = [1990, 300, 2054, 364]
+    boxes[30], boxes[31] = [2200, 0, 2264, 64], [2202, 0, 2266, 64]            # -0.0 before +0.0: a tie, the lower index wins
+    boxes[32], boxes[33] = [2200, 100, 2264, 164], [2202, 100, 2266, 164]      # +0.0 before -0.0
+    scores[30], scores[31], scores[32], scores[33] = -0.0, 0.0, 0.0, -0.0
+    boxes[40], boxes[41] = [2400, 0, 2464, 64], [2402, 0, 2466, 64]            # +inf is an ordinary, highest score here
+    scores[41] = float("inf")
+    for i in (50, 52, 54):                                                     # equal scores: index order
+        scores[i] = scores[49]
+    boxes, scores = np.asarray(boxes, dtype=np.float32), np.asarray(scores, dtype=np.float32)
+    M = plain.Margins()
+    ref = plain.nms(boxes, scores, thr, M, exact_iou=True)
+    assert M.disc["iou_terms"] == 0.0
+    kept = set(ref.tolist())
+    assert {63, 61} <= kept and not ({127, 64} & kept)
+    assert ({128, 191} <= kept) if thr == 0.7 else not ({128, 191} & kept)      # at 0.5 A itself suppresses C (IoU 3/5)
+    assert {20, 21, 30, 32, 41} <= kept and not ({31, 33, 40} & kept)
+    assert ({10, 11} <= kept) and ((13 in kept) == (thr == 0.7))
+    rc, keep, k = _nms_dev(device, boxes, scores, thr)
+    assert rc == 0 and keep[:k].tolist() == ref.tolist()
+
+
+def test_nms_op_refuses_4097(device):
+    """Above the cap of 4096 the call returns OVM_ERR_CAPACITY before any device work: keep_idx and *n_keep stay untouched."""
+    n = 4097
+    boxes = np.tile(np.asarray([0, 0, 8, 8], dtype=np.float32), (n, 1))
+    rc, keep, k = _nms_dev(device, boxes, np.zeros(n, dtype=np.float32), 0.5)
+    assert rc == -5
+    assert k == -3 and (keep == -1).all()
 
 
 def test_gdino_glue_matches_oracle(device):
