@@ -67,6 +67,15 @@ typedef struct OvmConfig {
    *   OVM_TOWER_DINOV2 (0)  build_dino_backbone, reference cubercnn/modeling/backbone/dino.py:17-153: hub DINOv2, patch 14,
    *                         LayerScale, erf-GELU, LN eps 1e-6, pos-embed bicubic with the +0.1 offset; pyramid scales (2, 1, 0.5)
    *                         -> p2..p4 at strides 7 / 14 / 28; checkpoint keys backbone.net.vit.*
+   *                         Two variants of the hub's model table are selected by the checkpoint, not by this struct:
+   *                         - register tokens (vit*14_reg): key backbone.net.vit.register_tokens [1][R][D], R <= 16. Sequence = class,
+   *                           R registers, patches (T = 1 + R + G^2); the registers get no position row; the position table is
+   *                           resized with antialiased bicubic and no offset (the hub builds these models with
+   *                           interpolate_offset = 0, interpolate_antialias = True); prompt_depth is refused (the reference's
+   *                           fusion takes x[:, 1:] as the patch tokens, dino.py:91-105)
+   *                         - SwiGLU FFN (vitg14): keys blocks.N.mlp.w12.{weight [2 Hs][D], bias}, mlp.w3.{weight [D][Hs], bias}
+   *                           instead of mlp.fc1 / mlp.fc2; Hs = w12 rows / 2 (4096 for ViT-g), at most 4 D after padding to 32.
+   *                           y = w3(silu(h[:Hs]) * h[Hs:]), h = w12(LN2(x)). Both or neither of w12 / fc1 present: refused
    *   OVM_TOWER_CLIP   (1)  build_clip_backbone, reference cubercnn/modeling/backbone/clip.py:17-166: open_clip VisionTransformer
    *                         image tower (conv1 without bias, class_embedding, ln_pre, QuickGELU, LN eps 1e-5, no ln_post / proj),
    *                         patch 16, pos-embed resized with antialiased bicubic (:98-133); pyramid scales (4, 2, 1, 0.5)
@@ -217,6 +226,10 @@ int ovm_host_resize_pos_embed_aa(const float* pos, int32_t M, int32_t D, int32_t
  * transformers' get_2d_sincos_pos_embed_from_grid): out [1+G*G][D], row 0 zero; first D/2 columns encode the x coordinate, the
  * rest y, each as [sin | cos] over D/4 frequencies 10000^(-i/(D/4)); computed in double, stored fp32 */
 int ovm_host_sincos_pos_embed(int32_t D, int32_t G, float* out);
+/* Row order of the w12 image ovm_op_gemm_swiglu / the engine stream: perm[n], n < 2 * ceil32(Hs), is the row of the checkpoint's
+ * w12 [2 Hs][K] (gates [0, Hs), values [Hs, 2 Hs)) that packed row n holds, or -1 for a zero row. Packed rows [32 q, 32 q + 16) are the
+ * gates of outputs 16 q .. 16 q + 15, rows [32 q + 16, 32 q + 32) their values. */
+int ovm_host_swiglu_perm(int32_t Hs, int32_t* perm /* [2 * ceil32(Hs)] */);
 /* InferenceSampler contiguous shard [begin,end) of rank (reference cubercnn/data/build.py:320) */
 int ovm_host_shard_range(int64_t n_items, int32_t rank, int32_t world, int64_t* begin, int64_t* end);
 
@@ -227,6 +240,16 @@ int ovm_op_split_f16(const float* x, int64_t n, uint16_t* hi, uint16_t* lo, ovm_
 int ovm_op_gemm(const uint16_t* a_hi, const uint16_t* a_lo, int32_t lda, const uint16_t* w_hi, const uint16_t* w_lo,
                 int32_t M, int32_t N, int32_t K, const float* bias, int32_t relu, float* c, int32_t ldc,
                 int32_t precision, ovm_stream_t stream);
+/* The fused first linear of a SwiGLU FFN (dinov2 SwiGLUFFNFused.w12) with the activation in the GEMM epilogue:
+ *   out[m][j] = silu(a[m] . Wg[j] + bg[j]) * (a[m] . Wu[j] + bu[j]),  j < Hs, computed in fp32 and stored as a split fp16 image
+ * of Kp = ceil32(Hs) columns whose columns [Hs, Kp) are written as zeros (the K padding of the next linear).
+ * The weight image holds 2 Kp rows in the order of ovm_host_swiglu_perm (blocks of 16 gate rows | 16 value rows, so one lane of the
+ * MFMA epilogue owns gate j and value j), padded with zero rows to a multiple of 128 rows (256 when the op_gemm256 tune key forces the
+ * 256 x 256 kernel; its split-K hint is ignored: this epilogue never runs split over K); bias [2 Kp] in the same order or null.
+ * Operand layouts as ovm_op_gemm. out_lo = out_hi + 32 selects the interleaved image (ldo >= 2 Kp), otherwise plain arrays (ldo >= Kp). */
+int ovm_op_gemm_swiglu(const uint16_t* a_hi, const uint16_t* a_lo, int32_t lda, const uint16_t* w_hi, const uint16_t* w_lo,
+                       int32_t M, int32_t Hs, int32_t K, const float* bias, uint16_t* out_hi, uint16_t* out_lo, int32_t ldo,
+                       int32_t precision, ovm_stream_t stream);
 /* hi, lo [rows][K] (K % 32 == 0) -> out [rows][K/32][hi 32 | lo 32]: the interleaved operand image of the split-precision GEMM.
  * In split mode ovm_op_gemm takes w_hi = such an image and w_lo = w_hi + 32; activations may be plain arrays or an image
  * (a_lo = a_hi + 32, lda = 2K). */

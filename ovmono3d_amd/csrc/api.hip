@@ -57,6 +57,9 @@ struct OvmHandle {
   std::string err;
   std::vector<void*> allocs;
   int G = 0, G2 = 0, T = 0, Tpad = 0, D = 0, C = 0, Kpe = 640, npass = 1;
+  // DINOv2 variants, read off the checkpoint (create_impl): register tokens between the class token and the patches (T = 1 + nreg +
+  // G^2), and the fused SwiGLU FFN (ffn_hs = hidden width Hs, 0 = GELU MLP; ffn_k = Hs padded to the k-step, the K of w3 / width of its input image)
+  int nreg = 0, ffn_hs = 0, ffn_k = 0; float* reg = nullptr;
   int patch = 14, nlev = 3;          // by tower: 14 / 3 levels (DINOv2, scales 2 1 0.5) or 16 / 4 levels (CLIP, scales 4 2 1 0.5)
   float ln_eps = 1e-6f;             // LayerNorm eps of the ViT blocks (1e-6 dinov2, 1e-5 open_clip)
   int mlp_act = 0;                  // fc1 activation: 0 erf-GELU, 3 QuickGELU
@@ -230,6 +233,23 @@ int pack_linear(OvmHandle* h, const WeightMap& wm, const std::string& prefix, in
   return OVM_OK;
 }
 
+// dinov2 SwiGLUFFNFused.w12 [2 Hs][K] (rows [0, Hs) gates, [Hs, 2 Hs) values) -> the row order EPI_SWIGLU pairs (gemm.hpp): blocks of
+// 16 gates | 16 values, outputs padded to Kp (a multiple of 32, >= Hs) with zero rows and zero bias (silu(0) * 0 = 0 fills the pad columns)
+int pack_swiglu_w12(OvmHandle* h, const WeightMap& wm, const std::string& prefix, int Hs, int Kp, int K, PackedLinear* out) {
+  const float *w, *b;
+  int r = get_host(h, wm, prefix + ".weight", (int64_t)2 * Hs * K, &w); if (r) return r;
+  r = get_host(h, wm, prefix + ".bias", (int64_t)2 * Hs, &b); if (r) return r;
+  const int K32 = (Hs + 31) / 32 * 32;
+  if (Kp % 32 != 0 || Kp < K32) return OVM_ERR_INVALID;
+  std::vector<int32_t> perm((size_t)2 * K32);
+  if (ovm_host_swiglu_perm(Hs, perm.data()) != OVM_OK) return OVM_ERR_INVALID;
+  std::vector<float> v((size_t)2 * Kp * K, 0.f), bv((size_t)2 * Kp, 0.f);
+  for (int n = 0; n < 2 * K32; ++n)                        // rows beyond 2 ceil32(Hs) are all padding
+    if (perm[n] >= 0) { memcpy(&v[(size_t)n * K], w + (size_t)perm[n] * K, (size_t)K * 4); bv[n] = b[perm[n]]; }
+  r = upload_packed(h, v, 2 * Kp, K, K, out); if (r) return r;
+  return upload_vec(h, bv, &out->bias);
+}
+
 // conv weight [Cout][Cin][k][k] -> [Cout][(ky*k+kx)*Cin + c]
 int pack_conv(OvmHandle* h, const WeightMap& wm, const std::string& prefix, int Cout, int Cin, int k, PackedLinear* out,
               bool bias) {
@@ -341,7 +361,8 @@ int gemm(OvmHandle* h, const GemmParams& p_in, int epi, int amode, hipStream_t s
   // (at batch >= 4 the N = D contractions - proj, fc2 - reach that tile count too: 128 x 128 tiles fetch twice the operand bytes
   // per MFMA from L2, which is what bounds them at batch 1, where only 128-wide tiles fill the chip)
   if (g_use_gemm256 && amode == A_ROWMAJOR && gemm256_supported(p, h->npass) &&
-      (long)((p.M + 255) / 256) * (p.N / 256) >= 192 && (epi == EPI_STORE || epi == EPI_RESID || epi == EPI_GELU || epi == EPI_QKV))
+      (long)((p.M + 255) / 256) * (p.N / 256) >= 192 &&
+      (epi == EPI_STORE || epi == EPI_RESID || epi == EPI_GELU || epi == EPI_QKV || epi == EPI_SWIGLU))   // w12 of ViT-g: N = 8192, 192 tiles from T = 1281
     return launch_gemm256(p, epi, 1, s);
   // experiment knob (ovm_tune_set "gemm256_ksplit"): the long-K contractions with too few 256-wide tiles (fc2 at batch 1: 64 tiles,
   // K = 4096) as k-slices of 256 x 256 tiles + a reduce pass - half the operand fetch of 128 x 128 tiles
@@ -590,6 +611,16 @@ static void host_linear_rows(const float* src, int L, int C, int Lo, float* dst)
 
 extern "C" {
 
+int ovm_host_swiglu_perm(int32_t Hs, int32_t* perm) {
+  if (Hs < 1 || !perm) return OVM_ERR_INVALID;
+  const int Kp = (Hs + 31) / 32 * 32;
+  for (int n = 0; n < 2 * Kp; ++n) {
+    const int j = ((n >> 5) << 4) | (n & 15);                   // output of packed row n (inverse of swiglu_row)
+    perm[n] = j < Hs ? ((n & 16) ? Hs + j : j) : -1;
+  }
+  return OVM_OK;
+}
+
 int ovm_host_sincos_pos_embed(int32_t D, int32_t G, float* out) {
   if (D <= 0 || D % 4 != 0 || G <= 0) return OVM_ERR_INVALID;
   const int Q = D / 4;                                       // frequencies per (coordinate, sin / cos)
@@ -633,10 +664,41 @@ static int create_impl(const OvmConfig* cfg, const OvmTensor* weights, int32_t n
     h->err = "invalid config (canvas % patch, embed_dim = heads*64 and %128 (%256 for 4-level towers), precision in {1,3}, fpn_channels %64)";
     return OVM_ERR_INVALID;
   }
+  WeightMap wm;
+  for (int i = 0; i < n_weights; ++i) wm.m[weights[i].name] = &weights[i];
+  const std::string V = vit_prefix ? vit_prefix : (clip ? "backbone.net.visual." : "backbone.net.vit.");
+  if (!p16 && weights) {
+    // DINOv2 variants: OvmConfig carries no field for them, the checkpoint does (as has_box below). Host-only checks, before any device call.
+    if (const OvmTensor* t = wm.get(V + "register_tokens")) {      // hub *_reg models: [1][R][D]
+      if (t->ndim != 3 || t->shape[0] != 1 || t->shape[2] != c.embed_dim) { h->err = "bad shape for " + V + "register_tokens (expected [1][R][embed_dim])"; return OVM_ERR_SHAPE; }
+      if (t->shape[1] > 16) { h->err = V + "register_tokens: more than 16 register tokens"; return OVM_ERR_CAPACITY; }
+      h->nreg = (int)t->shape[1];
+    }
+    const std::string M0 = V + "blocks.0.mlp.";
+    const OvmTensor *w12 = wm.get(M0 + "w12.weight"), *fc1 = wm.get(M0 + "fc1.weight");
+    if (w12 && fc1) { h->err = "checkpoint has both " + M0 + "w12.weight and " + M0 + "fc1.weight"; return OVM_ERR_INVALID; }
+    if (!w12 && !fc1) { h->err = "missing weight: " + M0 + "fc1.weight or " + M0 + "w12.weight"; return OVM_ERR_MISSING_WEIGHT; }
+    if (w12) {                                                     // hub vitg14: SwiGLUFFNFused, w12 [2 Hs][D], w3 [D][Hs]
+      if (w12->ndim != 2 || w12->shape[0] < 2 || w12->shape[0] % 2 != 0 || w12->shape[1] != c.embed_dim) {
+        h->err = "bad shape for " + M0 + "w12.weight (expected [2 Hs][embed_dim])"; return OVM_ERR_SHAPE;
+      }
+      const int64_t Hs = w12->shape[0] / 2;
+      const OvmTensor* w3 = wm.get(M0 + "w3.weight");
+      if (!w3) { h->err = "missing weight: " + M0 + "w3.weight"; return OVM_ERR_MISSING_WEIGHT; }
+      if (w3->ndim != 2 || w3->shape[0] != c.embed_dim || w3->shape[1] != Hs) {
+        h->err = "bad shape for " + M0 + "w3.weight (expected [embed_dim][" + std::to_string(Hs) + "] after " + M0 + "w12.weight)"; return OVM_ERR_SHAPE;
+      }
+      // the activation image lives in F1, sized for the 4 D wide GELU MLP; its width is the K of w3: whole 32-wide k-groups of the
+      // split image, whole 64-wide k-steps in one-pass mode
+      const int64_t kq = c.precision == 3 ? 32 : 64, Kp = (Hs + kq - 1) / kq * kq;
+      if (Kp > 4 * (int64_t)c.embed_dim) { h->err = M0 + "w12.weight: hidden width exceeds 4 * embed_dim"; return OVM_ERR_CAPACITY; }
+      h->ffn_hs = (int)Hs; h->ffn_k = (int)Kp;
+    }
+  }
   HCHECK(h, hipSetDevice(device));
   h->npass = c.precision;
   h->D = c.embed_dim; h->C = c.fpn_channels;
-  h->G = c.canvas / h->patch; h->G2 = h->G * h->G; h->T = h->G2 + (sam ? 0 : 1); h->Tpad = (h->T + 63) / 64 * 64;
+  h->G = c.canvas / h->patch; h->G2 = h->G * h->G; h->T = h->G2 + (sam ? 0 : 1) + h->nreg; h->Tpad = (h->T + 63) / 64 * 64;
   const int D = h->D, C = h->C, G = h->G, G2 = h->G2, T = h->T, L = c.depth, B = c.max_batch, R = c.max_rois;
   {
     // The GEMM kernels address operands with 32-bit element offsets (gemm.hip: gemm_offsets_fit): refuse a max_batch / max_rois
@@ -653,11 +715,8 @@ static int create_impl(const OvmConfig* cfg, const OvmTensor* weights, int32_t n
         return OVM_ERR_CAPACITY;
       }
   }
-  WeightMap wm;
-  for (int i = 0; i < n_weights; ++i) wm.m[weights[i].name] = &weights[i];
   int r;
   const int P = h->patch, PP = P * P;
-  const std::string V = vit_prefix ? vit_prefix : (clip ? "backbone.net.visual." : "backbone.net.vit.");
   const std::string PEW = clip ? "conv1.weight" : (mae ? "embeddings.patch_embeddings.projection.weight" : "patch_embed.proj.weight");
   // ---- patch embed: [D][3][P][P] -> [D][(py*P+px)*3 + c]; P = 14: K padded 588 -> 640
   {
@@ -668,7 +727,7 @@ static int create_impl(const OvmConfig* cfg, const OvmTensor* weights, int32_t n
         for (int t = 0; t < PP; ++t) v[(size_t)o * 3 * PP + t * 3 + ch] = w[((size_t)o * 3 + ch) * PP + t];
     r = upload_packed(h, v, D, 3 * PP, h->Kpe, &h->pe); if (r) return r;
     const float* pos;
-    std::vector<float> pi((size_t)T * D);
+    std::vector<float> pi((size_t)(G2 + (sam ? 0 : 1)) * D);         // one row per patch (+ class row): register tokens have none
     if (clip) {                                            // conv1 has no bias (open_clip VisionTransformer)
       h->pe.bias = nullptr;
       r = upload_f32(h, wm, V + "class_embedding", D, &h->cls); if (r) return r;
@@ -689,8 +748,11 @@ static int create_impl(const OvmConfig* cfg, const OvmTensor* weights, int32_t n
       r = upload_f32(h, wm, V + "cls_token", D, &h->cls); if (r) return r;
       r = get_host(h, wm, V + "pos_embed", (int64_t)(1 + c.pos_grid * c.pos_grid) * D, &pos); if (r) return r;
       // timm ViT of MiDaS: the reference resizes with the CLIP tower's antialiased bicubic (midas_final.py:64-66); DINOv2: hub rule
-      r = midas ? ovm_host_resize_pos_embed_aa(pos, c.pos_grid, D, G, pi.data()) : ovm_host_interp_pos_embed(pos, c.pos_grid, D, G, pi.data());
+      // the hub's *_reg models are built with interpolate_offset = 0, interpolate_antialias = True: F.interpolate(size = (G, G),
+      // bicubic, antialias), the resize of the CLIP tower
+      r = (midas || h->nreg) ? ovm_host_resize_pos_embed_aa(pos, c.pos_grid, D, G, pi.data()) : ovm_host_interp_pos_embed(pos, c.pos_grid, D, G, pi.data());
       if (r) return r;
+      if (h->nreg && (r = upload_f32(h, wm, V + "register_tokens", (int64_t)h->nreg * D, &h->reg))) return r;
     }
     r = upload_vec(h, pi, &h->pos); if (r) return r;
   }
@@ -759,8 +821,13 @@ static int create_impl(const OvmConfig* cfg, const OvmTensor* weights, int32_t n
     }
     if ((r = pack_linear(h, wm, P + "attn.qkv", 3 * D, D, &y.qkv))) return r;
     if ((r = pack_linear(h, wm, P + "attn.proj", D, D, &y.proj))) return r;
-    if ((r = pack_linear(h, wm, P + "mlp.fc1", 4 * D, D, &y.fc1))) return r;
-    if ((r = pack_linear(h, wm, P + "mlp.fc2", D, 4 * D, &y.fc2))) return r;
+    if (h->ffn_hs) {                                       // SwiGLUFFNFused: w12 row-permuted for EPI_SWIGLU, w3 with K padded to the image width
+      if ((r = pack_swiglu_w12(h, wm, P + "mlp.w12", h->ffn_hs, h->ffn_k, D, &y.fc1))) return r;
+      if ((r = pack_linear(h, wm, P + "mlp.w3", D, h->ffn_hs, &y.fc2, true, h->ffn_k))) return r;
+    } else {
+      if ((r = pack_linear(h, wm, P + "mlp.fc1", 4 * D, D, &y.fc1))) return r;
+      if ((r = pack_linear(h, wm, P + "mlp.fc2", D, 4 * D, &y.fc2))) return r;
+    }
   }
   const int res = c.pooler_res, F = c.fc_dim;
   if (tower_only) h->nlev = 0;
@@ -956,6 +1023,11 @@ int ovm_backbone_forward(OvmHandle* h, const OvmImage* images, int32_t B, const 
     // would raise a TypeError here: refuse rather than silently drop it
     h->err = "prompt_depth is only defined for the DINOv2 tower (depth_fusion, dino.py:91-105)"; return OVM_ERR_INVALID;
   }
+  if (prompt_depth && h->nreg) {
+    // the reference's fusion takes x[:, 1:] as the patch tokens (dino.py:91-105): with register tokens its torch.cat of [B, C, R + HW]
+    // with the [B, 1, HW] depth raises
+    h->err = "prompt_depth is not defined for a register-token model (depth fusion takes x[:, 1:] as the patch tokens, dino.py:91-105)"; return OVM_ERR_INVALID;
+  }
   if (prompt_depth && !h->has_dfuse) { h->err = "prompt_depth given but depth_fusion weights absent / disabled"; return OVM_ERR_INVALID; }
   const int rr = backbone_launches(h, B, prompt_depth, depth_h, depth_w, s);
   if (rr) return rr;
@@ -973,7 +1045,7 @@ static int tower_launches(OvmHandle* h, int B, hipStream_t s) {
   const int D = h->D, G = h->G, G2 = h->G2, T = h->T, L = c.depth;
   // ---- patch embed (+ preprocess) ----
   KCHECK(h, launch_patch_gather(h->d_imgs, B, G, h->patch, h->Kpe, c.pixel_mean, c.pixel_std, h->PA.hi, h->PA.lo, s));
-  if (!h->sam) KCHECK(h, launch_cls_init(h->X, h->cls, h->pos, B, T, D, s));       // SAM: no class token (T = G^2)
+  if (!h->sam) KCHECK(h, launch_cls_init(h->X, h->cls, h->pos, h->reg, h->nreg, B, T, D, s));       // SAM: no class token (T = G^2)
   {
     GemmParams p = gp_base(h->PA, h->Kpe, h->pe, B * G2);
     p.X = h->X; p.ldx = D; p.pos = h->pos; p.G2 = G2; p.T = T;
@@ -1047,13 +1119,18 @@ static int tower_launches(OvmHandle* h, int B, hipStream_t s) {
     }
     }
     { ProfScope ps(h, OVM_PROF_LN, s); KCHECK(h, launch_ln_rows(h->X, D, M, D, y.ln2g, y.ln2b, eps, o, s)); }
-    {
+    const int Kf = h->ffn_hs ? h->ffn_k : 4 * D;              // width of the FFN's activation image = K of its second linear
+    if (h->ffn_hs) {                                          // w12 with silu(gate) * value in the epilogue
+      GemmParams p = gp_base(h->HN, am * D, y.fc1, M); p.a_il = il;
+      p.Ohi = h->F1.hi; p.Olo = h->F1.lo; p.ldo = am * Kf; p.o_il = il;
+      KCHECK(h, gemm(h, p, EPI_SWIGLU, A_ROWMAJOR, s, OVM_PROF_FC1));
+    } else {
       GemmParams p = gp_base(h->HN, am * D, y.fc1, M); p.a_il = il;
       p.Ohi = h->F1.hi; p.Olo = h->F1.lo; p.ldo = am * 4 * D; p.o_il = il; p.relu = h->mlp_act;
       KCHECK(h, gemm(h, p, EPI_GELU, A_ROWMAJOR, s, OVM_PROF_FC1));
     }
     {
-      GemmParams p = gp_base(h->F1, am * 4 * D, y.fc2, M); p.a_il = il;
+      GemmParams p = gp_base(h->F1, am * Kf, y.fc2, M); p.a_il = il;
       p.gamma = y.ls2; p.X = h->X; p.ldx = D;
       KCHECK(h, gemm(h, p, EPI_RESID, A_ROWMAJOR, s, OVM_PROF_FC2));
     }

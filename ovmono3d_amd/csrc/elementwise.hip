@@ -69,16 +69,18 @@ int launch_patch_gather(const ImageDesc* d_imgs, int B, int G, int patch, int Kp
   return hipGetLastError() == hipSuccess ? OVM_OK : OVM_ERR_HIP;
 }
 
-// x[b][0][:] = cls + pos[0]   (dinov2 prepare_tokens_with_masks, reference dino.py:75)
+// x[b][0][:] = cls + pos[0]   (dinov2 prepare_tokens_with_masks, reference dino.py:75); register models: x[b][1 + r][:] = reg[r], inserted
+// after the position table was added, so without a position row
 __global__ void cls_init_kernel(float* __restrict__ X, const float* __restrict__ cls, const float* __restrict__ pos,
-                                int B, int T, int D) {
+                                const float* __restrict__ reg, int R, int B, int T, int D) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B * D) return;
-  const int b = i / D, n = i - b * D;
-  X[(size_t)b * T * D + n] = cls[n] + pos[n];
+  const int lead = (1 + R) * D;
+  if (i >= B * lead) return;
+  const int b = i / lead, n = i - b * lead;
+  X[(size_t)b * T * D + n] = n < D ? cls[n] + pos[n] : reg[n - D];
 }
-int launch_cls_init(float* X, const float* cls, const float* pos, int B, int T, int D, hipStream_t s) {
-  hipLaunchKernelGGL(cls_init_kernel, dim3((B * D + 255) / 256), dim3(256), 0, s, X, cls, pos, B, T, D);
+int launch_cls_init(float* X, const float* cls, const float* pos, const float* reg, int R, int B, int T, int D, hipStream_t s) {
+  hipLaunchKernelGGL(cls_init_kernel, dim3((B * (1 + R) * D + 255) / 256), dim3(256), 0, s, X, cls, pos, reg, R, B, T, D);
   return hipGetLastError() == hipSuccess ? OVM_OK : OVM_ERR_HIP;
 }
 

@@ -26,9 +26,10 @@ static int launch_one(const GemmParams& p, hipStream_t s) {
     // leftover rows (the cls token of the 4097-token canvas) ride along as extra dot-product workgroups
     q.tail_begin = p.M - tail;
     q.M = q.tail_begin;
-    const int waves = gemm_tail_waves(p.N, BM / 32);
+    const int cols = gemm_tail_cols(p.N, EPI);
+    const int waves = gemm_tail_waves(cols, BM / 32);
     q.tail_waves = waves;
-    tail_blocks = tail * ((p.N + 4 * waves - 1) / (4 * waves));
+    tail_blocks = tail * ((cols + 4 * waves - 1) / (4 * waves));
   }
   const int tiles_m = (q.M + BM - 1) / BM;
   const int tiles_n = (p.N + 127) / 128;
@@ -61,7 +62,7 @@ static int launch_ws(const GemmParams& p, hipStream_t s) {
   // (also the GroundingDINO engine's Swin proj / fc2 GEMMs: 40-90 tiles with 16-64 k-tiles, residual epilogue: the reduce
   // pass applies any epilogue, EPI_QKV's V^T scatter excepted)
   const int min_nk = g_splitk >= 2 ? 16 : 32, min_steps = g_splitk >= 2 ? 4 : 8;     // experiment (gemm_splitk 2): slices of >= 4 k-steps from 16 k-steps on
-  if (g_splitk && (EPI != EPI_QKV && EPI != EPI_PATCH && EPI != EPI_CONVT) && tiles_full <= 96 && nk >= min_nk && p.N % 4 == 0) {
+  if (g_splitk && (EPI != EPI_QKV && EPI != EPI_PATCH && EPI != EPI_CONVT && EPI != EPI_SWIGLU) && tiles_full <= 96 && nk >= min_nk && p.N % 4 == 0) {
     int ks = 256 / tiles_full; if (ks > 16) ks = 16; if (ks > nk / min_steps) ks = nk / min_steps;
     if (ks > 1) {
       const int chunk = (nk + ks - 1) / ks;
@@ -86,8 +87,9 @@ static int launch_ws(const GemmParams& p, hipStream_t s) {
   if (q.ksplit == 1 && g_tail_rows && tail > 0 && tail <= 8 && p.M > 128 && p.K % 64 == 0) {
     q.tail_begin = p.M - tail;
     q.M = q.tail_begin;
-    q.tail_waves = gemm_tail_waves(p.N, 8);                    // of the 8 waves per workgroup; 4 columns per wave
-    tail_blocks = tail * ((p.N + 4 * q.tail_waves - 1) / (4 * q.tail_waves));
+    const int cols = gemm_tail_cols(p.N, EPI);
+    q.tail_waves = gemm_tail_waves(cols, 8);                   // of the 8 waves per workgroup; 4 columns per wave
+    tail_blocks = tail * ((cols + 4 * q.tail_waves - 1) / (4 * q.tail_waves));
   }
   const int tiles_m = (q.M + 127) / 128;
   const int tiles_n = (p.N + 127) / 128;
@@ -172,6 +174,9 @@ int launch_gemm(const GemmParams& p, int npass, int epi, int amode, hipStream_t 
     case EPI_QKV:   return launch_prec<EPI_QKV, A_ROWMAJOR>(p, npass, s);
     case EPI_PATCH: return launch_prec<EPI_PATCH, A_ROWMAJOR>(p, npass, s);
     case EPI_CONVT: return launch_prec<EPI_CONVT, A_ROWMAJOR>(p, npass, s);
+    case EPI_SWIGLU:
+      if (p.N % 64 != 0 || !p.Ohi) return OVM_ERR_INVALID;      // whole 32-row gate | value blocks, outputs padded to 32
+      return launch_prec<EPI_SWIGLU, A_ROWMAJOR>(p, npass, s);
   }
   return OVM_ERR_INVALID;
 }

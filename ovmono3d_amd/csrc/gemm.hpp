@@ -12,14 +12,14 @@
 //  * AMODE selects how a row of A is addressed: dense row-major, or implicit-GEMM 3x3 convolution
 //    over a zero-bordered NHWC fp16 image (k = tap*C + c).
 //  * EPI selects the fused epilogue (bias/LayerScale/residual, GELU, QKV head split with V^T
-//    layout, patch-embed + pos-embed, ConvTranspose 2x2 scatter, generic store).
+//    layout, patch-embed + pos-embed, ConvTranspose 2x2 scatter, SwiGLU gate * value, generic store).
 #pragma once
 #include "common.hpp"
 
 namespace ovm {
 
 enum AMode { A_ROWMAJOR = 0, A_CONV3X3 = 1 };
-enum Epi { EPI_STORE = 0, EPI_RESID = 1, EPI_GELU = 2, EPI_QKV = 3, EPI_PATCH = 4, EPI_CONVT = 5 };
+enum Epi { EPI_STORE = 0, EPI_RESID = 1, EPI_GELU = 2, EPI_QKV = 3, EPI_PATCH = 4, EPI_CONVT = 5, EPI_SWIGLU = 6 };
 
 struct GemmParams {
   const half_t* Ahi; const half_t* Alo; int lda;
@@ -56,7 +56,12 @@ struct GemmParams {
   int padH, padW;
   // EPI_QKV
   half_t *Qhi, *Qlo, *Khi, *Klo, *Vhi, *Vlo; int T, Tpad, heads; float qscale;
-  // EPI_PATCH: X[(b*T + c + p)][n] = acc + bias[n] + pos[(c+p)*N + n],   m = b*G2 + p, c = T - G2 leading (class) tokens (1 or 0)
+  // EPI_SWIGLU: the fused w12 of a SwiGLU FFN. W rows (and bias) are permuted at pack time in blocks of 32: packed rows
+  // [32 q, 32 q + 16) are the gates of outputs 16 q .. 16 q + 15, rows [32 q + 16, 32 q + 32) their values, so a lane's two
+  // neighbouring 16-column accumulator groups hold gate j and value j (swiglu_row). N = 2 * (outputs padded to 32; pad rows
+  // zero); writes silu(g) * u as the N/2-wide fp16 split image Ohi / Olo (ldo, o_il as EPI_GELU). Never split over K.
+  // EPI_PATCH: X[(b*T + c + p)][n] = acc + bias[n] + pos[(c1+p)*N + n],   m = b*G2 + p, c = T - G2 leading tokens (class + register
+  // tokens, or none), c1 = 1 if the table has a class row (c > 0): the table is indexed by patch, register tokens have no row
   const float* pos; int G2;
   // EPI_CONVT: m = (b, i, j) over GxG, n = (a*2 + bb)*Cout + co -> NHWC [B][2G][2G][Cout]
   int G, Cout;
@@ -124,9 +129,47 @@ __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + e
 // open_clip QuickGELU (the activation of the OpenAI CLIP weights): x * sigmoid(1.702 x)
 __device__ __forceinline__ float gelu_quick(float x) { return x / (1.0f + expf(-1.702f * x)); }
 
+// EPI_SWIGLU: packed W row of the gate of output j (its value sits 16 rows further); host twin: ovm_host_swiglu_perm
+__host__ __device__ __forceinline__ int swiglu_row(int j) { return ((j >> 4) << 5) | (j & 15); }
+// columns a leftover-row wave group iterates over: the outputs
+__host__ __device__ __forceinline__ int gemm_tail_cols(int N, int epi) { return epi == EPI_SWIGLU ? N >> 1 : N; }
+
+// g[r] / u[r]: raw gate / value accumulators of (m, output j + r); j is a multiple of 4 and N/2 a multiple of 32 (launcher)
+__device__ __forceinline__ void epilogue_swiglu4(const GemmParams& p, int m, int j, f32x4 g, f32x4 u) {
+  if (j >= (p.N >> 1)) return;
+  if (p.bias) {
+    const int r0 = swiglu_row(j);
+    g += *(const f32x4*)(p.bias + r0);
+    u += *(const f32x4*)(p.bias + r0 + 16);
+  }
+  half4 h, l;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    half_t hh, ll; split_f16(g[r] / (1.0f + expf(-g[r])) * u[r], hh, ll); h[r] = hh; l[r] = ll;
+  }
+  const size_t o = (size_t)m * p.ldo + (p.o_il ? il_col(j) : j);
+  *(half4*)(p.Ohi + o) = h;
+  if (p.Olo) *(half4*)(p.Olo + o) = l;
+}
+
+// EPI_SWIGLU store of a wave's 64 x 64 staging tile (row-major fp32, packed columns nb .. nb + 63 = 32 outputs): 8 lanes cover a
+// row's 32 outputs (64 B of hi + 64 B of lo: one line of the interleaved image), a lane reads gate and value 16 columns apart
+template <int TLD>
+__device__ __forceinline__ void swiglu_store_tile(const GemmParams& p, const float* tile, int mrow0, int nb, int lane) {
+  const int oc = (lane & 7) * 4, gc = swiglu_row(oc);
+#pragma unroll 4
+  for (int it = 0; it < 8; ++it) {
+    const int row = it * 8 + (lane >> 3);
+    const f32x4 g = *(const f32x4*)(tile + row * TLD + gc);
+    const f32x4 u = *(const f32x4*)(tile + row * TLD + gc + 16);
+    if (mrow0 + row < p.M) epilogue_swiglu4(p, mrow0 + row, (nb >> 1) + oc, g, u);
+  }
+}
+
 template <int EPI>
 __device__ __forceinline__ void epilogue4(const GemmParams& p, int m, int n, f32x4 v) {
   // v[r] belongs to (m, n + r); n is a multiple of 4; caller guarantees m < M; n + r may be >= N.
+  if (EPI == EPI_SWIGLU) return;                  // pairs two accumulator groups: epilogue_swiglu4 (the launchers keep it off split-K)
   if (n >= p.N) return;
   float b4[4] = {0.f, 0.f, 0.f, 0.f};
   if (p.bias) {
@@ -187,7 +230,7 @@ __device__ __forceinline__ void epilogue4(const GemmParams& p, int m, int n, f32
   } else if (EPI == EPI_PATCH) {
     const int b = m / p.G2, pp = m - b * p.G2, c0 = p.T - p.G2;
     float* x = p.X + ((size_t)b * p.T + c0 + pp) * p.ldx + n;
-    const float* ps = p.pos + (size_t)(c0 + pp) * p.N + n;
+    const float* ps = p.pos + (size_t)((c0 > 0 ? 1 : 0) + pp) * p.N + n;
     for (int r = 0; r < 4 && n + r < p.N; ++r) x[r] = v[r] + b4[r] + ps[r];
   } else if (EPI == EPI_CONVT) {
     const int q = n / p.Cout, co = n - q * p.Cout;       // q = a*2 + bb; Cout % 4 == 0
@@ -379,6 +422,11 @@ __global__ __launch_bounds__(BM * 2) void gemm_kernel(const GemmParams p) {
   for (int mi = 0; mi < 4; ++mi) {
     const int m = m0 + wm * 64 + mi * 16 + fr;
     if (m >= p.M) continue;
+    if (EPI == EPI_SWIGLU) {                       // groups (0, 1) and (2, 3): gates and values of 16 outputs each
+#pragma unroll
+      for (int ni = 0; ni < 4; ni += 2) epilogue_swiglu4(p, m, ((n0 + wn * 64) >> 1) + ni * 8 + fq * 4, acc[ni][mi], acc[ni + 1][mi]);
+      continue;
+    }
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni) {
       const int n = n0 + wn * 64 + ni * 16 + fq * 4;
@@ -580,7 +628,9 @@ __global__ __launch_bounds__(512) void gemm_ws_kernel(const GemmParams p) {
   const int mb = m0 + wm * 64, nb = n0 + wn * 64;
   bool vt_tile = false;
   if (EPI == EPI_QKV && ksplit == 1) vt_tile = (nb / (p.N / 3)) == 2;   // wave-uniform: head blocks are 64 wide
-  if (!vt_tile) {
+  if (EPI == EPI_SWIGLU) {
+    swiglu_store_tile<TLD>(p, tile, mb, nb, lane);
+  } else if (!vt_tile) {
     const int col = (lane & 15) * 4;
 #pragma unroll 4
     for (int it = 0; it < 16; ++it) {
@@ -640,14 +690,19 @@ __device__ __forceinline__ void gemm_tail_body(const GemmParams& p, int tb) {
   const int lane = threadIdx.x & 63;
   const int waves = p.tail_waves > 0 ? p.tail_waves : (int)(blockDim.x >> 6);
   if ((int)(threadIdx.x >> 6) >= waves) return;
-  const int groups_per_row = (p.N + 4 * waves - 1) / (4 * waves);
+  // EPI_SWIGLU: a wave computes 4 outputs = 4 gate rows + the 4 value rows 16 further (n counts outputs)
+  constexpr int NR = (EPI == EPI_SWIGLU) ? 8 : 4;
+  const int NC = gemm_tail_cols(p.N, EPI);
+  const int groups_per_row = (NC + 4 * waves - 1) / (4 * waves);
   const int row = tb / groups_per_row;
   const int n = ((tb - row * groups_per_row) * waves + (threadIdx.x >> 6)) * 4;
   const int m = p.tail_begin + row;
-  if (n >= p.N || m >= p.M_total) return;
+  if (n >= NC || m >= p.M_total) return;
   constexpr bool AI = AIL && NPASS == 3, WI = NPASS == 3;
   const uint32_t arow = a_row_off<AMODE, AI>(p, m);
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  float acc[NR];
+#pragma unroll
+  for (int r = 0; r < NR; ++r) acc[r] = 0.f;
 #pragma unroll 2                                   // two iterations' loads in flight: the leftover-row round is latency, not bandwidth
   for (int k0 = lane * 8; k0 < p.K; k0 += 512) {
     const uint32_t ao = arow + a_k_off<AMODE, AI>(p, k0 & ~63) + (AI ? ((k0 & 32) * 2 + (k0 & 31)) : (k0 & 63));
@@ -661,8 +716,9 @@ __device__ __forceinline__ void gemm_tail_body(const GemmParams& p, int tb) {
       for (int j = 0; j < 8; ++j) a[j] += (float)al[j];
     }
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const size_t wo = (size_t)(n + r) * p.ldw + (WI ? ((size_t)(k0 >> 5) * 64 + (k0 & 31)) : (size_t)k0);
+    for (int r = 0; r < NR; ++r) {
+      const int wr = (EPI == EPI_SWIGLU) ? swiglu_row(n) + (r & 3) + (r >> 2) * 16 : n + r;
+      const size_t wo = (size_t)wr * p.ldw + (WI ? ((size_t)(k0 >> 5) * 64 + (k0 & 31)) : (size_t)k0);
       const half8 wh = *(const half8*)(p.Whi + wo);
       float w[8];
 #pragma unroll
@@ -676,16 +732,21 @@ __device__ __forceinline__ void gemm_tail_body(const GemmParams& p, int tb) {
       for (int j = 0; j < 8; ++j) acc[r] = fmaf(a[j], w[j], acc[r]);
     }
   }
-  f32x4 v;
+  f32x4 v, u = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int r = 0; r < 4; ++r) v[r] = wave_sum(acc[r]);
+  if (EPI == EPI_SWIGLU) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) u[r] = wave_sum(acc[NR - 4 + r]);
+  }
   if (lane == 0) {
     GemmParams q = p; q.M = p.M_total;
-    epilogue4<EPI>(q, m, n, v);
+    if (EPI == EPI_SWIGLU) epilogue_swiglu4(q, m, n, v, u); else epilogue4<EPI>(q, m, n, v);
   }
 }
 
 // waves per leftover-row workgroup (4 columns each) such that a row's columns spread over >= 128 workgroups where N allows
+// (N = gemm_tail_cols)
 inline int gemm_tail_waves(int N, int max_waves) { int w = max_waves; while (w > 1 && (N + 4 * w - 1) / (4 * w) < 128) w >>= 1; return w; }
 // Host launcher (defined in gemm.hip). npass in {1,3}.
 int launch_gemm(const GemmParams& p, int npass, int epi, int amode, hipStream_t stream);

@@ -222,11 +222,12 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmParams p) {
         }
       __builtin_amdgcn_wave_barrier();
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      if (EPI == EPI_SWIGLU) swiglu_store_tile<TLD>(p, tile, mrow0, nb, lane);
       const int col = (lane & 15) * 4;
       bool mine = false;
 #pragma unroll
       for (int ni = 0; ni < NTW; ++ni) mine = mine || ((col >> 4) == ni && !vt[ni]);
-      if (mine) {
+      if (mine && EPI != EPI_SWIGLU) {
 #pragma unroll 4
         for (int it = 0; it < 16; ++it) {
           const int row = it * 4 + (lane >> 4);
@@ -314,12 +315,13 @@ int launch256(const GemmParams& p, int want_split, hipStream_t s) {
   const int tail = p.M % 256;
   if (tail > 0 && tail <= 8 && p.M > 256) {             // leftover rows (the cls token): dot-product workgroups of the same launch
     q.tail_begin = p.M - tail; q.M = q.tail_begin;
-    q.tail_waves = gemm_tail_waves(p.N, 8);
-    tail_blocks = tail * ((p.N + 4 * q.tail_waves - 1) / (4 * q.tail_waves));
+    const int cols = gemm_tail_cols(p.N, EPI);
+    q.tail_waves = gemm_tail_waves(cols, 8);
+    tail_blocks = tail * ((cols + 4 * q.tail_waves - 1) / (4 * q.tail_waves));
   }
   const int tiles_m = (q.M + 255) / 256, tiles_n = (p.N + 255) / 256;
   const int nk = p.K / 32;
-  int ks = want_split;
+  int ks = (EPI == EPI_SWIGLU) ? 1 : want_split;           // the reduce pass has no gate * value epilogue
   if (ks > 1 && p.N % 4 == 0) {                           // (leftover rows keep their dot-product workgroups: those run the whole K and store final values)
     if (ks > nk / 8) ks = nk / 8;
     if (ks > 1) {
@@ -385,6 +387,7 @@ int launch_gemm256(const GemmParams& p, int epi, int ksplit_hint, hipStream_t s)
     case EPI_RESID: return launch256<EPI_RESID>(p, ksplit_hint, s);
     case EPI_GELU:  return launch256<EPI_GELU>(p, ksplit_hint, s);
     case EPI_QKV:   return launch256<EPI_QKV>(p, ksplit_hint, s);
+    case EPI_SWIGLU: return p.Ohi ? launch256<EPI_SWIGLU>(p, 1, s) : OVM_ERR_INVALID;
   }
   return OVM_ERR_INVALID;
 }

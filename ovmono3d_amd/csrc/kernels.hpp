@@ -70,7 +70,7 @@ struct CubeDecodeParams {
 int launch_patch_gather(const ImageDesc* d_imgs, int B, int G, int patch, int Kpad, const float* mean, const float* stdv,
                         half_t* Ahi, half_t* Alo, hipStream_t s);
 int launch_ln_gelu_split(half_t* hi, half_t* lo, int M, int D, const float* gamma, const float* beta, float eps, hipStream_t s);
-int launch_cls_init(float* X, const float* cls, const float* pos, int B, int T, int D, hipStream_t s);
+int launch_cls_init(float* X, const float* cls, const float* pos, const float* reg, int R, int B, int T, int D, hipStream_t s);
 int launch_ln_rows(const float* X, int ldx, int M, int D, const float* gamma, const float* beta, float eps,
                    const LnOut& o, hipStream_t s);
 int launch_tokens_cast(const float* X, int B, int T, int G2, int D, int ldo, const float* depth_tok,

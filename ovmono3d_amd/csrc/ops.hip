@@ -89,6 +89,31 @@ int ovm_op_gemm(const uint16_t* a_hi, const uint16_t* a_lo, int32_t lda, const u
   return launch_gemm(p, precision, EPI_STORE, A_ROWMAJOR, (hipStream_t)stream);
 }
 
+// w12 of a SwiGLU FFN with silu(gate) * value in the epilogue: out[M][Hs] = silu(A Wg^T + bg) * (A Wu^T + bu) as a split fp16 image
+// (see include/ovm3d.h for the row order of the weight image)
+int ovm_op_gemm_swiglu(const uint16_t* a_hi, const uint16_t* a_lo, int32_t lda, const uint16_t* w_hi, const uint16_t* w_lo,
+                       int32_t M, int32_t Hs, int32_t K, const float* bias, uint16_t* out_hi, uint16_t* out_lo, int32_t ldo,
+                       int32_t precision, ovm_stream_t stream) {
+  if (!a_hi || !w_hi || !out_hi || Hs < 1 || (precision != 1 && precision != 3)) return OVM_ERR_INVALID;
+  const int Kp = (Hs + 31) / 32 * 32;
+  GemmParams p; memset(&p, 0, sizeof(p));
+  p.Ahi = (const half_t*)a_hi; p.Alo = (const half_t*)a_lo; p.lda = lda;
+  p.Whi = (const half_t*)w_hi; p.Wlo = (const half_t*)w_lo;
+  if (precision == 3) {
+    if (w_lo != w_hi + 32 || !out_lo) return OVM_ERR_INVALID;
+    p.a_il = (a_lo == a_hi + 32);
+  }
+  p.o_il = (out_lo == out_hi + 32);
+  if (ldo < (p.o_il ? 2 : 1) * Kp) return OVM_ERR_SHAPE;
+  p.M = M; p.N = 2 * Kp; p.K = K; p.bias = bias;
+  p.Ohi = (half_t*)out_hi; p.Olo = (half_t*)out_lo; p.ldo = ldo;
+  if (g_op_gemm256 > 0) {                                     // forced onto the 256 x 256 kernel (no split-K with this epilogue)
+    if (!gemm256_supported(p, precision)) return OVM_ERR_INVALID;
+    return launch_gemm256(p, EPI_SWIGLU, 1, (hipStream_t)stream);
+  }
+  return launch_gemm(p, precision, EPI_SWIGLU, A_ROWMAJOR, (hipStream_t)stream);
+}
+
 namespace {
 __global__ void interleave_kernel(const half_t* __restrict__ hi, const half_t* __restrict__ lo, long rows, int K, half_t* __restrict__ out) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;

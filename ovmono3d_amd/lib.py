@@ -160,7 +160,7 @@ EXPORTS = [
     "ovm_create", "ovm_destroy", "ovm_last_error", "ovm_version", "ovm_abi_sizeof", "ovm_backbone_forward", "ovm_cube_forward",
     "ovm_rpn_box_forward", "ovm_gather_records", "ovm_gather_counts", "ovm_host_interp_pos_embed", "ovm_host_resize_pos_embed_aa", "ovm_host_sincos_pos_embed", "ovm_host_shard_range",
     "ovm_backbone_num_levels", "ovm_backbone_level",
-    "ovm_op_split_f16", "ovm_op_interleave", "ovm_op_gemm", "ovm_op_layernorm", "ovm_op_attention", "ovm_op_roi_align",
+    "ovm_op_split_f16", "ovm_op_interleave", "ovm_op_gemm", "ovm_op_gemm_swiglu", "ovm_host_swiglu_perm", "ovm_op_layernorm", "ovm_op_attention", "ovm_op_roi_align",
     "ovm_op_cube_decode", "ovm_op_nms", "ovm_op_rpn_proposals", "ovm_op_boxhead_post", "ovm_debug_copy", "ovm_set_corun", "ovm_profile_enable", "ovm_profile_read",
     "ovm_comm_unique_id", "ovm_comm_init", "ovm_comm_destroy", "ovm_tune_set", "ovm_gdino_postprocess", "ovm_box3d_iou", "ovm_eval_iou2d", "ovm_eval_match", "ovm_host_pil_bilinear_coeffs", "ovm_resize_bilinear_u8", "ovm_resize_bilinear_f32",
     "ovm_g_pack_weight", "ovm_g_linear", "ovm_g_layernorm", "ovm_g_bmm", "ovm_g_bmm2", "ovm_g_softmax", "ovm_g_softmax2", "ovm_g_eltwise", "ovm_g_gather_rows",
@@ -224,6 +224,8 @@ def load() -> C.CDLL:
     lib.ovm_op_split_f16.argtypes = [vp, i64, vp, vp, vp]
     lib.ovm_op_interleave.argtypes = [vp, vp, i64, i32, vp, vp]
     lib.ovm_op_gemm.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, vp, i32, vp, i32, i32, vp]
+    lib.ovm_op_gemm_swiglu.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, vp]
+    lib.ovm_host_swiglu_perm.argtypes = [i32, vp]
     lib.ovm_op_layernorm.argtypes = [vp, i32, i32, vp, vp, f32, vp, vp]
     lib.ovm_op_attention.argtypes = [vp, i32, i32, i32, vp, i32, vp]
     lib.ovm_op_roi_align.argtypes = [vp, vp, vp, C.POINTER(i32), C.POINTER(f32), i32, i32, i32, i32, vp, vp, i32, vp, vp]

@@ -116,6 +116,9 @@ class SimpleFeaturePyramidWithDepth:
         else:
             native, keep = self.engine.make_images(x)
             B = len(x)
+        if prompt_depth is not None and self.net.has_registers:
+            # the reference's fusion takes x[:, 1:] as the patch tokens (dino.py:91-105): with register tokens its torch.cat raises
+            raise ValueError("prompt_depth is not defined for a register-token model (depth fusion takes x[:, 1:] as the patch tokens)")
         feats = self.engine.backbone_forward(native, B, prompt_depth, export=self.export_features)
         if feats is not None:
             return feats

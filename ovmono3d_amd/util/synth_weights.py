@@ -23,12 +23,35 @@ VIT_ARCH = {
     "vitb14": (768, 12, 12),
     "vitl14": (1024, 24, 16),
     "vitg14": (1536, 40, 24),
-    # tiny architecture for fast CPU tests (not a hub model)
+    # the hub's register-token models (dino.py:31 has_registers): 4 register tokens after the class token
+    "vits14_reg": (384, 12, 6),
+    "vitb14_reg": (768, 12, 12),
+    "vitl14_reg": (1024, 24, 16),
+    "vitg14_reg": (1536, 40, 24),
+    # tiny architectures for fast CPU tests (not hub models): plain, with registers, with the SwiGLU FFN, with both
     "vittest14": (128, 2, 2),
+    "vittest14_reg": (128, 2, 2),
+    "vitgtest14": (128, 2, 2),
+    "vitgtest14_reg": (128, 2, 2),
     # ViT-L width at depth 2: full-size token / channel geometry (T = 4097 or 5477, D = 1024, 16 heads) at a cost the CPU
-    # oracle finishes in seconds (not a hub model)
+    # oracle finishes in seconds (not a hub model); likewise ViT-g (SwiGLU, Hs = 4096) and ViT-L with registers (T = 4101 at 896)
     "vitl14_d2": (1024, 2, 16),
+    "vitg14_d2": (1536, 2, 24),
+    "vitl14_reg_d2": (1024, 2, 16),
 }
+
+
+def vit_variant(model_name: str):
+    """(number of register tokens, FFN kind) of a ``VIT_ARCH`` name, as the hub builds them: ``*_reg`` models carry 4 register
+    tokens; the ``vitg*`` models use the fused SwiGLU FFN (``mlp.w12`` / ``mlp.w3``), every other one the GELU MLP."""
+    if model_name not in VIT_ARCH:
+        raise KeyError(model_name)
+    return (4 if "_reg" in model_name else 0), ("swiglu" if model_name.startswith("vitg") else "mlp")
+
+
+def swiglu_hidden(D: int) -> int:
+    """Hidden width of dinov2's SwiGLUFFNFused for mlp_ratio 4: (int(4 D * 2 / 3) + 7) // 8 * 8 (1536 -> 4096)."""
+    return (int(4 * D * 2 / 3) + 7) // 8 * 8
 
 
 CLIP_ARCH = {
@@ -82,10 +105,15 @@ def synth_state_dict(model_name: str = "vitl14", num_classes: int = 50, fpn_chan
     if model_name in SAM_ARCH:
         return synth_sam_state_dict(model_name, num_classes, fpn_channels, fc_dim, pooler_res, seed, num_anchors)
     D, L, _ = VIT_ARCH[model_name]
+    n_reg, ffn = vit_variant(model_name)
     g = torch.Generator().manual_seed(seed)
     sd: Dict[str, torch.Tensor] = {}
     V = "backbone.net.vit."
     sd[V + "cls_token"] = torch.randn(1, 1, D, generator=g) * 0.02
+    if n_reg:
+        # own generator: the other tensors of a *_reg model equal those of its plain twin. Non-zero (the hub initialises zeros, which
+        # would hide an indexing error)
+        sd[V + "register_tokens"] = torch.randn(1, n_reg, D, generator=torch.Generator().manual_seed(seed + 7919)) * 0.5
     sd[V + "pos_embed"] = torch.randn(1, 1 + pos_grid * pos_grid, D, generator=g) * 0.02
     sd[V + "mask_token"] = torch.zeros(1, D)
     w = torch.randn(D, 3, 14, 14, generator=g) * (1.0 / math.sqrt(588.0))
@@ -99,8 +127,13 @@ def synth_state_dict(model_name: str = "vitl14", num_classes: int = 50, fpn_chan
         sd[B + "attn.qkv.weight"], sd[B + "attn.qkv.bias"] = _lin(g, 3 * D, D, std=2.0 / math.sqrt(D))
         sd[B + "attn.proj.weight"], sd[B + "attn.proj.bias"] = _lin(g, D, D)
         sd[B + "ls1.gamma"] = (0.5 + torch.rand(D, generator=g)) * 0.5
-        sd[B + "mlp.fc1.weight"], sd[B + "mlp.fc1.bias"] = _lin(g, 4 * D, D)
-        sd[B + "mlp.fc2.weight"], sd[B + "mlp.fc2.bias"] = _lin(g, D, 4 * D)
+        if ffn == "swiglu":
+            Hs = swiglu_hidden(D)
+            sd[B + "mlp.w12.weight"], sd[B + "mlp.w12.bias"] = _lin(g, 2 * Hs, D, std=1.5 / math.sqrt(D), bias_std=0.1)
+            sd[B + "mlp.w3.weight"], sd[B + "mlp.w3.bias"] = _lin(g, D, Hs)
+        else:
+            sd[B + "mlp.fc1.weight"], sd[B + "mlp.fc1.bias"] = _lin(g, 4 * D, D)
+            sd[B + "mlp.fc2.weight"], sd[B + "mlp.fc2.bias"] = _lin(g, D, 4 * D)
         sd[B + "ls2.gamma"] = (0.5 + torch.rand(D, generator=g)) * 0.5
     sd[V + "norm.weight"] = torch.ones(D)
     sd[V + "norm.bias"] = torch.zeros(D)
