@@ -150,7 +150,7 @@ int ovm_destroy(OvmHandle* h);
 const char* ovm_last_error(const OvmHandle* h);
 const char* ovm_version(void);
 /* sizeof() of a struct of this header as the library was compiled ("OvmConfig", "OvmTensor", "OvmImage", "OvmDet3D",
- * "OvmGdinoConfig", "OvmJpegInfo", "OvmSceneInput", "OvmSceneLayout", "OvmSceneSegment", "OvmEvalCell", "OvmSamConfig"), -1 for an unknown name: lets a binding check its mirror of the layout before the first call. */
+ * "OvmGdinoConfig", "OvmJpegInfo", "OvmSceneInput", "OvmSceneLayout", "OvmSceneSegment", "OvmEvalCell", "OvmSamConfig", "OvmDepthProConfig"), -1 for an unknown name: lets a binding check its mirror of the layout before the first call. */
 int ovm_abi_sizeof(const char* struct_name);
 
 /* --- backbone: build_dino_backbone(...).forward(x, prompt_depth) -> {p2,p3,p4}
@@ -578,7 +578,7 @@ int ovm_render_scene(const OvmSceneLayout* layout, const OvmSceneSegment* grid, 
  * The training-free baseline of the reference (tools/ovmono3d_geo.py:127-258): a 2D box's mask pixels are un-projected with a
  * metric depth map, the cloud is yaw-aligned by the first principal direction of its (x, z) columns, outliers are removed with
  * DBSCAN (up to `trials` runs, eps doubling), and the box is the extent of the kept points. Of the two networks in front of it,
- * SAM is in this library (OvmSam below: its planes are what `mask` takes); Depth Pro is not: depth arrives as an array.
+ * SAM and Depth Pro are in this library (OvmSam, OvmDepthPro below: their planes and depth maps are what `mask` and `depth` take).
  *
  * Steps, all in fp64 as the reference (the numpy restatement is tests/geo_oracle.py):
  *  1. points, row-major over the mask pixels: z = depth[y][x]; p = (z (x - cx) / fx, -(z (y - cy) / fy), -z)
@@ -719,6 +719,59 @@ int ovm_sam_predict_boxes(OvmSam* sam, const float* boxes_xyxy, int32_t n, int32
  * [3][S][S] (the encoder's input as its patch rows hold it), "neck" [G][G][C], "dense_pe" [G][G][C]; of the last chunk of the
  * last predict call: "sparse" [n][2][C], "tokens_out" [n][3 + num_mask_tokens][C]. */
 int64_t ovm_sam_debug_copy(OvmSam* sam, const char* name, float* dst, int64_t capacity, ovm_stream_t stream);
+
+/* ---- Depth Pro, metric depth ------------------------------------------------------------------------------------------------
+ * The depth source of OVMono3D-GEO (reference tools/ovmono3d_geo.py:267,290-295: depth_pro's model.infer(image, f_px)). The
+ * arithmetic is Hugging Face transformers' DepthProForDepthEstimation + DepthProImageProcessor (preprocess and
+ * post_process_depth_estimation), and the weights carry the key names of the apple/DepthPro-hf checkpoint.
+ *
+ * The three encoders (patch, image, field of view) are DINOv2 towers of ovm_create's block code with HF key names; the 35 crops of
+ * the three-level pyramid run as one batch. Pyramid, token merge, neck, DPT fusion, the depth head, the field-of-view head and the
+ * conversion to metres are sequenced here. GEMMs and convolutions follow `precision` (1: fp16 operands, 3: split fp16 x 3);
+ * LayerNorm, softmax and every resampling are fp32.
+ *
+ * Scope: one image per call; ratios 0.25 / 0.5 / 1 with overlaps 0 / 0.5 / 0.25 on a canvas of 4 * crop (anything else:
+ * OVM_ERR_UNSUPPORTED); the three encoders share one architecture; no batch norm in the fusion units. */
+typedef struct OvmDepthPro OvmDepthPro;
+typedef struct OvmDepthProConfig {
+  int32_t embed_dim, depth, heads;          /* the towers: ViT-L 1024 / 24 / 16 (head dimension 64) */
+  int32_t patch, crop;                      /* ViT patch (16) and crop side = the towers' image size (384); canvas = 4 * crop */
+  int32_t hook_ids[2];                      /* blocks of the patch tower whose output feeds the two finest decoder levels (11, 5) */
+  int32_t fusion_dim;                       /* decoder width (256) */
+  int32_t scaled_dims[3];                   /* scaled_images_feature_dims (1024, 1024, 512) */
+  int32_t inter_dims[2];                    /* intermediate_feature_dims (256, 256) */
+  float ratios[3], overlaps[3];             /* scaled_images_ratios (0.25, 0.5, 1) and _overlap_ratios (0, 0.5, 0.25) */
+  int32_t merge_padding;                    /* 3 */
+  int32_t num_fov_layers;                   /* stride-2 convolutions of the field-of-view head (2) */
+  int32_t use_fov;                          /* 0: no field-of-view model is loaded and every call must give f_px */
+  int32_t precision;                        /* 1 or 3 */
+  float ln_eps;                             /* LayerNorm eps of the towers (1e-6) */
+} OvmDepthProConfig;
+int ovm_depthpro_create(const OvmDepthProConfig* cfg, const OvmTensor* weights, int32_t n_weights, int32_t device, OvmDepthPro** out);
+int ovm_depthpro_destroy(OvmDepthPro* dp);
+const char* ovm_depthpro_last_error(const OvmDepthPro* dp);
+/* Device workspace bytes of ovm_depthpro_infer for an H x W image (256-byte aligned by the caller). */
+int ovm_depthpro_workspace(const OvmDepthPro* dp, int32_t H, int32_t W, int64_t* bytes);
+/* image: uint8 device image [H][W][3] with any element strides; flip_bgr != 0 reverses the channels first. f_px > 0: the focal
+ * length in pixels of the original image; f_px <= 0: estimated by the field-of-view head, f = 0.5 W / tan(0.5 fov). depth_out:
+ * device fp32 [H][W] in metres, 1 / clamp(canonical * W / f resized to H x W, 1e-4, 1e4). fov_deg_out, f_px_out: device fp32
+ * scalars (fov_deg_out receives the head's estimate, or 0 without a field-of-view model); either may be NULL. Stream-ordered: the
+ * focal length is read from device memory, nothing is synchronised. The intermediates stay in the workspace for
+ * ovm_depthpro_debug_copy until the next call. */
+int ovm_depthpro_infer(OvmDepthPro* dp, const OvmImage* image, int32_t flip_bgr, float f_px, float* depth_out, float* fov_deg_out,
+                       float* f_px_out, void* workspace, int64_t workspace_bytes, ovm_stream_t stream);
+/* tests: copy a stage of the last infer into dst (device fp32); returns the element count or a negative error. NHWC throughout:
+ * "pyramid0/1/2" [s][s][3] (s = canvas, / 2, / 4), "tokens_patch" [35][T][D], "features0..5" (image, low, medium, high, hook 0,
+ * hook 1: [side][side][D]), "neck0..4" [side][side][fusion_dim], "fused", "canonical" [S][S], "fov" [1]. */
+int64_t ovm_depthpro_debug_copy(OvmDepthPro* dp, const char* name, float* dst, int64_t capacity, ovm_stream_t stream);
+/* Per-stage timing: after ovm_depthpro_profile_enable(dp, 1) every infer records HIP events at its stage boundaries on its stream;
+ * ovm_depthpro_stage_ms waits for the last infer and writes 7 durations in milliseconds (n >= 7): pyramid (with the border clear),
+ * towers, merge + neck, fusion, head, field of view, output. */
+int ovm_depthpro_profile_enable(OvmDepthPro* dp, int32_t on);
+int ovm_depthpro_stage_ms(OvmDepthPro* dp, float* ms, int32_t n);
+/* Host only (no device call): OVM_OK when the geometry of cfg is supported, else the error ovm_depthpro_create would give, with its
+ * message in msg (capacity bytes). */
+int ovm_host_depthpro_check(const OvmDepthProConfig* cfg, char* msg, int32_t capacity);
 
 #ifdef __cplusplus
 }

@@ -54,6 +54,9 @@ struct OvmHandle {
   OvmConfig cfg;
   int device = 0;
   bool tower_only = false;          // ovm::tower_create: the ViT blocks alone (no pyramid, no heads) - the SAM predictor's image encoder
+  // ovm::tower_create_ex / tower_forward_f32 (Depth Pro's encoders; all off by default): Hugging Face Dinov2Model key names with
+  // patch 16 and the model's final LayerNorm (the float input and the taps are arguments of tower_launches, not handle state)
+  bool hf_dinov2 = false; float *fin_g = nullptr, *fin_b = nullptr;
   std::string err;
   std::vector<void*> allocs;
   int G = 0, G2 = 0, T = 0, Tpad = 0, D = 0, C = 0, Kpe = 640, npass = 1;
@@ -419,6 +422,7 @@ int ovm_abi_sizeof(const char* name) {
   if (n == "OvmGeoResult") return (int)sizeof(OvmGeoResult);
   if (n == "OvmGeoBox") return (int)sizeof(OvmGeoBox);
   if (n == "OvmSamConfig") return (int)sizeof(OvmSamConfig);
+  if (n == "OvmDepthProConfig") return (int)sizeof(OvmDepthProConfig);
   return -1;
 }
 
@@ -644,7 +648,7 @@ int ovm_host_sincos_pos_embed(int32_t D, int32_t G, float* out) {
 
 // vit_prefix: key prefix of the ViT's tensors (null: the tower's own, backbone.net.vit. / backbone.net.visual.); tower_only: see OvmHandle
 static int create_impl(const OvmConfig* cfg, const OvmTensor* weights, int32_t n_weights, int32_t device, const char* vit_prefix, bool tower_only,
-                       OvmHandle** out) {
+                       OvmHandle** out, const TowerOpts* opts = nullptr) {
   if (!cfg || !out) return OVM_ERR_INVALID;
   OvmHandle* h = new OvmHandle();
   *out = h;
@@ -653,11 +657,15 @@ static int create_impl(const OvmConfig* cfg, const OvmTensor* weights, int32_t n
   const bool clip = c.tower == OVM_TOWER_CLIP, mae = c.tower == OVM_TOWER_MAE, midas = c.tower == OVM_TOWER_MIDAS, sam = c.tower == OVM_TOWER_SAM;
   const bool p16 = clip || mae || midas || sam;           // patch-16 towers behind the 4-level pyramid
   h->sam = sam;
+  const bool hf = opts && opts->hf_dinov2;               // HF Dinov2Model (Depth Pro's encoders): DINOv2 blocks, patch 16, HF key names
+  if (hf && (!tower_only || c.tower != OVM_TOWER_DINOV2)) { h->err = "invalid config (HF DINOv2 names: tower_create_ex with the DINOv2 tower only)"; return OVM_ERR_INVALID; }
+  h->hf_dinov2 = hf;
   if (sam && (c.sam_window < 1 || c.depth > 32 || c.pos_grid < 1)) { h->err = "invalid config (sam_window, depth <= 32, pos_grid)"; return OVM_ERR_INVALID; }
   if (c.tower != OVM_TOWER_DINOV2 && !p16) { h->err = "invalid config (tower)"; return OVM_ERR_INVALID; }
-  h->patch = p16 ? 16 : 14; h->nlev = p16 ? 4 : 3;
+  h->patch = (p16 || hf) ? 16 : 14; h->nlev = p16 ? 4 : 3;
   h->ln_eps = clip ? 1e-5f : (mae ? 1e-12f : 1e-6f); h->mlp_act = clip ? 3 : 0;
-  h->Kpe = p16 ? 768 : 640;
+  if (hf && opts->ln_eps > 0.f) h->ln_eps = opts->ln_eps;
+  h->Kpe = (p16 || hf) ? 768 : 640;
   // the scale-4 stage needs D/4 channels in 64-wide k-steps
   if (c.canvas % h->patch != 0 || c.embed_dim % 128 != 0 || c.embed_dim != c.heads * 64 || (c.precision != 1 && c.precision != 3) ||
       c.fpn_channels % 64 != 0 || c.max_batch < 1 || c.max_rois < 1 || (p16 && c.embed_dim % 256 != 0)) {
@@ -667,7 +675,7 @@ static int create_impl(const OvmConfig* cfg, const OvmTensor* weights, int32_t n
   WeightMap wm;
   for (int i = 0; i < n_weights; ++i) wm.m[weights[i].name] = &weights[i];
   const std::string V = vit_prefix ? vit_prefix : (clip ? "backbone.net.visual." : "backbone.net.vit.");
-  if (!p16 && weights) {
+  if (!p16 && !hf && weights) {
     // DINOv2 variants: OvmConfig carries no field for them, the checkpoint does (as has_box below). Host-only checks, before any device call.
     if (const OvmTensor* t = wm.get(V + "register_tokens")) {      // hub *_reg models: [1][R][D]
       if (t->ndim != 3 || t->shape[0] != 1 || t->shape[2] != c.embed_dim) { h->err = "bad shape for " + V + "register_tokens (expected [1][R][embed_dim])"; return OVM_ERR_SHAPE; }
@@ -717,7 +725,7 @@ static int create_impl(const OvmConfig* cfg, const OvmTensor* weights, int32_t n
   }
   int r;
   const int P = h->patch, PP = P * P;
-  const std::string PEW = clip ? "conv1.weight" : (mae ? "embeddings.patch_embeddings.projection.weight" : "patch_embed.proj.weight");
+  const std::string PEW = clip ? "conv1.weight" : ((mae || hf) ? "embeddings.patch_embeddings.projection.weight" : "patch_embed.proj.weight");
   // ---- patch embed: [D][3][P][P] -> [D][(py*P+px)*3 + c]; P = 14: K padded 588 -> 640
   {
     const float* w; r = get_host(h, wm, V + PEW, (int64_t)D * 3 * PP, &w); if (r) return r;
@@ -735,6 +743,14 @@ static int create_impl(const OvmConfig* cfg, const OvmTensor* weights, int32_t n
       r = ovm_host_resize_pos_embed_aa(pos, c.pos_grid, D, G, pi.data()); if (r) return r;
       r = upload_f32(h, wm, V + "ln_pre.weight", D, &h->lnpre_g); if (r) return r;
       r = upload_f32(h, wm, V + "ln_pre.bias", D, &h->lnpre_b); if (r) return r;
+    } else if (hf) {                                       // HF Dinov2Embeddings at its own grid: interpolate_pos_encoding returns the table as it is
+      if (c.pos_grid != G) { h->err = "HF DINOv2 tower: the position table must have the canvas grid (no interpolation)"; return OVM_ERR_UNSUPPORTED; }
+      r = upload_f32(h, wm, V + "embeddings.patch_embeddings.projection.bias", D, &h->pe.bias); if (r) return r;
+      r = upload_f32(h, wm, V + "embeddings.cls_token", D, &h->cls); if (r) return r;
+      r = get_host(h, wm, V + "embeddings.position_embeddings", (int64_t)(1 + G2) * D, &pos); if (r) return r;
+      memcpy(pi.data(), pos, pi.size() * 4);
+      r = upload_f32(h, wm, V + "layernorm.weight", D, &h->fin_g); if (r) return r;
+      r = upload_f32(h, wm, V + "layernorm.bias", D, &h->fin_b); if (r) return r;
     } else if (sam) {                                      // segment_anything: no class token, table [grid][grid][D], plain bicubic resize (sam.py:73-86)
       r = upload_f32(h, wm, V + "patch_embed.proj.bias", D, &h->pe.bias); if (r) return r;
       r = get_host(h, wm, V + "pos_embed", (int64_t)c.pos_grid * c.pos_grid * D, &pos); if (r) return r;
@@ -793,6 +809,21 @@ static int create_impl(const OvmConfig* cfg, const OvmTensor* weights, int32_t n
         host_linear_rows(t->data, (int)t->shape[0], 64, 2 * side - 1, tab.data());     // get_rel_pos: F.interpolate(mode="linear") when lengths differ
         if ((r = upload_vec(h, tab, hw ? &y.relw : &y.relh))) return r;
       }
+      continue;
+    }
+    if (hf) {                                              // HF Dinov2Layer: norm1, attention (query / key / value, output.dense), layer_scale1, norm2, mlp, layer_scale2
+      const std::string Pq = V + "encoder.layer." + std::to_string(l) + ".";
+      if ((r = upload_f32(h, wm, Pq + "norm1.weight", D, &y.ln1g))) return r;
+      if ((r = upload_f32(h, wm, Pq + "norm1.bias", D, &y.ln1b))) return r;
+      if ((r = upload_f32(h, wm, Pq + "norm2.weight", D, &y.ln2g))) return r;
+      if ((r = upload_f32(h, wm, Pq + "norm2.bias", D, &y.ln2b))) return r;
+      if ((r = upload_f32(h, wm, Pq + "layer_scale1.lambda1", D, &y.ls1))) return r;
+      if ((r = upload_f32(h, wm, Pq + "layer_scale2.lambda1", D, &y.ls2))) return r;
+      const std::string A = Pq + "attention.attention.";
+      if ((r = pack_concat(h, wm, {{A + "query", D}, {A + "key", D}, {A + "value", D}}, D, &y.qkv))) return r;
+      if ((r = pack_linear(h, wm, Pq + "attention.output.dense", D, D, &y.proj))) return r;
+      if ((r = pack_linear(h, wm, Pq + "mlp.fc1", 4 * D, D, &y.fc1))) return r;
+      if ((r = pack_linear(h, wm, Pq + "mlp.fc2", D, 4 * D, &y.fc2))) return r;
       continue;
     }
     if (mae) {                                             // HF ViTLayer: layernorm_before, attention (q / k / v / output.dense), layernorm_after, MLP
@@ -1040,11 +1071,13 @@ int ovm_backbone_forward(OvmHandle* h, const OvmImage* images, int32_t B, const 
 
 // patch embed (+ preprocess) and the ViT blocks: the residual stream h->X [B * T][D] fp32 afterwards holds the last block's tokens.
 // Shared by the backbone below and by the SAM predictor's image encoder (ovm::tower_forward).
-static int tower_launches(OvmHandle* h, int B, hipStream_t s) {
+struct TowerRun { const TowerViews* views; int ntap; const int* tap_blk; float* const* tap_dst; };   // tower_forward_f32's per-call arguments
+static int tower_launches(OvmHandle* h, int B, hipStream_t s, const TowerRun* run = nullptr) {
   const OvmConfig& c = h->cfg;
   const int D = h->D, G = h->G, G2 = h->G2, T = h->T, L = c.depth;
   // ---- patch embed (+ preprocess) ----
-  KCHECK(h, launch_patch_gather(h->d_imgs, B, G, h->patch, h->Kpe, c.pixel_mean, c.pixel_std, h->PA.hi, h->PA.lo, s));
+  if (run) KCHECK(h, launch_patch_gather_f32(*run->views, B, G, h->Kpe, h->PA.hi, h->PA.lo, s));
+  else KCHECK(h, launch_patch_gather(h->d_imgs, B, G, h->patch, h->Kpe, c.pixel_mean, c.pixel_std, h->PA.hi, h->PA.lo, s));
   if (!h->sam) KCHECK(h, launch_cls_init(h->X, h->cls, h->pos, h->reg, h->nreg, B, T, D, s));       // SAM: no class token (T = G^2)
   {
     GemmParams p = gp_base(h->PA, h->Kpe, h->pe, B * G2);
@@ -1134,6 +1167,8 @@ static int tower_launches(OvmHandle* h, int B, hipStream_t s) {
       p.gamma = y.ls2; p.X = h->X; p.ldx = D;
       KCHECK(h, gemm(h, p, EPI_RESID, A_ROWMAJOR, s, OVM_PROF_FC2));
     }
+    for (int t = 0; run && t < run->ntap; ++t)                // the residual stream after block l (HF hidden_states[l + 1])
+      if (run->tap_blk[t] == l) HCHECK(h, hipMemcpyAsync(run->tap_dst[t], h->X, (size_t)M * D * 4, hipMemcpyDeviceToDevice, s));
   }
   return OVM_OK;
 }
@@ -1506,6 +1541,33 @@ int tower_forward(OvmHandle* h, const OvmImage* image, hipStream_t s) {
   HCHECK(h, hipMemcpyAsync(h->d_imgs, h->h_imgs, sizeof(ImageDesc), hipMemcpyHostToDevice, s));
   h->lastB = 1;
   return tower_launches(h, 1, s);
+}
+
+int tower_create_ex(const OvmConfig* cfg, const OvmTensor* weights, int n_weights, int device, const char* vit_prefix, const TowerOpts* opts,
+                    OvmHandle** out) {
+  return create_impl(cfg, weights, n_weights, device, vit_prefix, true, out, opts);
+}
+
+int tower_forward_f32(OvmHandle* h, const TowerViews& views, int n_taps, const int* tap_blocks, float* const* tap_out, float* final_out,
+                      hipStream_t s) {
+  if (!h || !h->tower_only || h->patch != 16 || h->sam) return OVM_ERR_INVALID;
+  h->err.clear();
+  const int B = views.n;
+  if (B < 1 || B > h->cfg.max_batch || B > kMaxTowerViews) { h->err = "crop count exceeds max_batch"; return OVM_ERR_CAPACITY; }
+  if (n_taps < 0 || n_taps > kMaxTowerTaps) { h->err = "too many taps"; return OVM_ERR_CAPACITY; }
+  for (int t = 0; t < n_taps; ++t)
+    if (tap_blocks[t] < 0 || tap_blocks[t] >= h->cfg.depth || !tap_out[t]) { h->err = "tap block out of range"; return OVM_ERR_INVALID; }
+  if (final_out && !h->fin_g) { h->err = "the tower has no final LayerNorm"; return OVM_ERR_INVALID; }
+  HCHECK(h, hipSetDevice(h->device));
+  h->lastB = B;
+  const TowerRun run{&views, n_taps, tap_blocks, tap_out};
+  const int r = tower_launches(h, B, s, &run);
+  if (r) return r;
+  if (final_out) {
+    LnOut o; memset(&o, 0, sizeof(o)); o.f32 = final_out; o.ldf = h->D;
+    KCHECK(h, launch_ln_rows(h->X, h->D, B * h->T, h->D, h->fin_g, h->fin_b, h->ln_eps, o, s));
+  }
+  return OVM_OK;
 }
 
 const float* tower_tokens(const OvmHandle* h) { return h ? h->X : nullptr; }

@@ -1,6 +1,7 @@
 // HBM-bound helper kernels: patch gather (+normalise, +zero pad), LayerNorm (token rows and NHWC
 // channel rows), cls/pos init, dense-token cast, 2x2 max-pool, depth-prompt resize.
 #include "kernels.hpp"
+#include "sam.hpp"
 
 namespace ovm {
 
@@ -66,6 +67,35 @@ int launch_patch_gather(const ImageDesc* d_imgs, int B, int G, int patch, int Kp
   } else {
     return OVM_ERR_INVALID;
   }
+  return hipGetLastError() == hipSuccess ? OVM_OK : OVM_ERR_HIP;
+}
+
+// The same rows from normalised fp32 crops (Depth Pro: 35 overlapping crops of three pyramid levels, read in place). One thread per
+// (patch, py): 48 values, 96 contiguous bytes per part.
+__global__ void patch_gather_f32_kernel(const TowerViews v, int B, int G, int Kpad, half_t* __restrict__ Ahi, half_t* __restrict__ Alo) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  const int G2 = G * G;
+  if (idx >= B * G2 * 16) return;
+  const int py = idx & 15, pid = idx >> 4;
+  const int b = pid / G2, p = pid - b * G2;
+  const int gy = p / G, gx = p - gy * G;
+  const TowerView d = v.v[b];
+  const float* src = d.data + (size_t)(gy * 16 + py) * d.sH + (size_t)(gx * 16) * d.sW;
+  half_t* oh = Ahi + (size_t)pid * Kpad + py * 48;
+  half_t* ol = Alo ? Alo + (size_t)pid * Kpad + py * 48 : nullptr;
+  for (int px = 0; px < 16; ++px)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      half_t h, l; split_f16_nt(src[(size_t)px * d.sW + (size_t)c * d.sC], h, l);
+      oh[px * 3 + c] = h;
+      if (ol) ol[px * 3 + c] = l;
+    }
+}
+
+int launch_patch_gather_f32(const TowerViews& v, int B, int G, int Kpad, half_t* Ahi, half_t* Alo, hipStream_t s) {
+  if (Kpad != 768 || B < 1 || B > v.n) return OVM_ERR_INVALID;
+  const int total = B * G * G * 16;
+  hipLaunchKernelGGL(patch_gather_f32_kernel, dim3((total + 255) / 256), dim3(256), 0, s, v, B, G, Kpad, Ahi, Alo);
   return hipGetLastError() == hipSuccess ? OVM_OK : OVM_ERR_HIP;
 }
 

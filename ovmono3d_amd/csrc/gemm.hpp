@@ -51,6 +51,9 @@ struct GemmParams {
   int o_il;                                       // EPI_GELU: Ohi / Olo form an interleaved image (Olo = Ohi + 32, ldo = 2 N)
   int relu;                                       // EPI_STORE activation: 0 none, 1 ReLU, 2 GELU(erf); EPI_GELU: 3 = QuickGELU, else erf
   const float* R; int ldr;                        // EPI_STORE: optional fp32 residual added after the activation
+  const float* R2; int ldr2;                      // EPI_STORE: optional second fp32 residual (fusion: skip + the other branch)
+  int relu_o;                                     // EPI_STORE: Ohi / Olo receive relu(value) while C keeps the value - the input of a
+                                                  // pre-activation residual unit's first convolution, whose skip is the fp32 copy
   // EPI_STORE with padded-NHWC destination for Ohi/Olo (conv input): if padH>0, row m=(b,y,x) goes to
   // ((b*(padH+2) + y+1)*(padW+2) + x+1)
   int padH, padW;
@@ -63,7 +66,8 @@ struct GemmParams {
   // EPI_PATCH: X[(b*T + c + p)][n] = acc + bias[n] + pos[(c1+p)*N + n],   m = b*G2 + p, c = T - G2 leading tokens (class + register
   // tokens, or none), c1 = 1 if the table has a class row (c > 0): the table is indexed by patch, register tokens have no row
   const float* pos; int G2;
-  // EPI_CONVT: m = (b, i, j) over GxG, n = (a*2 + bb)*Cout + co -> NHWC [B][2G][2G][Cout]
+  // EPI_CONVT: m = (b, i, j) over GxG, n = (a*2 + bb)*Cout + co -> NHWC [B][2G][2G][Cout]; ldo > 0: pixel stride (columns of a
+  // wider buffer: one half of a channel concatenation); padH > 0: the interior of a zero-bordered [B][2G+2][2G+2] image
   int G, Cout;
   // set by the launcher: workgroups [0, main_tiles) run MFMA tiles over rows [0, tail_begin); workgroups beyond
   // them compute the leftover rows [tail_begin, M) with the dot-product body (see gemm_tail_body)
@@ -236,7 +240,8 @@ __device__ __forceinline__ void epilogue4(const GemmParams& p, int m, int n, f32
     const int q = n / p.Cout, co = n - q * p.Cout;       // q = a*2 + bb; Cout % 4 == 0
     const int a = q >> 1, bb = q & 1;
     const int j = m % p.G; const int t = m / p.G; const int i = t % p.G; const int b = t / p.G;
-    const size_t o = (((size_t)b * 2 * p.G + 2 * i + a) * 2 * p.G + 2 * j + bb) * p.Cout + co;
+    const int ps = p.ldo > 0 ? p.ldo : p.Cout, bd = p.padH > 0 ? 1 : 0, side = 2 * p.G + 2 * bd;
+    const size_t o = (((size_t)b * side + 2 * i + a + bd) * side + 2 * j + bb + bd) * ps + co;
     half4 h, l;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -252,6 +257,7 @@ __device__ __forceinline__ void epilogue4(const GemmParams& p, int m, int n, f32
       o4[r] = v[r] + b4[r];
       if (p.relu == 1) o4[r] = fmaxf(o4[r], 0.f); else if (p.relu == 2) o4[r] = gelu_erf(o4[r]);
       if (p.R && n + r < p.N) o4[r] += p.R[(size_t)m * p.ldr + n + r];
+      if (p.R2 && n + r < p.N) o4[r] += p.R2[(size_t)m * p.ldr2 + n + r];
     }
     if (p.C) {
       float* c = p.C + (size_t)m * p.ldc + n;
@@ -265,7 +271,7 @@ __device__ __forceinline__ void epilogue4(const GemmParams& p, int m, int n, f32
       }
       const size_t o = row * p.ldo + n;
       for (int r = 0; r < 4 && n + r < p.N; ++r) {
-        half_t hh, ll; split_f16(o4[r], hh, ll);
+        half_t hh, ll; split_f16(p.relu_o ? fmaxf(o4[r], 0.f) : o4[r], hh, ll);
         p.Ohi[o + r] = hh;
         if (p.Olo) p.Olo[o + r] = ll;
       }

@@ -156,6 +156,16 @@ class OvmSamConfig(C.Structure):
     ]
 
 
+class OvmDepthProConfig(C.Structure):
+    """Mirror of include/ovm3d.h OvmDepthProConfig."""
+    _fields_ = [
+        ("embed_dim", C.c_int32), ("depth", C.c_int32), ("heads", C.c_int32), ("patch", C.c_int32), ("crop", C.c_int32),
+        ("hook_ids", C.c_int32 * 2), ("fusion_dim", C.c_int32), ("scaled_dims", C.c_int32 * 3), ("inter_dims", C.c_int32 * 2),
+        ("ratios", C.c_float * 3), ("overlaps", C.c_float * 3), ("merge_padding", C.c_int32), ("num_fov_layers", C.c_int32),
+        ("use_fov", C.c_int32), ("precision", C.c_int32), ("ln_eps", C.c_float),
+    ]
+
+
 EXPORTS = [
     "ovm_create", "ovm_destroy", "ovm_last_error", "ovm_version", "ovm_abi_sizeof", "ovm_backbone_forward", "ovm_cube_forward",
     "ovm_rpn_box_forward", "ovm_gather_records", "ovm_gather_counts", "ovm_host_interp_pos_embed", "ovm_host_resize_pos_embed_aa", "ovm_host_sincos_pos_embed", "ovm_host_shard_range",
@@ -173,6 +183,8 @@ EXPORTS = [
     "ovm_host_geo_box",
     "ovm_sam_create", "ovm_sam_destroy", "ovm_sam_last_error", "ovm_sam_set_image", "ovm_sam_predict_boxes_workspace", "ovm_sam_predict_boxes",
     "ovm_sam_debug_copy",
+    "ovm_depthpro_create", "ovm_depthpro_destroy", "ovm_depthpro_last_error", "ovm_depthpro_workspace", "ovm_depthpro_infer",
+    "ovm_depthpro_debug_copy", "ovm_host_depthpro_check", "ovm_depthpro_profile_enable", "ovm_depthpro_stage_ms",
 ]
 PROF_NAMES = ("attn", "qkv", "proj", "fc1", "fc2", "ln")
 
@@ -200,7 +212,7 @@ def load() -> C.CDLL:
                          ("OvmJpegInfo", OvmJpegInfo), ("OvmSceneInput", OvmSceneInput), ("OvmSceneLayout", OvmSceneLayout),
                          ("OvmSceneSegment", OvmSceneSegment), ("OvmEvalCell", OvmEvalCell), ("OvmGeoParams", OvmGeoParams),
                          ("OvmGeoInstance", OvmGeoInstance), ("OvmGeoResult", OvmGeoResult), ("OvmGeoBox", OvmGeoBox),
-                         ("OvmSamConfig", OvmSamConfig)):
+                         ("OvmSamConfig", OvmSamConfig), ("OvmDepthProConfig", OvmDepthProConfig)):
         if lib.ovm_abi_sizeof(name.encode()) != C.sizeof(mirror):
             raise RuntimeError(f"{LIB_PATH}: sizeof({name}) = {lib.ovm_abi_sizeof(name.encode())} but the ctypes mirror has "
                                f"{C.sizeof(mirror)} bytes - rebuild the library (ovmono3d_amd/csrc/build.sh) or update lib.py")
@@ -267,6 +279,17 @@ def load() -> C.CDLL:
     lib.ovm_sam_predict_boxes.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, i64, vp]
     lib.ovm_sam_debug_copy.argtypes = [vp, C.c_char_p, vp, i64, vp]
     lib.ovm_sam_debug_copy.restype = i64
+    lib.ovm_depthpro_create.argtypes = [C.POINTER(OvmDepthProConfig), C.POINTER(OvmTensor), i32, i32, C.POINTER(vp)]
+    lib.ovm_depthpro_destroy.argtypes = [vp]
+    lib.ovm_depthpro_last_error.argtypes = [vp]
+    lib.ovm_depthpro_last_error.restype = C.c_char_p
+    lib.ovm_depthpro_workspace.argtypes = [vp, i32, i32, C.POINTER(i64)]
+    lib.ovm_depthpro_infer.argtypes = [vp, C.POINTER(OvmImage), i32, f32, vp, vp, vp, vp, i64, vp]
+    lib.ovm_depthpro_debug_copy.argtypes = [vp, C.c_char_p, vp, i64, vp]
+    lib.ovm_depthpro_debug_copy.restype = i64
+    lib.ovm_depthpro_profile_enable.argtypes = [vp, i32]
+    lib.ovm_depthpro_stage_ms.argtypes = [vp, vp, i32]
+    lib.ovm_host_depthpro_check.argtypes = [C.POINTER(OvmDepthProConfig), C.c_char_p, i32]
     lib.ovm_g_pack_weight.argtypes = [vp, i32, i32, i32, vp, vp, vp]
     lib.ovm_g_linear.argtypes = [vp, i32, i32, i32, vp, vp, i32, i32, vp, i32, vp, i32, vp, i32, i32, vp]
     lib.ovm_g_layernorm.argtypes = [vp, vp, i32, i32, vp, vp, f32, vp, vp]
@@ -297,7 +320,7 @@ def load() -> C.CDLL:
     lib.ovm_infer.argtypes = [vp, vp, C.POINTER(OvmImage), C.POINTER(i32), i32, C.POINTER(i32), i32, f32, f32, vp, i32, C.POINTER(i32), vp]
     for name in EXPORTS:
         if name not in ("ovm_last_error", "ovm_version", "ovm_debug_copy", "ovm_gdino_last_error", "ovm_gdino_debug_copy", "ovm_geo_last_error",
-                        "ovm_sam_last_error", "ovm_sam_debug_copy"):
+                        "ovm_sam_last_error", "ovm_sam_debug_copy", "ovm_depthpro_last_error", "ovm_depthpro_debug_copy"):
             getattr(lib, name).restype = i32
     # experiment knobs, e.g. OVM_TUNE="gemm_bm=256,attn_tail=0"
     for kv in filter(None, os.environ.get("OVM_TUNE", "").split(",")):

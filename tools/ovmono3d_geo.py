@@ -21,9 +21,16 @@ Masks, one of:
   ``--mask box``   the 2D box itself is the mask: the pixels ceil(x0) <= x < ceil(x1), ceil(y0) <= y < ceil(y1) of the xyxy box,
                    clipped to the image (the reference has no such mode; the rule is this project's).
 
-What is NOT here: Depth Pro, the network the reference takes its depth from. Depth is read from
-``<depth-dir>/test/<image base name>.npz`` (or ``<depth-dir>/<image base name>.npz``), key ``depth``, metres, at the image's own
-resolution - a map of another shape is refused, the reference never resizes it.
+Depth, one of:
+  ``--depth files``     (default) read from ``<depth-dir>/test/<image base name>.npz`` (or ``<depth-dir>/<image base name>.npz``), key
+                        ``depth``, metres, at the image's own resolution - a map of another shape is refused, the reference never
+                        resizes it.
+  ``--depth depthpro``  the reference's way (tools/ovmono3d_geo.py:267,290-295): Depth Pro on the device (ovmono3d_amd.depthpro,
+                        csrc/depthpro.hip) from ``--depthpro-weights`` (Hugging Face ``apple/DepthPro-hf`` key names; Apple's own
+                        ``depth_pro.pt`` names are not mapped). ``--depthpro-focal estimate`` (default) lets the field-of-view head
+                        choose the focal length, as the reference does for images without EXIF data (EXIF is not read here);
+                        ``--depthpro-focal K`` passes the dataset's ``K[0][0]``. ``--dump-depth DIR`` writes ``<DIR>/<image base
+                        name>.npz`` with key ``depth``: the files ``--depth-dir`` and DatasetMapper3D read.
 
 Instances below ``--score-threshold`` are dropped as in the reference. Instances the reference has no answer for (an empty mask,
 fewer than 2 points, a non-finite depth under the mask, a box outside the image, no mask in the mask file) are skipped, counted
@@ -52,25 +59,39 @@ def xywh_to_xyxy(b):
 
 
 def lift_image(depth, K, boxes_xyxy, masks, params):
-    """depth: float32 [H, W] numpy; masks: a list of uint8 [H, W] planes (numpy arrays or device tensors) or None (the box is the
+    """depth: float32 [H, W], numpy or a device tensor; masks: a list of uint8 [H, W] planes (numpy arrays or device tensors) or None (the box is the
     mask). One device call."""
     dev = torch.device("cuda", torch.cuda.current_device())
-    d = torch.from_numpy(depth).to(dev)
+    d = depth.to(dev) if isinstance(depth, torch.Tensor) else torch.from_numpy(depth).to(dev)
     m = None if masks is None else [x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in masks]
     return lift_boxes(d, K, boxes_xyxy=boxes_xyxy, masks=m, params=params)
 
 
-def sam_masks(predictor, image_root, file_path, height, width, boxes_xyxy):
-    """Device uint8 [n, H, W]: SAM's plane [2] for every box of one image (one set_image, one predict_boxes)."""
+def read_bgr(image_root, file_path, height, width, dev):
+    """The image as cv2.imread gives it, on the device: uint8 [H, W, 3], BGR."""
     from ovmono3d_amd.data.gpu_jpeg import read_image_device
     path = os.path.join(image_root, file_path)
     if not os.path.exists(path):
         raise SystemExit(f"no image {path} (--image-root)")
-    bgr = read_image_device(path, "BGR", predictor.engine.dev)
+    bgr = read_image_device(path, "BGR", dev)
     if tuple(bgr.shape[:2]) != (height, width):
         raise SystemExit(f"{path}: image is {tuple(bgr.shape[:2])} but the dataset says {(height, width)}")
+    return bgr
+
+
+def sam_masks(predictor, image_root, file_path, height, width, boxes_xyxy, bgr=None):
+    """Device uint8 [n, H, W]: SAM's plane [2] for every box of one image (one set_image, one predict_boxes)."""
+    if bgr is None:
+        bgr = read_bgr(image_root, file_path, height, width, predictor.engine.dev)
     predictor.set_image(bgr, image_format="BGR")   # the reference's call (run_seg_anything): a cv2 BGR array, declared as such
     return predictor.predict_boxes(boxes_xyxy, mask_index=2)
+
+
+def dump_depth(depth_dir, file_path, depth):
+    """The <image base name>.npz file load_depth reads."""
+    os.makedirs(depth_dir, exist_ok=True)
+    base = os.path.splitext(os.path.basename(file_path))[0]
+    np.savez(os.path.join(depth_dir, base + ".npz"), depth=depth.cpu().numpy().astype(np.float32))
 
 
 def dump_masks(mask_dir, image_id, positions, planes):
@@ -123,6 +144,13 @@ def run(args):
             raise SystemExit("--mask sam needs --sam-weights FILE and --image-root DIR")
         from ovmono3d_amd.sam import build_sam
         predictor = build_sam(args.sam_arch, args.sam_weights, image_size=args.sam_image_size)
+    depthpro = None
+    if args.depth == "depthpro":
+        if not args.depthpro_weights or not args.image_root:
+            raise SystemExit("--depth depthpro needs --depthpro-weights FILE and --image-root DIR")
+        from ovmono3d_amd.depthpro import build_depthpro
+        dp_config = json.loads(args.depthpro_config) if args.depthpro_config else None
+        depthpro = build_depthpro(args.depthpro_weights, config=dp_config)
     out, n_in, n_low, n_skip, n_lifted = [], 0, 0, 0, 0
     for rec in oracle:
         im = images.get(rec["image_id"])
@@ -135,11 +163,19 @@ def run(args):
         n_low += len(rec["instances"]) - len(cand)
         new_instances = []
         if cand:
-            depth = load_depth(args.depth_dir, im["file_path"], H, W)
+            bgr = None
+            if depthpro is not None:
+                bgr = read_bgr(args.image_root, im["file_path"], H, W, depthpro.dev)
+                f_px = float(K[0][0]) if args.depthpro_focal == "K" else None
+                depth = depthpro.infer(bgr, f_px=f_px, image_format="BGR")["depth"]
+                if args.dump_depth:
+                    dump_depth(args.dump_depth, im["file_path"], depth)
+            else:
+                depth = load_depth(args.depth_dir, im["file_path"], H, W)
             planes = None
             if use_sam:
                 boxes = np.asarray([xywh_to_xyxy(ins["bbox"]) for _, ins in cand], np.float64)
-                planes = list(sam_masks(predictor, args.image_root, im["file_path"], H, W, boxes))
+                planes = list(sam_masks(predictor, args.image_root, im["file_path"], H, W, boxes, bgr=bgr))
             elif not use_box:
                 have = load_masks(args.mask_dir, rec["image_id"], H, W)
                 missing = [pos for pos, _ in cand if pos not in have]
@@ -183,7 +219,16 @@ def argument_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--oracle2d", required=True, help="oracle-2D file (tools/make_oracle2d.py): [{image_id, instances[{bbox xywh, category_id, score}]}]")
     ap.add_argument("--dataset", required=True, help="Omni3D annotation json of the same images (file_path, height, width, K)")
-    ap.add_argument("--depth-dir", required=True, help="metric depth .npz files (key 'depth'), the ones DatasetMapper3D reads")
+    ap.add_argument("--depth", choices=("files", "depthpro"), default="files", help="files: read --depth-dir; depthpro: run Depth Pro on the device")
+    ap.add_argument("--depth-dir", default=None, help="metric depth .npz files (key 'depth'), the ones DatasetMapper3D reads (required with --depth files; "
+                                                        "refused with --depth depthpro, which would not read it)")
+    ap.add_argument("--depthpro-weights", default=None, help="Depth Pro checkpoint in Hugging Face key names (torch file or .safetensors)")
+    ap.add_argument("--depthpro-focal", choices=("estimate", "K"), default="estimate",
+                    help="estimate: the field-of-view head chooses the focal length; K: the dataset's K[0][0]")
+    ap.add_argument("--depthpro-config", default=None, metavar="JSON",
+                    help="fields of ovmono3d_amd.depthpro.DEFAULT_CONFIG to override, as a JSON object: a checkpoint of another size than "
+                         "apple/DepthPro-hf (e.g. '{\"embed_dim\": 128, \"depth\": 4, \"heads\": 2, \"crop\": 128}')")
+    ap.add_argument("--dump-depth", default=None, metavar="DIR", help="write the depth used as <DIR>/<image base name>.npz, the files --depth-dir reads")
     ap.add_argument("--mask-dir", default=None, help="<image_id>.npz with 'masks' uint8 [n, H, W] and 'index' int [n]")
     ap.add_argument("--mask", choices=("box", "sam"), default=None,
                     help="box: the 2D box is the mask - pixels ceil(x0) <= x < ceil(x1), ceil(y0) <= y < ceil(y1), clipped to the image; "
@@ -198,9 +243,25 @@ def argument_parser():
     return ap
 
 
+def check_args(args, parser=None):
+    """What argparse's ``required`` cannot say: --depth-dir is required unless Depth Pro supplies the depth."""
+    if args.depth == "files" and not args.depth_dir:
+        msg = "the following arguments are required: --depth-dir (or --depth depthpro)"
+        if parser is not None:
+            parser.error(msg)
+        raise SystemExit(msg)
+    if args.depth == "depthpro" and args.depth_dir:
+        msg = "--depth depthpro computes the depth: --depth-dir would not be read (to write depth files use --dump-depth DIR)"
+        if parser is not None:
+            parser.error(msg)
+        raise SystemExit(msg)
+    return args
+
+
 def main():
     logging.basicConfig(level=logging.INFO)
-    args = argument_parser().parse_args()
+    parser = argument_parser()
+    args = check_args(parser.parse_args(), parser)
     if not torch.cuda.is_available():
         raise SystemExit("OVMono3D-GEO runs on the HIP device (there is no CPU path)")
     print(json.dumps(run(args)))
