@@ -250,6 +250,37 @@ int ovm_op_gemm(const uint16_t* a_hi, const uint16_t* a_lo, int32_t lda, const u
 int ovm_op_gemm_swiglu(const uint16_t* a_hi, const uint16_t* a_lo, int32_t lda, const uint16_t* w_hi, const uint16_t* w_lo,
                        int32_t M, int32_t Hs, int32_t K, const float* bias, uint16_t* out_hi, uint16_t* out_lo, int32_t ldo,
                        int32_t precision, ovm_stream_t stream);
+/* One fused GEMM epilogue in isolation (test-only): out = epilogue(A W^T), launched exactly as the model path launches it. All
+ * pointers are fp32 device tensors; the adapter pads W to 256 rows, converts A and W to the (split, interleaved) fp16 operand
+ * images, and for amode 1 builds the zero-bordered image of the un-bordered NHWC input A [B][cH][cW][cC] (M = B cH cW, K = 9 cC,
+ * W columns ordered (dy*3 + dx)*cC + c). Outputs are fp32 buffers in the kernel's own layout, which the caller pre-fills (a value
+ * that is exact in fp16 survives wherever the kernel does not write): fp16 destinations are split from the caller's buffer before
+ * the launch and joined back after it.
+ *   epi 0 store : C [M][ldc] and / or O with row stride ldo; relu 0 none | 1 ReLU | 2 GELU(erf); + R [M][ldr] + R2 [M][ldr2] after the
+ *                 activation; relu_o: O receives relu(value); padH > 0: row (b, y, x) of O goes to the interior of a bordered
+ *                 [B][padH+2][padW+2] image
+ *   epi 1 resid : X[row_map ? row_map[m] : m][n] += (gamma ? gamma[n] : 1) * (acc + bias[n]), negative rows dropped
+ *   epi 2 gelu  : O = gelu(acc + bias) (relu 3: QuickGELU); o_il: O is the interleaved image [M][ldo = 2N] of hi and lo halves,
+ *                 returned element by element (hi at column il(n) = (n/32)*64 + n%32, lo 32 further)
+ *   epi 3 qkv   : N = 3 heads 64; Q (scaled by qscale), Kout [B][heads][T][64], Vt [B][heads][64][Tpad] with the token order of the
+ *                 attention kernel (bits 2 and 3 of the token index swapped inside each group of 16)
+ *   epi 4 patch : X[b*T + (T - G2) + p][n] = acc + bias[n] + pos[((T > G2) + p)*N + n], m = b*G2 + p
+ *   epi 5 convt : 2x2 stride-2 scatter, n = (a*2 + bb)*Cout + co -> O pixel (2i + a, 2j + bb) of [B][2G][2G], pixel stride ldo
+ *                 (0: Cout), padH > 0: the interior of a [B][2G+2][2G+2] image
+ * precision 1 | 3 (3: split operands; a_il: A as an interleaved image as well). route 0: launch_gemm; 1: the 256 x 256 kernel with
+ * split-K hint ksplit_hint. Routes inside launch_gemm follow the gemm_* tune keys. Invalid combinations return the launcher's code. */
+typedef struct OvmGemmEpiOp {
+  int32_t epi, amode, precision, a_il, route, ksplit_hint;
+  int32_t M, N, K, cH, cW, cC;
+  const float* A; const float* W; const float* bias;
+  const float* gamma; float* X; const int32_t* row_map; int32_t ldx, relu;
+  float* C; int32_t ldc, ldo;
+  float* O; int64_t o_elems; int32_t o_il, relu_o;
+  const float* R; const float* R2; int32_t ldr, ldr2, padH, padW;
+  float* Q; float* Kout; float* Vt; int32_t T, Tpad, heads; float qscale;
+  const float* pos; int32_t G2, G, Cout, reserved;
+} OvmGemmEpiOp;
+int ovm_op_gemm_epi(const OvmGemmEpiOp* op, ovm_stream_t stream);
 /* hi, lo [rows][K] (K % 32 == 0) -> out [rows][K/32][hi 32 | lo 32]: the interleaved operand image of the split-precision GEMM.
  * In split mode ovm_op_gemm takes w_hi = such an image and w_lo = w_hi + 32; activations may be plain arrays or an image
  * (a_lo = a_hi + 32, lda = 2K). */

@@ -423,6 +423,7 @@ int ovm_abi_sizeof(const char* name) {
   if (n == "OvmGeoBox") return (int)sizeof(OvmGeoBox);
   if (n == "OvmSamConfig") return (int)sizeof(OvmSamConfig);
   if (n == "OvmDepthProConfig") return (int)sizeof(OvmDepthProConfig);
+  if (n == "OvmGemmEpiOp") return (int)sizeof(OvmGemmEpiOp);
   return -1;
 }
 

@@ -125,6 +125,109 @@ __global__ void interleave_kernel(const half_t* __restrict__ hi, const half_t* _
 }
 }  // namespace
 
+namespace {
+// un-bordered NHWC fp32 [B][H][W][Cc] -> the interior of a zero-bordered split fp16 image [B][H+2][W+2][Cc] (border: the caller's memset)
+__global__ void pad_nhwc_split_kernel(const float* __restrict__ x, int64_t n, int H, int W, int Cc, half_t* __restrict__ hi,
+                                      half_t* __restrict__ lo) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int c = (int)(i % Cc); const int64_t px = i / Cc;
+  const int xx = (int)(px % W); const int64_t t = px / W; const int y = (int)(t % H); const int64_t b = t / H;
+  const size_t o = (size_t)(((b * (H + 2) + y + 1) * (W + 2) + xx + 1) * Cc + c);
+  half_t h, l; split_f16(x[i], h, l);
+  hi[o] = h;
+  if (lo) lo[o] = l;
+}
+inline dim3 grid1d(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
+}  // namespace
+
+// Any fused epilogue of gemm.hpp in isolation (tests): fp32 operands in, the kernel's own output layouts out. Converts the operands with
+// the kernels above, fills GemmParams and calls the launcher the model path calls; checks nothing the launchers check themselves.
+int ovm_op_gemm_epi(const OvmGemmEpiOp* d, ovm_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!d || !d->A || !d->W) return OVM_ERR_INVALID;
+  if ((d->precision != 1 && d->precision != 3) || d->M < 1 || d->N < 1 || d->K < 1) return OVM_ERR_INVALID;   // the conversions below need them
+  const bool split = d->precision == 3, conv = d->amode == A_CONV3X3, a_il = split && d->a_il;
+  if (conv && (d->cH < 1 || d->cW < 1 || d->cC < 1)) return OVM_ERR_INVALID;
+  if (d->epi == EPI_QKV && (!d->Q || !d->Kout || !d->Vt || d->T < 1 || d->heads < 1)) return OVM_ERR_INVALID;
+  if ((d->epi == EPI_RESID || d->epi == EPI_PATCH) && !d->X) return OVM_ERR_INVALID;
+  if (d->epi == EPI_PATCH && !d->pos) return OVM_ERR_INVALID;
+  if ((d->epi == EPI_GELU || d->epi == EPI_CONVT) && !d->O) return OVM_ERR_INVALID;
+  if (d->O && d->o_elems < 1) return OVM_ERR_INVALID;
+  Tmp tmp;
+  // ---- A: [M][K] rows, or the zero-bordered image of the un-bordered NHWC input
+  const int64_t a_rows = conv ? (int64_t)((d->M + d->cH * d->cW - 1) / (d->cH * d->cW)) * (d->cH + 2) * (d->cW + 2) : d->M;
+  const int a_k = conv ? d->cC : d->K;
+  if (split && (a_k % 32 != 0 || d->K % 32 != 0)) return OVM_ERR_SHAPE;          // no interleaved image exists (the launchers' K % BK)
+  const size_t na = (size_t)a_rows * a_k;
+  half_t* ah = tmp.get<half_t>(na, conv);
+  half_t* al = split ? tmp.get<half_t>(na, conv) : nullptr;
+  if (!ah || (split && !al)) return OVM_ERR_HIP;
+  if (conv) {
+    const int64_t n = (int64_t)(a_rows / ((d->cH + 2) * (d->cW + 2))) * d->cH * d->cW * d->cC;
+    hipLaunchKernelGGL(pad_nhwc_split_kernel, grid1d(n), dim3(256), 0, s, d->A, n, d->cH, d->cW, d->cC, ah, al);
+  } else {
+    hipLaunchKernelGGL(split_kernel, grid1d((int64_t)na), dim3(256), 0, s, d->A, (int64_t)na, ah, al);
+  }
+  GemmParams p; memset(&p, 0, sizeof(p));
+  p.Ahi = ah; p.Alo = al; p.lda = d->K;
+  if (a_il) {
+    half_t* ai = tmp.get<half_t>(2 * na);
+    if (!ai) return OVM_ERR_HIP;
+    hipLaunchKernelGGL(interleave_kernel, grid1d((int64_t)na), dim3(256), 0, s, ah, al, (long)a_rows, a_k, ai);
+    p.Ahi = ai; p.Alo = ai + 32; p.lda = 2 * d->K; p.a_il = 1;
+  }
+  // ---- W: zero rows up to a multiple of 256 (whole tiles of either kernel); split mode: the interleaved image
+  const size_t n_pad = ((size_t)d->N + 255) / 256 * 256, nw = n_pad * d->K;
+  float* wf = tmp.get<float>(nw, true);
+  half_t* wh = tmp.get<half_t>(nw);
+  half_t* wl = split ? tmp.get<half_t>(nw) : nullptr;
+  if (!wf || !wh || (split && !wl)) return OVM_ERR_HIP;
+  if (hipMemcpyAsync(wf, d->W, (size_t)d->N * d->K * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) return OVM_ERR_HIP;
+  hipLaunchKernelGGL(split_kernel, grid1d((int64_t)nw), dim3(256), 0, s, wf, (int64_t)nw, wh, wl);
+  p.Whi = wh;
+  if (split) {
+    half_t* wi = tmp.get<half_t>(2 * nw);
+    if (!wi) return OVM_ERR_HIP;
+    hipLaunchKernelGGL(interleave_kernel, grid1d((int64_t)nw), dim3(256), 0, s, wh, wl, (long)n_pad, d->K, wi);
+    p.Whi = wi; p.Wlo = wi + 32;
+  }
+  p.M = d->M; p.N = d->N; p.K = d->K; p.cH = d->cH; p.cW = d->cW; p.cC = d->cC;
+  p.bias = d->bias; p.gamma = d->gamma; p.X = d->X; p.ldx = d->ldx; p.row_map = d->row_map;
+  p.C = d->C; p.ldc = d->ldc; p.relu = d->relu; p.R = d->R; p.ldr = d->ldr; p.R2 = d->R2; p.ldr2 = d->ldr2; p.relu_o = d->relu_o;
+  p.padH = d->padH; p.padW = d->padW; p.ldo = d->ldo; p.o_il = d->o_il;
+  p.T = d->T; p.Tpad = d->Tpad; p.heads = d->heads; p.qscale = d->qscale; p.pos = d->pos; p.G2 = d->G2; p.G = d->G; p.Cout = d->Cout;
+  // ---- fp16 outputs: the caller's fp32 buffer (sentinels included) is split before the launch and joined back after it. An
+  // interleaved O is converted element by element (its hi and lo columns are separate elements of the caller's image).
+  struct Out { float* f; half_t* hi; half_t* lo; int64_t n; } outs[4]; int n_out = 0;
+  auto add_out = [&](float* f, int64_t n, bool with_lo) -> Out* {
+    Out& o = outs[n_out]; o.f = f; o.n = n;
+    o.hi = tmp.get<half_t>((size_t)n); o.lo = with_lo ? tmp.get<half_t>((size_t)n) : nullptr;
+    if (!o.hi || (with_lo && !o.lo)) return nullptr;
+    hipLaunchKernelGGL(split_kernel, grid1d(n), dim3(256), 0, s, f, n, o.hi, o.lo);
+    ++n_out;
+    return &o;
+  };
+  if (d->O) {
+    Out* o = add_out(d->O, d->o_elems, split && !d->o_il);
+    if (!o) return OVM_ERR_HIP;
+    p.Ohi = o->hi; p.Olo = d->o_il ? o->hi + 32 : o->lo;
+  }
+  if (d->epi == EPI_QKV) {
+    const int64_t bh = (int64_t)((d->M + d->T - 1) / d->T) * d->heads, nqk = bh * d->T * 64, nv = bh * 64 * d->Tpad;
+    if (nv < 1) return OVM_ERR_INVALID;
+    Out* q = add_out(d->Q, nqk, split); Out* k = add_out(d->Kout, nqk, split); Out* v = add_out(d->Vt, nv, split);
+    if (!q || !k || !v) return OVM_ERR_HIP;
+    p.Qhi = q->hi; p.Qlo = q->lo; p.Khi = k->hi; p.Klo = k->lo; p.Vhi = v->hi; p.Vlo = v->lo;
+  }
+  const int rc = d->route == 1 ? launch_gemm256(p, d->epi, d->ksplit_hint, s) : launch_gemm(p, d->precision, d->epi, d->amode, s);
+  if (rc == OVM_OK)
+    for (int i = 0; i < n_out; ++i)
+      hipLaunchKernelGGL(join_kernel, grid1d(outs[i].n), dim3(256), 0, s, outs[i].hi, outs[i].lo, outs[i].n, outs[i].f);
+  if (hipStreamSynchronize(s) != hipSuccess) return OVM_ERR_HIP;          // the scratch is freed on return
+  return rc;
+}
+
 // hi, lo [rows][K] (K % 32 == 0) -> out [rows][K/32][hi 32 | lo 32], the operand image of the split-mode GEMM
 int ovm_op_interleave(const uint16_t* hi, const uint16_t* lo, int64_t rows, int32_t K, uint16_t* out, ovm_stream_t stream) {
   if (rows <= 0) return OVM_OK;

@@ -166,11 +166,29 @@ class OvmDepthProConfig(C.Structure):
     ]
 
 
+
+class OvmGemmEpiOp(C.Structure):
+    """Mirror of include/ovm3d.h OvmGemmEpiOp (ovm_op_gemm_epi: one fused GEMM epilogue in isolation, for tests)."""
+    _fields_ = [
+        ("epi", C.c_int32), ("amode", C.c_int32), ("precision", C.c_int32), ("a_il", C.c_int32), ("route", C.c_int32),
+        ("ksplit_hint", C.c_int32),
+        ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("cH", C.c_int32), ("cW", C.c_int32), ("cC", C.c_int32),
+        ("A", C.c_void_p), ("W", C.c_void_p), ("bias", C.c_void_p),
+        ("gamma", C.c_void_p), ("X", C.c_void_p), ("row_map", C.c_void_p), ("ldx", C.c_int32), ("relu", C.c_int32),
+        ("C", C.c_void_p), ("ldc", C.c_int32), ("ldo", C.c_int32),
+        ("O", C.c_void_p), ("o_elems", C.c_int64), ("o_il", C.c_int32), ("relu_o", C.c_int32),
+        ("R", C.c_void_p), ("R2", C.c_void_p), ("ldr", C.c_int32), ("ldr2", C.c_int32), ("padH", C.c_int32), ("padW", C.c_int32),
+        ("Q", C.c_void_p), ("Kout", C.c_void_p), ("Vt", C.c_void_p), ("T", C.c_int32), ("Tpad", C.c_int32), ("heads", C.c_int32),
+        ("qscale", C.c_float),
+        ("pos", C.c_void_p), ("G2", C.c_int32), ("G", C.c_int32), ("Cout", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 EXPORTS = [
     "ovm_create", "ovm_destroy", "ovm_last_error", "ovm_version", "ovm_abi_sizeof", "ovm_backbone_forward", "ovm_cube_forward",
     "ovm_rpn_box_forward", "ovm_gather_records", "ovm_gather_counts", "ovm_host_interp_pos_embed", "ovm_host_resize_pos_embed_aa", "ovm_host_sincos_pos_embed", "ovm_host_shard_range",
     "ovm_backbone_num_levels", "ovm_backbone_level",
-    "ovm_op_split_f16", "ovm_op_interleave", "ovm_op_gemm", "ovm_op_gemm_swiglu", "ovm_host_swiglu_perm", "ovm_op_layernorm", "ovm_op_attention", "ovm_op_roi_align",
+    "ovm_op_split_f16", "ovm_op_interleave", "ovm_op_gemm", "ovm_op_gemm_epi", "ovm_op_gemm_swiglu", "ovm_host_swiglu_perm", "ovm_op_layernorm", "ovm_op_attention", "ovm_op_roi_align",
     "ovm_op_cube_decode", "ovm_op_nms", "ovm_op_rpn_proposals", "ovm_op_boxhead_post", "ovm_debug_copy", "ovm_set_corun", "ovm_profile_enable", "ovm_profile_read",
     "ovm_comm_unique_id", "ovm_comm_init", "ovm_comm_destroy", "ovm_tune_set", "ovm_gdino_postprocess", "ovm_box3d_iou", "ovm_eval_iou2d", "ovm_eval_match", "ovm_host_pil_bilinear_coeffs", "ovm_resize_bilinear_u8", "ovm_resize_bilinear_f32",
     "ovm_g_pack_weight", "ovm_g_linear", "ovm_g_layernorm", "ovm_g_bmm", "ovm_g_bmm2", "ovm_g_softmax", "ovm_g_softmax2", "ovm_g_eltwise", "ovm_g_gather_rows",
@@ -212,7 +230,7 @@ def load() -> C.CDLL:
                          ("OvmJpegInfo", OvmJpegInfo), ("OvmSceneInput", OvmSceneInput), ("OvmSceneLayout", OvmSceneLayout),
                          ("OvmSceneSegment", OvmSceneSegment), ("OvmEvalCell", OvmEvalCell), ("OvmGeoParams", OvmGeoParams),
                          ("OvmGeoInstance", OvmGeoInstance), ("OvmGeoResult", OvmGeoResult), ("OvmGeoBox", OvmGeoBox),
-                         ("OvmSamConfig", OvmSamConfig), ("OvmDepthProConfig", OvmDepthProConfig)):
+                         ("OvmSamConfig", OvmSamConfig), ("OvmDepthProConfig", OvmDepthProConfig), ("OvmGemmEpiOp", OvmGemmEpiOp)):
         if lib.ovm_abi_sizeof(name.encode()) != C.sizeof(mirror):
             raise RuntimeError(f"{LIB_PATH}: sizeof({name}) = {lib.ovm_abi_sizeof(name.encode())} but the ctypes mirror has "
                                f"{C.sizeof(mirror)} bytes - rebuild the library (ovmono3d_amd/csrc/build.sh) or update lib.py")
@@ -236,6 +254,7 @@ def load() -> C.CDLL:
     lib.ovm_op_split_f16.argtypes = [vp, i64, vp, vp, vp]
     lib.ovm_op_interleave.argtypes = [vp, vp, i64, i32, vp, vp]
     lib.ovm_op_gemm.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, vp, i32, vp, i32, i32, vp]
+    lib.ovm_op_gemm_epi.argtypes = [C.POINTER(OvmGemmEpiOp), vp]
     lib.ovm_op_gemm_swiglu.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, vp]
     lib.ovm_host_swiglu_perm.argtypes = [i32, vp]
     lib.ovm_op_layernorm.argtypes = [vp, i32, i32, vp, vp, f32, vp, vp]
