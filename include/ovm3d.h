@@ -390,6 +390,12 @@ int ovm_infer(OvmHandle* h, OvmGdino* g, const OvmImage* image, const int32_t* t
  * was sequenced from in round 1 (still exported: unit tests and the Python-sequenced cross-check path use them): fp32
  * row-major tensors in HBM, one call per op, all arithmetic on the device. */
 int ovm_g_pack_weight(const float* w, int32_t N, int32_t K, int32_t Kpad, uint16_t* hi, uint16_t* lo, ovm_stream_t stream);
+/* The same image written on the host (no device call; what every model handle packs its weights with). w: host [N][K] fp32;
+ * out: host, ceil128(N) * Kpad halves for precision 1 ([Npad][Kpad]) or twice that for precision 3 (the interleaved split image
+ * [Npad][Kpad/32][hi 32 | lo 32], hi = fp16(x), lo = fp16(x - hi), round to nearest even, subnormals kept), padding rows and columns
+ * zero. OVM_ERR_INVALID for a null pointer, N < 1, K < 1, Kpad < K or a precision other than 1 and 3; OVM_ERR_SHAPE for precision 3
+ * with Kpad % 32 != 0; out is left untouched then. */
+int ovm_host_pack_weight(const float* w, int32_t N, int32_t K, int32_t Kpad, int32_t precision, uint16_t* out);
 int ovm_g_linear(const float* x, int32_t ldx, int32_t M, int32_t K, const uint16_t* w_hi, const uint16_t* w_lo, int32_t N, int32_t Kpad,
                  const float* bias, int32_t act /* 0 none, 1 relu, 2 gelu */, const float* residual, int32_t ldr, float* y, int32_t ldy,
                  int32_t precision, ovm_stream_t stream);

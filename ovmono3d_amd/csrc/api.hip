@@ -5,7 +5,6 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
@@ -14,6 +13,7 @@
 #include "det2d.hpp"
 #include "gdino.hpp"
 #include "sam.hpp"
+#include "loader.hpp"
 
 using namespace ovm;
 
@@ -21,45 +21,37 @@ static_assert(sizeof(OvmDet3D) == kRecFloats * 4, "record layout");
 
 namespace {
 
-struct Split {                 // device fp16 split tensor
-  half_t* hi = nullptr; half_t* lo = nullptr;
-};
-
-struct PackedLinear { Split w; float* bias = nullptr; int N = 0, K = 0; };
-
 struct Layer {
   float *ln1g, *ln1b, *ln2g, *ln2b, *ls1, *ls2;
-  PackedLinear qkv, proj, fc1, fc2;
+  PackedLin qkv, proj, fc1, fc2;
   // SAM tower: window side of the block (0 = global attention) and its relative-position tables [2 s - 1][64] (s = window side,
   // or the canvas grid for a global block: resized at create when the checkpoint's table has another length)
   int ws = 0; float *relh = nullptr, *relw = nullptr;
 };
 
 struct SfpStage {              // 1x1 conv + LN, 3x3 conv + LN
-  PackedLinear c1, c3; float *n1g, *n1b, *n3g, *n3b;
+  PackedLin c1, c3; float *n1g, *n1b, *n3g, *n3b;
 };
 
 struct FpnLevel {              // one output level of the simple feature pyramid, finest first ("p2", "p3", ...)
   int side = 0; float stride = 0.f;
   SfpStage st;
   float* T1 = nullptr;         // fp32 conv output (1x1, then reused by the 3x3)
-  Split pad;                   // zero-bordered LN(1x1) image: the implicit-GEMM input of the 3x3
+  SplitImg pad;                   // zero-bordered LN(1x1) image: the implicit-GEMM input of the 3x3
   float* p = nullptr;          // the level's feature map, NHWC fp32
-  Split rpad;                  // zero-bordered fp16 copy of p (RPN conv input), when the checkpoint has an RPN
+  SplitImg rpad;                  // zero-bordered fp16 copy of p (RPN conv input), when the checkpoint has an RPN
 };
 
 }  // namespace
 
-struct OvmHandle {
+struct OvmHandle : ovm::Loader {
   OvmConfig cfg;
   int device = 0;
   bool tower_only = false;          // ovm::tower_create: the ViT blocks alone (no pyramid, no heads) - the SAM predictor's image encoder
   // ovm::tower_create_ex / tower_forward_f32 (Depth Pro's encoders; all off by default): Hugging Face Dinov2Model key names with
   // patch 16 and the model's final LayerNorm (the float input and the taps are arguments of tower_launches, not handle state)
   bool hf_dinov2 = false; float *fin_g = nullptr, *fin_b = nullptr;
-  std::string err;
-  std::vector<void*> allocs;
-  int G = 0, G2 = 0, T = 0, Tpad = 0, D = 0, C = 0, Kpe = 640, npass = 1;
+  int G = 0, G2 = 0, T = 0, Tpad = 0, D = 0, C = 0, Kpe = 640;
   // DINOv2 variants, read off the checkpoint (create_impl): register tokens between the class token and the patches (T = 1 + nreg +
   // G^2), and the fused SwiGLU FFN (ffn_hs = hidden width Hs, 0 = GELU MLP; ffn_k = Hs padded to the k-step, the K of w3 / width of its input image)
   int nreg = 0, ffn_hs = 0, ffn_k = 0; float* reg = nullptr;
@@ -68,25 +60,25 @@ struct OvmHandle {
   int mlp_act = 0;                  // fc1 activation: 0 erf-GELU, 3 QuickGELU
   int roiK = 0;
   // weights
-  PackedLinear pe; float *cls = nullptr, *pos = nullptr;
+  PackedLin pe; float *cls = nullptr, *pos = nullptr;
   float *lnpre_g = nullptr, *lnpre_b = nullptr;                 // open_clip ln_pre
   // SAM tower (windowed blocks run on window-partitioned rows like the Swin backbone of the detector)
   bool sam = false; int sam_ws = 0, sam_nw = 0, sam_rows = 0;   // window side, windows per image, rows per image of the partitioned layout
   int* sam_map = nullptr;                                       // [max_batch][sam_rows]: token row of X, -1 = padding
-  Split XW, CTX; float *QKVF = nullptr, *RELH = nullptr, *RELW = nullptr; int ldrel = 0;
+  SplitImg XW, CTX; float *QKVF = nullptr, *RELH = nullptr, *RELW = nullptr; int ldrel = 0;
   std::vector<Layer> layers;
-  PackedLinear dfuse; bool has_dfuse = false;
-  PackedLinear convt;                                           // ConvT D -> D/2 (first layer of the scale-2 and scale-4 stages... per stage)
-  PackedLinear convt4a, convt4b; float *up_ln_g = nullptr, *up_ln_b = nullptr;   // scale-4 stage: ConvT D -> D/2, LN, GELU, ConvT D/2 -> D/4
+  PackedLin dfuse; bool has_dfuse = false;
+  PackedLin convt;                                           // ConvT D -> D/2 (first layer of the scale-2 and scale-4 stages... per stage)
+  PackedLin convt4a, convt4b; float *up_ln_g = nullptr, *up_ln_b = nullptr;   // scale-4 stage: ConvT D -> D/2, LN, GELU, ConvT D/2 -> D/4
   FpnLevel lv[kMaxLevels];
-  PackedLinear cube_fc1, cube_fc2, cube_out;
-  PackedLinear box_fc1, box_fc2, box_out; bool has_box = false;
-  PackedLinear rpn_conv, rpn_out; bool has_rpn = false;
+  PackedLin cube_fc1, cube_fc2, cube_out;
+  PackedLin box_fc1, box_fc2, box_out; bool has_box = false;
+  PackedLin rpn_conv, rpn_out; bool has_rpn = false;
   // workspace
   float* X = nullptr;
-  Split PA, HN, AO, F1, Q, Kx, Vt, DT, DT4, DF, CT, CT4a, CT4b;
+  SplitImg PA, HN, AO, F1, Q, Kx, Vt, DT, DT4, DF, CT, CT4a, CT4b;
   float *dtok = nullptr, *FUS = nullptr;
-  Split RF, H1, H2; float* HO = nullptr; int lastN = 0;
+  SplitImg RF, H1, H2; float* HO = nullptr; int lastN = 0;
   float* attn_tail_ws = nullptr; int* attn_tail_cnt = nullptr;     // attention's leftover-query partials / arrival counters (attn_tail.hpp)
   float* splitk_ws = nullptr; size_t splitk_cap = 0;               // split-K partials of this handle's thin GEMMs (two handles on two streams
                                                                    // must not share the launcher's process-global, re-sizable workspace)
@@ -112,136 +104,30 @@ struct OvmHandle {
 
 namespace {
 
-#define HCHECK(h, call)                                                                    \
-  do {                                                                                     \
-    hipError_t e_ = (call);                                                                \
-    if (e_ != hipSuccess) {                                                                \
-      (h)->err = std::string(#call) + ": " + hipGetErrorString(e_);                        \
-      return OVM_ERR_HIP;                                                                  \
-    }                                                                                      \
-  } while (0)
-
-#define KCHECK(h, call)                                                                    \
-  do {                                                                                     \
-    int r_ = (call);                                                                       \
-    if (r_ != OVM_OK) {                                                                    \
-      if ((h)->err.empty() || r_ != OVM_ERR_HIP) (h)->err = std::string(#call) + " failed (" + std::to_string(r_) + ")"; \
-      return r_;                                                                           \
-    }                                                                                      \
-  } while (0)
-
-template <typename Tp>
-int dalloc(OvmHandle* h, Tp** p, size_t count, bool zero = false) {
-  void* q = nullptr;
-  size_t bytes = count * sizeof(Tp);
-  if (bytes == 0) bytes = 16;
-  HCHECK(h, hipMalloc(&q, bytes));
-  h->allocs.push_back(q);
-  if (zero) HCHECK(h, hipMemset(q, 0, bytes));
-  *p = (Tp*)q;
-  return OVM_OK;
-}
-
 // interleaved split image [rows][K/32][hi 32 | lo 32] (f16x3 mode; plain fp16 rows in one-pass mode): the A-operand layout of the
 // 256 x 256 GEMM (one 128-byte LDS-DMA line per row and k-group holds both parts)
-int salloc_il(OvmHandle* h, Split* s, size_t count) {
-  if (h->npass != 3) { s->lo = nullptr; return dalloc(h, &s->hi, count); }
-  int r = dalloc(h, &s->hi, 2 * count);
+int salloc_il(OvmHandle* h, SplitImg* s, size_t count) {
+  if (h->precision != 3) { s->lo = nullptr; return h->alloc(&s->hi, count); }
+  int r = h->alloc(&s->hi, 2 * count);
   if (r) return r;
   s->lo = s->hi + 32;
   return OVM_OK;
 }
 
-int salloc(OvmHandle* h, Split* s, size_t count, bool zero = false) {
-  int r = dalloc(h, &s->hi, count, zero);
+int salloc(OvmHandle* h, SplitImg* s, size_t count, bool zero = false) {
+  int r = h->alloc(&s->hi, count, zero);
   if (r) return r;
-  if (h->npass == 3) return dalloc(h, &s->lo, count, zero);
+  if (h->precision == 3) return h->alloc(&s->lo, count, zero);
   s->lo = nullptr;
-  return OVM_OK;
-}
-
-struct WeightMap {
-  std::map<std::string, const OvmTensor*> m;
-  const OvmTensor* get(const std::string& k) const {
-    auto it = m.find(k);
-    return it == m.end() ? nullptr : it->second;
-  }
-};
-
-int64_t numel(const OvmTensor* t) { int64_t n = 1; for (int i = 0; i < t->ndim; ++i) n *= t->shape[i]; return n; }
-
-int upload_f32(OvmHandle* h, const WeightMap& wm, const std::string& key, int64_t expect, float** out) {
-  const OvmTensor* t = wm.get(key);
-  if (!t) { h->err = "missing weight: " + key; return OVM_ERR_MISSING_WEIGHT; }
-  if (numel(t) != expect) { h->err = "bad shape for " + key; return OVM_ERR_SHAPE; }
-  int r = dalloc(h, out, (size_t)expect);
-  if (r) return r;
-  HCHECK(h, hipMemcpy(*out, t->data, (size_t)expect * 4, hipMemcpyHostToDevice));
-  return OVM_OK;
-}
-
-int upload_vec(OvmHandle* h, const std::vector<float>& v, float** out) {
-  int r = dalloc(h, out, v.size());
-  if (r) return r;
-  HCHECK(h, hipMemcpy(*out, v.data(), v.size() * 4, hipMemcpyHostToDevice));
-  return OVM_OK;
-}
-
-// Pack a host [N][K] fp32 matrix (already in GEMM k-order) into device fp16: one-pass mode [Npad][Kpad]; split mode the
-// interleaved image [Npad][Kpad/32][hi 32 | lo 32] the GEMM kernels stream (gemm.hpp), w.lo = w.hi + 32.
-int upload_packed(OvmHandle* h, const std::vector<float>& w, int N, int K, int Kpad, PackedLinear* out) {
-  const int Npad = (N + 127) / 128 * 128;
-  const bool il = h->npass == 3;
-  if (il && Kpad % 32 != 0) { h->err = "packed K must be a multiple of 32"; return OVM_ERR_SHAPE; }
-  const size_t ld = il ? (size_t)2 * Kpad : (size_t)Kpad;
-  std::vector<half_t> buf((size_t)Npad * ld, (half_t)0.f);
-  for (int n = 0; n < N; ++n)
-    for (int k = 0; k < K; ++k) {
-      const float x = w[(size_t)n * K + k];
-      const half_t hh = (half_t)x;
-      if (il) {
-        const size_t o = (size_t)n * ld + (size_t)(k >> 5) * 64 + (k & 31);
-        buf[o] = hh;
-        buf[o + 32] = (half_t)((x - (float)hh) * kLoScale);
-      } else {
-        buf[(size_t)n * ld + k] = hh;
-      }
-    }
-  int r = dalloc(h, &out->w.hi, buf.size());
-  if (r) return r;
-  HCHECK(h, hipMemcpy(out->w.hi, buf.data(), buf.size() * 2, hipMemcpyHostToDevice));
-  out->w.lo = il ? out->w.hi + 32 : nullptr;
-  out->N = N; out->K = Kpad;
-  return OVM_OK;
-}
-
-int get_host(OvmHandle* h, const WeightMap& wm, const std::string& key, int64_t expect, const float** p) {
-  const OvmTensor* t = wm.get(key);
-  if (!t) { h->err = "missing weight: " + key; return OVM_ERR_MISSING_WEIGHT; }
-  if (numel(t) != expect) { h->err = "bad shape for " + key + " (expected " + std::to_string(expect) + ")"; return OVM_ERR_SHAPE; }
-  *p = t->data;
-  return OVM_OK;
-}
-
-// nn.Linear weight [N][K] (+ optional bias) -> packed
-int pack_linear(OvmHandle* h, const WeightMap& wm, const std::string& prefix, int N, int K, PackedLinear* out,
-                bool bias = true, int Kpad = -1) {
-  const float* w; int r = get_host(h, wm, prefix + ".weight", (int64_t)N * K, &w);
-  if (r) return r;
-  std::vector<float> v(w, w + (size_t)N * K);
-  r = upload_packed(h, v, N, K, Kpad < 0 ? K : Kpad, out);
-  if (r) return r;
-  if (bias) return upload_f32(h, wm, prefix + ".bias", N, &out->bias);
-  out->bias = nullptr;
   return OVM_OK;
 }
 
 // dinov2 SwiGLUFFNFused.w12 [2 Hs][K] (rows [0, Hs) gates, [Hs, 2 Hs) values) -> the row order EPI_SWIGLU pairs (gemm.hpp): blocks of
 // 16 gates | 16 values, outputs padded to Kp (a multiple of 32, >= Hs) with zero rows and zero bias (silu(0) * 0 = 0 fills the pad columns)
-int pack_swiglu_w12(OvmHandle* h, const WeightMap& wm, const std::string& prefix, int Hs, int Kp, int K, PackedLinear* out) {
+int pack_swiglu_w12(OvmHandle* h, const WeightMap& wm, const std::string& prefix, int Hs, int Kp, int K, PackedLin* out) {
   const float *w, *b;
-  int r = get_host(h, wm, prefix + ".weight", (int64_t)2 * Hs * K, &w); if (r) return r;
-  r = get_host(h, wm, prefix + ".bias", (int64_t)2 * Hs, &b); if (r) return r;
+  int r = find_weight(h, wm, prefix + ".weight", (int64_t)2 * Hs * K, &w); if (r) return r;
+  r = find_weight(h, wm, prefix + ".bias", (int64_t)2 * Hs, &b); if (r) return r;
   const int K32 = (Hs + 31) / 32 * 32;
   if (Kp % 32 != 0 || Kp < K32) return OVM_ERR_INVALID;
   std::vector<int32_t> perm((size_t)2 * K32);
@@ -249,91 +135,32 @@ int pack_swiglu_w12(OvmHandle* h, const WeightMap& wm, const std::string& prefix
   std::vector<float> v((size_t)2 * Kp * K, 0.f), bv((size_t)2 * Kp, 0.f);
   for (int n = 0; n < 2 * K32; ++n)                        // rows beyond 2 ceil32(Hs) are all padding
     if (perm[n] >= 0) { memcpy(&v[(size_t)n * K], w + (size_t)perm[n] * K, (size_t)K * 4); bv[n] = b[perm[n]]; }
-  r = upload_packed(h, v, 2 * Kp, K, K, out); if (r) return r;
-  return upload_vec(h, bv, &out->bias);
-}
-
-// conv weight [Cout][Cin][k][k] -> [Cout][(ky*k+kx)*Cin + c]
-int pack_conv(OvmHandle* h, const WeightMap& wm, const std::string& prefix, int Cout, int Cin, int k, PackedLinear* out,
-              bool bias) {
-  const float* w; int r = get_host(h, wm, prefix + ".weight", (int64_t)Cout * Cin * k * k, &w);
-  if (r) return r;
-  std::vector<float> v((size_t)Cout * Cin * k * k);
-  for (int o = 0; o < Cout; ++o)
-    for (int c = 0; c < Cin; ++c)
-      for (int t = 0; t < k * k; ++t) v[((size_t)o * k * k + t) * Cin + c] = w[((size_t)o * Cin + c) * k * k + t];
-  r = upload_packed(h, v, Cout, Cin * k * k, Cin * k * k, out);
-  if (r) return r;
-  if (bias) return upload_f32(h, wm, prefix + ".bias", Cout, &out->bias);
-  out->bias = nullptr;
-  return OVM_OK;
+  return upload_packed(h, v.data(), 2 * Kp, K, K, bv.data(), 2 * Kp, out);
 }
 
 // FC over pooled RoI features: reference flatten order is (c, ph, pw); ROIAlign here emits (ph, pw, c)
-int pack_roi_fc(OvmHandle* h, const WeightMap& wm, const std::string& prefix, int N, int C, int res, PackedLinear* out) {
+int pack_roi_fc(OvmHandle* h, const WeightMap& wm, const std::string& prefix, int N, int C, int res, PackedLin* out) {
   const int K = C * res * res;
-  const float* w; int r = get_host(h, wm, prefix + ".weight", (int64_t)N * K, &w);
-  if (r) return r;
+  const float *w, *b;
+  int r = find_weight(h, wm, prefix + ".weight", (int64_t)N * K, &w); if (r) return r;
+  r = find_weight(h, wm, prefix + ".bias", N, &b); if (r) return r;
   std::vector<float> v((size_t)N * K);
   for (int n = 0; n < N; ++n)
     for (int c = 0; c < C; ++c)
       for (int s = 0; s < res * res; ++s) v[(size_t)n * K + (size_t)s * C + c] = w[(size_t)n * K + (size_t)c * res * res + s];
-  r = upload_packed(h, v, N, K, K, out);
-  if (r) return r;
-  return upload_f32(h, wm, prefix + ".bias", N, &out->bias);
-}
-
-// several small nn.Linear heads sharing one input, concatenated along N
-int pack_concat(OvmHandle* h, const WeightMap& wm, const std::vector<std::pair<std::string, int>>& parts, int K,
-                PackedLinear* out) {
-  int N = 0; for (auto& p : parts) N += p.second;
-  std::vector<float> v((size_t)N * K), b((size_t)N);
-  int n0 = 0;
-  for (auto& p : parts) {
-    const float *w, *bb;
-    int r = get_host(h, wm, p.first + ".weight", (int64_t)p.second * K, &w); if (r) return r;
-    r = get_host(h, wm, p.first + ".bias", p.second, &bb); if (r) return r;
-    memcpy(&v[(size_t)n0 * K], w, (size_t)p.second * K * 4);
-    memcpy(&b[n0], bb, (size_t)p.second * 4);
-    n0 += p.second;
-  }
-  int r = upload_packed(h, v, N, K, K, out);
-  if (r) return r;
-  return upload_vec(h, b, &out->bias);
-}
-
-// nn.Linear stored as bare parameters (nn.MultiheadAttention in_proj_weight / in_proj_bias)
-int pack_linear_named(OvmHandle* h, const WeightMap& wm, const std::string& wkey, const std::string& bkey, int N, int K, PackedLinear* out) {
-  const float* w; int r = get_host(h, wm, wkey, (int64_t)N * K, &w);
-  if (r) return r;
-  std::vector<float> v(w, w + (size_t)N * K);
-  r = upload_packed(h, v, N, K, K, out);
-  if (r) return r;
-  return upload_f32(h, wm, bkey, N, &out->bias);
-}
-
-// ConvTranspose2d k2 s2 weight [Cin][Cout][2][2] -> GEMM rows [(a*2+b)*Cout + co][ci]; bias [Cout] (applied per co in EPI_CONVT)
-int pack_convt(OvmHandle* h, const WeightMap& wm, const std::string& prefix, int Cin, int Cout, PackedLinear* out) {
-  const float* w; int r = get_host(h, wm, prefix + ".weight", (int64_t)Cin * Cout * 4, &w);
-  if (r) return r;
-  std::vector<float> v((size_t)4 * Cout * Cin);
-  for (int ci = 0; ci < Cin; ++ci)
-    for (int co = 0; co < Cout; ++co)
-      for (int q = 0; q < 4; ++q) v[((size_t)q * Cout + co) * Cin + ci] = w[((size_t)ci * Cout + co) * 4 + q];
-  r = upload_packed(h, v, 4 * Cout, Cin, Cin, out);
-  if (r) return r;
-  return upload_f32(h, wm, prefix + ".bias", Cout, &out->bias);
+  return upload_packed(h, v.data(), N, K, K, b, N, out);
 }
 
 int pack_sfp_stage(OvmHandle* h, const WeightMap& wm, const std::string& p1, const std::string& p3, int Cin, SfpStage* s) {
   const int C = h->C;
-  int r = pack_conv(h, wm, p1, C, Cin, 1, &s->c1, false); if (r) return r;
-  r = upload_f32(h, wm, p1 + ".norm.weight", C, &s->n1g); if (r) return r;
-  r = upload_f32(h, wm, p1 + ".norm.bias", C, &s->n1b); if (r) return r;
-  r = pack_conv(h, wm, p3, C, C, 3, &s->c3, false); if (r) return r;
-  r = upload_f32(h, wm, p3 + ".norm.weight", C, &s->n3g); if (r) return r;
-  return upload_f32(h, wm, p3 + ".norm.bias", C, &s->n3b);
+  int r = pack_conv(h, wm, p1, C, Cin, 1, BIAS_NONE, &s->c1); if (r) return r;
+  r = upload_weight(h, wm, p1 + ".norm.weight", C, &s->n1g); if (r) return r;
+  r = upload_weight(h, wm, p1 + ".norm.bias", C, &s->n1b); if (r) return r;
+  r = pack_conv(h, wm, p3, C, C, 3, BIAS_NONE, &s->c3); if (r) return r;
+  r = upload_weight(h, wm, p3 + ".norm.weight", C, &s->n3g); if (r) return r;
+  return upload_weight(h, wm, p3 + ".norm.bias", C, &s->n3b);
 }
+
 
 struct ProfScope {
   OvmHandle* h; int cat; hipStream_t s; hipEvent_t stop = nullptr;
@@ -363,22 +190,22 @@ int gemm(OvmHandle* h, const GemmParams& p_in, int epi, int amode, hipStream_t s
   // two-wave-group 256 x 256 kernel; everything else keeps the 128 x 128 kernels
   // (at batch >= 4 the N = D contractions - proj, fc2 - reach that tile count too: 128 x 128 tiles fetch twice the operand bytes
   // per MFMA from L2, which is what bounds them at batch 1, where only 128-wide tiles fill the chip)
-  if (g_use_gemm256 && amode == A_ROWMAJOR && gemm256_supported(p, h->npass) &&
+  if (g_use_gemm256 && amode == A_ROWMAJOR && gemm256_supported(p, h->precision) &&
       (long)((p.M + 255) / 256) * (p.N / 256) >= 192 &&
       (epi == EPI_STORE || epi == EPI_RESID || epi == EPI_GELU || epi == EPI_QKV || epi == EPI_SWIGLU))   // w12 of ViT-g: N = 8192, 192 tiles from T = 1281
     return launch_gemm256(p, epi, 1, s);
   // experiment knob (ovm_tune_set "gemm256_ksplit"): the long-K contractions with too few 256-wide tiles (fc2 at batch 1: 64 tiles,
   // K = 4096) as k-slices of 256 x 256 tiles + a reduce pass - half the operand fetch of 128 x 128 tiles
-  if (g_gemm256_ksplit > 1 && amode == A_ROWMAJOR && gemm256_supported(p, h->npass) && epi == EPI_RESID && p.K >= 2048 && !p.row_map)
+  if (g_gemm256_ksplit > 1 && amode == A_ROWMAJOR && gemm256_supported(p, h->precision) && epi == EPI_RESID && p.K >= 2048 && !p.row_map)
     return launch_gemm256(p, epi, g_gemm256_ksplit, s);
-  return launch_gemm(p, h->npass, epi, amode, s);
+  return launch_gemm(p, h->precision, epi, amode, s);
 }
 
-GemmParams gp_base(const Split& A, int lda, const PackedLinear& W, int M) {
+GemmParams gp_base(const SplitImg& A, int lda, const PackedLin& W, int M) {
   GemmParams p; memset(&p, 0, sizeof(p));
   p.Ahi = A.hi; p.Alo = A.lo; p.lda = lda;
-  p.Whi = W.w.hi; p.Wlo = W.w.lo;
-  p.M = M; p.N = W.N; p.K = W.K; p.bias = W.bias;
+  p.Whi = W.hi; p.Wlo = W.lo;
+  p.M = M; p.N = W.N; p.K = W.Kpad; p.bias = W.bias;
   return p;
 }
 
@@ -432,7 +259,7 @@ const char* ovm_last_error(const OvmHandle* h) { return h ? h->err.c_str() : "nu
 int ovm_destroy(OvmHandle* h) {
   if (!h) return OVM_OK;
   hipSetDevice(h->device);
-  for (void* p : h->allocs) hipFree(p);
+  h->free_all();
   if (h->h_imgs) hipHostFree(h->h_imgs);
   if (h->h_meta) hipHostFree(h->h_meta);
   if (h->inf_host) hipHostFree(h->inf_host);
@@ -452,51 +279,6 @@ int ovm_host_shard_range(int64_t n, int32_t rank, int32_t world, int64_t* begin,
   const int64_t b = rank * q + (rank < r ? rank : r);
   *begin = b;
   *end = b + q + (rank < r ? 1 : 0);
-  return OVM_OK;
-}
-
-// PyTorch upsample_bicubic2d, align_corners=False, scale_factor given (so the source scale is
-// 1/scale_factor, which is what dinov2's +0.1 offset relies on), A = -0.75, border indices clamped.
-int ovm_host_interp_pos_embed(const float* pos, int32_t M, int32_t D, int32_t G, float* out) {
-  if (M <= 0 || D <= 0 || G <= 0) return OVM_ERR_INVALID;
-  memcpy(out, pos, (size_t)D * 4);
-  if (G == M) { memcpy(out + D, pos + D, (size_t)M * M * D * 4); return OVM_OK; }
-  const double sf = ((double)G + 0.1) / (double)M;                  // python: float(w0 + 0.1) / M (double)
-  const float scale = (float)(1.0 / sf);
-  auto coef = [](float t, float* w) {
-    const float A = -0.75f;
-    auto c1 = [&](float x) { return ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f; };
-    auto c2 = [&](float x) { return ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A; };
-    w[0] = c2(t + 1.f); w[1] = c1(t); w[2] = c1(1.f - t); w[3] = c2(2.f - t);
-  };
-  const float* src = pos + D;
-  float* dst = out + D;
-  for (int oy = 0; oy < G; ++oy) {
-    const float ry = scale * ((float)oy + 0.5f) - 0.5f;
-    const int iy = (int)floorf(ry);
-    float wy[4]; coef(ry - (float)iy, wy);
-    for (int ox = 0; ox < G; ++ox) {
-      const float rx = scale * ((float)ox + 0.5f) - 0.5f;
-      const int ix = (int)floorf(rx);
-      float wx[4]; coef(rx - (float)ix, wx);
-      float* o = dst + ((size_t)oy * G + ox) * D;
-      for (int d = 0; d < D; ++d) o[d] = 0.f;
-      for (int a = 0; a < 4; ++a) {
-        int yy = iy - 1 + a; yy = yy < 0 ? 0 : (yy > M - 1 ? M - 1 : yy);
-        float rowacc_w[4];
-        for (int b = 0; b < 4; ++b) rowacc_w[b] = wx[b];
-        // PyTorch evaluates cubic_interp1d along x first for each of the 4 rows, then along y
-        for (int d = 0; d < D; ++d) {
-          float acc = 0.f;
-          for (int b = 0; b < 4; ++b) {
-            int xx = ix - 1 + b; xx = xx < 0 ? 0 : (xx > M - 1 ? M - 1 : xx);
-            acc += src[((size_t)yy * M + xx) * D + d] * rowacc_w[b];
-          }
-          o[d] += acc * wy[a];
-        }
-      }
-    }
-  }
   return OVM_OK;
 }
 
@@ -616,6 +398,15 @@ static void host_linear_rows(const float* src, int L, int C, int Lo, float* dst)
 
 extern "C" {
 
+// dinov2 interpolate_pos_encoding of a table [1 + M*M][D], class row kept: PyTorch upsample_bicubic2d, align_corners=False,
+// scale_factor given (so the source scale is 1/scale_factor, which is what dinov2's +0.1 offset relies on).
+int ovm_host_interp_pos_embed(const float* pos, int32_t M, int32_t D, int32_t G, float* out) {
+  if (M <= 0 || D <= 0 || G <= 0) return OVM_ERR_INVALID;
+  memcpy(out, pos, (size_t)D * 4);
+  const double sf = ((double)G + 0.1) / (double)M;                  // python: float(w0 + 0.1) / M (double)
+  return host_bicubic_grid(pos + D, M, D, G, (float)(1.0 / sf), out + D);
+}
+
 int ovm_host_swiglu_perm(int32_t Hs, int32_t* perm) {
   if (Hs < 1 || !perm) return OVM_ERR_INVALID;
   const int Kp = (Hs + 31) / 32 * 32;
@@ -673,8 +464,7 @@ static int create_impl(const OvmConfig* cfg, const OvmTensor* weights, int32_t n
     h->err = "invalid config (canvas % patch, embed_dim = heads*64 and %128 (%256 for 4-level towers), precision in {1,3}, fpn_channels %64)";
     return OVM_ERR_INVALID;
   }
-  WeightMap wm;
-  for (int i = 0; i < n_weights; ++i) wm.m[weights[i].name] = &weights[i];
+  const WeightMap wm(weights, n_weights);
   const std::string V = vit_prefix ? vit_prefix : (clip ? "backbone.net.visual." : "backbone.net.vit.");
   if (!p16 && !hf && weights) {
     // DINOv2 variants: OvmConfig carries no field for them, the checkpoint does (as has_box below). Host-only checks, before any device call.
@@ -704,15 +494,15 @@ static int create_impl(const OvmConfig* cfg, const OvmTensor* weights, int32_t n
       h->ffn_hs = (int)Hs; h->ffn_k = (int)Kp;
     }
   }
-  HCHECK(h, hipSetDevice(device));
-  h->npass = c.precision;
+  OVM_HIP(h, hipSetDevice(device));
+  h->precision = c.precision;
   h->D = c.embed_dim; h->C = c.fpn_channels;
   h->G = c.canvas / h->patch; h->G2 = h->G * h->G; h->T = h->G2 + (sam ? 0 : 1) + h->nreg; h->Tpad = (h->T + 63) / 64 * 64;
   const int D = h->D, C = h->C, G = h->G, G2 = h->G2, T = h->T, L = c.depth, B = c.max_batch, R = c.max_rois;
   {
     // The GEMM kernels address operands with 32-bit element offsets (gemm.hip: gemm_offsets_fit): refuse a max_batch / max_rois
     // whose largest activation image would not fit, here, before anything is allocated - not at the first oversized launch.
-    const uint64_t il = h->npass == 3 ? 2 : 1;                       // interleaved split rows are 2K halves long
+    const uint64_t il = h->precision == 3 ? 2 : 1;                       // interleaved split rows are 2K halves long
     const uint64_t side0 = (uint64_t)(p16 ? 4 : 2) * G + 2;          // finest pyramid level, zero-bordered
     const uint64_t worst[] = {(uint64_t)B * T * 4 * D * il,          // fc2's input (GELU output), the longest activation rows
                               (uint64_t)B * G2 * h->Kpe,             // patch rows
@@ -729,59 +519,59 @@ static int create_impl(const OvmConfig* cfg, const OvmTensor* weights, int32_t n
   const std::string PEW = clip ? "conv1.weight" : ((mae || hf) ? "embeddings.patch_embeddings.projection.weight" : "patch_embed.proj.weight");
   // ---- patch embed: [D][3][P][P] -> [D][(py*P+px)*3 + c]; P = 14: K padded 588 -> 640
   {
-    const float* w; r = get_host(h, wm, V + PEW, (int64_t)D * 3 * PP, &w); if (r) return r;
+    const float* w; r = find_weight(h, wm, V + PEW, (int64_t)D * 3 * PP, &w); if (r) return r;
     std::vector<float> v((size_t)D * 3 * PP);
     for (int o = 0; o < D; ++o)
       for (int ch = 0; ch < 3; ++ch)
         for (int t = 0; t < PP; ++t) v[(size_t)o * 3 * PP + t * 3 + ch] = w[((size_t)o * 3 + ch) * PP + t];
-    r = upload_packed(h, v, D, 3 * PP, h->Kpe, &h->pe); if (r) return r;
+    r = upload_packed(h, v.data(), D, 3 * PP, h->Kpe, nullptr, 0, &h->pe); if (r) return r;
     const float* pos;
     std::vector<float> pi((size_t)(G2 + (sam ? 0 : 1)) * D);         // one row per patch (+ class row): register tokens have none
     if (clip) {                                            // conv1 has no bias (open_clip VisionTransformer)
       h->pe.bias = nullptr;
-      r = upload_f32(h, wm, V + "class_embedding", D, &h->cls); if (r) return r;
-      r = get_host(h, wm, V + "positional_embedding", (int64_t)(1 + c.pos_grid * c.pos_grid) * D, &pos); if (r) return r;
+      r = upload_weight(h, wm, V + "class_embedding", D, &h->cls); if (r) return r;
+      r = find_weight(h, wm, V + "positional_embedding", (int64_t)(1 + c.pos_grid * c.pos_grid) * D, &pos); if (r) return r;
       r = ovm_host_resize_pos_embed_aa(pos, c.pos_grid, D, G, pi.data()); if (r) return r;
-      r = upload_f32(h, wm, V + "ln_pre.weight", D, &h->lnpre_g); if (r) return r;
-      r = upload_f32(h, wm, V + "ln_pre.bias", D, &h->lnpre_b); if (r) return r;
+      r = upload_weight(h, wm, V + "ln_pre.weight", D, &h->lnpre_g); if (r) return r;
+      r = upload_weight(h, wm, V + "ln_pre.bias", D, &h->lnpre_b); if (r) return r;
     } else if (hf) {                                       // HF Dinov2Embeddings at its own grid: interpolate_pos_encoding returns the table as it is
       if (c.pos_grid != G) { h->err = "HF DINOv2 tower: the position table must have the canvas grid (no interpolation)"; return OVM_ERR_UNSUPPORTED; }
-      r = upload_f32(h, wm, V + "embeddings.patch_embeddings.projection.bias", D, &h->pe.bias); if (r) return r;
-      r = upload_f32(h, wm, V + "embeddings.cls_token", D, &h->cls); if (r) return r;
-      r = get_host(h, wm, V + "embeddings.position_embeddings", (int64_t)(1 + G2) * D, &pos); if (r) return r;
+      r = upload_weight(h, wm, V + "embeddings.patch_embeddings.projection.bias", D, &h->pe.bias); if (r) return r;
+      r = upload_weight(h, wm, V + "embeddings.cls_token", D, &h->cls); if (r) return r;
+      r = find_weight(h, wm, V + "embeddings.position_embeddings", (int64_t)(1 + G2) * D, &pos); if (r) return r;
       memcpy(pi.data(), pos, pi.size() * 4);
-      r = upload_f32(h, wm, V + "layernorm.weight", D, &h->fin_g); if (r) return r;
-      r = upload_f32(h, wm, V + "layernorm.bias", D, &h->fin_b); if (r) return r;
+      r = upload_weight(h, wm, V + "layernorm.weight", D, &h->fin_g); if (r) return r;
+      r = upload_weight(h, wm, V + "layernorm.bias", D, &h->fin_b); if (r) return r;
     } else if (sam) {                                      // segment_anything: no class token, table [grid][grid][D], plain bicubic resize (sam.py:73-86)
-      r = upload_f32(h, wm, V + "patch_embed.proj.bias", D, &h->pe.bias); if (r) return r;
-      r = get_host(h, wm, V + "pos_embed", (int64_t)c.pos_grid * c.pos_grid * D, &pos); if (r) return r;
+      r = upload_weight(h, wm, V + "patch_embed.proj.bias", D, &h->pe.bias); if (r) return r;
+      r = find_weight(h, wm, V + "pos_embed", (int64_t)c.pos_grid * c.pos_grid * D, &pos); if (r) return r;
       r = host_bicubic_grid(pos, c.pos_grid, D, G, (float)c.pos_grid / (float)G, pi.data()); if (r) return r;
     } else if (mae) {                                      // HF ViTMAE embeddings, position table rebuilt for this grid (mae.py:62-78)
-      r = upload_f32(h, wm, V + "embeddings.patch_embeddings.projection.bias", D, &h->pe.bias); if (r) return r;
-      r = upload_f32(h, wm, V + "embeddings.cls_token", D, &h->cls); if (r) return r;
+      r = upload_weight(h, wm, V + "embeddings.patch_embeddings.projection.bias", D, &h->pe.bias); if (r) return r;
+      r = upload_weight(h, wm, V + "embeddings.cls_token", D, &h->cls); if (r) return r;
       r = ovm_host_sincos_pos_embed(D, G, pi.data()); if (r) return r;
     } else {
-      r = upload_f32(h, wm, V + "patch_embed.proj.bias", D, &h->pe.bias); if (r) return r;
-      r = upload_f32(h, wm, V + "cls_token", D, &h->cls); if (r) return r;
-      r = get_host(h, wm, V + "pos_embed", (int64_t)(1 + c.pos_grid * c.pos_grid) * D, &pos); if (r) return r;
+      r = upload_weight(h, wm, V + "patch_embed.proj.bias", D, &h->pe.bias); if (r) return r;
+      r = upload_weight(h, wm, V + "cls_token", D, &h->cls); if (r) return r;
+      r = find_weight(h, wm, V + "pos_embed", (int64_t)(1 + c.pos_grid * c.pos_grid) * D, &pos); if (r) return r;
       // timm ViT of MiDaS: the reference resizes with the CLIP tower's antialiased bicubic (midas_final.py:64-66); DINOv2: hub rule
       // the hub's *_reg models are built with interpolate_offset = 0, interpolate_antialias = True: F.interpolate(size = (G, G),
       // bicubic, antialias), the resize of the CLIP tower
       r = (midas || h->nreg) ? ovm_host_resize_pos_embed_aa(pos, c.pos_grid, D, G, pi.data()) : ovm_host_interp_pos_embed(pos, c.pos_grid, D, G, pi.data());
       if (r) return r;
-      if (h->nreg && (r = upload_f32(h, wm, V + "register_tokens", (int64_t)h->nreg * D, &h->reg))) return r;
+      if (h->nreg && (r = upload_weight(h, wm, V + "register_tokens", (int64_t)h->nreg * D, &h->reg))) return r;
     }
-    r = upload_vec(h, pi, &h->pos); if (r) return r;
+    r = upload_f32(h, pi.data(), pi.size(), &h->pos); if (r) return r;
   }
   h->layers.resize(L);
   for (int l = 0; l < L; ++l) {
     Layer& y = h->layers[l];
     if (clip) {                                            // open_clip ResidualAttentionBlock: ln_1, attn (nn.MultiheadAttention), ln_2, mlp
       const std::string Pq = V + "transformer.resblocks." + std::to_string(l) + ".";
-      if ((r = upload_f32(h, wm, Pq + "ln_1.weight", D, &y.ln1g))) return r;
-      if ((r = upload_f32(h, wm, Pq + "ln_1.bias", D, &y.ln1b))) return r;
-      if ((r = upload_f32(h, wm, Pq + "ln_2.weight", D, &y.ln2g))) return r;
-      if ((r = upload_f32(h, wm, Pq + "ln_2.bias", D, &y.ln2b))) return r;
+      if ((r = upload_weight(h, wm, Pq + "ln_1.weight", D, &y.ln1g))) return r;
+      if ((r = upload_weight(h, wm, Pq + "ln_1.bias", D, &y.ln1b))) return r;
+      if ((r = upload_weight(h, wm, Pq + "ln_2.weight", D, &y.ln2g))) return r;
+      if ((r = upload_weight(h, wm, Pq + "ln_2.bias", D, &y.ln2b))) return r;
       y.ls1 = y.ls2 = nullptr;                             // no LayerScale
       if ((r = pack_linear_named(h, wm, Pq + "attn.in_proj_weight", Pq + "attn.in_proj_bias", 3 * D, D, &y.qkv))) return r;
       if ((r = pack_linear(h, wm, Pq + "attn.out_proj", D, D, &y.proj))) return r;
@@ -791,10 +581,10 @@ static int create_impl(const OvmConfig* cfg, const OvmTensor* weights, int32_t n
     }
     if (sam) {                                             // segment_anything Block: norm1, attn (qkv, proj, rel_pos_h / _w), norm2, mlp (lin1, lin2)
       const std::string Pq = V + "blocks." + std::to_string(l) + ".";
-      if ((r = upload_f32(h, wm, Pq + "norm1.weight", D, &y.ln1g))) return r;
-      if ((r = upload_f32(h, wm, Pq + "norm1.bias", D, &y.ln1b))) return r;
-      if ((r = upload_f32(h, wm, Pq + "norm2.weight", D, &y.ln2g))) return r;
-      if ((r = upload_f32(h, wm, Pq + "norm2.bias", D, &y.ln2b))) return r;
+      if ((r = upload_weight(h, wm, Pq + "norm1.weight", D, &y.ln1g))) return r;
+      if ((r = upload_weight(h, wm, Pq + "norm1.bias", D, &y.ln1b))) return r;
+      if ((r = upload_weight(h, wm, Pq + "norm2.weight", D, &y.ln2g))) return r;
+      if ((r = upload_weight(h, wm, Pq + "norm2.bias", D, &y.ln2b))) return r;
       y.ls1 = y.ls2 = nullptr;
       if ((r = pack_linear(h, wm, Pq + "attn.qkv", 3 * D, D, &y.qkv))) return r;
       if ((r = pack_linear(h, wm, Pq + "attn.proj", D, D, &y.proj))) return r;
@@ -808,18 +598,18 @@ static int create_impl(const OvmConfig* cfg, const OvmTensor* weights, int32_t n
         if (!t || t->ndim != 2 || t->shape[1] != 64) { h->err = "missing or mis-shaped weight: " + key; return OVM_ERR_MISSING_WEIGHT; }
         std::vector<float> tab((size_t)(2 * side - 1) * 64);
         host_linear_rows(t->data, (int)t->shape[0], 64, 2 * side - 1, tab.data());     // get_rel_pos: F.interpolate(mode="linear") when lengths differ
-        if ((r = upload_vec(h, tab, hw ? &y.relw : &y.relh))) return r;
+        if ((r = upload_f32(h, tab.data(), tab.size(), hw ? &y.relw : &y.relh))) return r;
       }
       continue;
     }
     if (hf) {                                              // HF Dinov2Layer: norm1, attention (query / key / value, output.dense), layer_scale1, norm2, mlp, layer_scale2
       const std::string Pq = V + "encoder.layer." + std::to_string(l) + ".";
-      if ((r = upload_f32(h, wm, Pq + "norm1.weight", D, &y.ln1g))) return r;
-      if ((r = upload_f32(h, wm, Pq + "norm1.bias", D, &y.ln1b))) return r;
-      if ((r = upload_f32(h, wm, Pq + "norm2.weight", D, &y.ln2g))) return r;
-      if ((r = upload_f32(h, wm, Pq + "norm2.bias", D, &y.ln2b))) return r;
-      if ((r = upload_f32(h, wm, Pq + "layer_scale1.lambda1", D, &y.ls1))) return r;
-      if ((r = upload_f32(h, wm, Pq + "layer_scale2.lambda1", D, &y.ls2))) return r;
+      if ((r = upload_weight(h, wm, Pq + "norm1.weight", D, &y.ln1g))) return r;
+      if ((r = upload_weight(h, wm, Pq + "norm1.bias", D, &y.ln1b))) return r;
+      if ((r = upload_weight(h, wm, Pq + "norm2.weight", D, &y.ln2g))) return r;
+      if ((r = upload_weight(h, wm, Pq + "norm2.bias", D, &y.ln2b))) return r;
+      if ((r = upload_weight(h, wm, Pq + "layer_scale1.lambda1", D, &y.ls1))) return r;
+      if ((r = upload_weight(h, wm, Pq + "layer_scale2.lambda1", D, &y.ls2))) return r;
       const std::string A = Pq + "attention.attention.";
       if ((r = pack_concat(h, wm, {{A + "query", D}, {A + "key", D}, {A + "value", D}}, D, &y.qkv))) return r;
       if ((r = pack_linear(h, wm, Pq + "attention.output.dense", D, D, &y.proj))) return r;
@@ -829,10 +619,10 @@ static int create_impl(const OvmConfig* cfg, const OvmTensor* weights, int32_t n
     }
     if (mae) {                                             // HF ViTLayer: layernorm_before, attention (q / k / v / output.dense), layernorm_after, MLP
       const std::string Pq = V + "encoder.layer." + std::to_string(l) + ".";
-      if ((r = upload_f32(h, wm, Pq + "layernorm_before.weight", D, &y.ln1g))) return r;
-      if ((r = upload_f32(h, wm, Pq + "layernorm_before.bias", D, &y.ln1b))) return r;
-      if ((r = upload_f32(h, wm, Pq + "layernorm_after.weight", D, &y.ln2g))) return r;
-      if ((r = upload_f32(h, wm, Pq + "layernorm_after.bias", D, &y.ln2b))) return r;
+      if ((r = upload_weight(h, wm, Pq + "layernorm_before.weight", D, &y.ln1g))) return r;
+      if ((r = upload_weight(h, wm, Pq + "layernorm_before.bias", D, &y.ln1b))) return r;
+      if ((r = upload_weight(h, wm, Pq + "layernorm_after.weight", D, &y.ln2g))) return r;
+      if ((r = upload_weight(h, wm, Pq + "layernorm_after.bias", D, &y.ln2b))) return r;
       y.ls1 = y.ls2 = nullptr;
       const std::string A = Pq + "attention.attention.";
       if ((r = pack_concat(h, wm, {{A + "query", D}, {A + "key", D}, {A + "value", D}}, D, &y.qkv))) return r;
@@ -842,14 +632,14 @@ static int create_impl(const OvmConfig* cfg, const OvmTensor* weights, int32_t n
       continue;
     }
     const std::string P = V + "blocks." + std::to_string(l) + ".";
-    if ((r = upload_f32(h, wm, P + "norm1.weight", D, &y.ln1g))) return r;
-    if ((r = upload_f32(h, wm, P + "norm1.bias", D, &y.ln1b))) return r;
-    if ((r = upload_f32(h, wm, P + "norm2.weight", D, &y.ln2g))) return r;
-    if ((r = upload_f32(h, wm, P + "norm2.bias", D, &y.ln2b))) return r;
+    if ((r = upload_weight(h, wm, P + "norm1.weight", D, &y.ln1g))) return r;
+    if ((r = upload_weight(h, wm, P + "norm1.bias", D, &y.ln1b))) return r;
+    if ((r = upload_weight(h, wm, P + "norm2.weight", D, &y.ln2g))) return r;
+    if ((r = upload_weight(h, wm, P + "norm2.bias", D, &y.ln2b))) return r;
     if (midas) { y.ls1 = y.ls2 = nullptr; }                // timm Block with init_values=None: LayerScale is Identity
     else {
-      if ((r = upload_f32(h, wm, P + "ls1.gamma", D, &y.ls1))) return r;
-      if ((r = upload_f32(h, wm, P + "ls2.gamma", D, &y.ls2))) return r;
+      if ((r = upload_weight(h, wm, P + "ls1.gamma", D, &y.ls1))) return r;
+      if ((r = upload_weight(h, wm, P + "ls2.gamma", D, &y.ls2))) return r;
     }
     if ((r = pack_linear(h, wm, P + "attn.qkv", 3 * D, D, &y.qkv))) return r;
     if ((r = pack_linear(h, wm, P + "attn.proj", D, D, &y.proj))) return r;
@@ -878,14 +668,14 @@ static int create_impl(const OvmConfig* cfg, const OvmTensor* weights, int32_t n
     int li = 0;
     auto sname = [&](int lvl, int idx) { return "backbone.simfp_" + std::to_string(first + lvl) + "." + std::to_string(idx); };
     if (p16) {
-      if ((r = pack_convt(h, wm, sname(li, 0), D, D / 2, &h->convt4a))) return r;
-      if ((r = upload_f32(h, wm, sname(li, 1) + ".weight", D / 2, &h->up_ln_g))) return r;
-      if ((r = upload_f32(h, wm, sname(li, 1) + ".bias", D / 2, &h->up_ln_b))) return r;
-      if ((r = pack_convt(h, wm, sname(li, 3), D / 2, D / 4, &h->convt4b))) return r;
+      if ((r = pack_convt(h, wm, sname(li, 0), D, D / 2, BIAS_REQUIRED, false, &h->convt4a))) return r;
+      if ((r = upload_weight(h, wm, sname(li, 1) + ".weight", D / 2, &h->up_ln_g))) return r;
+      if ((r = upload_weight(h, wm, sname(li, 1) + ".bias", D / 2, &h->up_ln_b))) return r;
+      if ((r = pack_convt(h, wm, sname(li, 3), D / 2, D / 4, BIAS_REQUIRED, false, &h->convt4b))) return r;
       if ((r = pack_sfp_stage(h, wm, sname(li, 4), sname(li, 5), D / 4, &h->lv[li].st))) return r;
       h->lv[li].side = 4 * G; h->lv[li].stride = (float)P / 4.f; ++li;
     }
-    if ((r = pack_convt(h, wm, sname(li, 0), D, D / 2, &h->convt))) return r;
+    if ((r = pack_convt(h, wm, sname(li, 0), D, D / 2, BIAS_REQUIRED, false, &h->convt))) return r;
     if ((r = pack_sfp_stage(h, wm, sname(li, 1), sname(li, 2), D / 2, &h->lv[li].st))) return r;
     h->lv[li].side = 2 * G; h->lv[li].stride = (float)P / 2.f; ++li;
     if ((r = pack_sfp_stage(h, wm, sname(li, 0), sname(li, 1), D, &h->lv[li].st))) return r;
@@ -910,14 +700,14 @@ static int create_impl(const OvmConfig* cfg, const OvmTensor* weights, int32_t n
   h->has_rpn = wm.get("proposal_generator.rpn_head.conv.weight") != nullptr;
   if (h->has_rpn) {
     const std::string P = "proposal_generator.rpn_head.";
-    if ((r = pack_conv(h, wm, P + "conv", C, C, 3, &h->rpn_conv, true))) return r;
+    if ((r = pack_conv(h, wm, P + "conv", C, C, 3, BIAS_REQUIRED, &h->rpn_conv))) return r;
     // 1x1 convs: objectness [A][C] then deltas [4A][C]
     if ((r = pack_concat(h, wm, {{P + "objectness_logits", 3}, {P + "anchor_deltas", 12}}, C, &h->rpn_out))) return r;
   }
   }
   // ---- workspace
   const size_t MT = (size_t)B * T, MP = (size_t)B * G2;
-  if ((r = dalloc(h, &h->X, MT * D))) return r;
+  if ((r = h->alloc(&h->X, MT * D))) return r;
   if ((r = salloc(h, &h->PA, MP * h->Kpe))) return r;
   if ((r = salloc_il(h, &h->HN, MT * D))) return r;
   if ((r = salloc_il(h, &h->AO, MT * D))) return r;
@@ -926,17 +716,17 @@ static int create_impl(const OvmConfig* cfg, const OvmTensor* weights, int32_t n
   if ((r = salloc(h, &h->Kx, MT * D))) return r;
   if ((r = salloc(h, &h->Vt, (size_t)B * D * h->Tpad, true))) return r;
   h->splitk_cap = (size_t)112 << 20;     // split-K is only taken for <= 96 tiles of 128 x 128 with <= 16 slices: <= 100.7 MB of fp32 partials
-  { char* q = nullptr; if ((r = dalloc(h, &q, h->splitk_cap))) return r; h->splitk_ws = (float*)q; }
-  if ((r = dalloc(h, &h->attn_tail_ws, attn_tail_ws_floats(B, c.heads)))) return r;
-  if ((r = dalloc(h, &h->attn_tail_cnt, (size_t)B * c.heads * 8, true))) return r;
+  { char* q = nullptr; if ((r = h->alloc(&q, h->splitk_cap))) return r; h->splitk_ws = (float*)q; }
+  if ((r = h->alloc(&h->attn_tail_ws, attn_tail_ws_floats(B, c.heads)))) return r;
+  if ((r = h->alloc(&h->attn_tail_cnt, (size_t)B * c.heads * 8, true))) return r;
   if (!tower_only) {
     if ((r = salloc(h, &h->DT, MP * D))) return r;
     if ((r = salloc(h, &h->DT4, (size_t)B * (G / 2) * (G / 2) * D))) return r;
   }
   if (h->has_dfuse) {
     if ((r = salloc(h, &h->DF, MP * (D + 64)))) return r;
-    if ((r = dalloc(h, &h->dtok, MP))) return r;
-    if ((r = dalloc(h, &h->FUS, MP * D))) return r;
+    if ((r = h->alloc(&h->dtok, MP))) return r;
+    if ((r = h->alloc(&h->FUS, MP * D))) return r;
   }
   if (sam) {
     const int ws = c.sam_window, gp = (G + ws - 1) / ws * ws, nw1 = gp / ws;
@@ -950,21 +740,21 @@ static int create_impl(const OvmConfig* cfg, const OvmTensor* weights, int32_t n
               const int y = wy * ws + iy, x = wx * ws + ix;          // window_partition pads bottom / right (segment_anything)
               map[(size_t)b * h->sam_rows + ((size_t)(wy * nw1 + wx) * ws + iy) * ws + ix] = (y < G && x < G) ? b * T + y * G + x : -1;
             }
-    if ((r = dalloc(h, &h->sam_map, map.size()))) return r;
-    HCHECK(h, hipMemcpy(h->sam_map, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
+    if ((r = h->alloc(&h->sam_map, map.size()))) return r;
+    OVM_HIP(h, hipMemcpy(h->sam_map, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
     const size_t MW = (size_t)B * (h->sam_rows > T ? h->sam_rows : T);
     h->ldrel = ((ws > G ? ws : G) + 3) / 4 * 4;
     if ((r = salloc(h, &h->XW, MW * D))) return r;
     if ((r = salloc(h, &h->CTX, MW * D))) return r;
-    if ((r = dalloc(h, &h->QKVF, MW * 3 * D))) return r;
-    if ((r = dalloc(h, &h->RELH, MW * c.heads * h->ldrel))) return r;
-    if ((r = dalloc(h, &h->RELW, MW * c.heads * h->ldrel))) return r;
+    if ((r = h->alloc(&h->QKVF, MW * 3 * D))) return r;
+    if ((r = h->alloc(&h->RELH, MW * c.heads * h->ldrel))) return r;
+    if ((r = h->alloc(&h->RELW, MW * c.heads * h->ldrel))) return r;
   }
-  if ((r = dalloc(h, &h->d_imgs, (size_t)B))) return r;
-  if ((r = dalloc(h, &h->d_meta, (size_t)B))) return r;
-  HCHECK(h, hipHostMalloc((void**)&h->h_imgs, sizeof(ImageDesc) * B));
-  HCHECK(h, hipHostMalloc((void**)&h->h_meta, sizeof(ImageMeta) * B));
-  if (tower_only) { HCHECK(h, hipDeviceSynchronize()); return OVM_OK; }
+  if ((r = h->alloc(&h->d_imgs, (size_t)B))) return r;
+  if ((r = h->alloc(&h->d_meta, (size_t)B))) return r;
+  OVM_HIP(h, hipHostMalloc((void**)&h->h_imgs, sizeof(ImageDesc) * B));
+  OVM_HIP(h, hipHostMalloc((void**)&h->h_meta, sizeof(ImageMeta) * B));
+  if (tower_only) { OVM_HIP(h, hipDeviceSynchronize()); return OVM_OK; }
   const int G2x = 2 * G, G4 = G / 2;
   if ((r = salloc(h, &h->CT, (size_t)B * G2x * G2x * (D / 2)))) return r;
   if (p16) {
@@ -974,19 +764,19 @@ static int create_impl(const OvmConfig* cfg, const OvmTensor* weights, int32_t n
   for (int l = 0; l < h->nlev; ++l) {
     FpnLevel& f = h->lv[l];
     const size_t px = (size_t)B * f.side * f.side, pxp = (size_t)B * (f.side + 2) * (f.side + 2);
-    if ((r = dalloc(h, &f.T1, px * C))) return r;
+    if ((r = h->alloc(&f.T1, px * C))) return r;
     if ((r = salloc(h, &f.pad, pxp * C, true))) return r;
-    if ((r = dalloc(h, &f.p, px * C))) return r;
+    if ((r = h->alloc(&f.p, px * C))) return r;
     if (h->has_rpn && (r = salloc(h, &f.rpad, pxp * C, true))) return r;
   }
   const size_t RR = (size_t)R * B;
   if ((r = salloc(h, &h->RF, RR * h->roiK))) return r;
   if ((r = salloc(h, &h->H1, RR * F))) return r;
   if ((r = salloc(h, &h->H2, RR * F))) return r;
-  if ((r = dalloc(h, &h->HO, RR * 256))) return r;
-  if ((r = dalloc(h, &h->rec, RR * kRecFloats))) return r;
-  if ((r = dalloc(h, &h->keep, RR))) return r;
-  if ((r = dalloc(h, &h->d_bidx, RR))) return r;
+  if ((r = h->alloc(&h->HO, RR * 256))) return r;
+  if ((r = h->alloc(&h->rec, RR * kRecFloats))) return r;
+  if ((r = h->alloc(&h->keep, RR))) return r;
+  if ((r = h->alloc(&h->d_bidx, RR))) return r;
   if (h->has_rpn && h->has_box) {
     std::vector<void*> extra;
     int sides[kMaxLevels];
@@ -995,7 +785,7 @@ static int create_impl(const OvmConfig* cfg, const OvmTensor* weights, int32_t n
     for (void* p : extra) h->allocs.push_back(p);
     if (r) { h->err = "det2d workspace allocation failed"; return r; }
   }
-  HCHECK(h, hipDeviceSynchronize());
+  OVM_HIP(h, hipDeviceSynchronize());
   return OVM_OK;
 }
 
@@ -1005,32 +795,32 @@ int ovm_create(const OvmConfig* cfg, const OvmTensor* weights, int32_t n_weights
   return create_impl(cfg, weights, n_weights, device, nullptr, false, out);
 }
 
-static int sfp_branch(OvmHandle* h, const Split& in, int lda, int Bn, const FpnLevel& f, hipStream_t s) {
+static int sfp_branch(OvmHandle* h, const SplitImg& in, int lda, int Bn, const FpnLevel& f, hipStream_t s) {
   const int C = h->C, Hs = f.side, M = Bn * Hs * Hs;
   const SfpStage& st = f.st;
   GemmParams p = gp_base(in, lda, st.c1, M);
   p.C = f.T1; p.ldc = C;
-  KCHECK(h, gemm(h, p, EPI_STORE, A_ROWMAJOR, s));
+  OVM_TRY(h, gemm(h, p, EPI_STORE, A_ROWMAJOR, s));
   LnOut o; memset(&o, 0, sizeof(o));
   o.hi = f.pad.hi; o.lo = f.pad.lo; o.ld = C; o.padH = Hs; o.padW = Hs;
-  KCHECK(h, launch_ln_rows(f.T1, C, M, C, st.n1g, st.n1b, 1e-6f, o, s));
+  OVM_TRY(h, launch_ln_rows(f.T1, C, M, C, st.n1g, st.n1b, 1e-6f, o, s));
   GemmParams q; memset(&q, 0, sizeof(q));
-  q.Ahi = f.pad.hi; q.Alo = f.pad.lo; q.Whi = st.c3.w.hi; q.Wlo = st.c3.w.lo;
+  q.Ahi = f.pad.hi; q.Alo = f.pad.lo; q.Whi = st.c3.hi; q.Wlo = st.c3.lo;
   q.M = M; q.N = C; q.K = 9 * C; q.cH = Hs; q.cW = Hs; q.cC = C;
   q.C = f.T1; q.ldc = C;                                 // 1x1 output already consumed by the LN above
-  KCHECK(h, gemm(h, q, EPI_STORE, A_CONV3X3, s));
+  OVM_TRY(h, gemm(h, q, EPI_STORE, A_CONV3X3, s));
   LnOut o2; memset(&o2, 0, sizeof(o2));
   o2.f32 = f.p; o2.ldf = C;
   if (f.rpad.hi) { o2.hi = f.rpad.hi; o2.lo = f.rpad.lo; o2.ld = C; o2.padH = Hs; o2.padW = Hs; }
-  KCHECK(h, launch_ln_rows(f.T1, C, M, C, st.n3g, st.n3b, 1e-6f, o2, s));
+  OVM_TRY(h, launch_ln_rows(f.T1, C, M, C, st.n3g, st.n3b, 1e-6f, o2, s));
   return OVM_OK;
 }
 
 // ConvTranspose2d k2 s2 as a GEMM over the source pixels (EPI_CONVT scatters the 2x2 outputs): [Bn][Gs][Gs][Cin] -> [Bn][2Gs][2Gs][Cout]
-static int convt_up(OvmHandle* h, const Split& in, int Cin, int Bn, int Gs, const PackedLinear& w, const Split& out, hipStream_t s) {
+static int convt_up(OvmHandle* h, const SplitImg& in, int Cin, int Bn, int Gs, const PackedLin& w, const SplitImg& out, hipStream_t s) {
   GemmParams p = gp_base(in, Cin, w, Bn * Gs * Gs);
   p.Ohi = out.hi; p.Olo = out.lo; p.G = Gs; p.Cout = w.N / 4;
-  KCHECK(h, gemm(h, p, EPI_CONVT, A_ROWMAJOR, s));
+  OVM_TRY(h, gemm(h, p, EPI_CONVT, A_ROWMAJOR, s));
   return OVM_OK;
 }
 
@@ -1045,10 +835,10 @@ int ovm_backbone_forward(OvmHandle* h, const OvmImage* images, int32_t B, const 
     if (images[b].height > c.canvas || images[b].width > c.canvas || images[b].height < 1 || images[b].width < 1) {
       h->err = "image larger than SQUARE_PAD canvas"; return OVM_ERR_SHAPE;
     }
-  HCHECK(h, hipSetDevice(h->device));
+  OVM_HIP(h, hipSetDevice(h->device));
   fill_meta(h, images, B);
-  HCHECK(h, hipMemcpyAsync(h->d_imgs, h->h_imgs, sizeof(ImageDesc) * B, hipMemcpyHostToDevice, s));
-  HCHECK(h, hipMemcpyAsync(h->d_meta, h->h_meta, sizeof(ImageMeta) * B, hipMemcpyHostToDevice, s));
+  OVM_HIP(h, hipMemcpyAsync(h->d_imgs, h->h_imgs, sizeof(ImageDesc) * B, hipMemcpyHostToDevice, s));
+  OVM_HIP(h, hipMemcpyAsync(h->d_meta, h->h_meta, sizeof(ImageMeta) * B, hipMemcpyHostToDevice, s));
   h->lastB = B;
   if (prompt_depth && c.tower != OVM_TOWER_DINOV2) {
     // detectron2's SimpleFeaturePyramid.forward(x) takes no depth; the fork's RCNN3D passes one to every backbone and
@@ -1066,7 +856,7 @@ int ovm_backbone_forward(OvmHandle* h, const OvmImage* images, int32_t B, const 
   const int C = h->C;
   float* outs[3] = {p2, p3, p4};
   for (int l = 0; l < 3; ++l)
-    if (outs[l]) HCHECK(h, hipMemcpyAsync(outs[l], h->lv[l].p, (size_t)B * h->lv[l].side * h->lv[l].side * C * 4, hipMemcpyDeviceToDevice, s));
+    if (outs[l]) OVM_HIP(h, hipMemcpyAsync(outs[l], h->lv[l].p, (size_t)B * h->lv[l].side * h->lv[l].side * C * 4, hipMemcpyDeviceToDevice, s));
   return OVM_OK;
 }
 
@@ -1077,23 +867,23 @@ static int tower_launches(OvmHandle* h, int B, hipStream_t s, const TowerRun* ru
   const OvmConfig& c = h->cfg;
   const int D = h->D, G = h->G, G2 = h->G2, T = h->T, L = c.depth;
   // ---- patch embed (+ preprocess) ----
-  if (run) KCHECK(h, launch_patch_gather_f32(*run->views, B, G, h->Kpe, h->PA.hi, h->PA.lo, s));
-  else KCHECK(h, launch_patch_gather(h->d_imgs, B, G, h->patch, h->Kpe, c.pixel_mean, c.pixel_std, h->PA.hi, h->PA.lo, s));
-  if (!h->sam) KCHECK(h, launch_cls_init(h->X, h->cls, h->pos, h->reg, h->nreg, B, T, D, s));       // SAM: no class token (T = G^2)
+  if (run) OVM_TRY(h, launch_patch_gather_f32(*run->views, B, G, h->Kpe, h->PA.hi, h->PA.lo, s));
+  else OVM_TRY(h, launch_patch_gather(h->d_imgs, B, G, h->patch, h->Kpe, c.pixel_mean, c.pixel_std, h->PA.hi, h->PA.lo, s));
+  if (!h->sam) OVM_TRY(h, launch_cls_init(h->X, h->cls, h->pos, h->reg, h->nreg, B, T, D, s));       // SAM: no class token (T = G^2)
   {
     GemmParams p = gp_base(h->PA, h->Kpe, h->pe, B * G2);
     p.X = h->X; p.ldx = D; p.pos = h->pos; p.G2 = G2; p.T = T;
-    KCHECK(h, gemm(h, p, EPI_PATCH, A_ROWMAJOR, s));
+    OVM_TRY(h, gemm(h, p, EPI_PATCH, A_ROWMAJOR, s));
   }
   const int M = B * T;
   const float eps = h->ln_eps;
   if (h->lnpre_g) {                                        // open_clip: x = ln_pre(x + pos) (reference clip.py:78-79), in place
     LnOut o; memset(&o, 0, sizeof(o)); o.f32 = h->X; o.ldf = D;
-    ProfScope ps(h, OVM_PROF_LN, s); KCHECK(h, launch_ln_rows(h->X, D, M, D, h->lnpre_g, h->lnpre_b, eps, o, s));
+    ProfScope ps(h, OVM_PROF_LN, s); OVM_TRY(h, launch_ln_rows(h->X, D, M, D, h->lnpre_g, h->lnpre_b, eps, o, s));
   }
   for (int l = 0; l < L; ++l) {
     const Layer& y = h->layers[l];
-    const int il = h->npass == 3 ? 1 : 0, am = il ? 2 : 1;    // activations of the blocks: interleaved split images in f16x3 mode
+    const int il = h->precision == 3 ? 1 : 0, am = il ? 2 : 1;    // activations of the blocks: interleaved split images in f16x3 mode
     LnOut o; memset(&o, 0, sizeof(o)); o.hi = h->HN.hi; o.lo = h->HN.lo; o.ld = am * D; o.il = il;
     if (h->sam) {
       // segment_anything Block (reference sam.py:100-106 runs vit.blocks as they are): norm1 -> [zero-padded 14 x 14 windows] ->
@@ -1106,37 +896,37 @@ static int tower_launches(OvmHandle* h, int B, hipStream_t s, const TowerRun* ru
         rp.x = h->X; rp.ldx = D; rp.gamma = y.ln1g; rp.beta = y.ln1b; rp.eps = eps; rp.M = Mw; rp.D = D;
         if (ws) { rp.idx = h->sam_map; rp.nidx = 1; rp.seg = D; rp.zero_masked = 1; }
         rp.hi = h->XW.hi; rp.lo = h->XW.lo; rp.ldh = D;
-        ProfScope ps(h, OVM_PROF_LN, s); KCHECK(h, launch_rowop(rp, s));
+        ProfScope ps(h, OVM_PROF_LN, s); OVM_TRY(h, launch_rowop(rp, s));
       }
       {
         GemmParams p = gp_base(h->XW, D, y.qkv, Mw);
         p.C = h->QKVF; p.ldc = 3 * D;
-        KCHECK(h, gemm(h, p, EPI_STORE, A_ROWMAJOR, s, OVM_PROF_QKV));
+        OVM_TRY(h, gemm(h, p, EPI_STORE, A_ROWMAJOR, s, OVM_PROF_QKV));
       }
       {
         ProfScope ps(h, OVM_PROF_ATTN, s);
         // the bias tables use the UNSCALED query (add_decomposed_rel_pos is given q, the scores use q * scale)
-        KCHECK(h, launch_relpos_tables(h->QKVF, 3 * D, Mw, c.heads, 64, side, side, y.relh, y.relw, h->RELH, h->RELW, h->ldrel, s));
+        OVM_TRY(h, launch_relpos_tables(h->QKVF, 3 * D, Mw, c.heads, 64, side, side, y.relh, y.relw, h->RELH, h->RELW, h->ldrel, s));
         AttnF32Params a; memset(&a, 0, sizeof(a));
         a.q = h->QKVF; a.k = h->QKVF + D; a.v = h->QKVF + 2 * D; a.ldq = a.ldk = a.ldv = 3 * D;
         a.sq1 = a.sk1 = a.sv1 = (long)Tq * 3 * D; a.sq2 = a.sk2 = a.sv2 = 64;
         a.ohi = h->CTX.hi; a.olo = h->CTX.lo; a.ldoh = D; a.soh1 = (long)Tq * D; a.soh2 = 64;
         a.nb1 = nseq; a.nb2 = c.heads; a.Tq = Tq; a.Tk = Tq; a.DH = 64; a.scale = 0.125f;
         a.rel_h = h->RELH; a.rel_w = h->RELW; a.rel_gw = side; a.ldrel = h->ldrel;
-        KCHECK(h, launch_attn_f32(a, s));
+        OVM_TRY(h, launch_attn_f32(a, s));
       }
       {
         GemmParams p = gp_base(h->CTX, D, y.proj, Mw);
         p.X = h->X; p.ldx = D; p.row_map = ws ? h->sam_map : nullptr;
-        KCHECK(h, gemm(h, p, EPI_RESID, A_ROWMAJOR, s, OVM_PROF_PROJ));
+        OVM_TRY(h, gemm(h, p, EPI_RESID, A_ROWMAJOR, s, OVM_PROF_PROJ));
       }
     } else {
-    { ProfScope ps(h, OVM_PROF_LN, s); KCHECK(h, launch_ln_rows(h->X, D, M, D, y.ln1g, y.ln1b, eps, o, s)); }
+    { ProfScope ps(h, OVM_PROF_LN, s); OVM_TRY(h, launch_ln_rows(h->X, D, M, D, y.ln1g, y.ln1b, eps, o, s)); }
     {
       GemmParams p = gp_base(h->HN, am * D, y.qkv, M); p.a_il = il;
       p.Qhi = h->Q.hi; p.Qlo = h->Q.lo; p.Khi = h->Kx.hi; p.Klo = h->Kx.lo; p.Vhi = h->Vt.hi; p.Vlo = h->Vt.lo;
       p.T = T; p.Tpad = h->Tpad; p.heads = c.heads; p.qscale = kQScale;
-      KCHECK(h, gemm(h, p, EPI_QKV, A_ROWMAJOR, s, OVM_PROF_QKV));
+      OVM_TRY(h, gemm(h, p, EPI_QKV, A_ROWMAJOR, s, OVM_PROF_QKV));
     }
     {
       AttnParams a; memset(&a, 0, sizeof(a));
@@ -1144,32 +934,32 @@ static int tower_launches(OvmHandle* h, int B, hipStream_t s, const TowerRun* ru
       a.Ohi = h->AO.hi; a.Olo = h->AO.lo; a.ldo = am * D; a.o_il = il; a.B = B; a.heads = c.heads; a.T = T; a.Tpad = h->Tpad;
       a.corun = h->corun ? 1 : 0;
       a.tail_ws = h->attn_tail_ws; a.tail_cnt = h->attn_tail_cnt;     // leftover queries (T = 4097: one per head) split over the keys
-      { ProfScope ps(h, OVM_PROF_ATTN, s); KCHECK(h, launch_attention(a, h->npass, s)); }
+      { ProfScope ps(h, OVM_PROF_ATTN, s); OVM_TRY(h, launch_attention(a, h->precision, s)); }
     }
     {
       GemmParams p = gp_base(h->AO, am * D, y.proj, M); p.a_il = il;
       p.gamma = y.ls1; p.X = h->X; p.ldx = D;
-      KCHECK(h, gemm(h, p, EPI_RESID, A_ROWMAJOR, s, OVM_PROF_PROJ));
+      OVM_TRY(h, gemm(h, p, EPI_RESID, A_ROWMAJOR, s, OVM_PROF_PROJ));
     }
     }
-    { ProfScope ps(h, OVM_PROF_LN, s); KCHECK(h, launch_ln_rows(h->X, D, M, D, y.ln2g, y.ln2b, eps, o, s)); }
+    { ProfScope ps(h, OVM_PROF_LN, s); OVM_TRY(h, launch_ln_rows(h->X, D, M, D, y.ln2g, y.ln2b, eps, o, s)); }
     const int Kf = h->ffn_hs ? h->ffn_k : 4 * D;              // width of the FFN's activation image = K of its second linear
     if (h->ffn_hs) {                                          // w12 with silu(gate) * value in the epilogue
       GemmParams p = gp_base(h->HN, am * D, y.fc1, M); p.a_il = il;
       p.Ohi = h->F1.hi; p.Olo = h->F1.lo; p.ldo = am * Kf; p.o_il = il;
-      KCHECK(h, gemm(h, p, EPI_SWIGLU, A_ROWMAJOR, s, OVM_PROF_FC1));
+      OVM_TRY(h, gemm(h, p, EPI_SWIGLU, A_ROWMAJOR, s, OVM_PROF_FC1));
     } else {
       GemmParams p = gp_base(h->HN, am * D, y.fc1, M); p.a_il = il;
       p.Ohi = h->F1.hi; p.Olo = h->F1.lo; p.ldo = am * 4 * D; p.o_il = il; p.relu = h->mlp_act;
-      KCHECK(h, gemm(h, p, EPI_GELU, A_ROWMAJOR, s, OVM_PROF_FC1));
+      OVM_TRY(h, gemm(h, p, EPI_GELU, A_ROWMAJOR, s, OVM_PROF_FC1));
     }
     {
       GemmParams p = gp_base(h->F1, am * Kf, y.fc2, M); p.a_il = il;
       p.gamma = y.ls2; p.X = h->X; p.ldx = D;
-      KCHECK(h, gemm(h, p, EPI_RESID, A_ROWMAJOR, s, OVM_PROF_FC2));
+      OVM_TRY(h, gemm(h, p, EPI_RESID, A_ROWMAJOR, s, OVM_PROF_FC2));
     }
     for (int t = 0; run && t < run->ntap; ++t)                // the residual stream after block l (HF hidden_states[l + 1])
-      if (run->tap_blk[t] == l) HCHECK(h, hipMemcpyAsync(run->tap_dst[t], h->X, (size_t)M * D * 4, hipMemcpyDeviceToDevice, s));
+      if (run->tap_blk[t] == l) OVM_HIP(h, hipMemcpyAsync(run->tap_dst[t], h->X, (size_t)M * D * 4, hipMemcpyDeviceToDevice, s));
   }
   return OVM_OK;
 }
@@ -1177,32 +967,32 @@ static int tower_launches(OvmHandle* h, int B, hipStream_t s, const TowerRun* ru
 // every kernel launch of the backbone (patch embed .. pyramid), on stream s, shapes fixed by (B, canvas)
 static int backbone_launches(OvmHandle* h, int B, const float* prompt_depth, int depth_h, int depth_w, hipStream_t s) {
   const int D = h->D, G = h->G, G2 = h->G2, T = h->T;
-  KCHECK(h, tower_launches(h, B, s));
+  OVM_TRY(h, tower_launches(h, B, s));
   // ---- depth fusion at the last block output (reference dino.py:91-105) ----
   if (prompt_depth) {
-    KCHECK(h, launch_depth_resize(prompt_depth, B, depth_h, depth_w, G, h->dtok, s));
-    KCHECK(h, launch_tokens_cast(h->X, B, T, G2, D, D + 64, h->dtok, h->DF.hi, h->DF.lo, s));
+    OVM_TRY(h, launch_depth_resize(prompt_depth, B, depth_h, depth_w, G, h->dtok, s));
+    OVM_TRY(h, launch_tokens_cast(h->X, B, T, G2, D, D + 64, h->dtok, h->DF.hi, h->DF.lo, s));
     GemmParams p = gp_base(h->DF, D + 64, h->dfuse, B * G2);
     p.C = h->FUS; p.ldc = D;
-    KCHECK(h, gemm(h, p, EPI_STORE, A_ROWMAJOR, s));
-    KCHECK(h, launch_tokens_writeback(h->X, h->FUS, B, T, G2, D, s));
+    OVM_TRY(h, gemm(h, p, EPI_STORE, A_ROWMAJOR, s));
+    OVM_TRY(h, launch_tokens_writeback(h->X, h->FUS, B, T, G2, D, s));
   }
   // ---- dense tokens (no final LayerNorm: reference dino.py:88-110) ----
-  KCHECK(h, launch_tokens_cast(h->X, B, T, G2, D, D, nullptr, h->DT.hi, h->DT.lo, s));
+  OVM_TRY(h, launch_tokens_cast(h->X, B, T, G2, D, D, nullptr, h->DT.hi, h->DT.lo, s));
   // ---- SFP (reference dino.py:143-152,208-224; stages nohup.out:565-596; 4-level form clip.py:155-166) ----
   {
     int li = 0;
     if (h->nlev == 4) {                                    // scale 4: ConvT . LN . GELU . ConvT
-      KCHECK(h, convt_up(h, h->DT, D, B, G, h->convt4a, h->CT4a, s));
-      KCHECK(h, launch_ln_gelu_split(h->CT4a.hi, h->CT4a.lo, B * 4 * G2, D / 2, h->up_ln_g, h->up_ln_b, 1e-6f, s));
-      KCHECK(h, convt_up(h, h->CT4a, D / 2, B, 2 * G, h->convt4b, h->CT4b, s));
-      KCHECK(h, sfp_branch(h, h->CT4b, D / 4, B, h->lv[li++], s));
+      OVM_TRY(h, convt_up(h, h->DT, D, B, G, h->convt4a, h->CT4a, s));
+      OVM_TRY(h, launch_ln_gelu_split(h->CT4a.hi, h->CT4a.lo, B * 4 * G2, D / 2, h->up_ln_g, h->up_ln_b, 1e-6f, s));
+      OVM_TRY(h, convt_up(h, h->CT4a, D / 2, B, 2 * G, h->convt4b, h->CT4b, s));
+      OVM_TRY(h, sfp_branch(h, h->CT4b, D / 4, B, h->lv[li++], s));
     }
-    KCHECK(h, convt_up(h, h->DT, D, B, G, h->convt, h->CT, s));
-    KCHECK(h, sfp_branch(h, h->CT, D / 2, B, h->lv[li++], s));
-    KCHECK(h, sfp_branch(h, h->DT, D, B, h->lv[li++], s));
-    KCHECK(h, launch_maxpool2(h->DT.hi, h->DT.lo, B, G, D, h->DT4.hi, h->DT4.lo, s));
-    KCHECK(h, sfp_branch(h, h->DT4, D, B, h->lv[li++], s));
+    OVM_TRY(h, convt_up(h, h->DT, D, B, G, h->convt, h->CT, s));
+    OVM_TRY(h, sfp_branch(h, h->CT, D / 2, B, h->lv[li++], s));
+    OVM_TRY(h, sfp_branch(h, h->DT, D, B, h->lv[li++], s));
+    OVM_TRY(h, launch_maxpool2(h->DT.hi, h->DT.lo, B, G, D, h->DT4.hi, h->DT4.lo, s));
+    OVM_TRY(h, sfp_branch(h, h->DT4, D, B, h->lv[li++], s));
   }
   return OVM_OK;
 }
@@ -1234,39 +1024,39 @@ int ovm_cube_forward(OvmHandle* h, const OvmImage* images, int32_t B, const floa
   hipStream_t s = (hipStream_t)stream;
   if (B < 1 || B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return OVM_ERR_CAPACITY; }
   if (n > h->cfg.max_rois * h->cfg.max_batch) { h->err = "n exceeds max_rois*max_batch"; return OVM_ERR_CAPACITY; }
-  HCHECK(h, hipSetDevice(h->device));
+  OVM_HIP(h, hipSetDevice(h->device));
   if (n <= 0) {                                       // roi_heads.py:371-372: nothing to do
-    HCHECK(h, hipMemsetAsync(out_counts, 0, sizeof(int) * B, s));
+    OVM_HIP(h, hipMemsetAsync(out_counts, 0, sizeof(int) * B, s));
     return OVM_OK;
   }
   fill_meta(h, images, B);
-  HCHECK(h, hipMemcpyAsync(h->d_meta, h->h_meta, sizeof(ImageMeta) * B, hipMemcpyHostToDevice, s));
+  OVM_HIP(h, hipMemcpyAsync(h->d_meta, h->h_meta, sizeof(ImageMeta) * B, hipMemcpyHostToDevice, s));
   h->lastN = n;
   const int F = h->cfg.fc_dim;
   RoiParams rp; roi_params(h, &rp);
   rp.boxes = boxes; rp.batch_idx = image_idx; rp.n = n; rp.Ohi = h->RF.hi; rp.Olo = h->RF.lo; rp.ldo = h->roiK;
-  KCHECK(h, launch_roi_align(rp, s));
+  OVM_TRY(h, launch_roi_align(rp, s));
   {
     GemmParams p = gp_base(h->RF, h->roiK, h->cube_fc1, n);
     p.Ohi = h->H1.hi; p.Olo = h->H1.lo; p.ldo = F; p.relu = 1;
-    KCHECK(h, gemm(h, p, EPI_STORE, A_ROWMAJOR, s));
+    OVM_TRY(h, gemm(h, p, EPI_STORE, A_ROWMAJOR, s));
   }
   {
     GemmParams p = gp_base(h->H1, F, h->cube_fc2, n);
     p.Ohi = h->H2.hi; p.Olo = h->H2.lo; p.ldo = F; p.relu = 1;
-    KCHECK(h, gemm(h, p, EPI_STORE, A_ROWMAJOR, s));
+    OVM_TRY(h, gemm(h, p, EPI_STORE, A_ROWMAJOR, s));
   }
   {
     GemmParams p = gp_base(h->H2, F, h->cube_out, n);
     p.C = h->HO; p.ldc = 16;
-    KCHECK(h, gemm(h, p, EPI_STORE, A_ROWMAJOR, s));
+    OVM_TRY(h, gemm(h, p, EPI_STORE, A_ROWMAJOR, s));
   }
   CubeDecodeParams cp; memset(&cp, 0, sizeof(cp));
   cp.head = h->HO; cp.ldh = 16; cp.boxes = boxes; cp.scores = scores; cp.classes = classes; cp.batch_idx = image_idx;
   cp.meta = h->d_meta; cp.n = n; cp.virtual_focal = h->cfg.virtual_focal; cp.rec = h->rec; cp.keep = h->keep;
   cp.postprocess = postprocess;
-  KCHECK(h, launch_cube_decode(cp, s));
-  KCHECK(h, launch_compact_records(h->rec, h->keep, n, B, (float*)out, out_counts, s));
+  OVM_TRY(h, launch_cube_decode(cp, s));
+  OVM_TRY(h, launch_compact_records(h->rec, h->keep, n, B, (float*)out, out_counts, s));
   return OVM_OK;
 }
 
@@ -1277,19 +1067,19 @@ int ovm_rpn_box_forward(OvmHandle* h, const OvmImage* images, int32_t B, float* 
   if (!h->has_rpn || !h->has_box) { h->err = "checkpoint has no RPN / box-head weights"; return OVM_ERR_MISSING_WEIGHT; }
   if (B < 1 || B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return OVM_ERR_CAPACITY; }
   hipStream_t s = (hipStream_t)stream;
-  HCHECK(h, hipSetDevice(h->device));
+  OVM_HIP(h, hipSetDevice(h->device));
   fill_meta(h, images, B);
-  HCHECK(h, hipMemcpyAsync(h->d_meta, h->h_meta, sizeof(ImageMeta) * B, hipMemcpyHostToDevice, s));
+  OVM_HIP(h, hipMemcpyAsync(h->d_meta, h->h_meta, sizeof(ImageMeta) * B, hipMemcpyHostToDevice, s));
   Det2dModel m; memset(&m, 0, sizeof(m));
-  m.npass = h->npass; m.B = B; m.C = h->C; m.F = h->cfg.fc_dim; m.roiK = h->roiK;
+  m.npass = h->precision; m.B = B; m.C = h->C; m.F = h->cfg.fc_dim; m.roiK = h->roiK;
   m.num_classes = h->cfg.num_classes;
   m.nlev = h->nlev;
   for (int l = 0; l < h->nlev; ++l) { m.rpad[l] = {h->lv[l].rpad.hi, h->lv[l].rpad.lo}; m.stride[l] = h->lv[l].stride; }
-  m.rpn_conv_hi = h->rpn_conv.w.hi; m.rpn_conv_lo = h->rpn_conv.w.lo; m.rpn_conv_bias = h->rpn_conv.bias;
-  m.rpn_out_hi = h->rpn_out.w.hi; m.rpn_out_lo = h->rpn_out.w.lo; m.rpn_out_bias = h->rpn_out.bias;
-  m.fc1_hi = h->box_fc1.w.hi; m.fc1_lo = h->box_fc1.w.lo; m.fc1_bias = h->box_fc1.bias;
-  m.fc2_hi = h->box_fc2.w.hi; m.fc2_lo = h->box_fc2.w.lo; m.fc2_bias = h->box_fc2.bias;
-  m.out_hi = h->box_out.w.hi; m.out_lo = h->box_out.w.lo; m.out_bias = h->box_out.bias;
+  m.rpn_conv_hi = h->rpn_conv.hi; m.rpn_conv_lo = h->rpn_conv.lo; m.rpn_conv_bias = h->rpn_conv.bias;
+  m.rpn_out_hi = h->rpn_out.hi; m.rpn_out_lo = h->rpn_out.lo; m.rpn_out_bias = h->rpn_out.bias;
+  m.fc1_hi = h->box_fc1.hi; m.fc1_lo = h->box_fc1.lo; m.fc1_bias = h->box_fc1.bias;
+  m.fc2_hi = h->box_fc2.hi; m.fc2_lo = h->box_fc2.lo; m.fc2_bias = h->box_fc2.bias;
+  m.out_hi = h->box_out.hi; m.out_lo = h->box_out.lo; m.out_bias = h->box_out.bias;
   for (int i = 0; i < kMaxLevels; ++i) m.anchor_sizes[i] = h->cfg.anchor_sizes[i];
   for (int i = 0; i < 3; ++i) m.anchor_ratios[i] = h->cfg.anchor_ratios[i];
   m.pre_topk = h->cfg.rpn_pre_topk; m.post_topk = h->cfg.rpn_post_topk; m.rpn_nms = h->cfg.rpn_nms_thresh;
@@ -1314,17 +1104,17 @@ static int infer_forked(OvmHandle* h, OvmGdino* g, const OvmImage* image, const 
                         ovm_stream_t stream, int nq) {
   hipStream_t s = (hipStream_t)stream;
   // fork: detector on the side stream
-  HCHECK(h, hipEventRecord(h->ev_fork, s));
-  HCHECK(h, hipStreamWaitEvent(h->side, h->ev_fork, 0));
+  OVM_HIP(h, hipEventRecord(h->ev_fork, s));
+  OVM_HIP(h, hipStreamWaitEvent(h->side, h->ev_fork, 0));
   int r = ovm_gdino_forward(g, image, token_ids, ntok, nullptr, nullptr, nullptr, (ovm_stream_t)h->side);
   if (r) { h->err = std::string("ovm_gdino_forward: ") + ovm_gdino_last_error(g); return r; }
-  HCHECK(h, hipEventRecord(h->ev_join, h->side));
+  OVM_HIP(h, hipEventRecord(h->ev_join, h->side));
   // backbone on the caller's stream
   r = ovm_backbone_forward(h, image, 1, nullptr, 0, 0, nullptr, nullptr, nullptr, stream);
   if (r) return r;
   // join, output glue (three launches on the handle's scratch), kept count to the host (the one synchronisation in front of the
   // cube head, whose grid it sizes), cube head
-  HCHECK(h, hipStreamWaitEvent(s, h->ev_join, 0));
+  OVM_HIP(h, hipStreamWaitEvent(s, h->ev_join, 0));
   const float *logits = nullptr, *gboxes = nullptr; int ld = 0;
   r = ovm_gdino_last_outputs(g, &logits, &gboxes, &ld);
   if (r) { h->err = "detector outputs unavailable"; return r; }
@@ -1332,7 +1122,7 @@ static int infer_forked(OvmHandle* h, OvmGdino* g, const OvmImage* image, const 
     const size_t need = gdino_post_ws_bytes(nq, n_phrases);
     if (h->inf_ws_bytes < need) {
       char* q = nullptr;
-      if ((r = dalloc(h, &q, need + need / 4))) return r;        // (the previous block stays in h->allocs until ovm_destroy)
+      if ((r = h->alloc(&q, need + need / 4))) return r;        // (the previous block stays in h->allocs until ovm_destroy)
       h->inf_ws = q; h->inf_ws_bytes = need + need / 4;
     }
     r = launch_gdino_post_ws(logits, nq, ld, gboxes, spans, n_phrases, image->height, image->width, box_threshold, nms_threshold, h->inf_ws,
@@ -1342,15 +1132,15 @@ static int infer_forked(OvmHandle* h, OvmGdino* g, const OvmImage* image, const 
                               h->inf_boxes, h->inf_scores, h->inf_classes, h->inf_n, stream);
   }
   if (r) { h->err = "GroundingDINO output glue failed (" + std::to_string(r) + ")"; return r; }
-  if (!h->inf_host) HCHECK(h, hipHostMalloc((void**)&h->inf_host, 2 * sizeof(int), hipHostMallocDefault));
-  HCHECK(h, hipMemcpyAsync(&h->inf_host[0], h->inf_n, sizeof(int), hipMemcpyDeviceToHost, s));
-  HCHECK(h, hipStreamSynchronize(s));
+  if (!h->inf_host) OVM_HIP(h, hipHostMalloc((void**)&h->inf_host, 2 * sizeof(int), hipHostMallocDefault));
+  OVM_HIP(h, hipMemcpyAsync(&h->inf_host[0], h->inf_n, sizeof(int), hipMemcpyDeviceToHost, s));
+  OVM_HIP(h, hipStreamSynchronize(s));
   const int n2d = h->inf_host[0];
   if (n2d > out_capacity) { h->err = "output capacity too small"; return OVM_ERR_CAPACITY; }
   r = ovm_cube_forward(h, image, 1, h->inf_boxes, h->inf_scores, h->inf_classes, h->inf_idx, n2d, 1, out, h->inf_counts, stream);
   if (r) return r;
-  HCHECK(h, hipMemcpyAsync(&h->inf_host[1], h->inf_counts, sizeof(int), hipMemcpyDeviceToHost, s));
-  HCHECK(h, hipStreamSynchronize(s));
+  OVM_HIP(h, hipMemcpyAsync(&h->inf_host[1], h->inf_counts, sizeof(int), hipMemcpyDeviceToHost, s));
+  OVM_HIP(h, hipStreamSynchronize(s));
   *n_out = h->inf_host[1];
   return OVM_OK;
 }
@@ -1361,21 +1151,21 @@ int ovm_infer(OvmHandle* h, OvmGdino* g, const OvmImage* image, const int32_t* t
   if (!h || !g || !image || !token_ids || !out || !n_out) return OVM_ERR_INVALID;
   h->err.clear();
   hipStream_t s = (hipStream_t)stream;
-  HCHECK(h, hipSetDevice(h->device));
+  OVM_HIP(h, hipSetDevice(h->device));
   if (!h->side) {
     int lo = 0, hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-    HCHECK(h, hipStreamCreateWithPriority(&h->side, hipStreamNonBlocking, hi));      // short kernels: let them jump the ViT's queue
-    HCHECK(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-    HCHECK(h, hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
+    OVM_HIP(h, hipStreamCreateWithPriority(&h->side, hipStreamNonBlocking, hi));      // short kernels: let them jump the ViT's queue
+    OVM_HIP(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
+    OVM_HIP(h, hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
   }
   const int nq = ovm_gdino_num_queries(g);
   if (nq <= 0) { h->err = "bad detector handle"; return OVM_ERR_INVALID; }
   if (nq > h->cfg.max_rois * h->cfg.max_batch) { h->err = "detector queries exceed max_rois"; return OVM_ERR_CAPACITY; }
   if (h->inf_cap < nq) {
     int r;
-    if ((r = dalloc(h, &h->inf_boxes, (size_t)nq * 4)) || (r = dalloc(h, &h->inf_scores, (size_t)nq)) || (r = dalloc(h, &h->inf_classes, (size_t)nq)) ||
-        (r = dalloc(h, &h->inf_idx, (size_t)nq, true)) || (r = dalloc(h, &h->inf_n, 1)) || (r = dalloc(h, &h->inf_counts, 1))) return r;
+    if ((r = h->alloc(&h->inf_boxes, (size_t)nq * 4)) || (r = h->alloc(&h->inf_scores, (size_t)nq)) || (r = h->alloc(&h->inf_classes, (size_t)nq)) ||
+        (r = h->alloc(&h->inf_idx, (size_t)nq, true)) || (r = h->alloc(&h->inf_n, 1)) || (r = h->alloc(&h->inf_counts, 1))) return r;
     h->inf_cap = nq;
   }
   const int r_all = infer_forked(h, g, image, token_ids, ntok, spans, n_phrases, box_threshold, nms_threshold, out, out_capacity, n_out, stream, nq);
@@ -1409,8 +1199,8 @@ int ovm_profile_enable(OvmHandle* h, int32_t on) {
 // resets the counters. Synchronises the device.
 int ovm_profile_read(OvmHandle* h, float* ms, int32_t* launches) {
   if (!h) return OVM_ERR_INVALID;
-  HCHECK(h, hipSetDevice(h->device));
-  HCHECK(h, hipDeviceSynchronize());
+  OVM_HIP(h, hipSetDevice(h->device));
+  OVM_HIP(h, hipDeviceSynchronize());
   for (int c = 0; c < OVM_PROF_NCAT; ++c) {
     double tot = 0.0;
     for (size_t i = 0; i < h->prof_used[c]; ++i) {
@@ -1536,10 +1326,10 @@ int tower_forward(OvmHandle* h, const OvmImage* image, hipStream_t s) {
   if (image->height > c.canvas || image->width > c.canvas || image->height < 1 || image->width < 1) {
     h->err = "image larger than the encoder's canvas"; return OVM_ERR_SHAPE;
   }
-  HCHECK(h, hipSetDevice(h->device));
-  HCHECK(h, hipStreamSynchronize(s));                    // the pinned descriptor below may still be read by the previous call's upload
+  OVM_HIP(h, hipSetDevice(h->device));
+  OVM_HIP(h, hipStreamSynchronize(s));                    // the pinned descriptor below may still be read by the previous call's upload
   fill_meta(h, image, 1);
-  HCHECK(h, hipMemcpyAsync(h->d_imgs, h->h_imgs, sizeof(ImageDesc), hipMemcpyHostToDevice, s));
+  OVM_HIP(h, hipMemcpyAsync(h->d_imgs, h->h_imgs, sizeof(ImageDesc), hipMemcpyHostToDevice, s));
   h->lastB = 1;
   return tower_launches(h, 1, s);
 }
@@ -1559,14 +1349,14 @@ int tower_forward_f32(OvmHandle* h, const TowerViews& views, int n_taps, const i
   for (int t = 0; t < n_taps; ++t)
     if (tap_blocks[t] < 0 || tap_blocks[t] >= h->cfg.depth || !tap_out[t]) { h->err = "tap block out of range"; return OVM_ERR_INVALID; }
   if (final_out && !h->fin_g) { h->err = "the tower has no final LayerNorm"; return OVM_ERR_INVALID; }
-  HCHECK(h, hipSetDevice(h->device));
+  OVM_HIP(h, hipSetDevice(h->device));
   h->lastB = B;
   const TowerRun run{&views, n_taps, tap_blocks, tap_out};
   const int r = tower_launches(h, B, s, &run);
   if (r) return r;
   if (final_out) {
     LnOut o; memset(&o, 0, sizeof(o)); o.f32 = final_out; o.ldf = h->D;
-    KCHECK(h, launch_ln_rows(h->X, h->D, B * h->T, h->D, h->fin_g, h->fin_b, h->ln_eps, o, s));
+    OVM_TRY(h, launch_ln_rows(h->X, h->D, B * h->T, h->D, h->fin_g, h->fin_b, h->ln_eps, o, s));
   }
   return OVM_OK;
 }

@@ -20,8 +20,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // into ONE fp32 accumulator, so the split costs MFMA issue slots but no extra registers.
 // Q is stored pre-multiplied by dh^-0.5 * log2(e) (dh = 64) so that attention probabilities are exp2(s - m).
 constexpr float kQScale = 0.125f * 1.44269504088896340736f;
-constexpr float kLoScale = 1.0f;
-constexpr float kLoInv = 1.0f;
 
 // f32 -> f16, round-to-nearest-even, fp16 subnormal results preserved. Written as the scalar
 // v_cvt_f16_f32: when hipcc pairs two conversions into gfx950's v_cvt_pk_f16_f32 the subnormal results

@@ -23,7 +23,6 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
@@ -31,15 +30,14 @@
 #include "kernels.hpp"
 #include "sam.hpp"
 #include "depthpro.hpp"
+#include "loader.hpp"
 
 using namespace ovm;
 
 namespace {
 
-struct Lin { half_t* hi = nullptr; half_t* lo = nullptr; float* bias = nullptr; int N = 0, K = 0; };
-struct Img { half_t* hi = nullptr; half_t* lo = nullptr; };
-struct ResUnit { Lin c1, c2; };
-struct FusionLayer { ResUnit r1, r2; Lin deconv, proj; bool has_r1 = false, has_deconv = false; };
+struct ResUnit { PackedLin c1, c2; };
+struct FusionLayer { ResUnit r1, r2; PackedLin deconv, proj; bool has_r1 = false, has_deconv = false; };
 struct DirectConv { float* w = nullptr; float* b = nullptr; int Cin = 0, Cout = 0; };   // fp32 [Cout][ky][kx][Cin]
 
 constexpr int kTailCo = 32;      // channels of the depth head's last 3x3 convolution (fixed by the architecture)
@@ -51,34 +49,32 @@ struct BorderList { int n; Bordered b[kMaxBordered]; };
 struct Plan {                    // one infer's buffers, carved from the caller's workspace
   float *P0, *P1, *P2;                       // pyramid, NHWC fp32
   float *TOK, *TAP[2], *TOKI, *TOKF;         // patch tower: final tokens + two taps [35][T][D]; image / fov tower tokens [T][D]
-  Img FEAT[6];                               // image, low, medium, high, hook0, hook1: [side^2][D]
-  Img UA, UB;                                // upsample chain ping-pong (unpadded rows)
-  Img CAT;                                   // [ (2g)^2 ][2 * sd0]: low-res | image halves of the concatenation
-  Img UP[5];                                 // inputs of the five projections, zero-bordered (UP[4] unpadded when the projection is the identity)
-  float* NECK[5]; Img NECKP[5];              // projected features fp32 + relu'd zero-bordered copy
-  Img T1[5], HSP[5]; float* HS[5];           // per fusion level: relu(conv1) image, fused sum fp32 + relu'd image
-  Img Y[5], DEC[4]; float* HID[4];           // residual-unit output rows, deconvolution output rows, projected hidden state fp32 (next level's side)
-  float* FUSED; Img FUSEDP; Img H1, H2;      // head
+  SplitImg FEAT[6];                               // image, low, medium, high, hook0, hook1: [side^2][D]
+  SplitImg UA, UB;                                // upsample chain ping-pong (unpadded rows)
+  SplitImg CAT;                                   // [ (2g)^2 ][2 * sd0]: low-res | image halves of the concatenation
+  SplitImg UP[5];                                 // inputs of the five projections, zero-bordered (UP[4] unpadded when the projection is the identity)
+  float* NECK[5]; SplitImg NECKP[5];              // projected features fp32 + relu'd zero-bordered copy
+  SplitImg T1[5], HSP[5]; float* HS[5];           // per fusion level: relu(conv1) image, fused sum fp32 + relu'd image
+  SplitImg Y[5], DEC[4]; float* HID[4];           // residual-unit output rows, deconvolution output rows, projected hidden state fp32 (next level's side)
+  float* FUSED; SplitImg FUSEDP; SplitImg H1, H2;      // head
   float *CANON, *FOVF, *FV[6], *FOV;
   BorderList borders;                        // the zero-bordered images: their frames are cleared at the start of every infer
 };
 
 }  // namespace
 
-struct OvmDepthPro {
+struct OvmDepthPro : ovm::Loader {
   OvmDepthProConfig cfg;
   int device = 0;
-  std::string err;
-  std::vector<void*> allocs;
   DepthProGeom geo;
   OvmHandle *patch = nullptr, *image = nullptr, *fov = nullptr;
   int D = 0, T = 0, F = 0;
   bool ident4 = false;                       // the last projection is nn.Identity (inter_dims[1] == fusion_dim)
   int side[5] = {0}, upc[5] = {0};           // decoder level sides (2 g .. 32 g) and the channel counts entering the projections
-  Lin up_img, up_proj[5], up_ct[5][3], fuse, projc[5];
+  PackedLin up_img, up_proj[5], up_ct[5][3], fuse, projc[5];
   FusionLayer fl[5];
-  Lin head0, head1; half_t *tail_whi = nullptr, *tail_wlo = nullptr; float *tail_b = nullptr, *tail_w2 = nullptr, *tail_b2 = nullptr;
-  Lin fov_neck; DirectConv fov_conv, fov_head[4]; float *fov_fw = nullptr, *fov_fb = nullptr; int fov_k = 0, fov_fc = 0, fov_side[6] = {0};
+  PackedLin head0, head1; half_t *tail_whi = nullptr, *tail_wlo = nullptr; float *tail_b = nullptr, *tail_w2 = nullptr, *tail_b2 = nullptr;
+  PackedLin fov_neck; DirectConv fov_conv, fov_head[4]; float *fov_fw = nullptr, *fov_fb = nullptr; int fov_k = 0, fov_fc = 0, fov_side[6] = {0};
   float* splitk = nullptr; size_t splitk_cap = 0;
   Plan last; bool has_last = false;
   bool prof = false; hipEvent_t ev[kStages + 1] = {nullptr}; bool ev_valid = false;      // ovm_depthpro_profile_enable
@@ -86,119 +82,27 @@ struct OvmDepthPro {
 
 namespace {
 
-#define DCHECK(m, call)                                                                    \
-  do {                                                                                     \
-    hipError_t e_ = (call);                                                                \
-    if (e_ != hipSuccess) {                                                                \
-      (m)->err = std::string(#call) + ": " + hipGetErrorString(e_);                        \
-      return OVM_ERR_HIP;                                                                  \
-    }                                                                                      \
-  } while (0)
-
-#define DK(m, call)                                                                        \
-  do {                                                                                     \
-    int r_ = (call);                                                                       \
-    if (r_ != OVM_OK) {                                                                    \
-      if ((m)->err.empty()) (m)->err = std::string(#call) + " failed (" + std::to_string(r_) + ")"; \
-      return r_;                                                                           \
-    }                                                                                      \
-  } while (0)
-
-template <typename Tp>
-int dalloc(OvmDepthPro* m, Tp** p, size_t count) {
-  void* q = nullptr;
-  size_t bytes = count * sizeof(Tp);
-  if (bytes == 0) bytes = 16;
-  DCHECK(m, hipMalloc(&q, bytes));
-  m->allocs.push_back(q);
-  *p = (Tp*)q;
+// Conv2d k x k; the bias is taken when the checkpoint has one
+int pack_conv(OvmDepthPro* m, const WeightMap& wm, const std::string& prefix, int Cout, int Cin, int k, bool need_bias, PackedLin* out) {
+  int r = ovm::pack_conv(m, wm, prefix, Cout, Cin, k, BIAS_IF_PRESENT, out); if (r) return r;
+  if (need_bias && !out->bias) { m->err = "missing weight: " + prefix + ".bias"; return OVM_ERR_MISSING_WEIGHT; }
   return OVM_OK;
 }
 
-struct WMap {
-  std::map<std::string, const OvmTensor*> m;
-  const OvmTensor* get(const std::string& k) const { auto it = m.find(k); return it == m.end() ? nullptr : it->second; }
-};
-
-int64_t numel(const OvmTensor* t) { int64_t n = 1; for (int i = 0; i < t->ndim; ++i) n *= t->shape[i]; return n; }
-
-int host_of(OvmDepthPro* m, const WMap& wm, const std::string& key, int64_t expect, const float** p) {
-  const OvmTensor* t = wm.get(key);
-  if (!t) { m->err = "missing weight: " + key; return OVM_ERR_MISSING_WEIGHT; }
-  if (numel(t) != expect) { m->err = "bad shape for " + key + " (expected " + std::to_string(expect) + " elements)"; return OVM_ERR_SHAPE; }
-  *p = t->data;
-  return OVM_OK;
+// ConvTranspose2d k2 s2; bias [Cout] (EPI_CONVT adds it per co), taken when the checkpoint has one
+int pack_convt(OvmDepthPro* m, const WeightMap& wm, const std::string& prefix, int Cin, int Cout, PackedLin* out) {
+  return ovm::pack_convt(m, wm, prefix, Cin, Cout, BIAS_IF_PRESENT, false, out);
 }
 
-int upload(OvmDepthPro* m, const float* src, size_t n, float** out) {
-  int r = dalloc(m, out, n); if (r) return r;
-  DCHECK(m, hipMemcpy(*out, src, n * 4, hipMemcpyHostToDevice));
-  return OVM_OK;
-}
-
-// host [N][K] fp32 (GEMM k-order) -> the packed fp16 image launch_gemm streams (ovm_g_pack_weight), K padded to whole 64-wide k-steps
-int pack(OvmDepthPro* m, const float* w, int N, int K, const float* bias, int nbias, Lin* out) {
-  const int Kpad = (K + 63) / 64 * 64, Npad = (N + 127) / 128 * 128;
-  const bool split = m->cfg.precision == 3;
-  float* tmp = nullptr;
-  DCHECK(m, hipMalloc((void**)&tmp, (size_t)N * K * 4));
-  hipError_t e = hipMemcpy(tmp, w, (size_t)N * K * 4, hipMemcpyHostToDevice);
-  int r = e == hipSuccess ? dalloc(m, &out->hi, (size_t)Npad * Kpad * (split ? 2 : 1)) : OVM_ERR_HIP;
-  if (!r) {
-    out->lo = split ? out->hi + 32 : nullptr;
-    r = ovm_g_pack_weight(tmp, N, K, Kpad, (uint16_t*)out->hi, (uint16_t*)out->lo, nullptr);
-    if (!r && hipDeviceSynchronize() != hipSuccess) r = OVM_ERR_HIP;
-  }
-  (void)hipFree(tmp);
-  if (r) { if (m->err.empty()) m->err = "weight packing failed"; return r; }
-  out->N = N; out->K = Kpad; out->bias = nullptr;
-  if (bias) return upload(m, bias, (size_t)nbias, &out->bias);
-  return OVM_OK;
-}
-
-const float* opt_bias(const WMap& wm, const std::string& key, int64_t n) {
-  const OvmTensor* t = wm.get(key);
-  return (t && numel(t) == n) ? t->data : nullptr;
-}
-
-// Conv2d k x k weight [Cout][Cin][k][k] -> [Cout][(ky * k + kx) * Cin + c]; the bias is taken when the checkpoint has one
-int pack_conv(OvmDepthPro* m, const WMap& wm, const std::string& prefix, int Cout, int Cin, int k, bool need_bias, Lin* out) {
-  const float* w; int r = host_of(m, wm, prefix + ".weight", (int64_t)Cout * Cin * k * k, &w); if (r) return r;
-  const float* b = opt_bias(wm, prefix + ".bias", Cout);
-  if (need_bias && !b) { m->err = "missing weight: " + prefix + ".bias"; return OVM_ERR_MISSING_WEIGHT; }
-  const int kk = k * k;
-  std::vector<float> v((size_t)Cout * Cin * kk);
-  for (int o = 0; o < Cout; ++o)
-    for (int ci = 0; ci < Cin; ++ci)
-      for (int t = 0; t < kk; ++t) v[((size_t)o * kk + t) * Cin + ci] = w[((size_t)o * Cin + ci) * kk + t];
-  return pack(m, v.data(), Cout, Cin * kk, b, Cout, out);
-}
-
-// ConvTranspose2d k2 s2 weight [Cin][Cout][2][2] -> GEMM rows [(a * 2 + b) * Cout + co][ci]; bias [Cout] (EPI_CONVT adds it per co)
-int pack_convt(OvmDepthPro* m, const WMap& wm, const std::string& prefix, int Cin, int Cout, Lin* out) {
-  const float* w; int r = host_of(m, wm, prefix + ".weight", (int64_t)Cin * Cout * 4, &w); if (r) return r;
-  std::vector<float> v((size_t)4 * Cout * Cin);
-  for (int ci = 0; ci < Cin; ++ci)
-    for (int co = 0; co < Cout; ++co)
-      for (int q = 0; q < 4; ++q) v[((size_t)q * Cout + co) * Cin + ci] = w[((size_t)ci * Cout + co) * 4 + q];
-  return pack(m, v.data(), 4 * Cout, Cin, opt_bias(wm, prefix + ".bias", Cout), Cout, out);
-}
-
-int load_direct(OvmDepthPro* m, const WMap& wm, const std::string& prefix, int Cout, int Cin, DirectConv* d) {
+int load_direct(OvmDepthPro* m, const WeightMap& wm, const std::string& prefix, int Cout, int Cin, DirectConv* d) {
   const float *w, *b;
-  int r = host_of(m, wm, prefix + ".weight", (int64_t)Cout * Cin * 9, &w); if (r) return r;
-  r = host_of(m, wm, prefix + ".bias", Cout, &b); if (r) return r;
-  std::vector<float> v((size_t)Cout * Cin * 9);
-  for (int o = 0; o < Cout; ++o)
-    for (int ci = 0; ci < Cin; ++ci)
-      for (int t = 0; t < 9; ++t) v[((size_t)o * 9 + t) * Cin + ci] = w[((size_t)o * Cin + ci) * 9 + t];
+  int r = find_weight(m, wm, prefix + ".weight", (int64_t)Cout * Cin * 9, &w); if (r) return r;
+  r = find_weight(m, wm, prefix + ".bias", Cout, &b); if (r) return r;
+  const std::vector<float> v = reorder_conv(w, Cout, Cin, 3, 3);
   d->Cin = Cin; d->Cout = Cout;
-  r = upload(m, v.data(), v.size(), &d->w); if (r) return r;
-  return upload(m, b, (size_t)Cout, &d->b);
+  r = upload_f32(m, v.data(), v.size(), &d->w); if (r) return r;
+  return upload_f32(m, b, (size_t)Cout, &d->b);
 }
-
-inline dim3 g1(long n, int bs = 256) { return dim3((unsigned)((n + bs - 1) / bs)); }
-int last_launch() { return hipGetLastError() == hipSuccess ? OVM_OK : OVM_ERR_HIP; }
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------------------
 
@@ -439,22 +343,22 @@ __global__ void dp_depth_out_kernel(const float* __restrict__ canon, int S, int 
 
 // ---- GEMM wrappers ---------------------------------------------------------------------------------------------------------------
 
-GemmParams gp(OvmDepthPro* m, const Img& A, const Lin& w, long M) {
+GemmParams gp(OvmDepthPro* m, const SplitImg& A, const PackedLin& w, long M) {
   GemmParams p; memset(&p, 0, sizeof(p));
-  p.Ahi = A.hi; p.Alo = A.lo; p.Whi = w.hi; p.Wlo = w.lo; p.M = (int)M; p.N = w.N; p.K = w.K; p.bias = w.bias;
+  p.Ahi = A.hi; p.Alo = A.lo; p.Whi = w.hi; p.Wlo = w.lo; p.M = (int)M; p.N = w.N; p.K = w.Kpad; p.bias = w.bias;
   p.part_ws = m->splitk; p.part_cap = m->splitk_cap;
   return p;
 }
 
 // 1x1 convolution / linear on rows [M][lda]: C fp32 and / or split rows O (ldo; pad_side > 0: into a zero-bordered image)
-int lin(OvmDepthPro* m, const Img& A, int lda, long M, const Lin& w, float* C, const Img& O, int ldo, int pad_side, hipStream_t s) {
+int lin(OvmDepthPro* m, const SplitImg& A, int lda, long M, const PackedLin& w, float* C, const SplitImg& O, int ldo, int pad_side, hipStream_t s) {
   GemmParams p = gp(m, A, w, M);
   p.lda = lda; p.C = C; p.ldc = w.N; p.Ohi = O.hi; p.Olo = O.lo; p.ldo = ldo; p.padH = p.padW = pad_side;
   return launch_gemm(p, m->cfg.precision, EPI_STORE, A_ROWMAJOR, s);
 }
 
 // 3x3 convolution, pad 1, over a zero-bordered image: value = act(conv + bias) + R + R2; C fp32, O split (pad_o: zero-bordered, relu_o: relu'd)
-int conv3(OvmDepthPro* m, const Img& A, int side, int Cin, const Lin& w, int relu, const float* R, const float* R2, float* C, const Img& O, int ldo,
+int conv3(OvmDepthPro* m, const SplitImg& A, int side, int Cin, const PackedLin& w, int relu, const float* R, const float* R2, float* C, const SplitImg& O, int ldo,
           bool pad_o, bool relu_o, hipStream_t s) {
   GemmParams p = gp(m, A, w, (long)side * side);
   p.cH = p.cW = side; p.cC = Cin; p.K = 9 * Cin; p.relu = relu; p.R = R; p.ldr = w.N; p.R2 = R2; p.ldr2 = w.N;
@@ -463,13 +367,13 @@ int conv3(OvmDepthPro* m, const Img& A, int side, int Cin, const Lin& w, int rel
 }
 
 // ConvTranspose2d k2 s2: rows [side^2][lda] -> [2 side][2 side][Cout] (ldo: pixel stride of O; pad_o: zero-bordered)
-int convt(OvmDepthPro* m, const Img& A, int lda, int side, const Lin& w, const Img& O, int ldo, bool pad_o, hipStream_t s) {
+int convt(OvmDepthPro* m, const SplitImg& A, int lda, int side, const PackedLin& w, const SplitImg& O, int ldo, bool pad_o, hipStream_t s) {
   GemmParams p = gp(m, A, w, (long)side * side);
   p.lda = lda; p.Ohi = O.hi; p.Olo = O.lo; p.G = side; p.Cout = w.N / 4; p.ldo = ldo; p.padH = p.padW = pad_o ? 2 * side : 0;
   return launch_gemm(p, m->cfg.precision, EPI_CONVT, A_ROWMAJOR, s);
 }
 
-int unsplit(const Img& A, int side, int C, int ld, bool pad_in, float* out, const Img& P, hipStream_t s) {
+int unsplit(const SplitImg& A, int side, int C, int ld, bool pad_in, float* out, const SplitImg& P, hipStream_t s) {
   hipLaunchKernelGGL(dp_unsplit_kernel, g1((long)side * side * (C / 4)), dim3(256), 0, s, A.hi, A.lo, side, C, ld, pad_in ? 1 : 0, out, P.hi, P.lo);
   return last_launch();
 }
@@ -483,7 +387,7 @@ size_t plan(const OvmDepthPro* m, char* base, Plan* pl) {
   const bool split = m->cfg.precision == 3;
   size_t off = 0;
   auto takef = [&](float** p, size_t n) { *p = (float*)(base + off); off += (n * 4 + 255) / 256 * 256; };
-  auto takei = [&](Img* p, size_t n) {
+  auto takei = [&](SplitImg* p, size_t n) {
     p->hi = (half_t*)(base + off); off += (n * 2 + 255) / 256 * 256;
     p->lo = nullptr;
     if (split) { p->lo = (half_t*)(base + off); off += (n * 2 + 255) / 256 * 256; }
@@ -510,7 +414,7 @@ size_t plan(const OvmDepthPro* m, char* base, Plan* pl) {
   takef(&pl->FOV, 64);
   // zero-bordered images: only their frames are cleared (dp_clear_borders_kernel), the interiors are overwritten by every call
   pl->borders.n = 0;
-  auto takeb = [&](Img* p, int side, int C) {
+  auto takeb = [&](SplitImg* p, int side, int C) {
     takei(p, (size_t)(side + 2) * (side + 2) * C);
     pl->borders.b[pl->borders.n++] = Bordered{p->hi, p->lo, side, C};
   };
@@ -589,7 +493,7 @@ int ovm_depthpro_destroy(OvmDepthPro* m) {
   if (m->patch) ovm_destroy(m->patch);
   if (m->image) ovm_destroy(m->image);
   if (m->fov) ovm_destroy(m->fov);
-  for (void* p : m->allocs) (void)hipFree(p);
+  m->free_all();
   for (hipEvent_t e : m->ev) if (e) (void)hipEventDestroy(e);
   delete m;
   return OVM_OK;
@@ -599,7 +503,7 @@ int ovm_depthpro_create(const OvmDepthProConfig* cfg, const OvmTensor* weights, 
   if (!cfg || !out) return OVM_ERR_INVALID;
   OvmDepthPro* m = new OvmDepthPro();
   *out = m;
-  m->cfg = *cfg; m->device = device;
+  m->cfg = *cfg; m->device = device; m->precision = cfg->precision; m->k_align = 64;
   const OvmDepthProConfig& c = m->cfg;
   int r;
   if ((r = depthpro_geometry(c, &m->geo, &m->err))) return r;           // host only: before any device call
@@ -618,9 +522,8 @@ int ovm_depthpro_create(const OvmDepthProConfig* cfg, const OvmTensor* weights, 
   m->ident4 = c.inter_dims[1] == F;
   for (int i = 0; i < 5; ++i) m->side[i] = (2 * g) << i;
   m->upc[0] = c.scaled_dims[0]; m->upc[1] = c.scaled_dims[1]; m->upc[2] = c.scaled_dims[2]; m->upc[3] = c.inter_dims[0]; m->upc[4] = c.inter_dims[1];
-  DCHECK(m, hipSetDevice(device));
-  WMap wm;
-  for (int i = 0; i < n_weights; ++i) wm.m[weights[i].name] = &weights[i];
+  OVM_HIP(m, hipSetDevice(device));
+  const WeightMap wm(weights, n_weights);
   if (wm.get("fusion_stage.final.residual_layer1.batch_norm1.weight")) { m->err = "unsupported: batch norm in the fusion residual units"; return OVM_ERR_UNSUPPORTED; }
   // ---- the three towers
   {
@@ -680,32 +583,24 @@ int ovm_depthpro_create(const OvmDepthProConfig* cfg, const OvmTensor* weights, 
   {
     const int C = F / 2;
     const float *w, *b, *w2, *b2;
-    if ((r = host_of(m, wm, "head.layers.2.weight", (int64_t)kTailCo * C * 9, &w))) return r;
-    if ((r = host_of(m, wm, "head.layers.2.bias", kTailCo, &b))) return r;
-    if ((r = host_of(m, wm, "head.layers.4.weight", kTailCo, &w2))) return r;
-    if ((r = host_of(m, wm, "head.layers.4.bias", 1, &b2))) return r;
-    std::vector<half_t> vh((size_t)kTailCo * 9 * C), vl(vh.size());         // [32][tap * C + c], split
-    for (int o = 0; o < kTailCo; ++o)
-      for (int ci = 0; ci < C; ++ci)
-        for (int t = 0; t < 9; ++t) {
-          const float x = w[((size_t)o * C + ci) * 9 + t];
-          const half_t hh = (half_t)x;
-          vh[((size_t)o * 9 + t) * C + ci] = hh; vl[((size_t)o * 9 + t) * C + ci] = (half_t)(x - (float)hh);
-        }
-    if ((r = dalloc(m, &m->tail_whi, vh.size()))) return r;
-    if ((r = dalloc(m, &m->tail_wlo, vl.size()))) return r;
-    DCHECK(m, hipMemcpy(m->tail_whi, vh.data(), vh.size() * 2, hipMemcpyHostToDevice));
-    DCHECK(m, hipMemcpy(m->tail_wlo, vl.data(), vl.size() * 2, hipMemcpyHostToDevice));
-    if ((r = upload(m, b, kTailCo, &m->tail_b))) return r;
-    if ((r = upload(m, w2, kTailCo, &m->tail_w2))) return r;
-    if ((r = upload(m, b2, 1, &m->tail_b2))) return r;
+    if ((r = find_weight(m, wm, "head.layers.2.weight", (int64_t)kTailCo * C * 9, &w))) return r;
+    if ((r = find_weight(m, wm, "head.layers.2.bias", kTailCo, &b))) return r;
+    if ((r = find_weight(m, wm, "head.layers.4.weight", kTailCo, &w2))) return r;
+    if ((r = find_weight(m, wm, "head.layers.4.bias", 1, &b2))) return r;
+    const std::vector<float> v = reorder_conv(w, kTailCo, C, 3, 3);
+    std::vector<half_t> vh(v.size()), vl(v.size());                         // [32][tap * C + c], split
+    for (size_t i = 0; i < v.size(); ++i) { vh[i] = (half_t)v[i]; vl[i] = (half_t)(v[i] - (float)vh[i]); }
+    if ((r = m->alloc(&m->tail_whi, vh.size()))) return r;
+    if ((r = m->alloc(&m->tail_wlo, vl.size()))) return r;
+    OVM_HIP(m, hipMemcpy(m->tail_whi, vh.data(), vh.size() * 2, hipMemcpyHostToDevice));
+    OVM_HIP(m, hipMemcpy(m->tail_wlo, vl.data(), vl.size() * 2, hipMemcpyHostToDevice));
+    if ((r = upload_f32(m, b, kTailCo, &m->tail_b))) return r;
+    if ((r = upload_f32(m, w2, kTailCo, &m->tail_w2))) return r;
+    if ((r = upload_f32(m, b2, 1, &m->tail_b2))) return r;
   }
   // ---- field of view
   if (c.use_fov) {
-    const float *w, *b;
-    if ((r = host_of(m, wm, "fov_model.fov_encoder.neck.weight", (int64_t)(F / 2) * D, &w))) return r;
-    if ((r = host_of(m, wm, "fov_model.fov_encoder.neck.bias", F / 2, &b))) return r;
-    if ((r = pack(m, w, F / 2, D, b, F / 2, &m->fov_neck))) return r;
+    if ((r = pack_linear(m, wm, "fov_model.fov_encoder.neck", F / 2, D, &m->fov_neck))) return r;
     if ((r = load_direct(m, wm, "fov_model.conv", F / 2, F, &m->fov_conv))) return r;
     int sd = g; m->fov_side[0] = g;
     for (int i = 0; i < c.num_fov_layers; ++i) {
@@ -716,17 +611,16 @@ int ovm_depthpro_create(const OvmDepthProConfig* cfg, const OvmTensor* weights, 
     if (m->fov_k != sd) { m->err = "unsupported field-of-view head: its last convolution does not reduce the map to one number"; return OVM_ERR_UNSUPPORTED; }
     const std::string P = "fov_model.head.layers." + std::to_string(2 * c.num_fov_layers);
     const int k = m->fov_k, C = m->fov_fc;
-    if ((r = host_of(m, wm, P + ".weight", (int64_t)C * k * k, &w))) return r;
-    if ((r = host_of(m, wm, P + ".bias", 1, &b))) return r;
-    std::vector<float> v((size_t)C * k * k);              // [1][C][k][k] -> [ky][kx][C]
-    for (int ci = 0; ci < C; ++ci)
-      for (int t = 0; t < k * k; ++t) v[(size_t)t * C + ci] = w[(size_t)ci * k * k + t];
-    if ((r = upload(m, v.data(), v.size(), &m->fov_fw))) return r;
-    if ((r = upload(m, b, 1, &m->fov_fb))) return r;
+    const float *w, *b;
+    if ((r = find_weight(m, wm, P + ".weight", (int64_t)C * k * k, &w))) return r;
+    if ((r = find_weight(m, wm, P + ".bias", 1, &b))) return r;
+    const std::vector<float> v = reorder_conv(w, 1, C, k, k);     // [1][C][k][k] -> [ky][kx][C]
+    if ((r = upload_f32(m, v.data(), v.size(), &m->fov_fw))) return r;
+    if ((r = upload_f32(m, b, 1, &m->fov_fb))) return r;
   }
   m->splitk_cap = (size_t)112 << 20;                      // split-K: <= 96 tiles of 128 x 128, <= 16 slices of fp32 partials
-  { char* p = nullptr; if ((r = dalloc(m, &p, m->splitk_cap))) return r; m->splitk = (float*)p; }
-  DCHECK(m, hipDeviceSynchronize());
+  { char* p = nullptr; if ((r = m->alloc(&p, m->splitk_cap))) return r; m->splitk = (float*)p; }
+  OVM_HIP(m, hipDeviceSynchronize());
   return OVM_OK;
 }
 
@@ -753,7 +647,7 @@ int ovm_depthpro_infer(OvmDepthPro* m, const OvmImage* image, int32_t flip_bgr, 
     m->err = "workspace too small: " + std::to_string(workspace_bytes) + " bytes given, " + std::to_string(need) + " needed (ovm_depthpro_workspace)";
     return OVM_ERR_CAPACITY;
   }
-  DCHECK(m, hipSetDevice(m->device));
+  OVM_HIP(m, hipSetDevice(m->device));
   hipStream_t s = (hipStream_t)stream;
   const DepthProGeom& q = m->geo;
   const int H = image->height, W = image->width, S = q.S, g = q.g, D = m->D, F = m->F, T = m->T;
@@ -763,23 +657,23 @@ int ovm_depthpro_infer(OvmDepthPro* m, const OvmImage* image, int32_t flip_bgr, 
     return hipEventRecord(m->ev[i], s) == hipSuccess ? OVM_OK : OVM_ERR_HIP;
   };
   m->ev_valid = false;
-  DK(m, stamp(0));
+  OVM_TRY(m, stamp(0));
   {
     int mx = 0;
     for (int i = 0; i < pl.borders.n; ++i) { const int n = 4 * (pl.borders.b[i].side + 1) * (pl.borders.b[i].C / 8); if (n > mx) mx = n; }
     hipLaunchKernelGGL(dp_clear_borders_kernel, dim3((mx + 255) / 256, pl.borders.n), dim3(256), 0, s, pl.borders);
-    DK(m, last_launch());
+    OVM_TRY(m, last_launch());
     if (k64(F / 2) != F / 2) {                            // F / 2 = 32: H1's rows carry 32 pad columns, which the next GEMM reads
       const size_t hb = (size_t)m->side[4] * m->side[4] * k64(F / 2) * 2;
-      DCHECK(m, hipMemsetAsync(pl.H1.hi, 0, hb, s));
-      if (pl.H1.lo) DCHECK(m, hipMemsetAsync(pl.H1.lo, 0, hb, s));
+      OVM_HIP(m, hipMemsetAsync(pl.H1.hi, 0, hb, s));
+      if (pl.H1.lo) OVM_HIP(m, hipMemsetAsync(pl.H1.lo, 0, hb, s));
     }
   }
   // ---- 1. preprocess + pyramid
   hipLaunchKernelGGL(dp_pyramid_kernel, g1((long)(S / 4) * (S / 4) * 3), dim3(256), 0, s, (const uint8_t*)image->data, H, W, image->stride_h, image->stride_w,
                      image->stride_c, flip_bgr ? 1 : 0, S, pl.P0, pl.P1, pl.P2);
-  DK(m, last_launch());
-  DK(m, stamp(1));
+  OVM_TRY(m, last_launch());
+  OVM_TRY(m, stamp(1));
   // ---- 2. towers: 35 crops as one batch (high resolution first), the whole image at the crop side for the other two
   {
     TowerViews v; memset(&v, 0, sizeof(v));
@@ -791,13 +685,13 @@ int ovm_depthpro_infer(OvmDepthPro* m, const OvmImage* image, int32_t flip_bgr, 
           v.v[n++] = TowerView{lev[l] + ((size_t)i * q.stride[l] * ls[l] + (size_t)j * q.stride[l]) * 3, 1, (int64_t)3 * ls[l], 3};
     v.n = n;
     float* taps[2] = {pl.TAP[0], pl.TAP[1]};
-    DK(m, run_tower(m, m->patch, v, 2, c.hook_ids, taps, pl.TOK, "patch encoder", s));
+    OVM_TRY(m, run_tower(m, m->patch, v, 2, c.hook_ids, taps, pl.TOK, "patch encoder", s));
     TowerViews w1; memset(&w1, 0, sizeof(w1));
     w1.n = 1; w1.v[0] = TowerView{pl.P2, 1, (int64_t)3 * (S / 4), 3};
-    DK(m, run_tower(m, m->image, w1, 0, nullptr, nullptr, pl.TOKI, "image encoder", s));
-    if (c.use_fov) DK(m, run_tower(m, m->fov, w1, 0, nullptr, nullptr, pl.TOKF, "field-of-view encoder", s));
+    OVM_TRY(m, run_tower(m, m->image, w1, 0, nullptr, nullptr, pl.TOKI, "image encoder", s));
+    if (c.use_fov) OVM_TRY(m, run_tower(m, m->fov, w1, 0, nullptr, nullptr, pl.TOKF, "field-of-view encoder", s));
   }
-  DK(m, stamp(2));
+  OVM_TRY(m, stamp(2));
   // ---- 3. token merge: features 0..5 = image, low, medium, high, hook 0, hook 1
   {
     const int c_hi = 0, c_med = q.ncrop[0] * q.ncrop[0], c_low = c_med + q.ncrop[1] * q.ncrop[1];
@@ -806,90 +700,90 @@ int ovm_depthpro_infer(OvmDepthPro* m, const OvmImage* image, int32_t flip_bgr, 
       const int l = src[i].lvl, out = q.out[l];
       hipLaunchKernelGGL(dp_merge_kernel, g1((long)out * out * (D / 4)), dim3(256), 0, s, src[i].tok, T, D, src[i].crop0, q.ncrop[l], g, q.pad[l], q.merged[l], out,
                          pl.FEAT[i].hi, pl.FEAT[i].lo);
-      DK(m, last_launch());
+      OVM_TRY(m, last_launch());
     }
   }
   // ---- 4. neck
   const int sd0 = c.scaled_dims[0];
-  const Img none;
+  const SplitImg none;
   {
-    Img cat_img{pl.CAT.hi + sd0, pl.CAT.lo ? pl.CAT.lo + sd0 : nullptr};
-    DK(m, convt(m, pl.FEAT[0], D, g, m->up_img, cat_img, 2 * sd0, false, s));                        // image features -> second half
-    DK(m, lin(m, pl.FEAT[1], D, (long)g * g, m->up_proj[0], nullptr, pl.UA, sd0, 0, s));
-    DK(m, convt(m, pl.UA, sd0, g, m->up_ct[0][0], pl.CAT, 2 * sd0, false, s));                       // low resolution -> first half
-    DK(m, lin(m, pl.CAT, 2 * sd0, (long)4 * g * g, m->fuse, nullptr, pl.UP[0], sd0, 2 * g, s));
+    SplitImg cat_img{pl.CAT.hi + sd0, pl.CAT.lo ? pl.CAT.lo + sd0 : nullptr};
+    OVM_TRY(m, convt(m, pl.FEAT[0], D, g, m->up_img, cat_img, 2 * sd0, false, s));                        // image features -> second half
+    OVM_TRY(m, lin(m, pl.FEAT[1], D, (long)g * g, m->up_proj[0], nullptr, pl.UA, sd0, 0, s));
+    OVM_TRY(m, convt(m, pl.UA, sd0, g, m->up_ct[0][0], pl.CAT, 2 * sd0, false, s));                       // low resolution -> first half
+    OVM_TRY(m, lin(m, pl.CAT, 2 * sd0, (long)4 * g * g, m->fuse, nullptr, pl.UP[0], sd0, 2 * g, s));
     for (int i = 1; i < 5; ++i) {                                                                    // medium, high, hook 0, hook 1
       const int side_in = i == 1 ? 2 * g : 4 * g, nct = i < 3 ? 1 : i - 1, Cm = m->up_proj[i].N;
-      DK(m, lin(m, pl.FEAT[i + 1], D, (long)side_in * side_in, m->up_proj[i], nullptr, pl.UA, Cm, 0, s));
-      Img cur = pl.UA, nxt = pl.UB; int sd = side_in, Cc = Cm;
+      OVM_TRY(m, lin(m, pl.FEAT[i + 1], D, (long)side_in * side_in, m->up_proj[i], nullptr, pl.UA, Cm, 0, s));
+      SplitImg cur = pl.UA, nxt = pl.UB; int sd = side_in, Cc = Cm;
       for (int k = 0; k < nct; ++k) {
         const bool last = k + 1 == nct, pad = last && !(i == 4 && m->ident4);
-        const Img& dst = last ? pl.UP[i] : nxt;
-        DK(m, convt(m, cur, Cc, sd, m->up_ct[i][k], dst, m->upc[i], pad, s));
+        const SplitImg& dst = last ? pl.UP[i] : nxt;
+        OVM_TRY(m, convt(m, cur, Cc, sd, m->up_ct[i][k], dst, m->upc[i], pad, s));
         sd *= 2; Cc = m->upc[i];
-        if (!last) { Img t = cur; cur = nxt; nxt = t; }
+        if (!last) { SplitImg t = cur; cur = nxt; nxt = t; }
       }
     }
     for (int i = 0; i < 5; ++i) {
-      if (i == 4 && m->ident4) { DK(m, unsplit(pl.UP[4], m->side[4], F, F, false, pl.NECK[4], pl.NECKP[4], s)); break; }
-      DK(m, conv3(m, pl.UP[i], m->side[i], m->upc[i], m->projc[i], 0, nullptr, nullptr, pl.NECK[i], pl.NECKP[i], F, true, true, s));
+      if (i == 4 && m->ident4) { OVM_TRY(m, unsplit(pl.UP[4], m->side[4], F, F, false, pl.NECK[4], pl.NECKP[4], s)); break; }
+      OVM_TRY(m, conv3(m, pl.UP[i], m->side[i], m->upc[i], m->projc[i], 0, nullptr, nullptr, pl.NECK[i], pl.NECKP[i], F, true, true, s));
     }
   }
-  DK(m, stamp(3));
+  OVM_TRY(m, stamp(3));
   // ---- 5. fusion: y = x + conv2(relu(conv1(relu(x)))) with the relu'd images written by the producing epilogues
   for (int i = 0; i < 5; ++i) {
     const FusionLayer& y = m->fl[i];
     const int sd = m->side[i];
-    const float* hs = pl.NECK[i]; Img hsp = pl.NECKP[i];
+    const float* hs = pl.NECK[i]; SplitImg hsp = pl.NECKP[i];
     if (y.has_r1) {
-      DK(m, conv3(m, pl.NECKP[i], sd, F, y.r1.c1, 1, nullptr, nullptr, nullptr, pl.T1[i], F, true, false, s));
-      DK(m, conv3(m, pl.T1[i], sd, F, y.r1.c2, 0, pl.NECK[i], pl.HID[i - 1], pl.HS[i], pl.HSP[i], F, true, true, s));
+      OVM_TRY(m, conv3(m, pl.NECKP[i], sd, F, y.r1.c1, 1, nullptr, nullptr, nullptr, pl.T1[i], F, true, false, s));
+      OVM_TRY(m, conv3(m, pl.T1[i], sd, F, y.r1.c2, 0, pl.NECK[i], pl.HID[i - 1], pl.HS[i], pl.HSP[i], F, true, true, s));
       hs = pl.HS[i]; hsp = pl.HSP[i];
     }
-    DK(m, conv3(m, hsp, sd, F, y.r2.c1, 1, nullptr, nullptr, nullptr, pl.T1[i], F, true, false, s));
-    DK(m, conv3(m, pl.T1[i], sd, F, y.r2.c2, 0, hs, nullptr, nullptr, pl.Y[i], F, false, false, s));
+    OVM_TRY(m, conv3(m, hsp, sd, F, y.r2.c1, 1, nullptr, nullptr, nullptr, pl.T1[i], F, true, false, s));
+    OVM_TRY(m, conv3(m, pl.T1[i], sd, F, y.r2.c2, 0, hs, nullptr, nullptr, pl.Y[i], F, false, false, s));
     if (y.has_deconv) {
-      DK(m, convt(m, pl.Y[i], F, sd, y.deconv, pl.DEC[i], F, false, s));
-      DK(m, lin(m, pl.DEC[i], F, (long)4 * sd * sd, y.proj, pl.HID[i], none, 0, 0, s));
+      OVM_TRY(m, convt(m, pl.Y[i], F, sd, y.deconv, pl.DEC[i], F, false, s));
+      OVM_TRY(m, lin(m, pl.DEC[i], F, (long)4 * sd * sd, y.proj, pl.HID[i], none, 0, 0, s));
     } else {
-      DK(m, lin(m, pl.Y[i], F, (long)sd * sd, y.proj, pl.FUSED, pl.FUSEDP, F, sd, s));
+      OVM_TRY(m, lin(m, pl.Y[i], F, (long)sd * sd, y.proj, pl.FUSED, pl.FUSEDP, F, sd, s));
     }
   }
-  DK(m, stamp(4));
+  OVM_TRY(m, stamp(4));
   // ---- 6. depth head
   {
     const int sd = m->side[4], C = F / 2;
-    DK(m, conv3(m, pl.FUSEDP, sd, F, m->head0, 0, nullptr, nullptr, nullptr, pl.H1, k64(C), false, false, s));
-    DK(m, convt(m, pl.H1, k64(C), sd, m->head1, pl.H2, C, true, s));
+    OVM_TRY(m, conv3(m, pl.FUSEDP, sd, F, m->head0, 0, nullptr, nullptr, nullptr, pl.H1, k64(C), false, false, s));
+    OVM_TRY(m, convt(m, pl.H1, k64(C), sd, m->head1, pl.H2, C, true, s));
     if (c.precision == 3)
       hipLaunchKernelGGL(dp_head_tail_kernel<3>, dim3(S / 16, S / 16), dim3(256), 0, s, pl.H2.hi, pl.H2.lo, S, C, m->tail_whi, m->tail_wlo, m->tail_b, m->tail_w2, m->tail_b2, pl.CANON);
     else
       hipLaunchKernelGGL(dp_head_tail_kernel<1>, dim3(S / 16, S / 16), dim3(256), 0, s, pl.H2.hi, pl.H2.lo, S, C, m->tail_whi, m->tail_wlo, m->tail_b, m->tail_w2, m->tail_b2, pl.CANON);
-    DK(m, last_launch());
+    OVM_TRY(m, last_launch());
   }
-  DK(m, stamp(5));
+  OVM_TRY(m, stamp(5));
   // ---- 7. field of view
   if (c.use_fov) {
-    const Lin& nk = m->fov_neck;
-    DK(m, ovm_g_linear(pl.TOKF, D, T, D, (const uint16_t*)nk.hi, (const uint16_t*)nk.lo, nk.N, nk.K, nk.bias, 0, nullptr, 0, pl.FOVF, F / 2, c.precision, s));
+    const PackedLin& nk = m->fov_neck;
+    OVM_TRY(m, ovm_g_linear(pl.TOKF, D, T, D, (const uint16_t*)nk.hi, (const uint16_t*)nk.lo, nk.N, nk.Kpad, nk.bias, 0, nullptr, 0, pl.FOVF, F / 2, c.precision, s));
     hipLaunchKernelGGL(dp_conv_s2_kernel, g1((long)g * g * (F / 2)), dim3(256), 0, s, pl.NECK[0], 2 * g, F, m->fov_conv.w, m->fov_conv.b, g, F / 2,
                        pl.FOVF + F / 2 /* the class token's row is dropped */, F / 2, pl.FV[0]);
-    DK(m, last_launch());
+    OVM_TRY(m, last_launch());
     for (int i = 0; i < c.num_fov_layers; ++i) {
       const DirectConv& d = m->fov_head[i];
       hipLaunchKernelGGL(dp_conv_s2_kernel, g1((long)m->fov_side[i + 1] * m->fov_side[i + 1] * d.Cout), dim3(256), 0, s, pl.FV[i], m->fov_side[i], d.Cin, d.w, d.b,
                          m->fov_side[i + 1], d.Cout, (const float*)nullptr, 0, pl.FV[i + 1]);
-      DK(m, last_launch());
+      OVM_TRY(m, last_launch());
     }
     hipLaunchKernelGGL(dp_dot_kernel, dim3(1), dim3(256), 0, s, pl.FV[c.num_fov_layers], m->fov_fw, m->fov_fb, m->fov_k * m->fov_k * m->fov_fc, pl.FOV);
-    DK(m, last_launch());
+    OVM_TRY(m, last_launch());
   }
-  DK(m, stamp(6));
+  OVM_TRY(m, stamp(6));
   // ---- 8. metres
   hipLaunchKernelGGL(dp_depth_out_kernel, g1((long)H * W), dim3(256), 0, s, pl.CANON, S, H, W, f_px > 0.f ? f_px : 0.f, c.use_fov ? pl.FOV : (const float*)nullptr,
                      depth_out, fov_deg_out, f_px_out);
-  DK(m, last_launch());
-  DK(m, stamp(7));
+  OVM_TRY(m, last_launch());
+  OVM_TRY(m, stamp(7));
   m->ev_valid = m->prof;
   m->last = pl; m->has_last = true;
   return OVM_OK;
@@ -898,8 +792,8 @@ int ovm_depthpro_infer(OvmDepthPro* m, const OvmImage* image, int32_t flip_bgr, 
 int ovm_depthpro_profile_enable(OvmDepthPro* m, int32_t on) {
   if (!m || !m->patch) return OVM_ERR_INVALID;
   if (on && !m->ev[0]) {
-    DCHECK(m, hipSetDevice(m->device));
-    for (int i = 0; i <= kStages; ++i) DCHECK(m, hipEventCreate(&m->ev[i]));
+    OVM_HIP(m, hipSetDevice(m->device));
+    for (int i = 0; i <= kStages; ++i) OVM_HIP(m, hipEventCreate(&m->ev[i]));
   }
   m->prof = on != 0; m->ev_valid = false;
   return OVM_OK;
@@ -908,8 +802,8 @@ int ovm_depthpro_profile_enable(OvmDepthPro* m, int32_t on) {
 int ovm_depthpro_stage_ms(OvmDepthPro* m, float* ms, int32_t n) {
   if (!m || !ms || n < kStages) return OVM_ERR_INVALID;
   if (!m->ev_valid) { m->err = "no profiled infer to read (ovm_depthpro_profile_enable, then ovm_depthpro_infer)"; return OVM_ERR_INVALID; }
-  DCHECK(m, hipEventSynchronize(m->ev[kStages]));
-  for (int i = 0; i < kStages; ++i) DCHECK(m, hipEventElapsedTime(&ms[i], m->ev[i], m->ev[i + 1]));
+  OVM_HIP(m, hipEventSynchronize(m->ev[kStages]));
+  for (int i = 0; i < kStages; ++i) OVM_HIP(m, hipEventElapsedTime(&ms[i], m->ev[i], m->ev[i + 1]));
   return OVM_OK;
 }
 
@@ -927,7 +821,7 @@ int64_t ovm_depthpro_debug_copy(OvmDepthPro* m, const char* name, float* dst, in
     const int i = n[8] - '0'; const int64_t sd = i < 2 ? g : (i == 2 ? 2 * g : 4 * g);
     cnt = sd * sd * D;
     if (cnt > capacity) return OVM_ERR_CAPACITY;
-    return unsplit(pl.FEAT[i], (int)sd, (int)D, (int)D, false, dst, Img(), s) ? OVM_ERR_HIP : cnt;
+    return unsplit(pl.FEAT[i], (int)sd, (int)D, (int)D, false, dst, SplitImg(), s) ? OVM_ERR_HIP : cnt;
   } else if (n.size() == 5 && n.compare(0, 4, "neck") == 0 && n[4] >= '0' && n[4] <= '4') {
     const int i = n[4] - '0'; src = pl.NECK[i]; cnt = (int64_t)m->side[i] * m->side[i] * F;
   } else if (n == "fused") { src = pl.FUSED; cnt = (int64_t)m->side[4] * m->side[4] * F; }

@@ -324,7 +324,7 @@ __global__ void maxpool2_kernel(const half_t* __restrict__ Ihi, const half_t* __
     if (Ilo) l = *(const half4*)(Ilo + off);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const float v = (float)h[q] + (float)l[q] * kLoInv;
+      const float v = (float)h[q] + (float)l[q];
       if (t == 0 || v > best[q]) { best[q] = v; bh[q] = h[q]; bl[q] = l[q]; }
     }
   }

@@ -19,22 +19,21 @@
 #include <memory>
 #include <array>
 #include <string>
-#include <unordered_map>
 #include <vector>
 #include "../../include/ovm3d.h"
 #include "det2d.hpp"
 #include "gdino.hpp"
 #include "dec_chain.hpp"
 #include "kernels.hpp"
+#include "loader.hpp"
 
 using namespace ovm;
 
 namespace {
 
-struct Lin {                       // packed nn.Linear: split-fp16 weight image (gemm.hpp layout) + fp32 bias
-  half_t* hi = nullptr; half_t* lo = nullptr; float* bias = nullptr;
+struct Lin : PackedLin {
   half_t* frag = nullptr;          // decoder weights only: the same image in MFMA-fragment order (make_frag), for the row-chain kernels
-  int N = 0, K = 0, Kpad = 0;
+  std::vector<half_t> img;         // host copy of the image, kept from packing until make_frag has cut the fragment copy from it
 };
 struct Ln { float* g = nullptr; float* b = nullptr; };
 struct SplitBuf { half_t* hi = nullptr; half_t* lo = nullptr; int ld = 0; bool il = false; };   // il: one interleaved image [row][k/32][hi 32 | lo 32], lo = hi + 32, ld = 2 K
@@ -74,14 +73,9 @@ using ovm::g_gdino_gemm256;
 using ovm::g_gdino_ffn_split;
 using ovm::g_gdino_swin_fused;
 
-constexpr size_t kSlabBytes = (size_t)256 << 20;
-
-struct OvmGdino {
+struct OvmGdino : ovm::Loader {
   OvmGdinoConfig cfg;
-  int device = 0, npass = 3;
-  std::string err;
-  std::vector<void*> allocs;
-  char* slab = nullptr; size_t slab_off = 0, slab_cap = 0;      // current slab of dmal()
+  int device = 0;
   float* sine_dim_t = nullptr;                                 // [d_model / 4] frequency table of the decoder's sine embedding (dec_chain.hip)
   // ---- weights
   float *word = nullptr, *posemb = nullptr, *typemb = nullptr; Ln emb_ln; int bertD = 0, n_pos = 0, vocab = 0;
@@ -112,88 +106,9 @@ struct OvmGdino {
 
 namespace {
 
-#define GCHECK(g, call)                                                                     \
-  do {                                                                                     \
-    hipError_t e_ = (call);                                                                \
-    if (e_ != hipSuccess) { (g)->err = std::string(#call) + ": " + hipGetErrorString(e_); return OVM_ERR_HIP; } \
-  } while (0)
-#define RCHECK(g, call)                                                                     \
-  do {                                                                                     \
-    int r_ = (call);                                                                       \
-    if (r_ != OVM_OK) { if ((g)->err.empty()) (g)->err = std::string(#call) + " failed (" + std::to_string(r_) + ")"; return r_; } \
-  } while (0)
-
-typedef std::unordered_map<std::string, const OvmTensor*> WMap;
-
-int64_t numel(const OvmTensor* t) { int64_t n = 1; for (int i = 0; i < t->ndim; ++i) n *= t->shape[i]; return n; }
-
-int get(OvmGdino* g, const WMap& wm, const std::string& name, const OvmTensor** out) {
-  auto it = wm.find(name);
-  if (it == wm.end()) { g->err = "missing weight: " + name; return OVM_ERR_MISSING_WEIGHT; }
-  *out = it->second;
-  return OVM_OK;
-}
-
-// Weights and tables live in a few large slabs, not in one hipMalloc each: ~700 separate allocations scatter the checkpoint over as
-// many small VM mappings, and the latency-bound kernels of this branch (every workgroup touches every page of a weight matrix once)
-// then pay an address-translation miss per 4-KiB page; a slab is mapped with large fragments.
-template <typename T>
-int dmal(OvmGdino* g, T** p, size_t count) {
-  size_t bytes = count * sizeof(T); if (bytes == 0) bytes = 16;
-  bytes = (bytes + 255) & ~(size_t)255;
-  if (g->slab_off + bytes > g->slab_cap) {
-    const size_t cap = bytes > kSlabBytes ? bytes : kSlabBytes;
-    void* q = nullptr;
-    GCHECK(g, hipMalloc(&q, cap));
-    g->allocs.push_back(q);
-    g->slab = (char*)q; g->slab_cap = cap; g->slab_off = 0;
-  }
-  *p = (T*)(g->slab + g->slab_off);
-  g->slab_off += bytes;
-  return OVM_OK;
-}
-
-int up_vec(OvmGdino* g, const std::vector<float>& v, float** out) {
-  RCHECK(g, dmal(g, out, v.size()));
-  GCHECK(g, hipMemcpy(*out, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
-  return OVM_OK;
-}
-int up_f32(OvmGdino* g, const WMap& wm, const std::string& name, float** out, int64_t expect = -1) {
-  const OvmTensor* t; RCHECK(g, get(g, wm, name, &t));
-  if (expect >= 0 && numel(t) != expect) { g->err = "bad shape: " + name; return OVM_ERR_SHAPE; }
-  RCHECK(g, dmal(g, out, (size_t)numel(t)));
-  GCHECK(g, hipMemcpy(*out, t->data, (size_t)numel(t) * sizeof(float), hipMemcpyHostToDevice));
-  return OVM_OK;
-}
-int up_ln(OvmGdino* g, const WMap& wm, const std::string& prefix, Ln* ln) {
-  RCHECK(g, up_f32(g, wm, prefix + ".weight", &ln->g));
-  return up_f32(g, wm, prefix + ".bias", &ln->b);
-}
-
-// host rows [N][K] (+ bias [N] or empty) -> device weight image of gemm.hpp / gemm_small.hip
-int pack_host(OvmGdino* g, const std::vector<float>& w, const std::vector<float>& bias, int N, int K, Lin* out) {
-  const int Kpad = (K + 63) / 64 * 64, Npad = (N + 127) / 128 * 128;
-  const bool il = g->npass == 3;
-  const size_t ld = il ? (size_t)2 * Kpad : (size_t)Kpad;
-  std::vector<half_t> buf((size_t)Npad * ld, (half_t)0.f);
-  for (int n = 0; n < N; ++n)
-    for (int k = 0; k < K; ++k) {
-      const float x = w[(size_t)n * K + k];
-      const half_t hh = (half_t)x;
-      if (il) {
-        const size_t o = (size_t)n * ld + (size_t)(k >> 5) * 64 + (k & 31);
-        buf[o] = hh; buf[o + 32] = (half_t)(x - (float)hh);
-      } else {
-        buf[(size_t)n * ld + k] = hh;
-      }
-    }
-  RCHECK(g, dmal(g, &out->hi, buf.size()));
-  GCHECK(g, hipMemcpy(out->hi, buf.data(), buf.size() * sizeof(half_t), hipMemcpyHostToDevice));
-  out->lo = il ? out->hi + 32 : nullptr;
-  out->N = N; out->K = K; out->Kpad = Kpad;
-  out->bias = nullptr;
-  if (!bias.empty()) RCHECK(g, up_vec(g, bias, &out->bias));
-  return OVM_OK;
+int up_ln(OvmGdino* g, const WeightMap& wm, const std::string& prefix, Ln* ln) {
+  OVM_TRY(g, upload_weight(g, wm, prefix + ".weight", -1, &ln->g));
+  return upload_weight(g, wm, prefix + ".bias", -1, &ln->b);
 }
 
 // The row-chain kernels (dec_chain.hip) feed weight fragments from global memory straight into v_mfma_f32_16x16x32_f16: lane l wants
@@ -202,11 +117,12 @@ int pack_host(OvmGdino* g, const std::vector<float>& w, const std::vector<float>
 // the image in the order the lanes consume it: [tile of 16 rows][k-step of 32][hi | lo][lane 0..63][8 halves] - one load
 // instruction = 1 KiB contiguous.
 int make_frag(OvmGdino* g, Lin* w) {
-  if (g->npass != 3 || !w->hi) return OVM_OK;
-  const int Npad = (w->N + 127) / 128 * 128, KS = w->Kpad / 32;
+  std::vector<half_t> src; src.swap(w->img);          // released on return
+  if (g->precision != 3 || !w->hi) return OVM_OK;
+  const int Npad = npad128(w->N), KS = w->Kpad / 32;
   const size_t n = (size_t)Npad * 2 * w->Kpad;
-  std::vector<half_t> src(n), dst(n);
-  GCHECK(g, hipMemcpy(src.data(), w->hi, n * sizeof(half_t), hipMemcpyDeviceToHost));
+  if (src.size() != n) { g->err = "make_frag: the weight was packed without keeping its host image"; return OVM_ERR_INVALID; }
+  std::vector<half_t> dst(n);
   for (int tile = 0; tile < Npad / 16; ++tile)
     for (int ks = 0; ks < KS; ++ks)
       for (int part = 0; part < 2; ++part)
@@ -215,68 +131,43 @@ int make_frag(OvmGdino* g, Lin* w) {
           const size_t dof = ((((size_t)tile * KS + ks) * 2 + part) * 64 + lane) * 8;
           for (int e = 0; e < 8; ++e) dst[dof + e] = src[so + e];
         }
-  RCHECK(g, dmal(g, &w->frag, n));
-  GCHECK(g, hipMemcpy(w->frag, dst.data(), n * sizeof(half_t), hipMemcpyHostToDevice));
+  OVM_TRY(g, g->alloc(&w->frag, n));
+  OVM_HIP(g, hipMemcpy(w->frag, dst.data(), n * sizeof(half_t), hipMemcpyHostToDevice));
   return OVM_OK;
 }
 
-// concatenation along N of several nn.Linear (weight [n_i][K], optional bias), optional per-row scale of every part
-int pack_cat(OvmGdino* g, const WMap& wm, const std::vector<std::string>& prefixes, Lin* out, bool with_bias = true,
-             const float* row_scale = nullptr) {
-  std::vector<float> w, b;
-  int K = -1, N = 0;
-  for (auto& p : prefixes) {
-    const OvmTensor* t; RCHECK(g, get(g, wm, p + ".weight", &t));
-    const int n = (int)t->shape[0]; const int k = (int)(numel(t) / n);
-    if (K < 0) K = k; else if (K != k) { g->err = "pack_cat: K mismatch at " + p; return OVM_ERR_SHAPE; }
-    w.insert(w.end(), t->data, t->data + (size_t)n * k);
-    if (with_bias) {
-      const OvmTensor* bt; RCHECK(g, get(g, wm, p + ".bias", &bt));
-      b.insert(b.end(), bt->data, bt->data + n);
-    }
-    N += n;
-  }
-  if (row_scale) {
-    for (int n = 0; n < N; ++n) {
-      for (int k = 0; k < K; ++k) w[(size_t)n * K + k] *= row_scale[n];
-      if (with_bias) b[n] *= row_scale[n];
-    }
-  }
-  return pack_host(g, w, b, N, K, out);
+// concatenation along N of several nn.Linear, shapes read off the checkpoint; keep: a make_frag of this weight follows
+int pack_cat(OvmGdino* g, const WeightMap& wm, const std::vector<std::string>& prefixes, Lin* out, bool with_bias = true,
+             const float* row_scale = nullptr, bool keep = false) {
+  std::vector<std::pair<std::string, int>> parts;
+  for (auto& p : prefixes) parts.push_back({p, -1});
+  return pack_concat(g, wm, parts, -1, out, with_bias, row_scale, keep ? &out->img : nullptr);
 }
-int pack_lin(OvmGdino* g, const WMap& wm, const std::string& prefix, Lin* out, bool with_bias = true) {
-  return pack_cat(g, wm, {prefix}, out, with_bias);
+int pack_lin(OvmGdino* g, const WeightMap& wm, const std::string& prefix, Lin* out, bool with_bias = true, bool keep = false) {
+  return pack_cat(g, wm, {prefix}, out, with_bias, nullptr, keep);
 }
-// conv weight [Cout][Cin][k][k] -> rows [Cout][(ky*k + kx)*Cin + c]
-int pack_conv(OvmGdino* g, const WMap& wm, const std::string& prefix, Lin* out, int* ksize) {
-  const OvmTensor* t; RCHECK(g, get(g, wm, prefix + ".weight", &t));
-  const OvmTensor* bt; RCHECK(g, get(g, wm, prefix + ".bias", &bt));
+// square convolution, shape read off the checkpoint
+int pack_conv(OvmGdino* g, const WeightMap& wm, const std::string& prefix, Lin* out, int* ksize) {
+  const OvmTensor* t; OVM_TRY(g, find_weight(g, wm, prefix + ".weight", -1, &t));
   if (t->ndim != 4) { g->err = "conv weight must be 4-d: " + prefix; return OVM_ERR_SHAPE; }
-  const int Co = (int)t->shape[0], Ci = (int)t->shape[1], kh = (int)t->shape[2], kw = (int)t->shape[3];
-  std::vector<float> w((size_t)Co * Ci * kh * kw);
-  for (int o = 0; o < Co; ++o)
-    for (int c = 0; c < Ci; ++c)
-      for (int y = 0; y < kh; ++y)
-        for (int x = 0; x < kw; ++x) w[((size_t)o * kh * kw + y * kw + x) * Ci + c] = t->data[(((size_t)o * Ci + c) * kh + y) * kw + x];
-  std::vector<float> b(bt->data, bt->data + Co);
-  if (ksize) *ksize = kh;
-  return pack_host(g, w, b, Co, Ci * kh * kw, out);
+  if (ksize) *ksize = (int)t->shape[2];
+  return ovm::pack_conv(g, wm, prefix, (int)t->shape[0], (int)t->shape[1], (int)t->shape[2], BIAS_REQUIRED, out);
 }
 
-int load_mha(OvmGdino* g, const WMap& wm, const std::string& p, int heads, Mha* m, bool cross) {
+int load_mha(OvmGdino* g, const WeightMap& wm, const std::string& p, int heads, Mha* m, bool cross, bool keep = false) {
   m->heads = heads;
   if (cross) {
-    RCHECK(g, pack_lin(g, wm, p + "query", &m->q));
+    OVM_TRY(g, pack_lin(g, wm, p + "query", &m->q, true, keep));
   } else {
-    RCHECK(g, pack_cat(g, wm, {p + "query", p + "key"}, &m->qk));
-    RCHECK(g, pack_lin(g, wm, p + "value", &m->v));
+    OVM_TRY(g, pack_cat(g, wm, {p + "query", p + "key"}, &m->qk, true, nullptr, keep));
+    OVM_TRY(g, pack_lin(g, wm, p + "value", &m->v, true, keep));
   }
-  return pack_lin(g, wm, p + "out_proj", &m->out);
+  return pack_lin(g, wm, p + "out_proj", &m->out, true, keep);
 }
-int load_msda(OvmGdino* g, const WMap& wm, const std::string& p, MsdaW* m, bool with_value) {
-  RCHECK(g, pack_cat(g, wm, {p + "sampling_offsets", p + "attention_weights"}, &m->offw));
-  if (with_value) RCHECK(g, pack_lin(g, wm, p + "value_proj", &m->value));
-  return pack_lin(g, wm, p + "output_proj", &m->out);
+int load_msda(OvmGdino* g, const WeightMap& wm, const std::string& p, MsdaW* m, bool with_value, bool keep = false) {
+  OVM_TRY(g, pack_cat(g, wm, {p + "sampling_offsets", p + "attention_weights"}, &m->offw, true, nullptr, keep));
+  if (with_value) OVM_TRY(g, pack_lin(g, wm, p + "value_proj", &m->value, true, keep));
+  return pack_lin(g, wm, p + "output_proj", &m->out, true, keep);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -320,9 +211,9 @@ template <typename T>
 int pup(OvmGdino* g, Plan* pl, const std::vector<T>& v, T** out) {
   void* q = nullptr;
   size_t bytes = v.size() * sizeof(T); if (bytes == 0) bytes = 16;
-  GCHECK(g, hipMalloc(&q, bytes));
+  OVM_HIP(g, hipMalloc(&q, bytes));
   pl->allocs.push_back(q); pl->bytes += bytes;
-  if (!v.empty()) GCHECK(g, hipMemcpy(q, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  if (!v.empty()) OVM_HIP(g, hipMemcpy(q, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
   *out = (T*)q;
   return OVM_OK;
 }
@@ -330,7 +221,7 @@ template <typename T>
 int pal(OvmGdino* g, Plan* pl, T** out, size_t count) {
   void* q = nullptr;
   size_t bytes = count * sizeof(T); if (bytes == 0) bytes = 16;
-  GCHECK(g, hipMalloc(&q, bytes));
+  OVM_HIP(g, hipMalloc(&q, bytes));
   pl->allocs.push_back(q); pl->bytes += bytes;
   *out = (T*)q;
   return OVM_OK;
@@ -425,17 +316,17 @@ int build_plan(OvmGdino* g, int H, int W, const std::vector<int>& ids, const std
     if (ids[t] < 0 || ids[t] >= g->vocab) { g->err = "token id out of the vocabulary"; return OVM_ERR_INVALID; }
     if (pids[t] < 0 || pids[t] >= g->n_pos) { g->err = "position id out of range"; return OVM_ERR_INVALID; }
   }
-  RCHECK(g, pup(g, pl, ids, &pl->d_ids));
-  RCHECK(g, pup(g, pl, pids, &pl->d_pids));
+  OVM_TRY(g, pup(g, pl, ids, &pl->d_ids));
+  OVM_TRY(g, pup(g, pl, pids, &pl->d_pids));
   std::vector<float> bias((size_t)T * T);
   for (size_t i = 0; i < bias.size(); ++i) bias[i] = mask[i] ? 0.f : -3.4028234663852886e38f;     // torch.finfo(float32).min
-  RCHECK(g, pup(g, pl, bias, &pl->text_bias));
+  OVM_TRY(g, pup(g, pl, bias, &pl->text_bias));
   {
     std::vector<float> pf(T); for (int t = 0; t < T; ++t) pf[t] = (float)pids[t];
-    float* d_pf; RCHECK(g, pup(g, pl, pf, &d_pf));
-    RCHECK(g, pal(g, pl, &pl->text_pos, (size_t)T * D));
-    RCHECK(g, ovm_g_sine_embed(d_pf, T, 1, D, 10000.0f, pl->text_pos, nullptr));
-    GCHECK(g, hipDeviceSynchronize());
+    float* d_pf; OVM_TRY(g, pup(g, pl, pf, &d_pf));
+    OVM_TRY(g, pal(g, pl, &pl->text_pos, (size_t)T * D));
+    OVM_TRY(g, ovm_g_sine_embed(d_pf, T, 1, D, 10000.0f, pl->text_pos, nullptr));
+    OVM_HIP(g, hipDeviceSynchronize());
   }
   // ---- swin geometry
   const int P = 4, ws = c.swin_window;
@@ -449,7 +340,7 @@ int build_plan(OvmGdino* g, int H, int W, const std::vector<int>& ids, const std
             const int y = oy * P + py, x = ox * P + px;
             pm[((size_t)oy * pl->Wp + ox) * P * P + py * P + px] = (y < H && x < W) ? y * W + x : -1;
           }
-    RCHECK(g, pup(g, pl, pm, &pl->pe_map));
+    OVM_TRY(g, pup(g, pl, pm, &pl->pe_map));
   }
   int h = pl->Hp, w = pl->Wp;
   pl->geo.resize(g->stages.size());
@@ -461,8 +352,8 @@ int build_plan(OvmGdino* g, int H, int W, const std::vector<int>& ids, const std
       std::vector<int> win; std::vector<float> mk; int nW;
       window_maps(h, w, ws, sh ? ws / 2 : 0, &win, &mk, &nW);
       ge.wm[sh].nW = nW;
-      RCHECK(g, pup(g, pl, win, &ge.wm[sh].win));
-      if (!mk.empty()) RCHECK(g, pup(g, pl, mk, &ge.wm[sh].mask));
+      OVM_TRY(g, pup(g, pl, win, &ge.wm[sh].win));
+      if (!mk.empty()) OVM_TRY(g, pup(g, pl, mk, &ge.wm[sh].mask));
     }
     if (g->stages[s].has_out) feat_hw.push_back({h, w});
     if (g->stages[s].has_red) {
@@ -477,7 +368,7 @@ int build_plan(OvmGdino* g, int H, int W, const std::vector<int>& ids, const std
               mm[((size_t)oy * w2 + ox) * 4 + k++] = (y < h && x < w) ? y * w + x : -1;
             }
         }
-      RCHECK(g, pup(g, pl, mm, &ge.merge));
+      OVM_TRY(g, pup(g, pl, mm, &ge.merge));
       ge.h2 = h2; ge.w2 = w2;
       h = h2; w = w2;
     }
@@ -500,7 +391,7 @@ int build_plan(OvmGdino* g, int H, int W, const std::vector<int>& ids, const std
                 const int y = 2 * oy + ky - 1, x = 2 * ox + kx - 1;
                 cm[((size_t)oy * w2 + ox) * 9 + ky * 3 + kx] = (y >= 0 && y < lh && x >= 0 && x < lw) ? y * lw + x : -1;
               }
-        RCHECK(g, pup(g, pl, cm, &pl->conv_map));
+        OVM_TRY(g, pup(g, pl, cm, &pl->conv_map));
         pl->conv_h = lh; pl->conv_w = lw;
       } else { g->err = "more than one extra feature level is not supported"; return OVM_ERR_SHAPE; }
       lh = h2; lw = w2;
@@ -531,22 +422,22 @@ int build_plan(OvmGdino* g, int H, int W, const std::vector<int>& ids, const std
         valid[pl->lstart[l] + i] = ok ? pl->lstart[l] + i : -1;
       }
     }
-    RCHECK(g, pup(g, pl, pos, &pl->pos));
-    RCHECK(g, pup(g, pl, ref, &pl->ref));
-    RCHECK(g, pup(g, pl, prop, &pl->prop_logit));
-    RCHECK(g, pup(g, pl, valid, &pl->valid_idx));
+    OVM_TRY(g, pup(g, pl, pos, &pl->pos));
+    OVM_TRY(g, pup(g, pl, ref, &pl->ref));
+    OVM_TRY(g, pup(g, pl, prop, &pl->prop_logit));
+    OVM_TRY(g, pup(g, pl, valid, &pl->valid_idx));
   }
   if (S < c.num_queries) {       // torch.topk in the upstream two-stage selection raises the same way
     g->err = "selected index k out of range: " + std::to_string(S) + " encoder tokens < " + std::to_string(c.num_queries) + " queries (image too small)";
     return OVM_ERR_SHAPE;
   }
-  RCHECK(g, pal(g, pl, &pl->img, (size_t)H * W * 3));
+  OVM_TRY(g, pal(g, pl, &pl->img, (size_t)H * W * 3));
   pl->topk_N = 2048; while (pl->topk_N < S) pl->topk_N <<= 1;      // the bitonic sort's minimum length is one 2048-key tile
-  RCHECK(g, pal(g, pl, &pl->topk_keys, (size_t)pl->topk_N));
-  RCHECK(g, pal(g, pl, &pl->out_logits, (size_t)c.num_queries * c.max_text_len));
-  RCHECK(g, pal(g, pl, &pl->out_boxes, (size_t)c.num_queries * 4));
+  OVM_TRY(g, pal(g, pl, &pl->topk_keys, (size_t)pl->topk_N));
+  OVM_TRY(g, pal(g, pl, &pl->out_logits, (size_t)c.num_queries * c.max_text_len));
+  OVM_TRY(g, pal(g, pl, &pl->out_boxes, (size_t)c.num_queries * 4));
   pl->gemm_ws_cap = (size_t)64 << 20;
-  RCHECK(g, pal(g, pl, (char**)&pl->gemm_ws, pl->gemm_ws_cap));
+  OVM_TRY(g, pal(g, pl, (char**)&pl->gemm_ws, pl->gemm_ws_cap));
   guard.release();
   *out = pl;
   return OVM_OK;
@@ -601,7 +492,7 @@ struct Run {
     SplitBuf b; b.ld = (K + 63) / 64 * 64;
     const size_t bytes = rows * b.ld * sizeof(half_t);
     b.hi = (half_t*)alloc(bytes);
-    b.lo = g->npass == 3 ? (half_t*)alloc(bytes) : nullptr;
+    b.lo = g->precision == 3 ? (half_t*)alloc(bytes) : nullptr;
     if (b.ld != K && go()) {
       if (hipMemsetAsync(b.hi, 0, bytes, s) != hipSuccess) fail(OVM_ERR_HIP, "memset");
       if (b.lo && hipMemsetAsync(b.lo, 0, bytes, s) != hipSuccess) fail(OVM_ERR_HIP, "memset");
@@ -612,7 +503,7 @@ struct Run {
   // over K <= 256 (752 / 564 / 556 tiles of 128 x 128, i.e. 2-3 rounds of a kernel whose per-round cost hardly depends on K) are one
   // round of 256 x 256 tiles there. Falls back to planar rows when the kernel cannot take the shape (one-pass precision, K % 32).
   SplitBuf split_for256(size_t rows, int K) {
-    if (g->npass != 3 || K % 32 || !g_gdino_gemm256) return split(rows, K);
+    if (g->precision != 3 || K % 32 || !g_gdino_gemm256) return split(rows, K);
     SplitBuf b; b.il = true; b.ld = 2 * K;
     b.hi = (half_t*)alloc(rows * b.ld * sizeof(half_t)); b.lo = b.hi ? b.hi + 32 : nullptr;
     return b;
@@ -636,15 +527,15 @@ struct Run {
   }
   void gemm(const GemmParams& p, int epi) {
     if (!go()) return;
-    if (p.a_il && gemm256_supported(p, g->npass)) chk(launch_gemm256(p, epi, 1, s), "gemm256");
-    else chk(launch_gemm(p, g->npass, epi, A_ROWMAJOR, s), "gemm");
+    if (p.a_il && gemm256_supported(p, g->precision)) chk(launch_gemm256(p, epi, 1, s), "gemm256");
+    else chk(launch_gemm(p, g->precision, epi, A_ROWMAJOR, s), "gemm");
   }
 
   // small / mid GEMM reading fp32 activations directly (gemm_small.hip): y = act((A + A2) W^T + b) (+ R)
   void lin(const float* A, const float* A2, int lda, int M, const Lin& W, int act, const float* R, int ldr, float* C, int ldc) {
     if (!go() || M <= 0) return;
     if (!gemm_small_supported(A, lda, W.K) || (A2 && (((uintptr_t)A2) & 15))) { fail(OVM_ERR_SHAPE, "lin: unaligned fp32 operand"); return; }
-    chk(launch_gemm_small_ex(A, A2, lda, M, W.K, W.hi, W.lo, W.N, W.Kpad, W.bias, act, R, ldr, C, ldc, g->npass, ws, ws_cap, s),
+    chk(launch_gemm_small_ex(A, A2, lda, M, W.K, W.hi, W.lo, W.N, W.Kpad, W.bias, act, R, ldr, C, ldc, g->precision, ws, ws_cap, s),
         "lin");
   }
   void ln(const float* x, int M, int D, const Ln& w, float eps, const float* res, float* y, SplitBuf* sp = nullptr) {
@@ -759,7 +650,7 @@ int forward_impl(Run& r) {
         r.rowop(p);
       }
       SplitBuf ctx = r.split((size_t)M, C);
-      const bool fused = g_gdino_swin_fused && blk.qkv.frag && dh == 32 && swin_qkv_attn_supported(C, nh, ws, g->npass) && xw.ld % 8 == 0;
+      const bool fused = g_gdino_swin_fused && blk.qkv.frag && dh == 32 && swin_qkv_attn_supported(C, nh, ws, g->precision) && xw.ld % 8 == 0;
       if (fused) {
         // qkv projection inside the window kernel (one workgroup per (window, head)): no [M][3 C] fp32 round trip, one launch less
         SwinQkvAttnParams a; memset(&a, 0, sizeof(a));
@@ -951,7 +842,7 @@ int forward_impl(Run& r) {
     float* coord = r.f32((size_t)S * 4);
     { GemmParams q = r.gp(h2, S, g->enc_bbox[2]); q.C = coord; q.ldc = 4; r.gemm(q, EPI_STORE); }
     if (r.go()) r.chk(launch_select_ref(coord, 4, pl->prop_logit, sel, Q, ref, s), "select_ref");
-    if (r.go() && g->force_topk) GCHECK(g, hipMemcpyAsync(topk, g->force_topk, sizeof(int) * Q, hipMemcpyDeviceToDevice, s));
+    if (r.go() && g->force_topk) OVM_HIP(g, hipMemcpyAsync(topk, g->force_topk, sizeof(int) * Q, hipMemcpyDeviceToDevice, s));
     r.release(mk);
   }
   r.tap("topk", topk, Q);
@@ -975,7 +866,7 @@ int forward_impl(Run& r) {
     }
     float* val_all = r.f32((size_t)S * NL * D);
     { GemmParams q = r.gp(vsp, S, g->dec_value); q.C = val_all; q.ldc = NL * D; r.gemm(q, EPI_STORE); }
-    if (r.go()) GCHECK(g, hipMemcpyAsync(hs, g->tgt, sizeof(float) * (size_t)Q * D, hipMemcpyDeviceToDevice, s));
+    if (r.go()) OVM_HIP(g, hipMemcpyAsync(hs, g->tgt, sizeof(float) * (size_t)Q * D, hipMemcpyDeviceToDevice, s));
     float* sine = r.f32((size_t)Q * 2 * D);
     float* qh = r.f32((size_t)Q * D); float* qpos = r.f32((size_t)Q * D);
     float* qk = r.f32((size_t)Q * 2 * D); float* vq = r.f32((size_t)Q * D); float* ctx = r.f32((size_t)Q * D);
@@ -989,7 +880,7 @@ int forward_impl(Run& r) {
     // Row-chain form of a layer (dec_chain.hip): everything but the query self-attention is local to a query row, so a workgroup
     // walks 16 rows through the whole layer in LDS - 3 launches per layer instead of ~35 (ovm_tune_set "gdino_dec_chain" 0: the
     // launch-per-op sequence below, kept as the cross-check).
-    const bool chain = g_gdino_dec_chain && dec_chain_supported(D, c.heads, c.ffn_dim, c.n_levels, c.n_points, T, g->npass);
+    const bool chain = g_gdino_dec_chain && dec_chain_supported(D, c.heads, c.ffn_dim, c.n_levels, c.n_points, T, g->precision);
     auto cl = [](const Lin& w) { return ChainLin{w.frag, w.bias, w.N, w.K, w.Kpad}; };
     auto cn = [](const Ln& w) { return ChainLn{w.g, w.b}; };
     const int ffn_chunks = c.ffn_dim > 512 ? c.ffn_dim / 512 : 1;
@@ -1037,7 +928,7 @@ int forward_impl(Run& r) {
       mha_core(r, qk, 2 * D, qk + D, 2 * D, vq, D, Q, Q, ly.sa.heads, D, nullptr, 0, ctx, D);
       if (r.go()) r.chk(launch_dec_chain(dp, 1, s), "dec_chain_b");
       if (ffn_split && r.go()) r.chk(launch_dec_chain(dp, 2, s), "dec_chain_c");
-      if (i == NL - 1) { if (r.go()) GCHECK(g, hipMemcpyAsync(last_ref, rf, sizeof(float) * (size_t)Q * 4, hipMemcpyDeviceToDevice, s)); }
+      if (i == NL - 1) { if (r.go()) OVM_HIP(g, hipMemcpyAsync(last_ref, rf, sizeof(float) * (size_t)Q * 4, hipMemcpyDeviceToDevice, s)); }
       r.tap(("dec_hs" + std::to_string(i)).c_str(), hs, (int64_t)Q * D);
       if (i + 1 < NL) cur ^= 1;
     }
@@ -1067,7 +958,7 @@ int forward_impl(Run& r) {
       r.lin(hs, nullptr, D, Q, ly.fc1, 1, nullptr, 0, ffb, c.ffn_dim);
       r.lin(ffb, nullptr, c.ffn_dim, Q, ly.fc2, 0, hs, D, pre, D);
       r.ln(pre, Q, D, ly.ln4, eps, nullptr, hs);
-      if (i == NL - 1) { if (r.go()) GCHECK(g, hipMemcpyAsync(last_ref, rf, sizeof(float) * (size_t)Q * 4, hipMemcpyDeviceToDevice, s)); }
+      if (i == NL - 1) { if (r.go()) OVM_HIP(g, hipMemcpyAsync(last_ref, rf, sizeof(float) * (size_t)Q * 4, hipMemcpyDeviceToDevice, s)); }
       r.tap(("dec_hs" + std::to_string(i)).c_str(), hs, (int64_t)Q * D);
       // iterative box refinement (the update after the last layer is unused)
       if (i + 1 < NL) {
@@ -1106,7 +997,11 @@ int ovm_gdino_create(const OvmGdinoConfig* cfg, const OvmTensor* weights, int32_
   if (!cfg || !weights || !out) return OVM_ERR_INVALID;
   OvmGdino* g = new OvmGdino();
   *out = g;                                      // returned even on failure so that ovm_gdino_last_error can be read; destroy it
-  g->cfg = *cfg; g->device = device; g->npass = cfg->precision == 1 ? 1 : 3;
+  g->cfg = *cfg; g->device = device; g->precision = cfg->precision == 1 ? 1 : 3;
+  // Weights and tables live in a few large slabs, not in one hipMalloc each: ~700 separate allocations scatter the checkpoint over as
+  // many small VM mappings, and the latency-bound kernels of this branch (every workgroup touches every page of a weight matrix once)
+  // then pay an address-translation miss per 4-KiB page; a slab is mapped with large fragments.
+  g->policy = ALLOC_SLAB; g->k_align = 64;
   g->graphs_enabled = cfg->use_graphs;
   g->branches = g_gdino_branches;
   {
@@ -1119,40 +1014,39 @@ int ovm_gdino_create(const OvmGdinoConfig* cfg, const OvmTensor* weights, int32_
   }
   const OvmGdinoConfig& c = g->cfg;
   if (c.d_model % c.heads || c.n_levels > 8 || c.n_levels < 1 || c.swin_window <= 0) { g->err = "bad GroundingDINO config"; return OVM_ERR_INVALID; }
-  GCHECK(g, hipSetDevice(device));
-  WMap wm;
-  for (int i = 0; i < n_weights; ++i) wm[weights[i].name] = &weights[i];
+  OVM_HIP(g, hipSetDevice(device));
+  const WeightMap wm(weights, n_weights);
   const std::string M = "model.";
   // ---- BERT
   {
     const std::string e = M + "text_backbone.embeddings.";
-    const OvmTensor* t; RCHECK(g, get(g, wm, e + "word_embeddings.weight", &t));
+    const OvmTensor* t; OVM_TRY(g, find_weight(g, wm, e + "word_embeddings.weight", -1, &t));
     g->vocab = (int)t->shape[0]; g->bertD = (int)t->shape[1];
-    RCHECK(g, up_f32(g, wm, e + "word_embeddings.weight", &g->word));
-    RCHECK(g, get(g, wm, e + "position_embeddings.weight", &t)); g->n_pos = (int)t->shape[0];
-    RCHECK(g, up_f32(g, wm, e + "position_embeddings.weight", &g->posemb));
-    RCHECK(g, up_f32(g, wm, e + "token_type_embeddings.weight", &g->typemb));
-    RCHECK(g, up_ln(g, wm, e + "LayerNorm", &g->emb_ln));
+    OVM_TRY(g, upload_weight(g, wm, e + "word_embeddings.weight", -1, &g->word));
+    OVM_TRY(g, find_weight(g, wm, e + "position_embeddings.weight", -1, &t)); g->n_pos = (int)t->shape[0];
+    OVM_TRY(g, upload_weight(g, wm, e + "position_embeddings.weight", -1, &g->posemb));
+    OVM_TRY(g, upload_weight(g, wm, e + "token_type_embeddings.weight", -1, &g->typemb));
+    OVM_TRY(g, up_ln(g, wm, e + "LayerNorm", &g->emb_ln));
     for (int i = 0;; ++i) {
       const std::string p = M + "text_backbone.encoder.layer." + std::to_string(i) + ".";
-      if (!wm.count(p + "attention.self.query.weight")) break;
+      if (!wm.get(p + "attention.self.query.weight")) break;
       g->bert.emplace_back();
       BertLayer& ly = g->bert.back();
-      RCHECK(g, pack_cat(g, wm, {p + "attention.self.query", p + "attention.self.key", p + "attention.self.value"}, &ly.qkv));
-      RCHECK(g, pack_lin(g, wm, p + "attention.output.dense", &ly.ao));
-      RCHECK(g, up_ln(g, wm, p + "attention.output.LayerNorm", &ly.aln));
-      RCHECK(g, pack_lin(g, wm, p + "intermediate.dense", &ly.fi));
-      RCHECK(g, pack_lin(g, wm, p + "output.dense", &ly.fo));
-      RCHECK(g, up_ln(g, wm, p + "output.LayerNorm", &ly.oln));
+      OVM_TRY(g, pack_cat(g, wm, {p + "attention.self.query", p + "attention.self.key", p + "attention.self.value"}, &ly.qkv));
+      OVM_TRY(g, pack_lin(g, wm, p + "attention.output.dense", &ly.ao));
+      OVM_TRY(g, up_ln(g, wm, p + "attention.output.LayerNorm", &ly.aln));
+      OVM_TRY(g, pack_lin(g, wm, p + "intermediate.dense", &ly.fi));
+      OVM_TRY(g, pack_lin(g, wm, p + "output.dense", &ly.fo));
+      OVM_TRY(g, up_ln(g, wm, p + "output.LayerNorm", &ly.oln));
     }
     if (g->bertD % c.bert_heads) { g->err = "bert heads"; return OVM_ERR_INVALID; }
-    RCHECK(g, pack_lin(g, wm, M + "text_projection", &g->text_proj));
+    OVM_TRY(g, pack_lin(g, wm, M + "text_projection", &g->text_proj));
   }
   // ---- Swin
   {
     const std::string bb = M + "backbone.conv_encoder.model.", p = bb + "swin.";
-    RCHECK(g, pack_conv(g, wm, p + "embeddings.patch_embeddings.projection", &g->pe, nullptr));
-    RCHECK(g, up_ln(g, wm, p + "embeddings.norm", &g->pe_ln));
+    OVM_TRY(g, pack_conv(g, wm, p + "embeddings.patch_embeddings.projection", &g->pe, nullptr));
+    OVM_TRY(g, up_ln(g, wm, p + "embeddings.norm", &g->pe_ln));
     const int ws = c.swin_window, ws2 = ws * ws;
     std::vector<int> rel_index((size_t)ws2 * ws2);
     for (int a = 0; a < ws2; ++a)
@@ -1171,39 +1065,40 @@ int ovm_gdino_create(const OvmGdinoConfig* cfg, const OvmTensor* weights, int32_
         const std::string q = p + "encoder.layers." + std::to_string(s) + ".blocks." + std::to_string(b) + ".";
         st.blocks.emplace_back();
         SwinBlock& blk = st.blocks.back();
-        RCHECK(g, up_ln(g, wm, q + "layernorm_before", &blk.ln1));
-        RCHECK(g, up_ln(g, wm, q + "layernorm_after", &blk.ln2));
-        RCHECK(g, pack_cat(g, wm, {q + "attention.q_proj", q + "attention.k_proj", q + "attention.v_proj"}, &blk.qkv));
-        if (swin_qkv_attn_supported(C, st.nh, ws, g->npass)) RCHECK(g, make_frag(g, &blk.qkv));      // the window kernel projects q | k | v itself
-        RCHECK(g, pack_lin(g, wm, q + "attention.o_proj", &blk.proj));
-        RCHECK(g, pack_lin(g, wm, q + "mlp.fc1", &blk.fc1));
-        RCHECK(g, pack_lin(g, wm, q + "mlp.fc2", &blk.fc2));
-        const OvmTensor* tb; RCHECK(g, get(g, wm, q + "attention.relative_position_bias.relative_position_bias_table", &tb));
+        OVM_TRY(g, up_ln(g, wm, q + "layernorm_before", &blk.ln1));
+        OVM_TRY(g, up_ln(g, wm, q + "layernorm_after", &blk.ln2));
+        const bool fused = swin_qkv_attn_supported(C, st.nh, ws, g->precision);
+        OVM_TRY(g, pack_cat(g, wm, {q + "attention.q_proj", q + "attention.k_proj", q + "attention.v_proj"}, &blk.qkv, true, nullptr, fused));
+        if (fused) OVM_TRY(g, make_frag(g, &blk.qkv));      // the window kernel projects q | k | v itself
+        OVM_TRY(g, pack_lin(g, wm, q + "attention.o_proj", &blk.proj));
+        OVM_TRY(g, pack_lin(g, wm, q + "mlp.fc1", &blk.fc1));
+        OVM_TRY(g, pack_lin(g, wm, q + "mlp.fc2", &blk.fc2));
+        const OvmTensor* tb; OVM_TRY(g, find_weight(g, wm, q + "attention.relative_position_bias.relative_position_bias_table", -1, &tb));
         if (tb->shape[0] != (2 * ws - 1) * (2 * ws - 1) || tb->shape[1] != st.nh) { g->err = "relative position bias table shape"; return OVM_ERR_SHAPE; }
         std::vector<float> rb((size_t)st.nh * ws2 * ws2);
         for (int hh = 0; hh < st.nh; ++hh)
           for (size_t i = 0; i < (size_t)ws2 * ws2; ++i) rb[(size_t)hh * ws2 * ws2 + i] = tb->data[(size_t)rel_index[i] * st.nh + hh];
-        RCHECK(g, up_vec(g, rb, &blk.relbias));
+        OVM_TRY(g, upload_f32(g, rb.data(), rb.size(), &blk.relbias));
       }
       const std::string dk = p + "encoder.layers." + std::to_string(s) + ".downsample.";
-      if (wm.count(dk + "reduction.weight")) {
+      if (wm.get(dk + "reduction.weight")) {
         st.has_red = true;
-        RCHECK(g, pack_lin(g, wm, dk + "reduction", &st.red, false));
-        RCHECK(g, up_ln(g, wm, dk + "norm", &st.dn));
+        OVM_TRY(g, pack_lin(g, wm, dk + "reduction", &st.red, false));
+        OVM_TRY(g, up_ln(g, wm, dk + "norm", &st.dn));
       }
       const std::string nk = bb + "hidden_states_norms.stage" + std::to_string(s + 1);
-      if (wm.count(nk + ".weight")) { st.has_out = true; RCHECK(g, up_ln(g, wm, nk, &st.on)); }
+      if (wm.get(nk + ".weight")) { st.has_out = true; OVM_TRY(g, up_ln(g, wm, nk, &st.on)); }
       if (st.has_red) C *= 2;
     }
   }
   // ---- neck
   for (int l = 0; l < c.n_levels; ++l) {
     const std::string p = M + "input_proj_vision." + std::to_string(l);
-    RCHECK(g, pack_conv(g, wm, p + ".0", &g->inproj[l].w, &g->inproj[l].k));
-    RCHECK(g, up_ln(g, wm, p + ".1", &g->inproj[l].gn));
+    OVM_TRY(g, pack_conv(g, wm, p + ".0", &g->inproj[l].w, &g->inproj[l].k));
+    OVM_TRY(g, up_ln(g, wm, p + ".1", &g->inproj[l].gn));
   }
   {
-    const OvmTensor* t; RCHECK(g, get(g, wm, M + "level_embed", &t));
+    const OvmTensor* t; OVM_TRY(g, find_weight(g, wm, M + "level_embed", -1, &t));
     g->level_embed.assign(t->data, t->data + numel(t));
   }
   const int D = c.d_model;
@@ -1213,28 +1108,28 @@ int ovm_gdino_create(const OvmGdinoConfig* cfg, const OvmTensor* weights, int32_
     const std::string fu = p + "fusion_layer.", te = p + "text_enhancer_layer.", de = p + "deformable_layer.";
     g->enc.emplace_back();
     EncLayer& ly = g->enc.back();
-    RCHECK(g, up_ln(g, wm, fu + "layer_norm_vision", &ly.lnv));
-    RCHECK(g, up_ln(g, wm, fu + "layer_norm_text", &ly.lnt));
-    RCHECK(g, pack_cat(g, wm, {fu + "attn.vision_proj", fu + "attn.values_vision_proj"}, &ly.vqv));
-    RCHECK(g, pack_cat(g, wm, {fu + "attn.text_proj", fu + "attn.values_text_proj"}, &ly.tkv));
-    const OvmTensor *gv, *gt; RCHECK(g, get(g, wm, fu + "vision_param", &gv)); RCHECK(g, get(g, wm, fu + "text_param", &gt));
-    RCHECK(g, pack_cat(g, wm, {fu + "attn.out_vision_proj"}, &ly.ov, true, gv->data));     // layer scale folded into the projection
-    RCHECK(g, pack_cat(g, wm, {fu + "attn.out_text_proj"}, &ly.ot, true, gt->data));
-    RCHECK(g, load_mha(g, wm, te + "self_attn.", c.heads / 2, &ly.te, false));
-    RCHECK(g, up_ln(g, wm, te + "layer_norm_before", &ly.te_ln1));
-    RCHECK(g, up_ln(g, wm, te + "layer_norm_after", &ly.te_ln2));
-    RCHECK(g, pack_lin(g, wm, te + "fc1", &ly.te_fc1));
-    RCHECK(g, pack_lin(g, wm, te + "fc2", &ly.te_fc2));
-    RCHECK(g, load_msda(g, wm, de + "self_attn.", &ly.msda, true));
-    RCHECK(g, up_ln(g, wm, de + "self_attn_layer_norm", &ly.de_ln1));
-    RCHECK(g, up_ln(g, wm, de + "final_layer_norm", &ly.de_ln2));
-    RCHECK(g, pack_lin(g, wm, de + "fc1", &ly.de_fc1));
-    RCHECK(g, pack_lin(g, wm, de + "fc2", &ly.de_fc2));
+    OVM_TRY(g, up_ln(g, wm, fu + "layer_norm_vision", &ly.lnv));
+    OVM_TRY(g, up_ln(g, wm, fu + "layer_norm_text", &ly.lnt));
+    OVM_TRY(g, pack_cat(g, wm, {fu + "attn.vision_proj", fu + "attn.values_vision_proj"}, &ly.vqv));
+    OVM_TRY(g, pack_cat(g, wm, {fu + "attn.text_proj", fu + "attn.values_text_proj"}, &ly.tkv));
+    const OvmTensor *gv, *gt; OVM_TRY(g, find_weight(g, wm, fu + "vision_param", -1, &gv)); OVM_TRY(g, find_weight(g, wm, fu + "text_param", -1, &gt));
+    OVM_TRY(g, pack_cat(g, wm, {fu + "attn.out_vision_proj"}, &ly.ov, true, gv->data));     // layer scale folded into the projection
+    OVM_TRY(g, pack_cat(g, wm, {fu + "attn.out_text_proj"}, &ly.ot, true, gt->data));
+    OVM_TRY(g, load_mha(g, wm, te + "self_attn.", c.heads / 2, &ly.te, false));
+    OVM_TRY(g, up_ln(g, wm, te + "layer_norm_before", &ly.te_ln1));
+    OVM_TRY(g, up_ln(g, wm, te + "layer_norm_after", &ly.te_ln2));
+    OVM_TRY(g, pack_lin(g, wm, te + "fc1", &ly.te_fc1));
+    OVM_TRY(g, pack_lin(g, wm, te + "fc2", &ly.te_fc2));
+    OVM_TRY(g, load_msda(g, wm, de + "self_attn.", &ly.msda, true));
+    OVM_TRY(g, up_ln(g, wm, de + "self_attn_layer_norm", &ly.de_ln1));
+    OVM_TRY(g, up_ln(g, wm, de + "final_layer_norm", &ly.de_ln2));
+    OVM_TRY(g, pack_lin(g, wm, de + "fc1", &ly.de_fc1));
+    OVM_TRY(g, pack_lin(g, wm, de + "fc2", &ly.de_fc2));
   }
-  RCHECK(g, pack_lin(g, wm, M + "enc_output", &g->enc_output));
-  RCHECK(g, up_ln(g, wm, M + "enc_output_norm", &g->enc_output_ln));
-  for (int k = 0; k < 3; ++k) RCHECK(g, pack_lin(g, wm, M + "encoder_output_bbox_embed.layers." + std::to_string(k), &g->enc_bbox[k]));
-  RCHECK(g, up_f32(g, wm, M + "query_position_embeddings.weight", &g->tgt, (int64_t)c.num_queries * D));
+  OVM_TRY(g, pack_lin(g, wm, M + "enc_output", &g->enc_output));
+  OVM_TRY(g, up_ln(g, wm, M + "enc_output_norm", &g->enc_output_ln));
+  for (int k = 0; k < 3; ++k) OVM_TRY(g, pack_lin(g, wm, M + "encoder_output_bbox_embed.layers." + std::to_string(k), &g->enc_bbox[k]));
+  OVM_TRY(g, upload_weight(g, wm, M + "query_position_embeddings.weight", (int64_t)c.num_queries * D, &g->tgt));
   // ---- decoder
   {
     std::vector<std::string> kvnames, valnames;
@@ -1242,40 +1137,40 @@ int ovm_gdino_create(const OvmGdinoConfig* cfg, const OvmTensor* weights, int32_
       const std::string p = M + "decoder.layers." + std::to_string(i) + ".";
       g->dec.emplace_back();
       DecLayer& ly = g->dec.back();
-      RCHECK(g, load_mha(g, wm, p + "self_attn.", c.heads, &ly.sa, false));
-      RCHECK(g, up_ln(g, wm, p + "self_attn_layer_norm", &ly.ln1));
-      RCHECK(g, load_mha(g, wm, p + "encoder_attn_text.", c.heads, &ly.ca, true));
-      RCHECK(g, up_ln(g, wm, p + "encoder_attn_text_layer_norm", &ly.ln2));
-      RCHECK(g, load_msda(g, wm, p + "encoder_attn.", &ly.msda, false));
-      RCHECK(g, up_ln(g, wm, p + "encoder_attn_layer_norm", &ly.ln3));
-      RCHECK(g, pack_lin(g, wm, p + "fc1", &ly.fc1));
-      RCHECK(g, pack_lin(g, wm, p + "fc2", &ly.fc2));
-      RCHECK(g, up_ln(g, wm, p + "final_layer_norm", &ly.ln4));
+      OVM_TRY(g, load_mha(g, wm, p + "self_attn.", c.heads, &ly.sa, false, true));
+      OVM_TRY(g, up_ln(g, wm, p + "self_attn_layer_norm", &ly.ln1));
+      OVM_TRY(g, load_mha(g, wm, p + "encoder_attn_text.", c.heads, &ly.ca, true, true));
+      OVM_TRY(g, up_ln(g, wm, p + "encoder_attn_text_layer_norm", &ly.ln2));
+      OVM_TRY(g, load_msda(g, wm, p + "encoder_attn.", &ly.msda, false, true));
+      OVM_TRY(g, up_ln(g, wm, p + "encoder_attn_layer_norm", &ly.ln3));
+      OVM_TRY(g, pack_lin(g, wm, p + "fc1", &ly.fc1, true, true));
+      OVM_TRY(g, pack_lin(g, wm, p + "fc2", &ly.fc2, true, true));
+      OVM_TRY(g, up_ln(g, wm, p + "final_layer_norm", &ly.ln4));
       kvnames.push_back(p + "encoder_attn_text.key"); kvnames.push_back(p + "encoder_attn_text.value");
       valnames.push_back(p + "encoder_attn.value_proj");
     }
-    RCHECK(g, pack_cat(g, wm, kvnames, &g->dec_kv_text));
-    RCHECK(g, pack_cat(g, wm, valnames, &g->dec_value));
+    OVM_TRY(g, pack_cat(g, wm, kvnames, &g->dec_kv_text));
+    OVM_TRY(g, pack_cat(g, wm, valnames, &g->dec_value));
   }
-  RCHECK(g, up_ln(g, wm, M + "decoder.layer_norm", &g->dec_ln));
-  for (int k = 0; k < 2; ++k) RCHECK(g, pack_lin(g, wm, M + "decoder.reference_points_head.layers." + std::to_string(k), &g->ref_head[k]));
+  OVM_TRY(g, up_ln(g, wm, M + "decoder.layer_norm", &g->dec_ln));
+  for (int k = 0; k < 2; ++k) OVM_TRY(g, pack_lin(g, wm, M + "decoder.reference_points_head.layers." + std::to_string(k), &g->ref_head[k], true, true));
   g->bbox.resize(c.dec_layers);
   for (int i = 0; i < c.dec_layers; ++i)
-    for (int k = 0; k < 3; ++k) RCHECK(g, pack_lin(g, wm, "bbox_embed." + std::to_string(i) + ".layers." + std::to_string(k), &g->bbox[i][k]));
+    for (int k = 0; k < 3; ++k) OVM_TRY(g, pack_lin(g, wm, "bbox_embed." + std::to_string(i) + ".layers." + std::to_string(k), &g->bbox[i][k], true, i + 1 < c.dec_layers));
   {
     const int F = D / 2;
     std::vector<float> dt((size_t)F / 2);
     for (int i = 0; i < F / 2; ++i) dt[i] = powf(10000.0f, 2.f * (float)i / (float)F);       // sine_embed_kernel's dim_t for f / 2 = i
-    RCHECK(g, up_vec(g, dt, &g->sine_dim_t));
+    OVM_TRY(g, upload_f32(g, dt.data(), dt.size(), &g->sine_dim_t));
   }
   // fragment-ordered copies of everything the decoder's row-chain kernels multiply by
-  for (int k = 0; k < 2; ++k) RCHECK(g, make_frag(g, &g->ref_head[k]));
+  for (int k = 0; k < 2; ++k) OVM_TRY(g, make_frag(g, &g->ref_head[k]));
   for (int i = 0; i < c.dec_layers; ++i) {
     DecLayer& ly = g->dec[i];
-    for (Lin* w : {&ly.sa.qk, &ly.sa.v, &ly.sa.out, &ly.ca.q, &ly.ca.out, &ly.msda.offw, &ly.msda.out, &ly.fc1, &ly.fc2}) RCHECK(g, make_frag(g, w));
-    if (i + 1 < c.dec_layers) for (int k = 0; k < 3; ++k) RCHECK(g, make_frag(g, &g->bbox[i][k]));
+    for (Lin* w : {&ly.sa.qk, &ly.sa.v, &ly.sa.out, &ly.ca.q, &ly.ca.out, &ly.msda.offw, &ly.msda.out, &ly.fc1, &ly.fc2}) OVM_TRY(g, make_frag(g, w));
+    if (i + 1 < c.dec_layers) for (int k = 0; k < 3; ++k) OVM_TRY(g, make_frag(g, &g->bbox[i][k]));
   }
-  GCHECK(g, hipDeviceSynchronize());
+  OVM_HIP(g, hipDeviceSynchronize());
   return OVM_OK;
 }
 
@@ -1284,7 +1179,7 @@ int ovm_gdino_destroy(OvmGdino* g) {
   (void)hipSetDevice(g->device);
   (void)hipDeviceSynchronize();
   for (Plan* p : g->plans) delete p;
-  for (void* p : g->allocs) (void)hipFree(p);
+  g->free_all();
   if (g->aux) (void)hipStreamDestroy(g->aux);
   if (g->ev_fork) (void)hipEventDestroy(g->ev_fork);
   if (g->ev_join) (void)hipEventDestroy(g->ev_join);
@@ -1320,7 +1215,7 @@ int ovm_gdino_forward(OvmGdino* g, const OvmImage* image, const int32_t* token_i
   for (auto it = g->plans.begin(); it != g->plans.end(); ++it)
     if (plan_matches(*it, H, W, ids, pids)) { pl = *it; g->plans.erase(it); break; }
   if (!pl) {
-    RCHECK(g, build_plan(g, H, W, ids, pids, &pl));
+    OVM_TRY(g, build_plan(g, H, W, ids, pids, &pl));
     Run dry{g, pl, s, true};
     int r = forward_impl(dry);
     if (r) { delete pl; return r; }
@@ -1343,12 +1238,12 @@ int ovm_gdino_forward(OvmGdino* g, const OvmImage* image, const int32_t* token_i
   g->plans.push_front(pl);
   g->last = pl;
   // input normalisation reads the caller's buffer: outside the graph
-  RCHECK(g, ovm_g_normalize_image(image, g->cfg.pixel_mean, g->cfg.pixel_std, g->cfg.flip_channels, pl->img, s));
+  OVM_TRY(g, ovm_g_normalize_image(image, g->cfg.pixel_mean, g->cfg.pixel_std, g->cfg.flip_channels, pl->img, s));
   if (pl->exec) {
-    GCHECK(g, hipGraphLaunch(pl->exec, s));
+    OVM_HIP(g, hipGraphLaunch(pl->exec, s));
   } else {
     Run run{g, pl, s, false};
-    RCHECK(g, forward_impl(run));
+    OVM_TRY(g, forward_impl(run));
     pl->launches = run.launches;
     if (g->graphs_enabled) {
       // captured right after the first (eager) run of a plan, so every later call of this shape replays; a failed capture
@@ -1372,8 +1267,8 @@ int ovm_gdino_forward(OvmGdino* g, const OvmImage* image, const int32_t* token_i
   }
   g->launches_last = pl->launches;
   const size_t nl = (size_t)g->cfg.num_queries * g->cfg.max_text_len;
-  if (pred_logits) GCHECK(g, hipMemcpyAsync(pred_logits, pl->out_logits, nl * sizeof(float), hipMemcpyDeviceToDevice, s));
-  if (pred_boxes) GCHECK(g, hipMemcpyAsync(pred_boxes, pl->out_boxes, (size_t)g->cfg.num_queries * 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (pred_logits) OVM_HIP(g, hipMemcpyAsync(pred_logits, pl->out_logits, nl * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (pred_boxes) OVM_HIP(g, hipMemcpyAsync(pred_boxes, pl->out_boxes, (size_t)g->cfg.num_queries * 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
   return OVM_OK;
 }
 

@@ -41,7 +41,7 @@ __global__ void qkv_layout_kernel(const float* __restrict__ qkv, int B, int T, i
 __global__ void join_kernel(const half_t* __restrict__ hi, const half_t* __restrict__ lo, int64_t n, float* __restrict__ y) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  y[i] = (float)hi[i] + (lo ? (float)lo[i] * kLoInv : 0.f);
+  y[i] = (float)hi[i] + (lo ? (float)lo[i] : 0.f);
 }
 struct Tmp {
   std::vector<void*> p;

@@ -18,22 +18,21 @@
 
 #include <cmath>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
 #include "../../include/ovm3d.h"
 #include "kernels.hpp"
 #include "sam.hpp"
+#include "loader.hpp"
 
 using namespace ovm;
 
 namespace {
 
-struct Lin { half_t* hi = nullptr; half_t* lo = nullptr; float* bias = nullptr; int N = 0, K = 0, Kpad = 0; };
-struct Attn { Lin q, k, v, o; };
+struct Attn { PackedLin q, k, v, o; };
 struct Norm { float* g = nullptr; float* b = nullptr; };
-struct DecLayer { Attn self, t2i, i2t; Lin lin1, lin2; Norm n1, n2, n3, n4; };
+struct DecLayer { Attn self, t2i, i2t; PackedLin lin1, lin2; Norm n1, n2, n3, n4; };
 
 constexpr int kMaxTok = 8;           // tokens per box the image -> token kernel holds (1 IoU + mask tokens + 2 corners)
 constexpr float kDecEps = 1e-5f;     // nn.LayerNorm default of the two-way transformer
@@ -41,22 +40,20 @@ constexpr float kLn2dEps = 1e-6f;    // LayerNorm2d of the neck and the upscalin
 
 }  // namespace
 
-struct OvmSam {
+struct OvmSam : ovm::Loader {
   OvmSamConfig cfg;
   int device = 0;
-  std::string err;
-  std::vector<void*> allocs;
   OvmHandle* tower = nullptr;
   int G = 0, G2 = 0, C = 0, S = 0, L = 0, nt = 0, I = 0;      // grid, prompt width, image size, low-res side 4G, tokens per box, cross-attention width
   // neck
-  Lin neck1, neck3; Norm nn1, nn3;
+  PackedLin neck1, neck3; Norm nn1, nn3;
   half_t *pad_hi = nullptr, *pad_lo = nullptr; float *T1 = nullptr, *T2 = nullptr, *emb = nullptr, *src0 = nullptr, *pe = nullptr;
   // prompt encoder
   float *gauss = nullptr, *corner = nullptr /* point_embeddings 2, 3: [2][C] */, *no_mask = nullptr;
   // decoder
   float* out_tokens = nullptr;          // [1 + num_mask_tokens][C]: iou_token, mask_tokens
   std::vector<DecLayer> layers; Attn fin; Norm nfin;
-  Lin up1, up2; Norm upn; std::vector<Lin> hyper; Lin iou[8]; int n_iou = 0;
+  PackedLin up1, up2; Norm upn; std::vector<PackedLin> hyper; PackedLin iou[8]; int n_iou = 0;
   // image state
   bool has_image = false; int H = 0, W = 0, newh = 0, neww = 0;
   uint8_t *rs_tmp = nullptr, *rs_dst = nullptr; size_t rs_tmp_cap = 0;
@@ -68,115 +65,17 @@ struct OvmSam {
 
 namespace {
 
-#define SCHECK(m, call)                                                                    \
-  do {                                                                                     \
-    hipError_t e_ = (call);                                                                \
-    if (e_ != hipSuccess) {                                                                \
-      (m)->err = std::string(#call) + ": " + hipGetErrorString(e_);                        \
-      return OVM_ERR_HIP;                                                                  \
-    }                                                                                      \
-  } while (0)
-
-#define SK(m, call)                                                                        \
-  do {                                                                                     \
-    int r_ = (call);                                                                       \
-    if (r_ != OVM_OK) {                                                                    \
-      if ((m)->err.empty()) (m)->err = std::string(#call) + " failed (" + std::to_string(r_) + ")"; \
-      return r_;                                                                           \
-    }                                                                                      \
-  } while (0)
-
-template <typename Tp>
-int dalloc(OvmSam* m, Tp** p, size_t count, bool zero = false) {
-  void* q = nullptr;
-  size_t bytes = count * sizeof(Tp);
-  if (bytes == 0) bytes = 16;
-  SCHECK(m, hipMalloc(&q, bytes));
-  m->allocs.push_back(q);
-  if (zero) SCHECK(m, hipMemset(q, 0, bytes));
-  *p = (Tp*)q;
-  return OVM_OK;
-}
-
-struct WMap {
-  std::map<std::string, const OvmTensor*> m;
-  const OvmTensor* get(const std::string& k) const { auto it = m.find(k); return it == m.end() ? nullptr : it->second; }
-};
-
-int64_t numel(const OvmTensor* t) { int64_t n = 1; for (int i = 0; i < t->ndim; ++i) n *= t->shape[i]; return n; }
-
-int host_of(OvmSam* m, const WMap& wm, const std::string& key, int64_t expect, const float** p) {
-  const OvmTensor* t = wm.get(key);
-  if (!t) { m->err = "missing weight: " + key; return OVM_ERR_MISSING_WEIGHT; }
-  if (numel(t) != expect) { m->err = "bad shape for " + key + " (expected " + std::to_string(expect) + " elements)"; return OVM_ERR_SHAPE; }
-  *p = t->data;
-  return OVM_OK;
-}
-
-int upload(OvmSam* m, const float* src, size_t n, float** out) {
-  int r = dalloc(m, out, n); if (r) return r;
-  SCHECK(m, hipMemcpy(*out, src, n * 4, hipMemcpyHostToDevice));
-  return OVM_OK;
-}
-
-int upload_key(OvmSam* m, const WMap& wm, const std::string& key, int64_t expect, float** out) {
-  const float* p; int r = host_of(m, wm, key, expect, &p); if (r) return r;
-  return upload(m, p, (size_t)expect, out);
-}
-
-// host [N][K] fp32 (GEMM k-order) -> the packed fp16 image ovm_g_linear / launch_gemm stream (ovm_g_pack_weight)
-int pack(OvmSam* m, const float* w, int N, int K, const float* bias, Lin* out) {
-  const int Kpad = (K + 63) / 64 * 64, Npad = (N + 127) / 128 * 128;
-  const bool split = m->cfg.precision == 3;
-  float* tmp = nullptr;
-  SCHECK(m, hipMalloc((void**)&tmp, (size_t)N * K * 4));
-  hipError_t e = hipMemcpy(tmp, w, (size_t)N * K * 4, hipMemcpyHostToDevice);
-  int r = e == hipSuccess ? dalloc(m, &out->hi, (size_t)Npad * Kpad * (split ? 2 : 1)) : OVM_ERR_HIP;
-  if (!r) {
-    out->lo = split ? out->hi + 32 : nullptr;
-    r = ovm_g_pack_weight(tmp, N, K, Kpad, (uint16_t*)out->hi, (uint16_t*)out->lo, nullptr);
-    if (!r && hipDeviceSynchronize() != hipSuccess) r = OVM_ERR_HIP;
-  }
-  (void)hipFree(tmp);
-  if (r) { if (m->err.empty()) m->err = "weight packing failed"; return r; }
-  out->N = N; out->K = K; out->Kpad = Kpad; out->bias = nullptr;
-  if (bias) return upload(m, bias, (size_t)N, &out->bias);
-  return OVM_OK;
-}
-
-int pack_linear(OvmSam* m, const WMap& wm, const std::string& prefix, int N, int K, Lin* out) {
-  const float *w, *b;
-  int r = host_of(m, wm, prefix + ".weight", (int64_t)N * K, &w); if (r) return r;
-  r = host_of(m, wm, prefix + ".bias", N, &b); if (r) return r;
-  return pack(m, w, N, K, b, out);
-}
-
-int pack_attn(OvmSam* m, const WMap& wm, const std::string& prefix, int C, int I, Attn* a) {
+int pack_attn(OvmSam* m, const WeightMap& wm, const std::string& prefix, int C, int I, Attn* a) {
   int r = pack_linear(m, wm, prefix + ".q_proj", I, C, &a->q); if (r) return r;
   r = pack_linear(m, wm, prefix + ".k_proj", I, C, &a->k); if (r) return r;
   r = pack_linear(m, wm, prefix + ".v_proj", I, C, &a->v); if (r) return r;
   return pack_linear(m, wm, prefix + ".out_proj", C, I, &a->o);
 }
 
-int load_norm(OvmSam* m, const WMap& wm, const std::string& prefix, int D, Norm* n) {
-  int r = upload_key(m, wm, prefix + ".weight", D, &n->g); if (r) return r;
-  return upload_key(m, wm, prefix + ".bias", D, &n->b);
+int load_norm(OvmSam* m, const WeightMap& wm, const std::string& prefix, int D, Norm* n) {
+  int r = upload_weight(m, wm, prefix + ".weight", D, &n->g); if (r) return r;
+  return upload_weight(m, wm, prefix + ".bias", D, &n->b);
 }
-
-// ConvTranspose2d k2 s2 weight [Cin][Cout][2][2] -> GEMM rows [(a * 2 + b) * Cout + co][ci], bias tiled over the four taps
-int pack_convt(OvmSam* m, const WMap& wm, const std::string& prefix, int Cin, int Cout, Lin* out) {
-  const float *w, *b;
-  int r = host_of(m, wm, prefix + ".weight", (int64_t)Cin * Cout * 4, &w); if (r) return r;
-  r = host_of(m, wm, prefix + ".bias", Cout, &b); if (r) return r;
-  std::vector<float> v((size_t)4 * Cout * Cin), bb((size_t)4 * Cout);
-  for (int ci = 0; ci < Cin; ++ci)
-    for (int co = 0; co < Cout; ++co)
-      for (int q = 0; q < 4; ++q) v[((size_t)q * Cout + co) * Cin + ci] = w[((size_t)ci * Cout + co) * 4 + q];
-  for (int q = 0; q < 4; ++q) memcpy(&bb[(size_t)q * Cout], b, (size_t)Cout * 4);
-  return pack(m, v.data(), 4 * Cout, Cin, bb.data(), out);
-}
-
-inline dim3 g1(long n, int bs = 256) { return dim3((unsigned)((n + bs - 1) / bs)); }
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------------------
 
@@ -390,9 +289,7 @@ __global__ void sam_iou_slice_kernel(const float* __restrict__ head, int ldh, in
   iou[i] = head[(size_t)(i / 3) * ldh + 1 + i % 3];
 }
 
-int last_launch() { return hipGetLastError() == hipSuccess ? OVM_OK : OVM_ERR_HIP; }
-
-int lin(OvmSam* m, const Lin& w, const float* x, int ldx, long M, int act, const float* res, int ldr, float* y, int ldy, hipStream_t s) {
+int lin(OvmSam* m, const PackedLin& w, const float* x, int ldx, long M, int act, const float* res, int ldr, float* y, int ldy, hipStream_t s) {
   return ovm_g_linear(x, ldx, (int)M, w.K, (const uint16_t*)w.hi, (const uint16_t*)w.lo, w.N, w.Kpad, w.bias, act, res, ldr, y, ldy, m->cfg.precision, s);
 }
 
@@ -404,10 +301,10 @@ int add_bcast(const float* a, const float* b, float* out, long n, long bmod, hip
 // token queries [nb * nt][I] against Tk keys per box: scores (bmm) -> softmax -> context (bmm); heads x dh = I
 int token_attention(OvmSam* m, const float* Q, const float* K, const float* V, int nb, int Tk, int I, float* scores, float* ctx, hipStream_t s) {
   const int nt = m->nt, hd = m->cfg.dec_heads, dh = I / hd;
-  SK(m, ovm_g_bmm2(Q, K, scores, nb, hd, nt, Tk, dh, I, I, Tk, (int64_t)nt * I, (int64_t)Tk * I, (int64_t)hd * nt * Tk, dh, dh, (int64_t)nt * Tk, 1,
+  OVM_TRY(m, ovm_g_bmm2(Q, K, scores, nb, hd, nt, Tk, dh, I, I, Tk, (int64_t)nt * I, (int64_t)Tk * I, (int64_t)hd * nt * Tk, dh, dh, (int64_t)nt * Tk, 1,
                    1.0f / sqrtf((float)dh), s));
-  SK(m, ovm_g_softmax(scores, nb * hd * nt, Tk, Tk, nullptr, 0, 0, 0, s));
-  SK(m, ovm_g_bmm2(scores, V, ctx, nb, hd, nt, dh, Tk, Tk, I, I, (int64_t)hd * nt * Tk, (int64_t)Tk * I, (int64_t)nt * I, (int64_t)nt * Tk, dh, dh, 0, 1.0f, s));
+  OVM_TRY(m, ovm_g_softmax(scores, nb * hd * nt, Tk, Tk, nullptr, 0, 0, 0, s));
+  OVM_TRY(m, ovm_g_bmm2(scores, V, ctx, nb, hd, nt, dh, Tk, Tk, I, I, (int64_t)hd * nt * Tk, (int64_t)Tk * I, (int64_t)nt * I, (int64_t)nt * Tk, dh, dh, 0, 1.0f, s));
   return OVM_OK;
 }
 
@@ -438,82 +335,82 @@ int decode_chunk(OvmSam* m, const float* boxes, int nb, int mask_index, uint8_t*
   // 1. tokens + sparse embeddings; src = (embedding + no_mask_embed) per box
   hipLaunchKernelGGL(sam_box_tokens_kernel, g1(Mt * (C / 2)), dim3(256), 0, s, boxes, nb, nout, C, m->out_tokens, m->gauss, m->corner,
                      (double)m->neww / (double)m->W, (double)m->newh / (double)m->H, (float)m->S, w.tok0, m->dbg_sparse);
-  SK(m, last_launch());
-  SCHECK(m, hipMemcpyAsync(w.q, w.tok0, (size_t)Mt * C * 4, hipMemcpyDeviceToDevice, s));
+  OVM_TRY(m, last_launch());
+  OVM_HIP(m, hipMemcpyAsync(w.q, w.tok0, (size_t)Mt * C * 4, hipMemcpyDeviceToDevice, s));
   hipLaunchKernelGGL(sam_bcast_kernel, g1(Mi * C / 4), dim3(256), 0, s, (const float4*)m->src0, (float4*)w.keys, Mi * C / 4, (long)G2 * C / 4);
-  SK(m, last_launch());
+  OVM_TRY(m, last_launch());
   auto norm = [&](const Norm& n, const float* x, long M, float* y) { return ovm_g_layernorm(x, nullptr, (int)M, C, n.g, n.b, kDecEps, y, s); };
   // token -> image attention of one block (also the final one): q += out_proj(attn(q + pe_q, keys + pe_k, keys)), then the norm
   auto tok_to_img = [&](const Attn& a, const Norm& n) -> int {
-    SK(m, add_bcast(w.q, w.tok0, w.qpe, Mt * C, Mt * C, s));
-    SK(m, add_bcast(w.keys, m->pe, w.kpe, Mi * C, (long)G2 * C, s));
-    SK(m, lin(m, a.q, w.qpe, C, Mt, 0, nullptr, 0, w.tq, I, s));
-    SK(m, lin(m, a.k, w.kpe, C, Mi, 0, nullptr, 0, w.iA, I, s));
-    SK(m, lin(m, a.v, w.keys, C, Mi, 0, nullptr, 0, w.iB, I, s));
-    SK(m, token_attention(m, w.tq, w.iA, w.iB, nb, G2, I, w.scores, w.tctx, s));
-    SK(m, lin(m, a.o, w.tctx, I, Mt, 0, w.q, C, w.tout, C, s));
+    OVM_TRY(m, add_bcast(w.q, w.tok0, w.qpe, Mt * C, Mt * C, s));
+    OVM_TRY(m, add_bcast(w.keys, m->pe, w.kpe, Mi * C, (long)G2 * C, s));
+    OVM_TRY(m, lin(m, a.q, w.qpe, C, Mt, 0, nullptr, 0, w.tq, I, s));
+    OVM_TRY(m, lin(m, a.k, w.kpe, C, Mi, 0, nullptr, 0, w.iA, I, s));
+    OVM_TRY(m, lin(m, a.v, w.keys, C, Mi, 0, nullptr, 0, w.iB, I, s));
+    OVM_TRY(m, token_attention(m, w.tq, w.iA, w.iB, nb, G2, I, w.scores, w.tctx, s));
+    OVM_TRY(m, lin(m, a.o, w.tctx, I, Mt, 0, w.q, C, w.tout, C, s));
     return norm(n, w.tout, Mt, w.q);
   };
   for (int l = 0; l < c.dec_depth; ++l) {
     const DecLayer& y = m->layers[l];
     // self attention (layer 0: no positional encoding, and the output REPLACES the tokens)
     const float* qin = w.q;
-    if (l > 0) { SK(m, add_bcast(w.q, w.tok0, w.qpe, Mt * C, Mt * C, s)); qin = w.qpe; }
-    SK(m, lin(m, y.self.q, qin, C, Mt, 0, nullptr, 0, w.tq, C, s));
-    SK(m, lin(m, y.self.k, qin, C, Mt, 0, nullptr, 0, w.tk, C, s));
-    SK(m, lin(m, y.self.v, w.q, C, Mt, 0, nullptr, 0, w.tv, C, s));
-    SK(m, token_attention(m, w.tq, w.tk, w.tv, nb, nt, C, w.scores, w.tctx, s));
-    SK(m, lin(m, y.self.o, w.tctx, C, Mt, 0, l > 0 ? w.q : nullptr, C, w.tout, C, s));
-    SK(m, norm(y.n1, w.tout, Mt, w.q));
-    SK(m, tok_to_img(y.t2i, y.n2));
+    if (l > 0) { OVM_TRY(m, add_bcast(w.q, w.tok0, w.qpe, Mt * C, Mt * C, s)); qin = w.qpe; }
+    OVM_TRY(m, lin(m, y.self.q, qin, C, Mt, 0, nullptr, 0, w.tq, C, s));
+    OVM_TRY(m, lin(m, y.self.k, qin, C, Mt, 0, nullptr, 0, w.tk, C, s));
+    OVM_TRY(m, lin(m, y.self.v, w.q, C, Mt, 0, nullptr, 0, w.tv, C, s));
+    OVM_TRY(m, token_attention(m, w.tq, w.tk, w.tv, nb, nt, C, w.scores, w.tctx, s));
+    OVM_TRY(m, lin(m, y.self.o, w.tctx, C, Mt, 0, l > 0 ? w.q : nullptr, C, w.tout, C, s));
+    OVM_TRY(m, norm(y.n1, w.tout, Mt, w.q));
+    OVM_TRY(m, tok_to_img(y.t2i, y.n2));
     // MLP
-    SK(m, lin(m, y.lin1, w.q, C, Mt, 1, nullptr, 0, w.mlp, c.dec_mlp, s));
-    SK(m, lin(m, y.lin2, w.mlp, c.dec_mlp, Mt, 0, w.q, C, w.tout, C, s));
-    SK(m, norm(y.n3, w.tout, Mt, w.q));
+    OVM_TRY(m, lin(m, y.lin1, w.q, C, Mt, 1, nullptr, 0, w.mlp, c.dec_mlp, s));
+    OVM_TRY(m, lin(m, y.lin2, w.mlp, c.dec_mlp, Mt, 0, w.q, C, w.tout, C, s));
+    OVM_TRY(m, norm(y.n3, w.tout, Mt, w.q));
     // image -> token: the image rows (keys + pe, unchanged since tok_to_img) are the queries
-    SK(m, add_bcast(w.q, w.tok0, w.qpe, Mt * C, Mt * C, s));
-    SK(m, lin(m, y.i2t.q, w.kpe, C, Mi, 0, nullptr, 0, w.iA, I, s));
-    SK(m, lin(m, y.i2t.k, w.qpe, C, Mt, 0, nullptr, 0, w.tk, I, s));
-    SK(m, lin(m, y.i2t.v, w.q, C, Mt, 0, nullptr, 0, w.tv, I, s));
+    OVM_TRY(m, add_bcast(w.q, w.tok0, w.qpe, Mt * C, Mt * C, s));
+    OVM_TRY(m, lin(m, y.i2t.q, w.kpe, C, Mi, 0, nullptr, 0, w.iA, I, s));
+    OVM_TRY(m, lin(m, y.i2t.k, w.qpe, C, Mt, 0, nullptr, 0, w.tk, I, s));
+    OVM_TRY(m, lin(m, y.i2t.v, w.q, C, Mt, 0, nullptr, 0, w.tv, I, s));
     hipLaunchKernelGGL(sam_i2t_attn_kernel<16>, dim3((unsigned)(Mi / (256 / c.dec_heads))), dim3(256), 0, s, w.iA, I, w.tk, w.tv, I, nt, c.dec_heads, G2, Mi,
                        0.25f, w.iB, I);
-    SK(m, last_launch());
-    SK(m, lin(m, y.i2t.o, w.iB, I, Mi, 0, w.keys, C, w.tmp, C, s));
-    SK(m, norm(y.n4, w.tmp, Mi, w.keys));
+    OVM_TRY(m, last_launch());
+    OVM_TRY(m, lin(m, y.i2t.o, w.iB, I, Mi, 0, w.keys, C, w.tmp, C, s));
+    OVM_TRY(m, norm(y.n4, w.tmp, Mi, w.keys));
   }
-  SK(m, tok_to_img(m->fin, m->nfin));
-  SCHECK(m, hipMemcpyAsync(m->dbg_tokens, w.q, (size_t)Mt * C * 4, hipMemcpyDeviceToDevice, s));
+  OVM_TRY(m, tok_to_img(m->fin, m->nfin));
+  OVM_HIP(m, hipMemcpyAsync(m->dbg_tokens, w.q, (size_t)Mt * C * 4, hipMemcpyDeviceToDevice, s));
   m->dbg_n = nb;
   // 4. upscaling: ConvT . LayerNorm2d . GELU . ConvT . GELU as GEMMs over source pixels (blocked layout: file header)
   const int C4 = C / 4, C8 = C / 8;
-  SK(m, lin(m, m->up1, w.keys, C, Mi, 0, nullptr, 0, w.tmp, C, s));
+  OVM_TRY(m, lin(m, m->up1, w.keys, C, Mi, 0, nullptr, 0, w.tmp, C, s));
   hipLaunchKernelGGL(sam_ln_gelu_kernel, dim3((unsigned)((Mi * 4 + 3) / 4)), dim3(256), 0, s, w.tmp, Mi * 4, C4, m->upn.g, m->upn.b, kLn2dEps);
-  SK(m, last_launch());
-  SK(m, lin(m, m->up2, w.tmp, C4, Mi * 4, 2, nullptr, 0, w.up2, 4 * C8, s));
+  OVM_TRY(m, last_launch());
+  OVM_TRY(m, lin(m, m->up2, w.tmp, C4, Mi * 4, 2, nullptr, 0, w.up2, 4 * C8, s));
   // hypernetwork MLPs (every mask token when the low-resolution logits are asked for, else the requested one) and the IoU head
   const int t_first = lowres ? 0 : 1 + mask_index, t_last = lowres ? c.num_mask_tokens : 2 + mask_index;
   for (int t = t_first; t < t_last; ++t) {
-    const Lin* hl = &m->hyper[(size_t)t * 3];
-    SK(m, lin(m, hl[0], w.q + (size_t)(1 + t) * C, nt * C, nb, 1, nullptr, 0, w.h1, C, s));
-    SK(m, lin(m, hl[1], w.h1, C, nb, 1, nullptr, 0, w.h2, C, s));
-    SK(m, lin(m, hl[2], w.h2, C, nb, 0, nullptr, 0, w.hyp + (size_t)t * C8, c.num_mask_tokens * C8, s));
+    const PackedLin* hl = &m->hyper[(size_t)t * 3];
+    OVM_TRY(m, lin(m, hl[0], w.q + (size_t)(1 + t) * C, nt * C, nb, 1, nullptr, 0, w.h1, C, s));
+    OVM_TRY(m, lin(m, hl[1], w.h1, C, nb, 1, nullptr, 0, w.h2, C, s));
+    OVM_TRY(m, lin(m, hl[2], w.h2, C, nb, 0, nullptr, 0, w.hyp + (size_t)t * C8, c.num_mask_tokens * C8, s));
   }
   {
     const float* x = w.q; int ldx = nt * C; float* bufs[2] = {w.h1, w.h2};
     for (int i = 0; i < m->n_iou; ++i) {
       const bool last = i + 1 == m->n_iou;
       float* y = last ? w.iouh : bufs[i & 1]; const int ldy = last ? 128 : c.iou_hidden;
-      SK(m, lin(m, m->iou[i], x, ldx, nb, last ? 0 : 1, nullptr, 0, y, ldy, s));
+      OVM_TRY(m, lin(m, m->iou[i], x, ldx, nb, last ? 0 : 1, nullptr, 0, y, ldy, s));
       x = y; ldx = ldy;
     }
-    if (iou) { hipLaunchKernelGGL(sam_iou_slice_kernel, g1(nb * 3), dim3(256), 0, s, w.iouh, 128, nb, iou); SK(m, last_launch()); }
+    if (iou) { hipLaunchKernelGGL(sam_iou_slice_kernel, g1(nb * 3), dim3(256), 0, s, w.iouh, 128, nb, iou); OVM_TRY(m, last_launch()); }
   }
   // mask product: multimask slice 1:4 into `lowres`, or the requested token alone into the workspace
   const long LL = (long)m->L * m->L;
   float* planes = lowres ? lowres : w.low; const long stride = lowres ? 3 * LL : LL;
   hipLaunchKernelGGL(sam_mask_prod_kernel, g1(Mi * 16), dim3(256), 0, s, w.up2, w.hyp, c.num_mask_tokens * C8, lowres ? 1 : 1 + mask_index, lowres ? 3 : 1, C8, m->G,
                      Mi * 16, planes, stride);
-  SK(m, last_launch());
+  OVM_TRY(m, last_launch());
   // 5. postprocess_masks + threshold
   const long total = (long)nb * m->H * m->W;
   hipLaunchKernelGGL(sam_mask_out_kernel, g1((total + 3) / 4), dim3(256), 0, s, planes + (lowres ? (size_t)mask_index * LL : 0), stride, m->L, m->S, m->newh,
@@ -531,7 +428,7 @@ int ovm_sam_destroy(OvmSam* m) {
   if (!m) return OVM_OK;
   (void)hipSetDevice(m->device);
   if (m->tower) ovm_destroy(m->tower);
-  for (void* p : m->allocs) (void)hipFree(p);
+  m->free_all();
   if (m->rs_tmp) (void)hipFree(m->rs_tmp);
   if (m->tab) (void)hipFree(m->tab);
   delete m;
@@ -542,7 +439,7 @@ int ovm_sam_create(const OvmSamConfig* cfg, const OvmTensor* weights, int32_t n_
   if (!cfg || !out) return OVM_ERR_INVALID;
   OvmSam* m = new OvmSam();
   *out = m;
-  m->cfg = *cfg; m->device = device;
+  m->cfg = *cfg; m->device = device; m->precision = cfg->precision; m->k_align = 64;
   const OvmSamConfig& c = m->cfg;
   if (c.heads > 0 && c.embed_dim != c.heads * 64) {
     m->err = "unsupported image encoder: head dimension " + std::to_string(c.embed_dim / c.heads) + " (embed_dim " + std::to_string(c.embed_dim) +
@@ -559,7 +456,7 @@ int ovm_sam_create(const OvmSamConfig* cfg, const OvmTensor* weights, int32_t n_
   }
   m->G = c.image_size / c.patch; m->G2 = m->G * m->G; m->L = 4 * m->G; m->I = c.prompt_dim / c.attn_downsample;
   if (m->G2 % (256 / c.dec_heads) != 0) { m->err = "invalid config (grid cells must fill whole workgroups of the image -> token kernel)"; return OVM_ERR_INVALID; }
-  SCHECK(m, hipSetDevice(device));
+  OVM_HIP(m, hipSetDevice(device));
   {
     OvmConfig t; memset(&t, 0, sizeof(t));
     t.embed_dim = c.embed_dim; t.depth = c.depth; t.heads = c.heads; t.pos_grid = c.pos_grid; t.canvas = c.image_size; t.fpn_channels = 256;
@@ -569,42 +466,34 @@ int ovm_sam_create(const OvmSamConfig* cfg, const OvmTensor* weights, int32_t n_
     const int r = tower_create(&t, weights, n_weights, device, "image_encoder.", &m->tower);
     if (r) { m->err = std::string("image encoder: ") + ovm_last_error(m->tower); return r; }
   }
-  WMap wm;
-  for (int i = 0; i < n_weights; ++i) wm.m[weights[i].name] = &weights[i];
+  const WeightMap wm(weights, n_weights);
   const int C = m->C, D = c.embed_dim, G = m->G, G2 = m->G2, I = m->I;
   int r;
   // ---- neck: conv1x1 (no bias) . LayerNorm2d . conv3x3 (no bias, pad 1) . LayerNorm2d
   {
-    const float* w;
-    if ((r = host_of(m, wm, "image_encoder.neck.0.weight", (int64_t)C * D, &w))) return r;
-    if ((r = pack(m, w, C, D, nullptr, &m->neck1))) return r;
+    if ((r = pack_conv(m, wm, "image_encoder.neck.0", C, D, 1, BIAS_NONE, &m->neck1))) return r;
     if ((r = load_norm(m, wm, "image_encoder.neck.1", C, &m->nn1))) return r;
-    if ((r = host_of(m, wm, "image_encoder.neck.2.weight", (int64_t)C * C * 9, &w))) return r;
-    std::vector<float> v((size_t)C * C * 9);                         // [Cout][Cin][3][3] -> [Cout][(ky * 3 + kx) * Cin + c]
-    for (int o = 0; o < C; ++o)
-      for (int ci = 0; ci < C; ++ci)
-        for (int t = 0; t < 9; ++t) v[((size_t)o * 9 + t) * C + ci] = w[((size_t)o * C + ci) * 9 + t];
-    if ((r = pack(m, v.data(), C, 9 * C, nullptr, &m->neck3))) return r;
+    if ((r = pack_conv(m, wm, "image_encoder.neck.2", C, C, 3, BIAS_NONE, &m->neck3))) return r;
     if ((r = load_norm(m, wm, "image_encoder.neck.3", C, &m->nn3))) return r;
     const size_t pp = (size_t)(G + 2) * (G + 2) * C;
-    if ((r = dalloc(m, &m->pad_hi, pp, true))) return r;
-    if (c.precision == 3 && (r = dalloc(m, &m->pad_lo, pp, true))) return r;
-    if ((r = dalloc(m, &m->T1, (size_t)G2 * C))) return r;
-    if ((r = dalloc(m, &m->T2, (size_t)G2 * C))) return r;
-    if ((r = dalloc(m, &m->emb, (size_t)G2 * C))) return r;
-    if ((r = dalloc(m, &m->src0, (size_t)G2 * C))) return r;
-    if ((r = dalloc(m, &m->pe, (size_t)G2 * C))) return r;
+    if ((r = m->alloc(&m->pad_hi, pp, true))) return r;
+    if (c.precision == 3 && (r = m->alloc(&m->pad_lo, pp, true))) return r;
+    if ((r = m->alloc(&m->T1, (size_t)G2 * C))) return r;
+    if ((r = m->alloc(&m->T2, (size_t)G2 * C))) return r;
+    if ((r = m->alloc(&m->emb, (size_t)G2 * C))) return r;
+    if ((r = m->alloc(&m->src0, (size_t)G2 * C))) return r;
+    if ((r = m->alloc(&m->pe, (size_t)G2 * C))) return r;
   }
   // ---- prompt encoder (boxes): the Gaussian matrix, the two corner embeddings, no_mask_embed
   {
-    if ((r = upload_key(m, wm, "prompt_encoder.pe_layer.positional_encoding_gaussian_matrix", (int64_t)2 * (C / 2), &m->gauss))) return r;
+    if ((r = upload_weight(m, wm, "prompt_encoder.pe_layer.positional_encoding_gaussian_matrix", (int64_t)2 * (C / 2), &m->gauss))) return r;
     const float *p2, *p3;
-    if ((r = host_of(m, wm, "prompt_encoder.point_embeddings.2.weight", C, &p2))) return r;
-    if ((r = host_of(m, wm, "prompt_encoder.point_embeddings.3.weight", C, &p3))) return r;
+    if ((r = find_weight(m, wm, "prompt_encoder.point_embeddings.2.weight", C, &p2))) return r;
+    if ((r = find_weight(m, wm, "prompt_encoder.point_embeddings.3.weight", C, &p3))) return r;
     std::vector<float> cr((size_t)2 * C);
     memcpy(cr.data(), p2, (size_t)C * 4); memcpy(cr.data() + C, p3, (size_t)C * 4);
-    if ((r = upload(m, cr.data(), cr.size(), &m->corner))) return r;
-    if ((r = upload_key(m, wm, "prompt_encoder.no_mask_embed.weight", C, &m->no_mask))) return r;
+    if ((r = upload_f32(m, cr.data(), cr.size(), &m->corner))) return r;
+    if ((r = upload_weight(m, wm, "prompt_encoder.no_mask_embed.weight", C, &m->no_mask))) return r;
     hipLaunchKernelGGL(sam_dense_pe_kernel, g1((long)G2 * (C / 2)), dim3(256), 0, nullptr, m->gauss, G, C / 2, m->pe);
     if ((r = last_launch())) { m->err = "dense positional encoding launch failed"; return r; }
   }
@@ -612,11 +501,11 @@ int ovm_sam_create(const OvmSamConfig* cfg, const OvmTensor* weights, int32_t n_
   {
     const std::string Dp = "mask_decoder.";
     const float *it, *mt;
-    if ((r = host_of(m, wm, Dp + "iou_token.weight", C, &it))) return r;
-    if ((r = host_of(m, wm, Dp + "mask_tokens.weight", (int64_t)c.num_mask_tokens * C, &mt))) return r;
+    if ((r = find_weight(m, wm, Dp + "iou_token.weight", C, &it))) return r;
+    if ((r = find_weight(m, wm, Dp + "mask_tokens.weight", (int64_t)c.num_mask_tokens * C, &mt))) return r;
     std::vector<float> ot((size_t)(1 + c.num_mask_tokens) * C);
     memcpy(ot.data(), it, (size_t)C * 4); memcpy(ot.data() + C, mt, (size_t)c.num_mask_tokens * C * 4);
-    if ((r = upload(m, ot.data(), ot.size(), &m->out_tokens))) return r;
+    if ((r = upload_f32(m, ot.data(), ot.size(), &m->out_tokens))) return r;
     m->layers.resize(c.dec_depth);
     for (int l = 0; l < c.dec_depth; ++l) {
       DecLayer& y = m->layers[l];
@@ -633,9 +522,10 @@ int ovm_sam_create(const OvmSamConfig* cfg, const OvmTensor* weights, int32_t n_
     }
     if ((r = pack_attn(m, wm, Dp + "transformer.final_attn_token_to_image", C, I, &m->fin))) return r;
     if ((r = load_norm(m, wm, Dp + "transformer.norm_final_attn", C, &m->nfin))) return r;
-    if ((r = pack_convt(m, wm, Dp + "output_upscaling.0", C, C / 4, &m->up1))) return r;
+    // the upscaling runs as plain linears over the (tap, co) columns (file header): bias tiled over the four taps
+    if ((r = pack_convt(m, wm, Dp + "output_upscaling.0", C, C / 4, BIAS_REQUIRED, true, &m->up1))) return r;
     if ((r = load_norm(m, wm, Dp + "output_upscaling.1", C / 4, &m->upn))) return r;
-    if ((r = pack_convt(m, wm, Dp + "output_upscaling.3", C / 4, C / 8, &m->up2))) return r;
+    if ((r = pack_convt(m, wm, Dp + "output_upscaling.3", C / 4, C / 8, BIAS_REQUIRED, true, &m->up2))) return r;
     m->hyper.resize((size_t)c.num_mask_tokens * 3);
     for (int t = 0; t < c.num_mask_tokens; ++t) {
       const std::string P = Dp + "output_hypernetworks_mlps." + std::to_string(t) + ".layers.";
@@ -649,10 +539,10 @@ int ovm_sam_create(const OvmSamConfig* cfg, const OvmTensor* weights, int32_t n_
       if ((r = pack_linear(m, wm, Dp + "iou_prediction_head.layers." + std::to_string(i), on, in, &m->iou[i]))) return r;
     }
   }
-  if ((r = dalloc(m, &m->rs_dst, (size_t)c.image_size * c.image_size * 3))) return r;
-  if ((r = dalloc(m, &m->dbg_sparse, (size_t)c.max_boxes * 2 * C, true))) return r;
-  if ((r = dalloc(m, &m->dbg_tokens, (size_t)c.max_boxes * m->nt * C, true))) return r;
-  SCHECK(m, hipDeviceSynchronize());
+  if ((r = m->alloc(&m->rs_dst, (size_t)c.image_size * c.image_size * 3))) return r;
+  if ((r = m->alloc(&m->dbg_sparse, (size_t)c.max_boxes * 2 * C, true))) return r;
+  if ((r = m->alloc(&m->dbg_tokens, (size_t)c.max_boxes * m->nt * C, true))) return r;
+  OVM_HIP(m, hipDeviceSynchronize());
   return OVM_OK;
 }
 
@@ -662,7 +552,7 @@ int ovm_sam_set_image(OvmSam* m, const OvmImage* image, int32_t flip_bgr, ovm_st
   if (!m->tower) { m->err = "handle was not created"; return OVM_ERR_INVALID; }
   if (!image || !image->data || image->height < 1 || image->width < 1) { m->err = "null or empty image"; return OVM_ERR_INVALID; }
   hipStream_t s = (hipStream_t)stream;
-  SCHECK(m, hipSetDevice(m->device));
+  OVM_HIP(m, hipSetDevice(m->device));
   const OvmSamConfig& c = m->cfg;
   const int H = image->height, W = image->width, S = m->S, G = m->G, G2 = m->G2, C = m->C;
   // ResizeLongestSide.get_preprocess_shape
@@ -672,7 +562,7 @@ int ovm_sam_set_image(OvmSam* m, const OvmImage* image, int32_t flip_bgr, ovm_st
   m->has_image = false;
   const bool need_h = neww != W, need_v = newh != H;
   if (m->tabH != H || m->tabW != W) {
-    SCHECK(m, hipStreamSynchronize(s));                  // the previous tables may still be in use / in flight
+    OVM_HIP(m, hipStreamSynchronize(s));                  // the previous tables may still be in use / in flight
     const int xk = ovm_host_pil_bilinear_coeffs(W, neww, nullptr, nullptr, 0), yk = ovm_host_pil_bilinear_coeffs(H, newh, nullptr, nullptr, 0);
     if (xk < 1 || yk < 1) { m->err = "resize coefficient size query failed"; return OVM_ERR_INVALID; }
     m->xk = xk; m->yk = yk;
@@ -686,15 +576,15 @@ int ovm_sam_set_image(OvmSam* m, const OvmImage* image, int32_t flip_bgr, ovm_st
     if (n > m->tab_cap) {
       if (m->tab) (void)hipFree(m->tab);
       m->tab = nullptr; m->tab_cap = 0;
-      SCHECK(m, hipMalloc((void**)&m->tab, n * sizeof(int)));
+      OVM_HIP(m, hipMalloc((void**)&m->tab, n * sizeof(int)));
       m->tab_cap = n;
     }
-    SCHECK(m, hipMemcpy(m->tab, m->tab_host.data(), n * sizeof(int), hipMemcpyHostToDevice));
+    OVM_HIP(m, hipMemcpy(m->tab, m->tab_host.data(), n * sizeof(int), hipMemcpyHostToDevice));
     const size_t tmp_need = (size_t)H * neww * 3;
     if (tmp_need > m->rs_tmp_cap) {
       if (m->rs_tmp) (void)hipFree(m->rs_tmp);
       m->rs_tmp = nullptr; m->rs_tmp_cap = 0;
-      SCHECK(m, hipMalloc((void**)&m->rs_tmp, tmp_need));
+      OVM_HIP(m, hipMalloc((void**)&m->rs_tmp, tmp_need));
       m->rs_tmp_cap = tmp_need;
     }
     m->tabH = H; m->tabW = W;
@@ -715,18 +605,18 @@ int ovm_sam_set_image(OvmSam* m, const OvmImage* image, int32_t flip_bgr, ovm_st
     if (r) { m->err = std::string("image encoder: ") + ovm_last_error(m->tower); return r; }
   }
   // neck
-  SK(m, lin(m, m->neck1, tower_tokens(m->tower), c.embed_dim, G2, 0, nullptr, 0, m->T1, C, s));
+  OVM_TRY(m, lin(m, m->neck1, tower_tokens(m->tower), c.embed_dim, G2, 0, nullptr, 0, m->T1, C, s));
   {
     LnOut o; memset(&o, 0, sizeof(o));
     o.hi = m->pad_hi; o.lo = m->pad_lo; o.ld = C; o.padH = G; o.padW = G;
-    SK(m, launch_ln_rows(m->T1, C, G2, C, m->nn1.g, m->nn1.b, kLn2dEps, o, s));
+    OVM_TRY(m, launch_ln_rows(m->T1, C, G2, C, m->nn1.g, m->nn1.b, kLn2dEps, o, s));
     GemmParams q; memset(&q, 0, sizeof(q));
     q.Ahi = m->pad_hi; q.Alo = m->pad_lo; q.Whi = m->neck3.hi; q.Wlo = m->neck3.lo;
     q.M = G2; q.N = C; q.K = 9 * C; q.cH = G; q.cW = G; q.cC = C; q.C = m->T2; q.ldc = C; q.ws_slot = 1;
-    SK(m, launch_gemm(q, c.precision, EPI_STORE, A_CONV3X3, s));
+    OVM_TRY(m, launch_gemm(q, c.precision, EPI_STORE, A_CONV3X3, s));
   }
-  SK(m, ovm_g_layernorm(m->T2, nullptr, G2, C, m->nn3.g, m->nn3.b, kLn2dEps, m->emb, s));
-  SK(m, add_bcast(m->emb, m->no_mask, m->src0, (long)G2 * C, C, s));
+  OVM_TRY(m, ovm_g_layernorm(m->T2, nullptr, G2, C, m->nn3.g, m->nn3.b, kLn2dEps, m->emb, s));
+  OVM_TRY(m, add_bcast(m->emb, m->no_mask, m->src0, (long)G2 * C, C, s));
   m->H = H; m->W = W; m->newh = newh; m->neww = neww; m->has_image = true;
   return OVM_OK;
 }
@@ -752,7 +642,7 @@ int ovm_sam_predict_boxes(OvmSam* m, const float* boxes, int32_t n, int32_t mask
   int nb = n < m->cfg.max_boxes ? n : m->cfg.max_boxes;
   while (nb > 1 && (int64_t)carve(nullptr, nullptr, m, nb) > workspace_bytes) nb = (nb + 1) / 2;
   if ((int64_t)carve(nullptr, nullptr, m, nb) > workspace_bytes) { m->err = "workspace too small for one box (ovm_sam_predict_boxes_workspace)"; return OVM_ERR_CAPACITY; }
-  SCHECK(m, hipSetDevice(m->device));
+  OVM_HIP(m, hipSetDevice(m->device));
   hipStream_t s = (hipStream_t)stream;
   Work w; carve(&w, (char*)workspace, m, nb);
   const size_t HW = (size_t)m->H * m->W, LL = (size_t)m->L * m->L;

@@ -570,3 +570,21 @@ def test_create_refuses_offset_overflow(device):
         else:
             with pytest.raises(OvmError, match="32-bit"):
                 eng.load_state_dict(sd)
+
+
+@pytest.mark.parametrize("precision", [1, 3])
+def test_pack_weight_host_and_device_images_are_bit_identical(device, precision):
+    """One format, two writers: ovm_host_pack_weight (what the model handles upload) and pack_weight_kernel behind ovm_g_pack_weight."""
+    import pack_cases as pc
+    L = _lib()
+    for N, K, Kpad in pc.SHAPES:
+        w = pc.matrix(N, K)
+        rc, host = pc.host_image(L, w, Kpad, precision)
+        assert rc == 0
+        dev = torch.full((host.size,), 0x2BCD, dtype=torch.int16, device=device)      # the kernel writes the padding too
+        wd = torch.from_numpy(w).to(device)
+        lo = dev.data_ptr() + 64 if precision == 3 else None
+        assert L.ovm_g_pack_weight(wd.data_ptr(), N, K, Kpad, dev.data_ptr(), lo, _stream()) == 0
+        got = dev.cpu().numpy().view(np.uint16)
+        bad = np.flatnonzero(got != host)
+        assert bad.size == 0, (N, K, Kpad, bad[:8], got[bad[:8]], host[bad[:8]])

@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 import torch
 
+import pack_cases as pc
 from common import build_cfg
 from ovmono3d_amd.config import CfgNode, get_cfg, get_cfg_defaults
 from ovmono3d_amd.defaults import make_cfg
@@ -164,3 +165,22 @@ def test_clip_pos_embed_resize_matches_torch_antialiased_bicubic(M, G):
     assert L.ovm_host_resize_pos_embed_aa(src.ctypes.data, M, D, G, out.ctypes.data) == 0
     assert np.abs(out - ref.numpy()).max() < 2e-6
     assert np.array_equal(out[0], src[0])                                     # class row untouched
+
+
+@pytest.mark.parametrize("precision", [1, 3])
+@pytest.mark.parametrize("N,K,Kpad", pc.SHAPES)
+def test_host_pack_weight_matches_numpy_bit_for_bit(N, K, Kpad, precision):
+    """The packed weight image every model handle uploads (csrc/loader.hip) against a numpy statement of the format."""
+    from ovmono3d_amd import lib
+    w = pc.matrix(N, K)
+    rc, got = pc.host_image(lib.load(), w, Kpad, precision)
+    assert rc == 0
+    ref = pc.reference_image(w, Kpad, precision)
+    assert got.shape == ref.shape and np.array_equal(got, ref), np.flatnonzero(got != ref)[:8]
+
+
+@pytest.mark.parametrize("N,K,Kpad,precision,code", [(4, 70, 64, 1, -1), (0, 8, 64, 3, -1), (4, 8, 48, 3, -4)])
+def test_host_pack_weight_rejects_bad_shapes_and_leaves_out_untouched(N, K, Kpad, precision, code):
+    from ovmono3d_amd import lib
+    rc, out = pc.host_image(lib.load(), np.ones((N, K), np.float32), Kpad, precision)
+    assert rc == code and (out == 0xABCD).all()
