@@ -417,6 +417,17 @@ int ovm_g_groupnorm(const float* x, int32_t B, int32_t HW, int32_t C, int32_t gr
                     ovm_stream_t stream);
 int ovm_g_msdeform(const float* value, const int32_t* shapes_hw, int32_t L, int32_t B, int32_t S, int32_t Q, int32_t H, int32_t dh, int32_t P,
                    const float* loc, const float* w, float* out, ovm_stream_t stream);
+/* GroundingDINO BiMultiHeadAttention.forward (groundingdino/models/GroundingDINO/fuse_modules.py) as reached from
+ * roi_heads_gdino.py:186, after its four input projections: with A = scale * Q K_text^T per head (head h = columns h*dh ..),
+ * ctx_img = softmax over the T text tokens of A, times V_text; ctx_text = softmax over the S image tokens of A^T, times V_img.
+ * q, v_img: device fp32 [S][H*dh] (row strides ldq, ldvi); k_text, v_text: [T][H*dh] (ldk, ldvt); row strides multiples of 4 floats,
+ * rows 16-byte aligned. Outputs (device): ctx_img fp32 [S][ldc] and / or its split-fp16 image ctx_img_hi / ctx_img_lo [S][ldc]
+ * halves (either may be NULL, not both ctx_img and ctx_img_hi); ctx_text fp32 [T][H*dh]. dh = 256 and T <= 256 run the one-pass
+ * matrix-core kernel, anything else (dh % 4 == 0, dh <= 512) or generic != 0 the four generic kernels. Owns its scratch and
+ * synchronises the stream. OVM_ERR_INVALID (nothing launched) for a null pointer or a non-positive dimension. */
+int ovm_g_biattn(const float* q, int32_t ldq, const float* k_text, int32_t ldk, const float* v_img, int32_t ldvi, const float* v_text,
+                 int32_t ldvt, int32_t S, int32_t T, int32_t H, int32_t dh, float scale, float* ctx_img, uint16_t* ctx_img_hi,
+                 uint16_t* ctx_img_lo, int32_t ldc, float* ctx_text, int32_t generic, ovm_stream_t stream);
 int ovm_g_sine_embed(const float* pos, int64_t n, int32_t nc, int32_t F, float temperature, float* out, ovm_stream_t stream);
 int ovm_g_normalize_image(const OvmImage* image, const float* mean, const float* stdv, int32_t flip_channels, float* out_nhwc,
                           ovm_stream_t stream);

@@ -747,10 +747,11 @@ int forward_impl(Run& r) {
     float* tkv = r.f32((size_t)T * 2 * E);              // [text_proj | values_text_proj]
     SplitBuf cv = r.split((size_t)S, E);
     float* ct = r.f32((size_t)T * E);
-    const int chunk = 128, nchunk = (S + chunk - 1) / chunk;
-    float* sc = r.f32((size_t)HF * T * S);
-    float* stat = r.f32((size_t)HF * T * 2);
-    float* part = r.f32((size_t)nchunk * T * E);
+    const BiAttnWs bw = biattn_workspace(S, T, HF, dhf, false);       // the matrix-core path needs neither sc nor stat
+    float* sc = bw.sc ? r.f32(bw.sc) : nullptr;
+    float* stat = bw.stat ? r.f32(bw.stat) : nullptr;
+    float* part = r.f32(bw.part);
+    float* bml = bw.ml ? r.f32(2 * bw.ml) : nullptr;
     float* text2 = r.f32((size_t)T * D);
     float* tqk = r.f32((size_t)T * 2 * D); float* tv = r.f32((size_t)T * D); float* tctx = r.f32((size_t)T * D);
     float* tff = r.f32((size_t)T * c.ffn_dim);
@@ -773,8 +774,9 @@ int forward_impl(Run& r) {
         BiAttnParams b; memset(&b, 0, sizeof(b));
         b.qv = qvv; b.ldq = 2 * E; b.kt = tkv; b.ldk = 2 * E; b.vv = qvv + E; b.ldvv = 2 * E; b.vt = tkv + E; b.ldvt = 2 * E;
         b.S = S; b.T = T; b.H = HF; b.dh = dhf; b.scale = 1.0f / sqrtf((float)dhf);
-        b.cv_hi = cv.hi; b.cv_lo = cv.lo; b.ldcv = cv.ld; b.ct = ct; b.sc = sc; b.stat = stat; b.part = part; b.chunk = chunk; b.nchunk = nchunk;
-        r.chk(launch_biattn(b, s), "biattn"); r.launches += 3;
+        b.cv_hi = cv.hi; b.cv_lo = cv.lo; b.ldcv = cv.ld; b.ct = ct; b.sc = sc; b.stat = stat; b.part = part; b.chunk = bw.chunk; b.nchunk = bw.nchunk;
+        if (bml) { b.bm = bml; b.bl = bml + bw.ml; }
+        r.chk(launch_biattn(b, s), "biattn"); r.launches += bw.mfma ? 1 : 3;
       }
       // the two halves of the layer from here on touch disjoint buffers: text side (ot, text enhancer -> text) on the text
       // branch, image side (ov, deformable self-attention, FFN -> vis) on the main one; joined at the end of the layer

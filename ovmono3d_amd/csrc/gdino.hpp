@@ -64,6 +64,9 @@ int launch_relpos_tables(const float* q, int ldq, int M, int H, int DH, int gh, 
                          float* rel_w, int ldrel, hipStream_t s);
 
 // ---- bi-directional image <-> text attention of the fusion layer (4 heads x 256, T text tokens, S image tokens) ---------------
+// Two paths. dh = 256 (biattn_mfma_supported): one pass on the matrix cores, one workgroup per (chunk of 64 image tokens, head), plus
+// a combine launch - scores are computed once and used for both directions on chip. Anything else: the generic four kernels (image
+// side writing the raw scores, column statistics, text-side partials per 128 image tokens, combine). Same function, fp32 throughout.
 struct BiAttnParams {
   const float* qv; int ldq;           // [S][E] image queries  (vision_proj)
   const float* kt; int ldk;           // [T][E] text keys      (text_proj)
@@ -73,12 +76,19 @@ struct BiAttnParams {
   half_t* cv_hi; half_t* cv_lo; int ldcv;   // [S][E] image-side context (split fp16: A operand of out_vision_proj)
   float* cv;                          // or fp32 [S][E]
   float* ct;                          // [T][E] text-side context (fp32)
-  float* sc;                          // workspace [H][T][S] raw scaled scores
-  float* stat;                        // workspace [H][T][2] (max, sum)
-  float* part;                        // workspace [nchunk][T][E]
-  int chunk, nchunk;                  // S split for the text side
+  float* sc;                          // generic path: workspace [H][T][S] raw scaled scores
+  float* stat;                        // generic path: workspace [H][T][2] (max, sum)
+  float* part;                        // workspace [nchunk][T][E]: per-chunk partial text context
+  float* bm; float* bl;               // matrix-core path: workspaces [nchunk][H][T], per-chunk column maximum and sum of exp(score - max)
+  int chunk, nchunk;                  // S split for the text side: biattn_workspace's
+  int generic;                        // force the generic path (tests run both on the same inputs)
 };
-int launch_biattn(const BiAttnParams& p, hipStream_t s);      // 4 launches
+// workspace sizes in floats (0: not used by the path taken) and the chunking launch_biattn expects for this geometry
+struct BiAttnWs { bool mfma; int chunk, nchunk; size_t sc, stat, part, ml; };
+bool biattn_mfma_supported(int H, int dh, int T);
+BiAttnWs biattn_workspace(int S, int T, int H, int dh, bool generic);
+// OVM_ERR_INVALID (nothing launched) for a null pointer or a non-positive dimension; 2 launches (matrix-core path) or 4 (generic)
+int launch_biattn(const BiAttnParams& p, hipStream_t s);
 
 // ---- multi-scale deformable attention with the softmax over (levels x points) and the sampling locations fused ----------------
 struct MsDeformParams {

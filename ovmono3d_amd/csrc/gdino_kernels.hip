@@ -1,6 +1,7 @@
 // Fused device kernels of the native GroundingDINO engine (see gdino.hpp). gfx950, wave = 64.
 #include <hip/hip_runtime.h>
 #include <cmath>
+#include <cstring>
 #include "gdino.hpp"
 
 namespace ovm {
@@ -595,6 +596,272 @@ __global__ void biattn_txt_combine_kernel(const BiAttnParams p) {
   p.ct[(size_t)t * E + e] = acc / p.stat[2 * (h * p.T + t) + 1];
 }
 
+// One-pass bi-attention on the matrix cores (dh = 256): one workgroup of 4 waves per (chunk of kBiChunk image tokens, head). The
+// head's text keys and values are staged in LDS in blocks of 32 text tokens; the chunk's scores against a block are computed ONCE
+// (exact fp32 products, v_mfma_f32_16x16x4_f32, attn_f32_kernel's S^T = K Q^T arrangement: a lane's accumulator registers are 8
+// text tokens of one image token) and serve both directions while they are in registers:
+//   image side: softmax over the text tokens (online across blocks), context^T = V_text^T P^T with the probabilities as B operand
+//               straight from the accumulators; split-fp16 rows written where biattn_img_kernel writes them;
+//   text side:  the chunk's column maximum m and p' = exp(score - m) (rows past S: 0), column sum l, and the partial context
+//               part[c][t][:] = sum_s p'[s][t] V_img[s][:] - p' goes through LDS transposed, every wave takes 64 of the 256 value
+//               columns over all rows of the chunk, so the image values are read once and no partial is summed across waves; m and l
+//               are reduced across the waves through LDS in wave order. biattn_mfma_combine_kernel rescales the chunks to the
+//               global maximum (attn_tail_combine_kernel's algebra) - no score workspace, no statistics pass, no atomics.
+// MFMA operand maps (lane = (li = lane & 15, g = lane >> 4); A[row li][k g], B[k g][col li], D[row 4 g + r][col li]). The contracted
+// index may be permuted freely as long as A and B agree, and a tile's 16 rows / columns may be any 16 indices:
+//   scores   k-step (j, c) contracts head dims 16 j + 4 g + c: a 16-byte read per lane and j on both sides (Q from HBM, K from LDS);
+//   contexts value tile (dg, j) holds columns dg * 64 + 4 i + j, i = 0..15: one 16-byte read feeds the four tiles j = 0..3, and a
+//            lane's results for j = 0..3 are four consecutive columns (one 16-byte / 8-byte store).
+// LDS row strides 260 (keys, values) and 68 (p' transposed) floats: the 16 lanes of a 16-byte read phase lie 4 or 260 = 4 (mod 64)
+// floats apart - 64 distinct banks (attn_f32_kernel row).
+// Chunk = 64: 16 image tokens per wave, 74.5 KiB of LDS per workgroup so that two fit a CU's 160 KiB; at the headline 6,015 tokens
+// x 4 heads that is 376 workgroups, all resident at once on 256 CUs (512 slots), up to 8,192 tokens still in one round (the largest
+// images, ~10,000 tokens, add a fifth of a second one); 128 tokens would leave 188 workgroups on 256 CUs and need 8 waves for the same
+// registers per wave. The chunk does not depend on S, so a plan sizes part / m / l with biattn_workspace like the launcher.
+constexpr int kBiChunk = 64, kBiTB = 32, kBiDH = 256, kBiLDK = kBiDH + 4, kBiLDP = kBiChunk + 4;
+constexpr int kBiSmem = (2 * kBiTB * kBiLDK + kBiTB * kBiLDP + 8 * kBiTB) * 4;
+
+__global__ __launch_bounds__(256, 2) void biattn_mfma_kernel(const BiAttnParams p) {
+  constexpr int DH = kBiDH, TB = kBiTB, CS = kBiChunk, LDK = kBiLDK, LDP = kBiLDP;
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  float* Ks = (float*)smem_raw;                // [TB][LDK] text keys of the block
+  float* Vs = Ks + TB * LDK;                   // [TB][LDK] text values
+  float* Pt = Vs + TB * LDK;                   // [TB][LDP] p' transposed: [text token][image token of the chunk]
+  float* wmax = Pt + TB * LDP;                 // [4 waves][TB]
+  float* wsum = wmax + 4 * TB;                 // [4 waves][TB]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, g = lane >> 4;
+  const int c = blockIdx.x, h = blockIdx.y, s0 = c * CS;
+  const int E = p.H * DH;
+  const int srow = s0 + wave * 16 + li;
+  const bool qvalid = srow < p.S;
+  const float* qr = p.qv + (size_t)(qvalid ? srow : p.S - 1) * p.ldq + h * DH + 4 * g;   // rows past S: the last row, results discarded
+  f32x4 o[4][4];
+#pragma unroll
+  for (int dg = 0; dg < 4; ++dg)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[dg][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  float mi = -INFINITY, lsum = 0.f;
+
+  for (int t0 = 0; t0 < p.T; t0 += TB) {
+    const int nt = (p.T - t0 < TB) ? p.T - t0 : TB;
+    const int ntt = (nt + 15) >> 4;            // 16-token tiles of the block that hold a text token
+    f32x4 qf[16];                              // re-read per text block (cache hits past the first): 64 registers free for the contexts
+#pragma unroll
+    for (int j = 0; j < 16; ++j) qf[j] = *(const f32x4*)(qr + 16 * j);
+    __syncthreads();
+    for (int i = tid; i < TB * (DH / 4); i += 256) {
+      const int r = i / (DH / 4), cc = (i - r * (DH / 4)) * 4;
+      f32x4 kv = (f32x4){0.f, 0.f, 0.f, 0.f}, vv = kv;
+      if (r < nt) {
+        kv = *(const f32x4*)(p.kt + (size_t)(t0 + r) * p.ldk + h * DH + cc);
+        vv = *(const f32x4*)(p.vt + (size_t)(t0 + r) * p.ldvt + h * DH + cc);
+      }
+      *(f32x4*)(Ks + r * LDK + cc) = kv;
+      *(f32x4*)(Vs + r * LDK + cc) = vv;
+    }
+    __syncthreads();
+    // ---- scores: sc[tt][r] = scale * q[srow] . k[t0 + 16 tt + 4 g + r]
+    // Sixteen accumulators per token tile, one per 16-byte slice j of the head dimension (4 MFMAs = 16 products each), summed as a
+    // tree: 20 roundings deep instead of the 256 of a single chain. The scores set the error of both softmaxes (an absolute error of
+    // a score is a relative error of a probability); the generic kernels sum 4 products per lane and a 6-level wave reduction.
+    f32x4 sc[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+    for (int tt = 0; tt < 2; ++tt) {
+      if (tt < ntt) {                          // wave-uniform; a tile without a text token keeps score 0 and is masked or dropped below
+        const float* kr = Ks + (tt * 16 + li) * LDK + 4 * g;
+        f32x4 half[2];
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf) {       // eight accumulators at a time: registers
+          f32x4 a[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const f32x4 kq = *(const f32x4*)(kr + 16 * (8 * hf + j));
+            a[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int cc = 0; cc < 4; ++cc) a[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(kq[cc], qf[8 * hf + j][cc], a[j], 0, 0, 0);
+          }
+#pragma unroll
+          for (int st = 4; st > 0; st >>= 1)
+#pragma unroll
+            for (int j = 0; j < st; ++j) a[j] += a[j + st];
+          half[hf] = a[0];
+        }
+        sc[tt] = half[0] + half[1];
+      }
+    }
+#pragma unroll
+    for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sc[tt][r] *= p.scale;
+    // ---- text side: this wave's column maxima over its valid image tokens
+#pragma unroll
+    for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float v = qvalid ? sc[tt][r] : -INFINITY;
+        v = fmaxf(v, __shfl_xor(v, 1, 64)); v = fmaxf(v, __shfl_xor(v, 2, 64));
+        v = fmaxf(v, __shfl_xor(v, 4, 64)); v = fmaxf(v, __shfl_xor(v, 8, 64));
+        if (li == 0) wmax[wave * TB + tt * 16 + 4 * g + r] = v;
+      }
+    // ---- image side: online softmax over the text tokens, context^T += V_text^T P^T
+    {
+      f32x4 pr[2];
+      float bm = -INFINITY;
+#pragma unroll
+      for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          pr[tt][r] = (tt * 16 + 4 * g + r < nt) ? sc[tt][r] : -INFINITY;
+          bm = fmaxf(bm, pr[tt][r]);
+        }
+      bm = fmaxf(bm, __shfl_xor(bm, 16, 64));
+      bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
+      const float mn = fmaxf(mi, bm);          // finite: every block holds a text token
+      const float alpha = expf(mi - mn);       // first block: 0
+      mi = mn;
+      lsum *= alpha;
+      if (t0 > 0) {
+#pragma unroll
+        for (int dg = 0; dg < 4; ++dg)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) { o[dg][j][0] *= alpha; o[dg][j][1] *= alpha; o[dg][j][2] *= alpha; o[dg][j][3] *= alpha; }
+      }
+#pragma unroll
+      for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { pr[tt][r] = expf(pr[tt][r] - mn); lsum += pr[tt][r]; }
+#pragma unroll
+      for (int tt = 0; tt < 2; ++tt) {
+        if (tt < ntt) {                        // wave-uniform; the probabilities of a skipped tile are all 0
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float* vr = Vs + (tt * 16 + 4 * g + r) * LDK + 4 * li;
+#pragma unroll
+            for (int dg = 0; dg < 4; ++dg) {
+              const f32x4 vv = *(const f32x4*)(vr + dg * 64);
+#pragma unroll
+              for (int j = 0; j < 4; ++j) o[dg][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(vv[j], pr[tt][r], o[dg][j], 0, 0, 0);
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();
+    // ---- text side: p' = exp(score - chunk maximum) to LDS (transposed), column sums, then part = P'^T V_img for this wave's 64 columns
+    f32x4 vimg[4][4];                          // rows s0 + 16 sb + 4 g + cc (clamped: their p' is 0), columns wave * 64 + 4 li ..
+    {
+      const float* vb = p.vv + h * DH + wave * 64 + 4 * li;
+#pragma unroll
+      for (int sb = 0; sb < 4; ++sb)
+#pragma unroll
+        for (int cc = 0; cc < 4; ++cc) {
+          const int row = s0 + sb * 16 + 4 * g + cc;
+          vimg[sb][cc] = *(const f32x4*)(vb + (size_t)(row < p.S ? row : p.S - 1) * p.ldvv);
+        }
+    }
+#pragma unroll
+    for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int t = tt * 16 + 4 * g + r;
+        const float m = fmaxf(fmaxf(wmax[t], wmax[TB + t]), fmaxf(wmax[2 * TB + t], wmax[3 * TB + t]));
+        const float pv = qvalid ? expf(sc[tt][r] - m) : 0.f;
+        Pt[t * LDP + wave * 16 + li] = pv;
+        float v = pv;
+        v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 8, 64);
+        if (li == 0) wsum[wave * TB + t] = v;
+      }
+    __syncthreads();
+    if (tid < nt) {
+      const size_t oi = ((size_t)c * p.H + h) * p.T + t0 + tid;
+      p.bm[oi] = fmaxf(fmaxf(wmax[tid], wmax[TB + tid]), fmaxf(wmax[2 * TB + tid], wmax[3 * TB + tid]));
+      p.bl[oi] = ((wsum[tid] + wsum[TB + tid]) + wsum[2 * TB + tid]) + wsum[3 * TB + tid];
+    }
+    f32x4 ta[2][4];
+#pragma unroll
+    for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) ta[tt][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int sb = 0; sb < 4; ++sb) {
+      const f32x4 p0 = *(const f32x4*)(Pt + li * LDP + sb * 16 + 4 * g);
+      const f32x4 p1 = *(const f32x4*)(Pt + (16 + li) * LDP + sb * 16 + 4 * g);
+#pragma unroll
+      for (int cc = 0; cc < 4; ++cc)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          ta[0][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(p0[cc], vimg[sb][cc][j], ta[0][j], 0, 0, 0);
+          if (ntt > 1) ta[1][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(p1[cc], vimg[sb][cc][j], ta[1][j], 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int t = tt * 16 + 4 * g + r;
+        if (t < nt)
+          *(f32x4*)(p.part + ((size_t)c * p.T + t0 + t) * E + h * DH + wave * 64 + 4 * li) =
+              (f32x4){ta[tt][0][r], ta[tt][1][r], ta[tt][2][r], ta[tt][3][r]};
+      }
+  }
+  // ---- image side: normalise and write
+  lsum += __shfl_xor(lsum, 16, 64);
+  lsum += __shfl_xor(lsum, 32, 64);
+  if (!qvalid) return;
+  const float inv = 1.0f / lsum;
+#pragma unroll
+  for (int dg = 0; dg < 4; ++dg)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const f32x4 y = (f32x4){o[dg][0][r] * inv, o[dg][1][r] * inv, o[dg][2][r] * inv, o[dg][3][r] * inv};
+      const size_t oo = (size_t)srow * p.ldcv + h * DH + dg * 64 + 16 * g + 4 * r;
+      if (p.cv) *(f32x4*)(p.cv + oo) = y;
+      if (p.cv_hi) {
+        half4 hh, ll;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { half_t a, b; split_f16_nt(y[i], a, b); hh[i] = a; ll[i] = b; }
+        *(half4*)(p.cv_hi + oo) = hh;
+        if (p.cv_lo) *(half4*)(p.cv_lo + oo) = ll;
+      }
+    }
+}
+
+// ct[t][e] = sum_c part[c][t][e] exp(m_c - M) / sum_c l_c exp(m_c - M), M = max_c m_c. One workgroup per (text token, 64 columns):
+// all 256 threads fetch the chunks' partial rows into LDS, 128 chunks at a time (every load independent - a thread that walks the
+// chunks itself pays one memory latency per chunk: 42 us at 94 chunks), then the first wave sums them from LDS as ONE chain in
+// increasing chunk order. No atomics; the result depends on the inputs only.
+constexpr int kBiCombTile = 128;
+__global__ __launch_bounds__(256) void biattn_mfma_combine_kernel(const BiAttnParams p) {
+  __shared__ float xs[kBiCombTile][64];
+  __shared__ float ws[kBiCombTile], ls[kBiCombTile], red[4];
+  const int E = p.H * p.dh, nb = E / 64;                   // dh % 64 == 0: a workgroup's columns lie in one head
+  const int t = blockIdx.x / nb, e0 = (blockIdx.x - t * nb) * 64, h = e0 / p.dh;
+  const int tid = threadIdx.x, lane = tid & 63, cs = tid >> 6;
+  const size_t HT = (size_t)p.H * p.T, TE = (size_t)p.T * E;
+  const float* mp = p.bm + (size_t)h * p.T + t;
+  const float* lp = p.bl + (size_t)h * p.T + t;
+  const float* pp = p.part + (size_t)t * E + e0 + lane;
+  float M = -INFINITY;
+  for (int c = tid; c < p.nchunk; c += 256) M = fmaxf(M, mp[c * HT]);
+  M = wave_max(M);
+  if (lane == 0) red[cs] = M;
+  __syncthreads();
+  M = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  float num = 0.f, den = 0.f;
+  for (int c0 = 0; c0 < p.nchunk; c0 += kBiCombTile) {
+    const int n = (p.nchunk - c0 < kBiCombTile) ? p.nchunk - c0 : kBiCombTile;
+    __syncthreads();
+    if (tid < n) { ws[tid] = expf(mp[(c0 + tid) * HT] - M); ls[tid] = lp[(c0 + tid) * HT]; }
+#pragma unroll 8
+    for (int c = cs; c < n; c += 4) xs[c][lane] = pp[(c0 + c) * TE];
+    __syncthreads();
+    if (tid < 64) {
+      for (int c = 0; c < n; ++c) { const float w = ws[c]; num += xs[c][lane] * w; den += ls[c] * w; }
+    }
+  }
+  if (tid < 64) p.ct[(size_t)t * E + e0 + lane] = num / den;
+}
+
 // ------------------------------------------------------------------------------------------------------------------------------
 // Multi-scale deformable attention (Deformable-DETR sampling = F.grid_sample bilinear, zeros padding, align_corners=False), one
 // thread per (query, head, channel); the softmax over the L*P logits and the sampling locations are computed inline.
@@ -870,8 +1137,35 @@ int launch_relpos_tables(const float* q, int ldq, int M, int H, int DH, int gh, 
   return hipGetLastError() == hipSuccess ? OVM_OK : OVM_ERR_HIP;
 }
 
+bool biattn_mfma_supported(int H, int dh, int T) { return dh == kBiDH && H >= 1 && H <= 65535 && T >= 1 && T <= 256; }
+
+BiAttnWs biattn_workspace(int S, int T, int H, int dh, bool generic) {
+  BiAttnWs w; memset(&w, 0, sizeof(w));
+  if (S <= 0 || T <= 0 || H <= 0 || dh <= 0) return w;
+  w.mfma = !generic && biattn_mfma_supported(H, dh, T);
+  w.chunk = w.mfma ? kBiChunk : 128;
+  w.nchunk = (int)(((long)S + w.chunk - 1) / w.chunk);
+  w.part = (size_t)w.nchunk * T * H * dh;
+  if (w.mfma) { w.ml = (size_t)w.nchunk * H * T; }
+  else { w.sc = (size_t)H * T * S; w.stat = (size_t)H * T * 2; }
+  return w;
+}
+
 int launch_biattn(const BiAttnParams& p, hipStream_t s) {
-  if (p.dh % 4 || p.dh > 512 || p.chunk > 128 || p.chunk <= 0) return OVM_ERR_SHAPE;
+  if (p.S <= 0 || p.T <= 0 || p.H <= 0 || p.dh <= 0) return OVM_ERR_INVALID;
+  if (!p.qv || !p.kt || !p.vv || !p.vt || !p.ct || !p.part || (!p.cv && !p.cv_hi)) return OVM_ERR_INVALID;
+  const BiAttnWs w = biattn_workspace(p.S, p.T, p.H, p.dh, p.generic != 0);
+  if (w.mfma ? (!p.bm || !p.bl) : (!p.sc || !p.stat)) return OVM_ERR_INVALID;
+  if (p.chunk != w.chunk || p.nchunk != w.nchunk) return OVM_ERR_SHAPE;
+  if (w.mfma) {
+    if (p.ldq % 4 || p.ldk % 4 || p.ldvv % 4 || p.ldvt % 4 || p.ldcv % 4) return OVM_ERR_SHAPE;
+    static bool set = false;
+    if (!set) { (void)hipFuncSetAttribute((const void*)biattn_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kBiSmem); set = true; }
+    hipLaunchKernelGGL(biattn_mfma_kernel, dim3((unsigned)p.nchunk, (unsigned)p.H), dim3(256), kBiSmem, s, p);
+    hipLaunchKernelGGL(biattn_mfma_combine_kernel, dim3((unsigned)(p.T * (p.H * p.dh / 64))), dim3(256), 0, s, p);
+    return hipGetLastError() == hipSuccess ? OVM_OK : OVM_ERR_HIP;
+  }
+  if (p.dh % 4 || p.dh > 512) return OVM_ERR_SHAPE;
   if (p.dh <= 256) hipLaunchKernelGGL(biattn_img_kernel<1>, dim3((unsigned)(((long)p.S * p.H + 3) / 4)), dim3(256), 0, s, p);
   else hipLaunchKernelGGL(biattn_img_kernel<2>, dim3((unsigned)(((long)p.S * p.H + 3) / 4)), dim3(256), 0, s, p);
   hipLaunchKernelGGL(biattn_stats_kernel, dim3(p.H * p.T), dim3(256), 0, s, p);

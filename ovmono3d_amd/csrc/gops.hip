@@ -8,6 +8,7 @@
 #include "../../include/ovm3d.h"
 #include "kernels.hpp"
 #include "det2d.hpp"
+#include "gdino.hpp"
 
 using namespace ovm;
 
@@ -558,6 +559,27 @@ int ovm_g_rowmax(const float* x, int32_t rows, int32_t cols, int32_t ld, float* 
   if (rows <= 0) return OVM_OK;
   hipLaunchKernelGGL(rowmax_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, rows, cols, ld, out);
   return hipGetLastError() == hipSuccess ? OVM_OK : OVM_ERR_HIP;
+}
+
+int ovm_g_biattn(const float* q, int32_t ldq, const float* k_text, int32_t ldk, const float* v_img, int32_t ldvi, const float* v_text,
+                 int32_t ldvt, int32_t S, int32_t T, int32_t H, int32_t dh, float scale, float* ctx_img, uint16_t* ctx_img_hi,
+                 uint16_t* ctx_img_lo, int32_t ldc, float* ctx_text, int32_t generic, ovm_stream_t stream) {
+  if (!q || !k_text || !v_img || !v_text || !ctx_text || (!ctx_img && !ctx_img_hi) || S <= 0 || T <= 0 || H <= 0 || dh <= 0) return OVM_ERR_INVALID;
+  const BiAttnWs w = biattn_workspace(S, T, H, dh, generic != 0);
+  const size_t n = w.sc + w.stat + w.part + 2 * w.ml;
+  float* ws = nullptr;
+  if (hipMalloc((void**)&ws, n * sizeof(float)) != hipSuccess) return OVM_ERR_HIP;
+  BiAttnParams b; memset(&b, 0, sizeof(b));
+  b.qv = q; b.ldq = ldq; b.kt = k_text; b.ldk = ldk; b.vv = v_img; b.ldvv = ldvi; b.vt = v_text; b.ldvt = ldvt;
+  b.S = S; b.T = T; b.H = H; b.dh = dh; b.scale = scale;
+  b.cv = ctx_img; b.cv_hi = (half_t*)ctx_img_hi; b.cv_lo = (half_t*)ctx_img_lo; b.ldcv = ldc; b.ct = ctx_text;
+  b.part = ws; b.chunk = w.chunk; b.nchunk = w.nchunk; b.generic = generic != 0;
+  if (w.mfma) { b.bm = ws + w.part; b.bl = b.bm + w.ml; }
+  else { b.sc = ws + w.part; b.stat = b.sc + w.sc; }
+  int r = launch_biattn(b, (hipStream_t)stream);
+  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && !r) r = OVM_ERR_HIP;
+  (void)hipFree(ws);
+  return r;
 }
 
 int ovm_g_topk(const float* scores, int32_t n, int32_t k, int32_t* out_idx, ovm_stream_t stream) {

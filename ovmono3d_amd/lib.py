@@ -192,7 +192,7 @@ EXPORTS = [
     "ovm_op_cube_decode", "ovm_op_nms", "ovm_op_rpn_proposals", "ovm_op_boxhead_post", "ovm_debug_copy", "ovm_set_corun", "ovm_profile_enable", "ovm_profile_read",
     "ovm_comm_unique_id", "ovm_comm_init", "ovm_comm_destroy", "ovm_tune_set", "ovm_gdino_postprocess", "ovm_box3d_iou", "ovm_eval_iou2d", "ovm_eval_match", "ovm_host_pil_bilinear_coeffs", "ovm_resize_bilinear_u8", "ovm_resize_bilinear_f32",
     "ovm_g_pack_weight", "ovm_host_pack_weight", "ovm_g_linear", "ovm_g_layernorm", "ovm_g_bmm", "ovm_g_bmm2", "ovm_g_softmax", "ovm_g_softmax2", "ovm_g_eltwise", "ovm_g_gather_rows",
-    "ovm_g_groupnorm", "ovm_g_msdeform", "ovm_g_sine_embed", "ovm_g_normalize_image", "ovm_g_topk", "ovm_g_rowmax",
+    "ovm_g_groupnorm", "ovm_g_biattn", "ovm_g_msdeform", "ovm_g_sine_embed", "ovm_g_normalize_image", "ovm_g_topk", "ovm_g_rowmax",
     "ovm_gdino_create", "ovm_gdino_destroy", "ovm_gdino_last_error", "ovm_gdino_forward", "ovm_gdino_detect", "ovm_gdino_set_force_topk",
     "ovm_gdino_debug_copy", "ovm_debug_set_ptr", "ovm_gdino_num_queries", "ovm_gdino_last_outputs", "ovm_infer",
     "ovm_host_jpeg_info", "ovm_host_jpeg_entropy_decode", "ovm_jpeg_reconstruct",
@@ -321,6 +321,7 @@ def load() -> C.CDLL:
     lib.ovm_g_gather_rows.argtypes = [vp, i32, vp, i64, i32, i32, vp, vp]
     lib.ovm_g_groupnorm.argtypes = [vp, i32, i32, i32, i32, vp, vp, f32, vp, vp]
     lib.ovm_g_msdeform.argtypes = [vp, C.POINTER(i32), i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]
+    lib.ovm_g_biattn.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, i32, vp, i32, vp]
     lib.ovm_g_sine_embed.argtypes = [vp, i64, i32, i32, f32, vp, vp]
     lib.ovm_g_normalize_image.argtypes = [C.POINTER(OvmImage), C.POINTER(f32), C.POINTER(f32), i32, vp, vp]
     lib.ovm_g_topk.argtypes = [vp, i32, i32, vp, vp]
