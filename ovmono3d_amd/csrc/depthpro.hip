@@ -1,8 +1,8 @@
 // Depth Pro (include/ovm3d.h, "Depth Pro, metric depth"): Hugging Face DepthProForDepthEstimation + DepthProImageProcessor as
 // OVMono3D-GEO calls depth_pro's model.infer (reference tools/ovmono3d_geo.py:267,290-295).
 //
-// The three encoders are ovm::tower_create_ex instances (api.hip: DINOv2 blocks, HF key names, float input as strided views, taps,
-// final LayerNorm). Neck, fusion and the first two head layers go through launch_gemm (1x1: row-major, 3x3: A_CONV3X3, transposed
+// The three encoders are Towers of the Hugging Face Dinov2Model family (tower.hpp: float input as strided views, taps, final
+// LayerNorm). Neck, fusion and the first two head layers go through launch_gemm (1x1: row-major, 3x3: A_CONV3X3, transposed
 // convolutions: EPI_CONVT). The kernels of this file:
 //   dp_pyramid_kernel     uint8 image -> (x / 255 - 0.5) / 0.5 -> bilinear S x S -> the 0.5 and 0.25 levels, one pass; a thread owns a
 //                         4 x 4 block of level 0, which holds every tap of its 2 x 2 level-1 cells and of its level-2 cell
@@ -28,7 +28,7 @@
 
 #include "../../include/ovm3d.h"
 #include "kernels.hpp"
-#include "sam.hpp"
+#include "tower.hpp"
 #include "depthpro.hpp"
 #include "loader.hpp"
 
@@ -67,7 +67,7 @@ struct OvmDepthPro : ovm::Loader {
   OvmDepthProConfig cfg;
   int device = 0;
   DepthProGeom geo;
-  OvmHandle *patch = nullptr, *image = nullptr, *fov = nullptr;
+  Tower patch, image, fov;
   int D = 0, T = 0, F = 0;
   bool ident4 = false;                       // the last projection is nn.Identity (inter_dims[1] == fusion_dim)
   int side[5] = {0}, upc[5] = {0};           // decoder level sides (2 g .. 32 g) and the channel counts entering the projections
@@ -428,9 +428,9 @@ size_t plan(const OvmDepthPro* m, char* base, Plan* pl) {
   return off;
 }
 
-int run_tower(OvmDepthPro* m, OvmHandle* t, const TowerViews& v, int ntap, const int* blk, float* const* taps, float* fin, const char* what, hipStream_t s) {
+int run_tower(OvmDepthPro* m, Tower* t, const TowerViews& v, int ntap, const int* blk, float* const* taps, float* fin, const char* what, hipStream_t s) {
   const int r = tower_forward_f32(t, v, ntap, blk, taps, fin, s);
-  if (r) m->err = std::string(what) + ": " + ovm_last_error(t);
+  if (r) m->err = std::string(what) + ": " + t->err;
   return r;
 }
 
@@ -490,9 +490,7 @@ const char* ovm_depthpro_last_error(const OvmDepthPro* m) { return m ? m->err.c_
 int ovm_depthpro_destroy(OvmDepthPro* m) {
   if (!m) return OVM_OK;
   (void)hipSetDevice(m->device);
-  if (m->patch) ovm_destroy(m->patch);
-  if (m->image) ovm_destroy(m->image);
-  if (m->fov) ovm_destroy(m->fov);
+  m->patch.destroy(); m->image.destroy(); m->fov.destroy();
   m->free_all();
   for (hipEvent_t e : m->ev) if (e) (void)hipEventDestroy(e);
   delete m;
@@ -527,20 +525,19 @@ int ovm_depthpro_create(const OvmDepthProConfig* cfg, const OvmTensor* weights, 
   if (wm.get("fusion_stage.final.residual_layer1.batch_norm1.weight")) { m->err = "unsupported: batch norm in the fusion residual units"; return OVM_ERR_UNSUPPORTED; }
   // ---- the three towers
   {
-    OvmConfig t; memset(&t, 0, sizeof(t));
-    t.embed_dim = D; t.depth = c.depth; t.heads = c.heads; t.pos_grid = g; t.canvas = c.crop; t.fpn_channels = 256;
-    t.pooler_res = 1; t.precision = c.precision; t.max_rois = 1; t.tower = OVM_TOWER_DINOV2;
+    TowerConfig t; memset(&t, 0, sizeof(t));
+    t.family = FAM_DINOV2_HF; t.ln_eps = c.ln_eps;
+    t.embed_dim = D; t.depth = c.depth; t.heads = c.heads; t.pos_grid = g; t.canvas = c.crop; t.precision = c.precision;
     for (int i = 0; i < 3; ++i) t.pixel_std[i] = 1.f;
-    TowerOpts o; o.hf_dinov2 = 1; o.ln_eps = c.ln_eps;
-    struct { const char* prefix; OvmHandle** h; int batch; const char* what; bool on; } tw[3] = {
+    struct { const char* prefix; Tower* t; int batch; const char* what; bool on; } tw[3] = {
         {"depth_pro.encoder.patch_encoder.model.", &m->patch, q.total, "patch encoder", true},
         {"depth_pro.encoder.image_encoder.model.", &m->image, 1, "image encoder", true},
         {"fov_model.fov_encoder.model.", &m->fov, 1, "field-of-view encoder", c.use_fov != 0}};
     for (auto& x : tw) {
       if (!x.on) continue;
-      t.max_batch = x.batch;
-      r = tower_create_ex(&t, weights, n_weights, device, x.prefix, &o, x.h);
-      if (r) { m->err = std::string(x.what) + ": " + ovm_last_error(*x.h); return r; }
+      t.max_batch = x.batch; t.prefix = x.prefix;
+      if (!(r = x.t->configure(t))) r = x.t->load(weights, n_weights, device);
+      if (r) { m->err = std::string(x.what) + ": " + x.t->err; return r; }
     }
   }
   // ---- neck: feature_upsample, fuse_image_with_low_res, feature_projection
@@ -625,7 +622,7 @@ int ovm_depthpro_create(const OvmDepthProConfig* cfg, const OvmTensor* weights, 
 }
 
 int ovm_depthpro_workspace(const OvmDepthPro* m, int32_t H, int32_t W, int64_t* bytes) {
-  if (!m || !bytes || H < 1 || W < 1 || !m->patch) return OVM_ERR_INVALID;
+  if (!m || !bytes || H < 1 || W < 1 || !m->patch.fam) return OVM_ERR_INVALID;
   Plan pl;
   *bytes = (int64_t)plan(m, nullptr, &pl);
   return OVM_OK;
@@ -635,7 +632,7 @@ int ovm_depthpro_infer(OvmDepthPro* m, const OvmImage* image, int32_t flip_bgr, 
                        void* workspace, int64_t workspace_bytes, ovm_stream_t stream) {
   if (!m) return OVM_ERR_INVALID;
   m->err.clear();
-  if (!m->patch) { m->err = "handle was not created"; return OVM_ERR_INVALID; }
+  if (!m->patch.fam) { m->err = "handle was not created"; return OVM_ERR_INVALID; }
   if (!image || !image->data || image->height < 1 || image->width < 1) { m->err = "null or empty image"; return OVM_ERR_INVALID; }
   if (!depth_out || !workspace) { m->err = "null depth_out or workspace"; return OVM_ERR_INVALID; }
   if ((uintptr_t)workspace & 255) { m->err = "the workspace must be 256-byte aligned"; return OVM_ERR_INVALID; }
@@ -685,11 +682,11 @@ int ovm_depthpro_infer(OvmDepthPro* m, const OvmImage* image, int32_t flip_bgr, 
           v.v[n++] = TowerView{lev[l] + ((size_t)i * q.stride[l] * ls[l] + (size_t)j * q.stride[l]) * 3, 1, (int64_t)3 * ls[l], 3};
     v.n = n;
     float* taps[2] = {pl.TAP[0], pl.TAP[1]};
-    OVM_TRY(m, run_tower(m, m->patch, v, 2, c.hook_ids, taps, pl.TOK, "patch encoder", s));
+    OVM_TRY(m, run_tower(m, &m->patch, v, 2, c.hook_ids, taps, pl.TOK, "patch encoder", s));
     TowerViews w1; memset(&w1, 0, sizeof(w1));
     w1.n = 1; w1.v[0] = TowerView{pl.P2, 1, (int64_t)3 * (S / 4), 3};
-    OVM_TRY(m, run_tower(m, m->image, w1, 0, nullptr, nullptr, pl.TOKI, "image encoder", s));
-    if (c.use_fov) OVM_TRY(m, run_tower(m, m->fov, w1, 0, nullptr, nullptr, pl.TOKF, "field-of-view encoder", s));
+    OVM_TRY(m, run_tower(m, &m->image, w1, 0, nullptr, nullptr, pl.TOKI, "image encoder", s));
+    if (c.use_fov) OVM_TRY(m, run_tower(m, &m->fov, w1, 0, nullptr, nullptr, pl.TOKF, "field-of-view encoder", s));
   }
   OVM_TRY(m, stamp(2));
   // ---- 3. token merge: features 0..5 = image, low, medium, high, hook 0, hook 1
@@ -790,7 +787,7 @@ int ovm_depthpro_infer(OvmDepthPro* m, const OvmImage* image, int32_t flip_bgr, 
 }
 
 int ovm_depthpro_profile_enable(OvmDepthPro* m, int32_t on) {
-  if (!m || !m->patch) return OVM_ERR_INVALID;
+  if (!m || !m->patch.fam) return OVM_ERR_INVALID;
   if (on && !m->ev[0]) {
     OVM_HIP(m, hipSetDevice(m->device));
     for (int i = 0; i <= kStages; ++i) OVM_HIP(m, hipEventCreate(&m->ev[i]));
@@ -808,7 +805,7 @@ int ovm_depthpro_stage_ms(OvmDepthPro* m, float* ms, int32_t n) {
 }
 
 int64_t ovm_depthpro_debug_copy(OvmDepthPro* m, const char* name, float* dst, int64_t capacity, ovm_stream_t stream) {
-  if (!m || !name || !dst || !m->patch || !m->has_last) return OVM_ERR_INVALID;
+  if (!m || !name || !dst || !m->patch.fam || !m->has_last) return OVM_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   const std::string n(name);
   const Plan& pl = m->last; const DepthProGeom& q = m->geo;

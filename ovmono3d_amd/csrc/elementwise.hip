@@ -1,7 +1,7 @@
 // HBM-bound helper kernels: patch gather (+normalise, +zero pad), LayerNorm (token rows and NHWC
 // channel rows), cls/pos init, dense-token cast, 2x2 max-pool, depth-prompt resize.
 #include "kernels.hpp"
-#include "sam.hpp"
+#include "tower.hpp"
 
 namespace ovm {
 

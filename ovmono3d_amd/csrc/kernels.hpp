@@ -70,7 +70,7 @@ struct CubeDecodeParams {
 int launch_patch_gather(const ImageDesc* d_imgs, int B, int G, int patch, int Kpad, const float* mean, const float* stdv,
                         half_t* Ahi, half_t* Alo, hipStream_t s);
 struct TowerViews;
-// patch rows of fp32 crops given as strided views (sam.hpp TowerViews; patch 16, Kpad 768): the values are split as they are
+// patch rows of fp32 crops given as strided views (tower.hpp TowerViews; patch 16, Kpad 768): the values are split as they are
 int launch_patch_gather_f32(const TowerViews& v, int B, int G, int Kpad, half_t* Ahi, half_t* Alo, hipStream_t s);
 int launch_ln_gelu_split(half_t* hi, half_t* lo, int M, int D, const float* gamma, const float* beta, float eps, hipStream_t s);
 int launch_cls_init(float* X, const float* cls, const float* pos, const float* reg, int R, int B, int T, int D, hipStream_t s);

@@ -1,4 +1,5 @@
-// Host-side model loading shared by the four handles (OvmHandle, OvmGdino, OvmSam, OvmDepthPro): the state a handle embeds (error
+// Host-side model loading shared by the four handles (OvmHandle, OvmGdino, OvmSam, OvmDepthPro) and the ViT tower they hold
+// (tower.hpp: a Tower is a Loader of its own): the state a handle embeds (error
 // text, recorded device allocations, precision), the checkpoint map, fp32 uploads, the packed fp16 weight image of gemm.hpp and the
 // weight reorders that feed it. The image format is written here and nowhere else on the host (the device writer is
 // pack_weight_kernel in gops.hip; tests pin the two to each other).

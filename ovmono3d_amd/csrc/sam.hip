@@ -1,7 +1,7 @@
 // Segment Anything with box prompts (include/ovm3d.h, "Segment Anything, box-prompted"): SamPredictor.set_image / predict of
 // segment_anything as OVMono3D-GEO calls them (reference tools/ovmono3d_geo.py:213-217,270-272,308-309).
 //
-// The image encoder's blocks are the OVM_TOWER_SAM code of api.hip (ovm::tower_create / tower_forward). Everything behind them is
+// The image encoder's blocks are a Tower of the segment_anything family (tower.hpp: configure / load / tower_forward). Everything behind them is
 // sequenced here from the generic fp32 device ops (ovm_g_linear / ovm_g_layernorm / ovm_g_bmm2 / ovm_g_softmax) plus the kernels
 // of this file:
 //   sam_i2t_attn_kernel   image -> token cross attention: G*G queries against <= 8 token keys per box, score + softmax + value sum
@@ -23,8 +23,7 @@
 
 #include "../../include/ovm3d.h"
 #include "kernels.hpp"
-#include "sam.hpp"
-#include "loader.hpp"
+#include "tower.hpp"
 
 using namespace ovm;
 
@@ -43,7 +42,7 @@ constexpr float kLn2dEps = 1e-6f;    // LayerNorm2d of the neck and the upscalin
 struct OvmSam : ovm::Loader {
   OvmSamConfig cfg;
   int device = 0;
-  OvmHandle* tower = nullptr;
+  Tower tower;                               // the image encoder (tower.fam is set once ovm_sam_create has come as far as configuring it)
   int G = 0, G2 = 0, C = 0, S = 0, L = 0, nt = 0, I = 0;      // grid, prompt width, image size, low-res side 4G, tokens per box, cross-attention width
   // neck
   PackedLin neck1, neck3; Norm nn1, nn3;
@@ -427,7 +426,7 @@ const char* ovm_sam_last_error(const OvmSam* m) { return m ? m->err.c_str() : "n
 int ovm_sam_destroy(OvmSam* m) {
   if (!m) return OVM_OK;
   (void)hipSetDevice(m->device);
-  if (m->tower) ovm_destroy(m->tower);
+  m->tower.destroy();
   m->free_all();
   if (m->rs_tmp) (void)hipFree(m->rs_tmp);
   if (m->tab) (void)hipFree(m->tab);
@@ -458,13 +457,13 @@ int ovm_sam_create(const OvmSamConfig* cfg, const OvmTensor* weights, int32_t n_
   if (m->G2 % (256 / c.dec_heads) != 0) { m->err = "invalid config (grid cells must fill whole workgroups of the image -> token kernel)"; return OVM_ERR_INVALID; }
   OVM_HIP(m, hipSetDevice(device));
   {
-    OvmConfig t; memset(&t, 0, sizeof(t));
-    t.embed_dim = c.embed_dim; t.depth = c.depth; t.heads = c.heads; t.pos_grid = c.pos_grid; t.canvas = c.image_size; t.fpn_channels = 256;
+    TowerConfig t; memset(&t, 0, sizeof(t));
+    t.family = FAM_SAM; t.prefix = "image_encoder."; t.precision = c.precision; t.max_batch = 1; t.sam_window = c.window; t.sam_global_mask = c.global_mask;
+    t.embed_dim = c.embed_dim; t.depth = c.depth; t.heads = c.heads; t.pos_grid = c.pos_grid; t.canvas = c.image_size;
     for (int i = 0; i < 3; ++i) { t.pixel_mean[i] = c.pixel_mean[i]; t.pixel_std[i] = c.pixel_std[i]; }
-    t.pooler_res = 1; t.precision = c.precision; t.max_batch = 1; t.max_rois = 1; t.tower = OVM_TOWER_SAM; t.sam_window = c.window;
-    t.sam_global_mask = c.global_mask;
-    const int r = tower_create(&t, weights, n_weights, device, "image_encoder.", &m->tower);
-    if (r) { m->err = std::string("image encoder: ") + ovm_last_error(m->tower); return r; }
+    int r = m->tower.configure(t);
+    if (!r) r = m->tower.load(weights, n_weights, device);
+    if (r) { m->err = std::string("image encoder: ") + m->tower.err; return r; }
   }
   const WeightMap wm(weights, n_weights);
   const int C = m->C, D = c.embed_dim, G = m->G, G2 = m->G2, I = m->I;
@@ -549,7 +548,7 @@ int ovm_sam_create(const OvmSamConfig* cfg, const OvmTensor* weights, int32_t n_
 int ovm_sam_set_image(OvmSam* m, const OvmImage* image, int32_t flip_bgr, ovm_stream_t stream) {
   if (!m) return OVM_ERR_INVALID;
   m->err.clear();
-  if (!m->tower) { m->err = "handle was not created"; return OVM_ERR_INVALID; }
+  if (!m->tower.fam) { m->err = "handle was not created"; return OVM_ERR_INVALID; }
   if (!image || !image->data || image->height < 1 || image->width < 1) { m->err = "null or empty image"; return OVM_ERR_INVALID; }
   hipStream_t s = (hipStream_t)stream;
   OVM_HIP(m, hipSetDevice(m->device));
@@ -601,11 +600,11 @@ int ovm_sam_set_image(OvmSam* m, const OvmImage* image, int32_t flip_bgr, ovm_st
   net.stride_c = flip_bgr ? -1 : 1; net.stride_h = (int64_t)3 * neww; net.stride_w = 3;
   net.orig_height = H; net.orig_width = W;
   {
-    const int r = tower_forward(m->tower, &net, s);
-    if (r) { m->err = std::string("image encoder: ") + ovm_last_error(m->tower); return r; }
+    const int r = tower_forward(&m->tower, &net, s);
+    if (r) { m->err = std::string("image encoder: ") + m->tower.err; return r; }
   }
   // neck
-  OVM_TRY(m, lin(m, m->neck1, tower_tokens(m->tower), c.embed_dim, G2, 0, nullptr, 0, m->T1, C, s));
+  OVM_TRY(m, lin(m, m->neck1, tower_tokens(&m->tower), c.embed_dim, G2, 0, nullptr, 0, m->T1, C, s));
   {
     LnOut o; memset(&o, 0, sizeof(o));
     o.hi = m->pad_hi; o.lo = m->pad_lo; o.ld = C; o.padH = G; o.padW = G;
@@ -622,7 +621,7 @@ int ovm_sam_set_image(OvmSam* m, const OvmImage* image, int32_t flip_bgr, ovm_st
 }
 
 int ovm_sam_predict_boxes_workspace(const OvmSam* m, int32_t n, int64_t* bytes) {
-  if (!m || !bytes || n < 0 || !m->tower) return OVM_ERR_INVALID;
+  if (!m || !bytes || n < 0 || !m->tower.fam) return OVM_ERR_INVALID;
   const int nb = n < m->cfg.max_boxes ? n : m->cfg.max_boxes;
   *bytes = (int64_t)carve(nullptr, nullptr, m, nb < 1 ? 1 : nb);
   return OVM_OK;
@@ -632,7 +631,7 @@ int ovm_sam_predict_boxes(OvmSam* m, const float* boxes, int32_t n, int32_t mask
                           int64_t workspace_bytes, ovm_stream_t stream) {
   if (!m) return OVM_ERR_INVALID;
   m->err.clear();
-  if (!m->tower) { m->err = "handle was not created"; return OVM_ERR_INVALID; }
+  if (!m->tower.fam) { m->err = "handle was not created"; return OVM_ERR_INVALID; }
   if (!m->has_image) { m->err = "ovm_sam_set_image has not been called"; return OVM_ERR_INVALID; }
   if (n < 0 || mask_index < 0 || mask_index > 2) { m->err = "invalid arguments (n >= 0, mask_index 0..2)"; return OVM_ERR_INVALID; }
   if (n == 0) return OVM_OK;
@@ -656,7 +655,7 @@ int ovm_sam_predict_boxes(OvmSam* m, const float* boxes, int32_t n, int32_t mask
 }
 
 int64_t ovm_sam_debug_copy(OvmSam* m, const char* name, float* dst, int64_t capacity, ovm_stream_t stream) {
-  if (!m || !name || !dst || !m->tower) return OVM_ERR_INVALID;
+  if (!m || !name || !dst || !m->tower.fam) return OVM_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   const std::string n(name);
   const int C = m->C, G2 = m->G2;
@@ -665,7 +664,7 @@ int64_t ovm_sam_debug_copy(OvmSam* m, const char* name, float* dst, int64_t capa
     cnt = (int64_t)3 * m->S * m->S;
     if (cnt > capacity) return OVM_ERR_CAPACITY;
     const half_t *hi, *lo; int ld;
-    tower_patches(m->tower, &hi, &lo, &ld);
+    tower_patches(&m->tower, &hi, &lo, &ld);
     hipLaunchKernelGGL(sam_unpatch_kernel, g1(cnt), dim3(256), 0, s, hi, lo, ld, m->G, m->cfg.patch, dst);
     return last_launch() ? OVM_ERR_HIP : cnt;
   }

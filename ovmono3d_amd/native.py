@@ -6,7 +6,7 @@ every arithmetic step of the path runs inside libovm3d's HIP kernels.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -16,61 +16,41 @@ from .lib import OVM_REC_FLOATS, OVM_TOWER_CLIP, OVM_TOWER_DINOV2, OVM_TOWER_MAE
 from .util.synth_weights import CLIP_ARCH, MAE_ARCH, MIDAS_ARCH, SAM_ARCH, VIT_ARCH
 
 
+Backbone = NamedTuple("Backbone", [("tower", int), ("node", str), ("field", str), ("arch", dict), ("patch", int), ("scales", tuple), ("pos_grid", Optional[int])])
+# MODEL.BACKBONE.NAME -> tower id, config node under MODEL, its field that names the architecture, the architecture table (embed dim, depth,
+# heads[, patch, position grid, ...]), patch, pyramid scales (finest first), the checkpoint's position grid (None: the architecture's)
+BACKBONES = {
+    "build_dino_backbone": Backbone(OVM_TOWER_DINOV2, "DINO", "MODEL_NAME", VIT_ARCH, 14, (2.0, 1.0, 0.5), 37),
+    "build_clip_backbone": Backbone(OVM_TOWER_CLIP, "CLIP", "ARCH", CLIP_ARCH, 16, (4.0, 2.0, 1.0, 0.5), None),
+    "build_mae_backbone": Backbone(OVM_TOWER_MAE, "MAE", "CHECKPOINT", MAE_ARCH, 16, (4.0, 2.0, 1.0, 0.5), 0),      # table built on the host
+    "build_midas_backbone": Backbone(OVM_TOWER_MIDAS, "MIDAS", "ARCH", MIDAS_ARCH, 16, (4.0, 2.0, 1.0, 0.5), None),
+    "build_sam_backbone": Backbone(OVM_TOWER_SAM, "SAM", "ARCH", SAM_ARCH, 16, (4.0, 2.0, 1.0, 0.5), None),
+}
+
+
 def config_to_native(cfg) -> OvmConfig:
     """Reference config tree -> OvmConfig (keys cited in include/ovm3d.h)."""
     backbone = cfg.MODEL.BACKBONE.NAME
-    if backbone == "build_dino_backbone":
-        tower, patch = OVM_TOWER_DINOV2, 14
-        name = cfg.MODEL.DINO.MODEL_NAME
-        if name not in VIT_ARCH:
-            raise ValueError(f"unsupported MODEL.DINO.MODEL_NAME {name!r} (known: {sorted(VIT_ARCH)})")
-        if cfg.MODEL.DINO.NAME != "dinov2":
-            raise ValueError("only MODEL.DINO.NAME == 'dinov2' is on this path")
-        if cfg.MODEL.DINO.OUTPUT != "dense" or cfg.MODEL.DINO.RETURN_MULTILAYER or cfg.MODEL.DINO.LAYER != -1:
-            raise ValueError("native path supports MODEL.DINO.OUTPUT 'dense', LAYER -1, single layer")
-        D, L, heads = VIT_ARCH[name]
-        pos_grid, n_levels = 37, 3
-    elif backbone == "build_clip_backbone":
-        tower, patch = OVM_TOWER_CLIP, 16
-        name = cfg.MODEL.CLIP.ARCH
-        if name not in CLIP_ARCH:
-            raise ValueError(f"unsupported MODEL.CLIP.ARCH {name!r} (known: {sorted(CLIP_ARCH)})")
-        if cfg.MODEL.CLIP.OUTPUT != "dense" or cfg.MODEL.CLIP.RETURN_MULTILAYER or cfg.MODEL.CLIP.LAYER != -1:
-            raise ValueError("native path supports MODEL.CLIP.OUTPUT 'dense', LAYER -1, single layer")
-        D, L, heads, patch, pos_grid = CLIP_ARCH[name]
-        n_levels = 4
-    elif backbone == "build_mae_backbone":
-        tower = OVM_TOWER_MAE
-        name = cfg.MODEL.MAE.CHECKPOINT
-        if name not in MAE_ARCH:
-            raise ValueError(f"unsupported MODEL.MAE.CHECKPOINT {name!r} (known: {sorted(MAE_ARCH)})")
-        if cfg.MODEL.MAE.OUTPUT != "dense" or cfg.MODEL.MAE.RETURN_MULTILAYER or cfg.MODEL.MAE.LAYER != -1:
-            raise ValueError("native path supports MODEL.MAE.OUTPUT 'dense', LAYER -1, single layer")
-        D, L, heads, patch = MAE_ARCH[name]
-        # the reference taps hidden_states[num_layers - 1] (mae.py:43-55,110-116): the state before the LAST block, so one block fewer runs
-        L = L - 1
-        pos_grid, n_levels = 0, 4
-    elif backbone == "build_midas_backbone":
-        tower = OVM_TOWER_MIDAS
-        name = cfg.MODEL.MIDAS.ARCH
-        if name not in MIDAS_ARCH:
-            raise ValueError(f"unsupported MODEL.MIDAS.ARCH {name!r} (known: {sorted(MIDAS_ARCH)})")
-        if cfg.MODEL.MIDAS.OUTPUT != "dense" or cfg.MODEL.MIDAS.RETURN_MULTILAYER or cfg.MODEL.MIDAS.LAYER != -1:
-            raise ValueError("native path supports MODEL.MIDAS.OUTPUT 'dense', LAYER -1, single layer")
-        D, L, heads, patch, pos_grid = MIDAS_ARCH[name]
-        n_levels = 4
-    elif backbone == "build_sam_backbone":
-        tower = OVM_TOWER_SAM
-        name = cfg.MODEL.SAM.ARCH
-        if name not in SAM_ARCH:
-            raise ValueError(f"unsupported MODEL.SAM.ARCH {name!r} (known: {sorted(SAM_ARCH)})")
-        if cfg.MODEL.SAM.OUTPUT != "dense" or cfg.MODEL.SAM.RETURN_MULTILAYER or cfg.MODEL.SAM.LAYER != -1:
-            raise ValueError("native path supports MODEL.SAM.OUTPUT 'dense', LAYER -1, single layer")
-        D, L, heads, patch, pos_grid, sam_window, sam_global = SAM_ARCH[name]
-        n_levels = 4
-    else:
+    if backbone not in BACKBONES:
         raise ValueError(f"MODEL.BACKBONE.NAME {backbone!r} is not on the native path (build_dino_backbone, build_clip_backbone, "
                          "build_mae_backbone, build_midas_backbone, build_sam_backbone)")
+    bb = BACKBONES[backbone]
+    tower, patch, n_levels, node = bb.tower, bb.patch, len(bb.scales), getattr(cfg.MODEL, bb.node)
+    name = getattr(node, bb.field)
+    if name not in bb.arch:
+        raise ValueError(f"unsupported MODEL.{bb.node}.{bb.field} {name!r} (known: {sorted(bb.arch)})")
+    if tower == OVM_TOWER_DINOV2 and node.NAME != "dinov2":
+        raise ValueError("only MODEL.DINO.NAME == 'dinov2' is on this path")
+    if node.OUTPUT != "dense" or node.RETURN_MULTILAYER or node.LAYER != -1:
+        raise ValueError(f"native path supports MODEL.{bb.node}.OUTPUT 'dense', LAYER -1, single layer")
+    arch = bb.arch[name]
+    D, L, heads = arch[:3]
+    pos_grid = arch[4] if bb.pos_grid is None else bb.pos_grid
+    if tower == OVM_TOWER_MAE:
+        # the reference taps hidden_states[num_layers - 1] (mae.py:43-55,110-116): the state before the LAST block, so one block fewer runs
+        L = L - 1
+    if tower == OVM_TOWER_SAM:
+        sam_window, sam_global = arch[5], arch[6]
     H = cfg.MODEL.ROI_CUBE_HEAD
     unsupported = []
     if H.Z_TYPE != "direct": unsupported.append("Z_TYPE")
@@ -151,12 +131,12 @@ class Engine:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self._lib = _lib.load()
         self._h = C.c_void_p()
-        self.patch = 14 if self.ncfg.tower == OVM_TOWER_DINOV2 else 16
+        bb = BACKBONES[cfg.MODEL.BACKBONE.NAME]
+        self.patch = bb.patch
         self.G = self.ncfg.canvas // self.patch
         self.C = self.ncfg.fpn_channels
         # pyramid levels, finest first: (name, side of the grid on the canvas, stride in pixels)
-        scales = (2.0, 1.0, 0.5) if self.ncfg.tower == OVM_TOWER_DINOV2 else (4.0, 2.0, 1.0, 0.5)
-        self.levels = [(f"p{2 + i}", int(self.G * sc), self.patch / sc) for i, sc in enumerate(scales)]      # G odd: MaxPool2 floors
+        self.levels = [(f"p{2 + i}", int(self.G * sc), self.patch / sc) for i, sc in enumerate(bb.scales)]      # G odd: MaxPool2 floors
 
     # ---- lifecycle ---------------------------------------------------------------------------
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor]) -> None:

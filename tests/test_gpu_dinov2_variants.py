@@ -231,7 +231,7 @@ def test_rpn_route_tiny_register_model(device, variant_oracle):
 
 def test_vitg_width_depth2_canvas518(device, variant_oracle):
     """ViT-g width (D = 1536, Hs = 4096) at depth 2, canvas 518 (T = 1370). The w12 GEMM is M = 1370, N = 8192: 6 x 32 = 192 tiles of
-    256 x 256, the dispatcher's threshold, so it runs on the 256-tile kernel with EPI_SWIGLU (csrc/api.hip gemm()); with the
+    256 x 256, the dispatcher's threshold, so it runs on the 256-tile kernel with EPI_SWIGLU (csrc/tower.hip gemm()); with the
     "gemm256" tune key off it runs on the 128-tile kernels, and both must give the oracle's answer. The profile shows the two w12
     launches under the fc1 category."""
     L = _lib()
