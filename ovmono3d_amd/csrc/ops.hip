@@ -329,6 +329,7 @@ int ovm_tune_set(const char* key, int32_t value) {
 #endif
     attn_set_pp(value); return OVM_OK;
   }
+  // the four below are copied into a detector plan when it is built (GdinoTune, gdino_model.hpp): a plan keeps its values
   if (!strcmp(key, "gdino_ffn_split")) { ovm::set_gdino_ffn_split(value); return OVM_OK; }   // plans built afterwards: 0 = one workgroup per row block runs the whole FFN
   if (!strcmp(key, "gdino_swin_fused")) { ovm::set_gdino_swin_fused(value); return OVM_OK; }  // plans built afterwards: 0 = qkv GEMM + window attention as two launches
   if (!strcmp(key, "gdino_gemm256")) { ovm::set_gdino_gemm256(value); return OVM_OK; }       // plans built afterwards: 0 = planar rows, 128 x 128 tiles
@@ -348,8 +349,8 @@ int ovm_tune_set(const char* key, int32_t value) {
   if (!strcmp(key, "gemm256_ksplit")) { ovm::set_gemm256_ksplit(value); return OVM_OK; }
   if (!strcmp(key, "gemm256_n192")) { ovm::gemm256_set_n192(value); return OVM_OK; }     // qkv: 256 x 192 tiles when they fill the chip better (default 1)
   if (!strcmp(key, "gemm256")) { ovm::set_use_gemm256(value); return OVM_OK; }          // engine: 256 x 256 kernel for qkv / fc1 (default 1)
-  if (!strcmp(key, "op_gemm256")) { g_op_gemm256 = value; return OVM_OK; }
-  if (!strcmp(key, "gdino_branches")) { ovm::set_gdino_branches(value); return OVM_OK; }  // engines created afterwards: text branch on its own stream (default 1)              // ovm_op_gemm: force it, value = split-K hint
+  if (!strcmp(key, "op_gemm256")) { g_op_gemm256 = value; return OVM_OK; }              // ovm_op_gemm: force it, value = split-K hint
+  if (!strcmp(key, "gdino_branches")) { ovm::set_gdino_branches(value); return OVM_OK; }  // engines created afterwards: text branch on its own stream (default 1)
   return OVM_ERR_INVALID;
 }
 
