@@ -360,7 +360,9 @@ const char* ovm_gdino_last_error(const OvmGdino* g);
 /* image: uint8 at network resolution (device). token_ids: host int32 [ntok] = tokenizer(caption) incl. [CLS] / [SEP];
  * position_ids: host int32 [ntok] or NULL (upstream numbering: restart per phrase, delimiter included).
  * pred_logits: device fp32 [num_queries][max_text_len], pre-sigmoid, -inf beyond the caption; pred_boxes: device fp32
- * [num_queries][4] (cx, cy, w, h in [0, 1]). Either output may be NULL (results stay in the handle for ovm_gdino_detect). */
+ * [num_queries][4] (cx, cy, w, h in [0, 1]). Either output may be NULL (results stay in the handle for ovm_gdino_detect).
+ * ntok > max_text_len is OVM_ERR_INVALID. The row-chain decoder (tune key gdino_dec_chain) applies while heads * ntok <= 516 (64
+ * tokens at 8 heads); longer captions run the launch-per-op decoder. */
 int ovm_gdino_forward(OvmGdino* g, const OvmImage* image, const int32_t* token_ids, int32_t ntok, const int32_t* position_ids,
                       float* pred_logits, float* pred_boxes, ovm_stream_t stream);
 /* forward + the reference-owned output glue (ovm_gdino_postprocess below; roi_heads_gdino.py:186-202,236-263): outputs as there. */
@@ -433,6 +435,56 @@ int ovm_g_normalize_image(const OvmImage* image, const float* mean, const float*
                           ovm_stream_t stream);
 int ovm_g_rowmax(const float* x, int32_t rows, int32_t cols, int32_t ld, float* out, ovm_stream_t stream);
 int ovm_g_topk(const float* scores, int32_t n, int32_t k, int32_t* out_idx, ovm_stream_t stream);
+
+/* --- the fused kernels of ovm_gdino_forward (and, for the attention, of the SAM tower) one at a time, for tests: each descriptor
+ * mirrors the engine's own parameter block (csrc/gdino.hpp) field for field and the call is that kernel's launcher, nothing else -
+ * no conversion, no scratch, no synchronisation; all pointers are device memory the caller owns, the result is the launcher's code.
+ * OVM_ERR_INVALID for a null descriptor.
+ *
+ * attn_f32_kernel: o[b1][b2][q][0:DH] = softmax_k(scale q.k + bias_h[b2][q][k] + bias_b[b1][q][k] + rel_h[kh] + rel_w[kw]) v, exact
+ * fp32 products on the matrix cores, keys walked in chunks of 144. DH in {16, 32, 64}; sq1 .. so2 are the element strides of the two
+ * batch levels (b1 outer, b2 = head); o (fp32) and / or ohi, olo (split fp16: hi = fp16(y), lo = fp16(y - hi)) with their own strides;
+ * bias_h [nb2][Tq][ldbh] (stride sbh), bias_b [nb1][Tq][ldbb] (stride sbb, 0: shared by all b1), either may be NULL; rel_h, rel_w:
+ * [b1][q][b2][ldrel], key = kh * rel_gw + kw (NULL: none). k, v and o rows must be 16-byte aligned with strides that are multiples
+ * of 4 floats, else OVM_ERR_SHAPE (also for another DH); nothing is launched then. */
+typedef struct OvmAttnF32Op {
+  const float* q; const float* k; const float* v; int32_t ldq, ldk, ldv, reserved0;
+  int64_t sq1, sq2, sk1, sk2, sv1, sv2;
+  float* o; int32_t ldo, reserved1; int64_t so1, so2;
+  uint16_t* ohi; uint16_t* olo; int32_t ldoh, reserved2; int64_t soh1, soh2;
+  int32_t nb1, nb2, Tq, Tk, DH; float scale;
+  const float* bias_h; int64_t sbh; int32_t ldbh, reserved3;
+  const float* bias_b; int64_t sbb; int32_t ldbb, reserved4;
+  const float* rel_h; const float* rel_w; int32_t rel_gw, ldrel;
+} OvmAttnF32Op;
+int ovm_g_attn_f32(const OvmAttnF32Op* op, ovm_stream_t stream);
+/* msdeform_fused_kernel / msdeform_fused4_kernel (the latter where L * P = 16, dh % 4 == 0 and everything is 16-byte aligned, unless
+ * ovm_tune_set msdeform_vec = 0). value [S][ldv] (H * dh columns), level l = rows lstart[l] .. of an lh[l] x lw[l] map; ow [Q][ldow] =
+ * H*L*P (x, y) offsets then H*L*P logits; mode 0 (encoder): ref [Q][ldref >= 2] point, loc = ref + off / (W_l, H_l); mode 1
+ * (decoder): ref [Q][ldref >= 4] box (cx, cy, w, h), loc = c + off * wh * 0.5 / P. Bilinear taps as F.grid_sample (align_corners =
+ * False, zero padding), weights = softmax over the L*P logits of a head. out fp32 [Q][ldo] and / or split ohi, olo [Q][ldoh].
+ * L <= 8, else OVM_ERR_CAPACITY. */
+typedef struct OvmMsDeformOp {
+  const float* value; const float* ow; const float* ref; int32_t ldv, ldow, ldref, mode;
+  int32_t Q, H, dh, L, P, reserved0;
+  int32_t lh[8], lw[8], lstart[8];
+  float* out; uint16_t* ohi; uint16_t* olo; int32_t ldo, ldoh;
+} OvmMsDeformOp;
+int ovm_g_msdeform_fused(const OvmMsDeformOp* op, ovm_stream_t stream);
+/* rowop_kernel, one wave per row r < M: row = concat_j x[idx[r * nidx + j]][0:seg] (idx NULL: x[r][0:D]; idx < 0: zeros; D = nidx *
+ * seg) + res[r] -> LayerNorm(gamma, beta, eps) over D (gamma NULL: none) -> zero_masked: rows whose first index is negative are
+ * zero after the norm -> y; y2 = y + add[r % add_rows]. Outputs, each optional: y [M][ldy], y2 [M][ldy2], hi / lo = split fp16 of y
+ * [M][ldh] with columns D .. ldh written as zero, or with il = 1 ONE interleaved image (lo = hi + 32, ldh = 2 D, column n at
+ * (n / 32) * 64 + n % 32; anything else is OVM_ERR_INVALID), hi2 / lo2 = split of y2 [M][ldh2]. With a LayerNorm D <= 4096 on the
+ * float4 route (D, seg, ldx, ldr % 4 == 0 and 16-byte aligned x, res) and D <= 1024 otherwise, else OVM_ERR_SHAPE. */
+typedef struct OvmRowOp {
+  const float* x; const int32_t* idx; const float* res; const float* gamma; const float* beta; const float* add;
+  int32_t ldx, nidx, seg, ldr; float eps; int32_t zero_masked, ld_add, add_rows;
+  int32_t M, D;
+  float* y; float* y2; uint16_t* hi; uint16_t* lo; uint16_t* hi2; uint16_t* lo2;
+  int32_t ldy, ldy2, ldh, il, ldh2, reserved0;
+} OvmRowOp;
+int ovm_g_rowop(const OvmRowOp* op, ovm_stream_t stream);
 
 /* Process-global tuning knobs for experiments and tests (also settable as OVM_TUNE="key=value,..." when the host loads the
  * library). Defaults are the measured best; none changes results beyond fp32 summation order.

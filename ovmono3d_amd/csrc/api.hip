@@ -129,6 +129,9 @@ int ovm_abi_sizeof(const char* name) {
   if (n == "OvmSamConfig") return (int)sizeof(OvmSamConfig);
   if (n == "OvmDepthProConfig") return (int)sizeof(OvmDepthProConfig);
   if (n == "OvmGemmEpiOp") return (int)sizeof(OvmGemmEpiOp);
+  if (n == "OvmAttnF32Op") return (int)sizeof(OvmAttnF32Op);
+  if (n == "OvmMsDeformOp") return (int)sizeof(OvmMsDeformOp);
+  if (n == "OvmRowOp") return (int)sizeof(OvmRowOp);
   return -1;
 }
 

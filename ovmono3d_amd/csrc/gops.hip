@@ -586,4 +586,41 @@ int ovm_g_topk(const float* scores, int32_t n, int32_t k, int32_t* out_idx, ovm_
   return launch_topk(scores, n, k, out_idx, (hipStream_t)stream);
 }
 
+// The engine's fused kernels one at a time (tests): fill the launcher's own parameter block from the C descriptor, call the launcher.
+int ovm_g_attn_f32(const OvmAttnF32Op* d, ovm_stream_t stream) {
+  if (!d) return OVM_ERR_INVALID;
+  AttnF32Params a; memset(&a, 0, sizeof(a));
+  a.q = d->q; a.k = d->k; a.v = d->v; a.ldq = d->ldq; a.ldk = d->ldk; a.ldv = d->ldv;
+  a.sq1 = (long)d->sq1; a.sq2 = (long)d->sq2; a.sk1 = (long)d->sk1; a.sk2 = (long)d->sk2; a.sv1 = (long)d->sv1; a.sv2 = (long)d->sv2;
+  a.o = d->o; a.ldo = d->ldo; a.so1 = (long)d->so1; a.so2 = (long)d->so2;
+  a.ohi = (half_t*)d->ohi; a.olo = (half_t*)d->olo; a.ldoh = d->ldoh; a.soh1 = (long)d->soh1; a.soh2 = (long)d->soh2;
+  a.nb1 = d->nb1; a.nb2 = d->nb2; a.Tq = d->Tq; a.Tk = d->Tk; a.DH = d->DH; a.scale = d->scale;
+  a.bias_h = d->bias_h; a.sbh = (long)d->sbh; a.ldbh = d->ldbh;
+  a.bias_b = d->bias_b; a.sbb = (long)d->sbb; a.ldbb = d->ldbb;
+  a.rel_h = d->rel_h; a.rel_w = d->rel_w; a.rel_gw = d->rel_gw; a.ldrel = d->ldrel;
+  return launch_attn_f32(a, (hipStream_t)stream);
+}
+
+int ovm_g_msdeform_fused(const OvmMsDeformOp* d, ovm_stream_t stream) {
+  if (!d) return OVM_ERR_INVALID;
+  MsDeformParams m; memset(&m, 0, sizeof(m));
+  m.value = d->value; m.ldv = d->ldv; m.ow = d->ow; m.ldow = d->ldow; m.ref = d->ref; m.ldref = d->ldref; m.mode = d->mode;
+  m.Q = d->Q; m.H = d->H; m.dh = d->dh; m.L = d->L; m.P = d->P;
+  for (int l = 0; l < 8; ++l) { m.lh[l] = d->lh[l]; m.lw[l] = d->lw[l]; m.lstart[l] = d->lstart[l]; }
+  m.out = d->out; m.ldo = d->ldo; m.ohi = (half_t*)d->ohi; m.olo = (half_t*)d->olo; m.ldoh = d->ldoh;
+  return launch_msdeform_fused(m, (hipStream_t)stream);
+}
+
+int ovm_g_rowop(const OvmRowOp* d, ovm_stream_t stream) {
+  if (!d) return OVM_ERR_INVALID;
+  RowOpParams r; memset(&r, 0, sizeof(r));
+  r.x = d->x; r.ldx = d->ldx; r.idx = d->idx; r.nidx = d->nidx; r.seg = d->seg; r.res = d->res; r.ldr = d->ldr;
+  r.gamma = d->gamma; r.beta = d->beta; r.eps = d->eps; r.zero_masked = d->zero_masked;
+  r.add = d->add; r.ld_add = d->ld_add; r.add_rows = d->add_rows; r.M = d->M; r.D = d->D;
+  r.y = d->y; r.ldy = d->ldy; r.y2 = d->y2; r.ldy2 = d->ldy2;
+  r.hi = (half_t*)d->hi; r.lo = (half_t*)d->lo; r.ldh = d->ldh; r.il = d->il;
+  r.hi2 = (half_t*)d->hi2; r.lo2 = (half_t*)d->lo2; r.ldh2 = d->ldh2;
+  return launch_rowop(r, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -184,6 +184,44 @@ class OvmGemmEpiOp(C.Structure):
     ]
 
 
+class OvmAttnF32Op(C.Structure):
+    """Mirror of include/ovm3d.h OvmAttnF32Op (ovm_g_attn_f32: attn_f32_kernel in isolation, for tests)."""
+    _fields_ = [
+        ("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("ldq", C.c_int32), ("ldk", C.c_int32), ("ldv", C.c_int32),
+        ("reserved0", C.c_int32),
+        ("sq1", C.c_int64), ("sq2", C.c_int64), ("sk1", C.c_int64), ("sk2", C.c_int64), ("sv1", C.c_int64), ("sv2", C.c_int64),
+        ("o", C.c_void_p), ("ldo", C.c_int32), ("reserved1", C.c_int32), ("so1", C.c_int64), ("so2", C.c_int64),
+        ("ohi", C.c_void_p), ("olo", C.c_void_p), ("ldoh", C.c_int32), ("reserved2", C.c_int32), ("soh1", C.c_int64), ("soh2", C.c_int64),
+        ("nb1", C.c_int32), ("nb2", C.c_int32), ("Tq", C.c_int32), ("Tk", C.c_int32), ("DH", C.c_int32), ("scale", C.c_float),
+        ("bias_h", C.c_void_p), ("sbh", C.c_int64), ("ldbh", C.c_int32), ("reserved3", C.c_int32),
+        ("bias_b", C.c_void_p), ("sbb", C.c_int64), ("ldbb", C.c_int32), ("reserved4", C.c_int32),
+        ("rel_h", C.c_void_p), ("rel_w", C.c_void_p), ("rel_gw", C.c_int32), ("ldrel", C.c_int32),
+    ]
+
+
+class OvmMsDeformOp(C.Structure):
+    """Mirror of include/ovm3d.h OvmMsDeformOp (ovm_g_msdeform_fused: the fused deformable-attention kernels in isolation, for tests)."""
+    _fields_ = [
+        ("value", C.c_void_p), ("ow", C.c_void_p), ("ref", C.c_void_p), ("ldv", C.c_int32), ("ldow", C.c_int32), ("ldref", C.c_int32),
+        ("mode", C.c_int32),
+        ("Q", C.c_int32), ("H", C.c_int32), ("dh", C.c_int32), ("L", C.c_int32), ("P", C.c_int32), ("reserved0", C.c_int32),
+        ("lh", C.c_int32 * 8), ("lw", C.c_int32 * 8), ("lstart", C.c_int32 * 8),
+        ("out", C.c_void_p), ("ohi", C.c_void_p), ("olo", C.c_void_p), ("ldo", C.c_int32), ("ldoh", C.c_int32),
+    ]
+
+
+class OvmRowOp(C.Structure):
+    """Mirror of include/ovm3d.h OvmRowOp (ovm_g_rowop: rowop_kernel in isolation, for tests)."""
+    _fields_ = [
+        ("x", C.c_void_p), ("idx", C.c_void_p), ("res", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("add", C.c_void_p),
+        ("ldx", C.c_int32), ("nidx", C.c_int32), ("seg", C.c_int32), ("ldr", C.c_int32), ("eps", C.c_float),
+        ("zero_masked", C.c_int32), ("ld_add", C.c_int32), ("add_rows", C.c_int32),
+        ("M", C.c_int32), ("D", C.c_int32),
+        ("y", C.c_void_p), ("y2", C.c_void_p), ("hi", C.c_void_p), ("lo", C.c_void_p), ("hi2", C.c_void_p), ("lo2", C.c_void_p),
+        ("ldy", C.c_int32), ("ldy2", C.c_int32), ("ldh", C.c_int32), ("il", C.c_int32), ("ldh2", C.c_int32), ("reserved0", C.c_int32),
+    ]
+
+
 EXPORTS = [
     "ovm_create", "ovm_destroy", "ovm_last_error", "ovm_version", "ovm_abi_sizeof", "ovm_backbone_forward", "ovm_cube_forward",
     "ovm_rpn_box_forward", "ovm_gather_records", "ovm_gather_counts", "ovm_host_interp_pos_embed", "ovm_host_resize_pos_embed_aa", "ovm_host_sincos_pos_embed", "ovm_host_shard_range",
@@ -193,6 +231,7 @@ EXPORTS = [
     "ovm_comm_unique_id", "ovm_comm_init", "ovm_comm_destroy", "ovm_tune_set", "ovm_gdino_postprocess", "ovm_box3d_iou", "ovm_eval_iou2d", "ovm_eval_match", "ovm_host_pil_bilinear_coeffs", "ovm_resize_bilinear_u8", "ovm_resize_bilinear_f32",
     "ovm_g_pack_weight", "ovm_host_pack_weight", "ovm_g_linear", "ovm_g_layernorm", "ovm_g_bmm", "ovm_g_bmm2", "ovm_g_softmax", "ovm_g_softmax2", "ovm_g_eltwise", "ovm_g_gather_rows",
     "ovm_g_groupnorm", "ovm_g_biattn", "ovm_g_msdeform", "ovm_g_sine_embed", "ovm_g_normalize_image", "ovm_g_topk", "ovm_g_rowmax",
+    "ovm_g_attn_f32", "ovm_g_msdeform_fused", "ovm_g_rowop",
     "ovm_gdino_create", "ovm_gdino_destroy", "ovm_gdino_last_error", "ovm_gdino_forward", "ovm_gdino_detect", "ovm_gdino_set_force_topk",
     "ovm_gdino_debug_copy", "ovm_debug_set_ptr", "ovm_gdino_num_queries", "ovm_gdino_last_outputs", "ovm_infer",
     "ovm_host_jpeg_info", "ovm_host_jpeg_entropy_decode", "ovm_jpeg_reconstruct",
@@ -230,7 +269,8 @@ def load() -> C.CDLL:
                          ("OvmJpegInfo", OvmJpegInfo), ("OvmSceneInput", OvmSceneInput), ("OvmSceneLayout", OvmSceneLayout),
                          ("OvmSceneSegment", OvmSceneSegment), ("OvmEvalCell", OvmEvalCell), ("OvmGeoParams", OvmGeoParams),
                          ("OvmGeoInstance", OvmGeoInstance), ("OvmGeoResult", OvmGeoResult), ("OvmGeoBox", OvmGeoBox),
-                         ("OvmSamConfig", OvmSamConfig), ("OvmDepthProConfig", OvmDepthProConfig), ("OvmGemmEpiOp", OvmGemmEpiOp)):
+                         ("OvmSamConfig", OvmSamConfig), ("OvmDepthProConfig", OvmDepthProConfig), ("OvmGemmEpiOp", OvmGemmEpiOp),
+                         ("OvmAttnF32Op", OvmAttnF32Op), ("OvmMsDeformOp", OvmMsDeformOp), ("OvmRowOp", OvmRowOp)):
         if lib.ovm_abi_sizeof(name.encode()) != C.sizeof(mirror):
             raise RuntimeError(f"{LIB_PATH}: sizeof({name}) = {lib.ovm_abi_sizeof(name.encode())} but the ctypes mirror has "
                                f"{C.sizeof(mirror)} bytes - rebuild the library (ovmono3d_amd/csrc/build.sh) or update lib.py")
@@ -326,6 +366,9 @@ def load() -> C.CDLL:
     lib.ovm_g_normalize_image.argtypes = [C.POINTER(OvmImage), C.POINTER(f32), C.POINTER(f32), i32, vp, vp]
     lib.ovm_g_topk.argtypes = [vp, i32, i32, vp, vp]
     lib.ovm_g_rowmax.argtypes = [vp, i32, i32, i32, vp, vp]
+    lib.ovm_g_attn_f32.argtypes = [C.POINTER(OvmAttnF32Op), vp]
+    lib.ovm_g_msdeform_fused.argtypes = [C.POINTER(OvmMsDeformOp), vp]
+    lib.ovm_g_rowop.argtypes = [C.POINTER(OvmRowOp), vp]
     lib.ovm_gdino_postprocess.argtypes = [vp, i32, i32, vp, C.POINTER(i32), i32, i32, i32, f32, f32, vp, vp, vp, vp, vp]
     lib.ovm_gdino_create.argtypes = [C.POINTER(OvmGdinoConfig), C.POINTER(OvmTensor), i32, i32, C.POINTER(vp)]
     lib.ovm_gdino_destroy.argtypes = [vp]

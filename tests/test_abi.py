@@ -30,10 +30,15 @@ def test_struct_layouts_match_header():
     assert C.sizeof(lib.OvmTensor) == 8 + 8 + 8 + 32
     assert C.sizeof(lib.OvmConfig) == 4 * 7 + 12 + 12 + 4 * 5 + 4 + 16 + 12 + 4 * 2 + 4 + 4 + 4 + 4 + 4 * 3 + 4 * 3
     assert C.sizeof(lib.OvmGemmEpiOp) == 4 * 12 + 8 * 6 + 4 * 2 + 8 + 4 * 2 + 8 + 8 + 4 * 2 + 8 * 2 + 4 * 4 + 8 * 3 + 4 * 4 + 8 + 4 * 4
+    assert C.sizeof(lib.OvmAttnF32Op) == 8 * 3 + 4 * 4 + 8 * 6 + (8 + 4 * 2 + 8 * 2) + (8 * 2 + 4 * 2 + 8 * 2) + 4 * 6 + (8 + 8 + 4 * 2) * 2 + 8 * 2 + 4 * 2
+    assert C.sizeof(lib.OvmMsDeformOp) == 8 * 3 + 4 * 4 + 4 * 6 + 4 * 24 + 8 * 3 + 4 * 2
+    assert C.sizeof(lib.OvmRowOp) == 8 * 6 + 4 * 8 + 4 * 2 + 8 * 6 + 4 * 6
     # and the library agrees with every mirror (lib.load() also refuses a mismatch)
     L = lib.load()
     for name, mirror in (("OvmConfig", lib.OvmConfig), ("OvmTensor", lib.OvmTensor), ("OvmImage", lib.OvmImage),
                          ("OvmGdinoConfig", lib.OvmGdinoConfig), ("OvmGemmEpiOp", lib.OvmGemmEpiOp)):
+        assert L.ovm_abi_sizeof(name.encode()) == C.sizeof(mirror), name
+    for name, mirror in (("OvmAttnF32Op", lib.OvmAttnF32Op), ("OvmMsDeformOp", lib.OvmMsDeformOp), ("OvmRowOp", lib.OvmRowOp)):
         assert L.ovm_abi_sizeof(name.encode()) == C.sizeof(mirror), name
     assert L.ovm_abi_sizeof(b"OvmDet3D") == 192 and L.ovm_abi_sizeof(b"nope") == -1
 

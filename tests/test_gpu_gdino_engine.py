@@ -2,11 +2,13 @@
 sequencing) against the Hugging Face port, at test size and at the real Swin-B / BERT-base / 900-query size, plus the plan /
 HIP-graph machinery (replay == eager; plans of different shapes own their scratch). Parity vs upstream itself is unpinned."""
 import time
+from functools import lru_cache
 
 import pytest
 import torch
 
-from common import assert_close
+import gdino_caption_cases as CC
+from common import assert_close, rel_err
 from hf_gdino_patches import patch_hf_to_upstream
 from test_gpu_gdino import _small_hf_gdino
 
@@ -52,6 +54,108 @@ def test_engine_matches_hf_small(device):
     # default position ids = upstream numbering (phrase-relative, delimiter included): differs from HF's ids, runs, stays finite
     l2, b2 = eng.forward(img.to(device), ids.tolist())
     assert torch.isfinite(b2).all() and torch.isfinite(l2[:, :T]).all()
+
+
+# ---------------------------------------------------------------------------------------------------------- long captions
+LONG_HW = (96, 132)
+
+
+@lru_cache(maxsize=None)
+def _hf_small_pair():
+    """the test model twice: fp32 (whose weights the engine loads) and the same weights in float64"""
+    hf32, _ = _small_hf_gdino()
+    hf64, _ = _small_hf_gdino()
+    return hf32, hf64.double()
+
+
+@lru_cache(maxsize=None)
+def _long_image():
+    return torch.randint(0, 256, (3,) + LONG_HW, dtype=torch.uint8, generator=torch.Generator().manual_seed(2))
+
+
+@lru_cache(maxsize=None)
+def _hf_long(T):
+    """HF on the CPU for the seeded caption of T tokens: float64 = the reference, fp32 = the margin (its error against float64)"""
+    from transformers.models.grounding_dino.modeling_grounding_dino import generate_masks_with_special_tokens_and_transfer_map
+    hf32, hf64 = _hf_small_pair()
+    ids = torch.tensor(CC.caption_ids(T, 0))
+    x = _normalised(_long_image())[None]
+    with torch.no_grad():
+        o32 = hf32(pixel_values=x, input_ids=ids[None], return_dict=True)
+        torch.set_default_dtype(torch.float64)               # HF allocates the padded logits in the default dtype
+        try:
+            o64 = hf64(pixel_values=x.double(), input_ids=ids[None], return_dict=True)
+        finally:
+            torch.set_default_dtype(torch.float32)
+    assert o64.logits.dtype == torch.float64 and o64.pred_boxes.dtype == torch.float64
+    pick = lambda o: dict(enc_text=o.encoder_last_hidden_state_text[0], enc_vision=o.encoder_last_hidden_state_vision[0],
+                          boxes=o.pred_boxes[0], logits=o.logits[0][:, :T])
+    r64, r32 = pick(o64), pick(o32)
+    topk = torch.topk(o64.enc_outputs_class[0].max(-1)[0], SMALL["num_queries"])[1]
+    pids = generate_masks_with_special_tokens_and_transfer_map(ids[None])[1][0].tolist()
+    return dict(ids=ids.tolist(), pids=pids, ref=r64, margin={k: rel_err(r32[k], r64[k]) for k in r64}, topk=topk)
+
+
+@lru_cache(maxsize=None)
+def _launches_small(device, T, chain):
+    """kernel launches of one forward of the test model on the T-token caption, the decoder knob at `chain` while the plan is built"""
+    from ovmono3d_amd import lib
+    L = lib.load()
+    try:
+        assert L.ovm_tune_set(b"gdino_dec_chain", chain) == 0
+        eng = _engine(device, _hf_small_pair()[0].state_dict(), SMALL, use_graphs=False)
+        eng.forward(_long_image().to(device), CC.caption_ids(T, 0))
+        return eng.launches()
+    finally:
+        L.ovm_tune_set(b"gdino_dec_chain", 1)
+
+
+@pytest.mark.parametrize("T", CC.ENGINE_T)
+def test_engine_long_captions_match_hf_fp64_small(device, T):
+    """Captions as long as the reference builds them (the whole category list of a dataset, up to max_text_len = 256 tokens), at
+    the lengths where the native path changes (gdino_caption_cases.ENGINE_T): row chain full / declined, a second key chunk in the
+    masked text attentions with scalar and with float4 bias reads. Reference: HF in float64 on the CPU; bound per quantity: the
+    larger of test_engine_matches_hf_small's bound for it and 4 x HF-fp32-against-float64 on the same input."""
+    h = _hf_long(T)
+    ref, margin = h["ref"], h["margin"]
+    eng = _engine(device, _hf_small_pair()[0].state_dict(), SMALL, use_graphs=False)
+    img = _long_image().to(device)
+    eng.forward(img, h["ids"], h["pids"])
+    S = ref["enc_vision"].shape[0]
+    got = dict(enc_text=eng.debug("enc_text", (T, 64)), enc_vision=eng.debug("enc_vision", (S, 64)))
+    assert sorted(eng.debug("topk", (30,), torch.int32).cpu().tolist()) == sorted(h["topk"].tolist())
+    eng.set_force_topk(h["topk"])                                # HF's order of the selected proposals for the decoder comparison
+    logits, boxes = eng.forward(img, h["ids"], h["pids"])
+    got.update(boxes=boxes, logits=logits[:, :T])
+    assert logits.shape[1] == 256 and torch.isinf(logits[:, T:]).all() and (logits[:, T:] < 0).all()
+    base = dict(enc_text=1e-4, enc_vision=1e-4, boxes=2e-4, logits=2e-4)
+    errs = {k: rel_err(got[k], ref[k]) for k in base}
+    print(f"FIG engine T {T} " + " ".join(f"{k} err {errs[k]:.3e} hf32 {margin[k]:.3e}" for k in base))
+    for k in base:
+        assert torch.isfinite(got[k]).all(), k
+        assert errs[k] <= max(base[k], 4.0 * margin[k]), f"{k} at T = {T}: {errs[k]:.3e} (HF fp32: {margin[k]:.3e})"
+    if T in (129, 130):
+        # the route, by the launch counter: 4 heads x 129 tokens fill the row chain's score region exactly, 130 do not fit
+        on129, on130 = _launches_small(device, 129, 1), _launches_small(device, 130, 1)
+        off129, off130 = _launches_small(device, 129, 0), _launches_small(device, 130, 0)
+        off7, off8 = _launches_small(device, 7, 0), _launches_small(device, 8, 0)
+        print(f"FIG engine launches: row chain T129 {on129} T130 {on130}; launch per op T129 {off129} T130 {off130} T7 {off7} T8 {off8}")
+        assert on129 <= on130 - 15 * SMALL["dec_layers"]         # the per-layer drop the row-chain test asserts
+        assert abs(off130 - off129) <= abs(off8 - off7)          # one more token alone changes no more than it does on a short caption
+        assert on130 == off130                                   # declined: the knob makes no difference
+
+
+def test_engine_refuses_257_tokens_and_stays_usable(device):
+    """max_text_len is 256: one token more is OVM_ERR_INVALID before any device work, and the handle works afterwards"""
+    from ovmono3d_amd.lib import OvmError
+    eng = _engine(device, _hf_small_pair()[0].state_dict(), SMALL, use_graphs=False)
+    img = _long_image().to(device)
+    ids = CC.caption_ids(256, 0)
+    l0, b0 = eng.forward(img, ids)
+    with pytest.raises(OvmError, match="code -1"):
+        eng.forward(img, CC.caption_ids(257, 0))
+    l1, b1 = eng.forward(img, ids)
+    assert torch.isfinite(b1).all() and torch.equal(l0, l1) and torch.equal(b0, b1)
 
 
 def test_engine_matches_python_sequenced_path_small(device):
@@ -285,13 +389,20 @@ def test_vectorised_deformable_sampling_is_bit_identical(device):
         assert torch.equal(a, b)
 
 
-@pytest.mark.parametrize("size", ["small", "full"])
-def test_decoder_row_chain_matches_launch_per_op_decoder(device, size):
+@pytest.mark.parametrize("size,T", [pytest.param("small", None, id="small"), pytest.param("full", None, id="full"),
+                                    pytest.param("small", 129, id="small-T129"), pytest.param("full", 64, id="full-T64"),
+                                    pytest.param("full", 65, id="full-T65")])
+def test_decoder_row_chain_matches_launch_per_op_decoder(device, size, T):
     """dec_chain.hip (round 3): a decoder layer as two row-chain kernels around the query self-attention - 16 query rows per workgroup
     resident in LDS through fourteen linears, four LayerNorms, the text cross-attention, the deformable sampling and the box update -
     against the launch-per-op sequence it replaces (ovm_tune_set gdino_dec_chain = 0; itself checked against the HF port above).
     Same operands, same three-pass products, fp32 everywhere else; what differs is summation order inside LayerNorm / softmax /
-    the FFN's chunked second layer: logits and boxes within 2e-5, the launch count drops by ~30 per layer."""
+    the FFN's chunked second layer: logits and boxes within 2e-5, the launch count drops by ~30 per layer.
+
+    T: the seeded caption of that many tokens instead of the short one. The chain keeps its attention scores [16 rows x heads][T] in
+    an LDS region of 16 x 516 floats, so it applies while heads * T <= 516: small (4 heads) at T = 129 fills the region exactly,
+    full (8 heads) at T = 64 leaves 64 floats of a row unused, and at T = 65 the chain must decline - both knob settings then run
+    the launch-per-op decoder: the same launch count and the same bits."""
     from ovmono3d_amd import lib
     L = lib.load()
     g = torch.Generator().manual_seed(11)
@@ -303,6 +414,8 @@ def test_decoder_row_chain_matches_launch_per_op_decoder(device, size):
         from ovmono3d_amd.util.synth_gdino_weights import synth_gdino_state_dict
         sd, cfgk, hw = synth_gdino_state_dict(3), {}, (532, 709)
         ids = [101, 2000 + 17, 1012, 2000 + 29, 2000 + 31, 1012, 2000 + 5, 1012, 102]
+    if T is not None:
+        ids = CC.caption_ids(T, 0)
     img = torch.randint(0, 256, (3,) + hw, dtype=torch.uint8, generator=g).to(device)
     outs, launches = [], []
     try:
@@ -315,9 +428,14 @@ def test_decoder_row_chain_matches_launch_per_op_decoder(device, size):
             del eng
     finally:
         L.ovm_tune_set(b"gdino_dec_chain", 1)
-    print(f"decoder row chain ({size}): {launches[0]} -> {launches[1]} kernel launches per forward")
-    assert launches[1] <= launches[0] - 15 * (2 if size == "small" else 6)          # (op wrappers counted, split-K reduce launches not included)
+    print(f"decoder row chain ({size}, {len(ids)} tokens): {launches[0]} -> {launches[1]} kernel launches per forward")
     assert torch.isfinite(outs[1][0]).all() and torch.isfinite(outs[1][1]).all()
+    heads = 4 if size == "small" else 8
+    if heads * len(ids) > 516:                                   # the chain declines
+        assert launches[1] == launches[0]
+        assert torch.equal(outs[1][0], outs[0][0]) and torch.equal(outs[1][1], outs[0][1])
+        return
+    assert launches[1] <= launches[0] - 15 * (2 if size == "small" else 6)          # (op wrappers counted, split-K reduce launches not included)
     assert_close(outs[1][1], outs[0][1], 2e-5, "pred_boxes (row chain vs launch per op)")
     assert_close(outs[1][0], outs[0][0], 2e-5, "pred_logits (row chain vs launch per op)")
 
