@@ -319,6 +319,46 @@ int ovm_op_boxhead_post(const float* HO, int32_t ldh, const float* prop_boxes, c
                         int32_t B, int32_t R, int32_t K, float score_thresh, float nms_thresh, int32_t topk, float* boxes,
                         float* scores, int32_t* classes, int32_t* image_idx, float* scores_full, int32_t* out_counts,
                         ovm_stream_t stream);
+/* The kernels between the GEMMs, each on its own (test-only): thin adapters over the launchers the model path calls. Device pointers
+ * unless marked host; fp16 buffers are passed as uint16_t and written in the kernel's own layout, so the caller sees exactly which
+ * elements a kernel touches. A lo pointer may be NULL (one-pass mode). None synchronises unless it says so.
+ *
+ * ROIAlign with the pooler's level rule over nlevels <= 4 NHWC fp32 levels: feats (host array of device pointers), hw (host, [nlevels][2] =
+ * fh, fw) and scales (host). Row r of hi / lo (row stride ldo >= out*out*C, (ph, pw, c) order) receives box r. C % 4 != 0: OVM_ERR_SHAPE. */
+int ovm_op_roi_align_ex(const float* const* feats, int32_t nlevels, const int32_t* hw, const float* scales, int32_t C, int32_t out_res,
+                        int32_t min_level, int32_t max_level, const float* boxes, const int32_t* image_idx, int32_t n,
+                        uint16_t* hi, uint16_t* lo, int32_t ldo, ovm_stream_t stream);
+/* Stable compaction of the records (OvmDet3D rows) with keep != 0 into out, and counts [B] = kept records per image (field `image`). */
+int ovm_op_compact_records(const OvmDet3D* rec, const int32_t* keep, int32_t n, int32_t B, OvmDet3D* out, int32_t* counts,
+                           ovm_stream_t stream);
+/* LayerNorm of rows x [M][ldx] (D % 4 == 0, D <= 2048, else OVM_ERR_SHAPE) into any of: y fp32 [M][ldf]; hi / lo fp16 split rows of
+ * stride ld. padH > 0: row (b, yy, xx) of M = B padH padW goes to pixel (yy + 1, xx + 1) of a [B][padH + 2][padW + 2] image. il: hi / lo
+ * form an interleaved image (lo = hi + 32, ld = 2 D; column k at (k / 32) * 64 + k % 32). */
+int ovm_op_ln_rows(const float* x, int32_t ldx, int32_t M, int32_t D, const float* gamma, const float* beta, float eps, float* y,
+                   int32_t ldf, uint16_t* hi, uint16_t* lo, int32_t ld, int32_t padH, int32_t padW, int32_t il, ovm_stream_t stream);
+/* hi + lo [M][D] <- split(gelu_erf(LayerNorm(hi + lo))), in place (D % 4 == 0, D <= 1024, else OVM_ERR_SHAPE) */
+int ovm_op_ln_gelu_split(uint16_t* hi, uint16_t* lo, int32_t M, int32_t D, const float* gamma, const float* beta, float eps,
+                         ovm_stream_t stream);
+/* Patch rows of B uint8 images (host array; data, height, width and the three strides are read) on a G x G grid of patch x patch
+ * patches: hi / lo [B G^2][Kpad], column (py * patch + px) * 3 + c = (u8 - mean[c]) / std[c], zero outside the image and from column
+ * 3 patch^2 on. patch 14, or patch 16 with Kpad 768, else OVM_ERR_INVALID. mean, std: host [3]. Synchronises. */
+int ovm_op_patch_gather(const OvmImage* images, int32_t B, int32_t G, int32_t patch, int32_t Kpad, const float* mean, const float* std,
+                        uint16_t* hi, uint16_t* lo, ovm_stream_t stream);
+/* The same rows (patch 16, Kpad 768, else OVM_ERR_INVALID) from B <= 36 strided fp32 views, split as they are. views: host
+ * [B][4] = device address of the view's first pixel, then its channel, row and column strides in elements. */
+int ovm_op_patch_gather_f32(const int64_t* views, int32_t B, int32_t G, int32_t Kpad, uint16_t* hi, uint16_t* lo, ovm_stream_t stream);
+/* X [B][T][D]: token 0 <- cls + pos[0 .. D), tokens 1 .. R <- reg [R][D] */
+int ovm_op_cls_init(float* X, const float* cls, const float* pos, const float* reg, int32_t R, int32_t B, int32_t T, int32_t D,
+                    ovm_stream_t stream);
+/* The last G2 tokens of each image of X [B][T][D] as split rows hi / lo [B G2][ldo]; ldo > D: column D holds depth_tok [B G2] (zero
+ * when NULL) and the columns after it zero */
+int ovm_op_tokens_cast(const float* X, int32_t B, int32_t T, int32_t G2, int32_t D, int32_t ldo, const float* depth_tok, uint16_t* hi,
+                       uint16_t* lo, ovm_stream_t stream);
+/* The last G2 tokens of each image of X [B][T][D] <- F [B G2][D] */
+int ovm_op_tokens_writeback(float* X, const float* F, int32_t B, int32_t T, int32_t G2, int32_t D, ovm_stream_t stream);
+/* 2 x 2 / 2 max-pool of split NHWC rows [B][G][G][D] -> [B][G/2][G/2][D] (an odd last row and column are dropped) */
+int ovm_op_maxpool2(const uint16_t* in_hi, const uint16_t* in_lo, int32_t B, int32_t G, int32_t D, uint16_t* out_hi, uint16_t* out_lo,
+                    ovm_stream_t stream);
 
 /* --- GroundingDINO output glue of ROIHeads3DGDINO (reference roi_heads_gdino.py:186-202,236-263,266-294):
  * pred_logits [nq][ld] (pre-sigmoid token logits, ld = 256), pred_boxes [nq][4] cxcywh in [0,1] (device);

@@ -6,6 +6,7 @@
 #include "../../include/ovm3d.h"
 #include "kernels.hpp"
 #include "det2d.hpp"
+#include "tower.hpp"
 
 using namespace ovm;
 
@@ -313,6 +314,76 @@ int ovm_op_cube_decode(const float* head13, int32_t ld, const float* boxes, cons
   if (r) return r;
   if (hipStreamSynchronize(s) != hipSuccess) return OVM_ERR_HIP;
   return OVM_OK;
+}
+
+// ---- the kernels between the GEMMs, one launcher each (tests): the caller's buffers are the kernel's own, nothing is converted
+int ovm_op_roi_align_ex(const float* const* feats, int32_t nlevels, const int32_t* hw, const float* scales, int32_t C, int32_t out_res,
+                        int32_t min_level, int32_t max_level, const float* boxes, const int32_t* image_idx, int32_t n,
+                        uint16_t* hi, uint16_t* lo, int32_t ldo, ovm_stream_t stream) {
+  if (!feats || !hw || !scales || nlevels < 1 || nlevels > kMaxLevels) return OVM_ERR_INVALID;
+  RoiParams rp; memset(&rp, 0, sizeof(rp));
+  for (int l = 0; l < nlevels; ++l) { rp.feat[l] = feats[l]; rp.fh[l] = hw[2 * l]; rp.fw[l] = hw[2 * l + 1]; rp.scale[l] = scales[l]; }
+  rp.C = C; rp.nlevels = nlevels; rp.min_level = min_level; rp.max_level = max_level; rp.out = out_res;
+  rp.boxes = boxes; rp.batch_idx = image_idx; rp.n = n; rp.Ohi = (half_t*)hi; rp.Olo = (half_t*)lo; rp.ldo = ldo;
+  return launch_roi_align(rp, (hipStream_t)stream);
+}
+
+int ovm_op_compact_records(const OvmDet3D* rec, const int32_t* keep, int32_t n, int32_t B, OvmDet3D* out, int32_t* counts,
+                           ovm_stream_t stream) {
+  return launch_compact_records((const float*)rec, keep, n, B, (float*)out, counts, (hipStream_t)stream);
+}
+
+int ovm_op_ln_rows(const float* x, int32_t ldx, int32_t M, int32_t D, const float* gamma, const float* beta, float eps, float* y,
+                   int32_t ldf, uint16_t* hi, uint16_t* lo, int32_t ld, int32_t padH, int32_t padW, int32_t il, ovm_stream_t stream) {
+  LnOut o; memset(&o, 0, sizeof(o));
+  o.hi = (half_t*)hi; o.lo = (half_t*)lo; o.ld = ld; o.f32 = y; o.ldf = ldf; o.padH = padH; o.padW = padW; o.il = il;
+  return launch_ln_rows(x, ldx, M, D, gamma, beta, eps, o, (hipStream_t)stream);
+}
+
+int ovm_op_ln_gelu_split(uint16_t* hi, uint16_t* lo, int32_t M, int32_t D, const float* gamma, const float* beta, float eps,
+                         ovm_stream_t stream) {
+  return launch_ln_gelu_split((half_t*)hi, (half_t*)lo, M, D, gamma, beta, eps, (hipStream_t)stream);
+}
+
+int ovm_op_patch_gather(const OvmImage* images, int32_t B, int32_t G, int32_t patch, int32_t Kpad, const float* mean, const float* std,
+                        uint16_t* hi, uint16_t* lo, ovm_stream_t stream) {
+  if (!images || !mean || !std || B < 1) return OVM_ERR_INVALID;
+  std::vector<ImageDesc> hd(B);
+  for (int b = 0; b < B; ++b)
+    hd[b] = ImageDesc{images[b].data, images[b].height, images[b].width, images[b].stride_c, images[b].stride_h, images[b].stride_w};
+  Tmp tmp;
+  ImageDesc* dd = tmp.get<ImageDesc>(B);
+  if (!dd || hipMemcpy(dd, hd.data(), sizeof(ImageDesc) * B, hipMemcpyHostToDevice) != hipSuccess) return OVM_ERR_HIP;
+  const int r = launch_patch_gather(dd, B, G, patch, Kpad, mean, std, (half_t*)hi, (half_t*)lo, (hipStream_t)stream);
+  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && !r) return OVM_ERR_HIP;      // the descriptors are freed on return
+  return r;
+}
+
+int ovm_op_patch_gather_f32(const int64_t* views, int32_t B, int32_t G, int32_t Kpad, uint16_t* hi, uint16_t* lo, ovm_stream_t stream) {
+  if (!views || B < 1 || B > kMaxTowerViews) return OVM_ERR_INVALID;
+  TowerViews v; memset(&v, 0, sizeof(v));
+  v.n = B;
+  for (int b = 0; b < B; ++b) v.v[b] = TowerView{(const float*)(uintptr_t)views[4 * b], views[4 * b + 1], views[4 * b + 2], views[4 * b + 3]};
+  return launch_patch_gather_f32(v, B, G, Kpad, (half_t*)hi, (half_t*)lo, (hipStream_t)stream);
+}
+
+int ovm_op_cls_init(float* X, const float* cls, const float* pos, const float* reg, int32_t R, int32_t B, int32_t T, int32_t D,
+                    ovm_stream_t stream) {
+  return launch_cls_init(X, cls, pos, reg, R, B, T, D, (hipStream_t)stream);
+}
+
+int ovm_op_tokens_cast(const float* X, int32_t B, int32_t T, int32_t G2, int32_t D, int32_t ldo, const float* depth_tok, uint16_t* hi,
+                       uint16_t* lo, ovm_stream_t stream) {
+  return launch_tokens_cast(X, B, T, G2, D, ldo, depth_tok, (half_t*)hi, (half_t*)lo, (hipStream_t)stream);
+}
+
+int ovm_op_tokens_writeback(float* X, const float* F, int32_t B, int32_t T, int32_t G2, int32_t D, ovm_stream_t stream) {
+  return launch_tokens_writeback(X, F, B, T, G2, D, (hipStream_t)stream);
+}
+
+int ovm_op_maxpool2(const uint16_t* in_hi, const uint16_t* in_lo, int32_t B, int32_t G, int32_t D, uint16_t* out_hi, uint16_t* out_lo,
+                    ovm_stream_t stream) {
+  return launch_maxpool2((const half_t*)in_hi, (const half_t*)in_lo, B, G, D, (half_t*)out_hi, (half_t*)out_lo, (hipStream_t)stream);
 }
 
 // Tuning knobs for experiments (not part of the stable surface): "gemm_bm" = 0 (heuristic) | 128 | 256.

@@ -227,6 +227,8 @@ EXPORTS = [
     "ovm_rpn_box_forward", "ovm_gather_records", "ovm_gather_counts", "ovm_host_interp_pos_embed", "ovm_host_resize_pos_embed_aa", "ovm_host_sincos_pos_embed", "ovm_host_shard_range",
     "ovm_backbone_num_levels", "ovm_backbone_level",
     "ovm_op_split_f16", "ovm_op_interleave", "ovm_op_gemm", "ovm_op_gemm_epi", "ovm_op_gemm_swiglu", "ovm_host_swiglu_perm", "ovm_op_layernorm", "ovm_op_attention", "ovm_op_roi_align",
+    "ovm_op_roi_align_ex", "ovm_op_compact_records", "ovm_op_ln_rows", "ovm_op_ln_gelu_split", "ovm_op_patch_gather", "ovm_op_patch_gather_f32",
+    "ovm_op_cls_init", "ovm_op_tokens_cast", "ovm_op_tokens_writeback", "ovm_op_maxpool2",
     "ovm_op_cube_decode", "ovm_op_nms", "ovm_op_rpn_proposals", "ovm_op_boxhead_post", "ovm_debug_copy", "ovm_set_corun", "ovm_profile_enable", "ovm_profile_read",
     "ovm_comm_unique_id", "ovm_comm_init", "ovm_comm_destroy", "ovm_tune_set", "ovm_gdino_postprocess", "ovm_box3d_iou", "ovm_eval_iou2d", "ovm_eval_match", "ovm_host_pil_bilinear_coeffs", "ovm_resize_bilinear_u8", "ovm_resize_bilinear_f32",
     "ovm_g_pack_weight", "ovm_host_pack_weight", "ovm_g_linear", "ovm_g_layernorm", "ovm_g_bmm", "ovm_g_bmm2", "ovm_g_softmax", "ovm_g_softmax2", "ovm_g_eltwise", "ovm_g_gather_rows",
@@ -301,6 +303,16 @@ def load() -> C.CDLL:
     lib.ovm_op_attention.argtypes = [vp, i32, i32, i32, vp, i32, vp]
     lib.ovm_op_roi_align.argtypes = [vp, vp, vp, C.POINTER(i32), C.POINTER(f32), i32, i32, i32, i32, vp, vp, i32, vp, vp]
     lib.ovm_op_cube_decode.argtypes = [vp, i32, vp, vp, vp, vp, C.POINTER(OvmImage), i32, i32, f32, i32, vp, vp, vp]
+    lib.ovm_op_roi_align_ex.argtypes = [C.POINTER(vp), i32, C.POINTER(i32), C.POINTER(f32), i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp]
+    lib.ovm_op_compact_records.argtypes = [vp, vp, i32, i32, vp, vp, vp]
+    lib.ovm_op_ln_rows.argtypes = [vp, i32, i32, i32, vp, vp, f32, vp, i32, vp, vp, i32, i32, i32, i32, vp]
+    lib.ovm_op_ln_gelu_split.argtypes = [vp, vp, i32, i32, vp, vp, f32, vp]
+    lib.ovm_op_patch_gather.argtypes = [C.POINTER(OvmImage), i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32), vp, vp, vp]
+    lib.ovm_op_patch_gather_f32.argtypes = [C.POINTER(i64), i32, i32, i32, vp, vp, vp]
+    lib.ovm_op_cls_init.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp]
+    lib.ovm_op_tokens_cast.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]
+    lib.ovm_op_tokens_writeback.argtypes = [vp, vp, i32, i32, i32, i32, vp]
+    lib.ovm_op_maxpool2.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
     lib.ovm_op_nms.argtypes = [vp, vp, i32, f32, vp, vp, vp]
     lib.ovm_op_rpn_proposals.argtypes = [C.POINTER(vp), i32, C.POINTER(i32), C.POINTER(f32), C.POINTER(f32), C.POINTER(f32),
                                          C.POINTER(OvmImage), i32, i32, i32, f32, vp, vp, vp, vp]
