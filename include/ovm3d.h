@@ -593,6 +593,32 @@ int ovm_eval_match(const OvmEvalCell* cells, int32_t n_cells, int32_t max_gt, co
                    const uint8_t* gt_flag, const uint8_t* gt_crowd, const uint8_t* in_prox, const double* ranges, int32_t n_rng,
                    const double* floors, int32_t n_thr, int32_t* pick, uint8_t* ignored, int32_t* n_gt, ovm_stream_t stream);
 
+/* The exact 3D IoU of every cell's [n_dt][n_gt] block, written as fp64 straight into the CSR IoU buffer ovm_eval_match reads
+ * (`box3d_overlap` per cell, reference cubercnn/evaluation/omni3d_evaluation.py:109-169). dt_cell as for ovm_eval_iou2d;
+ * dt_corners [n_dt_total][8][3] / gt_corners [n_gt_total][8][3] fp32, the ground truth already through nan_to_num. Every value is
+ * (double) of what ovm_box3d_iou gives for the pair (the same per-pair code), a NaN written as 0. One wave per detection row, one
+ * lane per ground-truth box. All device. */
+int ovm_eval_iou3d(const OvmEvalCell* cells, const int32_t* dt_cell, int32_t n_dt_total, const float* dt_corners, const float* gt_corners,
+                   float eps_coplanar, float eps_nonzero, double* iou, ovm_stream_t stream);
+
+#define OVM_NHD_NONE 0    /* the detection has no pair */
+#define OVM_NHD_OK 1      /* paired and scored */
+#define OVM_NHD_SKIPPED 2 /* paired, but a corner distance is not finite: no score (scipy's linear_sum_assignment raises there) */
+
+/* Pairing and disentangled Normalised Hungarian Distance of Omni3DevalWithNHD (reference :2342-2484 with calculate_nhd /
+ * disentangled_nhd :2227-2290), one wave per detection row. Pairing: the first maximum of the row's IoU block (iou: the fp64 CSR
+ * blocks), accepted when it is > 0 and >= iou_thr and dt_ok[d] and gt_ok[g] (uint8: the record carries its fields); pair_gt [n_dt_total]
+ * receives the cell-local ground-truth index in file order, or -1. Cuboid records dt_cuboid [n_dt_total][15] / gt_cuboid
+ * [n_gt_total][15] fp32: xy (2), z, dimensions W H L (3), rotation row-major (9); rows without their fields are not read. Everything
+ * after the load is fp64: corners = signs * (L, H, W)/2 @ R^T + c for the prediction and for the prediction with only xy / z /
+ * dimensions / pose kept (the rest the ground truth's), the five 8x8 Euclidean cost matrices, each assignment solved exactly by
+ * dynamic programming over the 256 subsets, divided by the norm of the ground truth's axis-aligned extent (0 divides as IEEE
+ * does). nhd [n_dt_total][5] = overall, xy, z, dimensions, pose (written for OVM_NHD_OK rows only); status uint8 [n_dt_total] one of
+ * OVM_NHD_*; a skipped row gets pair_gt -1. max_gt: the largest n_gt of any cell, at most 4096 (OVM_ERR_CAPACITY otherwise). All device. */
+int ovm_eval_nhd(const OvmEvalCell* cells, const int32_t* dt_cell, int32_t n_dt_total, int32_t max_gt, const double* iou, double iou_thr,
+                 const uint8_t* dt_ok, const uint8_t* gt_ok, const float* dt_cuboid, const float* gt_cuboid, int32_t* pair_gt, double* nhd,
+                 uint8_t* status, ovm_stream_t stream);
+
 /* ---- data feeding ("next" row 2 of SURVEY.md 8f) ---------------------------------------------------------------------------
  * uint8 bilinear resize bit-identical to Pillow's Image.resize(size, BILINEAR), i.e. to detectron2's ResizeShortestEdge on
  * uint8 images (reference demo/demo.py:79-83, cubercnn/data/dataset_mapper.py:62-72). ovm_host_pil_bilinear_coeffs builds one

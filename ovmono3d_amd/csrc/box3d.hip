@@ -1,7 +1,11 @@
-// Exact intersection volume / IoU of oriented 3D boxes given by their 8 corners (pytorch3d corner order), one thread per
-// (detection, ground-truth) pair. Replaces pytorch3d's `_C.iou_box3d` behind the reference's `box3d_overlap`
-// (cubercnn/evaluation/omni3d_evaluation.py:109-169), including its validity screening of the detections
-// (`_check_coplanar` :68-87, `_check_nonzero` :90-107).
+// Exact intersection volume / IoU of oriented 3D boxes given by their 8 corners (pytorch3d corner order). Replaces
+// pytorch3d's `_C.iou_box3d` behind the reference's `box3d_overlap` (cubercnn/evaluation/omni3d_evaluation.py:109-169),
+// including its validity screening of the detections (`_check_coplanar` :68-87, `_check_nonzero` :90-107).
+//
+// Two entry points, one per-pair routine (pair_iou):
+//   ovm_box3d_iou   the N x M matrix of N detections and M ground-truth boxes, fp32, one thread per pair;
+//   ovm_eval_iou3d  the [n_dt][n_gt] block of every (image, category) cell of the evaluator, fp64, written straight into the
+//                   CSR IoU buffer ovm_eval_match reads; one wave per detection row, one lane per ground-truth box of its cell.
 //
 // Method: the intersection of two convex boxes is a convex polyhedron whose faces lie on faces of A or of B. By the
 // divergence theorem  V = 1/3 * sum_f (p_f . n_f) * area(f),  so
@@ -148,13 +152,11 @@ __device__ bool box_valid(const float* p, float eps_coplanar, float eps_nonzero)
   return true;
 }
 
-__global__ __launch_bounds__(128) void box3d_iou_kernel(const float* __restrict__ dt, const float* __restrict__ gt, int N, int M, float eps_coplanar,
-                                                        float eps_nonzero, float* __restrict__ iou, float* __restrict__ vol) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (long)N * M) return;
-  const int i = (int)(idx / M), j = (int)(idx % M);
-  const float* pa = dt + (size_t)i * 24;
-  const float* pb = gt + (size_t)j * 24;
+// IoU (and the clamped intersection volume) of detection corners `pa` and ground-truth corners `pb`, both [8][3] in camera
+// coordinates: the local frame, face clipping, clamp and detection screening described above. The one per-pair routine of
+// ovm_box3d_iou and ovm_eval_iou3d. Not inlined on purpose: inlined into two kernels the compiler contracts multiply-adds differently
+// in each (measured: 1 % of 2.6 M pairs differed in the last bits), and the evaluator's two routes must give the same IoU bit for bit.
+__device__ __noinline__ float pair_iou(const float* pa, const float* pb, float eps_coplanar, float eps_nonzero, float& vol) {
   // the local frame: both boxes minus the detection's corner centroid
   V3 o = {0.f, 0.f, 0.f};
   for (int k = 0; k < 8; ++k) o = o + corner(pa, k);
@@ -176,8 +178,36 @@ __global__ __launch_bounds__(128) void box3d_iou_kernel(const float* __restrict_
     r = (u > 0.f) ? fminf(v / u, 1.f) : 0.f;
   }
   if (!box_valid(pa, eps_coplanar, eps_nonzero)) { r = 0.f; }            // offending detections get IoU 0 (:160-167)
+  vol = v;
+  return r;
+}
+
+__global__ __launch_bounds__(128) void box3d_iou_kernel(const float* __restrict__ dt, const float* __restrict__ gt, int N, int M, float eps_coplanar,
+                                                        float eps_nonzero, float* __restrict__ iou, float* __restrict__ vol) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long)N * M) return;
+  const int i = (int)(idx / M), j = (int)(idx % M);
+  float v;
+  const float r = pair_iou(dt + (size_t)i * 24, gt + (size_t)j * 24, eps_coplanar, eps_nonzero, v);
   iou[idx] = r;
   if (vol) vol[idx] = v;
+}
+
+// One wave per detection row of the evaluator's CSR layout, lane l on the ground-truth boxes l, l + 64, ... of the row's cell: the
+// per-pair work is long and register-heavy, so a thread never owns more than its share of one row.
+__global__ __launch_bounds__(64) void eval_iou3d_kernel(const OvmEvalCell* __restrict__ cells, const int32_t* __restrict__ dt_cell, int32_t n_dt_total,
+                                                        const float* __restrict__ dt, const float* __restrict__ gt, float eps_coplanar,
+                                                        float eps_nonzero, double* __restrict__ iou) {
+  const int d = blockIdx.x;
+  if (d >= n_dt_total) return;
+  const OvmEvalCell c = cells[dt_cell[d]];
+  const long row = d - c.dt_off;
+  const float* pa = dt + (size_t)d * 24;
+  for (int g = threadIdx.x; g < c.n_gt; g += 64) {
+    float v;
+    const float r = pair_iou(pa, gt + (size_t)(c.gt_off + g) * 24, eps_coplanar, eps_nonzero, v);
+    iou[c.iou_off + row * c.n_gt + g] = (r != r) ? 0.0 : (double)r;
+  }
 }
 
 }  // namespace
@@ -189,5 +219,15 @@ extern "C" int ovm_box3d_iou(const float* boxes_dt, const float* boxes_gt, int32
   const long n = (long)N * M;
   hipLaunchKernelGGL(box3d_iou_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, (hipStream_t)stream, boxes_dt, boxes_gt, N, M, eps_coplanar,
                      eps_nonzero, iou, vol);
+  return hipGetLastError() == hipSuccess ? OVM_OK : OVM_ERR_HIP;
+}
+
+extern "C" int ovm_eval_iou3d(const OvmEvalCell* cells, const int32_t* dt_cell, int32_t n_dt_total, const float* dt_corners, const float* gt_corners,
+                              float eps_coplanar, float eps_nonzero, double* iou, ovm_stream_t stream) {
+  if (n_dt_total < 0) return OVM_ERR_INVALID;
+  if (n_dt_total == 0) return OVM_OK;
+  if (!cells || !dt_cell || !dt_corners || !gt_corners || !iou) return OVM_ERR_INVALID;
+  hipLaunchKernelGGL(eval_iou3d_kernel, dim3((unsigned)n_dt_total), dim3(64), 0, (hipStream_t)stream, cells, dt_cell, n_dt_total, dt_corners, gt_corners,
+                     eps_coplanar, eps_nonzero, iou);
   return hipGetLastError() == hipSuccess ? OVM_OK : OVM_ERR_HIP;
 }

@@ -16,7 +16,9 @@ real-data AP).
 
 ``eval_prox`` restores upstream Omni3D's proximity evaluation (reference :263 turns it on for Objectron and SUNRGBD, option
 :1483-1485, threshold :1459-1461), whose ``evaluateImg`` / ``computeIoU`` overrides the fork lost; ``matcher="device"`` runs the
-2D IoU and the greedy matching of every cell in HIP (``csrc/eval_match.hip``) with results equal to the host's.
+2D IoU and the greedy matching of every cell in HIP (``csrc/eval_match.hip``) with results equal to the host's;
+``stage3d="device"`` adds the two 3D stages around it: the 3D IoU of every cell in one launch (``ovm_eval_iou3d``, the values of
+``ovm_box3d_iou``) and the NHD pairing and scoring (``ovm_eval_nhd``, the assignments solved exactly in fp64), all from one upload.
 """
 from __future__ import annotations
 
@@ -132,17 +134,24 @@ class Omni3Deval:
     a detection whose 2D IoU with every ground truth of the cell (ignored, out-of-range and crowd boxes included) is at most
     ``proximity_thresh`` is ignored, and when every ground truth is ignored in the range (or there is none) every detection is.
     ``matcher``: "host" (numpy) or "device" (HIP kernels ``ovm_eval_iou2d`` / ``ovm_eval_match``, same results; no CPU
-    fallback)."""
+    fallback). ``stage3d``: "host" (one ``ovm_box3d_iou`` call per image, NHD through scipy) or "device" (``ovm_eval_iou3d`` and
+    ``ovm_eval_nhd`` in the device matcher's upload: the same IoU bit for bit, the NHD in fp64 from the same fp32-rounded fields);
+    needs ``matcher="device"`` and true 3D mode."""
 
     def __init__(self, gts: Sequence[Dict], dts: Sequence[Dict], mode: str = "3D", device: Optional[torch.device] = None,
                  fork_compat_2d_iou: bool = False, img_ids: Optional[Sequence] = None, cat_ids: Optional[Sequence] = None,
-                 nhd_iou_threshold: float = 0.5, eval_prox=False, matcher: str = "host"):
+                 nhd_iou_threshold: float = 0.5, eval_prox=False, matcher: str = "host", stage3d: str = "host"):
         if matcher not in ("host", "device"):
             raise ValueError(f"matcher must be 'host' or 'device', not {matcher!r}")
+        if stage3d not in ("host", "device"):
+            raise ValueError(f"stage3d must be 'host' or 'device', not {stage3d!r}")
+        if stage3d == "device" and (matcher != "device" or mode != "3D" or fork_compat_2d_iou):
+            raise ValueError("stage3d='device' needs matcher='device' and 3D mode without fork_compat_2d_iou")
         self.mode = mode
         self.params = Omni3DParams(mode)
         self.device = device
         self.matcher = matcher
+        self.stage3d = stage3d
         self.eval_prox = bool(eval_prox) if isinstance(eval_prox, (bool, np.bool_)) else frozenset(eval_prox)
         self.fork_compat_2d_iou = fork_compat_2d_iou
         self.nhd_iou_threshold = nhd_iou_threshold
@@ -164,6 +173,7 @@ class Omni3Deval:
         self.per_cell: Dict = {}
         self.eval: Dict = {}
         self.nhd_pairs: List[Dict] = []
+        self.nhd_pair_ids: List = []                                            # (detection id, ground-truth id) of each entry of nhd_pairs
 
     # ---- cells and their IoU ------------------------------------------------------------------------------------------
     def _prox_applies(self, img) -> bool:
@@ -202,7 +212,7 @@ class Omni3Deval:
             self.cells[key] = c
         true_3d = self.mode == "3D" and not self.fork_compat_2d_iou
         if not with_iou:
-            if true_3d:
+            if true_3d and self.stage3d == "host":
                 self._build_iou_3d()
             return
         for c in self.cells.values():
@@ -281,7 +291,7 @@ class Omni3Deval:
     def evaluate(self):
         self._build_cells(with_iou=self.matcher == "host")
         self._match_cells()
-        if self.mode == "3D":
+        if self.mode == "3D" and self.stage3d == "host":                        # stage3d="device": paired and scored in _match_device
             self._collect_nhd()
 
     def _match_cells(self):
@@ -293,7 +303,9 @@ class Omni3Deval:
 
     def _match_device(self):
         """Every cell packed CSR-style (vectorised, no loop per detection), one upload, the 2D IoU launch when the IoU or the
-        proximity flags are needed, one matcher launch, one download; ``per_cell`` in the host's format."""
+        proximity flags are needed, one matcher launch, one download; ``per_cell`` in the host's format. With ``stage3d="device"``
+        the corners and cuboid records ride in the same upload, ``ovm_eval_iou3d`` fills the IoU buffer before the matcher and
+        ``ovm_eval_nhd`` reads it after; the one download also brings the IoU blocks and ``nhd_pairs``."""
         if not torch.cuda.is_available():
             raise RuntimeError("matcher='device' needs a HIP device (no CPU fallback)")
         L = _lib.load()
@@ -303,6 +315,7 @@ class Omni3Deval:
         cs = [self.cells[k] for k in keys]
         n, A, T = len(cs), len(p.areaRng), len(p.iouThrs)
         true_3d = self.mode == "3D" and not self.fork_compat_2d_iou
+        dev3d = self.stage3d == "device"
         nd = np.array([len(c.score) for c in cs], dtype=np.int64)
         ng = np.array([len(c.gt_rng) for c in cs], dtype=np.int64)
         cells = np.zeros(n, dtype=_CELL_DTYPE)
@@ -321,31 +334,42 @@ class Omni3Deval:
                cat([c.gt_box for c in cs], np.float64, (-1, 4)), cat([c.dt_rng for c in cs], np.float64), cat([c.gt_rng for c in cs], np.float64),
                cat([c.gt_flag for c in cs], np.uint8), cat([c.gt_crowd for c in cs], np.uint8),
                np.asarray(p.areaRng, dtype=np.float64).reshape(-1), np.minimum(p.iouThrs, 1 - 1e-10).astype(np.float64)]
-        if true_3d:
+        if dev3d:
+            ins += self._pack_3d(cs, n_dt, n_gtb)
+        elif true_3d:
             ins.append(cat([c.iou for c in cs], np.float64))
         buf, io = _pack_segments(ins)
-        # outputs: pick int32, ignored uint8, n_gt int32, in_prox uint8, and the 2D IoU when it is computed here
+        # outputs: pick int32, ignored uint8, n_gt int32, in_prox uint8, and the IoU when it is computed here; with the 3D stages
+        # on the device also pair_gt int32, the NHD status uint8 and nhd fp64 [n_dt][5]
         outs = [np.zeros(n_dt * A * T, np.int32), np.zeros(n_dt * A * T, np.uint8), np.zeros(n * A, np.int32), np.zeros(n_dt, np.uint8)]
-        if not true_3d:
+        if not true_3d or dev3d:
             outs.append(np.zeros(n_iou, np.float64))
+        if dev3d:
+            outs += [np.zeros(n_dt, np.int32), np.zeros(n_dt, np.uint8), np.zeros(n_dt * 5, np.float64)]
         obytes, oo = _pack_segments(outs)
         d_in = torch.from_numpy(buf).to(dev)
         d_out = torch.empty(len(obytes), dtype=torch.uint8, device=dev)
         bi, bo = d_in.data_ptr(), d_out.data_ptr()
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        iou_ptr = (bi + io[10]) if true_3d else (bo + oo[4])
+        iou_ptr = (bi + io[10]) if true_3d and not dev3d else (bo + oo[4])
         prox_ptr = (bo + oo[3]) if any_prox else None
+        max_gt = int(ng.max()) if n else 0
+        if dev3d:
+            _lib.check(L.ovm_eval_iou3d(bi + io[0], bi + io[1], n_dt, bi + io[10], bi + io[11], 1e-4, 1e-8, iou_ptr, stream), what="ovm_eval_iou3d")
         if not true_3d or any_prox:
             _lib.check(L.ovm_eval_iou2d(bi + io[0], bi + io[1], n_dt, bi + io[2], bi + io[3], float(p.proximity_thresh),
                                         None if true_3d else iou_ptr, prox_ptr, stream), what="ovm_eval_iou2d")
-        _lib.check(L.ovm_eval_match(bi + io[0], n, int(ng.max()) if n else 0, iou_ptr, bi + io[4], bi + io[5], bi + io[6], bi + io[7], prox_ptr,
+        _lib.check(L.ovm_eval_match(bi + io[0], n, max_gt, iou_ptr, bi + io[4], bi + io[5], bi + io[6], bi + io[7], prox_ptr,
                                     bi + io[8], A, bi + io[9], T, bo + oo[0], bo + oo[1], bo + oo[2], stream), what="ovm_eval_match")
+        if dev3d:
+            _lib.check(L.ovm_eval_nhd(bi + io[0], bi + io[1], n_dt, max_gt, iou_ptr, float(self.nhd_iou_threshold), bi + io[12], bi + io[13],
+                                      bi + io[14], bi + io[15], bo + oo[5], bo + oo[7], bo + oo[6], stream), what="ovm_eval_nhd")
         host = d_out.cpu().numpy()
         pick = host[oo[0]:oo[0] + outs[0].nbytes].view(np.int32).astype(np.int64)
         ignored = host[oo[1]:oo[1] + outs[1].nbytes].view(np.bool_)
         matched = pick >= 0
         n_gt = host[oo[2]:oo[2] + outs[2].nbytes].view(np.int32).reshape(n, A)
-        if not true_3d:
+        if not true_3d or dev3d:
             iou = host[oo[4]:oo[4] + outs[4].nbytes].view(np.float64)
             for i, c in enumerate(cs):
                 c.iou = iou[iou_off[i]:iou_off[i] + nd[i] * ng[i]].reshape(nd[i], ng[i])
@@ -370,6 +394,47 @@ class Omni3Deval:
             for a in range(A):
                 self.per_cell[key, a] = {"score": c.score, "matched": mt[a], "ignored": ig[a], "n_gt": int(n_gt[i, a]), "gt_order": orders[a][g0:g1],
                                          "pick": pk[a]}
+        if dev3d:
+            status = host[oo[6]:oo[6] + outs[6].nbytes]
+            pair_gt = host[oo[5]:oo[5] + outs[5].nbytes].view(np.int32)
+            nhd = host[oo[7]:oo[7] + outs[7].nbytes].view(np.float64).reshape(n_dt, 5)
+            # the host's order: cells by (category, image) as strings, detections ascending
+            order = sorted(range(n), key=lambda i: (str(keys[i][1]), str(keys[i][0])))
+            rows = np.concatenate([np.arange(dt_off[i], dt_off[i] + nd[i]) for i in order]) if n else np.zeros(0, np.int64)
+            rows = rows[status[rows] == _lib.OVM_NHD_OK]
+            names = ("overall",) + _nhd.COMPONENTS
+            self.nhd_pairs = [dict(zip(names, v)) for v in nhd[rows].tolist()]
+            cell_of = ins[1]
+            self.nhd_pair_ids = [(cs[i].dt[r - dt_off[i]]["id"], cs[i].gt[g]["id"])
+                                 for r, i, g in zip(rows.tolist(), cell_of[rows].tolist(), pair_gt[rows].tolist())]
+
+    def _pack_3d(self, cs, n_dt, n_gtb):
+        """The 3D stages' inputs in detection / ground-truth row order: corners fp32 [.,8,3] (ground truth through nan_to_num, as
+        ``_build_iou_3d``), "carries its NHD fields" uint8, cuboid records fp32 [.,15] = xy, z (the record's depth), dimensions,
+        rotation - rounded to fp32 where ``nhd.cuboid_corners`` rounds them."""
+        def corners(recs, count):
+            a = np.asarray([r["bbox3D"] for r in recs], np.float32).reshape(-1, 8, 3) if recs else np.zeros((0, 8, 3), np.float32)
+            assert a.shape[0] == count
+            return a
+
+        def cuboids(recs, rot, need):
+            ok, out = np.zeros(len(recs), np.uint8), np.zeros((len(recs), 15), np.float32)
+            for i, r in enumerate(recs):
+                if any(f not in r for f in need):
+                    continue
+                try:                                                            # a malformed field raises in nhd.cuboid_corners too: no pair
+                    out[i, 0:2] = r["center_cam"][:2]
+                    out[i, 2] = r["depth"]
+                    out[i, 3:6] = r["dimensions"]
+                    out[i, 6:15] = np.asarray(r[rot], dtype=np.float32).reshape(9)
+                    ok[i] = 1
+                except Exception:
+                    out[i] = 0
+            return ok, out
+        dts, gts = [d for c in cs for d in c.dt], [g for c in cs for g in c.gt]
+        dt_ok, dt_cub = cuboids(dts, "pose", ("center_cam", "dimensions", "pose", "depth"))
+        gt_ok, gt_cub = cuboids(gts, "R_cam", ("center_cam", "dimensions", "R_cam", "depth"))
+        return [corners(dts, n_dt), np.nan_to_num(corners(gts, n_gtb), nan=0.0, posinf=0.0, neginf=0.0), dt_ok, gt_ok, dt_cub, gt_cub]
 
     # ---- precision / recall tables ----------------------------------------------------------------------------------------
     def accumulate(self):
@@ -427,7 +492,7 @@ class Omni3Deval:
         them, which leaves the mean where it is; here each pair is scored once. (Its IoU lookup reads the matrix in
         un-reordered ground-truth order while walking the reordered list, :2363-2392; the pairing here follows the intent.)"""
         need_dt, need_gt = ("center_cam", "dimensions", "pose", "depth"), ("center_cam", "dimensions", "R_cam", "depth")
-        self.nhd_pairs = []
+        self.nhd_pairs, self.nhd_pair_ids = [], []
         for key in sorted(self.cells, key=lambda k: (str(k[1]), str(k[0]))):
             c = self.cells[key]
             if not c.dt or not c.gt or c.iou.size == 0:
@@ -442,6 +507,7 @@ class Omni3Deval:
                 true = {"xy": g["center_cam"][:2], "z": g["depth"], "dimensions": g["dimensions"], "pose": g["R_cam"]}
                 try:
                     self.nhd_pairs.append(_nhd.disentangled_nhd(pred, true))
+                    self.nhd_pair_ids.append((d["id"], g["id"]))
                 except Exception:                                               # a degenerate box: the reference logs and moves on (:2424-2426)
                     continue
 
@@ -505,9 +571,11 @@ class Omni3Deval:
 
 
 def evaluate_omni3d(gts, dts: Sequence[Dict], device=None, only_2d: bool = False, fork_compat_2d_iou: bool = False,
-                    category_map=None, passthrough_dataset_ids: bool = False, eval_prox=False, matcher: str = "host") -> Dict:
+                    category_map=None, passthrough_dataset_ids: bool = False, eval_prox=False, matcher: str = "host",
+                    stage3d: str = "host") -> Dict:
     """AP2D and AP3D dictionaries for one dataset (reference _evaluate_predictions_on_omni :1255-1391 without the file plumbing).
-    ``eval_prox`` (a bool, or the image ids whose cells it applies to) and ``matcher``: as ``Omni3Deval``.
+    ``eval_prox`` (a bool, or the image ids whose cells it applies to) and ``matcher``: as ``Omni3Deval``; so is ``stage3d``, which
+    applies to the 3D pass.
 
     ``gts``: an ``Omni3DGroundTruth`` (images and categories evaluated = the dataset's, as the reference; detections on unknown
     images or categories are dropped :1319-1334) or a plain list of ground-truth dicts. ``category_map`` (``CategoryMap``): the
@@ -533,7 +601,7 @@ def evaluate_omni3d(gts, dts: Sequence[Dict], device=None, only_2d: bool = False
     if not only_2d:
         d3 = [d for d in dts if "bbox3D" in d]
         e3 = Omni3Deval(gts, d3, "3D", device=device, fork_compat_2d_iou=fork_compat_2d_iou, img_ids=img_ids, cat_ids=cat_ids,
-                        eval_prox=eval_prox, matcher=matcher)
+                        eval_prox=eval_prox, matcher=matcher, stage3d=stage3d)
         e3.evaluate(); e3.accumulate()
         res["bbox_3D"] = e3.summarize()
         if names is not None:

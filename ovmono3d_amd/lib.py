@@ -114,6 +114,10 @@ class OvmSceneSegment(C.Structure):
     _fields_ = [("x0", C.c_int64), ("y0", C.c_int64), ("x1", C.c_int64), ("y1", C.c_int64)]
 
 
+# include/ovm3d.h OVM_NHD_*: the per-detection status ovm_eval_nhd writes
+OVM_NHD_NONE, OVM_NHD_OK, OVM_NHD_SKIPPED = 0, 1, 2
+
+
 class OvmEvalCell(C.Structure):
     """Mirror of include/ovm3d.h OvmEvalCell."""
     _fields_ = [("iou_off", C.c_int64), ("dt_off", C.c_int32), ("n_dt", C.c_int32), ("gt_off", C.c_int32), ("n_gt", C.c_int32),
@@ -230,7 +234,7 @@ EXPORTS = [
     "ovm_op_roi_align_ex", "ovm_op_compact_records", "ovm_op_ln_rows", "ovm_op_ln_gelu_split", "ovm_op_patch_gather", "ovm_op_patch_gather_f32",
     "ovm_op_cls_init", "ovm_op_tokens_cast", "ovm_op_tokens_writeback", "ovm_op_maxpool2",
     "ovm_op_cube_decode", "ovm_op_nms", "ovm_op_rpn_proposals", "ovm_op_boxhead_post", "ovm_debug_copy", "ovm_set_corun", "ovm_profile_enable", "ovm_profile_read",
-    "ovm_comm_unique_id", "ovm_comm_init", "ovm_comm_destroy", "ovm_tune_set", "ovm_gdino_postprocess", "ovm_box3d_iou", "ovm_eval_iou2d", "ovm_eval_match", "ovm_host_pil_bilinear_coeffs", "ovm_resize_bilinear_u8", "ovm_resize_bilinear_f32",
+    "ovm_comm_unique_id", "ovm_comm_init", "ovm_comm_destroy", "ovm_tune_set", "ovm_gdino_postprocess", "ovm_box3d_iou", "ovm_eval_iou2d", "ovm_eval_match", "ovm_eval_iou3d", "ovm_eval_nhd", "ovm_host_pil_bilinear_coeffs", "ovm_resize_bilinear_u8", "ovm_resize_bilinear_f32",
     "ovm_g_pack_weight", "ovm_host_pack_weight", "ovm_g_linear", "ovm_g_layernorm", "ovm_g_bmm", "ovm_g_bmm2", "ovm_g_softmax", "ovm_g_softmax2", "ovm_g_eltwise", "ovm_g_gather_rows",
     "ovm_g_groupnorm", "ovm_g_biattn", "ovm_g_msdeform", "ovm_g_sine_embed", "ovm_g_normalize_image", "ovm_g_topk", "ovm_g_rowmax",
     "ovm_g_attn_f32", "ovm_g_msdeform_fused", "ovm_g_rowop",
@@ -333,6 +337,8 @@ def load() -> C.CDLL:
     lib.ovm_box3d_iou.argtypes = [vp, vp, i32, i32, f32, f32, vp, vp, vp]
     lib.ovm_eval_iou2d.argtypes = [vp, vp, i32, vp, vp, C.c_double, vp, vp, vp]
     lib.ovm_eval_match.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp]
+    lib.ovm_eval_iou3d.argtypes = [vp, vp, i32, vp, vp, f32, f32, vp, vp]
+    lib.ovm_eval_nhd.argtypes = [vp, vp, i32, i32, vp, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.ovm_geo_default_params.argtypes = [C.POINTER(OvmGeoParams)]
     lib.ovm_geo_last_error.argtypes = []
     lib.ovm_geo_last_error.restype = C.c_char_p

@@ -56,6 +56,8 @@ def run(args):
             raise SystemExit(f"--predictions takes NAME=FILE, got {item!r}")
         pairs.append((name, path))
     all_files, all_dets, prox_images, written = [], [], set(), {}
+    stage3d = "host" if args.only_2d else args.eval_3d                         # no 3D pass, no 3D stages
+    matcher = "device" if stage3d == "device" else args.eval_matcher          # the 3D stages ride in the device matcher's upload
     for name, path in pairs:
         gt_file = os.path.join(args.datasets_root, name + ".json")
         dets = [inst for rec in load_predictions(path) for inst in rec["instances"]]
@@ -68,7 +70,7 @@ def run(args):
         logger.info("%s: %d detections, %d ground-truth boxes", name, len(dets), len(gt))
         if len(gt):
             cmap = category_map_for(None, "novel", gt, args.category_meta)
-            ap = evaluate_omni3d(gt, dets, category_map=cmap, eval_prox=prox, matcher=args.eval_matcher, only_2d=args.only_2d)
+            ap = evaluate_omni3d(gt, dets, category_map=cmap, eval_prox=prox, matcher=matcher, stage3d=stage3d, only_2d=args.only_2d)
             os.makedirs(os.path.join(args.output_dir, name), exist_ok=True)
             written[name] = os.path.join(args.output_dir, name, "omni_ap.json")
             with open(written[name], "w") as f:
@@ -78,7 +80,7 @@ def run(args):
     gt = Omni3DGroundTruth(all_files, geo_filter_settings())
     if len(gt):
         ap = evaluate_omni3d(gt, all_dets, category_map=category_map_for(None, "novel", gt, args.category_meta), eval_prox=prox_images,
-                             matcher=args.eval_matcher, only_2d=args.only_2d)
+                             matcher=matcher, stage3d=stage3d, only_2d=args.only_2d)
         ap["collective"] = collective_summary(ap)
         os.makedirs(args.output_dir, exist_ok=True)
         written["all"] = os.path.join(args.output_dir, "omni_ap_all.json")
@@ -96,6 +98,8 @@ def argument_parser():
     ap.add_argument("--output-dir", default="output/ovmono3d_geo")
     ap.add_argument("--eval-prox", action="store_true", help="upstream Omni3D's proximity rule for SUNRGBD / Objectron, as tools/train_net.py")
     ap.add_argument("--eval-matcher", choices=("host", "device"), default="host")
+    ap.add_argument("--eval-3d", choices=("host", "device"), default="host", help="the evaluator's 3D IoU and NHD stages in HIP; implies "
+                    "--eval-matcher device")
     ap.add_argument("--only-2d", action="store_true", help="AP2D only (needs no GPU; the 3D IoU runs on the device)")
     return ap
 

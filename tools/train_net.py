@@ -16,7 +16,7 @@ forwarded to the model when TEST.ORACLE2D is set and the oracle file exists, and
 
 ``--eval-prox`` turns on upstream Omni3D's proximity evaluation for the datasets whose name contains Objectron or SUNRGBD
 (reference omni3d_evaluation.py:263), in their own evaluation and for their images in the collective pass; ``--eval-matcher
-device`` runs the evaluator's matching on the GPU (same results as ``host``).
+device`` runs the evaluator's matching on the GPU (same results as ``host``); ``--eval-3d device`` also its 3D IoU and NHD stages.
 """
 import argparse
 import json
@@ -61,7 +61,9 @@ def uses_proximity(name):
 
 
 def do_test(cfg, model, mode="base", datasets_root="datasets/Omni3D", image_root="datasets", depth_dir=None, category_meta=None,
-            eval_prox=False, matcher="host"):
+            eval_prox=False, matcher="host", stage3d="host"):
+    if stage3d == "device":                                                     # the 3D stages ride in the device matcher's upload
+        matcher = "device"
     if mode == "novel":
         names = cfg.DATASETS.TEST_NOVEL
     elif mode == "base":
@@ -97,7 +99,8 @@ def do_test(cfg, model, mode="base", datasets_root="datasets/Omni3D", image_root
                 prox_images |= set(gt.image_ids)
             if len(gt):
                 cmap = category_map_for(cfg, mode, gt, category_meta)
-                ap = evaluate_omni3d(gt, [inst for r in results for inst in r["instances"]], category_map=cmap, eval_prox=prox, matcher=matcher)
+                ap = evaluate_omni3d(gt, [inst for r in results for inst in r["instances"]], category_map=cmap, eval_prox=prox, matcher=matcher,
+                                     stage3d=stage3d)
                 with open(os.path.join(out_dir, name, "omni_ap.json"), "w") as f:
                     json.dump(ap, f)
                 with open(os.path.join(out_dir, name, "category_meta.json"), "w") as f:
@@ -113,7 +116,7 @@ def do_test(cfg, model, mode="base", datasets_root="datasets/Omni3D", image_root
         if len(gt):
             # a cell's matching depends on its own image only: the proximity rule goes with the images of its datasets
             ap = evaluate_omni3d(gt, all_dets, category_map=category_map_for(cfg, mode, gt, category_meta), eval_prox=prox_images,
-                                 matcher=matcher)
+                                 matcher=matcher, stage3d=stage3d)
             ap["collective"] = collective_summary(ap)
             with open(os.path.join(out_dir, "omni_ap_all.json"), "w") as f:
                 json.dump(ap, f)
@@ -156,11 +159,13 @@ def main(args):
         set_native_comm(NativeComm.from_torch_distributed(torch.device("cuda", local_rank)))
     DetectionCheckpointer(model, save_dir=cfg.OUTPUT_DIR).resume_or_load(cfg.MODEL.WEIGHTS, resume=args.resume)
     if cfg.TEST.CAT_MODE == "all":
-        do_test(cfg, model, "novel", args.datasets_root, args.image_root, args.depth_dir, args.category_meta, args.eval_prox, args.eval_matcher)
-        do_test(cfg, model, "base", args.datasets_root, args.image_root, args.depth_dir, args.category_meta, args.eval_prox, args.eval_matcher)
+        do_test(cfg, model, "novel", args.datasets_root, args.image_root, args.depth_dir, args.category_meta, args.eval_prox, args.eval_matcher,
+                args.eval_3d)
+        do_test(cfg, model, "base", args.datasets_root, args.image_root, args.depth_dir, args.category_meta, args.eval_prox, args.eval_matcher,
+                args.eval_3d)
     else:
         do_test(cfg, model, cfg.TEST.CAT_MODE, args.datasets_root, args.image_root, args.depth_dir, args.category_meta, args.eval_prox,
-                args.eval_matcher)
+                args.eval_matcher, args.eval_3d)
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()
@@ -184,6 +189,9 @@ def default_argument_parser():
                    "(upstream Omni3D's eval_prox)")
     p.add_argument("--eval-matcher", choices=("host", "device"), default="host", help="(native build) where the evaluator matches "
                    "detections to ground truth: host (numpy) or device (HIP kernel); the results are the same")
+    p.add_argument("--eval-3d", choices=("host", "device"), default="host", help="(native build) where the evaluator's 3D stages run: host "
+                   "(one 3D IoU call per image, NHD through scipy) or device (one IoU launch over all cells, NHD solved in HIP; implies "
+                   "--eval-matcher device); the IoU is the same bit for bit, the NHD agrees to fp32 rounding of the host path")
     p.add_argument("opts", default=None, nargs=argparse.REMAINDER)
     return p
 
