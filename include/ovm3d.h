@@ -281,6 +281,17 @@ typedef struct OvmGemmEpiOp {
   const float* pos; int32_t G2, G, Cout, reserved;
 } OvmGemmEpiOp;
 int ovm_op_gemm_epi(const OvmGemmEpiOp* op, ovm_stream_t stream);
+/* The fused two-layer MLP of the detector's image branch in isolation (test-only): the two launches of that route - fc1 + activation +
+ * fc2's k-slices in one kernel, then the split-K reduce - on the caller's own device buffers; nothing is converted or allocated.
+ * x_il: interleaved split rows [M][C/32][hi 32 | lo 32] (ovm_op_interleave), row stride ldx >= 2 C halves; w1_il: the same image of
+ * W1 [hidden][C], w2_il of W2 [C][hidden]; b1 [hidden], b2 [C] or null; act: 1 ReLU, 2 GELU(erf). ws: fp32 workspace of at least
+ * (hidden / 256) * M * C * 4 bytes, written as slabs [hidden / 256][M][C]. X != null: X [M][C] += result + b2 in place (a Swin block's
+ * residual); X == null: Y [M][C] = result + b2 (+ R [M][C] when given) (the encoder's FFN). All pointers 16-byte aligned.
+ * OVM_ERR_INVALID, and nothing launched, for a shape the kernel does not take (C % 32, hidden % 256, act, f16x3 only);
+ * OVM_ERR_CAPACITY, and nothing launched, when ws_bytes is too small. */
+int ovm_op_mlp_fused(const uint16_t* x_il, int32_t ldx, const uint16_t* w1_il, const float* b1, const uint16_t* w2_il, const float* b2,
+                     int32_t M, int32_t C, int32_t hidden, int32_t act, float* ws, int64_t ws_bytes, float* X, const float* R, float* Y,
+                     ovm_stream_t stream);
 /* hi, lo [rows][K] (K % 32 == 0) -> out [rows][K/32][hi 32 | lo 32]: the interleaved operand image of the split-precision GEMM.
  * In split mode ovm_op_gemm takes w_hi = such an image and w_lo = w_hi + 32; activations may be plain arrays or an image
  * (a_lo = a_hi + 32, lda = 2K). */
@@ -538,6 +549,8 @@ int ovm_g_rowop(const OvmRowOp* op, ovm_stream_t stream);
  *   gdino_ffn_split 0|1 (decoder row chains: the FFN's 512-column chunks on separate workgroups + a finishing kernel; bit-identical, faster for the detector alone, not beside the ViT; default 0; read when a plan is built),
  *   gdino_swin_fused 0|1 (Swin blocks: qkv projection inside the window-attention kernel; default 1; read when a plan is built),
  *   gdino_gemm256 0|1 (the detector's wide K <= 256 contractions on the 256 x 256 kernel; default 1; read when a plan is built),
+ *   gdino_mlp_fused 0|1|2 (the image branch's two-layer MLPs as one kernel + the split-K reduce: 0 off, 1 the Swin blocks whose fc2 is
+ *   split over K today, 2 those and the encoder's FFN where its slabs fit the workspace; default 1; read when a plan is built),
  *   attn_tail_split 0|1 (attention's leftover queries split over 16 key slices + combine kernel; default 1), attn_prio n (experiment:
  *   s_setprio inside the two-wave-group attention kernel; default 0), gemm256_ksplit n (experiment: split-K hint of the 256 x 256 kernel for
  *   proj / fc2; default 0 = off, measured slower), glin_wpe 2|4 (experiment: workgroups per CU the small fp32-A GEMM is compiled for; default 2),

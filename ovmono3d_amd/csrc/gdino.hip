@@ -23,12 +23,13 @@ using namespace ovm;
 using namespace ovm::gdino;
 
 namespace ovm {
-GdinoTune g_gdino_tune = {1, 1, 0, 1, 1};       // branches, dec_chain, ffn_split, swin_fused, gemm256
+GdinoTune g_gdino_tune = {1, 1, 0, 1, 1, 1};    // branches, dec_chain, ffn_split, swin_fused, gemm256, mlp_fused
 void set_gdino_branches(int v) { g_gdino_tune.branches = v ? 1 : 0; }       // engines created afterwards
-void set_gdino_dec_chain(int v) { g_gdino_tune.dec_chain = v ? 1 : 0; }     // this and the three below: plans built afterwards
+void set_gdino_dec_chain(int v) { g_gdino_tune.dec_chain = v ? 1 : 0; }     // this and the four below: plans built afterwards
 void set_gdino_ffn_split(int v) { g_gdino_tune.ffn_split = v ? 1 : 0; }
 void set_gdino_swin_fused(int v) { g_gdino_tune.swin_fused = v ? 1 : 0; }
 void set_gdino_gemm256(int v) { g_gdino_tune.gemm256 = v ? 1 : 0; }
+void set_gdino_mlp_fused(int v) { g_gdino_tune.mlp_fused = v < 0 ? 0 : (v > 2 ? 2 : v); }
 }  // namespace ovm
 
 namespace ovm {
@@ -146,6 +147,15 @@ void swin_block(Run& r, const SwinBlock& blk, const WinMaps& wmaps, float* x, in
   }
   // output projection; the epilogue un-partitions / un-shifts / crops through the same index map and adds the shortcut
   { GemmParams q = r.gp(ctx, M, blk.proj); q.X = x; q.ldx = C; q.row_map = wmaps.win; r.gemm(q, EPI_RESID); }
+  if (r.mlp_fused_ok(1, ntok, blk.fc1, blk.fc2, 2)) {
+    // fc1, GELU and fc2's k-slices in one kernel, then the reduce fc2 ends in anyway: no f1 image, one launch of fat workgroups less
+    SplitBuf hn = r.split_il((size_t)ntok, C);
+    r.ln(x, ntok, C, blk.ln2, eps, nullptr, nullptr, &hn);
+    GemmParams q = r.gp(hn, ntok, blk.fc2); q.X = x; q.ldx = C;
+    r.mlp_fused(hn, ntok, blk.fc1, blk.fc2, 2, q, EPI_RESID);
+    r.release(mk);
+    return;
+  }
   // stage 1 (17,689 tokens x 512 outputs over K = 128: 556 tiles of 128 x 128, or 140 of 256 x 256 in one round): interleaved rows
   const bool wide = ((ntok + 127) / 128) * ((4 * C + 127) / 128) > 512 && (4 * C) % 256 == 0;
   SplitBuf hn = wide ? r.split_for256((size_t)ntok, C) : r.split((size_t)ntok, C);
@@ -235,6 +245,7 @@ struct EncBufs {
   BiAttnWs bw; float *sc, *stat, *part, *bml;
   float *text2, *tqk, *tv, *tctx, *tff;
   SplitBuf vis_sp, visp_sp; float *val, *ow; SplitBuf dsp; float* pre; SplitBuf ff;
+  bool ffn_fused;                                          // the layers' FFN on the fused route (ff is not allocated then)
 };
 
 // bi-directional image <-> text attention; leaves the two contexts (cv, ct) and the normalised inputs (v, t) for the halves below
@@ -286,8 +297,13 @@ void deformable_layer(Run& r, const EncLayer& ly, EncBufs& b, float* vis) {
   deform(r, b.val, D, b.ow, NOW, pl->ref, 2, 0, S, nullptr, &b.dsp);
   { GemmParams q = r.gp(b.dsp, S, ly.msda.out); q.C = b.pre; q.ldc = D; q.R = vis; q.ldr = D; r.gemm(q, EPI_STORE); }
   r.ln(b.pre, S, D, ly.de_ln1, c.eps, nullptr, b.v, &b.vsp);
-  { GemmParams q = r.gp(b.vsp, S, ly.de_fc1); q.Ohi = b.ff.hi; q.Olo = b.ff.lo; q.ldo = b.ff.ld; q.relu = 1; r.gemm(q, EPI_STORE); }
-  { GemmParams q = r.gp(b.ff, S, ly.de_fc2); q.C = b.pre; q.ldc = D; q.R = b.v; q.ldr = D; r.gemm(q, EPI_STORE); }
+  if (b.ffn_fused) {
+    GemmParams q = r.gp(b.vsp, S, ly.de_fc2); q.C = b.pre; q.ldc = D; q.R = b.v; q.ldr = D;
+    r.mlp_fused(b.vsp, S, ly.de_fc1, ly.de_fc2, 1, q, EPI_STORE);
+  } else {
+    { GemmParams q = r.gp(b.vsp, S, ly.de_fc1); q.Ohi = b.ff.hi; q.Olo = b.ff.lo; q.ldo = b.ff.ld; q.relu = 1; r.gemm(q, EPI_STORE); }
+    { GemmParams q = r.gp(b.ff, S, ly.de_fc2); q.C = b.pre; q.ldc = D; q.R = b.v; q.ldr = D; r.gemm(q, EPI_STORE); }
+  }
   r.ln(b.pre, S, D, ly.de_ln2, c.eps, nullptr, vis);
 }
 
@@ -316,7 +332,9 @@ void encoder(Run& r, State& st) {
   b.ow = r.f32((size_t)S * now_cols(c));
   b.dsp = r.split((size_t)S, D);
   b.pre = r.f32((size_t)S * D);
-  b.ff = r.split((size_t)S, c.ffn_dim);
+  b.ffn_fused = b.vsp.il;
+  for (auto& ly : r.g->enc) b.ffn_fused = b.ffn_fused && r.mlp_fused_ok(2, S, ly.de_fc1, ly.de_fc2, 1);
+  if (!b.ffn_fused) b.ff = r.split((size_t)S, c.ffn_dim);
   const float* vis_in = st.vis0; const float* text_in = st.text0;
   for (auto& ly : r.g->enc) {
     fusion_layer(r, ly, b, vis_in, text_in);
@@ -665,7 +683,7 @@ int ovm_gdino_forward(OvmGdino* g, const OvmImage* image, const int32_t* token_i
   } else {
     Run run{g, pl, s, false};
     OVM_TRY(g, forward_impl(run));
-    pl->launches = run.launches;
+    pl->launches = run.launches; pl->mlp_fused_sites = run.mlp_sites;
     if (g->graphs_enabled) capture_plan(g, pl, s);
   }
   g->launches_last = pl->launches;
@@ -700,6 +718,7 @@ int ovm_gdino_last_outputs(OvmGdino* g, const float** pred_logits, const float**
 int64_t ovm_gdino_debug_copy(OvmGdino* g, const char* name, void* dst, int64_t capacity_elems, ovm_stream_t stream) {
   if (!g || !g->last || !name) return OVM_ERR_INVALID;
   if (std::string(name) == "launches") return g->launches_last;
+  if (std::string(name) == "mlp_fused_sites") return g->last->mlp_fused_sites;            // MLPs of the last plan's forward on the fused route
   if (std::string(name) == "plans") return (int64_t)g->plans.size();                      // plan-cache occupancy (tests, bench)
   if (std::string(name) == "plan_bytes") { int64_t b = 0; for (Plan* q : g->plans) b += (int64_t)q->bytes; return b; }
   auto it = g->last->taps.find(name);

@@ -58,6 +58,24 @@ struct SwinQkvAttnParams {
 bool swin_qkv_attn_supported(int C, int nh, int ws, int npass);
 int launch_swin_qkv_attn(const SwinQkvAttnParams& p, hipStream_t s);
 
+// ---- two-layer MLP in one kernel (mlp_fused.hip; f16x3 mode): a workgroup owns 64 rows and 256 hidden columns, computes its piece
+// of act(X W1^T + b1), keeps it in LDS as a split image and multiplies it by the matching k-slice of W2; the partial sums go to slab
+// `chunk` of the split-K workspace [hidden / 256][M][C] and splitk_epilogue_kernel finishes them (b2, residual, output forms).
+struct MlpFusedParams {
+  const half_t* X; int ldx;           // interleaved split rows [M][C/32][hi 32 | lo 32], row stride ldx >= 2 C halves
+  const half_t* W1; const float* b1;  // fc1: packed image [>= hidden][C/32][hi 32 | lo 32] (what the GEMMs read), bias [hidden] or null
+  const half_t* W2;                   // fc2: packed image [>= C][hidden/32][hi 32 | lo 32]
+  int M, C, hidden;
+  int act;                            // 1 ReLU, 2 GELU(erf)  (GemmParams::relu's codes)
+  float* part; size_t part_cap;       // workspace, bytes
+};
+bool mlp_fused_supported(int M, int C, int hidden, int act, int npass);
+size_t mlp_fused_ws_bytes(int M, int C, int hidden);
+// `out`: the second launch's operands as fc2's GemmParams carries them (bias = b2; EPI_RESID: X, ldx, gamma, row_map; EPI_STORE: C / Ohi,
+// R, ...); M, N and the split-K fields are set here. OVM_ERR_INVALID (nothing launched) for an unsupported shape or a missing
+// pointer, OVM_ERR_CAPACITY (nothing launched) when the slabs do not fit part_cap
+int launch_mlp_fused(const MlpFusedParams& p, const GemmParams& out, int epi, hipStream_t s);
+
 // rel_h[(m * H + h)][kh] = q[m][h*DH : (h+1)*DH] . Rh[qh - kh + gh - 1], rel_w likewise over kw with Rw and qw, for the rows m of
 // fp32 q (row stride ldq); a row's position on its gh x gw attention grid is (t / gw, t % gw) with t = m % (gh * gw)
 int launch_relpos_tables(const float* q, int ldq, int M, int H, int DH, int gh, int gw, const float* Rh, const float* Rw, float* rel_h,

@@ -18,7 +18,7 @@
 
 namespace ovm {
 
-// ovm_tune_set's detector keys, process wide. `branches` is copied into a handle when it is created, the other four into a Plan when it
+// ovm_tune_set's detector keys, process wide. `branches` is copied into a handle when it is created, the other five into a Plan when it
 // is built; the forward reads the plan's copy alone, so every pass over a plan (sizing, eager, capture, later eager calls) walks the
 // same allocation and launch sequence whatever is set in between.
 struct GdinoTune {
@@ -28,6 +28,8 @@ struct GdinoTune {
                        // but 51.14 -> 50.97 images/s beside the ViT (four times the workgroups on the chip): off
   int swin_fused;      // Swin blocks: qkv projection inside the window-attention kernel
   int gemm256;         // the wide K <= 256 contractions on the 256 x 256 GEMM (interleaved activations)
+  int mlp_fused;       // two-layer MLPs of the image branch in one kernel + the split-K reduce (mlp_fused.hip): 0 off, 1 Swin blocks,
+                       // 2 Swin blocks and the encoder's FFN
 };
 extern GdinoTune g_gdino_tune;
 
@@ -130,6 +132,7 @@ struct Plan {
   std::map<std::string, std::pair<const void*, int64_t>> taps;
   hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
   long launches = 0;
+  int mlp_fused_sites = 0;                       // MLPs of one forward that took the fused route (ovm_gdino_debug_copy "mlp_fused_sites")
   void drop_graph() {
     if (exec) { (void)hipGraphExecDestroy(exec); exec = nullptr; }
     if (graph) { (void)hipGraphDestroy(graph); graph = nullptr; }
@@ -157,6 +160,7 @@ struct Run {
   OvmGdino* g; Plan* pl; hipStream_t s; bool dry;
   size_t off = 0, peak = 0;
   long launches = 0;
+  int mlp_sites = 0;                             // MLPs on the fused route so far
   int rc = OVM_OK;
   // the two branches (see Model::aux). `s` is the stream the op wrappers launch on; fork() lets the text branch start from
   // the current point of the main stream, join() makes the main stream wait for it. Each branch has its own slice of the split-K
@@ -211,6 +215,12 @@ struct Run {
     b.hi = (half_t*)alloc(rows * b.ld * sizeof(half_t)); b.lo = b.hi ? b.hi + 32 : nullptr;
     return b;
   }
+  // interleaved split rows whatever the gemm256 knob says: the A operand of the fused MLP
+  SplitBuf split_il(size_t rows, int K) {
+    SplitBuf b; b.il = true; b.ld = 2 * K;
+    b.hi = (half_t*)alloc(rows * b.ld * sizeof(half_t)); b.lo = b.hi + 32;
+    return b;
+  }
   size_t mark() const { return off; }
   void release(size_t m) { off = m; }
   void fail(int r, const char* what) { if (rc == OVM_OK) { rc = r; if (g->err.empty()) g->err = what; } }
@@ -242,6 +252,28 @@ struct Run {
     if (!go()) return;
     if (p.a_il && gemm256_supported(p, g->precision)) chk(launch_gemm256(p, epi, 1, s), "gemm256");
     else chk(launch_gemm(p, g->precision, epi, A_ROWMAJOR, s), "gemm");
+  }
+
+  // Two-layer MLP fc2(act(fc1(x))) of the image branch: does this site take the fused route (mlp_fused.hip)? `site`: the knob value that
+  // enables it (1 Swin, 2 encoder). Yes when the kernel takes the shape, fc2 is one of the thin grids that end in the split-K reduce
+  // today (launch_ws: up to 96 tiles of 128 x 128 - elsewhere the fused route would ADD that launch: Swin stage 1) and the slabs fit
+  // the image branch's slice of the workspace; otherwise the caller issues the two GEMMs. The same answer in every pass over a plan.
+  bool mlp_fused_ok(int site, int M, const Lin& fc1, const Lin& fc2, int act) const {
+    const int C = fc2.N, hidden = fc1.N;
+    if (pl->tune.mlp_fused < site || g->precision != 3 || fc1.K != C || fc1.Kpad != C || fc2.K != hidden || fc2.Kpad != hidden) return false;
+    if (!mlp_fused_supported(M, C, hidden, act, g->precision)) return false;
+    if ((long)((M + 127) / 128) * ((C + 127) / 128) > 96) return false;
+    const size_t cap = (g->branches && g->aux) ? pl->gemm_ws_cap - kAuxWs : pl->gemm_ws_cap;
+    return mlp_fused_ws_bytes(M, C, hidden) <= cap;
+  }
+  // A: interleaved rows [M][2 C]; out: fc2's GemmParams with the epilogue operands set (its A side is not read)
+  void mlp_fused(const SplitBuf& A, int M, const Lin& fc1, const Lin& fc2, int act, const GemmParams& out, int epi) {
+    ++mlp_sites;
+    if (!go()) return;
+    MlpFusedParams p; memset(&p, 0, sizeof(p));
+    p.X = A.hi; p.ldx = A.ld; p.W1 = fc1.hi; p.b1 = fc1.bias; p.W2 = fc2.hi; p.M = M; p.C = fc2.N; p.hidden = fc1.N; p.act = act;
+    p.part = ws; p.part_cap = ws_cap;
+    chk(launch_mlp_fused(p, out, epi, s), "mlp_fused");
   }
 
   // small / mid GEMM reading fp32 activations directly (gemm_small.hip): y = act((A + A2) W^T + b) (+ R)

@@ -6,6 +6,7 @@
 #include "../../include/ovm3d.h"
 #include "kernels.hpp"
 #include "det2d.hpp"
+#include "gdino.hpp"
 #include "tower.hpp"
 
 using namespace ovm;
@@ -57,7 +58,7 @@ struct Tmp {
 };
 }  // namespace
 
-namespace ovm { void set_use_gemm256(int v); void set_gdino_branches(int v); void msdeform_set_vec(int v); void set_gdino_dec_chain(int v); void set_gdino_gemm256(int v); void set_gdino_swin_fused(int v); void set_gdino_ffn_split(int v); void gemm256_set_n192(int v); void set_gemm256_ksplit(int v); }
+namespace ovm { void set_use_gemm256(int v); void set_gdino_branches(int v); void msdeform_set_vec(int v); void set_gdino_dec_chain(int v); void set_gdino_gemm256(int v); void set_gdino_swin_fused(int v); void set_gdino_ffn_split(int v); void set_gdino_mlp_fused(int v); void gemm256_set_n192(int v); void set_gemm256_ksplit(int v); }
 
 extern "C" {
 
@@ -227,6 +228,22 @@ int ovm_op_gemm_epi(const OvmGemmEpiOp* d, ovm_stream_t stream) {
       hipLaunchKernelGGL(join_kernel, grid1d(outs[i].n), dim3(256), 0, s, outs[i].hi, outs[i].lo, outs[i].n, outs[i].f);
   if (hipStreamSynchronize(s) != hipSuccess) return OVM_ERR_HIP;          // the scratch is freed on return
   return rc;
+}
+
+// The two launches of the fused MLP route (mlp_fused.hip) on the caller's own buffers (tests): nothing is converted or allocated.
+// X != null: the residual stream, updated in place (EPI_RESID, as a Swin block); else Y = sum + b2 (+ R) (EPI_STORE, as the encoder's FFN).
+int ovm_op_mlp_fused(const uint16_t* x_il, int32_t ldx, const uint16_t* w1_il, const float* b1, const uint16_t* w2_il, const float* b2,
+                     int32_t M, int32_t C, int32_t hidden, int32_t act, float* ws, int64_t ws_bytes, float* X, const float* R, float* Y,
+                     ovm_stream_t stream) {
+  if (!mlp_fused_supported(M, C, hidden, act, 3) || ws_bytes < 0 || (!X && !Y)) return OVM_ERR_INVALID;
+  MlpFusedParams p; memset(&p, 0, sizeof(p));
+  p.X = (const half_t*)x_il; p.ldx = ldx; p.W1 = (const half_t*)w1_il; p.b1 = b1; p.W2 = (const half_t*)w2_il;
+  p.M = M; p.C = C; p.hidden = hidden; p.act = act; p.part = ws; p.part_cap = (size_t)ws_bytes;
+  GemmParams q; memset(&q, 0, sizeof(q));
+  q.bias = b2;
+  if (X) { q.X = X; q.ldx = C; return launch_mlp_fused(p, q, EPI_RESID, (hipStream_t)stream); }
+  q.C = Y; q.ldc = C; q.R = R; q.ldr = C;
+  return launch_mlp_fused(p, q, EPI_STORE, (hipStream_t)stream);
 }
 
 // hi, lo [rows][K] (K % 32 == 0) -> out [rows][K/32][hi 32 | lo 32], the operand image of the split-mode GEMM
@@ -400,7 +417,8 @@ int ovm_tune_set(const char* key, int32_t value) {
 #endif
     attn_set_pp(value); return OVM_OK;
   }
-  // the four below are copied into a detector plan when it is built (GdinoTune, gdino_model.hpp): a plan keeps its values
+  // the five below are copied into a detector plan when it is built (GdinoTune, gdino_model.hpp): a plan keeps its values
+  if (!strcmp(key, "gdino_mlp_fused")) { ovm::set_gdino_mlp_fused(value); return OVM_OK; }   // plans built afterwards: 0 = fc1 and fc2 as two GEMMs, 1 = Swin blocks fused, 2 = and the encoder's FFN
   if (!strcmp(key, "gdino_ffn_split")) { ovm::set_gdino_ffn_split(value); return OVM_OK; }   // plans built afterwards: 0 = one workgroup per row block runs the whole FFN
   if (!strcmp(key, "gdino_swin_fused")) { ovm::set_gdino_swin_fused(value); return OVM_OK; }  // plans built afterwards: 0 = qkv GEMM + window attention as two launches
   if (!strcmp(key, "gdino_gemm256")) { ovm::set_gdino_gemm256(value); return OVM_OK; }       // plans built afterwards: 0 = planar rows, 128 x 128 tiles

@@ -106,5 +106,6 @@ class GdinoEngine:
         return int(self.L.ovm_gdino_debug_copy(self._h, b"launches", None, 0, self._stream()))
 
     def debug_scalar(self, name: str) -> int:
-        """"plans": plans held by the cache; "plan_bytes": device memory they hold together; "launches": kernels of the last forward."""
+        """"plans": plans held by the cache; "plan_bytes": device memory they hold together; "launches": kernels of the last forward;
+        "mlp_fused_sites": MLPs of the last plan's forward on the fused route (ovm_tune_set gdino_mlp_fused)."""
         return int(self.L.ovm_gdino_debug_copy(self._h, name.encode(), None, 0, self._stream()))

@@ -230,7 +230,7 @@ EXPORTS = [
     "ovm_create", "ovm_destroy", "ovm_last_error", "ovm_version", "ovm_abi_sizeof", "ovm_backbone_forward", "ovm_cube_forward",
     "ovm_rpn_box_forward", "ovm_gather_records", "ovm_gather_counts", "ovm_host_interp_pos_embed", "ovm_host_resize_pos_embed_aa", "ovm_host_sincos_pos_embed", "ovm_host_shard_range",
     "ovm_backbone_num_levels", "ovm_backbone_level",
-    "ovm_op_split_f16", "ovm_op_interleave", "ovm_op_gemm", "ovm_op_gemm_epi", "ovm_op_gemm_swiglu", "ovm_host_swiglu_perm", "ovm_op_layernorm", "ovm_op_attention", "ovm_op_roi_align",
+    "ovm_op_split_f16", "ovm_op_interleave", "ovm_op_gemm", "ovm_op_gemm_epi", "ovm_op_mlp_fused", "ovm_op_gemm_swiglu", "ovm_host_swiglu_perm", "ovm_op_layernorm", "ovm_op_attention", "ovm_op_roi_align",
     "ovm_op_roi_align_ex", "ovm_op_compact_records", "ovm_op_ln_rows", "ovm_op_ln_gelu_split", "ovm_op_patch_gather", "ovm_op_patch_gather_f32",
     "ovm_op_cls_init", "ovm_op_tokens_cast", "ovm_op_tokens_writeback", "ovm_op_maxpool2",
     "ovm_op_cube_decode", "ovm_op_nms", "ovm_op_rpn_proposals", "ovm_op_boxhead_post", "ovm_debug_copy", "ovm_set_corun", "ovm_profile_enable", "ovm_profile_read",
@@ -301,6 +301,7 @@ def load() -> C.CDLL:
     lib.ovm_op_interleave.argtypes = [vp, vp, i64, i32, vp, vp]
     lib.ovm_op_gemm.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, vp, i32, vp, i32, i32, vp]
     lib.ovm_op_gemm_epi.argtypes = [C.POINTER(OvmGemmEpiOp), vp]
+    lib.ovm_op_mlp_fused.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, i64, vp, vp, vp, vp]
     lib.ovm_op_gemm_swiglu.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, vp]
     lib.ovm_host_swiglu_perm.argtypes = [i32, vp]
     lib.ovm_op_layernorm.argtypes = [vp, i32, i32, vp, vp, f32, vp, vp]
