@@ -10,7 +10,8 @@ when no detection is kept. ``MODEL.AMD.VIS False`` writes the JSON only.
 
 2D boxes: the reference's demo always goes through ROIHeads3DGDINO (category_list is set, :84). Select it with
 ``MODEL.ROI_HEADS.NAME ROIHeads3DGDINO``: the native GroundingDINO network (``ovmono3d_amd/gdino``) is built from
-``MODEL.AMD.GDINO_WEIGHTS`` (+ ``MODEL.AMD.BERT_VOCAB``) on first use and raises if the checkpoint is missing. Alternatives:
+``MODEL.AMD.GDINO_WEIGHTS`` (+ ``MODEL.AMD.BERT_VOCAB``) on first use and raises if the checkpoint is missing; its architecture
+(groundingdino_swinb_cogcoor.pth: Swin-B, groundingdino_swint_ogc.pth: Swin-T) is read off the checkpoint's tensors. Alternatives:
 ``--boxes-file`` with oracle-2D boxes ({image name: [{bbox xywh, category_id, score}]}), or the default
 ``MODEL.ROI_HEADS.NAME ROIHeads3D`` = the RPN + box-head path.
 """

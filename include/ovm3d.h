@@ -394,7 +394,9 @@ typedef struct OvmGdinoConfig {
   int32_t n_levels, n_points, num_queries, max_text_len;          /* cfg:19-21,16,33: 4, 4, 900, 256 */
   float pe_temperature, eps;                                      /* cfg:4-6: 20; LayerNorm eps 1e-5 */
   int32_t bert_heads;                                             /* bert-base-uncased: 12 */
-  int32_t swin_embed, swin_depths[4], swin_heads[4], swin_window; /* swin_B_384_22k (cfg:3): 128, 2/2/18/2, 4/8/16/32, 12 */
+  int32_t swin_embed, swin_depths[4], swin_heads[4], swin_window; /* swin_B_384_22k (cfg:3): 128, 2/2/18/2, 4/8/16/32, 12;
+                                                                     swin_T_224_1k (GroundingDINO_SwinT_OGC.py, groundingdino_swint_ogc.pth):
+                                                                     96, 2/2/6/2, 3/6/12/24, 7. Head dimension 16, 32 or 64 */
   float pixel_mean[3], pixel_std[3];                              /* MODEL.PIXEL_MEAN / STD in tensor channel order */
   int32_t flip_channels;                                          /* 1: the reference's images[0][[2,1,0]] (roi_heads_gdino.py:146) */
   int32_t precision;                                              /* 1 = fp16 operands, 3 = split fp16 (default) */
@@ -536,6 +538,21 @@ typedef struct OvmRowOp {
   int32_t ldy, ldy2, ldh, il, ldh2, reserved0;
 } OvmRowOp;
 int ovm_g_rowop(const OvmRowOp* op, ovm_stream_t stream);
+/* swin_qkv_attn_kernel (ws = 12) / swin7_qkv_attn_kernel (ws = 7): a Swin block's qkv projection and window attention in one launch, head
+ * dimension 32, C = 32 nh channels. xhi / xlo: window-partitioned rows [nW * ws^2][ldx] as planar split fp16 (hi = fp16(x), lo = fp16(x -
+ * hi)), columns C .. 32 KS zero; wfrag: the [3 C][C] weight (q | k | v rows) packed by ovm_host_pack_weight (precision 3, Kpad = 32 KS),
+ * then re-ordered [tile of 16 rows][k-step of 32][hi | lo][lane 0..63][8 halves] with lane l = row l % 16, halves 8 (l / 16) .. of the
+ * k-step; bias fp32 [3 C]; relbias fp32 [nh][ws^2][ws^2]; mask fp32 [nW][ws^2][ws^2] or NULL. Output: ohi / olo [nW * ws^2][ldo], head h
+ * at columns 32 h ..: softmax_k(scale q.k + relbias + mask) v, as split fp16. Three-pass split-fp16 products for the projection, exact
+ * fp32 products for the attention. ws = 12 needs C % 128 == 0 and KS % 4 == 0; ws = 7 takes any C = 32 nh with KS >= C / 32 and wpg =
+ * windows per workgroup (1, 2 or 4; 0 = the default). ldx % 8 == 0, ldo % 4 == 0, 16-byte aligned x, wfrag and bias (ws = 12: relbias
+ * and mask too), 8-byte aligned ohi and olo. Any other geometry: OVM_ERR_SHAPE, nothing launched. */
+typedef struct OvmSwinQkvAttnOp {
+  const uint16_t* xhi; const uint16_t* xlo; const uint16_t* wfrag; const float* bias; const float* relbias; const float* mask;
+  uint16_t* ohi; uint16_t* olo;
+  int32_t ldx, KS, C, nh, nW, ldo; float scale; int32_t ws, wpg, reserved0;
+} OvmSwinQkvAttnOp;
+int ovm_g_swin_qkv_attn(const OvmSwinQkvAttnOp* op, ovm_stream_t stream);
 
 /* Process-global tuning knobs for experiments and tests (also settable as OVM_TUNE="key=value,..." when the host loads the
  * library). Defaults are the measured best; none changes results beyond fp32 summation order.
@@ -547,7 +564,10 @@ int ovm_g_rowop(const OvmRowOp* op, ovm_stream_t stream);
  *   kernel; default 0: measured slower), attn_pp 0|1 (two-wave-group attention kernel), msdeform_vec 0|1 (vectorised deformable sampling;
  *   default 1), gdino_dec_chain 0|1 (GroundingDINO decoder layers as row-chain kernels; default 1; read when a plan is built),
  *   gdino_ffn_split 0|1 (decoder row chains: the FFN's 512-column chunks on separate workgroups + a finishing kernel; bit-identical, faster for the detector alone, not beside the ViT; default 0; read when a plan is built),
- *   gdino_swin_fused 0|1 (Swin blocks: qkv projection inside the window-attention kernel; default 1; read when a plan is built),
+ *   gdino_swin_fused 0|1 (Swin blocks: qkv projection inside the window-attention kernel, windows of 12 x 12 and of 7 x 7; default 1; read
+ *   when a plan is built), gdino_swin_tap n (tests: plans built afterwards keep copies of their n-th Swin block's window rows and context
+ *   rows and offer them, with that block's qkv fragment image, bias, relative-position bias and shift mask, to ovm_gdino_debug_copy as
+ *   "swin_tap_xhi|xlo|ohi|olo|wfrag|bias|relbias|mask", counted in 4-byte elements; default 0),
  *   gdino_gemm256 0|1 (the detector's wide K <= 256 contractions on the 256 x 256 kernel; default 1; read when a plan is built),
  *   gdino_mlp_fused 0|1|2 (the image branch's two-layer MLPs as one kernel + the split-K reduce: 0 off, 1 the Swin blocks whose fc2 is
  *   split over K today, 2 those and the encoder's FFN where its slabs fit the workspace; default 1; read when a plan is built),

@@ -297,7 +297,8 @@ def get_cfg_defaults(cfg: CfgNode) -> CfgNode:
     # "f16x3" (hi/lo split, three passes, ~f32 accuracy).
     cfg.MODEL.AMD = CfgNode(dict(GEMM_PRECISION="f16x3", MAX_BATCH=1, MAX_ROIS=1000,
                                  # GroundingDINO branch of ROIHeads3DGDINO: checkpoint (the reference hard-codes this path,
-                                 # roi_heads_gdino.py:87-91; "synthetic://gdino?seed=N" = random init) and bert-base-uncased vocab.txt
+                                 # roi_heads_gdino.py:87-91; groundingdino_swint_ogc.pth works too - the architecture is read off the tensors;
+                                 # "synthetic://gdino?arch=swinb|swint&seed=N" = random init) and bert-base-uncased vocab.txt
                                  GDINO_WEIGHTS="./checkpoints/groundingdino_swinb_cogcoor.pth", BERT_VOCAB="",
                                  GDINO_OVERLAP=True, GDINO_GRAPHS=True,
                                  # co-run mode: throttle the ViT attention to one 4-wave workgroup per CU while the detector runs beside it

@@ -132,6 +132,7 @@ int ovm_abi_sizeof(const char* name) {
   if (n == "OvmAttnF32Op") return (int)sizeof(OvmAttnF32Op);
   if (n == "OvmMsDeformOp") return (int)sizeof(OvmMsDeformOp);
   if (n == "OvmRowOp") return (int)sizeof(OvmRowOp);
+  if (n == "OvmSwinQkvAttnOp") return (int)sizeof(OvmSwinQkvAttnOp);
   return -1;
 }
 

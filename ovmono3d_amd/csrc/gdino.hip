@@ -23,11 +23,12 @@ using namespace ovm;
 using namespace ovm::gdino;
 
 namespace ovm {
-GdinoTune g_gdino_tune = {1, 1, 0, 1, 1, 1};    // branches, dec_chain, ffn_split, swin_fused, gemm256, mlp_fused
+GdinoTune g_gdino_tune = {1, 1, 0, 1, 1, 1, 0}; // branches, dec_chain, ffn_split, swin_fused, gemm256, mlp_fused, swin_tap
 void set_gdino_branches(int v) { g_gdino_tune.branches = v ? 1 : 0; }       // engines created afterwards
 void set_gdino_dec_chain(int v) { g_gdino_tune.dec_chain = v ? 1 : 0; }     // this and the four below: plans built afterwards
 void set_gdino_ffn_split(int v) { g_gdino_tune.ffn_split = v ? 1 : 0; }
 void set_gdino_swin_fused(int v) { g_gdino_tune.swin_fused = v ? 1 : 0; }
+void set_gdino_swin_tap(int v) { g_gdino_tune.swin_tap = v > 0 ? v : 0; }
 void set_gdino_gemm256(int v) { g_gdino_tune.gemm256 = v ? 1 : 0; }
 void set_gdino_mlp_fused(int v) { g_gdino_tune.mlp_fused = v < 0 ? 0 : (v > 2 ? 2 : v); }
 }  // namespace ovm
@@ -112,10 +113,14 @@ void text_encoder(Run& r, State& st) {
 
 // =============================== image: Swin backbone ===============================
 // one block on the residual stream x [ntok][C]: (shifted) window attention, then the FFN
-void swin_block(Run& r, const SwinBlock& blk, const WinMaps& wmaps, float* x, int C, int nh, int ntok) {
+void swin_block(Run& r, const SwinBlock& blk, const WinMaps& wmaps, float* x, int C, int nh, int ntok, int ordinal) {
   const OvmGdinoConfig& c = r.g->cfg;
   const int ws = c.swin_window, ws2 = ws * ws, dh = C / nh, nW = wmaps.nW, M = nW * ws2, precision = r.g->precision;
   const float eps = c.eps;
+  // tests (ovm_tune_set gdino_swin_tap): copies of this block's window rows and context rows that outlive the block's scratch
+  half_t* snap[4] = {nullptr, nullptr, nullptr, nullptr};
+  const size_t snap_bytes = (size_t)M * ((C + 63) / 64 * 64) * sizeof(half_t);
+  if (r.pl->tune.swin_tap == ordinal && precision == 3) for (half_t*& q : snap) q = (half_t*)r.alloc(snap_bytes);
   const size_t mk = r.mark();
   // LN1 + pad + cyclic shift + window partition -> split fp16 rows (padding rows are zero AFTER the norm)
   SplitBuf xw = r.split((size_t)M, C);
@@ -126,12 +131,24 @@ void swin_block(Run& r, const SwinBlock& blk, const WinMaps& wmaps, float* x, in
   }
   SplitBuf ctx = r.split((size_t)M, C);
   if (r.pl->tune.swin_fused && blk.qkv.frag && dh == 32 && swin_qkv_attn_supported(C, nh, ws, precision) && xw.ld % 8 == 0) {
-    // qkv projection inside the window kernel (one workgroup per (window, head)): no [M][3 C] fp32 round trip, one launch less
+    // qkv projection inside the window kernel (one workgroup per (window, head); per (windows, head) at ws = 7): no [M][3 C] fp32 round
+    // trip, one launch less
     SwinQkvAttnParams a; memset(&a, 0, sizeof(a));
     a.xhi = xw.hi; a.xlo = xw.lo; a.ldx = xw.ld; a.wfrag = blk.qkv.frag; a.KS = blk.qkv.Kpad / 32; a.bias = blk.qkv.bias;
     a.C = C; a.nh = nh; a.nW = nW; a.relbias = blk.relbias; a.mask = wmaps.mask; a.ohi = ctx.hi; a.olo = ctx.lo; a.ldo = ctx.ld;
-    a.scale = 1.0f / sqrtf((float)dh);
+    a.scale = 1.0f / sqrtf((float)dh); a.ws = ws;
     if (r.go()) r.chk(launch_swin_qkv_attn(a, r.s_main), "swin_qkv_attn");
+    if (snap[0]) {
+      r.copy(snap[0], xw.hi, snap_bytes, r.s_main); r.copy(snap[1], xw.lo, snap_bytes, r.s_main);
+      r.copy(snap[2], ctx.hi, snap_bytes, r.s_main); r.copy(snap[3], ctx.lo, snap_bytes, r.s_main);
+      const int64_t nrow = (int64_t)(snap_bytes / 4);                     // debug copies count 4-byte elements
+      r.tap("swin_tap_xhi", snap[0], nrow); r.tap("swin_tap_xlo", snap[1], nrow);
+      r.tap("swin_tap_ohi", snap[2], nrow); r.tap("swin_tap_olo", snap[3], nrow);
+      r.tap("swin_tap_wfrag", blk.qkv.frag, (int64_t)npad128(blk.qkv.N) * 2 * blk.qkv.Kpad / 2);
+      r.tap("swin_tap_bias", blk.qkv.bias, 3 * C);
+      r.tap("swin_tap_relbias", blk.relbias, (int64_t)nh * ws2 * ws2);
+      if (wmaps.mask) r.tap("swin_tap_mask", wmaps.mask, (int64_t)nW * ws2 * ws2);
+    }
   } else {
     float* qkv = r.f32((size_t)M * 3 * C);
     { GemmParams q = r.gp(xw, M, blk.qkv); q.C = qkv; q.ldc = 3 * C; r.gemm(q, EPI_STORE); }
@@ -199,11 +216,12 @@ void swin_backbone(Run& r, State& st) {
     r.ln(y, h * w, C, g->pe_ln, eps, nullptr, x);
     r.release(mk);
   }
+  int ordinal = 0;                                          // Swin blocks so far, 1-based inside swin_block
   for (size_t si = 0; si < g->stages.size(); ++si) {
     const SwinStage& stg = g->stages[si];
     const StageGeo& ge = pl->geo[si];
     const int ntok = h * w;
-    for (size_t b = 0; b < stg.blocks.size(); ++b) swin_block(r, stg.blocks[b], ge.wm[b & 1], x, C, stg.nh, ntok);
+    for (size_t b = 0; b < stg.blocks.size(); ++b) swin_block(r, stg.blocks[b], ge.wm[b & 1], x, C, stg.nh, ntok, ++ordinal);
     if (stg.has_out) {
       float* f = r.f32((size_t)ntok * C);
       r.ln(x, ntok, C, stg.on, eps, nullptr, f);

@@ -42,19 +42,22 @@ struct AttnF32Params {
 };
 int launch_attn_f32(const AttnF32Params& p, hipStream_t s);
 
-// ---- Swin window attention with its qkv projection inside (round 3): one workgroup per (window, head), windows of 144 tokens, head
-// dimension 32. [q | k | v] of the head = x_window W_head^T + b over split-fp16 rows straight from HBM (three-pass MFMA, weights in
+// ---- Swin window attention with its qkv projection inside (round 3), head dimension 32. Windows of ws * ws = 144 tokens (Swin-B):
+// one workgroup per (window, head); windows of 49 tokens (Swin-T): one workgroup per (wpg consecutive windows, head). [q | k | v] of the head = x_window W_head^T + b over split-fp16 rows straight from HBM (three-pass MFMA, weights in
 // MFMA-fragment order) lands in LDS in the layouts attn_f32_kernel stages; then that kernel's score / softmax / value loop.
 struct SwinQkvAttnParams {
-  const half_t* xhi; const half_t* xlo; int ldx;   // window-partitioned LayerNorm rows [nW * 144][ldx] (planar split fp16)
-  const half_t* wfrag; int KS;                     // qkv weight image in fragment order (make_frag), KS = Kpad / 32 k-steps
+  const half_t* xhi; const half_t* xlo; int ldx;   // window-partitioned LayerNorm rows [nW * ws^2][ldx] (planar split fp16, columns C .. zero)
+  const half_t* wfrag; int KS;                     // qkv weight image in fragment order (make_frag), KS = Kpad / 32 k-steps >= C / 32
   const float* bias;                               // [3 C]
   int C, nh, nW;
-  const float* relbias;                            // [nh][144][144]
-  const float* mask;                               // [nW][144][144] or null
-  half_t* ohi; half_t* olo; int ldo;               // context rows [nW * 144][ldo] (planar split fp16), head h at columns 32 h ..
+  const float* relbias;                            // [nh][ws^2][ws^2]
+  const float* mask;                               // [nW][ws^2][ws^2] or null
+  half_t* ohi; half_t* olo; int ldo;               // context rows [nW * ws^2][ldo] (planar split fp16), head h at columns 32 h ..
   float scale;
+  int ws;                                          // window side: 12 (C % 128 == 0, KS % 4 == 0) or 7 (any C = 32 nh)
+  int wpg;                                         // ws = 7: windows per workgroup, 1 | 2 | 4; 0 = the default (kSwin7WindowsPerGroup)
 };
+constexpr int kSwin7WindowsPerGroup = 1;    // measured: profiles/gdino_swint/README.md
 bool swin_qkv_attn_supported(int C, int nh, int ws, int npass);
 int launch_swin_qkv_attn(const SwinQkvAttnParams& p, hipStream_t s);
 

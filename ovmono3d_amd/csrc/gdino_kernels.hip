@@ -437,6 +437,191 @@ __global__ __launch_bounds__(576) void swin_qkv_attn_kernel(const SwinQkvAttnPar
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
+// The same for windows of 7 x 7 = 49 tokens (Swin-T), head dimension 32. A window is 4 row tiles of 16 (rows 49 .. 63 do not exist:
+// loads are clamped to row 48, the LDS rows are written as zero, keys 49 .. 63 score -inf, queries 49 .. 63 are not stored). A
+// workgroup is 4 waves and takes NWIN consecutive windows of one head: wave rt owns row tile rt of each of them in both phases.
+// Phase 1: per k-step a wave loads 12 weight fragments (q | k | v x 2 column tiles x hi / lo, 1 KiB contiguous each) ONCE and uses
+// them for its NWIN row tiles (2 NWIN activation fragments straight from the split rows), 18 NWIN MFMAs; the next step's loads are
+// issued before this step's MFMAs. Same products in the same order as the 128-tile GEMM; only the C / 32 k-steps that hold
+// channels run (the rows' pad columns are zero). Phase 2: attn_f32_kernel's loop for one chunk of 64 keys.
+// LDS per window: Q [64][40], K [64][40], V^T [32][72] floats. The 8 columns a lane reads of a Q / K row (8 g .. 8 g + 7) are kept
+// as two 16-byte slots at floats 4 g and 16 + 4 g: with ds_read_b128's lane groups ({0-3, 12-15, 20-27}, ...) a row stride of 40
+// floats then puts the 16 lanes of a group on 16 different slots of the 256-byte bank row; contiguous 8 g is 2-way at every stride
+// (36 included). V^T rows: stride 72 for the same reason (68 is 2-way). Bias and mask rows are 49 floats (no 16-byte alignment): read
+// as scalars.
+// ------------------------------------------------------------------------------------------------------------------------------
+template <int NWIN>
+__global__ __launch_bounds__(256) void swin7_qkv_attn_kernel(const SwinQkvAttnParams p) {
+  constexpr int DH = 32, T = 49, TP = 64, LDK = 40, LDT = 72, ND = DH / 16, NKT = TP / 16, WSZ = 2 * TP * LDK + DH * LDT;
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  float* const lds = (float*)smem_raw;           // window j: Q at j WSZ, K behind it, V^T behind that
+  const int tid = threadIdx.x, lane = tid & 63, rt = tid >> 6;
+  const int fr = lane & 15, fq = lane >> 4;
+  const int grp = (int)blockIdx.x / p.nh, h = (int)blockIdx.x - grp * p.nh;
+  const int w0 = grp * NWIN;
+  // ---------------- phase 1: [q | k | v] = x W^T + b ----------------
+  {
+    const int nks = p.C >> 5;
+    const int row = rt * 16 + fr, rowc = row < T ? row : T - 1;
+    const half_t* xh[NWIN]; const half_t* xl[NWIN];
+#pragma unroll
+    for (int j = 0; j < NWIN; ++j) {
+      const int wj = (w0 + j < p.nW) ? w0 + j : p.nW - 1;      // past the last window: re-load it (never stored)
+      const size_t o = ((size_t)wj * T + rowc) * p.ldx + fq * 8;
+      xh[j] = p.xhi + o; xl[j] = p.xlo + o;
+    }
+    const size_t wt = (size_t)p.KS * 1024;                      // tile stride = KS * (hi 512 + lo 512) halves
+    const half_t* wp[3];
+#pragma unroll
+    for (int part = 0; part < 3; ++part) wp[part] = p.wfrag + (size_t)((part * p.C + h * DH) >> 4) * wt + lane * 8;
+    f32x4 acc[6][NWIN];
+#pragma unroll
+    for (int t = 0; t < 6; ++t)
+#pragma unroll
+      for (int j = 0; j < NWIN; ++j) acc[t][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    half8 xa[2][2 * NWIN], wa[2][12];
+    auto loadk = [&](int ks, half8* xd, half8* wd) {
+      const int k = (ks < nks) ? ks : nks - 1;                  // past the end: re-load the last step (never used)
+#pragma unroll
+      for (int j = 0; j < NWIN; ++j) {
+        xd[2 * j] = *(const half8*)(xh[j] + k * 32);
+        xd[2 * j + 1] = *(const half8*)(xl[j] + k * 32);
+      }
+#pragma unroll
+      for (int t = 0; t < 6; ++t) {
+        const half_t* q = wp[t >> 1] + (t & 1) * wt + (size_t)k * 1024;
+        wd[2 * t] = *(const half8*)q;
+        wd[2 * t + 1] = *(const half8*)(q + 512);
+      }
+    };
+    auto mfmak = [&](const half8* xd, const half8* wd) {
+#pragma unroll
+      for (int t = 0; t < 6; ++t)
+#pragma unroll
+        for (int j = 0; j < NWIN; ++j) {
+          acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wd[2 * t + 1], xd[2 * j], acc[t][j], 0, 0, 0);
+          acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wd[2 * t], xd[2 * j + 1], acc[t][j], 0, 0, 0);
+          acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wd[2 * t], xd[2 * j], acc[t][j], 0, 0, 0);
+        }
+    };
+    loadk(0, xa[0], wa[0]);
+    for (int ks = 0; ks < nks; ks += 2) {
+      loadk(ks + 1, xa[1], wa[1]); __builtin_amdgcn_sched_barrier(0);
+      mfmak(xa[0], wa[0]); __builtin_amdgcn_sched_barrier(0);
+      loadk(ks + 2, xa[0], wa[0]); __builtin_amdgcn_sched_barrier(0);
+      if (ks + 1 < nks) mfmak(xa[1], wa[1]);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    // lane (fr, fq) holds row fr of its row tile, columns 4 fq .. 4 fq + 3 of a column tile (dec_chain.hip's convention)
+    const bool live = row < T;
+#pragma unroll
+    for (int t = 0; t < 6; ++t) {
+      const int part = t >> 1, d0 = (t & 1) * 16 + fq * 4;
+      const int pc = ((d0 >> 2) & 1) * 16 + (d0 >> 3) * 4;       // slot of columns d0 .. d0 + 3 in a Q / K row
+      const f32x4 b = *(const f32x4*)(p.bias + part * p.C + h * DH + d0);
+#pragma unroll
+      for (int j = 0; j < NWIN; ++j) {
+        float* base = lds + j * WSZ;
+        f32x4 y = (f32x4){acc[t][j][0] + b[0], acc[t][j][1] + b[1], acc[t][j][2] + b[2], acc[t][j][3] + b[3]};
+        if (!live) y = (f32x4){0.f, 0.f, 0.f, 0.f};
+        if (part == 0) *(f32x4*)(base + row * LDK + pc) = y;
+        else if (part == 1) *(f32x4*)(base + TP * LDK + row * LDK + pc) = y;
+        else { float* vd = base + 2 * TP * LDK + d0 * LDT + row; vd[0] = y[0]; vd[LDT] = y[1]; vd[2 * LDT] = y[2]; vd[3 * LDT] = y[3]; }
+      }
+    }
+  }
+  __syncthreads();
+  // ---------------- phase 2: attn_f32_kernel<32>'s loop over one chunk of 64 keys, per window ----------------
+  const int li = lane & 15, g = lane >> 4;
+  const int qi = rt * 16 + li, qc = qi < T ? qi : T - 1;
+  const float kLog2e = 1.44269504088896340736f;
+  const float sc = p.scale * kLog2e;
+#pragma unroll 1
+  for (int j = 0; j < NWIN; ++j) {
+    const int w = w0 + j;
+    if (w >= p.nW) break;                                       // workgroup-uniform
+    const float* Qs = lds + j * WSZ;
+    const float* Ks = Qs + TP * LDK;
+    const float* Vt = Ks + TP * LDK;
+    float qf[8];
+    {
+      const f32x4 a = *(const f32x4*)(Qs + qi * LDK + g * 4), b = *(const f32x4*)(Qs + qi * LDK + 16 + g * 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { qf[e] = a[e] * sc; qf[4 + e] = b[e] * sc; }
+    }
+    const float* bh = p.relbias + ((size_t)h * T + qc) * T;
+    const float* bb = p.mask ? p.mask + ((size_t)w * T + qc) * T : nullptr;
+    f32x4 o[ND];
+#pragma unroll
+    for (int d = 0; d < ND; ++d) o[d] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    float m = -INFINITY, l = 0.f;
+    f32x4 st[NKT];
+    float cmax = -INFINITY;
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt) {
+      f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+      const float* kr = Ks + (kt * 16 + li) * LDK + g * 4;
+      const f32x4 k0 = *(const f32x4*)kr, k1 = *(const f32x4*)(kr + 16);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(k0[e], qf[e], acc, 0, 0, 0);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(k1[e], qf[4 + e], acc, 0, 0, 0);
+      const int key0 = kt * 16 + g * 4;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int key = key0 + r;
+        float x = acc[r];
+        if (key < T) {
+          x += bh[key] * kLog2e;
+          if (bb) x += bb[key] * kLog2e;
+        } else {
+          x = -INFINITY;
+        }
+        acc[r] = x;
+        cmax = fmaxf(cmax, x);
+      }
+      st[kt] = acc;
+    }
+    cmax = fmaxf(cmax, __shfl_xor(cmax, 16, 64));
+    cmax = fmaxf(cmax, __shfl_xor(cmax, 32, 64));
+    const float mnew = fmaxf(m, cmax);
+    const float msafe = (mnew == -INFINITY) ? 0.f : mnew;
+    const float alpha = exp2f(m - msafe);
+    l *= alpha;
+#pragma unroll
+    for (int d = 0; d < ND; ++d) { o[d][0] *= alpha; o[d][1] *= alpha; o[d][2] *= alpha; o[d][3] *= alpha; }
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt) {
+      f32x4 pr;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { pr[r] = exp2f(st[kt][r] - msafe); l += pr[r]; }
+#pragma unroll
+      for (int d = 0; d < ND; ++d) {
+        const f32x4 vv = *(const f32x4*)(Vt + (d * 16 + li) * LDT + kt * 16 + g * 4);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[d] = __builtin_amdgcn_mfma_f32_16x16x4f32(vv[r], pr[r], o[d], 0, 0, 0);
+      }
+    }
+    l += __shfl_xor(l, 16, 64);
+    l += __shfl_xor(l, 32, 64);
+    const float inv = (l > 0.f) ? 1.0f / l : 0.f;
+    if (qi < T) {
+#pragma unroll
+      for (int d = 0; d < ND; ++d) {
+        const f32x4 y = (f32x4){o[d][0] * inv, o[d][1] * inv, o[d][2] * inv, o[d][3] * inv};
+        const int col = d * 16 + g * 4;
+        half4 hh, lo4;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { half_t a, b; split_f16_nt(y[r], a, b); hh[r] = a; lo4[r] = b; }
+        const size_t oo = ((size_t)w * T + qi) * p.ldo + h * DH + col;
+        *(half4*)(p.ohi + oo) = hh;
+        *(half4*)(p.olo + oo) = lo4;
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
 // Fusion-layer bi-attention.
 // ------------------------------------------------------------------------------------------------------------------------------
 // image side: one wave per (image token, head); softmax over the text tokens; also leaves the raw scores for the text side.
@@ -1059,18 +1244,40 @@ int launch_rowop(const RowOpParams& p, hipStream_t s) {
 }
 
 bool swin_qkv_attn_supported(int C, int nh, int ws, int npass) {
-  return npass == 3 && ws == 12 && nh > 0 && C == nh * 32 && C % 128 == 0;
+  if (npass != 3 || nh <= 0 || C != nh * 32) return false;
+  return ws == 7 || (ws == 12 && C % 128 == 0);
 }
 
 int launch_swin_qkv_attn(const SwinQkvAttnParams& p, hipStream_t s) {
+  if (p.ws != 7 && p.ws != 12) return OVM_ERR_SHAPE;
   if (p.nW <= 0) return OVM_OK;
   auto al16 = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
-  if (p.C != p.nh * 32 || p.C % 128 || p.KS * 32 < p.C || p.KS % 4 || p.ldx % 8 || p.ldo % 4 || !p.xhi || !p.xlo || !p.wfrag || !p.bias || !p.relbias ||
-      !p.ohi || !p.olo || !al16(p.xhi) || !al16(p.xlo) || !al16(p.wfrag) || !al16(p.bias) || !al16(p.relbias) || (p.mask && !al16(p.mask)))
+  if (p.nh <= 0 || p.C != p.nh * 32 || p.KS * 32 < p.C || p.ldx < p.C || p.ldo < p.C || p.ldx % 8 || p.ldo % 4 || !p.xhi || !p.xlo || !p.wfrag ||
+      !p.bias || !p.relbias || !p.ohi || !p.olo || !al16(p.xhi) || !al16(p.xlo) || !al16(p.wfrag) || !al16(p.bias) ||
+      (((uintptr_t)p.ohi | (uintptr_t)p.olo) & 7))               // the context rows are stored 4 halves at a time
     return OVM_ERR_SHAPE;
-  if ((long)p.nW * p.nh > 0x7fffffffL) return OVM_ERR_CAPACITY;
-  const int smem = (2 * 144 * 36 + 32 * 148) * 4;
-  hipLaunchKernelGGL(swin_qkv_attn_kernel, dim3((unsigned)(p.nW * p.nh)), dim3(576), smem, s, p);
+  if (p.ws == 12) {
+    if (p.C % 128 || p.KS % 4 || !al16(p.relbias) || (p.mask && !al16(p.mask))) return OVM_ERR_SHAPE;
+    if ((long)p.nW * p.nh > 0x7fffffffL) return OVM_ERR_CAPACITY;
+    const int smem = (2 * 144 * 36 + 32 * 148) * 4;
+    hipLaunchKernelGGL(swin_qkv_attn_kernel, dim3((unsigned)(p.nW * p.nh)), dim3(576), smem, s, p);
+    return hipGetLastError() == hipSuccess ? OVM_OK : OVM_ERR_HIP;
+  }
+  // 49-token windows: wpg windows of one head per workgroup (0: the measured default, profiles/gdino_swint/README.md; the engine
+  // always passes 0, the other shapes are reached through the test entry point's descriptor)
+  const int wpg = p.wpg ? p.wpg : kSwin7WindowsPerGroup;
+  if (wpg != 1 && wpg != 2 && wpg != 4) return OVM_ERR_SHAPE;
+  if ((long)((p.nW + wpg - 1) / wpg) * p.nh > 0x7fffffffL) return OVM_ERR_CAPACITY;
+  const dim3 grid((unsigned)(((p.nW + wpg - 1) / wpg) * p.nh)), block(256);
+  const int smem = wpg * (2 * 64 * 40 + 32 * 72) * 4;
+  if (wpg == 1) hipLaunchKernelGGL(swin7_qkv_attn_kernel<1>, grid, block, smem, s, p);
+  else if (wpg == 2) hipLaunchKernelGGL(swin7_qkv_attn_kernel<2>, grid, block, smem, s, p);
+  else {
+    // 116 KiB: above the 64 KiB a kernel gets without asking (a function-local static is initialised once, also under threads)
+    static const hipError_t once = hipFuncSetAttribute((const void*)swin7_qkv_attn_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    if (once != hipSuccess) return OVM_ERR_HIP;
+    hipLaunchKernelGGL(swin7_qkv_attn_kernel<4>, grid, block, smem, s, p);
+  }
   return hipGetLastError() == hipSuccess ? OVM_OK : OVM_ERR_HIP;
 }
 

@@ -18,7 +18,7 @@
 
 namespace ovm {
 
-// ovm_tune_set's detector keys, process wide. `branches` is copied into a handle when it is created, the other five into a Plan when it
+// ovm_tune_set's detector keys, process wide. `branches` is copied into a handle when it is created, the others into a Plan when it
 // is built; the forward reads the plan's copy alone, so every pass over a plan (sizing, eager, capture, later eager calls) walks the
 // same allocation and launch sequence whatever is set in between.
 struct GdinoTune {
@@ -26,10 +26,12 @@ struct GdinoTune {
   int dec_chain;       // decoder layers as row-chain kernels (dec_chain.hip); 0: one launch per op, kept as the cross-check
   int ffn_split;       // decoder chain B over (row blocks) x (FFN chunks) + chain C. Bit-identical; 8.61 -> 8.34 ms for the detector ALONE,
                        // but 51.14 -> 50.97 images/s beside the ViT (four times the workgroups on the chip): off
-  int swin_fused;      // Swin blocks: qkv projection inside the window-attention kernel
+  int swin_fused;      // Swin blocks: qkv projection inside the window-attention kernel (windows of 12 x 12 and 7 x 7)
   int gemm256;         // the wide K <= 256 contractions on the 256 x 256 GEMM (interleaved activations)
   int mlp_fused;       // two-layer MLPs of the image branch in one kernel + the split-K reduce (mlp_fused.hip): 0 off, 1 Swin blocks,
                        // 2 Swin blocks and the encoder's FFN
+  int swin_tap;        // tests: n > 0 keeps copies of the n-th Swin block's window rows and context rows (fused route) for
+                       // ovm_gdino_debug_copy "swin_tap_*"; costs arena and four copies per forward, so 0 outside tests
 };
 extern GdinoTune g_gdino_tune;
 

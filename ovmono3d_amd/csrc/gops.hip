@@ -623,4 +623,13 @@ int ovm_g_rowop(const OvmRowOp* d, ovm_stream_t stream) {
   return launch_rowop(r, (hipStream_t)stream);
 }
 
+int ovm_g_swin_qkv_attn(const OvmSwinQkvAttnOp* d, ovm_stream_t stream) {
+  if (!d) return OVM_ERR_INVALID;
+  SwinQkvAttnParams a; memset(&a, 0, sizeof(a));
+  a.xhi = (const half_t*)d->xhi; a.xlo = (const half_t*)d->xlo; a.ldx = d->ldx; a.wfrag = (const half_t*)d->wfrag; a.KS = d->KS;
+  a.bias = d->bias; a.C = d->C; a.nh = d->nh; a.nW = d->nW; a.relbias = d->relbias; a.mask = d->mask;
+  a.ohi = (half_t*)d->ohi; a.olo = (half_t*)d->olo; a.ldo = d->ldo; a.scale = d->scale; a.ws = d->ws; a.wpg = d->wpg;
+  return launch_swin_qkv_attn(a, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -36,6 +36,16 @@ class HashTokenizer:
         return [101] + ids + [102] if add_special_tokens else ids
 
 
+def synthetic_spec(url: str):
+    """``synthetic://gdino?arch=swinb|swint&seed=N`` -> (architecture record, seed); ``arch`` absent: Swin-B, ``seed`` absent: 0."""
+    from urllib.parse import parse_qs, urlsplit
+    q = parse_qs(urlsplit(url).query)
+    arch = q.get("arch", ["swinb"])[0].lower()
+    if arch not in ("swinb", "swint"):
+        raise ValueError(f"{url!r}: arch must be swinb or swint")
+    return (GDinoConfig.swin_t() if arch == "swint" else GDinoConfig()), int(q.get("seed", ["0"])[0])
+
+
 def convert_upstream_state_dict(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     """IDEA-Research/GroundingDINO checkpoint names -> the Hugging Face port's names the engine consumes.
     Written from the published module structures; it could not be checked against a real checkpoint offline."""
@@ -138,10 +148,12 @@ class NativeGroundingDino:
     cross-check of the engine; it is test infrastructure and not importable from the package.)"""
 
     def __init__(self, device: torch.device, state_dict: Dict[str, torch.Tensor], tokenizer, pixel_mean, pixel_std,
-                 cfg: GDinoConfig = GDinoConfig(), precision: int = 3, use_graphs: bool = True, max_plans: int = 0,
+                 cfg: Optional[GDinoConfig] = None, precision: int = 3, use_graphs: bool = True, max_plans: int = 0,
                  plan_budget_mb: int = 0):
         if "model.text_projection.weight" not in state_dict:
             state_dict = convert_upstream_state_dict(state_dict)
+        if cfg is None:                                  # the checkpoint decides: Swin-B, Swin-T, ...
+            cfg = GDinoConfig.from_state_dict(state_dict)
         self.tok, self.mean, self.std = tokenizer, list(pixel_mean), list(pixel_std)
         self.use_graphs = use_graphs
         self._tok_cache: Dict[str, tuple] = {}

@@ -17,11 +17,13 @@ from .config import GDinoConfig
 
 
 class GdinoEngine:
-    def __init__(self, device: torch.device, state_dict: Dict[str, torch.Tensor], cfg: GDinoConfig = GDinoConfig(),
+    def __init__(self, device: torch.device, state_dict: Dict[str, torch.Tensor], cfg: Optional[GDinoConfig] = None,
                  pixel_mean: Sequence[float] = (0.0, 0.0, 0.0), pixel_std: Sequence[float] = (1.0, 1.0, 1.0), flip_channels: bool = True,
                  precision: int = 3, use_graphs: bool = True, max_plans: int = 0, plan_budget_mb: int = 0):
         if device.type != "cuda":
             raise RuntimeError("the GroundingDINO engine runs on the HIP device only (no CPU fallback)")
+        if cfg is None:
+            cfg = GDinoConfig.from_state_dict(state_dict)
         self.dev, self.cfg, self.L = device, cfg, _lib.load()
         c = _lib.OvmGdinoConfig()
         c.d_model, c.enc_layers, c.dec_layers, c.heads, c.ffn_dim = cfg.d_model, cfg.enc_layers, cfg.dec_layers, cfg.heads, cfg.ffn_dim

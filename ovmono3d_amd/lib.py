@@ -226,6 +226,16 @@ class OvmRowOp(C.Structure):
     ]
 
 
+class OvmSwinQkvAttnOp(C.Structure):
+    """Mirror of include/ovm3d.h OvmSwinQkvAttnOp (ovm_g_swin_qkv_attn: the Swin qkv + window-attention kernels in isolation, for tests)."""
+    _fields_ = [
+        ("xhi", C.c_void_p), ("xlo", C.c_void_p), ("wfrag", C.c_void_p), ("bias", C.c_void_p), ("relbias", C.c_void_p), ("mask", C.c_void_p),
+        ("ohi", C.c_void_p), ("olo", C.c_void_p),
+        ("ldx", C.c_int32), ("KS", C.c_int32), ("C", C.c_int32), ("nh", C.c_int32), ("nW", C.c_int32), ("ldo", C.c_int32),
+        ("scale", C.c_float), ("ws", C.c_int32), ("wpg", C.c_int32), ("reserved0", C.c_int32),
+    ]
+
+
 EXPORTS = [
     "ovm_create", "ovm_destroy", "ovm_last_error", "ovm_version", "ovm_abi_sizeof", "ovm_backbone_forward", "ovm_cube_forward",
     "ovm_rpn_box_forward", "ovm_gather_records", "ovm_gather_counts", "ovm_host_interp_pos_embed", "ovm_host_resize_pos_embed_aa", "ovm_host_sincos_pos_embed", "ovm_host_shard_range",
@@ -237,7 +247,7 @@ EXPORTS = [
     "ovm_comm_unique_id", "ovm_comm_init", "ovm_comm_destroy", "ovm_tune_set", "ovm_gdino_postprocess", "ovm_box3d_iou", "ovm_eval_iou2d", "ovm_eval_match", "ovm_eval_iou3d", "ovm_eval_nhd", "ovm_host_pil_bilinear_coeffs", "ovm_resize_bilinear_u8", "ovm_resize_bilinear_f32",
     "ovm_g_pack_weight", "ovm_host_pack_weight", "ovm_g_linear", "ovm_g_layernorm", "ovm_g_bmm", "ovm_g_bmm2", "ovm_g_softmax", "ovm_g_softmax2", "ovm_g_eltwise", "ovm_g_gather_rows",
     "ovm_g_groupnorm", "ovm_g_biattn", "ovm_g_msdeform", "ovm_g_sine_embed", "ovm_g_normalize_image", "ovm_g_topk", "ovm_g_rowmax",
-    "ovm_g_attn_f32", "ovm_g_msdeform_fused", "ovm_g_rowop",
+    "ovm_g_attn_f32", "ovm_g_msdeform_fused", "ovm_g_rowop", "ovm_g_swin_qkv_attn",
     "ovm_gdino_create", "ovm_gdino_destroy", "ovm_gdino_last_error", "ovm_gdino_forward", "ovm_gdino_detect", "ovm_gdino_set_force_topk",
     "ovm_gdino_debug_copy", "ovm_debug_set_ptr", "ovm_gdino_num_queries", "ovm_gdino_last_outputs", "ovm_infer",
     "ovm_host_jpeg_info", "ovm_host_jpeg_entropy_decode", "ovm_jpeg_reconstruct",
@@ -276,7 +286,8 @@ def load() -> C.CDLL:
                          ("OvmSceneSegment", OvmSceneSegment), ("OvmEvalCell", OvmEvalCell), ("OvmGeoParams", OvmGeoParams),
                          ("OvmGeoInstance", OvmGeoInstance), ("OvmGeoResult", OvmGeoResult), ("OvmGeoBox", OvmGeoBox),
                          ("OvmSamConfig", OvmSamConfig), ("OvmDepthProConfig", OvmDepthProConfig), ("OvmGemmEpiOp", OvmGemmEpiOp),
-                         ("OvmAttnF32Op", OvmAttnF32Op), ("OvmMsDeformOp", OvmMsDeformOp), ("OvmRowOp", OvmRowOp)):
+                         ("OvmAttnF32Op", OvmAttnF32Op), ("OvmMsDeformOp", OvmMsDeformOp), ("OvmRowOp", OvmRowOp),
+                         ("OvmSwinQkvAttnOp", OvmSwinQkvAttnOp)):
         if lib.ovm_abi_sizeof(name.encode()) != C.sizeof(mirror):
             raise RuntimeError(f"{LIB_PATH}: sizeof({name}) = {lib.ovm_abi_sizeof(name.encode())} but the ctypes mirror has "
                                f"{C.sizeof(mirror)} bytes - rebuild the library (ovmono3d_amd/csrc/build.sh) or update lib.py")
@@ -388,6 +399,7 @@ def load() -> C.CDLL:
     lib.ovm_g_attn_f32.argtypes = [C.POINTER(OvmAttnF32Op), vp]
     lib.ovm_g_msdeform_fused.argtypes = [C.POINTER(OvmMsDeformOp), vp]
     lib.ovm_g_rowop.argtypes = [C.POINTER(OvmRowOp), vp]
+    lib.ovm_g_swin_qkv_attn.argtypes = [C.POINTER(OvmSwinQkvAttnOp), vp]
     lib.ovm_gdino_postprocess.argtypes = [vp, i32, i32, vp, C.POINTER(i32), i32, i32, i32, f32, f32, vp, vp, vp, vp, vp]
     lib.ovm_gdino_create.argtypes = [C.POINTER(OvmGdinoConfig), C.POINTER(OvmTensor), i32, i32, C.POINTER(vp)]
     lib.ovm_gdino_destroy.argtypes = [vp]

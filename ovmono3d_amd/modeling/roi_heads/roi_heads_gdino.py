@@ -9,8 +9,8 @@ GroundingDINO outputs ``{"pred_logits": [nq,256], "pred_boxes": [nq,4] cxcywh, "
 "phrase_ids": per-category token ids}`` - the reference-owned glue (caption building :176-181, phrase-logit
 reduction :273-294, threshold :197, cxcywh->xyxy :266-270, NMS :254, class index :162) then runs natively
 (``gdino_glue`` + ``ovm_gdino_postprocess``) - OR already post-processed ``{"bboxes", "scores", "labels"}``.
-By default the detector is the native GroundingDINO network (``ovmono3d_amd.gdino``: Swin-B + BERT + deformable
-transformer on libovm3d ops), built on first use from ``MODEL.AMD.GDINO_WEIGHTS``; if neither a checkpoint nor a detector
+By default the detector is the native GroundingDINO network (``ovmono3d_amd.gdino``: Swin-B or Swin-T + BERT + deformable
+transformer on libovm3d ops, the architecture read off the checkpoint), built on first use from ``MODEL.AMD.GDINO_WEIGHTS``; if neither a checkpoint nor a detector
 is available ``forward`` raises instead of silently falling back.
 """
 from __future__ import annotations
@@ -38,14 +38,14 @@ class ROIHeads3DGDINO(ROIHeads3D):
         first use so that a model without the checkpoint can still serve the oracle-2D / RPN paths."""
         import os
         from ...checkpoint import load_state_dict_file
-        from ...gdino.detector import HashTokenizer, NativeGroundingDino
+        from ...gdino.detector import HashTokenizer, NativeGroundingDino, synthetic_spec
         from .gdino_glue import WordPieceTokenizer
         cfg = self._gdino_cfg
         path = cfg.MODEL.AMD.GDINO_WEIGHTS
         if path.startswith("synthetic://"):
             from ...util.synth_gdino_weights import synth_gdino_state_dict
-            seed = int(path.split("seed=")[1]) if "seed=" in path else 0
-            sd, tok = synth_gdino_state_dict(seed), HashTokenizer()
+            arch, seed = synthetic_spec(path)
+            sd, tok = synth_gdino_state_dict(seed, arch), HashTokenizer()
         else:
             if not os.path.isfile(path):
                 raise NotImplementedError(
