@@ -150,7 +150,7 @@ int ovm_destroy(OvmHandle* h);
 const char* ovm_last_error(const OvmHandle* h);
 const char* ovm_version(void);
 /* sizeof() of a struct of this header as the library was compiled ("OvmConfig", "OvmTensor", "OvmImage", "OvmDet3D",
- * "OvmGdinoConfig", "OvmJpegInfo", "OvmSceneInput", "OvmSceneLayout", "OvmSceneSegment", "OvmEvalCell", "OvmSamConfig", "OvmDepthProConfig"), -1 for an unknown name: lets a binding check its mirror of the layout before the first call. */
+ * "OvmGdinoConfig", "OvmJpegInfo", "OvmSceneInput", "OvmSceneLayout", "OvmSceneSegment", "OvmPanelBox", "OvmPanelsInput", "OvmPanelPrim", "OvmPanelsLayout", "OvmEvalCell", "OvmSamConfig", "OvmDepthProConfig"), -1 for an unknown name: lets a binding check its mirror of the layout before the first call. */
 int ovm_abi_sizeof(const char* struct_name);
 
 /* --- backbone: build_dino_backbone(...).forward(x, prompt_depth) -> {p2,p3,p4}
@@ -772,6 +772,83 @@ int ovm_render_scene_workspace(const OvmSceneLayout* layout, int64_t glyph_bytes
 int ovm_render_scene(const OvmSceneLayout* layout, const OvmSceneSegment* grid, const uint8_t* glyphs, int64_t glyph_bytes,
                      const uint8_t* image, int64_t image_pitch, uint8_t* front, int64_t front_pitch, uint8_t* novel, int64_t novel_pitch,
                      void* workspace, int64_t workspace_bytes, ovm_stream_t stream);
+
+/* ---- Visualisation: evaluation sample panels -------------------------------------------------------------------------------
+ * visualize_from_instances of the reference (cubercnn/vis/vis.py:76-296): per sampled image a 2H x 3W mosaic of six copies of
+ * the image - columns: ground truth of all classes, ground truth of the evaluated classes, predictions; top row the 2D boxes,
+ * bottom row the 3D boxes (draw_3d_box_from_verts :695-728, draw_text :755-783). The rules are pinned by the numpy restatement
+ * tests/panels_oracle.py; parity with cv2 is unpinned (cv2 is not available to compare).
+ *
+ * ovm_host_panels_layout (host, fp64, no GPU) turns the boxes into the ordered primitive list of each panel; ovm_render_panels
+ * (device, one stream-ordered call) applies each panel's list, strictly in order, to a copy of the image and writes the mosaic.
+ * Primitives, in the reference's drawing order (a later primitive overwrites an earlier one):
+ *  - 2D panels, per box: the outline (int() of x, y, x + w, y + h) as four segments of thickness 2 - top, right, bottom, left -
+ *    in the class colour, then the class name's glyphs in the class colour, the mask's bottom-left at (int(x), int(y) - 10);
+ *  - 3D panels, per box with draw3d: the cuboid's corners (get_cuboid_verts_faces order) are R @ (+-l/2, +-h/2, +-w/2) +
+ *    center; its 12 edges in the order 0-1 1-2 2-3 3-0 1-5 5-6 6-2 4-5 4-7 6-7 0-4 3-7, each dropped when both ends lie behind
+ *    zplane = 0.05 and else cut at it (eps 1e-4) and projected, int() of the endpoints; then the label: the background
+ *    rectangle of draw_text at int() of the 2D box's x, y, clipped to the image, blended px * 0.33 + bg * (1 - 0.33) in fp64
+ *    (two products, one sum, truncated), then the glyphs in black or white by the mean of bg (> 127.5: black);
+ *  - the middle column holds only the ground-truth boxes with in_eval set.
+ * Declared deviations from the reference (the first four are the scene view's, above):
+ *  - thick lines: a pixel is covered when its integer centre lies within thickness / 2 of the segment;
+ *  - glyphs are a coverage mask made by the caller (Pillow's built-in font); putText's stroke thickness is ignored; the text size
+ *    of the label rectangle is the mask's size, and a box with an empty 0 x 0 mask gets no glyphs and no label rectangle;
+ *  - colours come from the caller (a deterministic colour per category_id);
+ *  - host geometry is fp64 (the reference's get_cuboid_verts is fp32);
+ *  - the 3D line thickness is max(1, int(round_half_even(3 * H / 500))): cv2 refuses thickness 0, which the reference's formula
+ *    gives below H = 84. */
+#define OVM_PANELS 6              /* 0 gt_all_2d, 1 gt_2d, 2 pred_2d, 3 gt_all_3d, 4 gt_3d, 5 pred_3d: row-major in the mosaic */
+#define OVM_PANEL_SEGMENT 0
+#define OVM_PANEL_BLEND 1
+#define OVM_PANEL_GLYPH 2
+
+typedef struct OvmPanelBox {
+  double bbox[4];                 /* x, y, w, h */
+  double center[3], dims[3];      /* camera-space centre; w, h, l */
+  double R[9];                    /* row-major pose */
+  uint8_t color[4];               /* class colour; component k lands in image channel k ([3] unused) */
+  int32_t draw3d;                 /* the cuboid and its label are drawn (a prediction: score > threshold) */
+  int32_t in_eval;                /* ground truth: also drawn in the middle column (ignored for predictions) */
+  int32_t glyph2d[2], glyph3d[2]; /* (width, height) of the name's mask at scale 0.5, and at scale 0.5 * H / 500 */
+} OvmPanelBox;
+
+typedef struct OvmPanelsInput {
+  int32_t height, width, n_gt, n_pred;
+  double K[9];
+  const OvmPanelBox* gt;          /* [n_gt] */
+  const OvmPanelBox* pred;        /* [n_pred] */
+} OvmPanelsInput;
+
+typedef struct OvmPanelPrim {
+  int32_t kind, thickness;        /* OVM_PANEL_*; thickness of a segment */
+  int64_t a[4];                   /* segment: x0, y0, x1, y1; blend: half-open x0, y0, x1, y1; glyph: top-left x, y, then w, h */
+  int64_t glyph_offset;           /* glyph: byte offset of its h x w mask in the glyph buffer */
+  uint8_t color[4];               /* segment and glyph colour, blend background ([3] unused) */
+  int32_t box;                    /* source: index into gt (panels 0, 1, 3, 4) or pred (panels 2, 5) */
+} OvmPanelPrim;
+
+typedef struct OvmPanelsLayout {
+  int32_t height, width, thickness3d, n_prims;   /* n_prims: the count needed, also on OVM_ERR_CAPACITY */
+  int32_t start[OVM_PANELS + 1];                 /* panel p owns prims[start[p] .. start[p + 1]) */
+  int32_t reserved;
+  int64_t glyph_bytes;                           /* size of the glyph buffer the offsets index */
+} OvmPanelsLayout;
+
+/* Glyph buffer order: per ground-truth box its 2D mask then its 3D mask, then the same per prediction, each h x w bytes
+ * row-major, nonzero = ink. Fills *out and prims[0 .. out->n_prims). OVM_ERR_CAPACITY, with out->n_prims set to the count
+ * needed, when prim_capacity is too small; OVM_ERR_INVALID for null, non-finite or out-of-range arguments. */
+int ovm_host_panels_layout(const OvmPanelsInput* in, OvmPanelsLayout* out, OvmPanelPrim* prims, int32_t prim_capacity);
+/* Device workspace bytes ovm_render_panels needs for this layout. */
+int ovm_render_panels_workspace(const OvmPanelsLayout* layout, int64_t* bytes);
+/* layout, prims, glyphs: host. image: device BGR uint8 [height][width][3], row pitch in bytes; mosaic: device
+ * [2 * height][3 * width][3], row pitch in bytes, must not overlap image. One pinned upload, one kernel, stream-ordered, no
+ * allocation once the pinned buffer has grown to size. Too small a workspace -> OVM_ERR_CAPACITY; null, inconsistent or
+ * out-of-range arguments (a glyph whose mask leaves the buffer, a start[] that is not ascending) -> OVM_ERR_INVALID, both before
+ * any device work. */
+int ovm_render_panels(const OvmPanelsLayout* layout, const OvmPanelPrim* prims, const uint8_t* glyphs, int64_t glyph_bytes,
+                      const uint8_t* image, int64_t image_pitch, uint8_t* mosaic, int64_t mosaic_pitch, void* workspace,
+                      int64_t workspace_bytes, ovm_stream_t stream);
 
 /* ---- OVMono3D-GEO -----------------------------------------------------------------------------------------------------------
  * The training-free baseline of the reference (tools/ovmono3d_geo.py:127-258): a 2D box's mask pixels are un-projected with a

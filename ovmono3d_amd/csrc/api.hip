@@ -121,6 +121,10 @@ int ovm_abi_sizeof(const char* name) {
   if (n == "OvmSceneInput") return (int)sizeof(OvmSceneInput);
   if (n == "OvmSceneLayout") return (int)sizeof(OvmSceneLayout);
   if (n == "OvmSceneSegment") return (int)sizeof(OvmSceneSegment);
+  if (n == "OvmPanelBox") return (int)sizeof(OvmPanelBox);
+  if (n == "OvmPanelsInput") return (int)sizeof(OvmPanelsInput);
+  if (n == "OvmPanelPrim") return (int)sizeof(OvmPanelPrim);
+  if (n == "OvmPanelsLayout") return (int)sizeof(OvmPanelsLayout);
   if (n == "OvmEvalCell") return (int)sizeof(OvmEvalCell);
   if (n == "OvmGeoParams") return (int)sizeof(OvmGeoParams);
   if (n == "OvmGeoInstance") return (int)sizeof(OvmGeoInstance);

@@ -25,10 +25,17 @@
 #include <vector>
 
 #include "../../include/ovm3d.h"
+#include "draw.hpp"
 
 #pragma clang fp contract(off)
 
 namespace {
+
+using ovm_draw::clampd;
+using ovm_draw::iround;
+using ovm_draw::project;
+using ovm_draw::seg_dist2;
+using ovm_draw::to_i64;
 
 // Each face of the cuboid as its four corners in the reference's (inward) winding, the first-to-third corner being the split
 // diagonal (get_cuboid_verts_faces, math_util.py:190-209): front 0-2, right 1-6, left 4-3, back 5-7, top 4-1, bottom 3-6.
@@ -191,16 +198,6 @@ __device__ inline bool overlaps(int bx0, int by0, int bx1, int by1, int tx0, int
   return bx0 <= bx1 && by0 <= by1 && bx0 < tx0 + kTile && bx1 >= tx0 && by0 < ty0 + kTile && by1 >= ty0;
 }
 
-__device__ inline double seg_dist2(double px, double py, double x0, double y0, double x1, double y1) {
-  const double dx = x1 - x0, dy = y1 - y0;
-  const double ex = px - x0, ey = py - y0;
-  const double ll = dx * dx + dy * dy;
-  double t = ll > 0.0 ? (ex * dx + ey * dy) / ll : 0.0;
-  t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
-  const double fx = ex - t * dx, fy = ey - t * dy;
-  return fx * fx + fy * fy;
-}
-
 __device__ inline float3 nrm(float x, float y, float z) {
   const float l = sqrtf(x * x + y * y + z * z);
   const float inv = 1.0f / (l > 1e-6f ? l : 1e-6f);
@@ -347,16 +344,6 @@ __global__ void __launch_bounds__(kThreads) scene_tiles(SceneArgs A) {
 
 // -------------------------------------------------------------------------------------------------------------------- host
 
-inline double clampd(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
-inline int64_t to_i64(double v) { return (int64_t)clampd(v, -1e15, 1e15); }   // int() of a finite projection
-inline int iround(double v) { return (int)std::nearbyint(v); }                  // np.round: half to even
-
-// K @ v / z, summed left to right as the numpy restatement does
-inline void project(const double* K, const double* v, double div, double* u) {
-  u[0] = (K[0] * v[0] + K[1] * v[1] + K[2] * v[2]) / div;
-  u[1] = (K[3] * v[0] + K[4] * v[1] + K[5] * v[2]) / div;
-}
-
 inline void rotate(const double* R, const double* c, const double* p, double* r) {
   const double d0 = p[0] - c[0], d1 = p[1] - c[1], d2 = p[2] - c[2];
   r[0] = R[0] * d0 + R[1] * d1 + R[2] * d2;
@@ -467,29 +454,12 @@ Packing plan(const OvmSceneLayout* L, int64_t glyph_bytes) {
   return p;
 }
 
-// Segment clipped (Liang-Barsky, fp64) to [-r, W - 1 + r] x [-r, H - 1 + r]: no pixel of the canvas within r of the segment
-// is lost. Returns false when nothing is left.
+// ovm_draw::clip_segment into an edge item: no pixel of the canvas within r of the segment is lost. False when nothing is left.
 bool clip_segment(double x0, double y0, double x1, double y1, double r, int W, int H, DItem* it) {
-  const double dx = x1 - x0, dy = y1 - y0;
-  const double pk[4] = {-dx, dx, -dy, dy};
-  const double qk[4] = {x0 - (-r), (W - 1 + r) - x0, y0 - (-r), (H - 1 + r) - y0};
-  double t0 = 0.0, t1 = 1.0;
-  for (int k = 0; k < 4; ++k) {
-    if (pk[k] == 0.0) {
-      if (qk[k] < 0.0) return false;
-    } else {
-      const double t = qk[k] / pk[k];
-      if (pk[k] < 0.0) t0 = t > t0 ? t : t0;
-      else t1 = t < t1 ? t : t1;
-    }
-  }
-  if (t0 > t1) return false;
-  it->a[0] = x0 + t0 * dx; it->a[1] = y0 + t0 * dy; it->a[2] = x0 + t1 * dx; it->a[3] = y0 + t1 * dy;
+  int32_t bb[4];
+  if (!ovm_draw::clip_segment(x0, y0, x1, y1, r, W, H, it->a, bb)) return false;
   it->r2 = r * r;
-  const double bx0 = std::floor(std::fmin(it->a[0], it->a[2]) - r), bx1 = std::ceil(std::fmax(it->a[0], it->a[2]) + r);
-  const double by0 = std::floor(std::fmin(it->a[1], it->a[3]) - r), by1 = std::ceil(std::fmax(it->a[1], it->a[3]) + r);
-  it->bx0 = (int)clampd(bx0, 0, W - 1); it->bx1 = (int)clampd(bx1, 0, W - 1);
-  it->by0 = (int)clampd(by0, 0, H - 1); it->by1 = (int)clampd(by1, 0, H - 1);
+  it->bx0 = bb[0]; it->by0 = bb[1]; it->bx1 = bb[2]; it->by1 = bb[3];
   it->kind = 0;
   return true;
 }

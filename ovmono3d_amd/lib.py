@@ -114,6 +114,41 @@ class OvmSceneSegment(C.Structure):
     _fields_ = [("x0", C.c_int64), ("y0", C.c_int64), ("x1", C.c_int64), ("y1", C.c_int64)]
 
 
+OVM_PANELS = 6
+OVM_PANEL_SEGMENT, OVM_PANEL_BLEND, OVM_PANEL_GLYPH = 0, 1, 2
+
+
+class OvmPanelBox(C.Structure):
+    """Mirror of include/ovm3d.h OvmPanelBox."""
+    _fields_ = [
+        ("bbox", C.c_double * 4), ("center", C.c_double * 3), ("dims", C.c_double * 3), ("R", C.c_double * 9),
+        ("color", C.c_uint8 * 4), ("draw3d", C.c_int32), ("in_eval", C.c_int32),
+        ("glyph2d", C.c_int32 * 2), ("glyph3d", C.c_int32 * 2),
+    ]
+
+
+class OvmPanelsInput(C.Structure):
+    _fields_ = [
+        ("height", C.c_int32), ("width", C.c_int32), ("n_gt", C.c_int32), ("n_pred", C.c_int32),
+        ("K", C.c_double * 9), ("gt", C.c_void_p), ("pred", C.c_void_p),
+    ]
+
+
+class OvmPanelPrim(C.Structure):
+    _fields_ = [
+        ("kind", C.c_int32), ("thickness", C.c_int32), ("a", C.c_int64 * 4), ("glyph_offset", C.c_int64),
+        ("color", C.c_uint8 * 4), ("box", C.c_int32),
+    ]
+
+
+class OvmPanelsLayout(C.Structure):
+    """Mirror of include/ovm3d.h OvmPanelsLayout."""
+    _fields_ = [
+        ("height", C.c_int32), ("width", C.c_int32), ("thickness3d", C.c_int32), ("n_prims", C.c_int32),
+        ("start", C.c_int32 * (OVM_PANELS + 1)), ("reserved", C.c_int32), ("glyph_bytes", C.c_int64),
+    ]
+
+
 # include/ovm3d.h OVM_NHD_*: the per-detection status ovm_eval_nhd writes
 OVM_NHD_NONE, OVM_NHD_OK, OVM_NHD_SKIPPED = 0, 1, 2
 
@@ -252,6 +287,7 @@ EXPORTS = [
     "ovm_gdino_debug_copy", "ovm_debug_set_ptr", "ovm_gdino_num_queries", "ovm_gdino_last_outputs", "ovm_infer",
     "ovm_host_jpeg_info", "ovm_host_jpeg_entropy_decode", "ovm_jpeg_reconstruct",
     "ovm_host_scene_layout", "ovm_render_scene_workspace", "ovm_render_scene",
+    "ovm_host_panels_layout", "ovm_render_panels_workspace", "ovm_render_panels",
     "ovm_geo_default_params", "ovm_geo_last_error", "ovm_geo_lift_workspace", "ovm_geo_lift", "ovm_geo_dbscan_workspace", "ovm_geo_dbscan",
     "ovm_host_geo_box",
     "ovm_sam_create", "ovm_sam_destroy", "ovm_sam_last_error", "ovm_sam_set_image", "ovm_sam_predict_boxes_workspace", "ovm_sam_predict_boxes",
@@ -283,7 +319,8 @@ def load() -> C.CDLL:
     lib.ovm_abi_sizeof.argtypes = [C.c_char_p]
     for name, mirror in (("OvmConfig", OvmConfig), ("OvmTensor", OvmTensor), ("OvmImage", OvmImage), ("OvmGdinoConfig", OvmGdinoConfig),
                          ("OvmJpegInfo", OvmJpegInfo), ("OvmSceneInput", OvmSceneInput), ("OvmSceneLayout", OvmSceneLayout),
-                         ("OvmSceneSegment", OvmSceneSegment), ("OvmEvalCell", OvmEvalCell), ("OvmGeoParams", OvmGeoParams),
+                         ("OvmSceneSegment", OvmSceneSegment), ("OvmPanelBox", OvmPanelBox), ("OvmPanelsInput", OvmPanelsInput),
+                         ("OvmPanelPrim", OvmPanelPrim), ("OvmPanelsLayout", OvmPanelsLayout), ("OvmEvalCell", OvmEvalCell), ("OvmGeoParams", OvmGeoParams),
                          ("OvmGeoInstance", OvmGeoInstance), ("OvmGeoResult", OvmGeoResult), ("OvmGeoBox", OvmGeoBox),
                          ("OvmSamConfig", OvmSamConfig), ("OvmDepthProConfig", OvmDepthProConfig), ("OvmGemmEpiOp", OvmGemmEpiOp),
                          ("OvmAttnF32Op", OvmAttnF32Op), ("OvmMsDeformOp", OvmMsDeformOp), ("OvmRowOp", OvmRowOp),
@@ -297,6 +334,9 @@ def load() -> C.CDLL:
     lib.ovm_host_scene_layout.argtypes = [C.POINTER(OvmSceneInput), C.POINTER(OvmSceneLayout), vp, i32]
     lib.ovm_render_scene_workspace.argtypes = [C.POINTER(OvmSceneLayout), i64, C.POINTER(i64)]
     lib.ovm_render_scene.argtypes = [C.POINTER(OvmSceneLayout), vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
+    lib.ovm_host_panels_layout.argtypes = [C.POINTER(OvmPanelsInput), C.POINTER(OvmPanelsLayout), vp, i32]
+    lib.ovm_render_panels_workspace.argtypes = [C.POINTER(OvmPanelsLayout), C.POINTER(i64)]
+    lib.ovm_render_panels.argtypes = [C.POINTER(OvmPanelsLayout), vp, vp, i64, vp, i64, vp, i64, vp, i64, vp]
     lib.ovm_backbone_forward.argtypes = [vp, C.POINTER(OvmImage), i32, vp, i32, i32, vp, vp, vp, vp]
     lib.ovm_cube_forward.argtypes = [vp, C.POINTER(OvmImage), i32, vp, vp, vp, vp, i32, i32, vp, vp, vp]
     lib.ovm_rpn_box_forward.argtypes = [vp, C.POINTER(OvmImage), i32, vp, vp, vp, vp, vp, vp, vp]

@@ -4,6 +4,8 @@ The small per-scene geometry runs on the host in the library (``ovm_host_scene_l
 blending, the ground grid, box edges and label compositing - is made by ``ovm_render_scene`` (ovmono3d_amd/csrc/render.hip).
 Label glyphs are coverage masks drawn here with Pillow's built-in font (the reference uses cv2's Hershey font); the rules and
 every declared deviation are listed in include/ovm3d.h and restated in numpy by tests/scene_oracle.py.
+
+``visualize_from_instances`` and ``render_panels`` (the evaluation's six-panel samples and 3D error line) live in ``panels.py``.
 """
 from __future__ import annotations
 
@@ -181,3 +183,6 @@ def concat_views(front: torch.Tensor, novel: torch.Tensor) -> torch.Tensor:
     if base is not None and base is novel._base and base.shape[1] == front.shape[1] + novel.shape[1]:
         return base
     return torch.cat((front, novel), 1)
+
+
+from .panels import SampleDataset, match_errors, panel_boxes, panels_layout, render_panels, visualize_from_instances  # noqa: E402,F401

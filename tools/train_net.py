@@ -17,6 +17,11 @@ forwarded to the model when TEST.ORACLE2D is set and the oracle file exists, and
 ``--eval-prox`` turns on upstream Omni3D's proximity evaluation for the datasets whose name contains Objectron or SUNRGBD
 (reference omni3d_evaluation.py:263), in their own evaluation and for their images in the collective pass; ``--eval-matcher
 device`` runs the evaluator's matching on the GPU (same results as ``host``); ``--eval-3d device`` also its 3D IoU and NHD stages.
+
+``--vis-every N`` (off by default; the reference uses 50) adds the reference's ``vis.visualize_from_instances`` step
+(tools/train_net.py:112-130): for every N-th image of a dataset a six-panel JPEG under ``<dataset>/vis/``, composed on the device,
+and one logged line with the mean centre, depth, size and rotation errors of the matched predictions; ``--vis-fork-compat`` takes
+those errors as the fork does (sampled images only, its rotation formula).
 """
 import argparse
 import json
@@ -61,7 +66,7 @@ def uses_proximity(name):
 
 
 def do_test(cfg, model, mode="base", datasets_root="datasets/Omni3D", image_root="datasets", depth_dir=None, category_meta=None,
-            eval_prox=False, matcher="host", stage3d="host"):
+            eval_prox=False, matcher="host", stage3d="host", vis_every=0, vis_fork_compat=False):
     if stage3d == "device":                                                     # the 3D stages ride in the device matcher's upload
         matcher = "device"
     if mode == "novel":
@@ -107,6 +112,13 @@ def do_test(cfg, model, mode="base", datasets_root="datasets/Omni3D", image_root
                     json.dump(cmap.to_meta(), f)
                 logger.info("%s: AP2D %.2f  AP3D %.2f  (AP3D@15 %.2f, @25 %.2f, @50 %.2f)  NHD %.4f", name, ap["bbox_2D"]["AP"],
                             ap["bbox_3D"]["AP"], ap["bbox_3D"]["AP15"], ap["bbox_3D"]["AP25"], ap["bbox_3D"]["AP50"], ap["bbox_3D"]["NHD"])
+                if vis_every > 0:
+                    # the reference's sample visualisation and 3D error line (tools/train_net.py:112-130), panels drawn on the device
+                    from ovmono3d_amd import vis
+                    logger.info(vis.visualize_from_instances(
+                        results, vis.SampleDataset.from_ground_truth(dicts, gt, cmap), name, cfg.INPUT.MIN_SIZE_TEST,
+                        os.path.join(out_dir, name), cmap.thing_classes, gt.category_names, "final", every=vis_every,
+                        fork_compat=vis_fork_compat))
 
 
     if get_rank() == 0 and len(all_files) > 1:
@@ -160,12 +172,12 @@ def main(args):
     DetectionCheckpointer(model, save_dir=cfg.OUTPUT_DIR).resume_or_load(cfg.MODEL.WEIGHTS, resume=args.resume)
     if cfg.TEST.CAT_MODE == "all":
         do_test(cfg, model, "novel", args.datasets_root, args.image_root, args.depth_dir, args.category_meta, args.eval_prox, args.eval_matcher,
-                args.eval_3d)
+                args.eval_3d, args.vis_every, args.vis_fork_compat)
         do_test(cfg, model, "base", args.datasets_root, args.image_root, args.depth_dir, args.category_meta, args.eval_prox, args.eval_matcher,
-                args.eval_3d)
+                args.eval_3d, args.vis_every, args.vis_fork_compat)
     else:
         do_test(cfg, model, cfg.TEST.CAT_MODE, args.datasets_root, args.image_root, args.depth_dir, args.category_meta, args.eval_prox,
-                args.eval_matcher, args.eval_3d)
+                args.eval_matcher, args.eval_3d, args.vis_every, args.vis_fork_compat)
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()
@@ -192,6 +204,11 @@ def default_argument_parser():
     p.add_argument("--eval-3d", choices=("host", "device"), default="host", help="(native build) where the evaluator's 3D stages run: host "
                    "(one 3D IoU call per image, NHD through scipy) or device (one IoU launch over all cells, NHD solved in HIP; implies "
                    "--eval-matcher device); the IoU is the same bit for bit, the NHD agrees to fp32 rounding of the host path")
+    p.add_argument("--vis-every", type=int, default=0, metavar="N", help="(native build) write a six-panel sample picture (ground truth of "
+                   "all / of the evaluated classes / predictions, 2D above 3D) for every N-th image of a dataset to <dataset>/vis/ and log the "
+                   "mean 3D errors of the matched predictions, as the reference's vis.visualize_from_instances; 0 = off (the reference uses 50)")
+    p.add_argument("--vis-fork-compat", action="store_true", help="(native build) with --vis-every: take the logged errors as the fork does "
+                   "(over the sampled images only, ry = pi/2 - (trace - 1)/2); default: over all images, ry the geodesic angle (upstream)")
     p.add_argument("opts", default=None, nargs=argparse.REMAINDER)
     return p
 
