@@ -571,6 +571,10 @@ int ovm_g_swin_qkv_attn(const OvmSwinQkvAttnOp* op, ovm_stream_t stream);
  *   gdino_gemm256 0|1 (the detector's wide K <= 256 contractions on the 256 x 256 kernel; default 1; read when a plan is built),
  *   gdino_mlp_fused 0|1|2 (the image branch's two-layer MLPs as one kernel + the split-K reduce: 0 off, 1 the Swin blocks whose fc2 is
  *   split over K today, 2 those and the encoder's FFN where its slabs fit the workspace; default 1; read when a plan is built),
+ *   gdino_enc_fold 0|1|2|3 (encoder: 1 = the position term of the sampling-offsets projection as a per-plan table, value and offsets projections as one GEMM, split rows written by their producers; 2 = the fold alone, 3 = the producers' split rows of the neck and the decoder inputs alone; default 0; read when a plan is built),
+ *   gdino_enc_tap 0|1 (tests: plans built afterwards keep copies of encoder layer 0's out-projection rows, their split and the value |
+ *   offsets projections' outputs for ovm_gdino_debug_copy "enc_pos|enc_vis0|enc_vis0_hi|enc_vis0_lo|enc_voff0|enc_P0", with gdino_enc_fold 0
+ *   "enc_val0|enc_ow0" for the last two; default 0),
  *   attn_tail_split 0|1 (attention's leftover queries split over 16 key slices + combine kernel; default 1), attn_prio n (experiment:
  *   s_setprio inside the two-wave-group attention kernel; default 0), gemm256_ksplit n (experiment: split-K hint of the 256 x 256 kernel for
  *   proj / fc2; default 0 = off, measured slower), glin_wpe 2|4 (experiment: workgroups per CU the small fp32-A GEMM is compiled for; default 2),

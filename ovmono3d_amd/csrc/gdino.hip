@@ -23,14 +23,16 @@ using namespace ovm;
 using namespace ovm::gdino;
 
 namespace ovm {
-GdinoTune g_gdino_tune = {1, 1, 0, 1, 1, 1, 0}; // branches, dec_chain, ffn_split, swin_fused, gemm256, mlp_fused, swin_tap
+GdinoTune g_gdino_tune = {1, 1, 0, 1, 1, 1, 0, 0, 0}; // branches, dec_chain, ffn_split, swin_fused, gemm256, mlp_fused, swin_tap, enc_fold, enc_tap
 void set_gdino_branches(int v) { g_gdino_tune.branches = v ? 1 : 0; }       // engines created afterwards
-void set_gdino_dec_chain(int v) { g_gdino_tune.dec_chain = v ? 1 : 0; }     // this and the four below: plans built afterwards
+void set_gdino_dec_chain(int v) { g_gdino_tune.dec_chain = v ? 1 : 0; }     // this and the ones below: plans built afterwards
 void set_gdino_ffn_split(int v) { g_gdino_tune.ffn_split = v ? 1 : 0; }
 void set_gdino_swin_fused(int v) { g_gdino_tune.swin_fused = v ? 1 : 0; }
 void set_gdino_swin_tap(int v) { g_gdino_tune.swin_tap = v > 0 ? v : 0; }
 void set_gdino_gemm256(int v) { g_gdino_tune.gemm256 = v ? 1 : 0; }
 void set_gdino_mlp_fused(int v) { g_gdino_tune.mlp_fused = v < 0 ? 0 : (v > 2 ? 2 : v); }
+void set_gdino_enc_fold(int v) { g_gdino_tune.enc_fold = (v < 0 || v > 3) ? 0 : v; }
+void set_gdino_enc_tap(int v) { g_gdino_tune.enc_tap = v ? 1 : 0; }
 }  // namespace ovm
 
 namespace ovm {
@@ -38,7 +40,7 @@ namespace gdino {
 namespace {
 
 // ---- buffers that cross stages (arena pointers; the order they are allocated in is the arena's layout)
-struct Feat { float* f; int h, w, C; };
+struct Feat { float* f; int h, w, C; SplitBuf sp; };     // sp: the rows as the neck's projection takes them (tune.prod_split())
 struct DecScratch {                                        // shared by the decoder layers and the heads
   float *tkv_all, *val_all;                                // all layers' text keys | values [T][NL 2 D], deformable values of the memory [S][NL D]
   float *sine, *qh, *qpos, *qk, *vq, *ctx, *pre, *ow, *ffb, *b1, *b2, *delta;
@@ -50,6 +52,7 @@ struct State {
   float *tx, *text0, *text;                                // BERT output, projected text features (kept intact for the debug tap), encoder text output
   std::vector<Feat> feats;                                 // Swin output stages
   float *vis0, *vis;                                       // projected image features, encoder state / output
+  SplitBuf dec_vsp;                                        // tune.prod_split(): the encoder output as dec_value's A operand
   float* ref; int* topk;                                   // two-stage selection
   float *hs, *last_ref, *hn;                               // decoder state, the last layer's reference boxes, normalised state
   DecScratch d;
@@ -224,8 +227,12 @@ void swin_backbone(Run& r, State& st) {
     for (size_t b = 0; b < stg.blocks.size(); ++b) swin_block(r, stg.blocks[b], ge.wm[b & 1], x, C, stg.nh, ntok, ++ordinal);
     if (stg.has_out) {
       float* f = r.f32((size_t)ntok * C);
-      r.ln(x, ntok, C, stg.on, eps, nullptr, f);
-      st.feats.push_back({f, h, w, C});
+      // the neck projects the level straight from these rows: the norm writes them split as well (they live until the neck, like f,
+      // which stays for the tap and for the extra level's 3 x 3 gather)
+      SplitBuf sp;
+      if (pl->tune.prod_split() && (int)st.feats.size() < g->cfg.n_levels) sp = r.split((size_t)ntok, C);
+      r.ln(x, ntok, C, stg.on, eps, nullptr, f, sp.hi ? &sp : nullptr);
+      st.feats.push_back({f, h, w, C, sp});
       r.tap("swin_stage" + std::to_string(st.feats.size()), f, (int64_t)ntok * C);
     }
     if (stg.has_red) { x = patch_merge(r, stg, ge, x, C); h = ge.h2; w = ge.w2; C = 2 * C; }
@@ -246,10 +253,13 @@ void neck(Run& r, State& st) {
     const bool conv = l >= (int)st.feats.size();          // the extra level: 3x3 stride-2 convolution of the last stage, rows gathered through the im2col map
     const Feat& f = conv ? st.feats.back() : st.feats[l];
     const int K = conv ? 9 * f.C : f.C;
-    SplitBuf a = r.split((size_t)n, K);
-    RowOpParams p = Run::rows(f.f, f.C, n, K); Run::into(p, a);
-    if (conv) { p.idx = pl->conv_map; p.nidx = 9; p.seg = f.C; }
-    r.rowop(p);
+    SplitBuf a = f.sp;
+    if (conv || !a.hi) {
+      a = r.split((size_t)n, K);
+      RowOpParams p = Run::rows(f.f, f.C, n, K); Run::into(p, a);
+      if (conv) { p.idx = pl->conv_map; p.nidx = 9; p.seg = f.C; }
+      r.rowop(p);
+    }
     GemmParams q = r.gp(a, n, g->inproj[l].w); q.C = y; q.ldc = D;
     r.gemm(q, EPI_STORE);
     if (r.go()) r.chk(ovm_g_groupnorm(y, 1, n, D, 32, g->inproj[l].gn.g, g->inproj[l].gn.b, 1e-5f, st.vis0 + (size_t)pl->lstart[l] * D, r.s_main), "groupnorm");
@@ -263,6 +273,8 @@ struct EncBufs {
   BiAttnWs bw; float *sc, *stat, *part, *bml;
   float *text2, *tqk, *tv, *tctx, *tff;
   SplitBuf vis_sp, visp_sp; float *val, *ow; SplitBuf dsp; float* pre; SplitBuf ff;
+  float* voff;                                             // tune.fold(): [value | offsets | logits] rows [S][D + NOW] in place of visp_sp, val, ow
+  float *tap_vis = nullptr, *tap_voff = nullptr; half_t *tap_hi = nullptr, *tap_lo = nullptr;   // tune.enc_tap: layer 0's copies
   bool ffn_fused;                                          // the layers' FFN on the fused route (ff is not allocated then)
 };
 
@@ -301,18 +313,43 @@ void text_enhancer(Run& r, const EncLayer& ly, EncBufs& b, float* text) {
 }
 
 // image half, on the main stream: the fusion's gated image output, deformable self-attention over the image tokens, FFN -> vis
-void deformable_layer(Run& r, const EncLayer& ly, EncBufs& b, float* vis) {
+// `li`: the layer's index; `out_sp`: split rows the final norm writes beside vis (the last layer's, for the decoder's value projection)
+void deformable_layer(Run& r, const EncLayer& ly, EncBufs& b, float* vis, int li, const SplitBuf* out_sp) {
   const OvmGdinoConfig& c = r.g->cfg; Plan* pl = r.pl;
   const int D = c.d_model, S = pl->S, NOW = now_cols(c);
-  { GemmParams q = r.gp(b.cv, S, ly.ov); q.C = vis; q.ldc = D; q.R = b.v; q.ldr = D; r.gemm(q, EPI_STORE); }
-  {
-    RowOpParams p = Run::rows(vis, D, S, D); Run::into(p, b.vis_sp);
-    p.add = pl->pos; p.ld_add = D; p.add_rows = S; p.hi2 = b.visp_sp.hi; p.lo2 = b.visp_sp.lo; p.ldh2 = b.visp_sp.ld;
-    r.rowop(p);
+  if (pl->tune.fold()) {
+    // the out-projection writes vis and its split rows; value and offsets projections read those rows as ONE GEMM over [value | offw],
+    // whose epilogue adds the layer's table P = pos W_off^T + b_off to the offsets columns (n >= D): no row pass, no vis + pos image
+    { GemmParams q = r.gp(b.cv, S, ly.ov); q.C = vis; q.ldc = D; q.R = b.v; q.ldr = D; q.Ohi = b.vis_sp.hi; q.Olo = b.vis_sp.lo; q.ldo = b.vis_sp.ld; r.gemm(q, EPI_STORE); }
+    { GemmParams q = r.gp(b.vis_sp, S, ly.msda.voff); q.C = b.voff; q.ldc = D + NOW; q.R = pl->enc_P[li]; q.ldr = NOW; q.r_n0 = D; r.gemm(q, EPI_STORE); }
+    deform(r, b.voff, D + NOW, b.voff + D, D + NOW, pl->ref, 2, 0, S, nullptr, &b.dsp);
+  } else {
+    { GemmParams q = r.gp(b.cv, S, ly.ov); q.C = vis; q.ldc = D; q.R = b.v; q.ldr = D; r.gemm(q, EPI_STORE); }
+    {
+      RowOpParams p = Run::rows(vis, D, S, D); Run::into(p, b.vis_sp);
+      p.add = pl->pos; p.ld_add = D; p.add_rows = S; p.hi2 = b.visp_sp.hi; p.lo2 = b.visp_sp.lo; p.ldh2 = b.visp_sp.ld;
+      r.rowop(p);
+    }
+    { GemmParams q = r.gp(b.vis_sp, S, ly.msda.value); q.C = b.val; q.ldc = D; r.gemm(q, EPI_STORE); }
+    { GemmParams q = r.gp(b.visp_sp, S, ly.msda.offw); q.C = b.ow; q.ldc = NOW; r.gemm(q, EPI_STORE); }
+    deform(r, b.val, D, b.ow, NOW, pl->ref, 2, 0, S, nullptr, &b.dsp);
   }
-  { GemmParams q = r.gp(b.vis_sp, S, ly.msda.value); q.C = b.val; q.ldc = D; r.gemm(q, EPI_STORE); }
-  { GemmParams q = r.gp(b.visp_sp, S, ly.msda.offw); q.C = b.ow; q.ldc = NOW; r.gemm(q, EPI_STORE); }
-  deform(r, b.val, D, b.ow, NOW, pl->ref, 2, 0, S, nullptr, &b.dsp);
+  if (li == 0 && b.tap_vis) {
+    // tests (ovm_tune_set gdino_enc_tap): layer 0's out-projection rows, their split and the projections' outputs, copied before the later
+    // layers reuse the buffers; debug copies count 4-byte elements
+    const size_t nsp = (size_t)S * b.vis_sp.ld * sizeof(half_t);
+    r.tap("enc_pos", pl->pos, (int64_t)S * D);
+    r.copy(b.tap_vis, vis, sizeof(float) * (size_t)S * D, r.s_main); r.tap("enc_vis0", b.tap_vis, (int64_t)S * D);
+    r.copy(b.tap_hi, b.vis_sp.hi, nsp, r.s_main); r.tap("enc_vis0_hi", b.tap_hi, (int64_t)(nsp / 4));
+    if (b.vis_sp.lo) { r.copy(b.tap_lo, b.vis_sp.lo, nsp, r.s_main); r.tap("enc_vis0_lo", b.tap_lo, (int64_t)(nsp / 4)); }
+    if (pl->tune.fold()) {
+      r.copy(b.tap_voff, b.voff, sizeof(float) * (size_t)S * (D + NOW), r.s_main); r.tap("enc_voff0", b.tap_voff, (int64_t)S * (D + NOW));
+      r.tap("enc_P0", pl->enc_P[0], (int64_t)S * NOW);
+    } else {
+      r.copy(b.tap_voff, b.val, sizeof(float) * (size_t)S * D, r.s_main); r.tap("enc_val0", b.tap_voff, (int64_t)S * D);
+      r.copy(b.tap_voff + (size_t)S * D, b.ow, sizeof(float) * (size_t)S * NOW, r.s_main); r.tap("enc_ow0", b.tap_voff + (size_t)S * D, (int64_t)S * NOW);
+    }
+  }
   { GemmParams q = r.gp(b.dsp, S, ly.msda.out); q.C = b.pre; q.ldc = D; q.R = vis; q.ldr = D; r.gemm(q, EPI_STORE); }
   r.ln(b.pre, S, D, ly.de_ln1, c.eps, nullptr, b.v, &b.vsp);
   if (b.ffn_fused) {
@@ -322,15 +359,23 @@ void deformable_layer(Run& r, const EncLayer& ly, EncBufs& b, float* vis) {
     { GemmParams q = r.gp(b.vsp, S, ly.de_fc1); q.Ohi = b.ff.hi; q.Olo = b.ff.lo; q.ldo = b.ff.ld; q.relu = 1; r.gemm(q, EPI_STORE); }
     { GemmParams q = r.gp(b.ff, S, ly.de_fc2); q.C = b.pre; q.ldc = D; q.R = b.v; q.ldr = D; r.gemm(q, EPI_STORE); }
   }
-  r.ln(b.pre, S, D, ly.de_ln2, c.eps, nullptr, vis);
+  r.ln(b.pre, S, D, ly.de_ln2, c.eps, nullptr, vis, out_sp);
 }
 
 void encoder(Run& r, State& st) {
   const OvmGdinoConfig& c = r.g->cfg;
   const int D = c.d_model, T = r.pl->T, S = r.pl->S, HF = c.heads / 2, E = c.ffn_dim / 2, dhf = E / HF;
+  const int NOW = now_cols(c), NE = (int)r.g->enc.size();
   r.join();                                               // text features and image features meet in the fusion layers
-  const size_t mk = r.mark();
   EncBufs b;
+  // what outlives the encoder's scratch: the rows the last layer's final norm writes for the decoder's value projection, test copies
+  if (r.pl->tune.prod_split() && NE > 0) st.dec_vsp = r.split_for256((size_t)S, D);
+  if (r.pl->tune.enc_tap && NE > 0) {
+    const size_t nsp = (size_t)S * ((D + 63) / 64 * 64) * sizeof(half_t);
+    b.tap_vis = r.f32((size_t)S * D); b.tap_voff = r.f32((size_t)S * (D + NOW));
+    b.tap_hi = (half_t*)r.alloc(nsp); b.tap_lo = (half_t*)r.alloc(nsp);
+  }
+  const size_t mk = r.mark();
   b.v = r.f32((size_t)S * D); b.vsp = r.split_for256((size_t)S, D);      // A of vqv / de_fc1: S x 2048 outputs over K = 256
   b.t = r.f32((size_t)T * D);
   b.qvv = r.f32((size_t)S * 2 * E);              // [vision_proj | values_vision_proj]
@@ -345,22 +390,30 @@ void encoder(Run& r, State& st) {
   b.text2 = r.f32((size_t)T * D);
   b.tqk = r.f32((size_t)T * 2 * D); b.tv = r.f32((size_t)T * D); b.tctx = r.f32((size_t)T * D);
   b.tff = r.f32((size_t)T * c.ffn_dim);
-  b.vis_sp = r.split((size_t)S, D); b.visp_sp = r.split((size_t)S, D);
-  b.val = r.f32((size_t)S * D);
-  b.ow = r.f32((size_t)S * now_cols(c));
+  b.vis_sp = r.split((size_t)S, D);
+  b.val = b.ow = b.voff = nullptr;
+  if (r.pl->tune.fold()) {
+    if ((int)r.pl->enc_P.size() != NE || D % 4) { r.fail(OVM_ERR_INVALID, "encoder: the plan has no offsets tables"); return; }
+    b.voff = r.f32((size_t)S * (D + NOW));                // value at column 0, offsets | logits at column D: both 16-byte aligned rows (D % 4 == 0)
+  } else {
+    b.visp_sp = r.split((size_t)S, D);
+    b.val = r.f32((size_t)S * D);
+    b.ow = r.f32((size_t)S * NOW);
+  }
   b.dsp = r.split((size_t)S, D);
   b.pre = r.f32((size_t)S * D);
   b.ffn_fused = b.vsp.il;
   for (auto& ly : r.g->enc) b.ffn_fused = b.ffn_fused && r.mlp_fused_ok(2, S, ly.de_fc1, ly.de_fc2, 1);
   if (!b.ffn_fused) b.ff = r.split((size_t)S, c.ffn_dim);
   const float* vis_in = st.vis0; const float* text_in = st.text0;
-  for (auto& ly : r.g->enc) {
+  for (int li = 0; li < NE; ++li) {
+    const EncLayer& ly = r.g->enc[li];
     fusion_layer(r, ly, b, vis_in, text_in);
     vis_in = st.vis; text_in = st.text;
     // the two halves of the layer from here on touch disjoint buffers: text side (ot, text enhancer -> text) on the text
     // branch, image side (ov, deformable self-attention, FFN -> vis) on the main one; joined at the end of the layer
     text_enhancer(r, ly, b, st.text);
-    deformable_layer(r, ly, b, st.vis);
+    deformable_layer(r, ly, b, st.vis, li, (li == NE - 1 && st.dec_vsp.hi) ? &st.dec_vsp : nullptr);
     r.join();
   }
   r.release(mk);
@@ -421,8 +474,11 @@ size_t decoder_inputs(Run& r, State& st) {
   const size_t mk = r.mark();
   d.tkv_all = r.f32((size_t)T * NL * 2 * D);
   r.lin(st.text, nullptr, D, T, g->dec_kv_text, 0, nullptr, 0, d.tkv_all, NL * 2 * D);
-  SplitBuf vsp = r.split_for256((size_t)S, D);
-  { RowOpParams p = Run::rows(st.vis, D, S, D); Run::into(p, vsp); r.rowop(p); }
+  SplitBuf vsp = st.dec_vsp;                                // written by the encoder's last norm (tune.prod_split())
+  if (!vsp.hi) {
+    vsp = r.split_for256((size_t)S, D);
+    RowOpParams p = Run::rows(st.vis, D, S, D); Run::into(p, vsp); r.rowop(p);
+  }
   d.val_all = r.f32((size_t)S * NL * D);
   { GemmParams q = r.gp(vsp, S, g->dec_value); q.C = d.val_all; q.ldc = NL * D; r.gemm(q, EPI_STORE); }
   r.copy(st.hs, g->tgt, sizeof(float) * (size_t)Q * D, r.s_main);
@@ -642,6 +698,7 @@ int ovm_gdino_create(const OvmGdinoConfig* cfg, const OvmTensor* weights, int32_
   OVM_TRY(g, load_neck(g, wm));
   OVM_TRY(g, load_encoder(g, wm));
   OVM_TRY(g, load_decoder(g, wm));
+  OVM_TRY(g, load_encoder_merged(g, wm));
   OVM_HIP(g, hipDeviceSynchronize());
   return OVM_OK;
 }

@@ -245,5 +245,21 @@ int load_decoder(OvmGdino* g, const WeightMap& wm) {
   return OVM_OK;
 }
 
+// [value_proj | sampling_offsets | attention_weights] of every encoder layer as one weight (GdinoTune::enc_fold): the bias covers the
+// value columns, that of the other columns lives in the plan's table (plan_offset_tables). The separate packs stay for enc_fold = 0.
+int load_encoder_merged(OvmGdino* g, const WeightMap& wm) {
+  for (size_t i = 0; i < g->enc.size(); ++i) {
+    MsdaW& m = g->enc[i].msda;
+    const std::string p = M + "encoder.layers." + std::to_string(i) + ".deformable_layer.self_attn.";
+    OVM_TRY(g, pack_cat(g, wm, {p + "value_proj", p + "sampling_offsets", p + "attention_weights"}, &m.voff, false));
+    if (m.voff.N != m.value.N + m.offw.N || m.voff.Kpad != m.value.Kpad) { g->err = "merged value | offsets weight shape"; return OVM_ERR_SHAPE; }
+    const float* bv; OVM_TRY(g, find_weight(g, wm, p + "value_proj.bias", m.value.N, &bv));
+    std::vector<float> b((size_t)m.voff.N, 0.f);
+    for (int n = 0; n < m.value.N; ++n) b[n] = bv[n];
+    OVM_TRY(g, upload_f32(g, b.data(), b.size(), &m.voff.bias));
+  }
+  return OVM_OK;
+}
+
 }  // namespace gdino
 }  // namespace ovm

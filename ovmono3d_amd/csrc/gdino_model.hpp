@@ -32,6 +32,17 @@ struct GdinoTune {
                        // 2 Swin blocks and the encoder's FFN
   int swin_tap;        // tests: n > 0 keeps copies of the n-th Swin block's window rows and context rows (fused route) for
                        // ovm_gdino_debug_copy "swin_tap_*"; costs arena and four copies per forward, so 0 outside tests
+  int enc_fold;        // encoder, image half: 1 = both halves below, 2 = the fold alone, 3 = the producers' split rows alone, 0 = neither.
+                       // Fold: (vis + pos) W_off^T + b_off = vis W_off^T + P with P = pos W_off^T + b_off a per-plan, per-layer table
+                       // (Plan::enc_P), so value and offsets projections are ONE GEMM over [value | offw] (MsdaW::voff) whose epilogue adds P
+                       // to the offsets columns, and the out-projection writes the split rows that GEMM reads (no row pass).
+                       // Producers' split rows: the Swin stages' out-norms write the rows the neck's projections read, the last
+                       // layer's final norm those of the decoder's value projection (no row pass at either site).
+  int enc_tap;         // tests: keeps copies of encoder layer 0's out-projection rows, their split and the value | offsets projections'
+                       // outputs for ovm_gdino_debug_copy "enc_pos|enc_vis0|enc_vis0_hi|enc_vis0_lo|enc_voff0|enc_P0" (enc_fold 0: "enc_val0|enc_ow0"
+                       // for the last two); costs arena and four copies per forward, so 0 outside tests
+  bool fold() const { return enc_fold == 1 || enc_fold == 2; }
+  bool prod_split() const { return enc_fold == 1 || enc_fold == 3; }
 };
 extern GdinoTune g_gdino_tune;
 
@@ -48,7 +59,7 @@ struct SwinBlock { Ln ln1, ln2; Lin qkv, proj, fc1, fc2; float* relbias = nullpt
 struct SwinStage { std::vector<SwinBlock> blocks; int nh = 0, C = 0; bool has_red = false; Lin red; Ln dn; bool has_out = false; Ln on; };
 struct BertLayer { Lin qkv, ao, fi, fo; Ln aln, oln; };
 struct Mha { Lin qk, v, out; Lin q, kv; int heads = 0; };       // qk: [query | key] rows; kv: [key | value]; q alone for cross attention
-struct MsdaW { Lin offw, value, out; };
+struct MsdaW { Lin offw, value, out; Lin voff; };   // voff (encoder layers): [value | offw] rows, bias on the value columns alone (GdinoTune::enc_fold)
 struct EncLayer {
   Ln lnv, lnt; Lin vqv, tkv, ov, ot;            // fusion: [vision_proj | values_vision_proj], [text_proj | values_text_proj], gated output projections
   Mha te; Ln te_ln1, te_ln2; Lin te_fc1, te_fc2;
@@ -103,6 +114,7 @@ int load_swin(OvmGdino* g, const WeightMap& wm);
 int load_neck(OvmGdino* g, const WeightMap& wm);
 int load_encoder(OvmGdino* g, const WeightMap& wm);
 int load_decoder(OvmGdino* g, const WeightMap& wm);      // with the heads and the fragment-ordered copies (make_frag)
+int load_encoder_merged(OvmGdino* g, const WeightMap& wm);   // MsdaW::voff of every encoder layer; last, so that no other weight moves
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // Plan: everything derived from (H, W, token ids, position ids)
@@ -124,6 +136,7 @@ struct Plan {
   int nlev = 0; int lh[8] = {0}, lw[8] = {0}, lstart[8] = {0}; int S = 0;
   int* conv_map = nullptr; int conv_h = 0, conv_w = 0;
   float* pos = nullptr; float* ref = nullptr; float* prop_logit = nullptr; int* valid_idx = nullptr;
+  std::vector<float*> enc_P;                     // tune.fold(): per encoder layer [S][NOW] = pos W_off^T + b_off (plan_offset_tables)
   // scratch owned by the plan
   float* img = nullptr;                          // normalised input image [H*W][3]
   char* arena = nullptr; size_t arena_cap = 0;

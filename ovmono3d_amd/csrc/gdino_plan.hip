@@ -249,6 +249,25 @@ int plan_scratch(OvmGdino* g, Plan* pl) {
   return pal(g, pl, (char**)&pl->gemm_ws, pl->gemm_ws_cap);
 }
 
+// tune.fold(): per encoder layer P [S][NOW] = pos W_off^T + b_off, the position term of the sampling-offsets | attention-weights
+// projection ((vis + pos) W^T + b = vis W^T + P; pos depends on the image shape and level_embed alone). Computed once, here, with the
+// engine's fp32-A GEMM on the null stream and finished before the plan is handed out; the forward's merged GEMM adds it in its epilogue.
+int plan_offset_tables(OvmGdino* g, Plan* pl) {
+  const OvmGdinoConfig& c = g->cfg;
+  const int S = pl->S, D = c.d_model, NOW = c.heads * c.n_levels * c.n_points * 3;
+  if (!gemm_small_supported(pl->pos, D, D)) { g->err = "offsets tables: d_model must be a multiple of 4"; return OVM_ERR_SHAPE; }
+  pl->enc_P.assign(g->enc.size(), nullptr);
+  for (size_t i = 0; i < g->enc.size(); ++i) {
+    const Lin& w = g->enc[i].msda.offw;
+    if (w.N != NOW || w.K != D) { g->err = "offsets tables: sampling-offsets weight shape"; return OVM_ERR_SHAPE; }
+    OVM_TRY(g, pal(g, pl, &pl->enc_P[i], (size_t)S * NOW));
+    OVM_TRY(g, launch_gemm_small_ex(pl->pos, nullptr, D, S, D, w.hi, w.lo, NOW, w.Kpad, w.bias, 0, nullptr, 0, pl->enc_P[i], NOW, g->precision,
+                                    pl->gemm_ws, pl->gemm_ws_cap, nullptr));
+  }
+  OVM_HIP(g, hipDeviceSynchronize());
+  return OVM_OK;
+}
+
 }  // namespace
 
 int build_plan(OvmGdino* g, int H, int W, const std::vector<int>& ids, const std::vector<int>& pids, Plan** out) {
@@ -261,6 +280,7 @@ int build_plan(OvmGdino* g, int H, int W, const std::vector<int>& ids, const std
   OVM_TRY(g, plan_levels(g, pl.get(), feat_hw));
   OVM_TRY(g, plan_encoder_tables(g, pl.get()));
   OVM_TRY(g, plan_scratch(g, pl.get()));
+  if (pl->tune.fold()) OVM_TRY(g, plan_offset_tables(g, pl.get()));      // after the scratch: the GEMM may split K through the plan's workspace
   *out = pl.release();
   return OVM_OK;
 }

@@ -51,6 +51,8 @@ struct GemmParams {
   int o_il;                                       // EPI_GELU: Ohi / Olo form an interleaved image (Olo = Ohi + 32, ldo = 2 N)
   int relu;                                       // EPI_STORE activation: 0 none, 1 ReLU, 2 GELU(erf); EPI_GELU: 3 = QuickGELU, else erf
   const float* R; int ldr;                        // EPI_STORE: optional fp32 residual added after the activation
+  int r_n0;                                       // ... to columns n >= r_n0 only, read at R[m * ldr + n - r_n0] (0: every column) - a
+                                                  // per-row table that belongs to the right-hand part of concatenated weights
   const float* R2; int ldr2;                      // EPI_STORE: optional second fp32 residual (fusion: skip + the other branch)
   int relu_o;                                     // EPI_STORE: Ohi / Olo receive relu(value) while C keeps the value - the input of a
                                                   // pre-activation residual unit's first convolution, whose skip is the fp32 copy
@@ -251,17 +253,30 @@ __device__ __forceinline__ void epilogue4(const GemmParams& p, int m, int n, f32
     *(half4*)(p.Ohi + o) = h;
     if (p.Olo) *(half4*)(p.Olo + o) = l;
   } else {  // EPI_STORE
+    // whole groups of four move as one 16-byte (fp16: 8-byte) access where the rows are aligned for it; same values either way
     float o4[4];
+    float r4[4] = {0.f, 0.f, 0.f, 0.f};
+    if (p.R) {
+      if (full && n >= p.r_n0 && !((p.ldr | p.r_n0) & 3) && !((uintptr_t)p.R & 15)) {
+        const f32x4 t = *(const f32x4*)(p.R + (size_t)m * p.ldr + n - p.r_n0);
+        r4[0] = t[0]; r4[1] = t[1]; r4[2] = t[2]; r4[3] = t[3];
+      } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (n + r < p.N && n + r >= p.r_n0) r4[r] = p.R[(size_t)m * p.ldr + n + r - p.r_n0];
+      }
+    }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       o4[r] = v[r] + b4[r];
       if (p.relu == 1) o4[r] = fmaxf(o4[r], 0.f); else if (p.relu == 2) o4[r] = gelu_erf(o4[r]);
-      if (p.R && n + r < p.N) o4[r] += p.R[(size_t)m * p.ldr + n + r];
+      if (p.R && n + r < p.N && n + r >= p.r_n0) o4[r] += r4[r];
       if (p.R2 && n + r < p.N) o4[r] += p.R2[(size_t)m * p.ldr2 + n + r];
     }
     if (p.C) {
       float* c = p.C + (size_t)m * p.ldc + n;
-      for (int r = 0; r < 4 && n + r < p.N; ++r) c[r] = o4[r];
+      if (full && !(p.ldc & 3) && !((uintptr_t)p.C & 15)) *(f32x4*)c = (f32x4){o4[0], o4[1], o4[2], o4[3]};
+      else for (int r = 0; r < 4 && n + r < p.N; ++r) c[r] = o4[r];
     }
     if (p.Ohi) {
       size_t row = (size_t)m;
@@ -270,10 +285,18 @@ __device__ __forceinline__ void epilogue4(const GemmParams& p, int m, int n, f32
         row = ((size_t)b * (p.padH + 2) + y + 1) * (p.padW + 2) + x + 1;
       }
       const size_t o = row * p.ldo + n;
-      for (int r = 0; r < 4 && n + r < p.N; ++r) {
-        half_t hh, ll; split_f16(p.relu_o ? fmaxf(o4[r], 0.f) : o4[r], hh, ll);
-        p.Ohi[o + r] = hh;
-        if (p.Olo) p.Olo[o + r] = ll;
+      if (full && !(p.ldo & 3) && !(((uintptr_t)p.Ohi | (uintptr_t)p.Olo) & 7)) {
+        half4 h, l;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { half_t hh, ll; split_f16(p.relu_o ? fmaxf(o4[r], 0.f) : o4[r], hh, ll); h[r] = hh; l[r] = ll; }
+        *(half4*)(p.Ohi + o) = h;
+        if (p.Olo) *(half4*)(p.Olo + o) = l;
+      } else {
+        for (int r = 0; r < 4 && n + r < p.N; ++r) {
+          half_t hh, ll; split_f16(p.relu_o ? fmaxf(o4[r], 0.f) : o4[r], hh, ll);
+          p.Ohi[o + r] = hh;
+          if (p.Olo) p.Olo[o + r] = ll;
+        }
       }
     }
   }

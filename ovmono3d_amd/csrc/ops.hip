@@ -58,7 +58,7 @@ struct Tmp {
 };
 }  // namespace
 
-namespace ovm { void set_use_gemm256(int v); void set_gdino_branches(int v); void msdeform_set_vec(int v); void set_gdino_dec_chain(int v); void set_gdino_gemm256(int v); void set_gdino_swin_fused(int v); void set_gdino_swin_tap(int v); void set_gdino_ffn_split(int v); void set_gdino_mlp_fused(int v); void gemm256_set_n192(int v); void set_gemm256_ksplit(int v); }
+namespace ovm { void set_use_gemm256(int v); void set_gdino_branches(int v); void msdeform_set_vec(int v); void set_gdino_dec_chain(int v); void set_gdino_gemm256(int v); void set_gdino_swin_fused(int v); void set_gdino_swin_tap(int v); void set_gdino_ffn_split(int v); void set_gdino_mlp_fused(int v); void set_gdino_enc_fold(int v); void set_gdino_enc_tap(int v); void gemm256_set_n192(int v); void set_gemm256_ksplit(int v); }
 
 extern "C" {
 
@@ -417,8 +417,10 @@ int ovm_tune_set(const char* key, int32_t value) {
 #endif
     attn_set_pp(value); return OVM_OK;
   }
-  // the five below are copied into a detector plan when it is built (GdinoTune, gdino_model.hpp): a plan keeps its values
+  // the gdino_* keys below are copied into a detector plan when it is built (GdinoTune, gdino_model.hpp): a plan keeps its values
   if (!strcmp(key, "gdino_mlp_fused")) { ovm::set_gdino_mlp_fused(value); return OVM_OK; }   // plans built afterwards: 0 = fc1 and fc2 as two GEMMs, 1 = Swin blocks fused, 2 = and the encoder's FFN
+  if (!strcmp(key, "gdino_enc_fold")) { ovm::set_gdino_enc_fold(value); return OVM_OK; }     // plans built afterwards: 0 = off, 1 = offsets term folded + no split passes, 2 / 3 = either half
+  if (!strcmp(key, "gdino_enc_tap")) { ovm::set_gdino_enc_tap(value); return OVM_OK; }        // tests; plans built afterwards
   if (!strcmp(key, "gdino_ffn_split")) { ovm::set_gdino_ffn_split(value); return OVM_OK; }   // plans built afterwards: 0 = one workgroup per row block runs the whole FFN
   if (!strcmp(key, "gdino_swin_tap")) { ovm::set_gdino_swin_tap(value); return OVM_OK; }      // tests; plans built afterwards
   if (!strcmp(key, "gdino_swin_fused")) { ovm::set_gdino_swin_fused(value); return OVM_OK; }  // plans built afterwards: 0 = qkv GEMM + window attention as two launches

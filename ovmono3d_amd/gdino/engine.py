@@ -2,6 +2,9 @@
 two-stage selection, decoder - is sequenced inside the library and replayed as one HIP graph per (image size, caption); Python
 only hands over the checkpoint tensors once and, per call, the image descriptor and the caption's token ids.
 
+Plan knobs (``ovm_tune_set`` keys a plan copies when it is built and keeps afterwards): ``gdino_dec_chain``, ``gdino_ffn_split``,
+``gdino_swin_fused``, ``gdino_gemm256``, ``gdino_mlp_fused``, ``gdino_enc_fold`` and the test keys ``gdino_swin_tap`` / ``gdino_enc_tap``.
+
 Replaces ``load_model(...)`` + ``model(image[None], captions=[caption])`` of reference
 cubercnn/modeling/roi_heads/roi_heads_gdino.py:16-23,186."""
 from __future__ import annotations
