@@ -98,23 +98,24 @@ def do_test(args, cfg, model):
         with open(os.path.join(cfg.OUTPUT_DIR, im_name + "_dets.json"), "w") as f:
             json.dump({"K": K.tolist(), "detections": out}, f)
         if vis_on:
-            write_views(im, K, out, kept_idx, cfg.OUTPUT_DIR, im_name)
+            write_views(im, K, out, kept_idx, cfg.OUTPUT_DIR, im_name, gpu_jpeg=bool(cfg.MODEL.AMD.get("GPU_JPEG_WRITE", True)))
 
 
-def write_views(im, K, dets, kept_idx, output_dir, im_name):
-    """demo.py:89-121: the kept boxes drawn (front + novel view, scale = H) into <name>_combine.jpg, else <name>_boxes.jpg."""
-    from PIL import Image
+def write_views(im, K, dets, kept_idx, output_dir, im_name, gpu_jpeg=True):
+    """demo.py:89-121: the kept boxes drawn (front + novel view, scale = H) into <name>_combine.jpg, else <name>_boxes.jpg.
+    gpu_jpeg: a picture on the device is encoded there (data/gpu_jpeg.py write_jpeg; the same bytes as the host's Image.save)."""
     from ovmono3d_amd import vis
+    from ovmono3d_amd.data.gpu_jpeg import write_jpeg
     if len(dets) > 0:
         corners = np.asarray([d["corners3D"] for d in dets], np.float64)
         colors = np.asarray([[c / 255.0 for c in vis.get_color(i)] for i in kept_idx], np.float32)
         text = ["{} {:.2f}".format(d["category"], d["score"]) for d in dets]
         front, novel = vis.draw_scene_view(im, K, corners, colors, text=text, scale=int(im.shape[0]), blend_weight=0.5,
                                            blend_weight_overlay=0.85)
-        bgr, name = vis.concat_views(front, novel).cpu().numpy(), im_name + "_combine.jpg"
+        bgr, name = vis.concat_views(front, novel), im_name + "_combine.jpg"
     else:
-        bgr, name = (im.cpu().numpy() if torch.is_tensor(im) else np.asarray(im)), im_name + "_boxes.jpg"
-    Image.fromarray(np.ascontiguousarray(bgr[:, :, ::-1])).save(os.path.join(output_dir, name), quality=95)
+        bgr, name = im, im_name + "_boxes.jpg"
+    write_jpeg(os.path.join(output_dir, name), bgr, quality=95, channel_order="BGR", use_device=gpu_jpeg)
 
 
 def setup(args):

@@ -150,7 +150,7 @@ int ovm_destroy(OvmHandle* h);
 const char* ovm_last_error(const OvmHandle* h);
 const char* ovm_version(void);
 /* sizeof() of a struct of this header as the library was compiled ("OvmConfig", "OvmTensor", "OvmImage", "OvmDet3D",
- * "OvmGdinoConfig", "OvmJpegInfo", "OvmSceneInput", "OvmSceneLayout", "OvmSceneSegment", "OvmPanelBox", "OvmPanelsInput", "OvmPanelPrim", "OvmPanelsLayout", "OvmEvalCell", "OvmSamConfig", "OvmDepthProConfig"), -1 for an unknown name: lets a binding check its mirror of the layout before the first call. */
+ * "OvmGdinoConfig", "OvmJpegInfo", "OvmJpegEncInfo", "OvmSceneInput", "OvmSceneLayout", "OvmSceneSegment", "OvmPanelBox", "OvmPanelsInput", "OvmPanelPrim", "OvmPanelsLayout", "OvmEvalCell", "OvmSamConfig", "OvmDepthProConfig"), -1 for an unknown name: lets a binding check its mirror of the layout before the first call. */
 int ovm_abi_sizeof(const char* struct_name);
 
 /* --- backbone: build_dino_backbone(...).forward(x, prompt_depth) -> {p2,p3,p4}
@@ -695,6 +695,40 @@ typedef struct OvmJpegInfo {
 int ovm_host_jpeg_info(const uint8_t* data, size_t n, OvmJpegInfo* info);
 int ovm_host_jpeg_entropy_decode(const uint8_t* data, size_t n, int16_t* coef, int64_t coef_capacity, OvmJpegInfo* info);
 int ovm_jpeg_reconstruct(const int16_t* coef, const OvmJpegInfo* info, uint8_t* planes, uint8_t* rgb, ovm_stream_t stream);
+
+/* JPEG encode, entirely on the device: the last step of the two picture paths. The reference hands the finished picture to
+ * cv2.imwrite (demo/demo.py:117-121, <name>_combine.jpg / <name>_boxes.jpg) and to Pillow's Image.save (cubercnn/vis/vis.py:274, the
+ * evaluation samples) - libjpeg-turbo at its defaults either way. Here the uint8 picture stays in HBM and only the compressed file
+ * crosses PCIe; the file is byte for byte the one Pillow's Image.save(f, "JPEG", quality=q[, subsampling=0]) writes.
+ *
+ * ovm_host_jpeg_encode_plan (host, replaces jpeg_set_quality + the marker writer): geometry, the quality-scaled Annex K quantisation
+ * tables and, when header is not null, the header_len bytes in front of the entropy-coded data (SOI, APP0 JFIF 1.01, one DQT per
+ * table, SOF0, DHT x 4, SOS; header_capacity >= 623). subsampling uses Pillow's numbering: 0 = 4:4:4, 2 = 4:2:0.
+ * ovm_jpeg_encode_workspace: the device scratch ovm_jpeg_encode needs and the output capacity header_len + 416 * coef_blocks + 16
+ * (a block emits at most 22 + 63 * 26 = 1660 bits < 208 bytes, at most doubled by byte stuffing).
+ * ovm_jpeg_forward (replaces libjpeg's colour conversion, downsampling, forward DCT and quantisation): img is device uint8 [H][W][3]
+ * in R, G, B order addressed by element strides (sy, sx, sc) - sc may be negative, so a BGR picture is passed as (base + 2, sc = -1);
+ * coef receives int16 [coef_blocks][64] in the layout ovm_jpeg_reconstruct reads; ws needs coef_blocks * 64 bytes here.
+ * ovm_jpeg_encode (replaces Image.save / cv2.imwrite's encoder): the whole file into out, its length into *out_len (both device
+ * memory; header is the host buffer the plan filled). Stream-ordered, no read back inside the call. ws and coef of the two device
+ * calls are 16-byte aligned (else OVM_ERR_INVALID).
+ * Scope: 8-bit baseline, three components YCbCr, luma sampling 2x2 or 1x1, standard Huffman tables, one interleaved scan, no restart
+ * markers. Quality outside 1..100 or a size outside 1..65535 -> OVM_ERR_INVALID; another subsampling -> OVM_ERR_UNSUPPORTED; too small
+ * a workspace or output -> OVM_ERR_CAPACITY (nothing is launched). Not offered: greyscale, 4:2:2 / 4:4:0, progressive and
+ * optimised-Huffman files, custom tables, dpi / EXIF / ICC / comment segments, 12-bit samples. */
+typedef struct OvmJpegEncInfo {
+  int32_t width, height, quality, hs, vs;   /* hs, vs: luma sampling, 2,2 or 1,1 */
+  int32_t bw[3], bh[3];                     /* coefficient plane of each component, in blocks (whole MCUs) */
+  int32_t mcus_x, mcus_y, coef_blocks, header_len;
+  uint16_t qt[2][64];                       /* natural order */
+} OvmJpegEncInfo;
+int ovm_host_jpeg_encode_plan(int32_t width, int32_t height, int32_t quality, int32_t subsampling, OvmJpegEncInfo* info, uint8_t* header,
+                              int32_t header_capacity);
+int ovm_jpeg_encode_workspace(const OvmJpegEncInfo* info, int64_t* ws_bytes, int64_t* out_capacity);
+int ovm_jpeg_forward(const uint8_t* img, int64_t sy, int64_t sx, int64_t sc, const OvmJpegEncInfo* info, uint8_t* ws, int64_t ws_bytes,
+                     int16_t* coef, ovm_stream_t stream);
+int ovm_jpeg_encode(const uint8_t* img, int64_t sy, int64_t sx, int64_t sc, const OvmJpegEncInfo* info, const uint8_t* header, uint8_t* ws,
+                    int64_t ws_bytes, uint8_t* out, int64_t out_capacity, int64_t* out_len, ovm_stream_t stream);
 
 /* ---- Visualisation ----------------------------------------------------------------------------------------------------------
  * draw_scene_view(mode in {front, novel, front_and_novel}) of the reference (cubercnn/vis/vis.py:309-640, edges :673-748, labels

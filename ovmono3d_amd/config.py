@@ -309,6 +309,9 @@ def get_cfg_defaults(cfg: CfgNode) -> CfgNode:
                                  # GPU_JPEG: baseline JPEGs are entropy-decoded on the host and reconstructed on the device (data/gpu_jpeg.py)
                                  # ResizeShortestEdge on the device (bit-identical to the host's Pillow resize)
                                  GPU_RESIZE=True, GPU_JPEG=True,
+                                 # GPU_JPEG_WRITE: <name>_combine.jpg and the --vis-every samples are JPEG-encoded on the device
+                                 # (data/gpu_jpeg.py write_jpeg, the same bytes as Pillow's Image.save); False: host copy + Pillow
+                                 GPU_JPEG_WRITE=True,
                                  # demo.py draws <name>_combine.jpg on the device (ovmono3d_amd/vis); False: detections JSON only
                                  VIS=True))
     return cfg

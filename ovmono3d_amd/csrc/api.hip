@@ -118,6 +118,7 @@ int ovm_abi_sizeof(const char* name) {
   if (n == "OvmDet3D") return (int)sizeof(OvmDet3D);
   if (n == "OvmGdinoConfig") return (int)sizeof(OvmGdinoConfig);
   if (n == "OvmJpegInfo") return (int)sizeof(OvmJpegInfo);
+  if (n == "OvmJpegEncInfo") return (int)sizeof(OvmJpegEncInfo);
   if (n == "OvmSceneInput") return (int)sizeof(OvmSceneInput);
   if (n == "OvmSceneLayout") return (int)sizeof(OvmSceneLayout);
   if (n == "OvmSceneSegment") return (int)sizeof(OvmSceneSegment);

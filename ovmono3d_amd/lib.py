@@ -69,6 +69,15 @@ class OvmJpegInfo(C.Structure):
     ]
 
 
+class OvmJpegEncInfo(C.Structure):
+    """Mirror of include/ovm3d.h OvmJpegEncInfo."""
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32), ("quality", C.c_int32), ("hs", C.c_int32), ("vs", C.c_int32),
+        ("bw", C.c_int32 * 3), ("bh", C.c_int32 * 3), ("mcus_x", C.c_int32), ("mcus_y", C.c_int32), ("coef_blocks", C.c_int32),
+        ("header_len", C.c_int32), ("qt", (C.c_uint16 * 64) * 2),
+    ]
+
+
 OVM_SCENE_MAX_BOXES = 1024
 OVM_SCENE_FRONT, OVM_SCENE_NOVEL = 1, 2
 
@@ -286,6 +295,7 @@ EXPORTS = [
     "ovm_gdino_create", "ovm_gdino_destroy", "ovm_gdino_last_error", "ovm_gdino_forward", "ovm_gdino_detect", "ovm_gdino_set_force_topk",
     "ovm_gdino_debug_copy", "ovm_debug_set_ptr", "ovm_gdino_num_queries", "ovm_gdino_last_outputs", "ovm_infer",
     "ovm_host_jpeg_info", "ovm_host_jpeg_entropy_decode", "ovm_jpeg_reconstruct",
+    "ovm_host_jpeg_encode_plan", "ovm_jpeg_encode_workspace", "ovm_jpeg_forward", "ovm_jpeg_encode",
     "ovm_host_scene_layout", "ovm_render_scene_workspace", "ovm_render_scene",
     "ovm_host_panels_layout", "ovm_render_panels_workspace", "ovm_render_panels",
     "ovm_geo_default_params", "ovm_geo_last_error", "ovm_geo_lift_workspace", "ovm_geo_lift", "ovm_geo_dbscan_workspace", "ovm_geo_dbscan",
@@ -318,7 +328,7 @@ def load() -> C.CDLL:
     lib.ovm_version.restype = C.c_char_p
     lib.ovm_abi_sizeof.argtypes = [C.c_char_p]
     for name, mirror in (("OvmConfig", OvmConfig), ("OvmTensor", OvmTensor), ("OvmImage", OvmImage), ("OvmGdinoConfig", OvmGdinoConfig),
-                         ("OvmJpegInfo", OvmJpegInfo), ("OvmSceneInput", OvmSceneInput), ("OvmSceneLayout", OvmSceneLayout),
+                         ("OvmJpegInfo", OvmJpegInfo), ("OvmJpegEncInfo", OvmJpegEncInfo), ("OvmSceneInput", OvmSceneInput), ("OvmSceneLayout", OvmSceneLayout),
                          ("OvmSceneSegment", OvmSceneSegment), ("OvmPanelBox", OvmPanelBox), ("OvmPanelsInput", OvmPanelsInput),
                          ("OvmPanelPrim", OvmPanelPrim), ("OvmPanelsLayout", OvmPanelsLayout), ("OvmEvalCell", OvmEvalCell), ("OvmGeoParams", OvmGeoParams),
                          ("OvmGeoInstance", OvmGeoInstance), ("OvmGeoResult", OvmGeoResult), ("OvmGeoBox", OvmGeoBox),
@@ -331,6 +341,10 @@ def load() -> C.CDLL:
     lib.ovm_host_jpeg_info.argtypes = [vp, C.c_size_t, C.POINTER(OvmJpegInfo)]
     lib.ovm_host_jpeg_entropy_decode.argtypes = [vp, C.c_size_t, vp, i64, C.POINTER(OvmJpegInfo)]
     lib.ovm_jpeg_reconstruct.argtypes = [vp, C.POINTER(OvmJpegInfo), vp, vp, vp]
+    lib.ovm_host_jpeg_encode_plan.argtypes = [i32, i32, i32, i32, C.POINTER(OvmJpegEncInfo), vp, i32]
+    lib.ovm_jpeg_encode_workspace.argtypes = [C.POINTER(OvmJpegEncInfo), C.POINTER(i64), C.POINTER(i64)]
+    lib.ovm_jpeg_forward.argtypes = [vp, i64, i64, i64, C.POINTER(OvmJpegEncInfo), vp, i64, vp, vp]
+    lib.ovm_jpeg_encode.argtypes = [vp, i64, i64, i64, C.POINTER(OvmJpegEncInfo), vp, vp, i64, vp, i64, vp, vp]
     lib.ovm_host_scene_layout.argtypes = [C.POINTER(OvmSceneInput), C.POINTER(OvmSceneLayout), vp, i32]
     lib.ovm_render_scene_workspace.argtypes = [C.POINTER(OvmSceneLayout), i64, C.POINTER(i64)]
     lib.ovm_render_scene.argtypes = [C.POINTER(OvmSceneLayout), vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]

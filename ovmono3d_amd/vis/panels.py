@@ -111,8 +111,10 @@ def panels_layout(K, height: int, width: int, gt_all: Sequence[Dict], gt_eval: S
 
 
 def render_panels(image_bgr_device: torch.Tensor, K, gt_all: Sequence[Dict], gt_eval: Sequence[bool], preds: Sequence[Dict], *,
-                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """The six-panel mosaic of one image, device uint8 [2H, 3W, 3] (BGR).
+                  out: Optional[torch.Tensor] = None, save_path: Optional[str] = None, gpu_jpeg: bool = True) -> torch.Tensor:
+    """The six-panel mosaic of one image, device uint8 [2H, 3W, 3] (BGR). save_path: the mosaic is also written there as a JPEG of
+    quality 95 (:274); gpu_jpeg: encoded on the device (data/gpu_jpeg.py write_jpeg), else copied to the host and saved with Pillow -
+    the same bytes either way.
 
     image_bgr_device: device uint8 [H, W, 3] (rows may be pitched). gt_all / preds: one dict per box with ``bbox`` (xywh),
     ``center_cam``, ``dimensions`` (w, h, l), ``pose`` (3 x 3), ``category_id`` (its colour, or ``color``), ``name`` and, optionally,
@@ -143,6 +145,9 @@ def render_panels(image_bgr_device: torch.Tensor, K, gt_all: Sequence[Dict], gt_
                                  img.stride(0), out.data_ptr(), out.stride(0), ws.data_ptr(), ws.numel(),
                                  C.c_void_p(stream.cuda_stream))
         _lib.check(rc, what="ovm_render_panels")
+        if save_path is not None:
+            from ..data.gpu_jpeg import write_jpeg
+            write_jpeg(save_path, out, quality=95, channel_order="BGR", use_device=gpu_jpeg)
     return out
 
 
@@ -235,7 +240,8 @@ def _mean(v: Sequence[float]) -> float:
 
 
 def visualize_from_instances(detections, dataset, dataset_name, min_size_test, output_folder, category_names_official,
-                             prompted_category_names, iteration="", *, every: int = 50, fork_compat: bool = False, device=None) -> str:
+                             prompted_category_names, iteration="", *, every: int = 50, fork_compat: bool = False, device=None,
+                             gpu_jpeg: bool = True) -> str:
     """Writes ``<output_folder>/vis/<dataset_name>_<imind:06d>.jpg`` for the images with ``imind % every == 0`` and returns the
     reference's log line ``<dataset_name>iter=<iteration>, xy(..), z(..), whl(.., .., ..), ry(..)``.
 
@@ -243,7 +249,8 @@ def visualize_from_instances(detections, dataset, dataset_name, min_size_test, o
     ry is the geodesic angle acos(clip((trace - 1) / 2, -1, 1)) (upstream Cube R-CNN). ``fork_compat=True``: over the sampled images
     only and ry = pi / 2 - (trace - 1) / 2, the pair dropped when the trace is outside [-1 - 1e-4, 3 + 1e-4] (what pytorch3d's
     ``so3_relative_angle(..., cos_bound=1)`` computes, read from its source; parity unpinned). ``device``: where the panels are drawn
-    (default: the current HIP device); without sampled images the GPU is not touched.
+    (default: the current HIP device); without sampled images the GPU is not touched. ``gpu_jpeg``: the samples are encoded on the
+    device (``write_jpeg``); False: copied to the host and saved with Pillow, as the reference does - the files are the same.
     """
     vis_folder = os.path.join(output_folder, "vis")
     os.makedirs(vis_folder, exist_ok=True)
@@ -269,10 +276,8 @@ def visualize_from_instances(detections, dataset, dataset_name, min_size_test, o
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         im = read_image_device(data_obj["file_name"], "BGR", dev)
         K, gt_all, gt_eval, preds = panel_boxes(im_obj, annos, category_names_official, prompted_category_names)
-        mosaic = render_panels(im, K, gt_all, gt_eval, preds)
-        from PIL import Image
-        Image.fromarray(np.ascontiguousarray(mosaic.cpu().numpy()[:, :, ::-1])).save(
-            os.path.join(vis_folder, f"{dataset_name}_{imind:06d}.jpg"), quality=95)
+        render_panels(im, K, gt_all, gt_eval, preds, save_path=os.path.join(vis_folder, f"{dataset_name}_{imind:06d}.jpg"),
+                      gpu_jpeg=gpu_jpeg)
     ry = errs[5] if len(errs[5]) else [1000, 1000]               # :286-287
     return dataset_name + "iter={}, xy({:.2f}), z({:.2f}), whl({:.2f}, {:.2f}, {:.2f}), ry({:.2f})\n".format(
         iteration, _mean(errs[0]), _mean(errs[1]), _mean(errs[2]), _mean(errs[3]), _mean(errs[4]), _mean(ry))

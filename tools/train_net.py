@@ -118,7 +118,7 @@ def do_test(cfg, model, mode="base", datasets_root="datasets/Omni3D", image_root
                     logger.info(vis.visualize_from_instances(
                         results, vis.SampleDataset.from_ground_truth(dicts, gt, cmap), name, cfg.INPUT.MIN_SIZE_TEST,
                         os.path.join(out_dir, name), cmap.thing_classes, gt.category_names, "final", every=vis_every,
-                        fork_compat=vis_fork_compat))
+                        fork_compat=vis_fork_compat, gpu_jpeg=bool(cfg.MODEL.AMD.get("GPU_JPEG_WRITE", True))))
 
 
     if get_rank() == 0 and len(all_files) > 1:
