@@ -57,9 +57,10 @@ def do_test(args, cfg, model):
         cats = cats_per_img.get(im_name, [])
         if cats == []:
             continue
-        if gpu_jpeg:                                                         # baseline JPEG: host entropy decode, pixels born on the device
+        if gpu_jpeg:                                                         # JPEG: entropy decode on the host or, with GPU_JPEG_ENTROPY, on the device; pixels born on the device
             from ovmono3d_amd.data.gpu_jpeg import read_image_device
-            im = read_image_device(os.path.join(args.input_folder, name), "BGR", torch.device("cuda"))
+            im = read_image_device(os.path.join(args.input_folder, name), "BGR", torch.device("cuda"),
+                                   entropy="device" if bool(cfg.MODEL.AMD.get("GPU_JPEG_ENTROPY", False)) else "host")
         else:
             im = read_image(os.path.join(args.input_folder, name), "BGR")   # cv2.imread order, demo.py:52
         h, w = im.shape[:2]

@@ -150,7 +150,7 @@ int ovm_destroy(OvmHandle* h);
 const char* ovm_last_error(const OvmHandle* h);
 const char* ovm_version(void);
 /* sizeof() of a struct of this header as the library was compiled ("OvmConfig", "OvmTensor", "OvmImage", "OvmDet3D",
- * "OvmGdinoConfig", "OvmJpegInfo", "OvmJpegEncInfo", "OvmSceneInput", "OvmSceneLayout", "OvmSceneSegment", "OvmPanelBox", "OvmPanelsInput", "OvmPanelPrim", "OvmPanelsLayout", "OvmEvalCell", "OvmSamConfig", "OvmDepthProConfig"), -1 for an unknown name: lets a binding check its mirror of the layout before the first call. */
+ * "OvmGdinoConfig", "OvmJpegInfo", "OvmJpegEncInfo", "OvmJpegDecPlan", "OvmSceneInput", "OvmSceneLayout", "OvmSceneSegment", "OvmPanelBox", "OvmPanelsInput", "OvmPanelPrim", "OvmPanelsLayout", "OvmEvalCell", "OvmSamConfig", "OvmDepthProConfig"), -1 for an unknown name: lets a binding check its mirror of the layout before the first call. */
 int ovm_abi_sizeof(const char* struct_name);
 
 /* --- backbone: build_dino_backbone(...).forward(x, prompt_depth) -> {p2,p3,p4}
@@ -671,7 +671,7 @@ int ovm_resize_bilinear_u8(const uint8_t* src, int32_t H, int32_t W, int32_t C, 
  * - detectron2's ResizeTransform takes this route for non-uint8 arrays). src [B][H][W] dense, dst [B][outH][outW], device. */
 int ovm_resize_bilinear_f32(const float* src, int32_t B, int32_t H, int32_t W, int32_t outH, int32_t outW, float* dst, ovm_stream_t stream);
 
-/* JPEG decode split at its only serial step. The reference reads images with cv2.imread (demo/demo.py:52) and detectron2's
+/* JPEG decode split behind its entropy stage. The reference reads images with cv2.imread (demo/demo.py:52) and detectron2's
  * read_image = Pillow (cubercnn/data/dataset_mapper.py:38), both libjpeg-turbo at its defaults (JDCT_ISLOW, fancy upsampling,
  * integer YCbCr -> RGB). ovm_host_jpeg_info walks the headers; ovm_host_jpeg_entropy_decode Huffman-decodes every scan on the
  * host into coefficient planes (int16 [coef_blocks][64] in natural order, component after component, each plane bw x bh blocks =
@@ -695,6 +695,54 @@ typedef struct OvmJpegInfo {
 int ovm_host_jpeg_info(const uint8_t* data, size_t n, OvmJpegInfo* info);
 int ovm_host_jpeg_entropy_decode(const uint8_t* data, size_t n, int16_t* coef, int64_t coef_capacity, OvmJpegInfo* info);
 int ovm_jpeg_reconstruct(const int16_t* coef, const OvmJpegInfo* info, uint8_t* planes, uint8_t* rgb, ovm_stream_t stream);
+
+/* The entropy stage on the device: a second route to the coefficient planes, for which only the file's bytes cross PCIe. Huffman
+ * streams resynchronise: a decoder started at a wrong bit falls in step with the true one after a few symbols, so the unstuffed
+ * stream is cut into subsequences of sub_bits bits, one thread each, whose entry states (bit, block of the MCU, zig-zag index) are
+ * relaxed - entry of i + 1 := exit of i - until none changes (csrc/jpeg_dec.hip; the decoding rules are jpeg_dec_core.hpp, shared
+ * with the host). The result is int16 [coef_blocks][64], bit for bit what ovm_host_jpeg_entropy_decode writes, for
+ * ovm_jpeg_reconstruct to read.
+ * Scope: 8-bit Huffman SOF0 / SOF1 with exactly one scan that carries all components in frame order (grey; YCbCr or RGB at 4:4:4,
+ * 4:2:2, 4:2:0), standard or optimised tables, with or without restart intervals, EOI right behind the scan. For anything else
+ * ovm_host_jpeg_decode_plan returns what ovm_host_jpeg_info returns, or OVM_ERR_UNSUPPORTED: the file takes the host route.
+ * The device accepts only what it can prove: result[0] (status, a device word) is 0 only when the marker sequence was the frame's,
+ * the entry states reached their fixed point within the rounds allowed, every restart segment completed exactly its blocks inside
+ * its own bits (which covers invalid codes, coefficients past index 63 and cut data) and every DC predictor stayed within the
+ * host's [-65536, 65535]; the bits are OVM_JPEG_DEC_*. On a non-zero status the planes are undefined and the caller runs the host
+ * decoder on the same bytes, which accepts or refuses as it always did: the device never calls a file invalid, it only declines.
+ * result[1] = relaxation rounds used: the sum over the sync_launches launches of the largest step count of any workgroup;
+ * result[2] = launches in which any thread decoded (at most sync_launches - 1 for an accepted file: a clean launch must follow the
+ * last productive one). result is three device words.
+ * ovm_host_jpeg_decode_plan: geometry, the scan's byte range ecs_offset / ecs_bytes within the file, table selectors per block of
+ * the MCU, and the Huffman tables in the kernels' form into tables (tables_capacity >= tables_bytes = 11008, else
+ * OVM_ERR_CAPACITY). max_rounds <= 0: the default (256 = wg_subs, at which a workgroup is certainly consistent).
+ * ovm_jpeg_entropy_decode: stream = the ecs_bytes bytes (device, any alignment), tables = the plan's table block (device, 16-byte
+ * aligned), ws (16-byte aligned, size from ovm_jpeg_entropy_decode_workspace), coef (16-byte aligned, coef_capacity >=
+ * coef_blocks * 64 elements). Stream-ordered, no read back inside; too small a buffer -> OVM_ERR_CAPACITY, nothing launched.
+ * ovm_host_jpeg_entropy_emulate: the same stages, rounds schedule and core routine run serially on the CPU (status, rounds and - launches may be null - productive launches as
+ * the device reports them): the algorithm's test bed on a machine without a GPU. Returns the plan's code when the plan declines. */
+#define OVM_JPEG_DEC_MARKER 1    /* an 0xFF followed by neither 0x00 nor the RSTn that is due */
+#define OVM_JPEG_DEC_SEGMENTS 2  /* restart-segment count differs from the frame's, or an empty segment */
+#define OVM_JPEG_DEC_NOSYNC 4    /* synchronisation did not converge within the rounds allowed */
+#define OVM_JPEG_DEC_COUNT 8     /* a segment completed another number of blocks than the frame needs */
+#define OVM_JPEG_DEC_BADCODE 16  /* invalid Huffman code or DC category > 11 */
+#define OVM_JPEG_DEC_ZIGZAG 32   /* coefficient at zig-zag index > 63 */
+#define OVM_JPEG_DEC_DCRANGE 64  /* DC predictor outside [-65536, 65535] */
+typedef struct OvmJpegDecPlan {
+  OvmJpegInfo info;
+  int64_t ecs_offset, ecs_bytes;            /* the entropy-coded segment within the file (stuffed, with its RSTn markers) */
+  int32_t restart_interval;                 /* MCUs per restart segment as the file's DRI states it, 0 = none */
+  int32_t mcus_x, mcus_y, blocks_per_mcu, segments;
+  int32_t sub_bits, wg_subs, sync_launches, max_rounds;
+  int32_t tables_bytes;
+  uint8_t sel_comp[8], sel_sub[8], sel_dc[8], sel_ac[8];   /* per block of the MCU: component, index in its h x v, DC / AC table */
+} OvmJpegDecPlan;
+int ovm_host_jpeg_decode_plan(const uint8_t* data, size_t n, int32_t max_rounds, OvmJpegDecPlan* plan, uint8_t* tables, int64_t tables_capacity);
+int ovm_jpeg_entropy_decode_workspace(const OvmJpegDecPlan* plan, int64_t* ws_bytes);
+int ovm_jpeg_entropy_decode(const uint8_t* stream, const uint8_t* tables, const OvmJpegDecPlan* plan, uint8_t* ws, int64_t ws_bytes,
+                            int16_t* coef, int64_t coef_capacity, int32_t* result, ovm_stream_t stream_handle);
+int ovm_host_jpeg_entropy_emulate(const uint8_t* data, size_t n, int32_t max_rounds, int16_t* coef, int64_t coef_capacity,
+                                  OvmJpegInfo* info, int32_t* status, int32_t* rounds, int32_t* launches);
 
 /* JPEG encode, entirely on the device: the last step of the two picture paths. The reference hands the finished picture to
  * cv2.imwrite (demo/demo.py:117-121, <name>_combine.jpg / <name>_boxes.jpg) and to Pillow's Image.save (cubercnn/vis/vis.py:274, the

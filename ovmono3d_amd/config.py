@@ -309,6 +309,9 @@ def get_cfg_defaults(cfg: CfgNode) -> CfgNode:
                                  # GPU_JPEG: baseline JPEGs are entropy-decoded on the host and reconstructed on the device (data/gpu_jpeg.py)
                                  # ResizeShortestEdge on the device (bit-identical to the host's Pillow resize)
                                  GPU_RESIZE=True, GPU_JPEG=True,
+                                 # GPU_JPEG_ENTROPY: the Huffman decode of such a file runs on the device too, only the file's bytes are
+                                 # uploaded (gpu_jpeg.entropy_decode_device); a file the device route declines is decoded by the host as before
+                                 GPU_JPEG_ENTROPY=False,
                                  # GPU_JPEG_WRITE: <name>_combine.jpg and the --vis-every samples are JPEG-encoded on the device
                                  # (data/gpu_jpeg.py write_jpeg, the same bytes as Pillow's Image.save); False: host copy + Pillow
                                  GPU_JPEG_WRITE=True,

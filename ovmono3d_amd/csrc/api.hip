@@ -119,6 +119,7 @@ int ovm_abi_sizeof(const char* name) {
   if (n == "OvmGdinoConfig") return (int)sizeof(OvmGdinoConfig);
   if (n == "OvmJpegInfo") return (int)sizeof(OvmJpegInfo);
   if (n == "OvmJpegEncInfo") return (int)sizeof(OvmJpegEncInfo);
+  if (n == "OvmJpegDecPlan") return (int)sizeof(OvmJpegDecPlan);
   if (n == "OvmSceneInput") return (int)sizeof(OvmSceneInput);
   if (n == "OvmSceneLayout") return (int)sizeof(OvmSceneLayout);
   if (n == "OvmSceneSegment") return (int)sizeof(OvmSceneSegment);

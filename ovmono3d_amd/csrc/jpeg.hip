@@ -1,9 +1,9 @@
-// Data feeding on the device ("next" row 2 of SURVEY.md 8f): JPEG decode split at the only serial step.
+// Data feeding on the device ("next" row 2 of SURVEY.md 8f): JPEG decode split behind its entropy stage.
 //
 // The reference reads its images with cv2.imread (demo/demo.py:52) / detectron2's read_image = Pillow
 // (cubercnn/data/dataset_mapper.py:38), i.e. with libjpeg-turbo at its defaults: JDCT_ISLOW, fancy upsampling, YCbCr -> RGB through
-// the integer tables of jdcolor.c. A baseline JPEG is (1) a Huffman-coded stream of quantised DCT coefficients - inherently serial,
-// decoded here on the host (`ovm_host_jpeg_entropy_decode`, jpeg_host.hpp; progressive files add their scans' bands and bit planes to the same coefficient planes) - and (2) dequantisation, an 8 x 8 inverse DCT per block, chroma
+// the integer tables of jdcolor.c. A baseline JPEG is (1) a Huffman-coded stream of quantised DCT coefficients -
+// decoded on the host (`ovm_host_jpeg_entropy_decode`, jpeg_host.hpp; or on the device for single-scan files, jpeg_dec.hip; progressive files add their scans' bands and bit planes to the same coefficient planes) - and (2) dequantisation, an 8 x 8 inverse DCT per block, chroma
 // upsampling and a colour transform per pixel - data parallel, all integer arithmetic, done here on the device
 // (`ovm_jpeg_reconstruct`) so that the image is born in HBM as the [H][W][3] uint8 tensor the resize kernel (resize.hip) and the
 // patch gather consume; what crosses PCIe is the coefficient planes (int16, mostly zero).

@@ -2,7 +2,7 @@
 //
 // The reference writes its pictures with cv2.imwrite / Pillow's Image.save (demo/demo.py:117 <name>_combine.jpg, cubercnn/vis/vis.py:274
 // the evaluation samples), i.e. with libjpeg-turbo at its defaults: JDCT_ISLOW, the Annex K tables scaled by the quality, 4:2:0, the
-// standard Huffman tables, one interleaved scan. Unlike the decode (jpeg.hip), the encode has no serial step: colour transform, chroma
+// standard Huffman tables, one interleaved scan. The encode needs no synchronisation of guessed states as the decode's entropy stage does (jpeg_dec.hip): colour transform, chroma
 // downsampling, forward DCT and quantisation are integer arithmetic per 8 x 8 block, and Huffman coding becomes parallel once every
 // block's bit length is known - an exclusive prefix sum gives each block its bit offset. So the finished uint8 picture never leaves
 // the device; what crosses PCIe is the compressed file. The file is byte for byte the one Pillow writes (the live oracle of

@@ -106,12 +106,13 @@ class DatasetMapper3D:
             self.gpu_depth_resize = DepthPromptResizeGPU(cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST)
         # baseline JPEGs reconstructed on the device from host-decoded coefficients (gpu_jpeg.py; bit-identical to the Pillow read)
         self.gpu_jpeg = self.gpu_resize is not None and bool(cfg.MODEL.AMD.get("GPU_JPEG", False))
+        self.jpeg_entropy = "device" if bool(cfg.MODEL.AMD.get("GPU_JPEG_ENTROPY", False)) else "host"
 
     def __call__(self, d: Dict) -> Dict:
         d = dict(d)
         if self.gpu_jpeg:
             from .gpu_jpeg import read_image_device
-            image = read_image_device(d["file_name"], self.image_format, torch.device("cuda"))      # uint8 [H, W, 3] in HBM
+            image = read_image_device(d["file_name"], self.image_format, torch.device("cuda"), entropy=self.jpeg_entropy)      # uint8 [H, W, 3] in HBM
         else:
             image = read_image(d["file_name"], self.image_format)
         depth = None

@@ -78,6 +78,17 @@ class OvmJpegEncInfo(C.Structure):
     ]
 
 
+class OvmJpegDecPlan(C.Structure):
+    """Mirror of include/ovm3d.h OvmJpegDecPlan."""
+    _fields_ = [
+        ("info", OvmJpegInfo), ("ecs_offset", C.c_int64), ("ecs_bytes", C.c_int64), ("restart_interval", C.c_int32),
+        ("mcus_x", C.c_int32), ("mcus_y", C.c_int32), ("blocks_per_mcu", C.c_int32), ("segments", C.c_int32),
+        ("sub_bits", C.c_int32), ("wg_subs", C.c_int32), ("sync_launches", C.c_int32), ("max_rounds", C.c_int32),
+        ("tables_bytes", C.c_int32), ("sel_comp", C.c_uint8 * 8), ("sel_sub", C.c_uint8 * 8), ("sel_dc", C.c_uint8 * 8),
+        ("sel_ac", C.c_uint8 * 8),
+    ]
+
+
 OVM_SCENE_MAX_BOXES = 1024
 OVM_SCENE_FRONT, OVM_SCENE_NOVEL = 1, 2
 
@@ -295,6 +306,7 @@ EXPORTS = [
     "ovm_gdino_create", "ovm_gdino_destroy", "ovm_gdino_last_error", "ovm_gdino_forward", "ovm_gdino_detect", "ovm_gdino_set_force_topk",
     "ovm_gdino_debug_copy", "ovm_debug_set_ptr", "ovm_gdino_num_queries", "ovm_gdino_last_outputs", "ovm_infer",
     "ovm_host_jpeg_info", "ovm_host_jpeg_entropy_decode", "ovm_jpeg_reconstruct",
+    "ovm_host_jpeg_decode_plan", "ovm_jpeg_entropy_decode_workspace", "ovm_jpeg_entropy_decode", "ovm_host_jpeg_entropy_emulate",
     "ovm_host_jpeg_encode_plan", "ovm_jpeg_encode_workspace", "ovm_jpeg_forward", "ovm_jpeg_encode",
     "ovm_host_scene_layout", "ovm_render_scene_workspace", "ovm_render_scene",
     "ovm_host_panels_layout", "ovm_render_panels_workspace", "ovm_render_panels",
@@ -328,7 +340,7 @@ def load() -> C.CDLL:
     lib.ovm_version.restype = C.c_char_p
     lib.ovm_abi_sizeof.argtypes = [C.c_char_p]
     for name, mirror in (("OvmConfig", OvmConfig), ("OvmTensor", OvmTensor), ("OvmImage", OvmImage), ("OvmGdinoConfig", OvmGdinoConfig),
-                         ("OvmJpegInfo", OvmJpegInfo), ("OvmJpegEncInfo", OvmJpegEncInfo), ("OvmSceneInput", OvmSceneInput), ("OvmSceneLayout", OvmSceneLayout),
+                         ("OvmJpegInfo", OvmJpegInfo), ("OvmJpegEncInfo", OvmJpegEncInfo), ("OvmJpegDecPlan", OvmJpegDecPlan), ("OvmSceneInput", OvmSceneInput), ("OvmSceneLayout", OvmSceneLayout),
                          ("OvmSceneSegment", OvmSceneSegment), ("OvmPanelBox", OvmPanelBox), ("OvmPanelsInput", OvmPanelsInput),
                          ("OvmPanelPrim", OvmPanelPrim), ("OvmPanelsLayout", OvmPanelsLayout), ("OvmEvalCell", OvmEvalCell), ("OvmGeoParams", OvmGeoParams),
                          ("OvmGeoInstance", OvmGeoInstance), ("OvmGeoResult", OvmGeoResult), ("OvmGeoBox", OvmGeoBox),
@@ -341,6 +353,10 @@ def load() -> C.CDLL:
     lib.ovm_host_jpeg_info.argtypes = [vp, C.c_size_t, C.POINTER(OvmJpegInfo)]
     lib.ovm_host_jpeg_entropy_decode.argtypes = [vp, C.c_size_t, vp, i64, C.POINTER(OvmJpegInfo)]
     lib.ovm_jpeg_reconstruct.argtypes = [vp, C.POINTER(OvmJpegInfo), vp, vp, vp]
+    lib.ovm_host_jpeg_decode_plan.argtypes = [vp, C.c_size_t, i32, C.POINTER(OvmJpegDecPlan), vp, i64]
+    lib.ovm_jpeg_entropy_decode_workspace.argtypes = [C.POINTER(OvmJpegDecPlan), C.POINTER(i64)]
+    lib.ovm_jpeg_entropy_decode.argtypes = [vp, vp, C.POINTER(OvmJpegDecPlan), vp, i64, vp, i64, vp, vp]
+    lib.ovm_host_jpeg_entropy_emulate.argtypes = [vp, C.c_size_t, i32, vp, i64, C.POINTER(OvmJpegInfo), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     lib.ovm_host_jpeg_encode_plan.argtypes = [i32, i32, i32, i32, C.POINTER(OvmJpegEncInfo), vp, i32]
     lib.ovm_jpeg_encode_workspace.argtypes = [C.POINTER(OvmJpegEncInfo), C.POINTER(i64), C.POINTER(i64)]
     lib.ovm_jpeg_forward.argtypes = [vp, i64, i64, i64, C.POINTER(OvmJpegEncInfo), vp, i64, vp, vp]
