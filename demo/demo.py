@@ -14,6 +14,13 @@ when no detection is kept. ``MODEL.AMD.VIS False`` writes the JSON only.
 (groundingdino_swinb_cogcoor.pth: Swin-B, groundingdino_swint_ogc.pth: Swin-T) is read off the checkpoint's tensors. Alternatives:
 ``--boxes-file`` with oracle-2D boxes ({image name: [{bbox xywh, category_id, score}]}), or the default
 ``MODEL.ROI_HEADS.NAME ROIHeads3D`` = the RPN + box-head path.
+
+Depth prompt (native build; the reference's demo never passes one, so a checkpoint trained with ``MODEL.DINO.USE_DEPTH_FUSION`` runs
+un-fused there - its debug.md:19): ``--depth none`` (default) is that behaviour; ``--depth depthpro --depthpro-weights FILE`` computes the
+prompt on the device from the image itself (Depth Pro, ``ovmono3d_amd.depthpro``; ``--dump-depth DIR`` also writes it as
+``<DIR>/<name>.npz``); ``--depth files --depth-dir DIR`` reads ``<DIR>/test/<name>.npz`` or ``<DIR>/<name>.npz`` and ends the run naming
+the image whose file is missing. Either way the map goes through ``data/depth_prompt.py prepare_prompt_depth``, the resizes of the
+evaluation's mapper, into ``model([d], prompt_depth=...)``.
 """
 import argparse
 import json
@@ -27,6 +34,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from ovmono3d_amd.checkpoint import DetectionCheckpointer  # noqa: E402
 from ovmono3d_amd.data import ResizeShortestEdge, read_image  # noqa: E402
+from ovmono3d_amd.data.depth_prompt import (add_depth_arguments, build_depth_prompt, check_depth_arguments, load_depth,  # noqa: E402
+                                            prepare_prompt_depth)
 from ovmono3d_amd.defaults import make_cfg  # noqa: E402
 from ovmono3d_amd.modeling import build_model  # noqa: E402
 
@@ -50,6 +59,12 @@ def do_test(args, cfg, model):
         from ovmono3d_amd.data.gpu_resize import ResizeShortestEdgeGPU
         gpu_resize = ResizeShortestEdgeGPU(cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST)
     gpu_jpeg = gpu_resize is not None and bool(cfg.MODEL.AMD.get("GPU_JPEG", False))
+    depth_source, depth_resize = None, resize
+    if args.depth != "none" and gpu_resize is not None:
+        from ovmono3d_amd.data.gpu_resize import DepthPromptResizeGPU
+        depth_resize = DepthPromptResizeGPU(cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST)
+    if args.depth == "depthpro":
+        depth_source = build_depth_prompt(args.depthpro_weights, args.depthpro_focal, args.depthpro_config, args.dump_depth, torch.device("cuda"))
     use_gdino_head = cfg.MODEL.ROI_HEADS.NAME == "ROIHeads3DGDINO"
     vis_on = bool(cfg.MODEL.AMD.get("VIS", True))
     for name in ims:
@@ -81,7 +96,14 @@ def do_test(args, cfg, model):
                              "gt_scores": torch.tensor([b.get("score", 1.0) for b in inst], dtype=torch.float32)}
         elif use_gdino_head:
             d["category_list"] = cats
-        dets = model([d])[0]["instances"]
+        prompt_depth = None
+        if args.depth == "depthpro":                                         # Depth Pro on the image the demo already holds
+            prompt_depth = depth_source(im, "BGR", K, file_name=name)
+        elif args.depth == "files":
+            prompt_depth = load_depth(args.depth_dir, name)
+        if prompt_depth is not None:
+            prompt_depth = prepare_prompt_depth(prompt_depth, (h, w), depth_resize)[None]
+        dets = model([d], prompt_depth=prompt_depth)[0]["instances"]
         n_det = len(dets) if dets.get_fields() else 0
         out, kept_idx = [], []
         if n_det > 0 and dets.has("pred_bbox3D"):
@@ -140,6 +162,8 @@ if __name__ == "__main__":
     parser.add_argument("--focal-length", type=float, default=0, help="focal length for image inputs (in px)")
     parser.add_argument("--principal-point", type=float, default=[], nargs=2, help="principal point for image inputs (in px)")
     parser.add_argument("--threshold", type=float, default=0.25, help="threshold on score for visualizing")
+    add_depth_arguments(parser, choices=("none", "files", "depthpro"), default="none",
+                        focal_help="the K[0][0] of this run: --focal-length, or without it the reference's convention 4.0 * h / 2 of the first image")
     parser.add_argument("--display", default=False, action="store_true", help="no-op: there is no GUI on the target (the views are written to <name>_combine.jpg)")
     parser.add_argument("--eval-only", default=True, action="store_true", help="perform evaluation only")
     parser.add_argument("--num-gpus", type=int, default=1, help="number of gpus *per machine*")
@@ -149,5 +173,6 @@ if __name__ == "__main__":
     parser.add_argument("opts", default=None, nargs=argparse.REMAINDER,
                         help="Modify config options by adding 'KEY VALUE' pairs at the end of the command.")
     args = parser.parse_args()
+    check_depth_arguments(args, parser, lambda: setup(args), files_need_dir=True)          # exit status 2 before any device call
     print("Command Line Args:", args)
     main(args)

@@ -441,6 +441,16 @@ int ovm_infer(OvmHandle* h, OvmGdino* g, const OvmImage* image, const int32_t* t
               int32_t n_phrases, float box_threshold, float nms_threshold, OvmDet3D* out, int32_t out_capacity, int32_t* n_out,
               ovm_stream_t stream);
 
+/* ovm_infer with a depth prompt: RCNN3D.forward(batched_inputs, prompt_depth) of the reference (rcnn3d.py:41,97: the backbone call
+ * becomes self.backbone(images.tensor, prompt_depth), dino.py:82-105 - the metric depth map, resized to the patch grid, concatenated
+ * to the last block's patch tokens and run through depth_fusion). prompt_depth: device fp32 [1][1][depth_h][depth_w] as for
+ * ovm_backbone_forward, read on the caller's stream, or NULL, which is ovm_infer. The refusals of ovm_backbone_forward for a prompt
+ * (a tower other than DINOv2, a register-token model, absent depth_fusion weights: OVM_ERR_INVALID with a message) are returned
+ * before anything is launched or forked; the handle stays usable. Every other argument, the kernels and their order as ovm_infer. */
+int ovm_infer_depth(OvmHandle* h, OvmGdino* g, const OvmImage* image, const float* prompt_depth, int32_t depth_h, int32_t depth_w,
+                    const int32_t* token_ids, int32_t ntok, const int32_t* spans, int32_t n_phrases, float box_threshold,
+                    float nms_threshold, OvmDet3D* out, int32_t out_capacity, int32_t* n_out, ovm_stream_t stream);
+
 /* --- generic device ops the GroundingDINO branch (ROIHeads3DGDINO's network, reference roi_heads_gdino.py:186) is
  * was sequenced from in round 1 (still exported: unit tests and the Python-sequenced cross-check path use them): fp32
  * row-major tensors in HBM, one call per op, all arithmetic on the device. */

@@ -325,6 +325,24 @@ static int convt_up(OvmHandle* h, const SplitImg& in, int Cin, int Bn, int Gs, c
   return OVM_OK;
 }
 
+// The depth prompts a handle cannot take (ovm_backbone_forward, ovm_infer_depth): sets the message, launches nothing.
+static int depth_prompt_refusal(OvmHandle* h, const float* prompt_depth, int depth_h, int depth_w) {
+  if (!prompt_depth) return OVM_OK;
+  if (h->cfg.tower != OVM_TOWER_DINOV2) {
+    // detectron2's SimpleFeaturePyramid.forward(x) takes no depth; the fork's RCNN3D passes one to every backbone and
+    // would raise a TypeError here (SURVEY.md 0.4): refuse rather than silently drop it
+    h->err = "prompt_depth is only defined for the DINOv2 tower (depth_fusion, dino.py:91-105)"; return OVM_ERR_INVALID;
+  }
+  if (h->tw.nreg) {
+    // the reference's fusion takes x[:, 1:] as the patch tokens (dino.py:91-105): with register tokens its torch.cat of [B, C, R + HW]
+    // with the [B, 1, HW] depth raises
+    h->err = "prompt_depth is not defined for a register-token model (depth fusion takes x[:, 1:] as the patch tokens, dino.py:91-105)"; return OVM_ERR_INVALID;
+  }
+  if (!h->has_dfuse) { h->err = "prompt_depth given but depth_fusion weights absent / disabled"; return OVM_ERR_INVALID; }
+  if (depth_h < 1 || depth_w < 1) { h->err = "prompt_depth needs depth_h >= 1 and depth_w >= 1"; return OVM_ERR_INVALID; }
+  return OVM_OK;
+}
+
 int ovm_backbone_forward(OvmHandle* h, const OvmImage* images, int32_t B, const float* prompt_depth, int32_t depth_h,
                          int32_t depth_w, float* p2, float* p3, float* p4, ovm_stream_t stream) {
   if (!h) return OVM_ERR_INVALID;
@@ -341,17 +359,7 @@ int ovm_backbone_forward(OvmHandle* h, const OvmImage* images, int32_t B, const 
   if (const int r = from_tower(h, h->tw.stage_images(images, B, s))) return r;
   OVM_HIP(h, hipMemcpyAsync(h->d_meta, h->h_meta, sizeof(ImageMeta) * B, hipMemcpyHostToDevice, s));
   h->lastB = B;
-  if (prompt_depth && c.tower != OVM_TOWER_DINOV2) {
-    // detectron2's SimpleFeaturePyramid.forward(x) takes no depth; the fork's RCNN3D passes one to every backbone and
-    // would raise a TypeError here (SURVEY.md 0.4): refuse rather than silently drop it
-    h->err = "prompt_depth is only defined for the DINOv2 tower (depth_fusion, dino.py:91-105)"; return OVM_ERR_INVALID;
-  }
-  if (prompt_depth && h->tw.nreg) {
-    // the reference's fusion takes x[:, 1:] as the patch tokens (dino.py:91-105): with register tokens its torch.cat of [B, C, R + HW]
-    // with the [B, 1, HW] depth raises
-    h->err = "prompt_depth is not defined for a register-token model (depth fusion takes x[:, 1:] as the patch tokens, dino.py:91-105)"; return OVM_ERR_INVALID;
-  }
-  if (prompt_depth && !h->has_dfuse) { h->err = "prompt_depth given but depth_fusion weights absent / disabled"; return OVM_ERR_INVALID; }
+  if (const int r = depth_prompt_refusal(h, prompt_depth, depth_h, depth_w)) return r;
   const int rr = backbone_launches(h, B, prompt_depth, depth_h, depth_w, s);
   if (rr) return rr;
   const int C = h->C;
@@ -497,9 +505,9 @@ int ovm_rpn_box_forward(OvmHandle* h, const OvmImage* images, int32_t B, float* 
 // before the output glue. One host synchronisation (the number of kept 2D boxes sizes the cube-head launch).
 // Everything of ovm_infer behind its argument checks: fork, the two networks, join, glue, cube head. Split off so that EVERY error exit
 // (a failed detector or backbone launch, an allocation, the capacity check) passes through one place that drains both streams.
-static int infer_forked(OvmHandle* h, OvmGdino* g, const OvmImage* image, const int32_t* token_ids, int32_t ntok, const int32_t* spans,
-                        int32_t n_phrases, float box_threshold, float nms_threshold, OvmDet3D* out, int32_t out_capacity, int32_t* n_out,
-                        ovm_stream_t stream, int nq) {
+static int infer_forked(OvmHandle* h, OvmGdino* g, const OvmImage* image, const float* prompt_depth, int32_t depth_h, int32_t depth_w,
+                        const int32_t* token_ids, int32_t ntok, const int32_t* spans, int32_t n_phrases, float box_threshold,
+                        float nms_threshold, OvmDet3D* out, int32_t out_capacity, int32_t* n_out, ovm_stream_t stream, int nq) {
   hipStream_t s = (hipStream_t)stream;
   // fork: detector on the side stream
   OVM_HIP(h, hipEventRecord(h->ev_fork, s));
@@ -508,7 +516,7 @@ static int infer_forked(OvmHandle* h, OvmGdino* g, const OvmImage* image, const 
   if (r) { h->err = std::string("ovm_gdino_forward: ") + ovm_gdino_last_error(g); return r; }
   OVM_HIP(h, hipEventRecord(h->ev_join, h->side));
   // backbone on the caller's stream
-  r = ovm_backbone_forward(h, image, 1, nullptr, 0, 0, nullptr, nullptr, nullptr, stream);
+  r = ovm_backbone_forward(h, image, 1, prompt_depth, depth_h, depth_w, nullptr, nullptr, nullptr, stream);
   if (r) return r;
   // join, output glue (three launches on the handle's scratch), kept count to the host (the one synchronisation in front of the
   // cube head, whose grid it sizes), cube head
@@ -543,11 +551,14 @@ static int infer_forked(OvmHandle* h, OvmGdino* g, const OvmImage* image, const 
   return OVM_OK;
 }
 
-int ovm_infer(OvmHandle* h, OvmGdino* g, const OvmImage* image, const int32_t* token_ids, int32_t ntok, const int32_t* spans,
-              int32_t n_phrases, float box_threshold, float nms_threshold, OvmDet3D* out, int32_t out_capacity, int32_t* n_out,
-              ovm_stream_t stream) {
+// ovm_infer with a depth prompt (reference rcnn3d.py:97: self.backbone(images.tensor, prompt_depth)); a null prompt_depth IS ovm_infer.
+int ovm_infer_depth(OvmHandle* h, OvmGdino* g, const OvmImage* image, const float* prompt_depth, int32_t depth_h, int32_t depth_w,
+                    const int32_t* token_ids, int32_t ntok, const int32_t* spans, int32_t n_phrases, float box_threshold,
+                    float nms_threshold, OvmDet3D* out, int32_t out_capacity, int32_t* n_out, ovm_stream_t stream) {
   if (!h || !g || !image || !token_ids || !out || !n_out) return OVM_ERR_INVALID;
   h->err.clear();
+  // the refusals of ovm_backbone_forward, in front of the fork: nothing is launched for a prompt the tower cannot take
+  if (const int r = depth_prompt_refusal(h, prompt_depth, depth_h, depth_w)) return r;
   hipStream_t s = (hipStream_t)stream;
   OVM_HIP(h, hipSetDevice(h->device));
   if (!h->side) {
@@ -566,7 +577,8 @@ int ovm_infer(OvmHandle* h, OvmGdino* g, const OvmImage* image, const int32_t* t
         (r = h->alloc(&h->inf_idx, (size_t)nq, true)) || (r = h->alloc(&h->inf_n, 1)) || (r = h->alloc(&h->inf_counts, 1))) return r;
     h->inf_cap = nq;
   }
-  const int r_all = infer_forked(h, g, image, token_ids, ntok, spans, n_phrases, box_threshold, nms_threshold, out, out_capacity, n_out, stream, nq);
+  const int r_all = infer_forked(h, g, image, prompt_depth, depth_h, depth_w, token_ids, ntok, spans, n_phrases, box_threshold, nms_threshold, out,
+                                 out_capacity, n_out, stream, nq);
   if (r_all != OVM_OK) {
     // The detector may still be running on the side stream, reading the caller's image and the plan arena: the caller is entitled to
     // free or reuse the image once this call has returned, and the next call's fork must not race with leftover work on h->inf_*.
@@ -574,6 +586,13 @@ int ovm_infer(OvmHandle* h, OvmGdino* g, const OvmImage* image, const int32_t* t
     (void)hipStreamSynchronize(s);
   }
   return r_all;
+}
+
+int ovm_infer(OvmHandle* h, OvmGdino* g, const OvmImage* image, const int32_t* token_ids, int32_t ntok, const int32_t* spans,
+              int32_t n_phrases, float box_threshold, float nms_threshold, OvmDet3D* out, int32_t out_capacity, int32_t* n_out,
+              ovm_stream_t stream) {
+  return ovm_infer_depth(h, g, image, nullptr, 0, 0, token_ids, ntok, spans, n_phrases, box_threshold, nms_threshold, out, out_capacity, n_out,
+                         stream);
 }
 
 // Co-run mode: the caller runs other work (the GroundingDINO detector) on a second stream while ovm_backbone_forward executes. The

@@ -4,6 +4,11 @@ host-decoded coefficients (gpu_jpeg.py), ``ResizeShortestEdge`` and the depth-pr
 the plain host code below is what the entry points use without one. The OUTPUT schema is the hot path's input
 contract: per image ``{"image": uint8 CHW, "height", "width", "K", "image_id", ["oracle2D"], ["depth"]}``
 (reference cubercnn/data/dataset_mapper.py:33-80, cubercnn/data/build.py:45-54,281-311, demo/demo.py:46-85).
+
+``"depth"`` is the depth prompt of a depth-fusion checkpoint, float32 [1, H', W'] at the network's input size: read from
+``<depth_dir>/test/<image base name>.npz`` as in the reference, or computed from the image itself by a ``depth_source`` (Depth Pro on
+the device, ``depth_prompt.DepthProPrompt``); either way ``depth_prompt.prepare_prompt_depth`` resizes it, so both routes give the same
+bits for the same map.
 """
 from __future__ import annotations
 
@@ -15,6 +20,7 @@ import numpy as np
 import torch
 
 from .. import lib as _lib
+from .depth_prompt import depth_prompt_unread, prepare_prompt_depth, resize_to_image_host
 
 
 def read_image(path: str, fmt: str = "RGB") -> np.ndarray:
@@ -89,7 +95,7 @@ def merge_oracle2d_to_detection_dicts(dataset_dicts: List[Dict], oracle_json: st
 class DatasetMapper3D:
     """Inference branch of reference cubercnn/data/dataset_mapper.py:18-80."""
 
-    def __init__(self, cfg, is_train: bool = False, depth_dir: Optional[str] = None):
+    def __init__(self, cfg, is_train: bool = False, depth_dir: Optional[str] = None, depth_source=None):
         assert not is_train, "training is out of scope"
         self.image_format = cfg.INPUT.FORMAT
         self.resize = ResizeShortestEdge(cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST)
@@ -98,6 +104,11 @@ class DatasetMapper3D:
         self.use_depth = (bool(cfg.MODEL.DINO.USE_DEPTH_FUSION) and cfg.MODEL.BACKBONE.NAME == "build_dino_backbone"
                           and depth_dir is not None)
         self.depth_dir = depth_dir
+        # depth_source(image HWC uint8, format, K, file_name=...) -> float32 [H, W] in metres (depth_prompt.DepthProPrompt: Depth Pro on
+        # the device) takes the place of the .npz read; a register-token model has no depth fusion either (backbone/dino.py)
+        self.depth_source = None
+        if depth_source is not None and depth_prompt_unread(cfg) is None:
+            self.depth_source, self.use_depth = depth_source, True
         # device-side ResizeShortestEdge (bit-identical to the Pillow path; gpu_resize.py) when a HIP device is present
         self.gpu_resize = None
         if bool(cfg.MODEL.AMD.get("GPU_RESIZE", False)) and str(cfg.MODEL.DEVICE).startswith("cuda") and torch.cuda.is_available():
@@ -115,28 +126,27 @@ class DatasetMapper3D:
             image = read_image_device(d["file_name"], self.image_format, torch.device("cuda"), entropy=self.jpeg_entropy)      # uint8 [H, W, 3] in HBM
         else:
             image = read_image(d["file_name"], self.image_format)
+        image_hw = tuple(image.shape[:2])
         depth = None
-        if self.use_depth:
+        if self.depth_source is not None:
+            depth = self.depth_source(image, self.image_format, d.get("K"), file_name=d["file_name"])
+        elif self.use_depth:
             base = os.path.splitext(os.path.basename(d["file_name"]))[0]
             try:
                 depth = np.load(os.path.join(self.depth_dir, "test", base + ".npz"))["depth"].astype("float32")
-                if self.gpu_resize is not None:
-                    pass                                                       # both resizes run on the device below
-                elif depth.shape[:2] != image.shape[:2]:
-                    depth = torch.nn.functional.interpolate(torch.from_numpy(depth)[None, None], size=tuple(image.shape[:2]),
-                                                            mode="bilinear", align_corners=False)[0, 0].numpy()
+                if self.gpu_resize is None:                                    # (on the device both resizes run below)
+                    depth = resize_to_image_host(depth, image_hw)
             except Exception:
-                depth = np.zeros(tuple(image.shape[:2]), dtype=np.float32)
+                depth = np.zeros(image_hw, dtype=np.float32)
         if self.gpu_resize is not None:
             dev_img = image if torch.is_tensor(image) else torch.from_numpy(np.ascontiguousarray(image)).cuda()
             d["image"] = self.gpu_resize(dev_img).permute(2, 0, 1)   # CHW view of the HWC result
         else:
             image = self.resize(image)
             d["image"] = torch.as_tensor(np.ascontiguousarray(image.transpose(2, 0, 1)))
-        if depth is not None and self.gpu_resize is not None:
-            d["depth"] = self.gpu_depth_resize(torch.from_numpy(np.ascontiguousarray(depth)).cuda(), tuple(image.shape[:2])).unsqueeze(0)
-        elif depth is not None:
-            d["depth"] = torch.as_tensor(np.ascontiguousarray(self.resize(depth))).unsqueeze(0)
+        if depth is not None:
+            # the two resizes of the reference's mapper (dataset_mapper.py:45-52,70-72), on the device when the image's is
+            d["depth"] = prepare_prompt_depth(depth, image_hw, self.gpu_depth_resize if self.gpu_resize is not None else self.resize).unsqueeze(0)
         return d
 
 

@@ -304,7 +304,7 @@ EXPORTS = [
     "ovm_g_groupnorm", "ovm_g_biattn", "ovm_g_msdeform", "ovm_g_sine_embed", "ovm_g_normalize_image", "ovm_g_topk", "ovm_g_rowmax",
     "ovm_g_attn_f32", "ovm_g_msdeform_fused", "ovm_g_rowop", "ovm_g_swin_qkv_attn",
     "ovm_gdino_create", "ovm_gdino_destroy", "ovm_gdino_last_error", "ovm_gdino_forward", "ovm_gdino_detect", "ovm_gdino_set_force_topk",
-    "ovm_gdino_debug_copy", "ovm_debug_set_ptr", "ovm_gdino_num_queries", "ovm_gdino_last_outputs", "ovm_infer",
+    "ovm_gdino_debug_copy", "ovm_debug_set_ptr", "ovm_gdino_num_queries", "ovm_gdino_last_outputs", "ovm_infer", "ovm_infer_depth",
     "ovm_host_jpeg_info", "ovm_host_jpeg_entropy_decode", "ovm_jpeg_reconstruct",
     "ovm_host_jpeg_decode_plan", "ovm_jpeg_entropy_decode_workspace", "ovm_jpeg_entropy_decode", "ovm_host_jpeg_entropy_emulate",
     "ovm_host_jpeg_encode_plan", "ovm_jpeg_encode_workspace", "ovm_jpeg_forward", "ovm_jpeg_encode",
@@ -483,6 +483,8 @@ def load() -> C.CDLL:
     lib.ovm_gdino_num_queries.argtypes = [vp]
     lib.ovm_gdino_last_outputs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32)]
     lib.ovm_infer.argtypes = [vp, vp, C.POINTER(OvmImage), C.POINTER(i32), i32, C.POINTER(i32), i32, f32, f32, vp, i32, C.POINTER(i32), vp]
+    lib.ovm_infer_depth.argtypes = [vp, vp, C.POINTER(OvmImage), vp, i32, i32, C.POINTER(i32), i32, C.POINTER(i32), i32, f32, f32, vp, i32,
+                                    C.POINTER(i32), vp]
     for name in EXPORTS:
         if name not in ("ovm_last_error", "ovm_version", "ovm_debug_copy", "ovm_gdino_last_error", "ovm_gdino_debug_copy", "ovm_geo_last_error",
                         "ovm_sam_last_error", "ovm_sam_debug_copy", "ovm_depthpro_last_error", "ovm_depthpro_debug_copy"):

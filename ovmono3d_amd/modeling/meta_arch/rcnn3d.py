@@ -108,10 +108,11 @@ class RCNN3D:
 
     def _infer_fused(self, batched_inputs, images, prompt_depth, do_postprocess):
         """The text-prompted path as ONE C call (``ovm_infer``) when nothing needs the stages separately: ROIHeads3DGDINO with
-        the native engine as its detector, one image with a category_list, no depth prompt, post-processing on. Same kernels in
-        the same order as the staged path below (the detector beside the backbone on a side stream); returns None otherwise."""
+        the native engine as its detector, one image with a category_list, post-processing on; a depth prompt rides along
+        (``ovm_infer_depth``). Same kernels in the same order as the staged path below (the detector beside the backbone on a side
+        stream); returns None otherwise."""
         rh = self.roi_heads
-        if not (do_postprocess and prompt_depth is None and len(batched_inputs) == 1 and hasattr(rh, "load_detector")
+        if not (do_postprocess and len(batched_inputs) == 1 and hasattr(rh, "load_detector")
                 and bool(self.cfg.MODEL.AMD.get("FUSED_INFER", True)) and bool(self.cfg.MODEL.AMD.GDINO_OVERLAP)
                 and "oracle2D" not in batched_inputs[0] and batched_inputs[0].get("category_list")):
             return None
@@ -120,12 +121,15 @@ class RCNN3D:
         eng = getattr(rh.detector, "engine", None)
         if eng is None or rh.loss_w_3d <= 0 or getattr(self.backbone, "export_features", False):
             return None
+        if prompt_depth is not None and (getattr(getattr(self.backbone, "net", None), "has_registers", True) or len(prompt_depth) != 1):
+            return None                                            # a backbone without the branch: the staged path raises as the reference does
         from ..roi_heads.gdino_glue import build_caption, phrase_spans
         cats = list(batched_inputs[0]["category_list"])
         caption, cap_list = build_caption(cats)
         ids, phrase_ids, _ = rh.detector._tokens(caption)
         spans = phrase_spans(ids, phrase_ids)
-        rec, n = self.engine.infer_gdino(images.native, eng._h, ids, spans, 0.001, 0.5, eng.cfg.num_queries)   # roi_heads_gdino.py:148,254
+        rec, n = self.engine.infer_gdino(images.native, eng._h, ids, spans, 0.001, 0.5, eng.cfg.num_queries,   # roi_heads_gdino.py:148,254
+                                          prompt_depth=prompt_depth)
         # phrase k -> class index: filtered_texts.index([name]) of the reference (:162) = first occurrence of the caption's name
         remap = [cats.index(c) if c in cats else -1 for c in cap_list]
         if any(r < 0 for r in remap):

@@ -254,18 +254,30 @@ class Engine:
         return rec[: sum(cl)], cl
 
     def infer_gdino(self, images, gdino_handle, token_ids: Sequence[int], spans: Sequence[Tuple[int, int]], box_threshold: float,
-                    nms_threshold: float, capacity: int):
+                    nms_threshold: float, capacity: int, prompt_depth: Optional[torch.Tensor] = None):
         """``ovm_infer``: preprocess -> backbone -> GroundingDINO engine (internal side stream) -> output glue -> cube head ->
-        postprocess for ONE image in one C call. Returns (records [n, 48], n)."""
+        postprocess for ONE image in one C call; with ``prompt_depth`` (fp32 [1, 1, h, w] or [1, h, w], as ``backbone_forward`` takes
+        it) ``ovm_infer_depth``, the same call with the depth-fusion branch. Returns (records [n, 48], n)."""
         self._require()
         ids = (C.c_int32 * len(token_ids))(*[int(i) for i in token_ids])
         flat = [int(v) for sp in spans for v in sp]
         sp = (C.c_int32 * max(len(flat), 1))(*flat)
         rec = torch.empty((max(capacity, 1), OVM_REC_FLOATS), dtype=torch.float32, device=self.device)
         n = C.c_int32(0)
-        rc = self._lib.ovm_infer(self._h, gdino_handle, images, ids, len(token_ids), sp, len(spans), float(box_threshold), float(nms_threshold),
-                                 rec.data_ptr(), int(capacity), C.byref(n), self._stream())
-        check(rc, self._h, "ovm_infer")
+        if prompt_depth is None:
+            rc = self._lib.ovm_infer(self._h, gdino_handle, images, ids, len(token_ids), sp, len(spans), float(box_threshold), float(nms_threshold),
+                                     rec.data_ptr(), int(capacity), C.byref(n), self._stream())
+            check(rc, self._h, "ovm_infer")
+            return rec[: n.value], int(n.value)
+        prompt_depth = prompt_depth.to(self.device, torch.float32).contiguous()
+        if prompt_depth.dim() == 3:
+            prompt_depth = prompt_depth.unsqueeze(1)
+        if prompt_depth.dim() != 4 or prompt_depth.shape[0] != 1 or prompt_depth.shape[1] != 1:
+            raise ValueError(f"prompt_depth must be [1, 1, h, w] for the one image of this call, is {tuple(prompt_depth.shape)}")
+        rc = self._lib.ovm_infer_depth(self._h, gdino_handle, images, prompt_depth.data_ptr(), int(prompt_depth.shape[-2]), int(prompt_depth.shape[-1]),
+                                       ids, len(token_ids), sp, len(spans), float(box_threshold), float(nms_threshold), rec.data_ptr(),
+                                       int(capacity), C.byref(n), self._stream())
+        check(rc, self._h, "ovm_infer_depth")                      # (synchronises the stream: prompt_depth outlives its reads)
         return rec[: n.value], int(n.value)
 
     def set_corun(self, on: bool = True) -> None:

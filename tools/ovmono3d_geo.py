@@ -47,6 +47,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+from ovmono3d_amd.data.depth_prompt import dump_depth, load_depth  # noqa: E402,F401
 from ovmono3d_amd.geo import GeoParams, lift_boxes  # noqa: E402
 
 logger = logging.getLogger("ovmono3d_geo")
@@ -87,13 +88,6 @@ def sam_masks(predictor, image_root, file_path, height, width, boxes_xyxy, bgr=N
     return predictor.predict_boxes(boxes_xyxy, mask_index=2)
 
 
-def dump_depth(depth_dir, file_path, depth):
-    """The <image base name>.npz file load_depth reads."""
-    os.makedirs(depth_dir, exist_ok=True)
-    base = os.path.splitext(os.path.basename(file_path))[0]
-    np.savez(os.path.join(depth_dir, base + ".npz"), depth=depth.cpu().numpy().astype(np.float32))
-
-
 def dump_masks(mask_dir, image_id, positions, planes):
     """The <image_id>.npz file load_masks reads."""
     os.makedirs(mask_dir, exist_ok=True)
@@ -101,20 +95,6 @@ def dump_masks(mask_dir, image_id, positions, planes):
     H, W = planes[0].shape
     np.savez_compressed(os.path.join(mask_dir, f"{image_id}.npz"), masks=np.stack(planes).astype(np.uint8).reshape(-1, H, W),
                         index=np.asarray(positions, np.int64))
-
-
-def load_depth(depth_dir, file_path, height, width):
-    base = os.path.splitext(os.path.basename(file_path))[0]
-    for cand in (os.path.join(depth_dir, "test", base + ".npz"), os.path.join(depth_dir, base + ".npz")):
-        if os.path.exists(cand):
-            depth = np.load(cand)["depth"]
-            if depth.ndim == 3 and depth.shape[0] == 1:
-                depth = depth[0]
-            if tuple(depth.shape) != (height, width):
-                raise SystemExit(f"{cand}: depth map is {tuple(depth.shape)} but the image is {(height, width)}; GEO needs the depth at "
-                                 "the image's own resolution (the reference never resizes it)")
-            return np.ascontiguousarray(depth, dtype=np.float32)
-    raise SystemExit(f"no depth file for {file_path} under {depth_dir}")
 
 
 def load_masks(mask_dir, image_id, height, width):

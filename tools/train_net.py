@@ -22,6 +22,12 @@ device`` runs the evaluator's matching on the GPU (same results as ``host``); ``
 (tools/train_net.py:112-130): for every N-th image of a dataset a six-panel JPEG under ``<dataset>/vis/``, composed on the device,
 and one logged line with the mean centre, depth, size and rotation errors of the matched predictions; ``--vis-fork-compat`` takes
 those errors as the fork does (sampled images only, its rotation formula).
+
+The depth prompt of a depth-fusion checkpoint (``MODEL.DINO.USE_DEPTH_FUSION``, the default): ``--depth files`` (default) reads
+``<--depth-dir>/test/<image base name>.npz`` as the reference's mapper does (no folder: no prompt; a missing file: zeros);
+``--depth depthpro`` computes it on the device from the image itself (Depth Pro, ``--depthpro-weights``; ``--depthpro-focal K`` hands it
+the dataset's ``K[0][0]``, ``estimate`` lets its field-of-view head choose) and ``--dump-depth DIR`` writes the maps as the files
+``--depth-dir`` reads. Both routes go through ``data/depth_prompt.py prepare_prompt_depth`` and give the same results for the same map.
 """
 import argparse
 import json
@@ -37,6 +43,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ovmono3d_amd.checkpoint import DetectionCheckpointer  # noqa: E402
 from ovmono3d_amd.data import (DatasetMapper3D, build_detection_test_loader, load_omni3d_json,  # noqa: E402
                                merge_oracle2d_to_detection_dicts)
+from ovmono3d_amd.data.depth_prompt import add_depth_arguments, build_depth_prompt, check_depth_arguments  # noqa: E402
 from ovmono3d_amd.defaults import make_cfg  # noqa: E402
 from ovmono3d_amd.evaluation import (CategoryMap, Omni3DEvaluator, Omni3DGroundTruth, collective_summary,  # noqa: E402
                                      eval_filter_settings, evaluate_omni3d, inference_on_dataset)
@@ -66,7 +73,7 @@ def uses_proximity(name):
 
 
 def do_test(cfg, model, mode="base", datasets_root="datasets/Omni3D", image_root="datasets", depth_dir=None, category_meta=None,
-            eval_prox=False, matcher="host", stage3d="host", vis_every=0, vis_fork_compat=False):
+            eval_prox=False, matcher="host", stage3d="host", vis_every=0, vis_fork_compat=False, depth_source=None):
     if stage3d == "device":                                                     # the 3D stages ride in the device matcher's upload
         matcher = "device"
     if mode == "novel":
@@ -86,7 +93,7 @@ def do_test(cfg, model, mode="base", datasets_root="datasets/Omni3D", image_root
             else:
                 logger.warning("%s: TEST.ORACLE2D is set but no oracle-2D file was found (DATASETS.ORACLE2D_FILES.%s.%s); "
                                "running the RPN + box-head path", name, cfg.DATASETS.ORACLE2D_FILES.EVAL_MODE, mode)
-        loader = build_detection_test_loader(cfg, dicts, DatasetMapper3D(cfg, False, depth_dir), get_rank(), get_world_size())
+        loader = build_detection_test_loader(cfg, dicts, DatasetMapper3D(cfg, False, depth_dir, depth_source), get_rank(), get_world_size())
         results = inference_on_dataset(model, loader, Omni3DEvaluator(name, out_dir))
         if get_rank() == 0:
             os.makedirs(os.path.join(out_dir, name), exist_ok=True)
@@ -170,14 +177,13 @@ def main(args):
         from ovmono3d_amd.evaluation.distributed import NativeComm, set_native_comm
         set_native_comm(NativeComm.from_torch_distributed(torch.device("cuda", local_rank)))
     DetectionCheckpointer(model, save_dir=cfg.OUTPUT_DIR).resume_or_load(cfg.MODEL.WEIGHTS, resume=args.resume)
-    if cfg.TEST.CAT_MODE == "all":
-        do_test(cfg, model, "novel", args.datasets_root, args.image_root, args.depth_dir, args.category_meta, args.eval_prox, args.eval_matcher,
-                args.eval_3d, args.vis_every, args.vis_fork_compat)
-        do_test(cfg, model, "base", args.datasets_root, args.image_root, args.depth_dir, args.category_meta, args.eval_prox, args.eval_matcher,
-                args.eval_3d, args.vis_every, args.vis_fork_compat)
-    else:
-        do_test(cfg, model, cfg.TEST.CAT_MODE, args.datasets_root, args.image_root, args.depth_dir, args.category_meta, args.eval_prox,
-                args.eval_matcher, args.eval_3d, args.vis_every, args.vis_fork_compat)
+    depth_source = None
+    if args.depth == "depthpro":                                                 # the depth prompt computed on the device from the image itself
+        depth_source = build_depth_prompt(args.depthpro_weights, args.depthpro_focal, args.depthpro_config, args.dump_depth,
+                                          torch.device("cuda", local_rank))
+    for mode in (("novel", "base") if cfg.TEST.CAT_MODE == "all" else (cfg.TEST.CAT_MODE,)):
+        do_test(cfg, model, mode, args.datasets_root, args.image_root, args.depth_dir, args.category_meta, args.eval_prox, args.eval_matcher,
+                args.eval_3d, args.vis_every, args.vis_fork_compat, depth_source)
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()
@@ -194,7 +200,7 @@ def default_argument_parser():
     p.add_argument("--dist-url", default="tcp://127.0.0.1:29500")
     p.add_argument("--datasets-root", default="datasets/Omni3D", help="(native build) folder of the Omni3D JSON files")
     p.add_argument("--image-root", default="datasets")
-    p.add_argument("--depth-dir", default=None, help="(native build) folder of depth-prompt .npz files")
+    add_depth_arguments(p)
     p.add_argument("--category-meta", default=None, help="(native build) category_meta.json-style file: thing_classes + "
                    "thing_dataset_id_to_contiguous_id of the model's class index; default: derived from the annotation file")
     p.add_argument("--eval-prox", action="store_true", help="(native build) proximity evaluation for the Objectron and SUNRGBD datasets "
@@ -214,7 +220,9 @@ def default_argument_parser():
 
 
 if __name__ == "__main__":
-    args = default_argument_parser().parse_args()
+    parser = default_argument_parser()
+    args = parser.parse_args()
+    check_depth_arguments(args, parser, lambda: make_cfg(args.config_file, args.opts))     # exit status 2 before any device call
     if args.num_gpus > 1 and "WORLD_SIZE" not in os.environ:
         # the reference's launch() spawns one process per GPU (tools/train_net.py:563-570); here the same via
         # torch.distributed.run, started as a child process before anything touches the GPU
