@@ -21,6 +21,11 @@ prompt on the device from the image itself (Depth Pro, ``ovmono3d_amd.depthpro``
 ``<DIR>/<name>.npz``); ``--depth files --depth-dir DIR`` reads ``<DIR>/test/<name>.npz`` or ``<DIR>/<name>.npz`` and ends the run naming
 the image whose file is missing. Either way the map goes through ``data/depth_prompt.py prepare_prompt_depth``, the resizes of the
 evaluation's mapper, into ``model([d], prompt_depth=...)``.
+
+``--show-points`` (native build, off by default; needs ``--depth depthpro|files``): the novel view of ``<name>_combine.jpg`` shows the
+run's metric depth map - the raw map at image size, before ``prepare_prompt_depth`` - as a point cloud under the boxes
+(``draw_scene_view(depth=...)``, ``ovm_render_scene_points``). ``<name>_dets.json`` does not depend on it. ``demo/demo_geo.py`` is the
+training-free OVMono3D-GEO method on the same kind of input.
 """
 import argparse
 import json
@@ -101,6 +106,7 @@ def do_test(args, cfg, model):
             prompt_depth = depth_source(im, "BGR", K, file_name=name)
         elif args.depth == "files":
             prompt_depth = load_depth(args.depth_dir, name)
+        raw_depth = scene_depth(prompt_depth, h, w, im_name) if args.show_points else None   # the map as computed or read, for the picture
         if prompt_depth is not None:
             prompt_depth = prepare_prompt_depth(prompt_depth, (h, w), depth_resize)[None]
         dets = model([d], prompt_depth=prompt_depth)[0]["instances"]
@@ -121,20 +127,39 @@ def do_test(args, cfg, model):
         with open(os.path.join(cfg.OUTPUT_DIR, im_name + "_dets.json"), "w") as f:
             json.dump({"K": K.tolist(), "detections": out}, f)
         if vis_on:
-            write_views(im, K, out, kept_idx, cfg.OUTPUT_DIR, im_name, gpu_jpeg=bool(cfg.MODEL.AMD.get("GPU_JPEG_WRITE", True)))
+            write_views(im, K, out, kept_idx, cfg.OUTPUT_DIR, im_name, gpu_jpeg=bool(cfg.MODEL.AMD.get("GPU_JPEG_WRITE", True)),
+                        depth=raw_depth)
 
 
-def write_views(im, K, dets, kept_idx, output_dir, im_name, gpu_jpeg=True):
+def scene_depth(depth, h, w, im_name):
+    """The depth map as draw_scene_view(depth=...) takes it: fp32 [h, w]. A map of another size is not a picture of this image."""
+    if depth is None:
+        return None
+    if torch.is_tensor(depth):
+        depth = depth.detach().to(torch.float32)
+    else:
+        depth = np.ascontiguousarray(depth, dtype=np.float32)
+    if depth.ndim == 3 and depth.shape[0] == 1:
+        depth = depth[0]
+    if tuple(depth.shape) != (h, w):
+        raise SystemExit(f"--show-points: the depth map of {im_name} is {tuple(depth.shape)} but the image is {(h, w)}")
+    return depth
+
+
+def write_views(im, K, dets, kept_idx, output_dir, im_name, gpu_jpeg=True, depth=None, labels=None):
     """demo.py:89-121: the kept boxes drawn (front + novel view, scale = H) into <name>_combine.jpg, else <name>_boxes.jpg.
-    gpu_jpeg: a picture on the device is encoded there (data/gpu_jpeg.py write_jpeg; the same bytes as the host's Image.save)."""
+    gpu_jpeg: a picture on the device is encoded there (data/gpu_jpeg.py write_jpeg; the same bytes as the host's Image.save).
+    depth: fp32 [H, W] metric depth of the image, drawn as a point cloud under the boxes of the novel view; labels: int32 [H, W], the
+    position in ``dets`` of the box a pixel belongs to or -1 (vis.labels_from_masks), tints the points. Both None: the reference's picture."""
     from ovmono3d_amd import vis
     from ovmono3d_amd.data.gpu_jpeg import write_jpeg
     if len(dets) > 0:
         corners = np.asarray([d["corners3D"] for d in dets], np.float64)
         colors = np.asarray([[c / 255.0 for c in vis.get_color(i)] for i in kept_idx], np.float32)
         text = ["{} {:.2f}".format(d["category"], d["score"]) for d in dets]
+        points = {} if depth is None else {"depth": depth, "point_labels": labels}
         front, novel = vis.draw_scene_view(im, K, corners, colors, text=text, scale=int(im.shape[0]), blend_weight=0.5,
-                                           blend_weight_overlay=0.85)
+                                           blend_weight_overlay=0.85, **points)
         bgr, name = vis.concat_views(front, novel), im_name + "_combine.jpg"
     else:
         bgr, name = im, im_name + "_boxes.jpg"
@@ -164,6 +189,8 @@ if __name__ == "__main__":
     parser.add_argument("--threshold", type=float, default=0.25, help="threshold on score for visualizing")
     add_depth_arguments(parser, choices=("none", "files", "depthpro"), default="none",
                         focal_help="the K[0][0] of this run: --focal-length, or without it the reference's convention 4.0 * h / 2 of the first image")
+    parser.add_argument("--show-points", default=False, action="store_true",
+                        help="(native build) draw the depth map of --depth depthpro|files as a point cloud under the boxes of the novel view")
     parser.add_argument("--display", default=False, action="store_true", help="no-op: there is no GUI on the target (the views are written to <name>_combine.jpg)")
     parser.add_argument("--eval-only", default=True, action="store_true", help="perform evaluation only")
     parser.add_argument("--num-gpus", type=int, default=1, help="number of gpus *per machine*")
@@ -173,6 +200,8 @@ if __name__ == "__main__":
     parser.add_argument("opts", default=None, nargs=argparse.REMAINDER,
                         help="Modify config options by adding 'KEY VALUE' pairs at the end of the command.")
     args = parser.parse_args()
+    if args.show_points and args.depth == "none":
+        parser.error("--show-points draws the run's depth map: it needs --depth depthpro or --depth files")
     check_depth_arguments(args, parser, lambda: setup(args), files_need_dir=True)          # exit status 2 before any device call
     print("Command Line Args:", args)
     main(args)

@@ -1,0 +1,206 @@
+#!/usr/bin/env python3
+"""OVMono3D-GEO, the training-free method, on a folder of images and a list of names per image - what demo/demo.py is for OVMono3D-LIFT.
+
+    python demo/demo_geo.py --config-file configs/OVMono3D_dinov2_SFP.yaml --input-folder datasets/coco_examples \\
+        --labels-file datasets/coco_examples/labels.json --depth depthpro --depthpro-weights checkpoints/depthpro_hf.safetensors \\
+        --mask sam --sam-weights checkpoints/sam_vit_l_0b3195.pth \\
+        MODEL.AMD.GDINO_WEIGHTS checkpoints/groundingdino_swinb_cogcoor.pth MODEL.AMD.BERT_VOCAB bert-base-uncased/vocab.txt OUTPUT_DIR output/geo
+
+Per image, all on the device: read (the device JPEG route) -> K by demo.py's focal-length convention (the first image's focal length
+sticks) -> 2D boxes, from ``--boxes-file`` ({image name: [{bbox xywh, category_id, score}]}) or from the native GroundingDINO detector
+prompted with the image's names (tools/make_oracle2d.py's detector, caption and thresholds; boxes scaled back to the image) -> boxes
+below ``--threshold`` dropped -> metric depth (``--depth depthpro``: Depth Pro on the image; ``--depth files``: ``<depth-dir>/test/<name>.npz``
+or ``<depth-dir>/<name>.npz``) -> a mask per box (``--mask sam``: Segment Anything prompted with the box, plane [2]; ``--mask box``: the box
+itself) -> ``ovmono3d_amd.geo.lift_boxes``. Written: ``<name>_dets.json`` in demo.py's schema (instances the lift has no answer for are
+left out and counted in the printed line) and ``<name>_combine.jpg``, demo.py's picture; with ``--show-points`` (the default) its novel
+view shows the depth map as a point cloud under the boxes, each box's points tinted with its colour. ``<name>_boxes.jpg`` (the input)
+when nothing is lifted.
+
+The LIFT model is not built: ``MODEL.WEIGHTS`` is not needed, the config supplies the detector's settings and ``OUTPUT_DIR``.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (os.path.join(ROOT, "tools"), os.path.join(ROOT, "demo"), ROOT):
+    sys.path.insert(0, p)
+
+from demo import write_views  # noqa: E402
+from make_oracle2d import build_caption, build_detector, gdino_postprocess, phrase_spans  # noqa: E402
+from ovmono3d_geo import check_args, sam_masks, xywh_to_xyxy  # noqa: E402
+
+from ovmono3d_amd.data.depth_prompt import add_depth_arguments, build_depth_prompt, load_depth  # noqa: E402
+from ovmono3d_amd.data.gpu_jpeg import read_image_device  # noqa: E402
+from ovmono3d_amd.data.gpu_resize import ResizeShortestEdgeGPU  # noqa: E402
+from ovmono3d_amd.defaults import make_cfg  # noqa: E402
+from ovmono3d_amd.geo import GeoParams, box_to_rect, lift_boxes  # noqa: E402
+
+BOX_THRESHOLD, NMS_THRESHOLD = 0.001, 0.5                            # tools/make_oracle2d.py's defaults
+
+
+def detect_boxes(det, resize, bgr, cats, input_format="BGR"):
+    """The native detector on one device image: (boxes xyxy [n, 4] at the image's resolution - float32 values, as tools/make_oracle2d.py
+    writes them -, scores [n], class index [n])."""
+    caption, _ = build_caption(cats)
+    net = resize(bgr if input_format == "BGR" else bgr.flip(-1))
+    r = det(net.permute(2, 0, 1).contiguous(), caption)
+    boxes, scores, cls = gdino_postprocess(r["pred_logits"], r["pred_boxes"], phrase_spans(r["input_ids"], r["phrase_ids"]), tuple(net.shape[:2]),
+                                           box_threshold=BOX_THRESHOLD, nms_threshold=NMS_THRESHOLD)
+    sy, sx = bgr.shape[0] / net.shape[0], bgr.shape[1] / net.shape[1]                      # network resolution -> original resolution
+    b = boxes.cpu().numpy() * np.array([sx, sy, sx, sy], np.float32)
+    return b.astype(np.float64).reshape(-1, 4), scores.cpu().tolist(), cls.cpu().tolist()
+
+
+def box_masks(boxes_xyxy, h, w, device):
+    """uint8 [n, h, w]: the pixels ``--mask box`` lifts (geo.box_to_rect, clipped to the image)."""
+    planes = torch.zeros((len(boxes_xyxy), h, w), dtype=torch.uint8, device=device)
+    for i, b in enumerate(boxes_xyxy):
+        x0, y0, x1, y1 = box_to_rect(b)
+        planes[i, max(y0, 0):max(min(y1, h), 0), max(x0, 0):max(min(x1, w), 0)] = 1
+    return planes
+
+
+def do_test(args, cfg):
+    from ovmono3d_amd import vis
+    dev = torch.device("cuda", torch.cuda.current_device())
+    ims = sorted(f for f in os.listdir(args.input_folder) if not f.endswith(".json"))
+    with open(args.labels_file) as f:
+        cats_per_img = json.load(f)
+    boxes_per_img = None
+    if args.boxes_file:
+        with open(args.boxes_file) as f:
+            boxes_per_img = json.load(f)
+    detector = resize = None
+    if boxes_per_img is None:
+        detector = build_detector(cfg, dev)
+        resize = ResizeShortestEdgeGPU(cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST)
+    depth_source = None
+    if args.depth == "depthpro":
+        depth_source = build_depth_prompt(args.depthpro_weights, args.depthpro_focal, args.depthpro_config, args.dump_depth, dev)
+    predictor = None
+    if args.mask == "sam":
+        from ovmono3d_amd.sam import build_sam
+        predictor = build_sam(args.sam_arch, args.sam_weights, device=dev, image_size=args.sam_image_size)
+    params = GeoParams()
+    focal_length, principal_point = args.focal_length, args.principal_point
+    os.makedirs(cfg.OUTPUT_DIR, exist_ok=True)
+    for name in ims:
+        im_name = os.path.splitext(name)[0]
+        cats = cats_per_img.get(im_name, [])
+        if cats == []:
+            continue
+        stages, t0 = {}, time.perf_counter()
+
+        def lap(stage):
+            nonlocal t0
+            if args.stage_times:
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                stages[stage] = round((t1 - t0) * 1e3, 3)
+                t0 = t1
+
+        im = read_image_device(os.path.join(args.input_folder, name), "BGR", dev)
+        h, w = int(im.shape[0]), int(im.shape[1])
+        if focal_length == 0:
+            focal_length = 4.0 * h / 2                                       # demo.py:63-65
+        px, py = (w / 2, h / 2) if len(principal_point) == 0 else principal_point
+        K = np.array([[focal_length, 0.0, px], [0.0, focal_length, py], [0.0, 0.0, 1.0]])
+        lap("read")
+        if boxes_per_img is not None:
+            inst = boxes_per_img.get(im_name, [])
+            boxes = np.asarray([xywh_to_xyxy(b["bbox"]) for b in inst], np.float64).reshape(-1, 4)
+            scores, classes = [float(b.get("score", 1.0)) for b in inst], [int(b["category_id"]) for b in inst]
+        else:
+            boxes, scores, classes = detect_boxes(detector, resize, im, cats, cfg.INPUT.FORMAT)
+        cand = [i for i, s in enumerate(scores) if not s < args.threshold]
+        lap("boxes")
+        out, kept_idx, labels, depth = [], [], None, None
+        if cand:
+            if depth_source is not None:
+                depth = depth_source(im, "BGR", K, file_name=name)
+            else:
+                depth = torch.from_numpy(load_depth(args.depth_dir, name, h, w)).to(dev)
+            lap("depth")
+            cboxes = boxes[cand]
+            planes = sam_masks(predictor, None, None, h, w, cboxes, bgr=im) if predictor is not None else None
+            lap("masks")
+            lifted = lift_boxes(depth, K, boxes_xyxy=cboxes, masks=list(planes) if planes is not None else None, params=params)
+            lap("lift")
+            for k, (i, box) in enumerate(zip(cand, lifted)):
+                if box is None:
+                    continue
+                kept_idx.append(k)
+                ci = classes[i]
+                out.append({"category": cats[ci] if 0 <= ci < len(cats) else ci, "score": float(scores[i]),
+                            "bbox3D": list(box["center_cam"]) + list(box["dimensions"]), "pose": box["pose"], "corners3D": box["bbox3D"],
+                            "center_2D": list(box["center_2D"]), "bbox2D": [float(v) for v in boxes[i]]})
+            if out and args.show_points:
+                if planes is None:
+                    planes = box_masks(cboxes, h, w, dev)
+                labels = vis.labels_from_masks(planes[kept_idx])
+        print("File: {} with {} dets ({} boxes at or above the threshold, {} not lifted)".format(im_name, len(out), len(cand), len(cand) - len(out)))
+        with open(os.path.join(cfg.OUTPUT_DIR, im_name + "_dets.json"), "w") as f:
+            json.dump({"K": K.tolist(), "detections": out}, f)
+        write_views(im, K, out, kept_idx, cfg.OUTPUT_DIR, im_name, gpu_jpeg=bool(cfg.MODEL.AMD.get("GPU_JPEG_WRITE", True)),
+                    depth=depth if out and args.show_points else None, labels=labels)
+        lap("views")
+        if args.stage_times:
+            print("stage_ms " + json.dumps({"image": im_name, **stages}))
+
+
+def argument_parser():
+    parser = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    parser.add_argument("--config-file", default="", metavar="FILE", help="path to config file")
+    parser.add_argument("--input-folder", type=str, help="folder of images to process", required=True)
+    parser.add_argument("--labels-file", type=str, help="path to labels file: {image name: [category names]}", required=True)
+    parser.add_argument("--boxes-file", type=str, default="", help="2D boxes per image ({image name: [{bbox xywh, category_id, score}]}) instead of the detector")
+    parser.add_argument("--focal-length", type=float, default=0, help="focal length for image inputs (in px)")
+    parser.add_argument("--principal-point", type=float, default=[], nargs=2, help="principal point for image inputs (in px)")
+    parser.add_argument("--threshold", type=float, default=0.30, help="2D boxes scoring below it are dropped (the reference GEO's cut)")
+    add_depth_arguments(parser, choices=("depthpro", "files"), default="depthpro",
+                        focal_help="the K[0][0] of this run: --focal-length, or without it the reference's convention 4.0 * h / 2 of the first image")
+    parser.add_argument("--mask", choices=("sam", "box"), default="sam",
+                        help="sam: Segment Anything prompted with the box, plane [2] of its multimask outputs (the reference's rule); "
+                             "box: the 2D box is the mask")
+    parser.add_argument("--sam-weights", default=None, help="segment_anything checkpoint (.pth)")
+    parser.add_argument("--sam-arch", default="vit_l", help="vit_b or vit_l (vit_h has head dimension 80: refused)")
+    parser.add_argument("--sam-image-size", type=int, default=None, help=argparse.SUPPRESS)      # tests: a small encoder input
+    parser.add_argument("--stage-times", action="store_true", help=argparse.SUPPRESS)            # measurements: synchronise and print per-stage ms
+    parser.add_argument("--show-points", default=True, action=argparse.BooleanOptionalAction,
+                        help="draw the depth map as a point cloud under the boxes of the novel view, tinted per box")
+    parser.add_argument("opts", default=None, nargs=argparse.REMAINDER,
+                        help="Modify config options by adding 'KEY VALUE' pairs at the end of the command.")
+    return parser
+
+
+def check_arguments(args, parser):
+    """Exit status 2 for what cannot work, before any device call."""
+    check_args(args, parser)                                                 # --depth-dir with --depth files only (tools/ovmono3d_geo.py)
+    if args.depth == "depthpro" and not args.depthpro_weights:
+        parser.error("--depth depthpro needs --depthpro-weights FILE")
+    if args.depth != "depthpro" and args.dump_depth:
+        parser.error("--dump-depth writes the depth that --depth depthpro computes")
+    if args.mask == "sam" and not args.sam_weights:
+        parser.error("--mask sam needs --sam-weights FILE")
+    return args
+
+
+def main():
+    parser = argument_parser()
+    args = check_arguments(parser.parse_args(), parser)
+    print("Command Line Args:", args)
+    cfg = make_cfg(args.config_file, args.opts)
+    if not torch.cuda.is_available():
+        raise SystemExit("OVMono3D-GEO runs on the HIP device (there is no CPU path)")
+    with torch.no_grad():
+        do_test(args, cfg)
+
+
+if __name__ == "__main__":
+    main()

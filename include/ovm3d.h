@@ -869,6 +869,36 @@ int ovm_render_scene(const OvmSceneLayout* layout, const OvmSceneSegment* grid, 
                      const uint8_t* image, int64_t image_pitch, uint8_t* front, int64_t front_pitch, uint8_t* novel, int64_t novel_pitch,
                      void* workspace, int64_t workspace_bytes, ovm_stream_t stream);
 
+/* ovm_render_scene with the scene's geometry under the boxes of the novel view: a metric depth map of the front image, splatted
+ * as a z-buffered point cloud. A layer of this project (declared deviation: the reference draws the boxes over the bare grid);
+ * the rules are restated in numpy by tests/scene_points_oracle.py.
+ *
+ * Pass A (scene_splat, one thread per front pixel (i, j), fp64 with contraction off): d = depth[i][j]; the pixel is skipped unless
+ * d is finite and > 0. Camera point under the renderer's sampling convention, X = ((j + 0.5) - K[2]) / K[0] * d,
+ * Y = ((i + 0.5) - K[5]) / K[4] * d, Z = d with the front view's K; novel frame as the layout moves box corners,
+ * r = R (p - center) summed left to right, r[2] += zoom_bias * zoom_factor; skipped unless r[2] >= zplane and r[2] > 0;
+ * (x, y) = floor of K_novel r / r[2]. Key = float bits of (float)r[2] in the high word, i * width + j in the low word: the nearest
+ * point wins, the lower source index on a tie. The key goes, by 64-bit atomicMin, to every canvas pixel of the point_size x
+ * point_size square centred on (x, y); the buffer starts as all ones (no point), and its final state does not depend on the
+ * execution order.
+ * Pass B (inside scene_tiles): only where a novel-view pixel has no triangle - the pixel that is otherwise the canvas (225) or
+ * grid (175) grey. With a key there the base colour is the image's BGR at the winning source pixel, and with labels given and
+ * 0 <= labels[i][j] < n_boxes there it is tinted, (image[ch] + edge_u8[b][ch] + 1) >> 1 (any other label value: no tint). Box
+ * faces stay on top, edges and labels are drawn after as before, the front view is ovm_render_scene's. With early_return set
+ * nothing is splatted: both views are ovm_render_scene's and the key buffer stays all ones.
+ *
+ * depth: device fp32 [height][width] of the front view; labels: device int32 of the same shape or null; both with a row pitch in
+ * bytes (a multiple of 4, at least one row). R: host, the rotation given to ovm_host_scene_layout (the layout does not keep it).
+ * point_size: odd, 1..9. zbuf_out: null, or device uint64 [scale][scale] that receives the key buffer. The layout must draw both
+ * views. A null depth or R, a bad pitch or point_size, a layout without both views -> OVM_ERR_INVALID, before any device work.
+ * The workspace is ovm_render_scene's plus the key buffer: ovm_render_scene_points_workspace. */
+int ovm_render_scene_points_workspace(const OvmSceneLayout* layout, int64_t glyph_bytes, int64_t* bytes);
+int ovm_render_scene_points(const OvmSceneLayout* layout, const OvmSceneSegment* grid, const uint8_t* glyphs, int64_t glyph_bytes,
+                            const uint8_t* image, int64_t image_pitch, uint8_t* front, int64_t front_pitch, uint8_t* novel,
+                            int64_t novel_pitch, const float* depth, int64_t depth_pitch, const int32_t* labels, int64_t labels_pitch,
+                            const double* R, int32_t point_size, uint64_t* zbuf_out, void* workspace, int64_t workspace_bytes,
+                            ovm_stream_t stream);
+
 /* ---- Visualisation: evaluation sample panels -------------------------------------------------------------------------------
  * visualize_from_instances of the reference (cubercnn/vis/vis.py:76-296): per sampled image a 2H x 3W mosaic of six copies of
  * the image - columns: ground truth of all classes, ground truth of the evaluated classes, predictions; top row the 2D boxes,

@@ -25,7 +25,7 @@ inline int64_t to_i64(double v) { return (int64_t)clampd(v, -1e15, 1e15); }   //
 inline int iround(double v) { return (int)std::nearbyint(v); }                  // np.round: half to even
 
 // K @ v / div, summed left to right as the numpy restatements do
-inline void project(const double* K, const double* v, double div, double* u) {
+__host__ __device__ inline void project(const double* K, const double* v, double div, double* u) {
 #pragma clang fp contract(off)
   u[0] = (K[0] * v[0] + K[1] * v[1] + K[2] * v[2]) / div;
   u[1] = (K[3] * v[0] + K[4] * v[1] + K[5] * v[2]) / div;

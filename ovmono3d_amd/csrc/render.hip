@@ -14,6 +14,15 @@
 //                 Phong shading and softmax_rgb_blend of the winner, the silhouette blend or canvas, then the edges and labels
 //                 strictly in draw order (a label background blends over earlier boxes' edges), the overlay, and one BGR write.
 // Coverage and depth are fp64 with contraction off, as in the numpy restatement; shading is fp32 as in pytorch3d.
+//
+// Point cloud (ovm_render_scene_points; a layer of this project, the reference has none): between the upload and the two kernels
+//   scene_splat   one thread per pixel of the front image: the pixel's metric depth un-projected under the front K, moved into the
+//                 novel frame as the layout moves box corners, projected under the novel K, and its key (float bits of the novel z,
+//                 source index) written with a 64-bit atomicMin into a scale x scale buffer over a point_size square. The minimum
+//                 does not depend on the execution order (nor does the read that, for point_size > 1, skips an atomic that could not
+//                 lower the stored key). All fp64, contraction off (tests/scene_points_oracle.py restates it).
+//   scene_tiles   reads that buffer where a novel-view pixel has no triangle: the winner's image colour, tinted by its box, takes
+//                 the place of the canvas / grid grey. With the buffer pointer null the kernel is ovm_render_scene's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -95,7 +104,29 @@ struct SceneArgs {
   int32_t early_return, render_front;   // render_front: blend_weight > 0
   double bw, one_minus_bw, bwo, one_minus_bwo;
   int32_t overlay;
+  // point cloud under the boxes of the novel view (ovm_render_scene_points); zbuf null: none
+  const unsigned long long* zbuf;       // [novel H][novel W] keys, all ones = no point
+  const int32_t* labels;                // box index per front pixel or null
+  int64_t labels_pitch;
+  const uint8_t* tint;                  // [n_boxes][4] edge colours
+  int32_t img_w, n_boxes;
 };
+
+struct SplatArgs {
+  const float* depth;
+  int64_t depth_pitch;
+  unsigned long long* zbuf;
+  int32_t H, W, S, half;                // front image size, novel canvas, (point_size - 1) / 2
+  double fx, cx, fy, cy;                // front K[0], K[2], K[4], K[5]
+  double R[9], c[3], shift, zplane, Kn[9];
+};
+
+inline __host__ __device__ void rotate(const double* R, const double* c, const double* p, double* r) {
+  const double d0 = p[0] - c[0], d1 = p[1] - c[1], d2 = p[2] - c[2];
+  r[0] = R[0] * d0 + R[1] * d1 + R[2] * d2;
+  r[1] = R[3] * d0 + R[4] * d1 + R[5] * d2;
+  r[2] = R[6] * d0 + R[7] * d1 + R[8] * d2;
+}
 
 // ------------------------------------------------------------------------------------------------------------------ device
 
@@ -178,6 +209,35 @@ __global__ void __launch_bounds__(64) scene_setup(const DBox* __restrict__ boxes
     }
     out[sub] = r;
   }
+}
+
+// Pass A of the point cloud: one thread per front pixel (row blockIdx.y). Every write lands inside the S x S key buffer.
+__global__ void __launch_bounds__(kThreads) scene_splat(SplatArgs P) {
+  const int j = blockIdx.x * kThreads + threadIdx.x, i = blockIdx.y;
+  if (j >= P.W || i >= P.H) return;
+  const float df = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(P.depth) + (int64_t)i * P.depth_pitch + 4 * (int64_t)j);
+  if (!(isfinite(df) && df > 0.0f)) return;
+  const double d = (double)df;
+  const double p[3] = {((j + 0.5) - P.cx) / P.fx * d, ((i + 0.5) - P.cy) / P.fy * d, d};
+  double r[3], u[2];
+  rotate(P.R, P.c, p, r);
+  r[2] = r[2] + P.shift;
+  if (!(r[2] >= P.zplane && r[2] > 0.0)) return;
+  project(P.Kn, r, r[2], u);
+  const double tx = floor(u[0]), ty = floor(u[1]);
+  const double lo = -(double)P.half, hi = (double)(P.S - 1 + P.half);
+  if (!(tx >= lo && tx <= hi && ty >= lo && ty <= hi)) return;           // NaN, infinite or no pixel of the footprint on the canvas
+  const int x = (int)tx, y = (int)ty;
+  const unsigned long long key = ((unsigned long long)__float_as_uint((float)r[2]) << 32) | (unsigned int)(i * P.W + j);
+  const int x0 = x - P.half > 0 ? x - P.half : 0, x1 = x + P.half < P.S - 1 ? x + P.half : P.S - 1;
+  const int y0 = y - P.half > 0 ? y - P.half : 0, y1 = y + P.half < P.S - 1 ? y + P.half : P.S - 1;
+  for (int yy = y0; yy <= y1; ++yy)
+    for (int xx = x0; xx <= x1; ++xx) {
+      // keys only ever fall, so a (possibly stale) read at or below this key proves the atomic would change nothing. Footprints of
+      // neighbouring points overlap, single pixels hardly: at point_size 1 the read costs more than it saves (profiles/scene_points)
+      unsigned long long* z = P.zbuf + (int64_t)yy * P.S + xx;
+      if (P.half == 0 || *z > key) atomicMin(z, key);
+    }
 }
 
 // Order-preserving compaction of the chunk [base, base + kThreads) into list[]; returns the count.
@@ -306,6 +366,18 @@ __global__ void __launch_bounds__(kThreads) scene_tiles(SceneArgs A) {
       c[ch] = V.front ? (int)((double)r[ch] * A.bw + (double)c[ch] * A.one_minus_bw) : r[ch];
   } else if (live && !V.front) {
     c[0] = c[1] = c[2] = A.early_return ? 255 : (on_grid ? 175 : 225);
+    if (A.zbuf) {                        // pass B of the point cloud: the nearest point's image colour, tinted by its box
+      const unsigned long long key = A.zbuf[(int64_t)y * V.W + x];
+      if (key != ~0ull) {
+        const unsigned int src = (unsigned int)key;
+        const int si = (int)(src / (unsigned int)A.img_w), sj = (int)(src % (unsigned int)A.img_w);
+        const uint8_t* ip = A.image + (int64_t)si * A.image_pitch + 3 * sj;
+        int b = -1;
+        if (A.labels) b = *reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(A.labels) + (int64_t)si * A.labels_pitch + 4 * (int64_t)sj);
+        const bool tinted = b >= 0 && b < A.n_boxes;
+        for (int ch = 0; ch < 3; ++ch) c[ch] = tinted ? ((int)ip[ch] + (int)A.tint[4 * b + ch] + 1) >> 1 : (int)ip[ch];
+      }
+    }
   }
   // 4. edges and labels in draw order
   if (!A.early_return) {
@@ -343,13 +415,6 @@ __global__ void __launch_bounds__(kThreads) scene_tiles(SceneArgs A) {
 }
 
 // -------------------------------------------------------------------------------------------------------------------- host
-
-inline void rotate(const double* R, const double* c, const double* p, double* r) {
-  const double d0 = p[0] - c[0], d1 = p[1] - c[1], d2 = p[2] - c[2];
-  r[0] = R[0] * d0 + R[1] * d1 + R[2] * d2;
-  r[1] = R[3] * d0 + R[4] * d1 + R[5] * d2;
-  r[2] = R[6] * d0 + R[7] * d1 + R[8] * d2;
-}
 
 // np.arange(start, stop) for floats: n = ceil(stop - start), values start + i * ((start + 1) - start)
 inline int64_t arange_len(double a, double b) {
@@ -435,11 +500,11 @@ struct GridCam {
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 struct Packing {
-  size_t boxes, kv, items[2], grid, glyphs, staged, tris[2], total;
+  size_t boxes, kv, items[2], grid, glyphs, tint, staged, tris[2], zbuf, total;
   int nitem_cap[2];
 };
 
-Packing plan(const OvmSceneLayout* L, int64_t glyph_bytes) {
+Packing plan(const OvmSceneLayout* L, int64_t glyph_bytes, bool points = false) {
   Packing p{};
   const int n = L->n_boxes;
   size_t o = 0;
@@ -448,8 +513,10 @@ Packing plan(const OvmSceneLayout* L, int64_t glyph_bytes) {
   for (int v = 0; v < 2; ++v) { p.nitem_cap[v] = 13 * n; p.items[v] = o; o = align256(o + sizeof(DItem) * (size_t)(13 * n)); }
   p.grid = o; o = align256(o + sizeof(DItem) * (size_t)L->n_grid);
   p.glyphs = o; o = align256(o + (size_t)glyph_bytes);
+  if (points) { p.tint = o; o = align256(o + 4 * (size_t)n); }
   p.staged = o;
   for (int v = 0; v < 2; ++v) { p.tris[v] = o; o = align256(o + sizeof(DTri) * 24 * (size_t)n); }
+  if (points) { p.zbuf = o; o = align256(o + sizeof(unsigned long long) * (size_t)L->view[1].height * (size_t)L->view[1].width); }
   p.total = o;
   return p;
 }
@@ -665,9 +732,24 @@ int ovm_render_scene_workspace(const OvmSceneLayout* layout, int64_t glyph_bytes
   return OVM_OK;
 }
 
-int ovm_render_scene(const OvmSceneLayout* L, const OvmSceneSegment* grid, const uint8_t* glyphs, int64_t glyph_bytes,
-                     const uint8_t* image, int64_t image_pitch, uint8_t* front, int64_t front_pitch, uint8_t* novel, int64_t novel_pitch,
-                     void* workspace, int64_t workspace_bytes, ovm_stream_t stream) {
+}  // extern "C"
+
+namespace {
+
+struct Points {          // the extra arguments of ovm_render_scene_points
+  const float* depth;
+  int64_t depth_pitch;
+  const int32_t* labels;
+  int64_t labels_pitch;
+  const double* R;
+  int32_t point_size;
+  uint64_t* zbuf_out;
+};
+
+// ovm_render_scene (pts null) and ovm_render_scene_points: every refusal comes before any device work.
+int render(const OvmSceneLayout* L, const OvmSceneSegment* grid, const uint8_t* glyphs, int64_t glyph_bytes, const uint8_t* image,
+           int64_t image_pitch, uint8_t* front, int64_t front_pitch, uint8_t* novel, int64_t novel_pitch, const Points* pts,
+           void* workspace, int64_t workspace_bytes, ovm_stream_t stream) {
   if (!layout_ok(L) || glyph_bytes < 0 || glyph_bytes != glyph_total(L) || (glyph_bytes > 0 && !glyphs) ||
       (L->n_grid > 0 && !grid) || !workspace)
     return OVM_ERR_INVALID;
@@ -675,7 +757,13 @@ int ovm_render_scene(const OvmSceneLayout* L, const OvmSceneSegment* grid, const
   const OvmSceneView& N = L->view[1];
   if (F.drawn && (!image || !front || image_pitch < 3 * (int64_t)F.width || front_pitch < 3 * (int64_t)F.width)) return OVM_ERR_INVALID;
   if (N.drawn && (!novel || novel_pitch < 3 * (int64_t)N.width)) return OVM_ERR_INVALID;
-  const Packing pk = plan(L, glyph_bytes);
+  if (pts) {
+    if (!F.drawn || !N.drawn || !pts->depth || !pts->R || !finite_all(pts->R, 9)) return OVM_ERR_INVALID;
+    if (pts->depth_pitch < 4 * (int64_t)F.width || (pts->depth_pitch & 3)) return OVM_ERR_INVALID;
+    if (pts->labels && (pts->labels_pitch < 4 * (int64_t)F.width || (pts->labels_pitch & 3))) return OVM_ERR_INVALID;
+    if (pts->point_size < 1 || pts->point_size > 9 || !(pts->point_size & 1)) return OVM_ERR_INVALID;
+  }
+  const Packing pk = plan(L, glyph_bytes, pts != nullptr);
   if (workspace_bytes < (int64_t)pk.total) return OVM_ERR_CAPACITY;
   const int n = L->n_boxes;
 
@@ -751,6 +839,8 @@ int ovm_render_scene(const OvmSceneLayout* L, const OvmSceneSegment* grid, const
     }
   }
   if (glyph_bytes > 0) std::memcpy(st + pk.glyphs, glyphs, (size_t)glyph_bytes);
+  if (pts)
+    for (int b = 0; b < n; ++b) std::memcpy(st + pk.tint + 4 * (size_t)b, L->edge_u8[b], 4);
 
   hipStream_t s = (hipStream_t)stream;
   uint8_t* ws = (uint8_t*)workspace;
@@ -791,9 +881,56 @@ int ovm_render_scene(const OvmSceneLayout* L, const OvmSceneSegment* grid, const
                                                    reinterpret_cast<const double*>(ws + pk.kv), reinterpret_cast<DTri*>(ws + pk.tris[0]),
                                                    reinterpret_cast<DTri*>(ws + pk.tris[1]), mask);
   }
+  if (pts) {
+    unsigned long long* zbuf = reinterpret_cast<unsigned long long*>(ws + pk.zbuf);
+    const size_t zbytes = sizeof(unsigned long long) * (size_t)N.height * (size_t)N.width;
+    if (hipMemsetAsync(zbuf, 0xff, zbytes, s) != hipSuccess) return OVM_ERR_HIP;
+    if (!L->early_return) {              // an empty grid draws the bare render: nothing is splatted
+      SplatArgs P{};
+      P.depth = pts->depth; P.depth_pitch = pts->depth_pitch; P.zbuf = zbuf;
+      P.H = F.height; P.W = F.width; P.S = N.width; P.half = (pts->point_size - 1) / 2;
+      P.fx = F.K[0]; P.cx = F.K[2]; P.fy = F.K[4]; P.cy = F.K[5];
+      std::memcpy(P.R, pts->R, sizeof P.R);
+      std::memcpy(P.c, L->center, sizeof P.c);
+      P.shift = L->zoom_bias * L->zoom_factor;
+      P.zplane = L->zplane;
+      std::memcpy(P.Kn, N.K, sizeof P.Kn);
+      scene_splat<<<dim3((unsigned)((F.width + kThreads - 1) / kThreads), (unsigned)F.height), kThreads, 0, s>>>(P);
+      A.zbuf = zbuf; A.labels = pts->labels; A.labels_pitch = pts->labels_pitch;
+      A.tint = ws + pk.tint; A.img_w = F.width; A.n_boxes = n;
+    }
+    if (pts->zbuf_out && hipMemcpyAsync(pts->zbuf_out, zbuf, zbytes, hipMemcpyDeviceToDevice, s) != hipSuccess) return OVM_ERR_HIP;
+  }
   const int tiles = A.v[0].tiles + A.v[1].tiles;
   if (tiles > 0) scene_tiles<<<tiles, kThreads, 0, s>>>(A);
   return hipGetLastError() == hipSuccess ? OVM_OK : OVM_ERR_HIP;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ovm_render_scene(const OvmSceneLayout* L, const OvmSceneSegment* grid, const uint8_t* glyphs, int64_t glyph_bytes,
+                     const uint8_t* image, int64_t image_pitch, uint8_t* front, int64_t front_pitch, uint8_t* novel, int64_t novel_pitch,
+                     void* workspace, int64_t workspace_bytes, ovm_stream_t stream) {
+  return render(L, grid, glyphs, glyph_bytes, image, image_pitch, front, front_pitch, novel, novel_pitch, nullptr, workspace,
+                workspace_bytes, stream);
+}
+
+int ovm_render_scene_points_workspace(const OvmSceneLayout* layout, int64_t glyph_bytes, int64_t* bytes) {
+  if (!layout_ok(layout) || glyph_bytes < 0 || !bytes || !layout->view[0].drawn || !layout->view[1].drawn) return OVM_ERR_INVALID;
+  *bytes = (int64_t)plan(layout, glyph_bytes, true).total;
+  return OVM_OK;
+}
+
+int ovm_render_scene_points(const OvmSceneLayout* L, const OvmSceneSegment* grid, const uint8_t* glyphs, int64_t glyph_bytes,
+                            const uint8_t* image, int64_t image_pitch, uint8_t* front, int64_t front_pitch, uint8_t* novel,
+                            int64_t novel_pitch, const float* depth, int64_t depth_pitch, const int32_t* labels, int64_t labels_pitch,
+                            const double* R, int32_t point_size, uint64_t* zbuf_out, void* workspace, int64_t workspace_bytes,
+                            ovm_stream_t stream) {
+  const Points pts{depth, depth_pitch, labels, labels_pitch, R, point_size, zbuf_out};
+  return render(L, grid, glyphs, glyph_bytes, image, image_pitch, front, front_pitch, novel, novel_pitch, &pts, workspace,
+                workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -308,7 +308,7 @@ EXPORTS = [
     "ovm_host_jpeg_info", "ovm_host_jpeg_entropy_decode", "ovm_jpeg_reconstruct",
     "ovm_host_jpeg_decode_plan", "ovm_jpeg_entropy_decode_workspace", "ovm_jpeg_entropy_decode", "ovm_host_jpeg_entropy_emulate",
     "ovm_host_jpeg_encode_plan", "ovm_jpeg_encode_workspace", "ovm_jpeg_forward", "ovm_jpeg_encode",
-    "ovm_host_scene_layout", "ovm_render_scene_workspace", "ovm_render_scene",
+    "ovm_host_scene_layout", "ovm_render_scene_workspace", "ovm_render_scene", "ovm_render_scene_points_workspace", "ovm_render_scene_points",
     "ovm_host_panels_layout", "ovm_render_panels_workspace", "ovm_render_panels",
     "ovm_geo_default_params", "ovm_geo_last_error", "ovm_geo_lift_workspace", "ovm_geo_lift", "ovm_geo_dbscan_workspace", "ovm_geo_dbscan",
     "ovm_host_geo_box",
@@ -364,6 +364,9 @@ def load() -> C.CDLL:
     lib.ovm_host_scene_layout.argtypes = [C.POINTER(OvmSceneInput), C.POINTER(OvmSceneLayout), vp, i32]
     lib.ovm_render_scene_workspace.argtypes = [C.POINTER(OvmSceneLayout), i64, C.POINTER(i64)]
     lib.ovm_render_scene.argtypes = [C.POINTER(OvmSceneLayout), vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
+    lib.ovm_render_scene_points_workspace.argtypes = [C.POINTER(OvmSceneLayout), i64, C.POINTER(i64)]
+    lib.ovm_render_scene_points.argtypes = [C.POINTER(OvmSceneLayout), vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
+                                            C.POINTER(C.c_double * 9), i32, vp, vp, i64, vp]
     lib.ovm_host_panels_layout.argtypes = [C.POINTER(OvmPanelsInput), C.POINTER(OvmPanelsLayout), vp, i32]
     lib.ovm_render_panels_workspace.argtypes = [C.POINTER(OvmPanelsLayout), C.POINTER(i64)]
     lib.ovm_render_panels.argtypes = [C.POINTER(OvmPanelsLayout), vp, vp, i64, vp, i64, vp, i64, vp, i64, vp]

@@ -112,18 +112,76 @@ def scene_layout(K, height: int, width: int, corners, colors, masks=None, scale:
         return lay, grid[:lay.n_grid]
 
 
+def _check_points(depth, point_size, labels, zbuf_out, hw, scale: int, mode: str) -> None:
+    """The argument checks of the point cloud; host only."""
+    if mode != "front_and_novel":
+        raise ValueError("draw_scene_view: the point cloud is the front image's depth in the novel view: mode must be front_and_novel")
+    if isinstance(point_size, bool) or not isinstance(point_size, (int, np.integer)) or not 1 <= point_size <= 9 or point_size % 2 == 0:
+        raise ValueError(f"draw_scene_view: point_size must be odd and in 1..9, is {point_size!r}")
+    for a, name, tdt, ndt in ((depth, "depth", torch.float32, np.float32), (labels, "point_labels", torch.int32, np.int32)):
+        if a is None:
+            continue
+        if torch.is_tensor(a):
+            if not a.is_cuda:
+                raise ValueError(f"draw_scene_view: {name} is a CPU tensor; pass a tensor on the HIP device, or a numpy array to upload")
+            ok = a.dtype == tdt
+        elif isinstance(a, np.ndarray):
+            ok = a.dtype == ndt
+        else:
+            raise ValueError(f"draw_scene_view: {name} must be a device tensor or a numpy array")
+        if not ok or tuple(a.shape) != tuple(hw):
+            raise ValueError(f"draw_scene_view: {name} must be {ndt.__name__} [{hw[0]}, {hw[1]}], is {a.dtype} {list(a.shape)}")
+    if zbuf_out is not None and not (torch.is_tensor(zbuf_out) and zbuf_out.is_cuda and zbuf_out.dtype == torch.int64 and
+                                     tuple(zbuf_out.shape) == (scale, scale) and zbuf_out.is_contiguous()):
+        raise ValueError(f"draw_scene_view: zbuf_out must be a contiguous device int64 [{scale}, {scale}] tensor")
+
+
+def _rows_on(a, device) -> torch.Tensor:
+    """A checked [H, W] map on the device with unit column stride (rows may be pitched: a column slice of a wider buffer)."""
+    t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+    t = t.to(device)
+    return t if t.stride(1) == 1 and t.stride(0) >= t.shape[1] else t.contiguous()
+
+
+def labels_from_masks(masks: torch.Tensor) -> torch.Tensor:
+    """uint8 (or bool) [n, H, W] device planes, nonzero = inside, to the int32 [H, W] map ``draw_scene_view(point_labels=...)`` takes: the
+    lowest plane index that covers the pixel, -1 where none does."""
+    if not torch.is_tensor(masks) or masks.dim() != 3 or masks.dtype not in (torch.uint8, torch.bool):
+        raise ValueError("labels_from_masks: masks must be uint8 or bool [n, H, W]")
+    n = masks.shape[0]
+    if n == 0:
+        return torch.full(tuple(masks.shape[1:]), -1, dtype=torch.int32, device=masks.device)
+    idx = torch.arange(n, dtype=torch.int32, device=masks.device).view(n, 1, 1)
+    first = torch.where(masks != 0, idx, torch.full_like(idx, n)).amin(0)
+    return torch.where(first < n, first, torch.full_like(first, -1))
+
+
 def draw_scene_view(im, K, corners, colors, text: Optional[Sequence[str]] = None, scale: int = 1000, R=None, T=None,
                     mode: str = "front_and_novel", blend_weight: float = 0.80, blend_weight_overlay: float = 1.0,
-                    ground_bounds=None, zplane: float = 0.05, device=None):
+                    ground_bounds=None, zplane: float = 0.05, device=None, depth=None, point_size: int = 3, point_labels=None,
+                    zbuf_out=None):
     """Draw the boxes into the image (front) and a top-down view of them (novel), on the device.
 
     im: BGR uint8 [H, W, 3], numpy or torch (a device tensor is used in place). corners: [n, 8, 3] camera-space corners in
     pred_bbox3D order. colors: [n, 3] in [0, 1] (component k lands in image channel k, as in the reference). text: one label per
     box or None. Returns device uint8 tensors: (front, novel) for 'front_and_novel' - when scale == H they are the two halves of
     one [H, W + scale, 3] buffer -, front for 'front', novel for 'novel'.
+
+    depth: None (the reference's picture, ``ovm_render_scene``), or the metric depth of ``im``, fp32 [H, W], a device tensor or a numpy
+    array to upload: the novel view then shows it as a point cloud under the boxes (``ovm_render_scene_points``; mode
+    'front_and_novel' only), each point a ``point_size`` (odd, 1..9) square in the image's colour at its pixel. point_labels: int32
+    [H, W] (``labels_from_masks``), the box index per pixel or -1: labelled points are tinted with their box's edge colour.
+    zbuf_out: a device int64 [scale, scale] tensor that receives the splat's key buffer (tests). A wrong dtype or shape, or a CPU
+    tensor, raises ValueError before any device call.
     """
     if mode not in MODES:
         raise ValueError(f"draw_scene_view: mode {mode!r} is not supported (front, novel, front_and_novel)")
+    if depth is None and (point_labels is not None or zbuf_out is not None):
+        raise ValueError("draw_scene_view: point_labels and zbuf_out belong to the point cloud: pass depth")
+    if depth is not None:
+        if not (torch.is_tensor(im) or isinstance(im, np.ndarray)) or im.ndim != 3:
+            raise ValueError("draw_scene_view: im must be uint8 [H, W, 3]")
+        _check_points(depth, point_size, point_labels, zbuf_out, (int(im.shape[0]), int(im.shape[1])), int(scale), mode)
     if device is None:
         device = im.device if torch.is_tensor(im) and im.is_cuda else torch.device("cuda", torch.cuda.current_device())
     device = torch.device(device)
@@ -148,7 +206,10 @@ def draw_scene_view(im, K, corners, colors, text: Optional[Sequence[str]] = None
     glyphs = np.ascontiguousarray(glyphs, np.uint8)
     L = _lib.load()
     ws_bytes = C.c_int64()
-    _lib.check(L.ovm_render_scene_workspace(C.byref(lay), glyphs.size, C.byref(ws_bytes)), what="ovm_render_scene_workspace")
+    if depth is not None:
+        _lib.check(L.ovm_render_scene_points_workspace(C.byref(lay), glyphs.size, C.byref(ws_bytes)), what="ovm_render_scene_points_workspace")
+    else:
+        _lib.check(L.ovm_render_scene_workspace(C.byref(lay), glyphs.size, C.byref(ws_bytes)), what="ovm_render_scene_workspace")
     want_f, want_n = bool(MODES[mode] & _lib.OVM_SCENE_FRONT), bool(MODES[mode] & _lib.OVM_SCENE_NOVEL)
     with torch.cuda.device(device):
         img = img.to(device, non_blocking=False).contiguous()
@@ -165,11 +226,22 @@ def draw_scene_view(im, K, corners, colors, text: Optional[Sequence[str]] = None
                 novel = torch.empty((S, S, 3), dtype=torch.uint8, device=device)
             fp, np_ = 3 * W, 3 * S
         stream = torch.cuda.current_stream(device)
-        rc = L.ovm_render_scene(C.byref(lay), grid.ctypes.data if len(grid) else None, glyphs.ctypes.data if glyphs.size else None,
-                                glyphs.size, img.data_ptr(), img.stride(0), front.data_ptr() if front is not None else None, fp,
-                                novel.data_ptr() if novel is not None else None, np_, ws.data_ptr(), ws.numel(),
-                                C.c_void_p(stream.cuda_stream))
-        _lib.check(rc, what="ovm_render_scene")
+        if depth is not None:
+            dep, lab = _rows_on(depth, device), (_rows_on(point_labels, device) if point_labels is not None else None)
+            Rn = (C.c_double * 9)(*_as_f64(euler2mat([np.pi / 3, 0, 0]) if R is None else R, (9,)).tolist())
+            rc = L.ovm_render_scene_points(C.byref(lay), grid.ctypes.data if len(grid) else None, glyphs.ctypes.data if glyphs.size else None,
+                                           glyphs.size, img.data_ptr(), img.stride(0), front.data_ptr(), fp, novel.data_ptr(), np_,
+                                           dep.data_ptr(), 4 * dep.stride(0), lab.data_ptr() if lab is not None else None,
+                                           4 * lab.stride(0) if lab is not None else 0, C.byref(Rn), int(point_size),
+                                           zbuf_out.data_ptr() if zbuf_out is not None else None, ws.data_ptr(), ws.numel(),
+                                           C.c_void_p(stream.cuda_stream))
+            _lib.check(rc, what="ovm_render_scene_points")
+        else:
+            rc = L.ovm_render_scene(C.byref(lay), grid.ctypes.data if len(grid) else None, glyphs.ctypes.data if glyphs.size else None,
+                                    glyphs.size, img.data_ptr(), img.stride(0), front.data_ptr() if front is not None else None, fp,
+                                    novel.data_ptr() if novel is not None else None, np_, ws.data_ptr(), ws.numel(),
+                                    C.c_void_p(stream.cuda_stream))
+            _lib.check(rc, what="ovm_render_scene")
     if mode == "front":
         return front
     if mode == "novel":
