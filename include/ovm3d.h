@@ -1175,6 +1175,76 @@ int ovm_depthpro_stage_ms(OvmDepthPro* dp, float* ms, int32_t n);
  * message in msg (capacity bytes). */
 int ovm_host_depthpro_check(const OvmDepthProConfig* cfg, char* msg, int32_t capacity);
 
+/* ---- the kernels of the SAM and Depth Pro engines one at a time (tests) ---------------------------------------------------------
+ * Each call is the launcher the engine itself uses (csrc/sam.hip, csrc/depthpro.hip), nothing else. Device pointers unless marked
+ * host; fp32 row-major; fp16 buffers are passed as uint16_t. None synchronises. An argument outside a kernel's contract is refused
+ * before anything is launched: OVM_ERR_INVALID for a null pointer or a non-positive count, OVM_ERR_SHAPE for the limits named below.
+ *
+ * get_dense_pe: pe [G*G][2 F] = [sin | cos](2 pi (2 c - 1) . gauss), c = ((j + 0.5) / G, (i + 0.5) / G) for row i * G + j; gauss [2][F]. */
+int ovm_op_sam_dense_pe(const float* gauss, int32_t G, int32_t F, float* pe, ovm_stream_t stream);
+/* Tokens of nb boxes: tok [nb][nout + 2][C] = out_tokens [nout][C], then the two box corners: boxes [nb][4] xyxy in the pixels of the
+ * H x W image, scaled by neww / W and newh / H (fp64), + 0.5, / S, encoded with gauss [2][C/2], + corner [2][C]. sparse [nb][2][C]
+ * receives the two corner rows as well. C % 2 != 0: OVM_ERR_SHAPE. */
+int ovm_op_sam_box_tokens(const float* boxes, int32_t nb, int32_t nout, int32_t C, const float* out_tokens, const float* gauss, const float* corner,
+                          int32_t H, int32_t W, int32_t newh, int32_t neww, int32_t S, float* tok, float* sparse, ovm_stream_t stream);
+/* x [M][D] <- gelu_erf(LayerNorm(x)), in place. D > 256: OVM_ERR_SHAPE. */
+int ovm_op_sam_ln_gelu(float* x, int64_t M, int32_t D, const float* gamma, const float* beta, float eps, ovm_stream_t stream);
+/* Image -> token attention, head dimension 16: q [nb * G2][ldq] and o [nb * G2][ldo] hold heads x 16 columns, k / v [nb * nt][ld];
+ * o = softmax_t(scale q . k_t) v over the nt tokens of the row's own box. OVM_ERR_SHAPE unless 1 <= nt <= 8, heads <= 16,
+ * 256 % heads == 0, G2 % (256 / heads) == 0, ldq, ld, ldo >= 16 heads and ldq % 4 == ldo % 4 == 0; q and o 16-byte aligned. */
+int ovm_op_sam_i2t_attn(const float* q, int32_t ldq, const float* k, const float* v, int32_t ld, int32_t nt, int32_t heads, int32_t G2, int32_t nb,
+                        float scale, float* o, int32_t ldo, ovm_stream_t stream);
+/* Hypernetwork product over the blocked upscaled map up [nb * G*G * 4][4 * C8]: pixel (4 i + 2 a + a2, 4 j + 2 b + b2) of box n is
+ * row (n * G*G + i * G + j) * 4 + a * 2 + b, columns (a2 * 2 + b2) * C8 .. + C8. out[n * out_box_stride + t * L*L + Y * L + X] =
+ * hyper[n * ld_hyper + (t0 + t) * C8 ..] . up[n][Y][X][:], t < ntk, L = 4 G. OVM_ERR_SHAPE unless C8 % 4 == 0, ld_hyper % 4 == 0,
+ * ld_hyper >= (t0 + ntk) * C8 and out_box_stride >= ntk * L*L. */
+int ovm_op_sam_mask_prod(const float* up, const float* hyper, int32_t ld_hyper, int32_t t0, int32_t ntk, int32_t C8, int32_t G, int32_t nb, float* out,
+                         int64_t out_box_stride, ovm_stream_t stream);
+/* postprocess_masks + threshold: out uint8 [nb][H][W] (any byte alignment) = bilinear(bilinear(logits L x L -> S x S)[:newh, :neww]
+ * -> H x W) > 0, plane n at logits + n * box_stride. newh or neww outside 1 .. S: OVM_ERR_SHAPE. */
+int ovm_op_sam_mask_out(const float* logits, int64_t box_stride, int32_t L, int32_t S, int32_t newh, int32_t neww, int32_t H, int32_t W, int32_t nb,
+                        uint8_t* out, ovm_stream_t stream);
+/* Patch rows hi (+ lo, may be NULL) [G*G][ld], column (py * P + px) * 3 + c -> out fp32 [3][G P][G P]. ld < 3 P^2: OVM_ERR_SHAPE. */
+int ovm_op_sam_unpatch(const uint16_t* hi, const uint16_t* lo, int32_t ld, int32_t G, int32_t P, float* out, ovm_stream_t stream);
+/* iou [n][3] = head [n][ldh] columns 1 .. 3. ldh < 4: OVM_ERR_SHAPE. */
+int ovm_op_sam_iou_slice(const float* head, int32_t ldh, int32_t n, float* iou, ovm_stream_t stream);
+/* out[i] = a[i] + b[i % bmod], i < n; b == NULL: out[i] = a[i % bmod]. n % 4 != 0 or bmod % 4 != 0: OVM_ERR_SHAPE. 16-byte aligned. */
+int ovm_op_sam_add_bcast(const float* a, const float* b, float* out, int64_t n, int64_t bmod, ovm_stream_t stream);
+
+/* uint8 image (H x W, 3 channels, element strides; flip: channel 2 - c) -> (x / 255 - 0.5) / 0.5 -> bilinear S x S = P0 [S][S][3], and
+ * F.interpolate(scale_factor 0.5 / 0.25) of it: P1 [S/2][S/2][3], P2 [S/4][S/4][3]. S % 4 != 0: OVM_ERR_SHAPE. */
+int ovm_op_dp_pyramid(const uint8_t* img, int32_t H, int32_t W, int64_t stride_h, int64_t stride_w, int64_t stride_c, int32_t flip, int32_t S, float* P0,
+                      float* P1, float* P2, ovm_stream_t stream);
+/* merge_patches: tok [crops][T][D], the n x n crops from crop0 on, each T = 1 + g*g tokens (token 0 skipped); the first crop of an
+ * axis keeps cells [0, g - pad), inner ones [pad, g - pad), the last [pad, g): a map of side Ms = n g - 2 (n - 1) pad, bilinearly
+ * resized to out x out when out != Ms, as split rows hi / lo (lo may be NULL) [out*out][D]. OVM_ERR_SHAPE unless D % 4 == 0,
+ * T >= 1 + g*g, 2 pad < g, pad == 0 for n == 1 and Ms as above. */
+int ovm_op_dp_merge(const float* tok, int32_t T, int32_t D, int32_t crop0, int32_t n, int32_t g, int32_t pad, int32_t Ms, int32_t out, uint16_t* hi,
+                    uint16_t* lo, ovm_stream_t stream);
+/* Split pixels hi + lo (lo may be NULL), pixel stride ld, [side*side] or (pad_in) the interior of [side + 2][side + 2] -> out fp32
+ * [side*side][C] and / or split(relu(value)) into the interior of p_hi / p_lo [side + 2][side + 2][C] (any may be NULL, not both out
+ * and p_hi). OVM_ERR_SHAPE unless C % 4 == 0, ld % 4 == 0 and ld >= C. */
+int ovm_op_dp_unsplit(const uint16_t* hi, const uint16_t* lo, int32_t side, int32_t C, int32_t ld, int32_t pad_in, float* out, uint16_t* p_hi,
+                      uint16_t* p_lo, ovm_stream_t stream);
+/* out [So][So][Cout] = relu(conv3x3 stride 2 pad 1 of in [Si][Si][Cin] + bias) + add[(oy * So + ox) * ld_add + co] (add may be NULL),
+ * So = (Si - 1) / 2 + 1, w [Cout][3][3][Cin]. Cin % 4 != 0, or ld_add < Cout: OVM_ERR_SHAPE. */
+int ovm_op_dp_conv_s2(const float* in, int32_t Si, int32_t Cin, const float* w, const float* bias, int32_t Cout, const float* add, int32_t ld_add,
+                      float* out, ovm_stream_t stream);
+/* out[0] = bias[0] + sum_i in[i] w[i], i < n */
+int ovm_op_dp_dot(const float* in, const float* w, const float* bias, int32_t n, float* out, ovm_stream_t stream);
+/* The depth head's tail on the matrix cores: out [S][S] = relu(b2 + w2 . relu(b1 + conv3x3(in))) with in = hi (+ lo at precision 3)
+ * zero-bordered [S + 2][S + 2][C] and w_hi (+ w_lo) fp16 [32][9 C], k = (ky * 3 + kx) * C + c. S % 16 != 0 or C % 32 != 0: OVM_ERR_SHAPE. */
+int ovm_op_dp_head_tail(const uint16_t* hi, const uint16_t* lo, int32_t S, int32_t C, const uint16_t* w_hi, const uint16_t* w_lo, const float* b1,
+                        const float* w2, const float* b2, int32_t precision, float* out, ovm_stream_t stream);
+/* Zeroes the one-pixel frame of n <= 24 images hi[i] (+ lo[i]; lo or lo[i] may be NULL) [side[i] + 2][side[i] + 2][C[i]]; hi, lo, side, C: host
+ * arrays. C[i] % 8 != 0 or n > 24: OVM_ERR_SHAPE. */
+int ovm_op_dp_clear_borders(uint16_t* const* hi, uint16_t* const* lo, const int32_t* side, const int32_t* C, int32_t n, ovm_stream_t stream);
+/* post_process_depth_estimation: f = f_px when > 0, else 0.5 W / tan(0.5 deg2rad(fov_deg[0])); depth [H][W] = 1 / clamp(bilinear S x S
+ * -> H x W of canon * W / f, 1e-4, 1e4). fov_out / f_out (may be NULL) receive fov_deg[0] (0 when fov_deg is NULL) and f. f_px <= 0
+ * with fov_deg NULL: OVM_ERR_INVALID. */
+int ovm_op_dp_depth_out(const float* canon, int32_t S, int32_t H, int32_t W, float f_px, const float* fov_deg, float* depth, float* fov_out, float* f_out,
+                        ovm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -373,8 +373,66 @@ int convt(OvmDepthPro* m, const SplitImg& A, int lda, int side, const PackedLin&
   return launch_gemm(p, m->cfg.precision, EPI_CONVT, A_ROWMAJOR, s);
 }
 
+// ---- launchers of the kernels above: the engine and the per-kernel entry points at the end of the file fill every launch here. A
+// precondition the engine guarantees by its configuration is checked again, before the launch.
+
 int unsplit(const SplitImg& A, int side, int C, int ld, bool pad_in, float* out, const SplitImg& P, hipStream_t s) {
+  if (C < 4 || C % 4 != 0 || ld % 4 != 0 || ld < C) return OVM_ERR_SHAPE;
   hipLaunchKernelGGL(dp_unsplit_kernel, g1((long)side * side * (C / 4)), dim3(256), 0, s, A.hi, A.lo, side, C, ld, pad_in ? 1 : 0, out, P.hi, P.lo);
+  return last_launch();
+}
+
+// a thread owns a 4 x 4 block of level 0
+int launch_pyramid(const uint8_t* img, int H, int W, int64_t sH, int64_t sW, int64_t sC, int flip, int S, float* P0, float* P1, float* P2, hipStream_t s) {
+  if (S < 4 || S % 4 != 0) return OVM_ERR_SHAPE;
+  hipLaunchKernelGGL(dp_pyramid_kernel, g1((long)(S / 4) * (S / 4) * 3), dim3(256), 0, s, img, H, W, sH, sW, sC, flip, S, P0, P1, P2);
+  return last_launch();
+}
+
+int launch_merge(const float* tok, int T, int D, int crop0, int n, int g, int pad, int Ms, int out, half_t* Ohi, half_t* Olo, hipStream_t s) {
+  if (D < 4 || D % 4 != 0) return OVM_ERR_SHAPE;
+  hipLaunchKernelGGL(dp_merge_kernel, g1((long)out * out * (D / 4)), dim3(256), 0, s, tok, T, D, crop0, n, g, pad, Ms, out, Ohi, Olo);
+  return last_launch();
+}
+
+// So = the side a 3x3 stride-2 pad-1 convolution leaves of Si
+int launch_conv_s2(const float* in, int Si, int Cin, const float* w, const float* bias, int So, int Cout, const float* add, int ld_add, float* out, hipStream_t s) {
+  if (Cin < 4 || Cin % 4 != 0 || So != (Si - 1) / 2 + 1) return OVM_ERR_SHAPE;
+  hipLaunchKernelGGL(dp_conv_s2_kernel, g1((long)So * So * Cout), dim3(256), 0, s, in, Si, Cin, w, bias, So, Cout, add, ld_add, out);
+  return last_launch();
+}
+
+int launch_dot(const float* in, const float* w, const float* bias, int n, float* out, hipStream_t s) {
+  hipLaunchKernelGGL(dp_dot_kernel, dim3(1), dim3(256), 0, s, in, w, bias, n, out);
+  return last_launch();
+}
+
+// a workgroup owns 16 x 16 pixels, a k-step 32 channels
+int launch_head_tail(const SplitImg& in, int S, int C, const half_t* whi, const half_t* wlo, const float* b1, const float* w2, const float* b2, int precision,
+                     float* out, hipStream_t s) {
+  if (S < 16 || S % 16 != 0 || C < 32 || C % 32 != 0) return OVM_ERR_SHAPE;
+  if (precision == 3)
+    hipLaunchKernelGGL(dp_head_tail_kernel<3>, dim3(S / 16, S / 16), dim3(256), 0, s, in.hi, in.lo, S, C, whi, wlo, b1, w2, b2, out);
+  else
+    hipLaunchKernelGGL(dp_head_tail_kernel<1>, dim3(S / 16, S / 16), dim3(256), 0, s, in.hi, in.lo, S, C, whi, wlo, b1, w2, b2, out);
+  return last_launch();
+}
+
+// a thread clears 8 channels of one frame pixel
+int launch_clear_borders(const BorderList& bl, hipStream_t s) {
+  if (bl.n < 1 || bl.n > kMaxBordered) return OVM_ERR_SHAPE;
+  int mx = 0;
+  for (int i = 0; i < bl.n; ++i) {
+    if (bl.b[i].side < 1 || bl.b[i].C < 8 || bl.b[i].C % 8 != 0) return OVM_ERR_SHAPE;
+    const int n = 4 * (bl.b[i].side + 1) * (bl.b[i].C / 8);
+    if (n > mx) mx = n;
+  }
+  hipLaunchKernelGGL(dp_clear_borders_kernel, dim3((mx + 255) / 256, bl.n), dim3(256), 0, s, bl);
+  return last_launch();
+}
+
+int launch_depth_out(const float* canon, int S, int H, int W, float f_given, const float* fov, float* depth, float* fov_out, float* f_out, hipStream_t s) {
+  hipLaunchKernelGGL(dp_depth_out_kernel, g1((long)H * W), dim3(256), 0, s, canon, S, H, W, f_given, fov, depth, fov_out, f_out);
   return last_launch();
 }
 
@@ -656,10 +714,7 @@ int ovm_depthpro_infer(OvmDepthPro* m, const OvmImage* image, int32_t flip_bgr, 
   m->ev_valid = false;
   OVM_TRY(m, stamp(0));
   {
-    int mx = 0;
-    for (int i = 0; i < pl.borders.n; ++i) { const int n = 4 * (pl.borders.b[i].side + 1) * (pl.borders.b[i].C / 8); if (n > mx) mx = n; }
-    hipLaunchKernelGGL(dp_clear_borders_kernel, dim3((mx + 255) / 256, pl.borders.n), dim3(256), 0, s, pl.borders);
-    OVM_TRY(m, last_launch());
+    OVM_TRY(m, launch_clear_borders(pl.borders, s));
     if (k64(F / 2) != F / 2) {                            // F / 2 = 32: H1's rows carry 32 pad columns, which the next GEMM reads
       const size_t hb = (size_t)m->side[4] * m->side[4] * k64(F / 2) * 2;
       OVM_HIP(m, hipMemsetAsync(pl.H1.hi, 0, hb, s));
@@ -667,9 +722,7 @@ int ovm_depthpro_infer(OvmDepthPro* m, const OvmImage* image, int32_t flip_bgr, 
     }
   }
   // ---- 1. preprocess + pyramid
-  hipLaunchKernelGGL(dp_pyramid_kernel, g1((long)(S / 4) * (S / 4) * 3), dim3(256), 0, s, (const uint8_t*)image->data, H, W, image->stride_h, image->stride_w,
-                     image->stride_c, flip_bgr ? 1 : 0, S, pl.P0, pl.P1, pl.P2);
-  OVM_TRY(m, last_launch());
+  OVM_TRY(m, launch_pyramid((const uint8_t*)image->data, H, W, image->stride_h, image->stride_w, image->stride_c, flip_bgr ? 1 : 0, S, pl.P0, pl.P1, pl.P2, s));
   OVM_TRY(m, stamp(1));
   // ---- 2. towers: 35 crops as one batch (high resolution first), the whole image at the crop side for the other two
   {
@@ -695,9 +748,7 @@ int ovm_depthpro_infer(OvmDepthPro* m, const OvmImage* image, int32_t flip_bgr, 
     struct { const float* tok; int crop0, lvl; } src[6] = {{pl.TOKI, 0, 2}, {pl.TOK, c_low, 2}, {pl.TOK, c_med, 1}, {pl.TOK, c_hi, 0}, {pl.TAP[0], c_hi, 0}, {pl.TAP[1], c_hi, 0}};
     for (int i = 0; i < 6; ++i) {
       const int l = src[i].lvl, out = q.out[l];
-      hipLaunchKernelGGL(dp_merge_kernel, g1((long)out * out * (D / 4)), dim3(256), 0, s, src[i].tok, T, D, src[i].crop0, q.ncrop[l], g, q.pad[l], q.merged[l], out,
-                         pl.FEAT[i].hi, pl.FEAT[i].lo);
-      OVM_TRY(m, last_launch());
+      OVM_TRY(m, launch_merge(src[i].tok, T, D, src[i].crop0, q.ncrop[l], g, q.pad[l], q.merged[l], out, pl.FEAT[i].hi, pl.FEAT[i].lo, s));
     }
   }
   // ---- 4. neck
@@ -752,34 +803,24 @@ int ovm_depthpro_infer(OvmDepthPro* m, const OvmImage* image, int32_t flip_bgr, 
     const int sd = m->side[4], C = F / 2;
     OVM_TRY(m, conv3(m, pl.FUSEDP, sd, F, m->head0, 0, nullptr, nullptr, nullptr, pl.H1, k64(C), false, false, s));
     OVM_TRY(m, convt(m, pl.H1, k64(C), sd, m->head1, pl.H2, C, true, s));
-    if (c.precision == 3)
-      hipLaunchKernelGGL(dp_head_tail_kernel<3>, dim3(S / 16, S / 16), dim3(256), 0, s, pl.H2.hi, pl.H2.lo, S, C, m->tail_whi, m->tail_wlo, m->tail_b, m->tail_w2, m->tail_b2, pl.CANON);
-    else
-      hipLaunchKernelGGL(dp_head_tail_kernel<1>, dim3(S / 16, S / 16), dim3(256), 0, s, pl.H2.hi, pl.H2.lo, S, C, m->tail_whi, m->tail_wlo, m->tail_b, m->tail_w2, m->tail_b2, pl.CANON);
-    OVM_TRY(m, last_launch());
+    OVM_TRY(m, launch_head_tail(pl.H2, S, C, m->tail_whi, m->tail_wlo, m->tail_b, m->tail_w2, m->tail_b2, c.precision, pl.CANON, s));
   }
   OVM_TRY(m, stamp(5));
   // ---- 7. field of view
   if (c.use_fov) {
     const PackedLin& nk = m->fov_neck;
     OVM_TRY(m, ovm_g_linear(pl.TOKF, D, T, D, (const uint16_t*)nk.hi, (const uint16_t*)nk.lo, nk.N, nk.Kpad, nk.bias, 0, nullptr, 0, pl.FOVF, F / 2, c.precision, s));
-    hipLaunchKernelGGL(dp_conv_s2_kernel, g1((long)g * g * (F / 2)), dim3(256), 0, s, pl.NECK[0], 2 * g, F, m->fov_conv.w, m->fov_conv.b, g, F / 2,
-                       pl.FOVF + F / 2 /* the class token's row is dropped */, F / 2, pl.FV[0]);
-    OVM_TRY(m, last_launch());
+    OVM_TRY(m, launch_conv_s2(pl.NECK[0], 2 * g, F, m->fov_conv.w, m->fov_conv.b, g, F / 2, pl.FOVF + F / 2 /* the class token's row is dropped */, F / 2,
+                              pl.FV[0], s));
     for (int i = 0; i < c.num_fov_layers; ++i) {
       const DirectConv& d = m->fov_head[i];
-      hipLaunchKernelGGL(dp_conv_s2_kernel, g1((long)m->fov_side[i + 1] * m->fov_side[i + 1] * d.Cout), dim3(256), 0, s, pl.FV[i], m->fov_side[i], d.Cin, d.w, d.b,
-                         m->fov_side[i + 1], d.Cout, (const float*)nullptr, 0, pl.FV[i + 1]);
-      OVM_TRY(m, last_launch());
+      OVM_TRY(m, launch_conv_s2(pl.FV[i], m->fov_side[i], d.Cin, d.w, d.b, m->fov_side[i + 1], d.Cout, nullptr, 0, pl.FV[i + 1], s));
     }
-    hipLaunchKernelGGL(dp_dot_kernel, dim3(1), dim3(256), 0, s, pl.FV[c.num_fov_layers], m->fov_fw, m->fov_fb, m->fov_k * m->fov_k * m->fov_fc, pl.FOV);
-    OVM_TRY(m, last_launch());
+    OVM_TRY(m, launch_dot(pl.FV[c.num_fov_layers], m->fov_fw, m->fov_fb, m->fov_k * m->fov_k * m->fov_fc, pl.FOV, s));
   }
   OVM_TRY(m, stamp(6));
   // ---- 8. metres
-  hipLaunchKernelGGL(dp_depth_out_kernel, g1((long)H * W), dim3(256), 0, s, pl.CANON, S, H, W, f_px > 0.f ? f_px : 0.f, c.use_fov ? pl.FOV : (const float*)nullptr,
-                     depth_out, fov_deg_out, f_px_out);
-  OVM_TRY(m, last_launch());
+  OVM_TRY(m, launch_depth_out(pl.CANON, S, H, W, f_px > 0.f ? f_px : 0.f, c.use_fov ? pl.FOV : (const float*)nullptr, depth_out, fov_deg_out, f_px_out, s));
   OVM_TRY(m, stamp(7));
   m->ev_valid = m->prof;
   m->last = pl; m->has_last = true;
@@ -828,6 +869,63 @@ int64_t ovm_depthpro_debug_copy(OvmDepthPro* m, const char* name, float* dst, in
   if (cnt > capacity) return OVM_ERR_CAPACITY;
   if (hipMemcpyAsync(dst, src, (size_t)cnt * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return OVM_ERR_HIP;
   return cnt;
+}
+
+// The kernels of this file one at a time (tests): the arguments are checked, then the engine's own launcher is called. None synchronises.
+int ovm_op_dp_pyramid(const uint8_t* img, int32_t H, int32_t W, int64_t stride_h, int64_t stride_w, int64_t stride_c, int32_t flip, int32_t S, float* P0,
+                      float* P1, float* P2, ovm_stream_t stream) {
+  if (!img || !P0 || !P1 || !P2 || H < 1 || W < 1) return OVM_ERR_INVALID;
+  return launch_pyramid(img, H, W, stride_h, stride_w, stride_c, flip ? 1 : 0, S, P0, P1, P2, (hipStream_t)stream);
+}
+
+int ovm_op_dp_merge(const float* tok, int32_t T, int32_t D, int32_t crop0, int32_t n, int32_t g, int32_t pad, int32_t Ms, int32_t out, uint16_t* hi,
+                    uint16_t* lo, ovm_stream_t stream) {
+  if (!tok || !hi || crop0 < 0 || n < 1 || g < 1 || pad < 0 || out < 1) return OVM_ERR_INVALID;
+  if (n == 1 && pad != 0) return OVM_ERR_SHAPE;
+  if (T < 1 + g * g || 2 * pad >= g || Ms != n * g - 2 * (n - 1) * pad) return OVM_ERR_SHAPE;
+  return launch_merge(tok, T, D, crop0, n, g, pad, Ms, out, (half_t*)hi, (half_t*)lo, (hipStream_t)stream);
+}
+
+int ovm_op_dp_unsplit(const uint16_t* hi, const uint16_t* lo, int32_t side, int32_t C, int32_t ld, int32_t pad_in, float* out, uint16_t* p_hi,
+                      uint16_t* p_lo, ovm_stream_t stream) {
+  if (!hi || side < 1 || (!out && !p_hi) || (p_lo && !p_hi)) return OVM_ERR_INVALID;
+  return unsplit(SplitImg{(half_t*)hi, (half_t*)lo}, side, C, ld, pad_in != 0, out, SplitImg{(half_t*)p_hi, (half_t*)p_lo}, (hipStream_t)stream);
+}
+
+int ovm_op_dp_conv_s2(const float* in, int32_t Si, int32_t Cin, const float* w, const float* bias, int32_t Cout, const float* add, int32_t ld_add,
+                      float* out, ovm_stream_t stream) {
+  if (!in || !w || !bias || !out || Si < 1 || Cout < 1) return OVM_ERR_INVALID;
+  if (add && ld_add < Cout) return OVM_ERR_SHAPE;
+  return launch_conv_s2(in, Si, Cin, w, bias, (Si - 1) / 2 + 1, Cout, add, ld_add, out, (hipStream_t)stream);
+}
+
+int ovm_op_dp_dot(const float* in, const float* w, const float* bias, int32_t n, float* out, ovm_stream_t stream) {
+  if (!in || !w || !bias || !out || n < 1) return OVM_ERR_INVALID;
+  return launch_dot(in, w, bias, n, out, (hipStream_t)stream);
+}
+
+int ovm_op_dp_head_tail(const uint16_t* hi, const uint16_t* lo, int32_t S, int32_t C, const uint16_t* w_hi, const uint16_t* w_lo, const float* b1,
+                        const float* w2, const float* b2, int32_t precision, float* out, ovm_stream_t stream) {
+  if (!hi || !w_hi || !b1 || !w2 || !b2 || !out || (precision != 1 && precision != 3) || (precision == 3 && (!lo || !w_lo))) return OVM_ERR_INVALID;
+  return launch_head_tail(SplitImg{(half_t*)hi, (half_t*)lo}, S, C, (const half_t*)w_hi, (const half_t*)w_lo, b1, w2, b2, precision, out, (hipStream_t)stream);
+}
+
+int ovm_op_dp_clear_borders(uint16_t* const* hi, uint16_t* const* lo, const int32_t* side, const int32_t* C, int32_t n, ovm_stream_t stream) {
+  if (!hi || !side || !C || n < 1) return OVM_ERR_INVALID;
+  if (n > kMaxBordered) return OVM_ERR_SHAPE;
+  BorderList bl; memset(&bl, 0, sizeof(bl));
+  bl.n = n;
+  for (int i = 0; i < n; ++i) {
+    if (!hi[i]) return OVM_ERR_INVALID;
+    bl.b[i] = Bordered{(half_t*)hi[i], lo ? (half_t*)lo[i] : nullptr, side[i], C[i]};
+  }
+  return launch_clear_borders(bl, (hipStream_t)stream);
+}
+
+int ovm_op_dp_depth_out(const float* canon, int32_t S, int32_t H, int32_t W, float f_px, const float* fov_deg, float* depth, float* fov_out, float* f_out,
+                        ovm_stream_t stream) {
+  if (!canon || !depth || S < 1 || H < 1 || W < 1 || (!(f_px > 0.f) && !fov_deg)) return OVM_ERR_INVALID;
+  return launch_depth_out(canon, S, H, W, f_px > 0.f ? f_px : 0.f, fov_deg, depth, fov_out, f_out, (hipStream_t)stream);
 }
 
 }  // extern "C"

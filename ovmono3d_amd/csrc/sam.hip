@@ -292,8 +292,75 @@ int lin(OvmSam* m, const PackedLin& w, const float* x, int ldx, long M, int act,
   return ovm_g_linear(x, ldx, (int)M, w.K, (const uint16_t*)w.hi, (const uint16_t*)w.lo, w.N, w.Kpad, w.bias, act, res, ldr, y, ldy, m->cfg.precision, s);
 }
 
+// ---- launchers: the engine and the per-kernel entry points at the end of the file fill every launch here. A precondition the engine
+// guarantees by its configuration is checked again, before the launch, so that a call outside it is an error and not a partial result.
+
+// out[i] = a[i] + b[i % bmod]; the kernels move float4s: n and bmod are multiples of 4
 int add_bcast(const float* a, const float* b, float* out, long n, long bmod, hipStream_t s) {
+  if (n < 0 || bmod < 4 || n % 4 != 0 || bmod % 4 != 0) return OVM_ERR_SHAPE;
+  if (n == 0) return OVM_OK;
   hipLaunchKernelGGL(sam_add_bcast_kernel, g1(n / 4), dim3(256), 0, s, (const float4*)a, (const float4*)b, (float4*)out, n / 4, bmod / 4);
+  return last_launch();
+}
+
+// out[i] = b[i % bmod]
+int bcast(const float* b, float* out, long n, long bmod, hipStream_t s) {
+  if (n < 0 || bmod < 4 || n % 4 != 0 || bmod % 4 != 0) return OVM_ERR_SHAPE;
+  if (n == 0) return OVM_OK;
+  hipLaunchKernelGGL(sam_bcast_kernel, g1(n / 4), dim3(256), 0, s, (const float4*)b, (float4*)out, n / 4, bmod / 4);
+  return last_launch();
+}
+
+int launch_dense_pe(const float* gauss, int G, int F, float* pe, hipStream_t s) {
+  hipLaunchKernelGGL(sam_dense_pe_kernel, g1((long)G * G * F), dim3(256), 0, s, gauss, G, F, pe);
+  return last_launch();
+}
+
+// boxes in the pixels of the H x W image; ResizeLongestSide's frame is newh x neww inside S x S
+int launch_box_tokens(const float* boxes, int nb, int nout, int C, const float* out_tokens, const float* gauss, const float* corner, int H, int W, int newh,
+                      int neww, int S, float* tok, float* sparse, hipStream_t s) {
+  hipLaunchKernelGGL(sam_box_tokens_kernel, g1((long)nb * (nout + 2) * (C / 2)), dim3(256), 0, s, boxes, nb, nout, C, out_tokens, gauss, corner,
+                     (double)neww / (double)W, (double)newh / (double)H, (float)S, tok, sparse);
+  return last_launch();
+}
+
+// one wave holds a row in four registers per lane: D <= 256
+int launch_ln_gelu(float* x, long M, int D, const float* g, const float* b, float eps, hipStream_t s) {
+  if (D < 1 || D > 256) return OVM_ERR_SHAPE;
+  hipLaunchKernelGGL(sam_ln_gelu_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, x, M, D, g, b, eps);
+  return last_launch();
+}
+
+// head dimension 16; a workgroup's 256 / heads pixels belong to one box and its LDS holds kMaxTok tokens of 256 columns
+int launch_i2t_attn(const float* q, int ldq, const float* k, const float* v, int ld, int nt, int heads, int G2, int nb, float scale, float* o, int ldo,
+                    hipStream_t s) {
+  if (nt < 1 || nt > kMaxTok || heads < 1 || heads > 16 || 256 % heads != 0 || G2 < 1 || G2 % (256 / heads) != 0) return OVM_ERR_SHAPE;
+  if (ldq < heads * 16 || ld < heads * 16 || ldo < heads * 16 || ldq % 4 != 0 || ldo % 4 != 0) return OVM_ERR_SHAPE;
+  const long rows = (long)nb * G2;
+  hipLaunchKernelGGL(sam_i2t_attn_kernel<16>, dim3((unsigned)(rows / (256 / heads))), dim3(256), 0, s, q, ldq, k, v, ld, nt, heads, G2, rows, scale, o, ldo);
+  return last_launch();
+}
+
+int launch_mask_prod(const float* up, const float* hyper, int ld_hyper, int t0, int ntk, int C8, int G, int nb, float* out, long out_box_stride, hipStream_t s) {
+  if (C8 < 4 || C8 % 4 != 0 || ld_hyper % 4 != 0) return OVM_ERR_SHAPE;
+  const long total = (long)nb * G * G * 16;
+  hipLaunchKernelGGL(sam_mask_prod_kernel, g1(total), dim3(256), 0, s, up, hyper, ld_hyper, t0, ntk, C8, G, total, out, out_box_stride);
+  return last_launch();
+}
+
+int launch_mask_out(const float* logits, long box_stride, int L, int S, int newh, int neww, int H, int W, int nb, uint8_t* out, hipStream_t s) {
+  const long total = (long)nb * H * W;
+  hipLaunchKernelGGL(sam_mask_out_kernel, g1((total + 3) / 4), dim3(256), 0, s, logits, box_stride, L, S, newh, neww, H, W, total, out);
+  return last_launch();
+}
+
+int launch_unpatch(const half_t* hi, const half_t* lo, int ld, int G, int P, float* out, hipStream_t s) {
+  hipLaunchKernelGGL(sam_unpatch_kernel, g1((long)3 * G * P * G * P), dim3(256), 0, s, hi, lo, ld, G, P, out);
+  return last_launch();
+}
+
+int launch_iou_slice(const float* head, int ldh, int n, float* iou, hipStream_t s) {
+  hipLaunchKernelGGL(sam_iou_slice_kernel, g1((long)n * 3), dim3(256), 0, s, head, ldh, n, iou);
   return last_launch();
 }
 
@@ -332,12 +399,9 @@ int decode_chunk(OvmSam* m, const float* boxes, int nb, int mask_index, uint8_t*
   const int C = m->C, nt = m->nt, G2 = m->G2, I = m->I, nout = 1 + c.num_mask_tokens;
   const long Mt = (long)nb * nt, Mi = (long)nb * G2;
   // 1. tokens + sparse embeddings; src = (embedding + no_mask_embed) per box
-  hipLaunchKernelGGL(sam_box_tokens_kernel, g1(Mt * (C / 2)), dim3(256), 0, s, boxes, nb, nout, C, m->out_tokens, m->gauss, m->corner,
-                     (double)m->neww / (double)m->W, (double)m->newh / (double)m->H, (float)m->S, w.tok0, m->dbg_sparse);
-  OVM_TRY(m, last_launch());
+  OVM_TRY(m, launch_box_tokens(boxes, nb, nout, C, m->out_tokens, m->gauss, m->corner, m->H, m->W, m->newh, m->neww, m->S, w.tok0, m->dbg_sparse, s));
   OVM_HIP(m, hipMemcpyAsync(w.q, w.tok0, (size_t)Mt * C * 4, hipMemcpyDeviceToDevice, s));
-  hipLaunchKernelGGL(sam_bcast_kernel, g1(Mi * C / 4), dim3(256), 0, s, (const float4*)m->src0, (float4*)w.keys, Mi * C / 4, (long)G2 * C / 4);
-  OVM_TRY(m, last_launch());
+  OVM_TRY(m, bcast(m->src0, w.keys, Mi * C, (long)G2 * C, s));
   auto norm = [&](const Norm& n, const float* x, long M, float* y) { return ovm_g_layernorm(x, nullptr, (int)M, C, n.g, n.b, kDecEps, y, s); };
   // token -> image attention of one block (also the final one): q += out_proj(attn(q + pe_q, keys + pe_k, keys)), then the norm
   auto tok_to_img = [&](const Attn& a, const Norm& n) -> int {
@@ -371,9 +435,7 @@ int decode_chunk(OvmSam* m, const float* boxes, int nb, int mask_index, uint8_t*
     OVM_TRY(m, lin(m, y.i2t.q, w.kpe, C, Mi, 0, nullptr, 0, w.iA, I, s));
     OVM_TRY(m, lin(m, y.i2t.k, w.qpe, C, Mt, 0, nullptr, 0, w.tk, I, s));
     OVM_TRY(m, lin(m, y.i2t.v, w.q, C, Mt, 0, nullptr, 0, w.tv, I, s));
-    hipLaunchKernelGGL(sam_i2t_attn_kernel<16>, dim3((unsigned)(Mi / (256 / c.dec_heads))), dim3(256), 0, s, w.iA, I, w.tk, w.tv, I, nt, c.dec_heads, G2, Mi,
-                       0.25f, w.iB, I);
-    OVM_TRY(m, last_launch());
+    OVM_TRY(m, launch_i2t_attn(w.iA, I, w.tk, w.tv, I, nt, c.dec_heads, G2, nb, 0.25f, w.iB, I, s));
     OVM_TRY(m, lin(m, y.i2t.o, w.iB, I, Mi, 0, w.keys, C, w.tmp, C, s));
     OVM_TRY(m, norm(y.n4, w.tmp, Mi, w.keys));
   }
@@ -383,8 +445,7 @@ int decode_chunk(OvmSam* m, const float* boxes, int nb, int mask_index, uint8_t*
   // 4. upscaling: ConvT . LayerNorm2d . GELU . ConvT . GELU as GEMMs over source pixels (blocked layout: file header)
   const int C4 = C / 4, C8 = C / 8;
   OVM_TRY(m, lin(m, m->up1, w.keys, C, Mi, 0, nullptr, 0, w.tmp, C, s));
-  hipLaunchKernelGGL(sam_ln_gelu_kernel, dim3((unsigned)((Mi * 4 + 3) / 4)), dim3(256), 0, s, w.tmp, Mi * 4, C4, m->upn.g, m->upn.b, kLn2dEps);
-  OVM_TRY(m, last_launch());
+  OVM_TRY(m, launch_ln_gelu(w.tmp, Mi * 4, C4, m->upn.g, m->upn.b, kLn2dEps, s));
   OVM_TRY(m, lin(m, m->up2, w.tmp, C4, Mi * 4, 2, nullptr, 0, w.up2, 4 * C8, s));
   // hypernetwork MLPs (every mask token when the low-resolution logits are asked for, else the requested one) and the IoU head
   const int t_first = lowres ? 0 : 1 + mask_index, t_last = lowres ? c.num_mask_tokens : 2 + mask_index;
@@ -402,19 +463,14 @@ int decode_chunk(OvmSam* m, const float* boxes, int nb, int mask_index, uint8_t*
       OVM_TRY(m, lin(m, m->iou[i], x, ldx, nb, last ? 0 : 1, nullptr, 0, y, ldy, s));
       x = y; ldx = ldy;
     }
-    if (iou) { hipLaunchKernelGGL(sam_iou_slice_kernel, g1(nb * 3), dim3(256), 0, s, w.iouh, 128, nb, iou); OVM_TRY(m, last_launch()); }
+    if (iou) OVM_TRY(m, launch_iou_slice(w.iouh, 128, nb, iou, s));
   }
   // mask product: multimask slice 1:4 into `lowres`, or the requested token alone into the workspace
   const long LL = (long)m->L * m->L;
   float* planes = lowres ? lowres : w.low; const long stride = lowres ? 3 * LL : LL;
-  hipLaunchKernelGGL(sam_mask_prod_kernel, g1(Mi * 16), dim3(256), 0, s, w.up2, w.hyp, c.num_mask_tokens * C8, lowres ? 1 : 1 + mask_index, lowres ? 3 : 1, C8, m->G,
-                     Mi * 16, planes, stride);
-  OVM_TRY(m, last_launch());
+  OVM_TRY(m, launch_mask_prod(w.up2, w.hyp, c.num_mask_tokens * C8, lowres ? 1 : 1 + mask_index, lowres ? 3 : 1, C8, m->G, nb, planes, stride, s));
   // 5. postprocess_masks + threshold
-  const long total = (long)nb * m->H * m->W;
-  hipLaunchKernelGGL(sam_mask_out_kernel, g1((total + 3) / 4), dim3(256), 0, s, planes + (lowres ? (size_t)mask_index * LL : 0), stride, m->L, m->S, m->newh,
-                     m->neww, m->H, m->W, total, masks);
-  return last_launch();
+  return launch_mask_out(planes + (lowres ? (size_t)mask_index * LL : 0), stride, m->L, m->S, m->newh, m->neww, m->H, m->W, nb, masks, s);
 }
 
 }  // namespace
@@ -493,8 +549,7 @@ int ovm_sam_create(const OvmSamConfig* cfg, const OvmTensor* weights, int32_t n_
     memcpy(cr.data(), p2, (size_t)C * 4); memcpy(cr.data() + C, p3, (size_t)C * 4);
     if ((r = upload_f32(m, cr.data(), cr.size(), &m->corner))) return r;
     if ((r = upload_weight(m, wm, "prompt_encoder.no_mask_embed.weight", C, &m->no_mask))) return r;
-    hipLaunchKernelGGL(sam_dense_pe_kernel, g1((long)G2 * (C / 2)), dim3(256), 0, nullptr, m->gauss, G, C / 2, m->pe);
-    if ((r = last_launch())) { m->err = "dense positional encoding launch failed"; return r; }
+    if ((r = launch_dense_pe(m->gauss, G, C / 2, m->pe, nullptr))) { m->err = "dense positional encoding launch failed"; return r; }
   }
   // ---- mask decoder
   {
@@ -665,8 +720,7 @@ int64_t ovm_sam_debug_copy(OvmSam* m, const char* name, float* dst, int64_t capa
     if (cnt > capacity) return OVM_ERR_CAPACITY;
     const half_t *hi, *lo; int ld;
     tower_patches(&m->tower, &hi, &lo, &ld);
-    hipLaunchKernelGGL(sam_unpatch_kernel, g1(cnt), dim3(256), 0, s, hi, lo, ld, m->G, m->cfg.patch, dst);
-    return last_launch() ? OVM_ERR_HIP : cnt;
+    return launch_unpatch(hi, lo, ld, m->G, m->cfg.patch, dst, s) ? OVM_ERR_HIP : cnt;
   }
   if (n == "neck") { src = m->emb; cnt = (int64_t)G2 * C; }
   else if (n == "dense_pe") { src = m->pe; cnt = (int64_t)G2 * C; }
@@ -676,6 +730,63 @@ int64_t ovm_sam_debug_copy(OvmSam* m, const char* name, float* dst, int64_t capa
   if (cnt > capacity) return OVM_ERR_CAPACITY;
   if (cnt && hipMemcpyAsync(dst, src, (size_t)cnt * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return OVM_ERR_HIP;
   return cnt;
+}
+
+// The kernels of this file one at a time (tests): the arguments are checked, then the engine's own launcher is called. None synchronises.
+int ovm_op_sam_dense_pe(const float* gauss, int32_t G, int32_t F, float* pe, ovm_stream_t stream) {
+  if (!gauss || !pe || G < 1 || F < 1) return OVM_ERR_INVALID;
+  return launch_dense_pe(gauss, G, F, pe, (hipStream_t)stream);
+}
+
+int ovm_op_sam_box_tokens(const float* boxes, int32_t nb, int32_t nout, int32_t C, const float* out_tokens, const float* gauss, const float* corner,
+                          int32_t H, int32_t W, int32_t newh, int32_t neww, int32_t S, float* tok, float* sparse, ovm_stream_t stream) {
+  if (!boxes || !out_tokens || !gauss || !corner || !tok || !sparse || nb < 1 || nout < 0 || H < 1 || W < 1 || newh < 1 || neww < 1 || S < 1) return OVM_ERR_INVALID;
+  if (C < 2 || C % 2 != 0) return OVM_ERR_SHAPE;
+  return launch_box_tokens(boxes, nb, nout, C, out_tokens, gauss, corner, H, W, newh, neww, S, tok, sparse, (hipStream_t)stream);
+}
+
+int ovm_op_sam_ln_gelu(float* x, int64_t M, int32_t D, const float* gamma, const float* beta, float eps, ovm_stream_t stream) {
+  if (!x || !gamma || !beta || M < 1) return OVM_ERR_INVALID;
+  return launch_ln_gelu(x, (long)M, D, gamma, beta, eps, (hipStream_t)stream);
+}
+
+int ovm_op_sam_i2t_attn(const float* q, int32_t ldq, const float* k, const float* v, int32_t ld, int32_t nt, int32_t heads, int32_t G2, int32_t nb,
+                        float scale, float* o, int32_t ldo, ovm_stream_t stream) {
+  if (!q || !k || !v || !o || nb < 1) return OVM_ERR_INVALID;
+  if ((((uintptr_t)q) | ((uintptr_t)o)) & 15) return OVM_ERR_INVALID;
+  return launch_i2t_attn(q, ldq, k, v, ld, nt, heads, G2, nb, scale, o, ldo, (hipStream_t)stream);
+}
+
+int ovm_op_sam_mask_prod(const float* up, const float* hyper, int32_t ld_hyper, int32_t t0, int32_t ntk, int32_t C8, int32_t G, int32_t nb, float* out,
+                         int64_t out_box_stride, ovm_stream_t stream) {
+  if (!up || !hyper || !out || G < 1 || nb < 1 || t0 < 0 || ntk < 1) return OVM_ERR_INVALID;
+  if (C8 > 0 && ld_hyper < (t0 + ntk) * C8) return OVM_ERR_SHAPE;
+  if (out_box_stride < (int64_t)ntk * 16 * G * G) return OVM_ERR_SHAPE;
+  return launch_mask_prod(up, hyper, ld_hyper, t0, ntk, C8, G, nb, out, (long)out_box_stride, (hipStream_t)stream);
+}
+
+int ovm_op_sam_mask_out(const float* logits, int64_t box_stride, int32_t L, int32_t S, int32_t newh, int32_t neww, int32_t H, int32_t W, int32_t nb,
+                        uint8_t* out, ovm_stream_t stream) {
+  if (!logits || !out || nb < 1 || L < 1 || H < 1 || W < 1) return OVM_ERR_INVALID;
+  if (newh < 1 || neww < 1 || newh > S || neww > S) return OVM_ERR_SHAPE;
+  return launch_mask_out(logits, (long)box_stride, L, S, newh, neww, H, W, nb, out, (hipStream_t)stream);
+}
+
+int ovm_op_sam_unpatch(const uint16_t* hi, const uint16_t* lo, int32_t ld, int32_t G, int32_t P, float* out, ovm_stream_t stream) {
+  if (!hi || !out || G < 1 || P < 1) return OVM_ERR_INVALID;
+  if (ld < 3 * P * P) return OVM_ERR_SHAPE;
+  return launch_unpatch((const half_t*)hi, (const half_t*)lo, ld, G, P, out, (hipStream_t)stream);
+}
+
+int ovm_op_sam_iou_slice(const float* head, int32_t ldh, int32_t n, float* iou, ovm_stream_t stream) {
+  if (!head || !iou || n < 1) return OVM_ERR_INVALID;
+  if (ldh < 4) return OVM_ERR_SHAPE;
+  return launch_iou_slice(head, ldh, n, iou, (hipStream_t)stream);
+}
+
+int ovm_op_sam_add_bcast(const float* a, const float* b, float* out, int64_t n, int64_t bmod, ovm_stream_t stream) {
+  if (!a || !out || n < 1 || bmod < 1) return OVM_ERR_INVALID;
+  return b ? add_bcast(a, b, out, (long)n, (long)bmod, (hipStream_t)stream) : bcast(a, out, (long)n, (long)bmod, (hipStream_t)stream);
 }
 
 }  // extern "C"

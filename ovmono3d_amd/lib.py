@@ -316,6 +316,10 @@ EXPORTS = [
     "ovm_sam_debug_copy",
     "ovm_depthpro_create", "ovm_depthpro_destroy", "ovm_depthpro_last_error", "ovm_depthpro_workspace", "ovm_depthpro_infer",
     "ovm_depthpro_debug_copy", "ovm_host_depthpro_check", "ovm_depthpro_profile_enable", "ovm_depthpro_stage_ms",
+    "ovm_op_sam_dense_pe", "ovm_op_sam_box_tokens", "ovm_op_sam_ln_gelu", "ovm_op_sam_i2t_attn", "ovm_op_sam_mask_prod", "ovm_op_sam_mask_out",
+    "ovm_op_sam_unpatch", "ovm_op_sam_iou_slice", "ovm_op_sam_add_bcast",
+    "ovm_op_dp_pyramid", "ovm_op_dp_merge", "ovm_op_dp_unsplit", "ovm_op_dp_conv_s2", "ovm_op_dp_dot", "ovm_op_dp_head_tail",
+    "ovm_op_dp_clear_borders", "ovm_op_dp_depth_out",
 ]
 PROF_NAMES = ("attn", "qkv", "proj", "fc1", "fc2", "ln")
 
@@ -452,6 +456,23 @@ def load() -> C.CDLL:
     lib.ovm_depthpro_profile_enable.argtypes = [vp, i32]
     lib.ovm_depthpro_stage_ms.argtypes = [vp, vp, i32]
     lib.ovm_host_depthpro_check.argtypes = [C.POINTER(OvmDepthProConfig), C.c_char_p, i32]
+    lib.ovm_op_sam_dense_pe.argtypes = [vp, i32, i32, vp, vp]
+    lib.ovm_op_sam_box_tokens.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
+    lib.ovm_op_sam_ln_gelu.argtypes = [vp, i64, i32, vp, vp, f32, vp]
+    lib.ovm_op_sam_i2t_attn.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, i32, f32, vp, i32, vp]
+    lib.ovm_op_sam_mask_prod.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, i64, vp]
+    lib.ovm_op_sam_mask_out.argtypes = [vp, i64, i32, i32, i32, i32, i32, i32, i32, vp, vp]
+    lib.ovm_op_sam_unpatch.argtypes = [vp, vp, i32, i32, i32, vp, vp]
+    lib.ovm_op_sam_iou_slice.argtypes = [vp, i32, i32, vp, vp]
+    lib.ovm_op_sam_add_bcast.argtypes = [vp, vp, vp, i64, i64, vp]
+    lib.ovm_op_dp_pyramid.argtypes = [vp, i32, i32, i64, i64, i64, i32, i32, vp, vp, vp, vp]
+    lib.ovm_op_dp_merge.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]
+    lib.ovm_op_dp_unsplit.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
+    lib.ovm_op_dp_conv_s2.argtypes = [vp, i32, i32, vp, vp, i32, vp, i32, vp, vp]
+    lib.ovm_op_dp_dot.argtypes = [vp, vp, vp, i32, vp, vp]
+    lib.ovm_op_dp_head_tail.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp]
+    lib.ovm_op_dp_clear_borders.argtypes = [C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), i32, vp]
+    lib.ovm_op_dp_depth_out.argtypes = [vp, i32, i32, i32, f32, vp, vp, vp, vp, vp]
     lib.ovm_g_pack_weight.argtypes = [vp, i32, i32, i32, vp, vp, vp]
     lib.ovm_host_pack_weight.argtypes = [vp, i32, i32, i32, i32, vp]
     lib.ovm_g_linear.argtypes = [vp, i32, i32, i32, vp, vp, i32, i32, vp, i32, vp, i32, vp, i32, i32, vp]

@@ -165,6 +165,10 @@ TINY = dict(arch="vit_test", image_size=128, seed=3, hw=(70, 100), image_seed=1,
 VITB = dict(arch="vit_b", image_size=1024, seed=5, hw=(600, 900), image_seed=2,
             boxes=[[100.0, 80.0, 400.0, 380.0], [0.0, 0.0, 900.0, 600.0], [450.5, 200.25, 452.0, 203.0], [700.0, 300.0, 950.0, 650.0],
                    [30.0, 400.0, 330.0, 590.0], [500.0, 20.0, 880.0, 290.0], [250.0, 250.0, 650.0, 350.0], [10.0, 10.0, 60.0, 50.0]])
+# portrait, an odd pixel count, and more boxes than one decoder pass takes (max_boxes = 2): the second chunk's masks start at byte
+# 2 * 99 * 71 = 2 (mod 4), where the mask kernel cannot use its 32-bit stores
+PORTRAIT = dict(arch="vit_test", image_size=128, seed=3, hw=(99, 71), image_seed=4, max_boxes=2,
+                boxes=[[10.0, 20.0, 50.0, 80.0], [30.5, 5.25, 60.0, 40.0], [-8.0, 60.0, 90.0, 120.0]])      # the last reaches outside
 
 
 def case_inputs(case):

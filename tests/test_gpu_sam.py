@@ -16,11 +16,19 @@ Measured on an MI355X with its 16 host threads (HF fp32 vs fp64 | HIP precision 
     vit_b, image 1024, 600 x 900 input, 8 boxes
       low-res logits       1.63e-06 | 5.22e-06
       IoU predictions      9.81e-07 | 3.64e-06
+    vit_test, image 128, 99 x 71 input (portrait, odd pixel count), 3 boxes in chunks of max_boxes = 2
+      preprocessed image   5.02e-08 | 1.39e-07
+      neck output          2.05e-06 | 3.75e-06
+      sparse embeddings    9.26e-07 | 9.26e-07      (last chunk)
+      decoder tokens       5.97e-07 | 1.17e-06      (last chunk)
+      low-res logits       2.09e-06 | 3.69e-06
+      IoU predictions      8.59e-07 | 9.40e-07
 
 Masks at (H, W): every pixel whose fp64 logit at output resolution lies outside +- band must agree exactly, band = the absolute
 tolerance of the low-res logits (4 x the fp32 run's largest absolute error); pixels inside are left out, at most 1 % per mask.
 Measured: band 1.2e-3 (vit_test) and 1.5e-3 (vit_b) against logits of standard deviation 29; no disagreement; left out at most
-0.029 % (vit_test, plane 2) and 0.005 % (vit_b) of a mask. The masks are compared at precision 3.
+0.029 % (vit_test, plane 2) and 0.005 % (vit_b) of a mask. The masks are compared at precision 3. The portrait case (band 1.5e-3,
+nothing left out, no disagreement) puts its second chunk's masks at byte 2 * 99 * 71 = 2 (mod 4): the mask kernel's byte stores.
 """
 import numpy as np
 import pytest
@@ -155,6 +163,50 @@ def test_predict_before_set_image_is_an_error(device, tiny):
     pred = _predictor(so.TINY, sd, device)
     with pytest.raises(RuntimeError):
         pred.predict_boxes([[0, 0, 5, 5]])
+
+
+@pytest.fixture(scope="module")
+def portrait():
+    return so.reference_pair(so.PORTRAIT)
+
+
+def _portrait_stages(pred, img, device, mask_index=2):
+    """_hip_stages for a case that runs in chunks: "sparse" and "tokens_out" are those of the last chunk."""
+    case = so.PORTRAIT
+    eng = pred.engine
+    pred.set_image(torch.from_numpy(img).to(device), "RGB")
+    boxes = torch.tensor(case["boxes"], dtype=torch.float32, device=device)
+    H, W = case["hw"]
+    masks, iou, low = eng.predict_boxes(boxes, H, W, mask_index, want_iou=True, want_lowres=True)
+    S, G, C = case["image_size"], case["image_size"] // 16, 256
+    last = len(case["boxes"]) % case["max_boxes"] or case["max_boxes"]
+    out = {"pre": eng.debug("preprocessed", (3, S, S)), "neck": eng.debug("neck", (G, G, C)), "sparse": eng.debug("sparse", (last, 2, C)),
+           "tokens": eng.debug("tokens_out", (last, 7, C)), "low": low, "iou": iou, "masks": masks}
+    torch.cuda.synchronize()
+    return out, last
+
+
+def test_portrait_stages_in_chunks_match_fp64_within_4x_the_fp32_run(device, portrait):
+    """99 x 71 (H > W, an odd pixel count), three boxes with max_boxes = 2: every stage under the rules of this file; the last chunk's
+    sparse embeddings and decoder tokens against the last rows of the references."""
+    r64, r32, sd, img = portrait
+    pred = _predictor(so.PORTRAIT, sd, device, max_boxes=so.PORTRAIT["max_boxes"])
+    hip, last = _portrait_stages(pred, img, device)
+    tail = lambda r: {k: (v[-last:] if k in ("sparse", "tokens") else v) for k, v in r.items()}          # noqa: E731
+    _check_floats(hip, tail(r64), tail(r32), [k for k, _ in STAGES], "vit_test portrait p3")
+
+
+@pytest.mark.parametrize("mask_index", [0, 1, 2])
+def test_portrait_masks_second_chunk_starts_off_a_word(device, portrait, mask_index):
+    r64, r32, sd, img = portrait
+    H, W = so.PORTRAIT["hw"]
+    assert (so.PORTRAIT["max_boxes"] * H * W) % 4 == 2
+    pred = _predictor(so.PORTRAIT, sd, device, max_boxes=so.PORTRAIT["max_boxes"])
+    pred.set_image(torch.from_numpy(img).to(device), "RGB")
+    masks = pred.predict_boxes(so.PORTRAIT["boxes"], mask_index=mask_index)
+    assert masks.dtype == torch.uint8 and tuple(masks.shape) == (len(so.PORTRAIT["boxes"]), H, W)
+    band = FACTOR * float((r32["low"].double() - r64["low"]).abs().max())
+    _check_masks(masks, r64["logits"][:, mask_index], band, f"vit_test portrait plane {mask_index}")
 
 
 def test_vit_b_1024_logits_iou_and_masks(device, vitb):

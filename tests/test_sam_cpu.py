@@ -93,6 +93,19 @@ def test_masks_of_the_tiny_case_are_well_conditioned():
         assert 0.01 < float((plane > 0).double().mean()) < 0.99
 
 
+def test_masks_of_the_portrait_case_are_well_conditioned():
+    """The same check for the portrait case (99 x 71, three boxes in chunks of two)."""
+    r64, r32, _, _ = so.reference_pair(so.PORTRAIT)
+    band = 4.0 * float((r32["low"].double() - r64["low"]).abs().max())
+    shares = so.band_share(r64["logits"], band)
+    print(f"portrait case: band {band:.3e}, largest share inside {max(shares):.4%}, logit std {float(r64['logits'].std()):.2f}")
+    H, W = so.PORTRAIT["hw"]
+    assert H > W and (so.PORTRAIT["max_boxes"] * H * W) % 4 == 2 and len(so.PORTRAIT["boxes"]) > so.PORTRAIT["max_boxes"]
+    assert tuple(r64["logits"].shape) == (3, 3, H, W) and max(shares) <= 0.01, shares
+    for plane in r64["logits"].reshape(-1, H * W):
+        assert 0.01 < float((plane > 0).double().mean()) < 0.99
+
+
 def test_masks_of_the_vit_b_case_are_well_conditioned():
     """The same check for the vit_b case at 1024 (two CPU forward passes of ViT-B: about a minute)."""
     torch.set_num_threads(min(16, torch.get_num_threads()))
