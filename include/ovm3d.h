@@ -563,6 +563,41 @@ typedef struct OvmSwinQkvAttnOp {
   int32_t ldx, KS, C, nh, nW, ldo; float scale; int32_t ws, wpg, reserved0;
 } OvmSwinQkvAttnOp;
 int ovm_g_swin_qkv_attn(const OvmSwinQkvAttnOp* op, ovm_stream_t stream);
+/* The split image of ovm_host_pack_weight (precision 3, [ceil128(N)][Kpad/32][hi 32 | lo 32]) re-ordered for the kernels that feed
+ * weight fragments from global memory straight into the matrix cores (the decoder row chains, the Swin window kernels): [tile of 16
+ * rows][k-step of 32][hi | lo][lane 0..63][8 halves], lane l = row l % 16, halves 8 (l / 16) .. of the k-step. Host only; out holds
+ * as many halves as the image and must not alias it. This is the function the GroundingDINO loader cuts its fragment copies with.
+ * OVM_ERR_INVALID for a null pointer, out == image, N < 1 or Kpad < 32; OVM_ERR_SHAPE for Kpad % 32 != 0; out untouched then. */
+int ovm_host_frag_order(const uint16_t* image, int32_t N, int32_t Kpad, uint16_t* out);
+/* dec_chain_a_kernel / dec_chain_b_kernel / dec_chain_c_kernel (csrc/dec_chain.hip): a GroundingDINO decoder layer around its query
+ * self-attention, 16 query rows per workgroup. part 0 (chain A): qpos = ref_point_head(sine(ref)), qk = (hs + qpos) W_qk ([Q][2 D]),
+ * v = hs W_v. part 1 (chain B): hs <- LN1(hs + ctx W_o); text cross-attention over the T rows of tk / tv (row stride ldt) + LN2;
+ * deformable sampling of val ([S][ldv], level l = rows lstart[l] .. of an lh[l] x lw[l] map, box mode of OvmMsDeformOp) + LN3; FFN +
+ * LN4 -> hs (in place); ref_next = sigmoid(bbox MLP(hs) + logit(clamp(ref, 1e-5, 1 - 1e-5))) unless ref_next is NULL. With ffn_split > 1
+ * (= ffn / 512) part 1 runs on a (row blocks x 512-column chunks) grid and ends at the partial products in ffn_x [Q][D] and ffn_part
+ * [ffn_split][Q][D]; part 2 (chain C) adds them up and finishes the layer, bit-identical to ffn_split <= 1.
+ * lin[]: ref_point_head 0, 1 (2 D -> D -> D), self-attention q | k (N = 2 D), v, out, text-attention q, out, sampling offsets | logits
+ * (N = 3 heads L P), deformable out, fc1, fc2, bbox MLP 0, 1, 2 (N = 4); w: ovm_host_pack_weight (precision 3) then ovm_host_frag_order,
+ * 16-byte aligned; bias [N]. ln[]: LN1 .. LN4. sine_dim_t [D / 4]: 10000^(2 i / (D / 2)). The call is the engine's launcher
+ * (launch_dec_chain) behind a check of the descriptor: OVM_ERR_INVALID for a null descriptor, part outside 0..2, part 2 with
+ * ffn_split <= 1 or a null pointer (ref_next may be NULL and lin[11..13] then too; ffn_x / ffn_part only count with ffn_split > 1);
+ * OVM_ERR_SHAPE for a geometry ovm_host_dec_chain_supported refuses, a non-positive size, a lin[] entry whose N, K, Kpad are not the
+ * geometry's, ldt or ldv below D or not a multiple of 4, or a row pointer that is not 16-byte aligned. Nothing is launched then. */
+typedef struct OvmChainLin { const uint16_t* w; const float* bias; int32_t N, K, Kpad, reserved0; } OvmChainLin;
+typedef struct OvmChainLn { const float* gamma; const float* beta; } OvmChainLn;
+typedef struct OvmDecChainOp {
+  int32_t Q, D, T, heads, ffn; float eps;
+  float* hs; const float* ref; const float* sine_dim_t; float* ref_next; float* qpos; float* qk; float* v; const float* ctx;
+  const float* tk; const float* tv; const float* val; int32_t ldt, ldv;
+  int32_t L, P; int32_t lh[8], lw[8], lstart[8];
+  OvmChainLin lin[14];
+  OvmChainLn ln[4];
+  int32_t ffn_split, reserved0; float* ffn_x; float* ffn_part;
+} OvmDecChainOp;
+int ovm_g_dec_chain(const OvmDecChainOp* op, int32_t part, ovm_stream_t stream);
+/* 1 when the decoder row chains take this geometry (what the engine asks before it picks that route; split-fp16 weights, i.e.
+ * precision 3, only), else 0. Host only. */
+int ovm_host_dec_chain_supported(int32_t D, int32_t heads, int32_t ffn, int32_t L, int32_t P, int32_t T, int32_t precision);
 
 /* Process-global tuning knobs for experiments and tests (also settable as OVM_TUNE="key=value,..." when the host loads the
  * library). Defaults are the measured best; none changes results beyond fp32 summation order.

@@ -139,6 +139,7 @@ int ovm_abi_sizeof(const char* name) {
   if (n == "OvmMsDeformOp") return (int)sizeof(OvmMsDeformOp);
   if (n == "OvmRowOp") return (int)sizeof(OvmRowOp);
   if (n == "OvmSwinQkvAttnOp") return (int)sizeof(OvmSwinQkvAttnOp);
+  if (n == "OvmDecChainOp") return (int)sizeof(OvmDecChainOp);
   return -1;
 }
 

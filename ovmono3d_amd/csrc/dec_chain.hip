@@ -258,8 +258,8 @@ __global__ __launch_bounds__(NT) void dec_chain_b_kernel(const DecChainParams p)
       sc[i] = s * scale;
     }
     __syncthreads();
-    if (tid < npair) {
-      float* s = sc + tid * T;
+    for (int pr = tid; pr < npair; pr += NT) {              // heads > 32: more (row, head) pairs than threads
+      float* s = sc + pr * T;
       float mx = -INFINITY;
       for (int k = 0; k < T; ++k) mx = fmaxf(mx, s[k]);
       float den = 0.f;

@@ -5,7 +5,7 @@
 
 namespace ovm {
 
-// w: the split weight image in MFMA-fragment order [Npad/16][Kpad/32][hi | lo][lane 0..63][8 halves] (gdino.hip: make_frag)
+// w: the split weight image in MFMA-fragment order [Npad/16][Kpad/32][hi | lo][lane 0..63][8 halves] (loader.hip: host_frag_order)
 struct ChainLin { const half_t* w; const float* bias; int N, K, Kpad; };
 struct ChainLn { const float* g; const float* b; };
 

@@ -23,18 +23,10 @@ int up_ln(OvmGdino* g, const WeightMap& wm, const std::string& prefix, Ln* ln) {
 int make_frag(OvmGdino* g, Lin* w) {
   std::vector<half_t> src; src.swap(w->img);          // released on return
   if (g->precision != 3 || !w->hi) return OVM_OK;
-  const int Npad = npad128(w->N), KS = w->Kpad / 32;
-  const size_t n = (size_t)Npad * 2 * w->Kpad;
+  const size_t n = packed_halves(w->N, w->Kpad, 3);
   if (src.size() != n) { g->err = "make_frag: the weight was packed without keeping its host image"; return OVM_ERR_INVALID; }
   std::vector<half_t> dst(n);
-  for (int tile = 0; tile < Npad / 16; ++tile)
-    for (int ks = 0; ks < KS; ++ks)
-      for (int part = 0; part < 2; ++part)
-        for (int lane = 0; lane < 64; ++lane) {
-          const size_t so = (size_t)(tile * 16 + (lane & 15)) * 2 * w->Kpad + (size_t)ks * 64 + part * 32 + (lane >> 4) * 8;
-          const size_t dof = ((((size_t)tile * KS + ks) * 2 + part) * 64 + lane) * 8;
-          for (int e = 0; e < 8; ++e) dst[dof + e] = src[so + e];
-        }
+  if (const int r = host_frag_order(src.data(), w->N, w->Kpad, dst.data())) { g->err = "make_frag: not a split image with Kpad % 32 == 0"; return r; }
   OVM_TRY(g, g->alloc(&w->frag, n));
   OVM_HIP(g, hipMemcpy(w->frag, dst.data(), n * sizeof(half_t), hipMemcpyHostToDevice));
   return OVM_OK;

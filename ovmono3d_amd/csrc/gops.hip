@@ -9,6 +9,7 @@
 #include "kernels.hpp"
 #include "det2d.hpp"
 #include "gdino.hpp"
+#include "dec_chain.hpp"
 
 using namespace ovm;
 
@@ -630,6 +631,52 @@ int ovm_g_swin_qkv_attn(const OvmSwinQkvAttnOp* d, ovm_stream_t stream) {
   a.bias = d->bias; a.C = d->C; a.nh = d->nh; a.nW = d->nW; a.relbias = d->relbias; a.mask = d->mask;
   a.ohi = (half_t*)d->ohi; a.olo = (half_t*)d->olo; a.ldo = d->ldo; a.scale = d->scale; a.ws = d->ws; a.wpg = d->wpg;
   return launch_swin_qkv_attn(a, (hipStream_t)stream);
+}
+
+
+// The decoder row chains alone: the descriptor is checked (the kernels trust their parameter block), copied field for field into the
+// launcher's own block and handed to the launcher the engine calls.
+int ovm_g_dec_chain(const OvmDecChainOp* d, int32_t part, ovm_stream_t stream) {
+  if (!d || part < 0 || part > 2) return OVM_ERR_INVALID;
+  const bool split = d->ffn_split > 1;
+  if (part == 2 && !split) return OVM_ERR_INVALID;
+  if (!d->hs || !d->ref || !d->sine_dim_t || !d->qpos || !d->qk || !d->v || !d->ctx || !d->tk || !d->tv || !d->val) return OVM_ERR_INVALID;
+  if (split && (!d->ffn_x || !d->ffn_part)) return OVM_ERR_INVALID;
+  const int nlin = d->ref_next ? 14 : 11;                     // the last layer refines no boxes: no bbox MLP
+  for (int i = 0; i < nlin; ++i) if (!d->lin[i].w || !d->lin[i].bias) return OVM_ERR_INVALID;
+  for (int i = 0; i < 4; ++i) if (!d->ln[i].gamma || !d->ln[i].beta) return OVM_ERR_INVALID;
+  const int D = d->D, F = d->ffn;
+  if (d->Q < 1 || D < 1 || d->T < 1 || d->heads < 1 || F < 1 || d->L < 1 || d->L > 8 || d->P < 1) return OVM_ERR_SHAPE;
+  if (!dec_chain_supported(D, d->heads, F, d->L, d->P, d->T, 3)) return OVM_ERR_SHAPE;
+  if (split && (F <= 512 || d->ffn_split != F / 512)) return OVM_ERR_SHAPE;
+  for (int l = 0; l < d->L; ++l) if (d->lh[l] < 1 || d->lw[l] < 1 || d->lstart[l] < 0) return OVM_ERR_SHAPE;
+  if (d->ldt < D || d->ldv < D || d->ldt % 4 || d->ldv % 4) return OVM_ERR_SHAPE;
+  for (const void* p : {(const void*)d->hs, (const void*)d->qpos, (const void*)d->qk, (const void*)d->v, (const void*)d->ctx, (const void*)d->tk,
+                        (const void*)d->tv, (const void*)d->val, (const void*)d->ffn_x, (const void*)d->ffn_part})
+    if ((uintptr_t)p % 16) return OVM_ERR_SHAPE;
+  const int NK[14][2] = {{D, 2 * D}, {D, D}, {2 * D, D}, {D, D}, {D, D}, {D, D}, {D, D}, {3 * d->heads * d->L * d->P, D}, {D, D},
+                         {F, D}, {D, F}, {D, D}, {D, D}, {4, D}};
+  for (int i = 0; i < nlin; ++i) {
+    const OvmChainLin& w = d->lin[i];
+    if (w.N != NK[i][0] || w.K != NK[i][1] || w.Kpad < w.K || w.Kpad % 32 || (uintptr_t)w.w % 16) return OVM_ERR_SHAPE;
+  }
+  DecChainParams p; memset(&p, 0, sizeof(p));
+  p.Q = d->Q; p.D = D; p.T = d->T; p.heads = d->heads; p.ffn = F; p.eps = d->eps;
+  p.hs = d->hs; p.ref = d->ref; p.sine_dim_t = d->sine_dim_t; p.ref_next = d->ref_next; p.qpos = d->qpos; p.qk = d->qk; p.v = d->v; p.ctx = d->ctx;
+  p.tk = d->tk; p.tv = d->tv; p.ldt = d->ldt; p.val = d->val; p.ldv = d->ldv;
+  p.L = d->L; p.P = d->P;
+  for (int l = 0; l < 8; ++l) { p.lh[l] = d->lh[l]; p.lw[l] = d->lw[l]; p.lstart[l] = d->lstart[l]; }
+  ChainLin* lin[14] = {&p.ref0, &p.ref1, &p.sa_qk, &p.sa_v, &p.sa_out, &p.ca_q, &p.ca_out, &p.offw, &p.msda_out, &p.fc1, &p.fc2, &p.bb0, &p.bb1, &p.bb2};
+  for (int i = 0; i < nlin; ++i) *lin[i] = ChainLin{(const half_t*)d->lin[i].w, d->lin[i].bias, d->lin[i].N, d->lin[i].K, d->lin[i].Kpad};
+  ChainLn* ln[4] = {&p.ln1, &p.ln2, &p.ln3, &p.ln4};
+  for (int i = 0; i < 4; ++i) *ln[i] = ChainLn{d->ln[i].gamma, d->ln[i].beta};
+  if (split) { p.ffn_split = d->ffn_split; p.ffn_x = d->ffn_x; p.ffn_part = d->ffn_part; }
+  return launch_dec_chain(p, part, (hipStream_t)stream);
+}
+
+int ovm_host_dec_chain_supported(int32_t D, int32_t heads, int32_t ffn, int32_t L, int32_t P, int32_t T, int32_t precision) {
+  if (D < 1 || heads < 1 || ffn < 1 || L < 1 || P < 1 || T < 1) return 0;
+  return dec_chain_supported(D, heads, ffn, L, P, T, precision) ? 1 : 0;
 }
 
 }  // extern "C"

@@ -87,6 +87,21 @@ int host_pack_weight(const float* w, int N, int K, int Kpad, int precision, half
   return OVM_OK;
 }
 
+int host_frag_order(const half_t* image, int N, int Kpad, half_t* out) {
+  if (!image || !out || image == out || N < 1 || Kpad < 32) return OVM_ERR_INVALID;
+  if (Kpad % 32 != 0) return OVM_ERR_SHAPE;
+  const int Npad = npad128(N), KS = Kpad / 32;
+  for (int tile = 0; tile < Npad / 16; ++tile)
+    for (int ks = 0; ks < KS; ++ks)
+      for (int part = 0; part < 2; ++part)
+        for (int lane = 0; lane < 64; ++lane) {
+          const size_t so = (size_t)(tile * 16 + (lane & 15)) * 2 * Kpad + (size_t)ks * 64 + part * 32 + (lane >> 4) * 8;
+          const size_t dof = ((((size_t)tile * KS + ks) * 2 + part) * 64 + lane) * 8;
+          for (int e = 0; e < 8; ++e) out[dof + e] = image[so + e];
+        }
+  return OVM_OK;
+}
+
 int upload_packed(Loader* L, const float* w, int N, int K, int Kpad, const float* bias, int nbias, PackedLin* out,
                   std::vector<half_t>* image) {
   std::vector<half_t> local;
@@ -188,4 +203,8 @@ int pack_convt(Loader* L, const WeightMap& wm, const std::string& prefix, int Ci
 
 extern "C" int ovm_host_pack_weight(const float* w, int32_t N, int32_t K, int32_t Kpad, int32_t precision, uint16_t* out) {
   return ovm::host_pack_weight(w, N, K, Kpad, precision, (ovm::half_t*)out);
+}
+
+extern "C" int ovm_host_frag_order(const uint16_t* image, int32_t N, int32_t Kpad, uint16_t* out) {
+  return ovm::host_frag_order((const ovm::half_t*)image, N, Kpad, (ovm::half_t*)out);
 }

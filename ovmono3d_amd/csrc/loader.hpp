@@ -89,6 +89,10 @@ inline size_t packed_halves(int N, int Kpad, int precision) { return (size_t)npa
 // OVM_ERR_INVALID: null pointers, N < 1, K < 1, Kpad < K, precision not 1 or 3; OVM_ERR_SHAPE: split mode with Kpad % 32 != 0
 // (out is not written then).
 int host_pack_weight(const float* w, int N, int K, int Kpad, int precision, half_t* out);
+// the split (precision 3) image of host_pack_weight -> the same halves in MFMA-fragment order [tile of 16 rows][k-step of 32][hi | lo]
+// [lane 0..63][8 halves], lane l = row l % 16, halves 8 (l / 16) .. of the k-step: what the row-chain and Swin window kernels load.
+// OVM_ERR_INVALID: null pointers, image == out, N < 1, Kpad < 32; OVM_ERR_SHAPE: Kpad % 32 != 0 (out is not written then). No HIP calls.
+int host_frag_order(const half_t* image, int N, int Kpad, half_t* out);
 // packs and uploads; bias: nbias floats or null. image: when given, receives the host image (gdino's fragment copies are cut from it)
 int upload_packed(Loader* L, const float* w, int N, int K, int Kpad, const float* bias, int nbias, PackedLin* out,
                   std::vector<half_t>* image = nullptr);

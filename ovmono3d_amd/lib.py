@@ -291,6 +291,29 @@ class OvmSwinQkvAttnOp(C.Structure):
     ]
 
 
+class OvmChainLin(C.Structure):
+    """Mirror of include/ovm3d.h OvmChainLin: one linear of the decoder row chains (fragment-ordered split image, bias, N, K, Kpad)."""
+    _fields_ = [("w", C.c_void_p), ("bias", C.c_void_p), ("N", C.c_int32), ("K", C.c_int32), ("Kpad", C.c_int32), ("reserved0", C.c_int32)]
+
+
+class OvmChainLn(C.Structure):
+    _fields_ = [("gamma", C.c_void_p), ("beta", C.c_void_p)]
+
+
+class OvmDecChainOp(C.Structure):
+    """Mirror of include/ovm3d.h OvmDecChainOp (ovm_g_dec_chain: the decoder row-chain kernels in isolation, for tests)."""
+    LIN = ("ref0", "ref1", "sa_qk", "sa_v", "sa_out", "ca_q", "ca_out", "offw", "msda_out", "fc1", "fc2", "bb0", "bb1", "bb2")
+    _fields_ = [
+        ("Q", C.c_int32), ("D", C.c_int32), ("T", C.c_int32), ("heads", C.c_int32), ("ffn", C.c_int32), ("eps", C.c_float),
+        ("hs", C.c_void_p), ("ref", C.c_void_p), ("sine_dim_t", C.c_void_p), ("ref_next", C.c_void_p), ("qpos", C.c_void_p),
+        ("qk", C.c_void_p), ("v", C.c_void_p), ("ctx", C.c_void_p),
+        ("tk", C.c_void_p), ("tv", C.c_void_p), ("val", C.c_void_p), ("ldt", C.c_int32), ("ldv", C.c_int32),
+        ("L", C.c_int32), ("P", C.c_int32), ("lh", C.c_int32 * 8), ("lw", C.c_int32 * 8), ("lstart", C.c_int32 * 8),
+        ("lin", OvmChainLin * 14), ("ln", OvmChainLn * 4),
+        ("ffn_split", C.c_int32), ("reserved0", C.c_int32), ("ffn_x", C.c_void_p), ("ffn_part", C.c_void_p),
+    ]
+
+
 EXPORTS = [
     "ovm_create", "ovm_destroy", "ovm_last_error", "ovm_version", "ovm_abi_sizeof", "ovm_backbone_forward", "ovm_cube_forward",
     "ovm_rpn_box_forward", "ovm_gather_records", "ovm_gather_counts", "ovm_host_interp_pos_embed", "ovm_host_resize_pos_embed_aa", "ovm_host_sincos_pos_embed", "ovm_host_shard_range",
@@ -303,6 +326,7 @@ EXPORTS = [
     "ovm_g_pack_weight", "ovm_host_pack_weight", "ovm_g_linear", "ovm_g_layernorm", "ovm_g_bmm", "ovm_g_bmm2", "ovm_g_softmax", "ovm_g_softmax2", "ovm_g_eltwise", "ovm_g_gather_rows",
     "ovm_g_groupnorm", "ovm_g_biattn", "ovm_g_msdeform", "ovm_g_sine_embed", "ovm_g_normalize_image", "ovm_g_topk", "ovm_g_rowmax",
     "ovm_g_attn_f32", "ovm_g_msdeform_fused", "ovm_g_rowop", "ovm_g_swin_qkv_attn",
+    "ovm_host_frag_order", "ovm_g_dec_chain", "ovm_host_dec_chain_supported",
     "ovm_gdino_create", "ovm_gdino_destroy", "ovm_gdino_last_error", "ovm_gdino_forward", "ovm_gdino_detect", "ovm_gdino_set_force_topk",
     "ovm_gdino_debug_copy", "ovm_debug_set_ptr", "ovm_gdino_num_queries", "ovm_gdino_last_outputs", "ovm_infer", "ovm_infer_depth",
     "ovm_host_jpeg_info", "ovm_host_jpeg_entropy_decode", "ovm_jpeg_reconstruct",
@@ -350,7 +374,7 @@ def load() -> C.CDLL:
                          ("OvmGeoInstance", OvmGeoInstance), ("OvmGeoResult", OvmGeoResult), ("OvmGeoBox", OvmGeoBox),
                          ("OvmSamConfig", OvmSamConfig), ("OvmDepthProConfig", OvmDepthProConfig), ("OvmGemmEpiOp", OvmGemmEpiOp),
                          ("OvmAttnF32Op", OvmAttnF32Op), ("OvmMsDeformOp", OvmMsDeformOp), ("OvmRowOp", OvmRowOp),
-                         ("OvmSwinQkvAttnOp", OvmSwinQkvAttnOp)):
+                         ("OvmSwinQkvAttnOp", OvmSwinQkvAttnOp), ("OvmDecChainOp", OvmDecChainOp)):
         if lib.ovm_abi_sizeof(name.encode()) != C.sizeof(mirror):
             raise RuntimeError(f"{LIB_PATH}: sizeof({name}) = {lib.ovm_abi_sizeof(name.encode())} but the ctypes mirror has "
                                f"{C.sizeof(mirror)} bytes - rebuild the library (ovmono3d_amd/csrc/build.sh) or update lib.py")
@@ -494,6 +518,9 @@ def load() -> C.CDLL:
     lib.ovm_g_msdeform_fused.argtypes = [C.POINTER(OvmMsDeformOp), vp]
     lib.ovm_g_rowop.argtypes = [C.POINTER(OvmRowOp), vp]
     lib.ovm_g_swin_qkv_attn.argtypes = [C.POINTER(OvmSwinQkvAttnOp), vp]
+    lib.ovm_host_frag_order.argtypes = [vp, i32, i32, vp]
+    lib.ovm_g_dec_chain.argtypes = [C.POINTER(OvmDecChainOp), i32, vp]
+    lib.ovm_host_dec_chain_supported.argtypes = [i32, i32, i32, i32, i32, i32, i32]
     lib.ovm_gdino_postprocess.argtypes = [vp, i32, i32, vp, C.POINTER(i32), i32, i32, i32, f32, f32, vp, vp, vp, vp, vp]
     lib.ovm_gdino_create.argtypes = [C.POINTER(OvmGdinoConfig), C.POINTER(OvmTensor), i32, i32, C.POINTER(vp)]
     lib.ovm_gdino_destroy.argtypes = [vp]

@@ -40,6 +40,7 @@ def test_struct_layouts_match_header():
         assert L.ovm_abi_sizeof(name.encode()) == C.sizeof(mirror), name
     for name, mirror in (("OvmAttnF32Op", lib.OvmAttnF32Op), ("OvmMsDeformOp", lib.OvmMsDeformOp), ("OvmRowOp", lib.OvmRowOp)):
         assert L.ovm_abi_sizeof(name.encode()) == C.sizeof(mirror), name
+    assert L.ovm_abi_sizeof(b"OvmDecChainOp") == C.sizeof(lib.OvmDecChainOp) == 4 * 6 + 8 * 8 + (8 * 3 + 4 * 2) + 4 * 26 + 32 * 14 + 16 * 4 + (4 * 2 + 8 * 2)
     assert L.ovm_abi_sizeof(b"OvmDet3D") == 192 and L.ovm_abi_sizeof(b"nope") == -1
 
 
