@@ -44,6 +44,11 @@ __device__ __forceinline__ void split_f16_nt(float x, half_t& hi, half_t& lo) {
   hi = cvt_f16_rn_nt(x);
   lo = cvt_f16_rn_nt(x - (float)hi);
 }
+// four at a time: the 8-byte hi and lo stores of four consecutive columns
+__device__ __forceinline__ void split4_f16_nt(f32x4 x, half4& hi, half4& lo) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) { half_t a, b; split_f16_nt(x[r], a, b); hi[r] = a; lo[r] = b; }
+}
 
 __device__ __forceinline__ void split_f16(float x, half_t& hi, half_t& lo) {
   hi = cvt_f16_rn(x);

@@ -9,6 +9,7 @@ namespace ovm {
 namespace {
 
 inline dim3 g1(long n, int bs = 256) { return dim3((unsigned)((n + bs - 1) / bs)); }
+inline bool al16(const void* q) { return (((uintptr_t)q) & 15) == 0; }
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // Row operator. One wave per output row; the row (after gather and residual) is held in registers when a LayerNorm needs two
@@ -133,6 +134,109 @@ __global__ __launch_bounds__(256) void rowop_kernel(const RowOpParams p) {
 // between the two products. v_mfma_f32_16x16x4_f32 is an exact fp32 FMA chain (MI355X_MICROARCH.md, Matrix cores).
 // ------------------------------------------------------------------------------------------------------------------------------
 constexpr int kKC = 144;                       // keys per LDS chunk (= one Swin window)
+constexpr float kLog2e = 1.44269504088896340736f;
+
+// Where the j-th 16-byte piece of lane group g's NS head dimensions sits in a K (or Q) row in LDS. The dimensions a lane contracts
+// are the same in both layouts (g * NS + 4 j + 0..3, the same regrouping on the Q side); only the address differs.
+template <int NS> struct KRowContig { static __device__ __forceinline__ int off(int g, int j) { return g * NS + 4 * j; } };
+struct KRowTwoSlot { static __device__ __forceinline__ int off(int g, int j) { return 16 * j + 4 * g; } };   // NS = 8; swin7_qkv_attn_kernel
+
+__device__ __forceinline__ void add_bias_log2(f32x4& acc, const f32x4 b) {
+  acc[0] += b[0] * kLog2e; acc[1] += b[1] * kLog2e; acc[2] += b[2] * kLog2e; acc[3] += b[3] * kLog2e;
+}
+
+// Biases of a lane's 4 keys key0 .. key0 + 3 in log2 units; keys from Tk on score -inf. bh / bb: the query's bias rows or null.
+// float4 reads: Tk % 4 == 0 and 16-byte aligned bias rows, so the 4 keys lie inside or outside together
+__device__ __forceinline__ void attn_bias_vec(f32x4& acc, int key0, int Tk, const float* bh, const float* bb) {
+  if (key0 < Tk) {
+    if (bh) add_bias_log2(acc, *(const f32x4*)(bh + key0));
+    if (bb) add_bias_log2(acc, *(const f32x4*)(bb + key0));
+  } else {
+    acc = (f32x4){-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+  }
+}
+// scalar reads, any Tk and alignment; rh / rw: the query's relative-position tables over a grid gw keys wide, or null
+__device__ __forceinline__ void attn_bias_scalar(f32x4& acc, int key0, int Tk, const float* bh, const float* bb, const float* rh,
+                                                 const float* rw, int gw) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int key = key0 + r;
+    float x = acc[r];
+    if (key < Tk) {
+      if (bh) x += bh[key] * kLog2e;
+      if (bb) x += bb[key] * kLog2e;
+      if (rh) { const int kh = key / gw; x += (rh[kh] + rw[key - kh * gw]) * kLog2e; }
+    } else {
+      x = -INFINITY;
+    }
+    acc[r] = x;
+  }
+}
+
+// One chunk of 16 NKT keys that is staged in LDS - K rows [keys][LDK] in layout KL, V transposed [16 ND][LDT] - against the wave's 16
+// queries qf[] (pre-scaled by scale * log2(e)); o, m and l carry the online softmax from chunk to chunk. Only the first nkt key tiles
+// hold keys (wave-uniform; a constant folds the tests away). bias(key0, acc) adds the biases of the lane's keys kc + 16 kt + 4 g + 0..3.
+template <int NS, int ND, int NKT, int LDK, int LDT, class KL, class Bias>
+__device__ __forceinline__ void attn_f32_chunk(const float* Ks, const float* Vt, const float (&qf)[NS], int nkt, int kc, Bias bias,
+                                               f32x4 (&o)[ND], float& m, float& l) {
+  const int lane = threadIdx.x & 63, li = lane & 15, g = lane >> 4;
+  f32x4 st[NKT];
+  float cmax = -INFINITY;
+#pragma unroll
+  for (int kt = 0; kt < NKT; ++kt) {
+    if (kt < nkt) {
+      f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+      const float* kr = Ks + (kt * 16 + li) * LDK;
+      f32x4 kq[NS / 4];
+#pragma unroll
+      for (int j = 0; j < NS / 4; ++j) kq[j] = *(const f32x4*)(kr + KL::off(g, j));
+#pragma unroll
+      for (int s = 0; s < NS; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(kq[s >> 2][s & 3], qf[s], acc, 0, 0, 0);
+      bias(kc + kt * 16 + g * 4, acc);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) cmax = fmaxf(cmax, acc[r]);
+      st[kt] = acc;
+    } else {
+      st[kt] = (f32x4){-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    }
+  }
+  cmax = fmaxf(cmax, __shfl_xor(cmax, 16, 64));
+  cmax = fmaxf(cmax, __shfl_xor(cmax, 32, 64));
+  const float mnew = fmaxf(m, cmax);
+  const float msafe = (mnew == -INFINITY) ? 0.f : mnew;       // a chunk (and all before it) entirely masked: exp2f(-inf - 0) = 0, no NaN
+  const float alpha = exp2f(m - msafe);        // m = -inf -> 0
+  l *= alpha;
+#pragma unroll
+  for (int d = 0; d < ND; ++d) { o[d][0] *= alpha; o[d][1] *= alpha; o[d][2] *= alpha; o[d][3] *= alpha; }
+  m = mnew;
+#pragma unroll
+  for (int kt = 0; kt < NKT; ++kt) {
+    if (kt < nkt) {
+      f32x4 pr;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { pr[r] = exp2f(st[kt][r] - msafe); l += pr[r]; }
+#pragma unroll
+      for (int d = 0; d < ND; ++d) {
+        const f32x4 vv = *(const f32x4*)(Vt + (d * 16 + li) * LDT + kt * 16 + g * 4);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[d] = __builtin_amdgcn_mfma_f32_16x16x4f32(vv[r], pr[r], o[d], 0, 0, 0);
+      }
+    }
+  }
+}
+
+// After the last chunk: l over the 4 lane groups, o / l (0 for a query whose keys were all masked), and store(col, y) for the lane's
+// columns col .. col + 3 of its query's head - all lanes take part in the reduction, only live ones store.
+template <int ND, class Store>
+__device__ __forceinline__ void attn_f32_finish(const f32x4 (&o)[ND], float l, bool live, Store store) {
+  l += __shfl_xor(l, 16, 64);
+  l += __shfl_xor(l, 32, 64);
+  const float inv = (l > 0.f) ? 1.0f / l : 0.f;
+  if (!live) return;
+#pragma unroll
+  for (int d = 0; d < ND; ++d)
+    store(d * 16 + (int)((threadIdx.x & 63) >> 4) * 4, (f32x4){o[d][0] * inv, o[d][1] * inv, o[d][2] * inv, o[d][3] * inv});
+}
 
 template <int DH>
 __global__ __launch_bounds__(576) void attn_f32_kernel(const AttnF32Params p) {
@@ -153,7 +257,6 @@ __global__ __launch_bounds__(576) void attn_f32_kernel(const AttnF32Params p) {
   const int q0 = (blockIdx.x * (nthr >> 6) + wave) * 16;
   const bool wave_active = q0 < p.Tq;          // idle waves still help staging and must reach the barriers
   const int qi = (q0 + li < p.Tq) ? q0 + li : p.Tq - 1;
-  const float kLog2e = 1.44269504088896340736f;
   float qf[NS];
   {
     const float sc = p.scale * kLog2e;
@@ -188,104 +291,60 @@ __global__ __launch_bounds__(576) void attn_f32_kernel(const AttnF32Params p) {
     __syncthreads();
     if (!wave_active) continue;
     const int nk = (p.Tk - kc < kKC) ? p.Tk - kc : kKC;
-    const int nkt = (nk + 15) >> 4;
-    f32x4 st[NKT];
-    float cmax = -INFINITY;
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) {
-      if (kt < nkt) {                          // wave-uniform
-        f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
-        const float* kr = Ks + (kt * 16 + li) * LDK + g * NS;
-        f32x4 kq[NS / 4];
-#pragma unroll
-        for (int j = 0; j < NS / 4; ++j) kq[j] = *(const f32x4*)(kr + 4 * j);
-#pragma unroll
-        for (int s = 0; s < NS; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(kq[s >> 2][s & 3], qf[s], acc, 0, 0, 0);
-        const int key0 = kc + kt * 16 + g * 4;
-        if (p.bias_vec) {                      // wave-uniform: Tk % 4 == 0 and 16-byte aligned bias rows -> 4 keys per load
-          if (key0 < p.Tk) {
-            if (bh) { const f32x4 b = *(const f32x4*)(bh + key0); acc[0] += b[0] * kLog2e; acc[1] += b[1] * kLog2e; acc[2] += b[2] * kLog2e; acc[3] += b[3] * kLog2e; }
-            if (bb) { const f32x4 b = *(const f32x4*)(bb + key0); acc[0] += b[0] * kLog2e; acc[1] += b[1] * kLog2e; acc[2] += b[2] * kLog2e; acc[3] += b[3] * kLog2e; }
-          } else {
-            acc = (f32x4){-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-          }
-#pragma unroll
-          for (int r = 0; r < 4; ++r) cmax = fmaxf(cmax, acc[r]);
-        } else {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int key = key0 + r;
-            float x = acc[r];
-            if (key < p.Tk) {
-              if (bh) x += bh[key] * kLog2e;
-              if (bb) x += bb[key] * kLog2e;
-              if (rh) { const int kh = key / p.rel_gw; x += (rh[kh] + rw[key - kh * p.rel_gw]) * kLog2e; }
-            } else {
-              x = -INFINITY;
-            }
-            acc[r] = x;
-            cmax = fmaxf(cmax, x);
-          }
-        }
-        st[kt] = acc;
-      } else {
-        st[kt] = (f32x4){-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-      }
-    }
-    cmax = fmaxf(cmax, __shfl_xor(cmax, 16, 64));
-    cmax = fmaxf(cmax, __shfl_xor(cmax, 32, 64));
-    const float mnew = fmaxf(m, cmax);
-    const float msafe = (mnew == -INFINITY) ? 0.f : mnew;
-    const float alpha = exp2f(m - msafe);      // m = -inf -> 0
-    l *= alpha;
-#pragma unroll
-    for (int d = 0; d < ND; ++d) { o[d][0] *= alpha; o[d][1] *= alpha; o[d][2] *= alpha; o[d][3] *= alpha; }
-    m = mnew;
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) {
-      if (kt < nkt) {
-        f32x4 pr;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { pr[r] = exp2f(st[kt][r] - msafe); l += pr[r]; }
-#pragma unroll
-        for (int d = 0; d < ND; ++d) {
-          const f32x4 vv = *(const f32x4*)(Vt + (d * 16 + li) * LDT + kt * 16 + g * 4);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) o[d] = __builtin_amdgcn_mfma_f32_16x16x4f32(vv[r], pr[r], o[d], 0, 0, 0);
-        }
-      }
-    }
+    attn_f32_chunk<NS, ND, NKT, LDK, LDT, KRowContig<NS>>(Ks, Vt, qf, (nk + 15) >> 4, kc, [&](int key0, f32x4& acc) {
+      if (p.bias_vec) attn_bias_vec(acc, key0, p.Tk, bh, bb);            // wave-uniform (launcher)
+      else attn_bias_scalar(acc, key0, p.Tk, bh, bb, rh, rw, p.rel_gw);
+    }, o, m, l);
   }
   if (!wave_active) return;
-  l += __shfl_xor(l, 16, 64);
-  l += __shfl_xor(l, 32, 64);
-  const float inv = (l > 0.f) ? 1.0f / l : 0.f;
-  if (q0 + li < p.Tq) {
-#pragma unroll
-    for (int d = 0; d < ND; ++d) {
-      const f32x4 y = (f32x4){o[d][0] * inv, o[d][1] * inv, o[d][2] * inv, o[d][3] * inv};
-      const int col = d * 16 + g * 4;
-      if (p.o) *(f32x4*)(p.o + (size_t)b1 * p.so1 + (size_t)b2 * p.so2 + (size_t)(q0 + li) * p.ldo + col) = y;
-      if (p.ohi) {
-        half4 h, lo4;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { half_t hh, ll; split_f16_nt(y[r], hh, ll); h[r] = hh; lo4[r] = ll; }
-        const size_t oo = (size_t)b1 * p.soh1 + (size_t)b2 * p.soh2 + (size_t)(q0 + li) * p.ldoh + col;
-        *(half4*)(p.ohi + oo) = h;
-        if (p.olo) *(half4*)(p.olo + oo) = lo4;
-      }
+  attn_f32_finish(o, l, q0 + li < p.Tq, [&](int col, const f32x4 y) {
+    if (p.o) *(f32x4*)(p.o + (size_t)b1 * p.so1 + (size_t)b2 * p.so2 + (size_t)(q0 + li) * p.ldo + col) = y;
+    if (p.ohi) {
+      half4 h, lo4;
+      split4_f16_nt(y, h, lo4);
+      const size_t oo = (size_t)b1 * p.soh1 + (size_t)b2 * p.soh2 + (size_t)(q0 + li) * p.ldoh + col;
+      *(half4*)(p.ohi + oo) = h;
+      if (p.olo) *(half4*)(p.olo + oo) = lo4;
     }
-  }
+  });
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
-// Swin window attention with the qkv projection inside. Phase 1: the 9 waves form a 3 x 3 grid over (48 window rows) x (q | k | v of
-// the head): per k-step a lane loads 6 activation fragments (3 row tiles x hi / lo, 16 B each, straight from the split rows in HBM)
-// and 4 weight fragments (2 column tiles x hi / lo, 1 KiB contiguous per instruction in the fragment-ordered image), the next step's
-// loads are issued before this step's 18 MFMAs. Same products in the same order as the 128-tile GEMM (lo . hi, hi . lo, hi . hi per
-// k-step of 32). The accumulators go to LDS as Q rows [144][36], K rows [144][36] and V transposed [32][148] - what attn_f32_kernel
-// stages from HBM. Phase 2: that kernel's loop for one chunk of 144 keys (wave = 16 queries).
+// Swin window attention with the qkv projection inside: two kernels, windows of 12 x 12 and of 7 x 7 tokens, head dimension 32.
+// Phase 1 computes [q | k | v] = x W^T + b of one head on the matrix cores into LDS, in the layouts attn_f32_kernel stages from HBM;
+// phase 2 is attn_f32_chunk on it. The three helpers below are what the two phase 1s share; their load pipelines differ.
 // ------------------------------------------------------------------------------------------------------------------------------
+// Fragment-ordered split weight image (make_frag): a 16-row tile is KS k-steps of 1024 halves - the hi fragment, at + 512 the lo
+// fragment, a lane's 8 halves at lane * 8 in each (1 KiB contiguous per load instruction).
+__device__ __forceinline__ const half_t* wfrag_tile(const half_t* wfrag, int KS, int tile, int lane) {
+  return wfrag + (size_t)tile * KS * 1024 + lane * 8;
+}
+__device__ __forceinline__ void wfrag_load(const half_t* tl, int KS, int n, int k, half8& hi, half8& lo) {   // n tiles behind tl, k-step k
+  const half_t* q = tl + n * ((size_t)KS * 1024) + (size_t)k * 1024;
+  hi = *(const half8*)q;
+  lo = *(const half8*)(q + 512);
+}
+
+// One k-step of 32 of acc += w x^T on split operands, the products in the 128-tile GEMM's order: lo . hi, hi . lo, hi . hi
+__device__ __forceinline__ void mfma_split3(f32x4& acc, half8 w_hi, half8 w_lo, half8 x_hi, half8 x_lo) {
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(w_lo, x_hi, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(w_hi, x_lo, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(w_hi, x_hi, acc, 0, 0, 0);
+}
+
+// y = columns d0 .. d0 + 3 of the head's 32 in window row `row` of part 0 = q, 1 = k, 2 = v. A Q / K row takes them at float pc, V goes
+// in transposed.
+template <int LDK, int LDT>
+__device__ __forceinline__ void qkv_to_lds(int part, const f32x4 y, float* Qs, float* Ks, float* Vt, int row, int pc, int d0) {
+  if (part == 0) *(f32x4*)(Qs + row * LDK + pc) = y;
+  else if (part == 1) *(f32x4*)(Ks + row * LDK + pc) = y;
+  else { float* vd = Vt + d0 * LDT + row; vd[0] = y[0]; vd[LDT] = y[1]; vd[2 * LDT] = y[2]; vd[3 * LDT] = y[3]; }
+}
+
+// Windows of 144 tokens, one workgroup per (window, head). Phase 1: the 9 waves form a 3 x 3 grid over (48 window rows) x (q | k | v of
+// the head): per k-step a lane loads 6 activation fragments (3 row tiles x hi / lo, 16 B each, straight from the split rows in HBM)
+// and 4 weight fragments (2 column tiles x hi / lo), the next step's loads are issued before this step's 18 MFMAs. The accumulators go
+// to LDS as Q rows [144][36], K rows [144][36] and V transposed [32][148]. Phase 2: one chunk of 144 keys (wave = 16 queries).
 __global__ __launch_bounds__(576) void swin_qkv_attn_kernel(const SwinQkvAttnParams p) {
   constexpr int DH = 32, WS2 = 144, LDK = DH + 4, LDT = WS2 + 4, NS = DH / 4, ND = DH / 16, NKT = WS2 / 16;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -301,8 +360,7 @@ __global__ __launch_bounds__(576) void swin_qkv_attn_kernel(const SwinQkvAttnPar
     const int tile0 = (ng * p.C + h * DH) >> 4;               // first of the two 16-row weight tiles of this part and head
     const half_t* xh = p.xhi + (size_t)(w * WS2 + mg * 48 + fr) * p.ldx + fq * 8;
     const half_t* xl = p.xlo + (size_t)(w * WS2 + mg * 48 + fr) * p.ldx + fq * 8;
-    const half_t* wp = p.wfrag + (size_t)tile0 * p.KS * 1024 + lane * 8;       // tile stride = KS * (hi 512 + lo 512) halves
-    const size_t wt = (size_t)p.KS * 1024;
+    const half_t* wp = wfrag_tile(p.wfrag, p.KS, tile0, lane);
     f32x4 acc[2][3];
 #pragma unroll
     for (int n = 0; n < 2; ++n)
@@ -322,20 +380,13 @@ __global__ __launch_bounds__(576) void swin_qkv_attn_kernel(const SwinQkvAttnPar
     auto loadw = [&](int ks, half8* wd) {
       const int k = (ks < p.KS) ? ks : p.KS - 1;
 #pragma unroll
-      for (int n = 0; n < 2; ++n) {
-        wd[2 * n] = *(const half8*)(wp + n * wt + (size_t)k * 1024);
-        wd[2 * n + 1] = *(const half8*)(wp + n * wt + (size_t)k * 1024 + 512);
-      }
+      for (int n = 0; n < 2; ++n) wfrag_load(wp, p.KS, n, k, wd[2 * n], wd[2 * n + 1]);
     };
     auto mfmak = [&](const half8* xd, const half8* wd) {
 #pragma unroll
       for (int n = 0; n < 2; ++n)
 #pragma unroll
-        for (int m = 0; m < 3; ++m) {
-          acc[n][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wd[2 * n + 1], xd[2 * m], acc[n][m], 0, 0, 0);
-          acc[n][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wd[2 * n], xd[2 * m + 1], acc[n][m], 0, 0, 0);
-          acc[n][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wd[2 * n], xd[2 * m], acc[n][m], 0, 0, 0);
-        }
+        for (int m = 0; m < 3; ++m) mfma_split3(acc[n][m], wd[2 * n], wd[2 * n + 1], xd[2 * m], xd[2 * m + 1]);
     };
     loadw(0, wa[0]); loadw(1, wa[1]); loadw(2, wa[2]); loadx(0, xa[0]);
     for (int ks = 0; ks < p.KS; ks += 4) {                    // KS % 4 == 0 (C % 128 == 0, launcher)
@@ -355,20 +406,13 @@ __global__ __launch_bounds__(576) void swin_qkv_attn_kernel(const SwinQkvAttnPar
       const int d0 = n * 16 + fq * 4;
       const f32x4 b = *(const f32x4*)(p.bias + ng * p.C + h * DH + d0);
 #pragma unroll
-      for (int m = 0; m < 3; ++m) {
-        const int row = mg * 48 + m * 16 + fr;
-        const f32x4 y = (f32x4){acc[n][m][0] + b[0], acc[n][m][1] + b[1], acc[n][m][2] + b[2], acc[n][m][3] + b[3]};
-        if (ng == 0) *(f32x4*)(Qs + row * LDK + d0) = y;
-        else if (ng == 1) *(f32x4*)(Ks + row * LDK + d0) = y;
-        else { float* vd = Vt + d0 * LDT + row; vd[0] = y[0]; vd[LDT] = y[1]; vd[2 * LDT] = y[2]; vd[3 * LDT] = y[3]; }
-      }
+      for (int m = 0; m < 3; ++m) qkv_to_lds<LDK, LDT>(ng, acc[n][m] + b, Qs, Ks, Vt, mg * 48 + m * 16 + fr, d0, d0);
     }
   }
   __syncthreads();
-  // ---------------- phase 2: attn_f32_kernel<32>'s loop over one chunk of 144 keys ----------------
+  // ---------------- phase 2 ----------------
   const int li = lane & 15, g = lane >> 4;
   const int q0 = wave * 16, qi = q0 + li;
-  const float kLog2e = 1.44269504088896340736f;
   float qf[NS];
   {
     const float sc = p.scale * kLog2e;
@@ -377,82 +421,41 @@ __global__ __launch_bounds__(576) void swin_qkv_attn_kernel(const SwinQkvAttnPar
     for (int s = 0; s < NS; ++s) qf[s] = qr[s] * sc;
   }
   const float* bh = p.relbias + ((size_t)h * WS2 + qi) * WS2;
+  __builtin_assume(bh != nullptr);              // the launcher refuses a null relbias: no test of it per key tile
   const float* bb = p.mask ? p.mask + ((size_t)w * WS2 + qi) * WS2 : nullptr;
   f32x4 o[ND];
 #pragma unroll
   for (int d = 0; d < ND; ++d) o[d] = (f32x4){0.f, 0.f, 0.f, 0.f};
   float m = -INFINITY, l = 0.f;
-  f32x4 st[NKT];
-  float cmax = -INFINITY;
-#pragma unroll
-  for (int kt = 0; kt < NKT; ++kt) {
-    f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const float* kr = Ks + (kt * 16 + li) * LDK + g * NS;
-    f32x4 kq[NS / 4];
-#pragma unroll
-    for (int j = 0; j < NS / 4; ++j) kq[j] = *(const f32x4*)(kr + 4 * j);
-#pragma unroll
-    for (int s = 0; s < NS; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(kq[s >> 2][s & 3], qf[s], acc, 0, 0, 0);
-    const int key0 = kt * 16 + g * 4;
-    { const f32x4 b = *(const f32x4*)(bh + key0); acc[0] += b[0] * kLog2e; acc[1] += b[1] * kLog2e; acc[2] += b[2] * kLog2e; acc[3] += b[3] * kLog2e; }
-    if (bb) { const f32x4 b = *(const f32x4*)(bb + key0); acc[0] += b[0] * kLog2e; acc[1] += b[1] * kLog2e; acc[2] += b[2] * kLog2e; acc[3] += b[3] * kLog2e; }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) cmax = fmaxf(cmax, acc[r]);
-    st[kt] = acc;
-  }
-  cmax = fmaxf(cmax, __shfl_xor(cmax, 16, 64));
-  cmax = fmaxf(cmax, __shfl_xor(cmax, 32, 64));
-  const float mnew = fmaxf(m, cmax);
-  const float msafe = (mnew == -INFINITY) ? 0.f : mnew;
-  const float alpha = exp2f(m - msafe);
-  l *= alpha;
-#pragma unroll
-  for (int d = 0; d < ND; ++d) { o[d][0] *= alpha; o[d][1] *= alpha; o[d][2] *= alpha; o[d][3] *= alpha; }
-#pragma unroll
-  for (int kt = 0; kt < NKT; ++kt) {
-    f32x4 pr;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { pr[r] = exp2f(st[kt][r] - msafe); l += pr[r]; }
-#pragma unroll
-    for (int d = 0; d < ND; ++d) {
-      const f32x4 vv = *(const f32x4*)(Vt + (d * 16 + li) * LDT + kt * 16 + g * 4);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) o[d] = __builtin_amdgcn_mfma_f32_16x16x4f32(vv[r], pr[r], o[d], 0, 0, 0);
-    }
-  }
-  l += __shfl_xor(l, 16, 64);
-  l += __shfl_xor(l, 32, 64);
-  const float inv = (l > 0.f) ? 1.0f / l : 0.f;
-#pragma unroll
-  for (int d = 0; d < ND; ++d) {
-    const f32x4 y = (f32x4){o[d][0] * inv, o[d][1] * inv, o[d][2] * inv, o[d][3] * inv};
-    const int col = d * 16 + g * 4;
+  attn_f32_chunk<NS, ND, NKT, LDK, LDT, KRowContig<NS>>(Ks, Vt, qf, NKT, 0, [&](int key0, f32x4& acc) {
+    attn_bias_vec(acc, key0, WS2, bh, bb);
+  }, o, m, l);
+  attn_f32_finish(o, l, true, [&](int col, const f32x4 y) {
     half4 hh, lo4;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { half_t a, b; split_f16_nt(y[r], a, b); hh[r] = a; lo4[r] = b; }
+    split4_f16_nt(y, hh, lo4);
     const size_t oo = (size_t)(w * WS2 + qi) * p.ldo + h * DH + col;
     *(half4*)(p.ohi + oo) = hh;
     *(half4*)(p.olo + oo) = lo4;
-  }
+  });
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
-// The same for windows of 7 x 7 = 49 tokens (Swin-T), head dimension 32. A window is 4 row tiles of 16 (rows 49 .. 63 do not exist:
-// loads are clamped to row 48, the LDS rows are written as zero, keys 49 .. 63 score -inf, queries 49 .. 63 are not stored). A
-// workgroup is 4 waves and takes NWIN consecutive windows of one head: wave rt owns row tile rt of each of them in both phases.
-// Phase 1: per k-step a wave loads 12 weight fragments (q | k | v x 2 column tiles x hi / lo, 1 KiB contiguous each) ONCE and uses
-// them for its NWIN row tiles (2 NWIN activation fragments straight from the split rows), 18 NWIN MFMAs; the next step's loads are
-// issued before this step's MFMAs. Same products in the same order as the 128-tile GEMM; only the C / 32 k-steps that hold
-// channels run (the rows' pad columns are zero). Phase 2: attn_f32_kernel's loop for one chunk of 64 keys.
+// The same for windows of 7 x 7 = 49 tokens (Swin-T). A window is 4 row tiles of 16 (rows 49 .. 63 do not exist: loads are clamped to
+// row 48, the LDS rows are written as zero, keys 49 .. 63 score -inf, queries 49 .. 63 are not stored). A workgroup is 4 waves and
+// takes NWIN consecutive windows of one head: wave rt owns row tile rt of each of them in both phases.
+// Phase 1: per k-step a wave loads 12 weight fragments (q | k | v x 2 column tiles x hi / lo) ONCE and uses them for its NWIN row
+// tiles (2 NWIN activation fragments straight from the split rows), 18 NWIN MFMAs; the next step's loads are issued before this
+// step's MFMAs. Only the C / 32 k-steps that hold channels run (the rows' pad columns are zero). Phase 2: one chunk of 64 keys per
+// window.
 // LDS per window: Q [64][40], K [64][40], V^T [32][72] floats. The 8 columns a lane reads of a Q / K row (8 g .. 8 g + 7) are kept
-// as two 16-byte slots at floats 4 g and 16 + 4 g: with ds_read_b128's lane groups ({0-3, 12-15, 20-27}, ...) a row stride of 40
-// floats then puts the 16 lanes of a group on 16 different slots of the 256-byte bank row; contiguous 8 g is 2-way at every stride
-// (36 included). V^T rows: stride 72 for the same reason (68 is 2-way). Bias and mask rows are 49 floats (no 16-byte alignment): read
-// as scalars.
+// as two 16-byte slots at floats 4 g and 16 + 4 g (KRowTwoSlot): with ds_read_b128's lane groups ({0-3, 12-15, 20-27}, ...) a row
+// stride of 40 floats then puts the 16 lanes of a group on 16 different slots of the 256-byte bank row; contiguous 8 g is 2-way at
+// every stride (36 included). V^T rows: stride 72 for the same reason (68 is 2-way). Bias and mask rows are 49 floats (no 16-byte
+// alignment): read as scalars.
 // ------------------------------------------------------------------------------------------------------------------------------
 template <int NWIN>
 __global__ __launch_bounds__(256) void swin7_qkv_attn_kernel(const SwinQkvAttnParams p) {
-  constexpr int DH = 32, T = 49, TP = 64, LDK = 40, LDT = 72, ND = DH / 16, NKT = TP / 16, WSZ = 2 * TP * LDK + DH * LDT;
+  constexpr int DH = 32, T = 49, TP = 64, LDK = 40, LDT = 72, NS = DH / 4, ND = DH / 16, NKT = TP / 16, WSZ = 2 * TP * LDK + DH * LDT;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* const lds = (float*)smem_raw;           // window j: Q at j WSZ, K behind it, V^T behind that
   const int tid = threadIdx.x, lane = tid & 63, rt = tid >> 6;
@@ -470,10 +473,9 @@ __global__ __launch_bounds__(256) void swin7_qkv_attn_kernel(const SwinQkvAttnPa
       const size_t o = ((size_t)wj * T + rowc) * p.ldx + fq * 8;
       xh[j] = p.xhi + o; xl[j] = p.xlo + o;
     }
-    const size_t wt = (size_t)p.KS * 1024;                      // tile stride = KS * (hi 512 + lo 512) halves
     const half_t* wp[3];
 #pragma unroll
-    for (int part = 0; part < 3; ++part) wp[part] = p.wfrag + (size_t)((part * p.C + h * DH) >> 4) * wt + lane * 8;
+    for (int part = 0; part < 3; ++part) wp[part] = wfrag_tile(p.wfrag, p.KS, (part * p.C + h * DH) >> 4, lane);
     f32x4 acc[6][NWIN];
 #pragma unroll
     for (int t = 0; t < 6; ++t)
@@ -488,21 +490,13 @@ __global__ __launch_bounds__(256) void swin7_qkv_attn_kernel(const SwinQkvAttnPa
         xd[2 * j + 1] = *(const half8*)(xl[j] + k * 32);
       }
 #pragma unroll
-      for (int t = 0; t < 6; ++t) {
-        const half_t* q = wp[t >> 1] + (t & 1) * wt + (size_t)k * 1024;
-        wd[2 * t] = *(const half8*)q;
-        wd[2 * t + 1] = *(const half8*)(q + 512);
-      }
+      for (int t = 0; t < 6; ++t) wfrag_load(wp[t >> 1], p.KS, t & 1, k, wd[2 * t], wd[2 * t + 1]);
     };
     auto mfmak = [&](const half8* xd, const half8* wd) {
 #pragma unroll
       for (int t = 0; t < 6; ++t)
 #pragma unroll
-        for (int j = 0; j < NWIN; ++j) {
-          acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wd[2 * t + 1], xd[2 * j], acc[t][j], 0, 0, 0);
-          acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wd[2 * t], xd[2 * j + 1], acc[t][j], 0, 0, 0);
-          acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wd[2 * t], xd[2 * j], acc[t][j], 0, 0, 0);
-        }
+        for (int j = 0; j < NWIN; ++j) mfma_split3(acc[t][j], wd[2 * t], wd[2 * t + 1], xd[2 * j], xd[2 * j + 1]);
     };
     loadk(0, xa[0], wa[0]);
     for (int ks = 0; ks < nks; ks += 2) {
@@ -516,25 +510,22 @@ __global__ __launch_bounds__(256) void swin7_qkv_attn_kernel(const SwinQkvAttnPa
     const bool live = row < T;
 #pragma unroll
     for (int t = 0; t < 6; ++t) {
-      const int part = t >> 1, d0 = (t & 1) * 16 + fq * 4;
+      const int d0 = (t & 1) * 16 + fq * 4;
       const int pc = ((d0 >> 2) & 1) * 16 + (d0 >> 3) * 4;       // slot of columns d0 .. d0 + 3 in a Q / K row
-      const f32x4 b = *(const f32x4*)(p.bias + part * p.C + h * DH + d0);
+      const f32x4 b = *(const f32x4*)(p.bias + (t >> 1) * p.C + h * DH + d0);
 #pragma unroll
       for (int j = 0; j < NWIN; ++j) {
-        float* base = lds + j * WSZ;
-        f32x4 y = (f32x4){acc[t][j][0] + b[0], acc[t][j][1] + b[1], acc[t][j][2] + b[2], acc[t][j][3] + b[3]};
+        float* Qs = lds + j * WSZ;
+        f32x4 y = acc[t][j] + b;
         if (!live) y = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if (part == 0) *(f32x4*)(base + row * LDK + pc) = y;
-        else if (part == 1) *(f32x4*)(base + TP * LDK + row * LDK + pc) = y;
-        else { float* vd = base + 2 * TP * LDK + d0 * LDT + row; vd[0] = y[0]; vd[LDT] = y[1]; vd[2 * LDT] = y[2]; vd[3 * LDT] = y[3]; }
+        qkv_to_lds<LDK, LDT>(t >> 1, y, Qs, Qs + TP * LDK, Qs + 2 * TP * LDK, row, pc, d0);
       }
     }
   }
   __syncthreads();
-  // ---------------- phase 2: attn_f32_kernel<32>'s loop over one chunk of 64 keys, per window ----------------
+  // ---------------- phase 2, per window ----------------
   const int li = lane & 15, g = lane >> 4;
   const int qi = rt * 16 + li, qc = qi < T ? qi : T - 1;
-  const float kLog2e = 1.44269504088896340736f;
   const float sc = p.scale * kLog2e;
 #pragma unroll 1
   for (int j = 0; j < NWIN; ++j) {
@@ -543,81 +534,29 @@ __global__ __launch_bounds__(256) void swin7_qkv_attn_kernel(const SwinQkvAttnPa
     const float* Qs = lds + j * WSZ;
     const float* Ks = Qs + TP * LDK;
     const float* Vt = Ks + TP * LDK;
-    float qf[8];
+    float qf[NS];
     {
-      const f32x4 a = *(const f32x4*)(Qs + qi * LDK + g * 4), b = *(const f32x4*)(Qs + qi * LDK + 16 + g * 4);
+      const f32x4 a = *(const f32x4*)(Qs + qi * LDK + KRowTwoSlot::off(g, 0)), b = *(const f32x4*)(Qs + qi * LDK + KRowTwoSlot::off(g, 1));
 #pragma unroll
       for (int e = 0; e < 4; ++e) { qf[e] = a[e] * sc; qf[4 + e] = b[e] * sc; }
     }
     const float* bh = p.relbias + ((size_t)h * T + qc) * T;
+    __builtin_assume(bh != nullptr);            // the launcher refuses a null relbias: no test of it per key
     const float* bb = p.mask ? p.mask + ((size_t)w * T + qc) * T : nullptr;
     f32x4 o[ND];
 #pragma unroll
     for (int d = 0; d < ND; ++d) o[d] = (f32x4){0.f, 0.f, 0.f, 0.f};
     float m = -INFINITY, l = 0.f;
-    f32x4 st[NKT];
-    float cmax = -INFINITY;
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) {
-      f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
-      const float* kr = Ks + (kt * 16 + li) * LDK + g * 4;
-      const f32x4 k0 = *(const f32x4*)kr, k1 = *(const f32x4*)(kr + 16);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(k0[e], qf[e], acc, 0, 0, 0);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(k1[e], qf[4 + e], acc, 0, 0, 0);
-      const int key0 = kt * 16 + g * 4;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int key = key0 + r;
-        float x = acc[r];
-        if (key < T) {
-          x += bh[key] * kLog2e;
-          if (bb) x += bb[key] * kLog2e;
-        } else {
-          x = -INFINITY;
-        }
-        acc[r] = x;
-        cmax = fmaxf(cmax, x);
-      }
-      st[kt] = acc;
-    }
-    cmax = fmaxf(cmax, __shfl_xor(cmax, 16, 64));
-    cmax = fmaxf(cmax, __shfl_xor(cmax, 32, 64));
-    const float mnew = fmaxf(m, cmax);
-    const float msafe = (mnew == -INFINITY) ? 0.f : mnew;
-    const float alpha = exp2f(m - msafe);
-    l *= alpha;
-#pragma unroll
-    for (int d = 0; d < ND; ++d) { o[d][0] *= alpha; o[d][1] *= alpha; o[d][2] *= alpha; o[d][3] *= alpha; }
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) {
-      f32x4 pr;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { pr[r] = exp2f(st[kt][r] - msafe); l += pr[r]; }
-#pragma unroll
-      for (int d = 0; d < ND; ++d) {
-        const f32x4 vv = *(const f32x4*)(Vt + (d * 16 + li) * LDT + kt * 16 + g * 4);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) o[d] = __builtin_amdgcn_mfma_f32_16x16x4f32(vv[r], pr[r], o[d], 0, 0, 0);
-      }
-    }
-    l += __shfl_xor(l, 16, 64);
-    l += __shfl_xor(l, 32, 64);
-    const float inv = (l > 0.f) ? 1.0f / l : 0.f;
-    if (qi < T) {
-#pragma unroll
-      for (int d = 0; d < ND; ++d) {
-        const f32x4 y = (f32x4){o[d][0] * inv, o[d][1] * inv, o[d][2] * inv, o[d][3] * inv};
-        const int col = d * 16 + g * 4;
-        half4 hh, lo4;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { half_t a, b; split_f16_nt(y[r], a, b); hh[r] = a; lo4[r] = b; }
-        const size_t oo = ((size_t)w * T + qi) * p.ldo + h * DH + col;
-        *(half4*)(p.ohi + oo) = hh;
-        *(half4*)(p.olo + oo) = lo4;
-      }
-    }
+    attn_f32_chunk<NS, ND, NKT, LDK, LDT, KRowTwoSlot>(Ks, Vt, qf, NKT, 0, [&](int key0, f32x4& acc) {
+      attn_bias_scalar(acc, key0, T, bh, bb, nullptr, nullptr, 0);
+    }, o, m, l);
+    attn_f32_finish(o, l, qi < T, [&](int col, const f32x4 y) {
+      half4 hh, lo4;
+      split4_f16_nt(y, hh, lo4);
+      const size_t oo = ((size_t)w * T + qi) * p.ldo + h * DH + col;
+      *(half4*)(p.ohi + oo) = hh;
+      *(half4*)(p.olo + oo) = lo4;
+    });
   }
 }
 
@@ -700,8 +639,7 @@ __global__ __launch_bounds__(256) void biattn_img_kernel(const BiAttnParams p) {
       if (p.cv) *(f32x4*)(p.cv + (size_t)s * p.ldcv + h * dh + e) = y;
       if (p.cv_hi) {
         half4 hh, ll;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { half_t a, b; split_f16_nt(y[r], a, b); hh[r] = a; ll[r] = b; }
+        split4_f16_nt(y, hh, ll);
         *(half4*)(p.cv_hi + (size_t)s * p.ldcv + h * dh + e) = hh;
         if (p.cv_lo) *(half4*)(p.cv_lo + (size_t)s * p.ldcv + h * dh + e) = ll;
       }
@@ -1003,8 +941,7 @@ __global__ __launch_bounds__(256, 2) void biattn_mfma_kernel(const BiAttnParams 
       if (p.cv) *(f32x4*)(p.cv + oo) = y;
       if (p.cv_hi) {
         half4 hh, ll;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { half_t a, b; split_f16_nt(y[i], a, b); hh[i] = a; ll[i] = b; }
+        split4_f16_nt(y, hh, ll);
         *(half4*)(p.cv_hi + oo) = hh;
         if (p.cv_lo) *(half4*)(p.cv_lo + oo) = ll;
       }
@@ -1224,7 +1161,6 @@ int launch_rowop(const RowOpParams& p, hipStream_t s) {
   if (p.M <= 0) return OVM_OK;
   if (p.il && (!p.hi || p.lo != p.hi + 32 || p.D % 32 || p.ldh != 2 * p.D)) return OVM_ERR_INVALID;     // one interleaved image, no K padding
   const int seg = p.idx ? p.seg : p.D;
-  auto al16 = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
   const bool v4 = (p.D % 4 == 0) && (seg % 4 == 0) && (p.ldx % 4 == 0) && al16(p.x) && (!p.res || (p.ldr % 4 == 0 && al16(p.res)));
   const dim3 grid((p.M + 3) / 4), block(256);
   if (p.gamma) {
@@ -1251,7 +1187,6 @@ bool swin_qkv_attn_supported(int C, int nh, int ws, int npass) {
 int launch_swin_qkv_attn(const SwinQkvAttnParams& p, hipStream_t s) {
   if (p.ws != 7 && p.ws != 12) return OVM_ERR_SHAPE;
   if (p.nW <= 0) return OVM_OK;
-  auto al16 = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
   if (p.nh <= 0 || p.C != p.nh * 32 || p.KS * 32 < p.C || p.ldx < p.C || p.ldo < p.C || p.ldx % 8 || p.ldo % 4 || !p.xhi || !p.xlo || !p.wfrag ||
       !p.bias || !p.relbias || !p.ohi || !p.olo || !al16(p.xhi) || !al16(p.xlo) || !al16(p.wfrag) || !al16(p.bias) ||
       (((uintptr_t)p.ohi | (uintptr_t)p.olo) & 7))               // the context rows are stored 4 halves at a time
@@ -1283,7 +1218,6 @@ int launch_swin_qkv_attn(const SwinQkvAttnParams& p, hipStream_t s) {
 
 int launch_attn_f32(const AttnF32Params& p, hipStream_t s) {
   if (p.Tq <= 0 || p.Tk <= 0 || p.nb1 <= 0 || p.nb2 <= 0) return OVM_OK;
-  auto al16 = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
   if (p.ldk % 4 || p.ldv % 4 || !al16(p.k) || !al16(p.v) || p.sk1 % 4 || p.sk2 % 4 || p.sv1 % 4 || p.sv2 % 4) return OVM_ERR_SHAPE;
   if (p.o && (p.ldo % 4 || !al16(p.o) || p.so1 % 4 || p.so2 % 4)) return OVM_ERR_SHAPE;
   if (p.ohi && (p.ldoh % 4 || p.soh1 % 4 || p.soh2 % 4)) return OVM_ERR_SHAPE;
@@ -1297,11 +1231,13 @@ int launch_attn_f32(const AttnF32Params& p, hipStream_t s) {
   pv.bias_vec = (p.Tk % 4 == 0) && !p.rel_h && (p.bias_h || p.bias_b) &&
                 (!p.bias_h || (al16(p.bias_h) && p.ldbh % 4 == 0 && p.sbh % 4 == 0)) &&
                 (!p.bias_b || (al16(p.bias_b) && p.ldbb % 4 == 0 && p.sbb % 4 == 0));
+  // DH = 64 needs 75 KiB of LDS: opted in like swin7_qkv_attn_kernel<4> above
 #define OVM_ATTN_F32(DH_)                                                                              \
   {                                                                                                    \
     const int smem = kKC * ((DH_) + 4) * 4 + (DH_) * (kKC + 4) * 4;                                    \
-    static bool set = false;                                                                           \
-    if (!set && smem > 65536) { (void)hipFuncSetAttribute((const void*)attn_f32_kernel<DH_>, hipFuncAttributeMaxDynamicSharedMemorySize, smem); set = true; } \
+    static const hipError_t once =                                                                     \
+        smem > 65536 ? hipFuncSetAttribute((const void*)attn_f32_kernel<DH_>, hipFuncAttributeMaxDynamicSharedMemorySize, smem) : hipSuccess; \
+    if (once != hipSuccess) return OVM_ERR_HIP;                                                        \
     hipLaunchKernelGGL((attn_f32_kernel<DH_>), grid, block, smem, s, pv);                               \
   }
   if (p.DH == 16) OVM_ATTN_F32(16)
@@ -1366,8 +1302,8 @@ int launch_biattn(const BiAttnParams& p, hipStream_t s) {
   if (p.chunk != w.chunk || p.nchunk != w.nchunk) return OVM_ERR_SHAPE;
   if (w.mfma) {
     if (p.ldq % 4 || p.ldk % 4 || p.ldvv % 4 || p.ldvt % 4 || p.ldcv % 4) return OVM_ERR_SHAPE;
-    static bool set = false;
-    if (!set) { (void)hipFuncSetAttribute((const void*)biattn_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kBiSmem); set = true; }
+    static const hipError_t once = hipFuncSetAttribute((const void*)biattn_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kBiSmem);
+    if (once != hipSuccess) return OVM_ERR_HIP;
     hipLaunchKernelGGL(biattn_mfma_kernel, dim3((unsigned)p.nchunk, (unsigned)p.H), dim3(256), kBiSmem, s, p);
     hipLaunchKernelGGL(biattn_mfma_combine_kernel, dim3((unsigned)(p.T * (p.H * p.dh / 64))), dim3(256), 0, s, p);
     return hipGetLastError() == hipSuccess ? OVM_OK : OVM_ERR_HIP;
@@ -1386,9 +1322,9 @@ void msdeform_set_vec(int v) { g_msdeform_vec = v; }
 
 int launch_msdeform_fused(const MsDeformParams& p, hipStream_t s) {
   if (p.L > 8 || p.Q <= 0) return p.Q <= 0 ? OVM_OK : OVM_ERR_CAPACITY;
-  const bool al16 = !(((uintptr_t)p.value | (uintptr_t)p.ow | (uintptr_t)p.out | (uintptr_t)p.ohi | (uintptr_t)p.olo) & 15);
+  const bool aligned = !(((uintptr_t)p.value | (uintptr_t)p.ow | (uintptr_t)p.out | (uintptr_t)p.ohi | (uintptr_t)p.olo) & 15);
   if (g_msdeform_vec && p.L * p.P == 16 && p.dh % 4 == 0 && p.ldv % 4 == 0 && p.ldow % 4 == 0 && p.ldo % 4 == 0 && p.ldoh % 4 == 0 &&
-      (p.H * p.L * p.P * 2) % 4 == 0 && al16) {
+      (p.H * p.L * p.P * 2) % 4 == 0 && aligned) {
     hipLaunchKernelGGL(msdeform_fused4_kernel<16>, g1((long)p.Q * p.H * (p.dh / 4)), dim3(256), 0, s, p);
     return hipGetLastError() == hipSuccess ? OVM_OK : OVM_ERR_HIP;
   }
