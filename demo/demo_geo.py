@@ -16,6 +16,13 @@ left out and counted in the printed line) and ``<name>_combine.jpg``, demo.py's 
 view shows the depth map as a point cloud under the boxes, each box's points tinted with its colour. ``<name>_boxes.jpg`` (the input)
 when nothing is lifted.
 
+``--points-file FILE`` replaces the detector with clicks: ``{image name: [{"points": [[x, y], ...], "labels": [1, 0, ...],
+"category_name": str, optional "bbox": xywh, optional "score"}]}`` (labels 1 foreground, 0 background; at most 8 points). Neither
+GroundingDINO weights nor a vocabulary nor ``--labels-file`` are needed: Segment Anything masks what was clicked (plane [2], as for
+boxes; a "bbox" joins the clicks as a box prompt) and the mask is lifted. The record's 2D box is the entry's "bbox", else the tight box
+of its mask; its score the entry's, else 1.0. ``--sam-refine N`` runs N refinement passes behind the first (the same prompt with the
+previous low-resolution logits as ``mask_input``), for boxes and for clicks.
+
 The LIFT model is not built: ``MODEL.WEIGHTS`` is not needed, the config supplies the detector's settings and ``OUTPUT_DIR``.
 """
 import argparse
@@ -33,7 +40,7 @@ for p in (os.path.join(ROOT, "tools"), os.path.join(ROOT, "demo"), ROOT):
 
 from demo import write_views  # noqa: E402
 from make_oracle2d import build_caption, build_detector, gdino_postprocess, phrase_spans  # noqa: E402
-from ovmono3d_geo import check_args, sam_masks, xywh_to_xyxy  # noqa: E402
+from ovmono3d_geo import check_args, refined_masks, sam_masks, xywh_to_xyxy  # noqa: E402
 
 from ovmono3d_amd.data.depth_prompt import add_depth_arguments, build_depth_prompt, load_depth  # noqa: E402
 from ovmono3d_amd.data.gpu_jpeg import read_image_device  # noqa: E402
@@ -66,18 +73,52 @@ def box_masks(boxes_xyxy, h, w, device):
     return planes
 
 
+def group_point_prompts(entries):
+    """{(point count, has box): [positions in ``entries``]}, in order of first appearance. One predict_prompts call takes prompts of one
+    shape; no prompt is padded with label -1 points to fit another's, so each sees exactly its own tokens."""
+    groups = {}
+    for i, e in enumerate(entries):
+        if len(e["points"]) != len(e["labels"]):
+            raise SystemExit(f"--points-file: entry {i} has {len(e['points'])} points and {len(e['labels'])} labels")
+        groups.setdefault((len(e["points"]), "bbox" in e), []).append(i)
+    return groups
+
+
+def point_masks(predictor, bgr, entries, refine=0):
+    """SAM's plane [2] for the click prompts ``entries`` of one image: (device uint8 [n, H, W] in the entries' order, xyxy boxes float64
+    [n, 4]: the entry's own "bbox", else the tight box of its mask - zeros for an empty one)."""
+    h, w = int(bgr.shape[0]), int(bgr.shape[1])
+    planes = torch.zeros((len(entries), h, w), dtype=torch.uint8, device=bgr.device)
+    boxes = np.zeros((len(entries), 4), np.float64)
+    if not entries:
+        return planes, boxes
+    predictor.set_image(bgr, image_format="BGR")
+    for (_, has_box), idx in group_point_prompts(entries).items():
+        given = np.asarray([xywh_to_xyxy(entries[i]["bbox"]) for i in idx], np.float64) if has_box else None
+        masks = refined_masks(predictor, refine, point_coords=np.asarray([entries[i]["points"] for i in idx], np.float32),
+                              point_labels=np.asarray([entries[i]["labels"] for i in idx], np.int32), boxes=given)
+        planes[idx] = masks
+        boxes[idx] = given if has_box else predictor.mask_boxes(masks)[0].cpu().numpy().astype(np.float64)
+    return planes, boxes
+
+
 def do_test(args, cfg):
     from ovmono3d_amd import vis
     dev = torch.device("cuda", torch.cuda.current_device())
     ims = sorted(f for f in os.listdir(args.input_folder) if not f.endswith(".json"))
-    with open(args.labels_file) as f:
-        cats_per_img = json.load(f)
+    cats_per_img, points_per_img = {}, None
+    if args.points_file:
+        with open(args.points_file) as f:
+            points_per_img = json.load(f)
+    else:
+        with open(args.labels_file) as f:
+            cats_per_img = json.load(f)
     boxes_per_img = None
     if args.boxes_file:
         with open(args.boxes_file) as f:
             boxes_per_img = json.load(f)
     detector = resize = None
-    if boxes_per_img is None:
+    if boxes_per_img is None and points_per_img is None:
         detector = build_detector(cfg, dev)
         resize = ResizeShortestEdgeGPU(cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST)
     depth_source = None
@@ -92,7 +133,8 @@ def do_test(args, cfg):
     os.makedirs(cfg.OUTPUT_DIR, exist_ok=True)
     for name in ims:
         im_name = os.path.splitext(name)[0]
-        cats = cats_per_img.get(im_name, [])
+        entries = points_per_img.get(im_name, []) if points_per_img is not None else None
+        cats = cats_per_img.get(im_name, []) if entries is None else [e["category_name"] for e in entries]
         if cats == []:
             continue
         stages, t0 = {}, time.perf_counter()
@@ -112,7 +154,10 @@ def do_test(args, cfg):
         px, py = (w / 2, h / 2) if len(principal_point) == 0 else principal_point
         K = np.array([[focal_length, 0.0, px], [0.0, focal_length, py], [0.0, 0.0, 1.0]])
         lap("read")
-        if boxes_per_img is not None:
+        if entries is not None:                                              # the 2D boxes come with the masks, below
+            boxes = np.zeros((len(entries), 4), np.float64)
+            scores, classes = [float(e.get("score", 1.0)) for e in entries], list(range(len(entries)))
+        elif boxes_per_img is not None:
             inst = boxes_per_img.get(im_name, [])
             boxes = np.asarray([xywh_to_xyxy(b["bbox"]) for b in inst], np.float64).reshape(-1, 4)
             scores, classes = [float(b.get("score", 1.0)) for b in inst], [int(b["category_id"]) for b in inst]
@@ -127,8 +172,11 @@ def do_test(args, cfg):
             else:
                 depth = torch.from_numpy(load_depth(args.depth_dir, name, h, w)).to(dev)
             lap("depth")
+            if entries is not None:
+                planes, boxes[cand] = point_masks(predictor, im, [entries[i] for i in cand], args.sam_refine)
             cboxes = boxes[cand]
-            planes = sam_masks(predictor, None, None, h, w, cboxes, bgr=im) if predictor is not None else None
+            if entries is None:
+                planes = sam_masks(predictor, None, None, h, w, cboxes, bgr=im, refine=args.sam_refine) if predictor is not None else None
             lap("masks")
             lifted = lift_boxes(depth, K, boxes_xyxy=cboxes, masks=list(planes) if planes is not None else None, params=params)
             lap("lift")
@@ -158,7 +206,12 @@ def argument_parser():
     parser = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     parser.add_argument("--config-file", default="", metavar="FILE", help="path to config file")
     parser.add_argument("--input-folder", type=str, help="folder of images to process", required=True)
-    parser.add_argument("--labels-file", type=str, help="path to labels file: {image name: [category names]}", required=True)
+    parser.add_argument("--labels-file", type=str, default="", help="path to labels file: {image name: [category names]} (required without --points-file)")
+    parser.add_argument("--points-file", type=str, default="",
+                        help="click prompts per image ({image name: [{points [[x, y]], labels [1 | 0], category_name, optional bbox xywh, optional score}]}) "
+                             "instead of the detector: Segment Anything masks what was clicked")
+    parser.add_argument("--sam-refine", type=int, default=0, metavar="N",
+                        help="--mask sam: N more passes per prompt with the previous pass's low-resolution logits as mask_input (default 0)")
     parser.add_argument("--boxes-file", type=str, default="", help="2D boxes per image ({image name: [{bbox xywh, category_id, score}]}) instead of the detector")
     parser.add_argument("--focal-length", type=float, default=0, help="focal length for image inputs (in px)")
     parser.add_argument("--principal-point", type=float, default=[], nargs=2, help="principal point for image inputs (in px)")
@@ -181,7 +234,13 @@ def argument_parser():
 
 def check_arguments(args, parser):
     """Exit status 2 for what cannot work, before any device call."""
-    check_args(args, parser)                                                 # --depth-dir with --depth files only (tools/ovmono3d_geo.py)
+    check_args(args, parser)                                                 # --depth-dir with --depth files only, --sam-refine (tools/ovmono3d_geo.py)
+    if args.points_file and args.mask != "sam":
+        parser.error("--points-file prompts Segment Anything with the clicks: it needs --mask sam, not --mask box")
+    if args.points_file and args.boxes_file:
+        parser.error("--points-file and --boxes-file both replace the detector: give one")
+    if not args.points_file and not args.labels_file:
+        parser.error("the following arguments are required: --labels-file (or --points-file)")
     if args.depth == "depthpro" and not args.depthpro_weights:
         parser.error("--depth depthpro needs --depthpro-weights FILE")
     if args.depth != "depthpro" and args.dump_depth:

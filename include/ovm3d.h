@@ -1118,7 +1118,8 @@ int ovm_host_geo_box(const OvmGeoResult* result, const double* K, OvmGeoBox* box
  * `precision` (1: fp16 operands, 3: split fp16 x 3); softmax, LayerNorm, sin / cos and the resampling are fp32.
  *
  * Scope: head dimension 64 in the image encoder (vit_b, vit_l). vit_h (1280 wide, 16 heads: head dimension 80) is refused with
- * OVM_ERR_UNSUPPORTED. Box prompts only (no points, no mask input: the dense prompt is no_mask_embed). */
+ * OVM_ERR_UNSUPPORTED. ovm_sam_predict_boxes is the reference's call (a box, multimask outputs); ovm_sam_predict below takes
+ * points, a box, a mask input and the single-mask output as well. */
 typedef struct OvmSam OvmSam;
 typedef struct OvmSamConfig {
   int32_t embed_dim, depth, heads, patch;   /* image encoder: vit_b 768 / 12 / 12 / 16, vit_l 1024 / 24 / 16 / 16 */
@@ -1154,8 +1155,34 @@ int ovm_sam_predict_boxes(OvmSam* sam, const float* boxes_xyxy, int32_t n, int32
                           float* lowres, void* workspace, int64_t workspace_bytes, ovm_stream_t stream);
 /* tests: copy an intermediate into dst (device fp32); returns the element count or a negative error. names: "preprocessed"
  * [3][S][S] (the encoder's input as its patch rows hold it), "neck" [G][G][C], "dense_pe" [G][G][C]; of the last chunk of the
- * last predict call: "sparse" [n][2][C], "tokens_out" [n][3 + num_mask_tokens][C]. */
+ * last predict call: "sparse" [n][ns][C], "tokens_out" [n][nt][C] (ovm_sam_predict_boxes: ns = 2, nt = 3 + num_mask_tokens;
+ * ovm_sam_predict: ns and nt as described there); "dense" [G][G][C]: the dense prompt embedding of the last prompt of that chunk
+ * (its mask embedding, or no_mask_embed in every cell). */
 int64_t ovm_sam_debug_copy(OvmSam* sam, const char* name, float* dst, int64_t capacity, ovm_stream_t stream);
+
+/* SamPredictor.predict with every prompt kind, for n prompts of one shape on the image of the last ovm_sam_set_image.
+ *   points_xy   device fp32 [n][n_points][2], original pixels (x, y); labels device int32 [n][n_points]: 1 foreground, 0 background,
+ *               -1 padding (not_a_point_embed alone, no positional part). 0 <= n_points <= 8, else OVM_ERR_SHAPE. The labels live on
+ *               the device and are not read back: a value outside {1, 0, -1} is the caller's to refuse (ovmono3d_amd.sam does), the
+ *               kernel gives it the padding token. Both may be NULL when n_points == 0.
+ *   boxes_xyxy  device fp32 [n][4] or NULL. Without a box segment_anything appends one padding token, with a box it does not: the
+ *               sparse embeddings are [n][ns][C], ns = n_points + (box ? 2 : 1), ordered points, (padding), (corner 0, corner 1),
+ *               and the decoder runs nt = 1 + num_mask_tokens + ns <= 15 tokens per prompt. Neither points nor box: OVM_ERR_INVALID.
+ *   mask_inputs device fp32 [n][4G][4G] low-resolution logits of an earlier call, or NULL (no_mask_embed). Run through
+ *               mask_downscaling (conv 2x2 s2 1 -> 4, LayerNorm2d, GELU, conv 2x2 s2 4 -> 16, LayerNorm2d, GELU, conv 1x1 16 -> C, fp32).
+ *   multimask   != 0: K = 3 planes (mask tokens 1..3), masks_u8 receives plane mask_index 0..2; 0: K = 1 (mask token 0, IoU column
+ *               0), mask_index must be 0.
+ *   masks_u8 device uint8 [n][H][W]; iou device fp32 [n][K] or NULL; lowres device fp32 [n][K][4G][4G] or NULL.
+ * Chunks of max_boxes prompts as ovm_sam_predict_boxes; a call with n_points == 0, a box, no mask input and multimask != 0 IS
+ * ovm_sam_predict_boxes (same launches, same bytes). Stream-ordered, no synchronisation. */
+int ovm_sam_predict_workspace(const OvmSam* sam, int32_t n, int32_t n_points, int32_t has_box, int32_t has_mask, int64_t* bytes);
+int ovm_sam_predict(OvmSam* sam, const float* points_xy, const int32_t* labels, int32_t n_points, const float* boxes_xyxy,
+                    const float* mask_inputs, int32_t n, int32_t multimask, int32_t mask_index, uint8_t* masks_u8, float* iou, float* lowres,
+                    void* workspace, int64_t workspace_bytes, ovm_stream_t stream);
+/* The tight box and the pixel count of n masks (device uint8 [n][H][W], nonzero = inside): boxes_xyxy_out device fp32 [n][4] =
+ * (xmin, ymin, xmax + 1, ymax + 1), counts_out device int32 [n]; an empty mask gives zeros. Integer reductions (wave, then
+ * atomicMin / atomicMax / atomicAdd into the outputs): exact. boxes_xyxy_out 16-byte aligned. Stream-ordered. */
+int ovm_sam_mask_boxes(const uint8_t* masks_u8, int32_t n, int32_t H, int32_t W, float* boxes_xyxy_out, int32_t* counts_out, ovm_stream_t stream);
 
 /* ---- Depth Pro, metric depth ------------------------------------------------------------------------------------------------
  * The depth source of OVMono3D-GEO (reference tools/ovmono3d_geo.py:267,290-295: depth_pro's model.infer(image, f_px)). The
@@ -1229,6 +1256,24 @@ int ovm_op_sam_ln_gelu(float* x, int64_t M, int32_t D, const float* gamma, const
  * 256 % heads == 0, G2 % (256 / heads) == 0, ldq, ld, ldo >= 16 heads and ldq % 4 == ldo % 4 == 0; q and o 16-byte aligned. */
 int ovm_op_sam_i2t_attn(const float* q, int32_t ldq, const float* k, const float* v, int32_t ld, int32_t nt, int32_t heads, int32_t G2, int32_t nb,
                         float scale, float* o, int32_t ldo, ovm_stream_t stream);
+/* The same kernel instantiated for up to 16 tokens (32 KB of LDS): 1 <= nt <= 16, every other limit as above; for nt <= 8 the bytes
+ * of ovm_op_sam_i2t_attn. */
+int ovm_op_sam_i2t_attn16(const float* q, int32_t ldq, const float* k, const float* v, int32_t ld, int32_t nt, int32_t heads, int32_t G2, int32_t nb,
+                          float scale, float* o, int32_t ldo, ovm_stream_t stream);
+/* Tokens of nb prompts with P points each (and a box each when boxes != NULL): tok [nb][nout + ns][C] = out_tokens [nout][C], then
+ * the ns = P + (boxes ? 2 : 1) sparse rows, which sparse [nb][ns][C] receives as well: point p = PE of points [nb][P][2] (x, y;
+ * scaled, + 0.5, / S and encoded as the corners of ovm_op_sam_box_tokens) + point_emb [2][C] row 1 for label 1, row 0 for label 0;
+ * any other label: not_a_point [C] alone. Without boxes one more not_a_point row follows; with boxes [nb][4] the two corner rows of
+ * ovm_op_sam_box_tokens. labels int32 [nb][P]; points and labels may be NULL when P == 0. P > 8 or C % 2 != 0: OVM_ERR_SHAPE. */
+int ovm_op_sam_point_tokens(const float* points, const int32_t* labels, const float* boxes, int32_t nb, int32_t P, int32_t nout, int32_t C,
+                            const float* out_tokens, const float* gauss, const float* point_emb, const float* not_a_point, const float* corner,
+                            int32_t H, int32_t W, int32_t newh, int32_t neww, int32_t S, float* tok, float* sparse, ovm_stream_t stream);
+/* mask_downscaling of the prompt encoder, fused, fp32: mask [n][4G][4G] -> out [n][G*G][C], row i * G + j = conv1x1(GELU(LN2d(conv
+ * 2x2 s2(GELU(LN2d(conv 2x2 s2(mask patch 4i.., 4j..))))))). w0 [4][1][2][2], b0 [4], g1 / be1 [4] (LayerNorm2d, eps 1e-6, biased
+ * variance over the channels), w3 [16][4][2][2], b3 [16], g4 / be4 [16], w6 [C][16], b6 [C]. C outside 1 .. 256: OVM_ERR_SHAPE. */
+int ovm_op_sam_mask_embed(const float* mask, int32_t n, int32_t G, int32_t C, const float* w0, const float* b0, const float* g1, const float* be1,
+                          const float* w3, const float* b3, const float* g4, const float* be4, const float* w6, const float* b6, float* out,
+                          ovm_stream_t stream);
 /* Hypernetwork product over the blocked upscaled map up [nb * G*G * 4][4 * C8]: pixel (4 i + 2 a + a2, 4 j + 2 b + b2) of box n is
  * row (n * G*G + i * G + j) * 4 + a * 2 + b, columns (a2 * 2 + b2) * C8 .. + C8. out[n * out_box_stride + t * L*L + Y * L + X] =
  * hyper[n * ld_hyper + (t0 + t) * C8 ..] . up[n][Y][X][:], t < ntk, L = 4 G. OVM_ERR_SHAPE unless C8 % 4 == 0, ld_hyper % 4 == 0,

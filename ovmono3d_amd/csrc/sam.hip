@@ -1,11 +1,14 @@
-// Segment Anything with box prompts (include/ovm3d.h, "Segment Anything, box-prompted"): SamPredictor.set_image / predict of
-// segment_anything as OVMono3D-GEO calls them (reference tools/ovmono3d_geo.py:213-217,270-272,308-309).
+// Segment Anything (include/ovm3d.h, "Segment Anything, box-prompted"): SamPredictor.set_image / predict of segment_anything as
+// OVMono3D-GEO calls them (reference tools/ovmono3d_geo.py:213-217,270-272,308-309: a box, multimask outputs), and the predictor's
+// other prompts (points, a box with points, a mask input, the single-mask output: ovm_sam_predict).
 //
 // The image encoder's blocks are a Tower of the segment_anything family (tower.hpp: configure / load / tower_forward). Everything behind them is
 // sequenced here from the generic fp32 device ops (ovm_g_linear / ovm_g_layernorm / ovm_g_bmm2 / ovm_g_softmax) plus the kernels
 // of this file:
-//   sam_i2t_attn_kernel   image -> token cross attention: G*G queries against <= 8 token keys per box, score + softmax + value sum
-//                         in registers (a tiled attention kernel would spend its key tile on 7 keys)
+//   sam_i2t_attn_kernel   image -> token cross attention: G*G queries against <= 8 (box prompts) or <= 16 token keys per prompt,
+//                         score + softmax + value sum in registers (a tiled attention kernel would spend its key tile on 7 keys)
+//   sam_point_tokens_kernel / sam_mask_embed_kernel   the prompt encoder for points and for a mask input (mask_downscaling, fused)
+//   sam_mask_boxes_kernel tight box and pixel count of a mask plane
 //   sam_mask_out_kernel   postprocess_masks + threshold: both bilinear resamplings (4G -> S, crop, -> H x W) evaluated per output
 //                         pixel from the low-resolution logits, uint8 written at (H, W); the S x S plane never exists in HBM
 //   sam_mask_prod_kernel  hypernetwork product over the requested mask tokens
@@ -34,6 +37,8 @@ struct Norm { float* g = nullptr; float* b = nullptr; };
 struct DecLayer { Attn self, t2i, i2t; PackedLin lin1, lin2; Norm n1, n2, n3, n4; };
 
 constexpr int kMaxTok = 8;           // tokens per box the image -> token kernel holds (1 IoU + mask tokens + 2 corners)
+constexpr int kMaxTok16 = 16;        // its second instantiation: point prompts
+constexpr int kMaxPoints = 8;        // points per prompt: 5 + 8 + 2 = 15 tokens
 constexpr float kDecEps = 1e-5f;     // nn.LayerNorm default of the two-way transformer
 constexpr float kLn2dEps = 1e-6f;    // LayerNorm2d of the neck and the upscaling
 
@@ -49,6 +54,9 @@ struct OvmSam : ovm::Loader {
   half_t *pad_hi = nullptr, *pad_lo = nullptr; float *T1 = nullptr, *T2 = nullptr, *emb = nullptr, *src0 = nullptr, *pe = nullptr;
   // prompt encoder
   float *gauss = nullptr, *corner = nullptr /* point_embeddings 2, 3: [2][C] */, *no_mask = nullptr;
+  float *point_emb = nullptr /* point_embeddings 0, 1: [2][C] */, *not_a_point = nullptr;
+  float *md_w0 = nullptr, *md_b0 = nullptr, *md_g1 = nullptr, *md_be1 = nullptr, *md_w3 = nullptr, *md_b3 = nullptr, *md_g4 = nullptr, *md_be4 = nullptr,
+        *md_w6 = nullptr, *md_b6 = nullptr;                                                       // mask_downscaling 0, 1, 3, 4, 6
   // decoder
   float* out_tokens = nullptr;          // [1 + num_mask_tokens][C]: iou_token, mask_tokens
   std::vector<DecLayer> layers; Attn fin; Norm nfin;
@@ -59,7 +67,7 @@ struct OvmSam : ovm::Loader {
   int *tab = nullptr; size_t tab_cap = 0; int tabH = -1, tabW = -1, xk = 0, yk = 0; size_t off_xc = 0, off_yb = 0, off_yc = 0;
   std::vector<int> tab_host;
   // debug copies of the last chunk
-  float *dbg_sparse = nullptr, *dbg_tokens = nullptr; int dbg_n = 0;
+  float *dbg_sparse = nullptr, *dbg_tokens = nullptr, *dbg_dense = nullptr; int dbg_n = 0, dbg_ns = 2, dbg_nt = 0; bool dbg_dense_mask = false;
 };
 
 namespace {
@@ -131,6 +139,93 @@ __global__ void sam_box_tokens_kernel(const float* __restrict__ boxes, int nb, i
   sp[f] = s; sp[F + f] = c;
 }
 
+// tokens of one chunk with P points per prompt: tok[b] = [iou_token, mask_tokens, points, then one padding token (no boxes) or the two
+// corners]; the sparse rows go to `sparse` [nb][ns][C] as well. A point is treated as a corner is (apply_coords in fp64, + 0.5, / S in
+// fp32) and gets point_embeddings[label] for label 0 / 1; any other label is PromptEncoder's -1: not_a_point_embed alone.
+__global__ void sam_point_tokens_kernel(const float* __restrict__ points, const int* __restrict__ labels, const float* __restrict__ boxes, int nb, int P,
+                                        int nout, int C, const float* __restrict__ out_tokens, const float* __restrict__ gauss,
+                                        const float* __restrict__ point_emb, const float* __restrict__ not_a_point, const float* __restrict__ corner,
+                                        double sx, double sy, float S, float* __restrict__ tok, float* __restrict__ sparse) {
+  const int ns = P + (boxes ? 2 : 1), nt = nout + ns, F = C / 2;
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long)nb * nt * F) return;
+  const int f = (int)(idx % F), t = (int)((idx / F) % nt), b = (int)(idx / ((long)F * nt));
+  float* o = tok + ((size_t)b * nt + t) * C;
+  if (t < nout) { o[f] = out_tokens[(size_t)t * C + f]; o[F + f] = out_tokens[(size_t)t * C + F + f]; return; }
+  const int k = t - nout;
+  const int lab = k < P ? labels[(size_t)b * P + k] : -1;
+  float s, c;
+  if (k < P && (lab == 0 || lab == 1)) {
+    const float* pt = points + ((size_t)b * P + k) * 2;
+    const float px = (float)((double)pt[0] * sx), py = (float)((double)pt[1] * sy);
+    pe_encode((px + 0.5f) / S, (py + 0.5f) / S, gauss, F, f, &s, &c);
+    s += point_emb[(size_t)lab * C + f]; c += point_emb[(size_t)lab * C + F + f];
+  } else if (k < P || !boxes) {
+    s = not_a_point[f]; c = not_a_point[F + f];
+  } else {
+    const int j = k - P;
+    const float px = (float)((double)boxes[b * 4 + 2 * j] * sx), py = (float)((double)boxes[b * 4 + 2 * j + 1] * sy);
+    pe_encode((px + 0.5f) / S, (py + 0.5f) / S, gauss, F, f, &s, &c);
+    s += corner[(size_t)j * C + f]; c += corner[(size_t)j * C + F + f];
+  }
+  o[f] = s; o[F + f] = c;
+  float* sp = sparse + ((size_t)b * ns + k) * C;
+  sp[f] = s; sp[F + f] = c;
+}
+
+__device__ __forceinline__ float gelu_erf(float y) { return 0.5f * y * (1.0f + erff(y * 0.70710678118654752440f)); }
+
+// PromptEncoder.mask_downscaling, fused: one workgroup per embedding cell (prompt b, cell i * G + j). The cell's 4 x 4 patch of the
+// mask goes to LDS; 16 threads run conv 2x2 s2 (1 -> 4) . LayerNorm2d . GELU . conv 2x2 s2 (4 -> 16) . LayerNorm2d . GELU on it (four
+// positions x four channels, then sixteen channels), every thread c < C the 1x1 convolution's channel c. out [b][cell][C].
+__global__ __launch_bounds__(256) void sam_mask_embed_kernel(const float* __restrict__ mask, int G, int C, const float* __restrict__ w0,
+                                                             const float* __restrict__ b0, const float* __restrict__ g1, const float* __restrict__ be1,
+                                                             const float* __restrict__ w3, const float* __restrict__ b3, const float* __restrict__ g4,
+                                                             const float* __restrict__ be4, const float* __restrict__ w6, const float* __restrict__ b6,
+                                                             float eps, float* __restrict__ out) {
+  __shared__ float patch[16], s1[16], a1[16], s2[16], a2[16];
+  const int cell = blockIdx.x, b = blockIdx.y, i = cell / G, j = cell - i * G, L = 4 * G, t = threadIdx.x;
+  if (t < 16) patch[t] = mask[(size_t)b * L * L + (size_t)(4 * i + (t >> 2)) * L + 4 * j + (t & 3)];
+  __syncthreads();
+  if (t < 16) {                                                  // conv 1: position p = (py, px) of the 2 x 2 map, channel c
+    const int p = t >> 2, c = t & 3, py = p >> 1, px = p & 1;
+    float v = b0[c];
+    for (int ky = 0; ky < 2; ++ky)
+      for (int kx = 0; kx < 2; ++kx) v = fmaf(w0[c * 4 + ky * 2 + kx], patch[(2 * py + ky) * 4 + 2 * px + kx], v);
+    s1[t] = v;
+  }
+  __syncthreads();
+  if (t < 16) {                                                  // LayerNorm2d over the 4 channels of the position, GELU
+    const int p = t >> 2, c = t & 3;
+    const float mean = (s1[p * 4] + s1[p * 4 + 1] + s1[p * 4 + 2] + s1[p * 4 + 3]) * 0.25f;
+    float q = 0.f;
+    for (int k = 0; k < 4; ++k) { const float d = s1[p * 4 + k] - mean; q = fmaf(d, d, q); }
+    a1[t] = gelu_erf((s1[t] - mean) / sqrtf(q * 0.25f + eps) * g1[c] + be1[c]);
+  }
+  __syncthreads();
+  if (t < 16) {                                                  // conv 2: channel t from [ci][ky][kx]; position (ky, kx) is a1's p
+    float v = b3[t];
+    for (int ci = 0; ci < 4; ++ci)
+      for (int p = 0; p < 4; ++p) v = fmaf(w3[t * 16 + ci * 4 + p], a1[p * 4 + ci], v);
+    s2[t] = v;
+  }
+  __syncthreads();
+  if (t < 16) {
+    float mean = 0.f;
+    for (int k = 0; k < 16; ++k) mean += s2[k];
+    mean *= 0.0625f;
+    float q = 0.f;
+    for (int k = 0; k < 16; ++k) { const float d = s2[k] - mean; q = fmaf(d, d, q); }
+    a2[t] = gelu_erf((s2[t] - mean) / sqrtf(q * 0.0625f + eps) * g4[t] + be4[t]);
+  }
+  __syncthreads();
+  if (t < C) {
+    float v = b6[t];
+    for (int k = 0; k < 16; ++k) v = fmaf(w6[t * 16 + k], a2[k], v);
+    out[((size_t)b * G * G + cell) * C + t] = v;
+  }
+}
+
 // rows of D channels: x = GELU(LayerNorm(x)), in place; one wave per row (D <= 256)
 __global__ __launch_bounds__(256) void sam_ln_gelu_kernel(float* __restrict__ x, long M, int D, const float* __restrict__ g,
                                                           const float* __restrict__ b, float eps) {
@@ -154,12 +249,12 @@ __global__ __launch_bounds__(256) void sam_ln_gelu_kernel(float* __restrict__ x,
 }
 
 // Image -> token cross attention. q [nb * G2][ldq] (heads x DH columns), k / v [nb * nt][ld] -> o [nb * G2][ldo]. One thread per
-// (pixel, head): its DH query values in registers, the box's nt keys and values in LDS, softmax over nt in registers. A workgroup
+// (pixel, head): its DH query values in registers, the box's nt <= MAXT keys and values in LDS, softmax over nt in registers. A workgroup
 // of 256 threads covers 256 / heads consecutive pixels of ONE box (G2 % (256 / heads) == 0 is checked by the launcher).
-template <int DH>
+template <int DH, int MAXT>                                     // MAXT: the token bound (LDS: 2 KB per token)
 __global__ __launch_bounds__(256) void sam_i2t_attn_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ k, const float* __restrict__ v,
                                                            int ld, int nt, int heads, int G2, long rows, float scale, float* __restrict__ o, int ldo) {
-  __shared__ float ks[kMaxTok * 256], vs[kMaxTok * 256];
+  __shared__ float ks[MAXT * 256], vs[MAXT * 256];
   const int ppb = 256 / heads;                                  // pixels per workgroup
   const long row0 = (long)blockIdx.x * ppb;
   const int box = (int)(row0 / G2), width = heads * DH;
@@ -175,9 +270,9 @@ __global__ __launch_bounds__(256) void sam_i2t_attn_kernel(const float* __restri
   const float4* qp = reinterpret_cast<const float4*>(q + (size_t)row * ldq + h * DH);
 #pragma unroll
   for (int d = 0; d < DH / 4; ++d) { const float4 t4 = qp[d]; qr[4 * d] = t4.x; qr[4 * d + 1] = t4.y; qr[4 * d + 2] = t4.z; qr[4 * d + 3] = t4.w; }
-  float sc[kMaxTok]; float mx = -INFINITY;
+  float sc[MAXT]; float mx = -INFINITY;
 #pragma unroll
-  for (int t = 0; t < kMaxTok; ++t) {
+  for (int t = 0; t < MAXT; ++t) {
     float a = 0.f;
     if (t < nt) {
       const float* kr = ks + t * width + h * DH;
@@ -189,13 +284,13 @@ __global__ __launch_bounds__(256) void sam_i2t_attn_kernel(const float* __restri
   }
   float sum = 0.f;
 #pragma unroll
-  for (int t = 0; t < kMaxTok; ++t) { sc[t] = t < nt ? expf(sc[t] - mx) : 0.f; sum += sc[t]; }
+  for (int t = 0; t < MAXT; ++t) { sc[t] = t < nt ? expf(sc[t] - mx) : 0.f; sum += sc[t]; }
   const float inv = 1.0f / sum;
   float acc[DH];
 #pragma unroll
   for (int d = 0; d < DH; ++d) acc[d] = 0.f;
 #pragma unroll
-  for (int t = 0; t < kMaxTok; ++t)
+  for (int t = 0; t < MAXT; ++t)
     if (t < nt) {
       const float p = sc[t] * inv; const float* vr = vs + t * width + h * DH;
 #pragma unroll
@@ -281,11 +376,47 @@ __global__ void sam_unpatch_kernel(const half_t* __restrict__ hi, const half_t* 
   out[idx] = (float)hi[o] + (lo ? (float)lo[o] : 0.f);
 }
 
-// iou[b][0:3] = head[b][1:4]
-__global__ void sam_iou_slice_kernel(const float* __restrict__ head, int ldh, int n, float* __restrict__ iou) {
+// iou[b][0:nc] = head[b][c0 : c0 + nc] (multimask: columns 1 .. 3; single mask: column 0)
+__global__ void sam_iou_slice_kernel(const float* __restrict__ head, int ldh, int n, int c0, int nc, float* __restrict__ iou) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n * 3) return;
-  iou[i] = head[(size_t)(i / 3) * ldh + 1 + i % 3];
+  if (i >= n * nc) return;
+  iou[i] = head[(size_t)(i / nc) * ldh + c0 + i % nc];
+}
+
+// Tight box and pixel count of mask plane blockIdx.y: per-thread extremes over a grid-stride walk, a wave reduction, then one integer
+// atomic per wave and value into box [n][4] (xmin, ymin, xmax, ymax as int32, preset to INT_MAX / -1) and cnt [n].
+__global__ void sam_mask_boxes_init_kernel(int* __restrict__ box, int* __restrict__ cnt, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  box[4 * i] = 0x7fffffff; box[4 * i + 1] = 0x7fffffff; box[4 * i + 2] = -1; box[4 * i + 3] = -1; cnt[i] = 0;
+}
+
+__global__ __launch_bounds__(256) void sam_mask_boxes_kernel(const uint8_t* __restrict__ masks, int H, int W, int* __restrict__ box, int* __restrict__ cnt) {
+  const int b = blockIdx.y; const long HW = (long)H * W;
+  const uint8_t* mk = masks + (size_t)b * HW;
+  int x0 = 0x7fffffff, y0 = 0x7fffffff, x1 = -1, y1 = -1, c = 0;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < HW; i += (long)gridDim.x * 256)
+    if (mk[i]) {
+      const int y = (int)(i / W), x = (int)(i - (long)y * W);
+      x0 = min(x0, x); y0 = min(y0, y); x1 = max(x1, x); y1 = max(y1, y); ++c;
+    }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    x0 = min(x0, __shfl_xor(x0, o, 64)); y0 = min(y0, __shfl_xor(y0, o, 64));
+    x1 = max(x1, __shfl_xor(x1, o, 64)); y1 = max(y1, __shfl_xor(y1, o, 64)); c += __shfl_xor(c, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0 && c > 0) {
+    atomicMin(&box[4 * b], x0); atomicMin(&box[4 * b + 1], y0); atomicMax(&box[4 * b + 2], x1); atomicMax(&box[4 * b + 3], y1); atomicAdd(&cnt[b], c);
+  }
+}
+
+// int32 (xmin, ymin, xmax, ymax) -> fp32 (xmin, ymin, xmax + 1, ymax + 1) in place; zeros for an empty mask
+__global__ void sam_mask_boxes_final_kernel(int* __restrict__ box, const int* __restrict__ cnt, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int4 v = reinterpret_cast<const int4*>(box)[i];
+  const bool any = cnt[i] > 0;
+  reinterpret_cast<float4*>(box)[i] = any ? make_float4((float)v.x, (float)v.y, (float)(v.z + 1), (float)(v.w + 1)) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
 int lin(OvmSam* m, const PackedLin& w, const float* x, int ldx, long M, int act, const float* res, int ldr, float* y, int ldy, hipStream_t s) {
@@ -324,6 +455,26 @@ int launch_box_tokens(const float* boxes, int nb, int nout, int C, const float* 
   return last_launch();
 }
 
+// points and a box or the padding token per prompt (the kernel's comment); P <= kMaxPoints
+int launch_point_tokens(const float* points, const int* labels, const float* boxes, int nb, int P, int nout, int C, const float* out_tokens, const float* gauss,
+                        const float* point_emb, const float* not_a_point, const float* corner, int H, int W, int newh, int neww, int S, float* tok,
+                        float* sparse, hipStream_t s) {
+  if (P < 0 || P > kMaxPoints || (P == 0 && !boxes) || (P > 0 && (!points || !labels))) return OVM_ERR_SHAPE;
+  const int nt = nout + P + (boxes ? 2 : 1);
+  hipLaunchKernelGGL(sam_point_tokens_kernel, g1((long)nb * nt * (C / 2)), dim3(256), 0, s, points, labels, boxes, nb, P, nout, C, out_tokens, gauss, point_emb,
+                     not_a_point, corner, (double)neww / (double)W, (double)newh / (double)H, (float)S, tok, sparse);
+  return last_launch();
+}
+
+// one workgroup of 256 threads per cell: C <= 256; grid.y = prompts
+int launch_mask_embed(const float* mask, int n, int G, int C, const float* w0, const float* b0, const float* g1_, const float* be1, const float* w3,
+                      const float* b3, const float* g4, const float* be4, const float* w6, const float* b6, float* out, hipStream_t s) {
+  if (C < 1 || C > 256 || G < 1 || n < 1 || n > 65535) return OVM_ERR_SHAPE;
+  hipLaunchKernelGGL(sam_mask_embed_kernel, dim3((unsigned)(G * G), (unsigned)n), dim3(256), 0, s, mask, G, C, w0, b0, g1_, be1, w3, b3, g4, be4, w6, b6,
+                     kLn2dEps, out);
+  return last_launch();
+}
+
 // one wave holds a row in four registers per lane: D <= 256
 int launch_ln_gelu(float* x, long M, int D, const float* g, const float* b, float eps, hipStream_t s) {
   if (D < 1 || D > 256) return OVM_ERR_SHAPE;
@@ -331,13 +482,14 @@ int launch_ln_gelu(float* x, long M, int D, const float* g, const float* b, floa
   return last_launch();
 }
 
-// head dimension 16; a workgroup's 256 / heads pixels belong to one box and its LDS holds kMaxTok tokens of 256 columns
+// head dimension 16; a workgroup's 256 / heads pixels belong to one box and its LDS holds MAXT tokens of 256 columns
+template <int MAXT>
 int launch_i2t_attn(const float* q, int ldq, const float* k, const float* v, int ld, int nt, int heads, int G2, int nb, float scale, float* o, int ldo,
                     hipStream_t s) {
-  if (nt < 1 || nt > kMaxTok || heads < 1 || heads > 16 || 256 % heads != 0 || G2 < 1 || G2 % (256 / heads) != 0) return OVM_ERR_SHAPE;
+  if (nt < 1 || nt > MAXT || heads < 1 || heads > 16 || 256 % heads != 0 || G2 < 1 || G2 % (256 / heads) != 0) return OVM_ERR_SHAPE;
   if (ldq < heads * 16 || ld < heads * 16 || ldo < heads * 16 || ldq % 4 != 0 || ldo % 4 != 0) return OVM_ERR_SHAPE;
   const long rows = (long)nb * G2;
-  hipLaunchKernelGGL(sam_i2t_attn_kernel<16>, dim3((unsigned)(rows / (256 / heads))), dim3(256), 0, s, q, ldq, k, v, ld, nt, heads, G2, rows, scale, o, ldo);
+  hipLaunchKernelGGL((sam_i2t_attn_kernel<16, MAXT>), dim3((unsigned)(rows / (256 / heads))), dim3(256), 0, s, q, ldq, k, v, ld, nt, heads, G2, rows, scale, o, ldo);
   return last_launch();
 }
 
@@ -359,14 +511,25 @@ int launch_unpatch(const half_t* hi, const half_t* lo, int ld, int G, int P, flo
   return last_launch();
 }
 
-int launch_iou_slice(const float* head, int ldh, int n, float* iou, hipStream_t s) {
-  hipLaunchKernelGGL(sam_iou_slice_kernel, g1((long)n * 3), dim3(256), 0, s, head, ldh, n, iou);
+int launch_iou_slice(const float* head, int ldh, int n, int c0, int nc, float* iou, hipStream_t s) {
+  hipLaunchKernelGGL(sam_iou_slice_kernel, g1((long)n * nc), dim3(256), 0, s, head, ldh, n, c0, nc, iou);
+  return last_launch();
+}
+
+// box: fp32 [n][4] used as int32 until the last kernel; every plane gets up to 256 workgroups, each thread at least 8 pixels
+int launch_mask_boxes(const uint8_t* masks, int n, int H, int W, float* box, int* cnt, hipStream_t s) {
+  if (n > 65535) return OVM_ERR_SHAPE;
+  const long HW = (long)H * W;
+  long gx = (HW + 2047) / 2048; if (gx > 256) gx = 256;
+  hipLaunchKernelGGL(sam_mask_boxes_init_kernel, g1(n), dim3(256), 0, s, (int*)box, cnt, n);
+  hipLaunchKernelGGL(sam_mask_boxes_kernel, dim3((unsigned)gx, (unsigned)n), dim3(256), 0, s, masks, H, W, (int*)box, cnt);
+  hipLaunchKernelGGL(sam_mask_boxes_final_kernel, g1(n), dim3(256), 0, s, (int*)box, (const int*)cnt, n);
   return last_launch();
 }
 
 // token queries [nb * nt][I] against Tk keys per box: scores (bmm) -> softmax -> context (bmm); heads x dh = I
-int token_attention(OvmSam* m, const float* Q, const float* K, const float* V, int nb, int Tk, int I, float* scores, float* ctx, hipStream_t s) {
-  const int nt = m->nt, hd = m->cfg.dec_heads, dh = I / hd;
+int token_attention(OvmSam* m, const float* Q, const float* K, const float* V, int nb, int nt, int Tk, int I, float* scores, float* ctx, hipStream_t s) {
+  const int hd = m->cfg.dec_heads, dh = I / hd;
   OVM_TRY(m, ovm_g_bmm2(Q, K, scores, nb, hd, nt, Tk, dh, I, I, Tk, (int64_t)nt * I, (int64_t)Tk * I, (int64_t)hd * nt * Tk, dh, dh, (int64_t)nt * Tk, 1,
                    1.0f / sqrtf((float)dh), s));
   OVM_TRY(m, ovm_g_softmax(scores, nb * hd * nt, Tk, Tk, nullptr, 0, 0, 0, s));
@@ -375,11 +538,12 @@ int token_attention(OvmSam* m, const float* Q, const float* K, const float* V, i
 }
 
 struct Work {                       // one chunk's buffers, carved from the caller's workspace
-  float *tok0, *q, *qpe, *tq, *tk, *tv, *tctx, *tout, *mlp, *keys, *kpe, *tmp, *iA, *iB, *scores, *up2, *hyp, *h1, *h2, *iouh, *low;
+  float *tok0, *q, *qpe, *tq, *tk, *tv, *tctx, *tout, *mlp, *keys, *kpe, *tmp, *iA, *iB, *scores, *up2, *hyp, *h1, *h2, *iouh, *low, *dense;
 };
 
-size_t carve(Work* w, char* base, const OvmSam* m, long nb) {
-  const size_t C = m->C, nt = m->nt, G2 = m->G2, I = m->I, Mt = (size_t)nb * nt, Mi = (size_t)nb * G2;
+// nt: tokens per prompt of the call; has_mask: the mask-input route's dense embeddings [nb * G2][C] follow everything else
+size_t carve(Work* w, char* base, const OvmSam* m, long nb, int nt_call, bool has_mask) {
+  const size_t C = m->C, nt = (size_t)nt_call, G2 = m->G2, I = m->I, Mt = (size_t)nb * nt, Mi = (size_t)nb * G2;
   const size_t hid = m->cfg.iou_hidden > m->C ? m->cfg.iou_hidden : m->C;
   size_t off = 0;
   auto take = [&](float** p, size_t floats) { if (w) *p = (float*)(base + off); off += (floats * 4 + 255) / 256 * 256; };
@@ -391,17 +555,40 @@ size_t carve(Work* w, char* base, const OvmSam* m, long nb) {
   take(&x->up2, Mi * 2 * C);                                        // [nb * G2 * 4][4 * C / 8]
   take(&x->hyp, (size_t)nb * m->cfg.num_mask_tokens * (C / 8)); take(&x->h1, (size_t)nb * hid); take(&x->h2, (size_t)nb * hid);
   take(&x->iouh, (size_t)nb * 128); take(&x->low, (size_t)nb * m->L * m->L);
+  x->dense = nullptr;
+  if (has_mask) take(&x->dense, Mi * C);
   return off;
 }
 
-int decode_chunk(OvmSam* m, const float* boxes, int nb, int mask_index, uint8_t* masks, float* iou, float* lowres, const Work& w, hipStream_t s) {
+// the prompts of one call (device pointers, advanced per chunk by decode's caller)
+struct Prompt {
+  const float* points = nullptr; const int* labels = nullptr; int P = 0;       // [n][P][2], [n][P]
+  const float* boxes = nullptr;                                                 // [n][4] or null
+  const float* mask_in = nullptr;                                               // [n][L][L] or null
+  bool multimask = true;
+  int ns() const { return P + (boxes ? 2 : 1); }
+};
+
+int decode_chunk(OvmSam* m, const Prompt& pr, int nb, int mask_index, uint8_t* masks, float* iou, float* lowres, const Work& w, hipStream_t s) {
   const OvmSamConfig& c = m->cfg;
-  const int C = m->C, nt = m->nt, G2 = m->G2, I = m->I, nout = 1 + c.num_mask_tokens;
+  const int C = m->C, G2 = m->G2, I = m->I, nout = 1 + c.num_mask_tokens, nt = nout + pr.ns();
   const long Mt = (long)nb * nt, Mi = (long)nb * G2;
-  // 1. tokens + sparse embeddings; src = (embedding + no_mask_embed) per box
-  OVM_TRY(m, launch_box_tokens(boxes, nb, nout, C, m->out_tokens, m->gauss, m->corner, m->H, m->W, m->newh, m->neww, m->S, w.tok0, m->dbg_sparse, s));
+  // 1. tokens + sparse embeddings (a box alone: the box kernel, as ever); src = embedding + (no_mask_embed | mask embedding) per prompt
+  if (pr.P == 0 && pr.boxes)
+    OVM_TRY(m, launch_box_tokens(pr.boxes, nb, nout, C, m->out_tokens, m->gauss, m->corner, m->H, m->W, m->newh, m->neww, m->S, w.tok0, m->dbg_sparse, s));
+  else
+    OVM_TRY(m, launch_point_tokens(pr.points, pr.labels, pr.boxes, nb, pr.P, nout, C, m->out_tokens, m->gauss, m->point_emb, m->not_a_point, m->corner, m->H,
+                                   m->W, m->newh, m->neww, m->S, w.tok0, m->dbg_sparse, s));
   OVM_HIP(m, hipMemcpyAsync(w.q, w.tok0, (size_t)Mt * C * 4, hipMemcpyDeviceToDevice, s));
-  OVM_TRY(m, bcast(m->src0, w.keys, Mi * C, (long)G2 * C, s));
+  if (pr.mask_in) {
+    OVM_TRY(m, launch_mask_embed(pr.mask_in, nb, m->G, C, m->md_w0, m->md_b0, m->md_g1, m->md_be1, m->md_w3, m->md_b3, m->md_g4, m->md_be4, m->md_w6, m->md_b6,
+                                 w.dense, s));
+    OVM_TRY(m, add_bcast(w.dense, m->emb, w.keys, Mi * C, (long)G2 * C, s));
+    OVM_HIP(m, hipMemcpyAsync(m->dbg_dense, w.dense + (size_t)(nb - 1) * G2 * C, (size_t)G2 * C * 4, hipMemcpyDeviceToDevice, s));
+  } else {
+    OVM_TRY(m, bcast(m->src0, w.keys, Mi * C, (long)G2 * C, s));
+  }
+  m->dbg_dense_mask = pr.mask_in != nullptr; m->dbg_ns = pr.ns(); m->dbg_nt = nt;
   auto norm = [&](const Norm& n, const float* x, long M, float* y) { return ovm_g_layernorm(x, nullptr, (int)M, C, n.g, n.b, kDecEps, y, s); };
   // token -> image attention of one block (also the final one): q += out_proj(attn(q + pe_q, keys + pe_k, keys)), then the norm
   auto tok_to_img = [&](const Attn& a, const Norm& n) -> int {
@@ -410,7 +597,7 @@ int decode_chunk(OvmSam* m, const float* boxes, int nb, int mask_index, uint8_t*
     OVM_TRY(m, lin(m, a.q, w.qpe, C, Mt, 0, nullptr, 0, w.tq, I, s));
     OVM_TRY(m, lin(m, a.k, w.kpe, C, Mi, 0, nullptr, 0, w.iA, I, s));
     OVM_TRY(m, lin(m, a.v, w.keys, C, Mi, 0, nullptr, 0, w.iB, I, s));
-    OVM_TRY(m, token_attention(m, w.tq, w.iA, w.iB, nb, G2, I, w.scores, w.tctx, s));
+    OVM_TRY(m, token_attention(m, w.tq, w.iA, w.iB, nb, nt, G2, I, w.scores, w.tctx, s));
     OVM_TRY(m, lin(m, a.o, w.tctx, I, Mt, 0, w.q, C, w.tout, C, s));
     return norm(n, w.tout, Mt, w.q);
   };
@@ -422,7 +609,7 @@ int decode_chunk(OvmSam* m, const float* boxes, int nb, int mask_index, uint8_t*
     OVM_TRY(m, lin(m, y.self.q, qin, C, Mt, 0, nullptr, 0, w.tq, C, s));
     OVM_TRY(m, lin(m, y.self.k, qin, C, Mt, 0, nullptr, 0, w.tk, C, s));
     OVM_TRY(m, lin(m, y.self.v, w.q, C, Mt, 0, nullptr, 0, w.tv, C, s));
-    OVM_TRY(m, token_attention(m, w.tq, w.tk, w.tv, nb, nt, C, w.scores, w.tctx, s));
+    OVM_TRY(m, token_attention(m, w.tq, w.tk, w.tv, nb, nt, nt, C, w.scores, w.tctx, s));
     OVM_TRY(m, lin(m, y.self.o, w.tctx, C, Mt, 0, l > 0 ? w.q : nullptr, C, w.tout, C, s));
     OVM_TRY(m, norm(y.n1, w.tout, Mt, w.q));
     OVM_TRY(m, tok_to_img(y.t2i, y.n2));
@@ -435,7 +622,8 @@ int decode_chunk(OvmSam* m, const float* boxes, int nb, int mask_index, uint8_t*
     OVM_TRY(m, lin(m, y.i2t.q, w.kpe, C, Mi, 0, nullptr, 0, w.iA, I, s));
     OVM_TRY(m, lin(m, y.i2t.k, w.qpe, C, Mt, 0, nullptr, 0, w.tk, I, s));
     OVM_TRY(m, lin(m, y.i2t.v, w.q, C, Mt, 0, nullptr, 0, w.tv, I, s));
-    OVM_TRY(m, launch_i2t_attn(w.iA, I, w.tk, w.tv, I, nt, c.dec_heads, G2, nb, 0.25f, w.iB, I, s));
+    if (nt <= kMaxTok) OVM_TRY(m, launch_i2t_attn<kMaxTok>(w.iA, I, w.tk, w.tv, I, nt, c.dec_heads, G2, nb, 0.25f, w.iB, I, s));
+    else OVM_TRY(m, launch_i2t_attn<kMaxTok16>(w.iA, I, w.tk, w.tv, I, nt, c.dec_heads, G2, nb, 0.25f, w.iB, I, s));
     OVM_TRY(m, lin(m, y.i2t.o, w.iB, I, Mi, 0, w.keys, C, w.tmp, C, s));
     OVM_TRY(m, norm(y.n4, w.tmp, Mi, w.keys));
   }
@@ -447,8 +635,10 @@ int decode_chunk(OvmSam* m, const float* boxes, int nb, int mask_index, uint8_t*
   OVM_TRY(m, lin(m, m->up1, w.keys, C, Mi, 0, nullptr, 0, w.tmp, C, s));
   OVM_TRY(m, launch_ln_gelu(w.tmp, Mi * 4, C4, m->upn.g, m->upn.b, kLn2dEps, s));
   OVM_TRY(m, lin(m, m->up2, w.tmp, C4, Mi * 4, 2, nullptr, 0, w.up2, 4 * C8, s));
-  // hypernetwork MLPs (every mask token when the low-resolution logits are asked for, else the requested one) and the IoU head
-  const int t_first = lowres ? 0 : 1 + mask_index, t_last = lowres ? c.num_mask_tokens : 2 + mask_index;
+  // hypernetwork MLPs (every mask token when the low-resolution logits are asked for, else the requested one) and the IoU head.
+  // multimask: the planes are mask tokens 1 .. 3 and IoU columns 1 .. 3; single mask: token 0, column 0
+  const int K = pr.multimask ? 3 : 1, tk0 = pr.multimask ? 1 : 0;
+  const int t_first = lowres ? 0 : tk0 + mask_index, t_last = lowres ? (pr.multimask ? c.num_mask_tokens : 1) : tk0 + mask_index + 1;
   for (int t = t_first; t < t_last; ++t) {
     const PackedLin* hl = &m->hyper[(size_t)t * 3];
     OVM_TRY(m, lin(m, hl[0], w.q + (size_t)(1 + t) * C, nt * C, nb, 1, nullptr, 0, w.h1, C, s));
@@ -463,12 +653,12 @@ int decode_chunk(OvmSam* m, const float* boxes, int nb, int mask_index, uint8_t*
       OVM_TRY(m, lin(m, m->iou[i], x, ldx, nb, last ? 0 : 1, nullptr, 0, y, ldy, s));
       x = y; ldx = ldy;
     }
-    if (iou) OVM_TRY(m, launch_iou_slice(w.iouh, 128, nb, iou, s));
+    if (iou) OVM_TRY(m, launch_iou_slice(w.iouh, 128, nb, tk0, K, iou, s));
   }
   // mask product: multimask slice 1:4 into `lowres`, or the requested token alone into the workspace
   const long LL = (long)m->L * m->L;
-  float* planes = lowres ? lowres : w.low; const long stride = lowres ? 3 * LL : LL;
-  OVM_TRY(m, launch_mask_prod(w.up2, w.hyp, c.num_mask_tokens * C8, lowres ? 1 : 1 + mask_index, lowres ? 3 : 1, C8, m->G, nb, planes, stride, s));
+  float* planes = lowres ? lowres : w.low; const long stride = lowres ? K * LL : LL;
+  OVM_TRY(m, launch_mask_prod(w.up2, w.hyp, c.num_mask_tokens * C8, lowres ? tk0 : tk0 + mask_index, lowres ? K : 1, C8, m->G, nb, planes, stride, s));
   // 5. postprocess_masks + threshold
   return launch_mask_out(planes + (lowres ? (size_t)mask_index * LL : 0), stride, m->L, m->S, m->newh, m->neww, m->H, m->W, nb, masks, s);
 }
@@ -501,7 +691,7 @@ int ovm_sam_create(const OvmSamConfig* cfg, const OvmTensor* weights, int32_t n_
              " / " + std::to_string(c.heads) + " heads); the attention kernels take head dimension 64 only (vit_b, vit_l; vit_h has 80)";
     return OVM_ERR_UNSUPPORTED;
   }
-  m->C = c.prompt_dim; m->S = c.image_size; m->nt = 1 + c.num_mask_tokens + 2;
+  m->C = c.prompt_dim; m->S = c.image_size; m->nt = 1 + c.num_mask_tokens + 2;       // the box route's token count
   if (c.heads < 1 || c.patch != 16 || c.image_size < 16 || c.image_size % 16 != 0 || c.prompt_dim < 64 || c.prompt_dim % 64 != 0 || c.prompt_dim > 256 ||
       c.dec_depth < 1 || c.dec_heads < 1 || c.attn_downsample < 1 || c.prompt_dim % (c.attn_downsample * c.dec_heads) != 0 ||
       c.prompt_dim / c.attn_downsample / c.dec_heads != 16 || 256 % c.dec_heads != 0 || c.num_mask_tokens != 4 || m->nt > kMaxTok || c.iou_depth < 2 ||
@@ -549,6 +739,24 @@ int ovm_sam_create(const OvmSamConfig* cfg, const OvmTensor* weights, int32_t n_
     memcpy(cr.data(), p2, (size_t)C * 4); memcpy(cr.data() + C, p3, (size_t)C * 4);
     if ((r = upload_f32(m, cr.data(), cr.size(), &m->corner))) return r;
     if ((r = upload_weight(m, wm, "prompt_encoder.no_mask_embed.weight", C, &m->no_mask))) return r;
+    // points and the mask input
+    const float *p0, *p1;
+    if ((r = find_weight(m, wm, "prompt_encoder.point_embeddings.0.weight", C, &p0))) return r;
+    if ((r = find_weight(m, wm, "prompt_encoder.point_embeddings.1.weight", C, &p1))) return r;
+    memcpy(cr.data(), p0, (size_t)C * 4); memcpy(cr.data() + C, p1, (size_t)C * 4);
+    if ((r = upload_f32(m, cr.data(), cr.size(), &m->point_emb))) return r;
+    if ((r = upload_weight(m, wm, "prompt_encoder.not_a_point_embed.weight", C, &m->not_a_point))) return r;
+    const std::string Md = "prompt_encoder.mask_downscaling.";
+    if ((r = upload_weight(m, wm, Md + "0.weight", 4 * 4, &m->md_w0))) return r;
+    if ((r = upload_weight(m, wm, Md + "0.bias", 4, &m->md_b0))) return r;
+    if ((r = upload_weight(m, wm, Md + "1.weight", 4, &m->md_g1))) return r;
+    if ((r = upload_weight(m, wm, Md + "1.bias", 4, &m->md_be1))) return r;
+    if ((r = upload_weight(m, wm, Md + "3.weight", 16 * 16, &m->md_w3))) return r;
+    if ((r = upload_weight(m, wm, Md + "3.bias", 16, &m->md_b3))) return r;
+    if ((r = upload_weight(m, wm, Md + "4.weight", 16, &m->md_g4))) return r;
+    if ((r = upload_weight(m, wm, Md + "4.bias", 16, &m->md_be4))) return r;
+    if ((r = upload_weight(m, wm, Md + "6.weight", (int64_t)C * 16, &m->md_w6))) return r;
+    if ((r = upload_weight(m, wm, Md + "6.bias", C, &m->md_b6))) return r;
     if ((r = launch_dense_pe(m->gauss, G, C / 2, m->pe, nullptr))) { m->err = "dense positional encoding launch failed"; return r; }
   }
   // ---- mask decoder
@@ -594,8 +802,11 @@ int ovm_sam_create(const OvmSamConfig* cfg, const OvmTensor* weights, int32_t n_
     }
   }
   if ((r = m->alloc(&m->rs_dst, (size_t)c.image_size * c.image_size * 3))) return r;
-  if ((r = m->alloc(&m->dbg_sparse, (size_t)c.max_boxes * 2 * C, true))) return r;
-  if ((r = m->alloc(&m->dbg_tokens, (size_t)c.max_boxes * m->nt * C, true))) return r;
+  const int ns_max = kMaxPoints + 2, nt_max = 1 + c.num_mask_tokens + ns_max;
+  if ((r = m->alloc(&m->dbg_sparse, (size_t)c.max_boxes * ns_max * C, true))) return r;
+  if ((r = m->alloc(&m->dbg_tokens, (size_t)c.max_boxes * nt_max * C, true))) return r;
+  if ((r = m->alloc(&m->dbg_dense, (size_t)G2 * C, true))) return r;
+  m->dbg_nt = m->nt;
   OVM_HIP(m, hipDeviceSynchronize());
   return OVM_OK;
 }
@@ -678,7 +889,40 @@ int ovm_sam_set_image(OvmSam* m, const OvmImage* image, int32_t flip_bgr, ovm_st
 int ovm_sam_predict_boxes_workspace(const OvmSam* m, int32_t n, int64_t* bytes) {
   if (!m || !bytes || n < 0 || !m->tower.fam) return OVM_ERR_INVALID;
   const int nb = n < m->cfg.max_boxes ? n : m->cfg.max_boxes;
-  *bytes = (int64_t)carve(nullptr, nullptr, m, nb < 1 ? 1 : nb);
+  *bytes = (int64_t)carve(nullptr, nullptr, m, nb < 1 ? 1 : nb, m->nt, false);
+  return OVM_OK;
+}
+
+int ovm_sam_predict_workspace(const OvmSam* m, int32_t n, int32_t n_points, int32_t has_box, int32_t has_mask, int64_t* bytes) {
+  if (!m || !bytes || n < 0 || !m->tower.fam) return OVM_ERR_INVALID;
+  if (n_points < 0 || n_points > kMaxPoints) return OVM_ERR_SHAPE;
+  if (n_points == 0 && !has_box) return OVM_ERR_INVALID;
+  const int nb = n < m->cfg.max_boxes ? n : m->cfg.max_boxes;
+  *bytes = (int64_t)carve(nullptr, nullptr, m, nb < 1 ? 1 : nb, 1 + m->cfg.num_mask_tokens + n_points + (has_box ? 2 : 1), has_mask != 0);
+  return OVM_OK;
+}
+
+// the chunk loop of both predict calls; the arguments were checked by the caller
+static int run_prompts(OvmSam* m, const Prompt& all, int n, int mask_index, uint8_t* masks, float* iou, float* lowres, void* workspace, int64_t workspace_bytes,
+                       hipStream_t s) {
+  const int nt = 1 + m->cfg.num_mask_tokens + all.ns(); const bool hm = all.mask_in != nullptr;
+  // the largest chunk the workspace holds (the carve is linear in the box count up to the 256-byte rounding of each buffer)
+  int nb = n < m->cfg.max_boxes ? n : m->cfg.max_boxes;
+  while (nb > 1 && (int64_t)carve(nullptr, nullptr, m, nb, nt, hm) > workspace_bytes) nb = (nb + 1) / 2;
+  if ((int64_t)carve(nullptr, nullptr, m, nb, nt, hm) > workspace_bytes) { m->err = "workspace too small for one box (ovm_sam_predict_boxes_workspace)"; return OVM_ERR_CAPACITY; }
+  OVM_HIP(m, hipSetDevice(m->device));
+  Work w; carve(&w, (char*)workspace, m, nb, nt, hm);
+  const size_t HW = (size_t)m->H * m->W, LL = (size_t)m->L * m->L, K = all.multimask ? 3 : 1;
+  for (int b0 = 0; b0 < n; b0 += nb) {
+    const int cnt = n - b0 < nb ? n - b0 : nb;
+    Prompt pr = all;
+    if (all.P) { pr.points = all.points + (size_t)b0 * all.P * 2; pr.labels = all.labels + (size_t)b0 * all.P; }
+    if (all.boxes) pr.boxes = all.boxes + (size_t)b0 * 4;
+    if (all.mask_in) pr.mask_in = all.mask_in + (size_t)b0 * LL;
+    const int r = decode_chunk(m, pr, cnt, mask_index, masks + (size_t)b0 * HW, iou ? iou + (size_t)b0 * K : nullptr,
+                               lowres ? lowres + (size_t)b0 * K * LL : nullptr, w, s);
+    if (r) return r;
+  }
   return OVM_OK;
 }
 
@@ -692,21 +936,33 @@ int ovm_sam_predict_boxes(OvmSam* m, const float* boxes, int32_t n, int32_t mask
   if (n == 0) return OVM_OK;
   if (!boxes || !masks || !workspace) { m->err = "null boxes, masks or workspace"; return OVM_ERR_INVALID; }
   if ((uintptr_t)workspace & 255) { m->err = "the workspace must be 256-byte aligned"; return OVM_ERR_INVALID; }
-  // the largest chunk the workspace holds (the carve is linear in the box count up to the 256-byte rounding of each buffer)
-  int nb = n < m->cfg.max_boxes ? n : m->cfg.max_boxes;
-  while (nb > 1 && (int64_t)carve(nullptr, nullptr, m, nb) > workspace_bytes) nb = (nb + 1) / 2;
-  if ((int64_t)carve(nullptr, nullptr, m, nb) > workspace_bytes) { m->err = "workspace too small for one box (ovm_sam_predict_boxes_workspace)"; return OVM_ERR_CAPACITY; }
-  OVM_HIP(m, hipSetDevice(m->device));
-  hipStream_t s = (hipStream_t)stream;
-  Work w; carve(&w, (char*)workspace, m, nb);
-  const size_t HW = (size_t)m->H * m->W, LL = (size_t)m->L * m->L;
-  for (int b0 = 0; b0 < n; b0 += nb) {
-    const int cnt = n - b0 < nb ? n - b0 : nb;
-    const int r = decode_chunk(m, boxes + (size_t)b0 * 4, cnt, mask_index, masks + (size_t)b0 * HW, iou ? iou + (size_t)b0 * 3 : nullptr,
-                               lowres ? lowres + (size_t)b0 * 3 * LL : nullptr, w, s);
-    if (r) return r;
-  }
-  return OVM_OK;
+  Prompt pr; pr.boxes = boxes;
+  return run_prompts(m, pr, n, mask_index, masks, iou, lowres, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int ovm_sam_predict(OvmSam* m, const float* points_xy, const int32_t* labels, int32_t n_points, const float* boxes, const float* mask_inputs, int32_t n,
+                    int32_t multimask, int32_t mask_index, uint8_t* masks, float* iou, float* lowres, void* workspace, int64_t workspace_bytes,
+                    ovm_stream_t stream) {
+  if (!m) return OVM_ERR_INVALID;
+  m->err.clear();
+  if (!m->tower.fam) { m->err = "handle was not created"; return OVM_ERR_INVALID; }
+  if (!m->has_image) { m->err = "ovm_sam_set_image has not been called"; return OVM_ERR_INVALID; }
+  if (n_points < 0 || n_points > kMaxPoints) { m->err = "at most 8 points per prompt"; return OVM_ERR_SHAPE; }
+  if (n_points == 0 && !boxes) { m->err = "a prompt needs points or a box"; return OVM_ERR_INVALID; }
+  if (n < 0 || mask_index < 0 || mask_index > (multimask ? 2 : 0)) { m->err = "invalid arguments (n >= 0, mask_index 0..2, 0 without multimask)"; return OVM_ERR_INVALID; }
+  if (n == 0) return OVM_OK;
+  if ((n_points > 0 && (!points_xy || !labels)) || !masks || !workspace) { m->err = "null points, labels, masks or workspace"; return OVM_ERR_INVALID; }
+  if ((uintptr_t)workspace & 255) { m->err = "the workspace must be 256-byte aligned"; return OVM_ERR_INVALID; }
+  Prompt pr; pr.points = n_points ? points_xy : nullptr; pr.labels = n_points ? labels : nullptr; pr.P = n_points; pr.boxes = boxes; pr.mask_in = mask_inputs;
+  pr.multimask = multimask != 0;
+  return run_prompts(m, pr, n, mask_index, masks, iou, lowres, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int ovm_sam_mask_boxes(const uint8_t* masks, int32_t n, int32_t H, int32_t W, float* boxes_out, int32_t* counts_out, ovm_stream_t stream) {
+  if (n < 0 || H < 1 || W < 1) return OVM_ERR_INVALID;
+  if (n == 0) return OVM_OK;
+  if (!masks || !boxes_out || !counts_out || ((uintptr_t)boxes_out & 15)) return OVM_ERR_INVALID;
+  return launch_mask_boxes(masks, n, H, W, boxes_out, counts_out, (hipStream_t)stream);
 }
 
 int64_t ovm_sam_debug_copy(OvmSam* m, const char* name, float* dst, int64_t capacity, ovm_stream_t stream) {
@@ -724,8 +980,14 @@ int64_t ovm_sam_debug_copy(OvmSam* m, const char* name, float* dst, int64_t capa
   }
   if (n == "neck") { src = m->emb; cnt = (int64_t)G2 * C; }
   else if (n == "dense_pe") { src = m->pe; cnt = (int64_t)G2 * C; }
-  else if (n == "sparse") { src = m->dbg_sparse; cnt = (int64_t)m->dbg_n * 2 * C; }
-  else if (n == "tokens_out") { src = m->dbg_tokens; cnt = (int64_t)m->dbg_n * m->nt * C; }
+  else if (n == "sparse") { src = m->dbg_sparse; cnt = (int64_t)m->dbg_n * m->dbg_ns * C; }
+  else if (n == "tokens_out") { src = m->dbg_tokens; cnt = (int64_t)m->dbg_n * m->dbg_nt * C; }
+  else if (n == "dense") {
+    cnt = (int64_t)G2 * C;
+    if (cnt > capacity) return OVM_ERR_CAPACITY;
+    if (m->dbg_dense_mask) src = m->dbg_dense;
+    else return bcast(m->no_mask, dst, cnt, C, s) ? OVM_ERR_HIP : cnt;
+  }
   else return OVM_ERR_INVALID;
   if (cnt > capacity) return OVM_ERR_CAPACITY;
   if (cnt && hipMemcpyAsync(dst, src, (size_t)cnt * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return OVM_ERR_HIP;
@@ -754,7 +1016,32 @@ int ovm_op_sam_i2t_attn(const float* q, int32_t ldq, const float* k, const float
                         float scale, float* o, int32_t ldo, ovm_stream_t stream) {
   if (!q || !k || !v || !o || nb < 1) return OVM_ERR_INVALID;
   if ((((uintptr_t)q) | ((uintptr_t)o)) & 15) return OVM_ERR_INVALID;
-  return launch_i2t_attn(q, ldq, k, v, ld, nt, heads, G2, nb, scale, o, ldo, (hipStream_t)stream);
+  return launch_i2t_attn<kMaxTok>(q, ldq, k, v, ld, nt, heads, G2, nb, scale, o, ldo, (hipStream_t)stream);
+}
+
+int ovm_op_sam_i2t_attn16(const float* q, int32_t ldq, const float* k, const float* v, int32_t ld, int32_t nt, int32_t heads, int32_t G2, int32_t nb,
+                          float scale, float* o, int32_t ldo, ovm_stream_t stream) {
+  if (!q || !k || !v || !o || nb < 1) return OVM_ERR_INVALID;
+  if ((((uintptr_t)q) | ((uintptr_t)o)) & 15) return OVM_ERR_INVALID;
+  return launch_i2t_attn<kMaxTok16>(q, ldq, k, v, ld, nt, heads, G2, nb, scale, o, ldo, (hipStream_t)stream);
+}
+
+int ovm_op_sam_point_tokens(const float* points, const int32_t* labels, const float* boxes, int32_t nb, int32_t P, int32_t nout, int32_t C,
+                            const float* out_tokens, const float* gauss, const float* point_emb, const float* not_a_point, const float* corner, int32_t H,
+                            int32_t W, int32_t newh, int32_t neww, int32_t S, float* tok, float* sparse, ovm_stream_t stream) {
+  if (!out_tokens || !gauss || !point_emb || !not_a_point || !corner || !tok || !sparse || nb < 1 || nout < 0 || H < 1 || W < 1 || newh < 1 || neww < 1 || S < 1)
+    return OVM_ERR_INVALID;
+  if (P < 0 || (P > 0 && (!points || !labels)) || (P == 0 && !boxes)) return OVM_ERR_INVALID;
+  if (C < 2 || C % 2 != 0 || P > kMaxPoints) return OVM_ERR_SHAPE;
+  return launch_point_tokens(points, labels, boxes, nb, P, nout, C, out_tokens, gauss, point_emb, not_a_point, corner, H, W, newh, neww, S, tok, sparse,
+                             (hipStream_t)stream);
+}
+
+int ovm_op_sam_mask_embed(const float* mask, int32_t n, int32_t G, int32_t C, const float* w0, const float* b0, const float* g1_, const float* be1,
+                          const float* w3, const float* b3, const float* g4, const float* be4, const float* w6, const float* b6, float* out,
+                          ovm_stream_t stream) {
+  if (!mask || !w0 || !b0 || !g1_ || !be1 || !w3 || !b3 || !g4 || !be4 || !w6 || !b6 || !out || n < 1 || G < 1) return OVM_ERR_INVALID;
+  return launch_mask_embed(mask, n, G, C, w0, b0, g1_, be1, w3, b3, g4, be4, w6, b6, out, (hipStream_t)stream);
 }
 
 int ovm_op_sam_mask_prod(const float* up, const float* hyper, int32_t ld_hyper, int32_t t0, int32_t ntk, int32_t C8, int32_t G, int32_t nb, float* out,
@@ -781,7 +1068,7 @@ int ovm_op_sam_unpatch(const uint16_t* hi, const uint16_t* lo, int32_t ld, int32
 int ovm_op_sam_iou_slice(const float* head, int32_t ldh, int32_t n, float* iou, ovm_stream_t stream) {
   if (!head || !iou || n < 1) return OVM_ERR_INVALID;
   if (ldh < 4) return OVM_ERR_SHAPE;
-  return launch_iou_slice(head, ldh, n, iou, (hipStream_t)stream);
+  return launch_iou_slice(head, ldh, n, 1, 3, iou, (hipStream_t)stream);
 }
 
 int ovm_op_sam_add_bcast(const float* a, const float* b, float* out, int64_t n, int64_t bmod, ovm_stream_t stream) {

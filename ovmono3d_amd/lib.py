@@ -337,11 +337,11 @@ EXPORTS = [
     "ovm_geo_default_params", "ovm_geo_last_error", "ovm_geo_lift_workspace", "ovm_geo_lift", "ovm_geo_dbscan_workspace", "ovm_geo_dbscan",
     "ovm_host_geo_box",
     "ovm_sam_create", "ovm_sam_destroy", "ovm_sam_last_error", "ovm_sam_set_image", "ovm_sam_predict_boxes_workspace", "ovm_sam_predict_boxes",
-    "ovm_sam_debug_copy",
+    "ovm_sam_debug_copy", "ovm_sam_predict_workspace", "ovm_sam_predict", "ovm_sam_mask_boxes",
     "ovm_depthpro_create", "ovm_depthpro_destroy", "ovm_depthpro_last_error", "ovm_depthpro_workspace", "ovm_depthpro_infer",
     "ovm_depthpro_debug_copy", "ovm_host_depthpro_check", "ovm_depthpro_profile_enable", "ovm_depthpro_stage_ms",
     "ovm_op_sam_dense_pe", "ovm_op_sam_box_tokens", "ovm_op_sam_ln_gelu", "ovm_op_sam_i2t_attn", "ovm_op_sam_mask_prod", "ovm_op_sam_mask_out",
-    "ovm_op_sam_unpatch", "ovm_op_sam_iou_slice", "ovm_op_sam_add_bcast",
+    "ovm_op_sam_unpatch", "ovm_op_sam_iou_slice", "ovm_op_sam_add_bcast", "ovm_op_sam_i2t_attn16", "ovm_op_sam_point_tokens", "ovm_op_sam_mask_embed",
     "ovm_op_dp_pyramid", "ovm_op_dp_merge", "ovm_op_dp_unsplit", "ovm_op_dp_conv_s2", "ovm_op_dp_dot", "ovm_op_dp_head_tail",
     "ovm_op_dp_clear_borders", "ovm_op_dp_depth_out",
 ]
@@ -469,6 +469,9 @@ def load() -> C.CDLL:
     lib.ovm_sam_predict_boxes.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, i64, vp]
     lib.ovm_sam_debug_copy.argtypes = [vp, C.c_char_p, vp, i64, vp]
     lib.ovm_sam_debug_copy.restype = i64
+    lib.ovm_sam_predict_workspace.argtypes = [vp, i32, i32, i32, i32, C.POINTER(i64)]
+    lib.ovm_sam_predict.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, i64, vp]
+    lib.ovm_sam_mask_boxes.argtypes = [vp, i32, i32, i32, vp, vp, vp]
     lib.ovm_depthpro_create.argtypes = [C.POINTER(OvmDepthProConfig), C.POINTER(OvmTensor), i32, i32, C.POINTER(vp)]
     lib.ovm_depthpro_destroy.argtypes = [vp]
     lib.ovm_depthpro_last_error.argtypes = [vp]
@@ -489,6 +492,9 @@ def load() -> C.CDLL:
     lib.ovm_op_sam_unpatch.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     lib.ovm_op_sam_iou_slice.argtypes = [vp, i32, i32, vp, vp]
     lib.ovm_op_sam_add_bcast.argtypes = [vp, vp, vp, i64, i64, vp]
+    lib.ovm_op_sam_i2t_attn16.argtypes = lib.ovm_op_sam_i2t_attn.argtypes
+    lib.ovm_op_sam_point_tokens.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
+    lib.ovm_op_sam_mask_embed.argtypes = [vp, i32, i32, i32] + [vp] * 12
     lib.ovm_op_dp_pyramid.argtypes = [vp, i32, i32, i64, i64, i64, i32, i32, vp, vp, vp, vp]
     lib.ovm_op_dp_merge.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]
     lib.ovm_op_dp_unsplit.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]

@@ -1,8 +1,10 @@
-"""Segment Anything with box prompts on the device: the mask source of OVMono3D-GEO (reference tools/ovmono3d_geo.py:213-217,
-270-272,308-309 - segment_anything's ``SamPredictor.set_image`` then ``predict(box=...)``, plane ``[2]`` of the multimask outputs).
+"""Segment Anything on the device: the mask source of OVMono3D-GEO (reference tools/ovmono3d_geo.py:213-217,270-272,308-309 -
+segment_anything's ``SamPredictor.set_image`` then ``predict(box=...)``, plane ``[2]`` of the multimask outputs) and the rest of the
+predictor's prompt surface: clicks (foreground, background, padding), a box with clicks, a previous low-resolution mask fed back
+as ``mask_input``, and the single-mask output.
 
 ``build_sam(arch, checkpoint)`` loads a segment_anything checkpoint by its own key names into libovm3d's ``OvmSam`` handle
-(csrc/sam.hip): image encoder (the OVM_TOWER_SAM blocks + neck), prompt encoder for boxes, two-way-transformer mask decoder and
+(csrc/sam.hip): image encoder (the OVM_TOWER_SAM blocks + neck), prompt encoder, two-way-transformer mask decoder and
 ``postprocess_masks`` all run there; masks come back as device uint8 planes that ``ovmono3d_amd.geo.lift_boxes`` takes as they
 are. There is no CPU or PyTorch path.
 
@@ -24,6 +26,48 @@ from ..util.synth_weights import SAM_ARCH
 VIT_H = (1280, 32, 16, 16, 64, 14, (7, 15, 23, 31))
 PIXEL_MEAN = (123.675, 116.28, 103.53)
 PIXEL_STD = (58.395, 57.12, 57.375)
+MAX_POINTS = 8                       # points per prompt (csrc/sam.hip: 5 + 8 + 2 = 15 of the 16 tokens its second attention kernel holds)
+
+
+def check_prompts(point_coords=None, point_labels=None, boxes=None, mask_inputs=None, low_side: Optional[int] = None):
+    """The argument rules of ``predict`` / ``predict_prompts``, on the host and before any device call. Returns
+    ``(n, P, coords float32 [n, P, 2] | None, labels int32 [n, P] | None, boxes float32 [n, 4] | None)``; ``mask_inputs`` is only
+    checked for its shape ([n, L, L], L = ``low_side`` when given). ValueError for: no prompt at all, coordinates without labels (or
+    the reverse), more than MAX_POINTS points, a label outside {1, 0, -1}, counts that differ between the arguments."""
+    def host(x, dtype):
+        if isinstance(x, torch.Tensor):
+            x = x.detach().cpu().numpy()
+        return np.asarray(x, dtype)
+
+    if (point_coords is None) != (point_labels is None):
+        raise ValueError("point_coords and point_labels come together")
+    coords = labels = bx = None
+    n = None
+    if point_coords is not None:
+        coords, lab = host(point_coords, np.float32), host(point_labels, np.float64)
+        if coords.ndim != 3 or coords.shape[-1] != 2 or lab.shape != coords.shape[:2]:
+            raise ValueError(f"point_coords must be [n, P, 2] and point_labels [n, P], are {coords.shape} and {lab.shape}")
+        if coords.shape[1] > MAX_POINTS:
+            raise ValueError(f"at most {MAX_POINTS} points per prompt, got {coords.shape[1]}")
+        bad = sorted(set(np.unique(lab).tolist()) - {1.0, 0.0, -1.0})
+        if bad:
+            raise ValueError(f"point labels must be 1 (foreground), 0 (background) or -1 (padding), got {bad}")
+        labels = lab.astype(np.int32)
+        n = coords.shape[0]
+        if coords.shape[1] == 0:
+            coords = labels = None
+    if boxes is not None:
+        bx = host(boxes, np.float32).reshape(-1, 4)
+        if n is not None and bx.shape[0] != n:
+            raise ValueError(f"{bx.shape[0]} boxes for {n} point prompts")
+        n = bx.shape[0]
+    if coords is None and bx is None:
+        raise ValueError("a prompt needs points or a box")
+    if mask_inputs is not None:
+        shp = tuple(mask_inputs.shape)
+        if len(shp) != 3 or shp[0] != n or shp[1] != shp[2] or (low_side is not None and shp[1] != low_side):
+            raise ValueError(f"mask_inputs must be [{n}, L, L] with L = {low_side if low_side is not None else '4 x grid'}, is {shp}")
+    return n, (0 if coords is None else coords.shape[1]), coords, labels, bx
 
 
 def sam_config(arch: str, image_size: Optional[int] = None, precision: int = 3, max_boxes: int = 16) -> "_lib.OvmSamConfig":
@@ -112,6 +156,42 @@ class SamEngine:
                                                    ws.data_ptr(), ws.numel(), self._stream()), "ovm_sam_predict_boxes")
         return masks, iou, low
 
+    def prompt_workspace(self, n: int, n_points: int, has_box: bool, has_mask: bool) -> torch.Tensor:
+        nbytes = C.c_int64()
+        self._chk(self.L.ovm_sam_predict_workspace(self._h, int(n), int(n_points), int(has_box), int(has_mask), C.byref(nbytes)),
+                  "ovm_sam_predict_workspace")
+        if self._ws is None or self._ws.numel() < nbytes.value:
+            self._ws = None
+            self._ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.dev)
+        return self._ws
+
+    def predict_prompts(self, coords: Optional[torch.Tensor], labels: Optional[torch.Tensor], boxes: Optional[torch.Tensor],
+                        mask_inputs: Optional[torch.Tensor], H: int, W: int, multimask: bool = True, mask_index: int = 2, want_iou: bool = False,
+                        want_lowres: bool = False, workspace: Optional[torch.Tensor] = None):
+        """ovm_sam_predict on device tensors already checked (``check_prompts``): coords fp32 [n, P, 2], labels int32 [n, P], boxes
+        fp32 [n, 4], mask_inputs fp32 [n, L, L]; any of them None. (masks uint8 [n, H, W], iou [n, K] | None, lowres [n, K, L, L] | None)."""
+        n = int(coords.shape[0] if coords is not None else boxes.shape[0])
+        P = int(coords.shape[1]) if coords is not None else 0
+        K, Ls = (3 if multimask else 1), 4 * self.grid
+        masks = torch.empty((n, H, W), dtype=torch.uint8, device=self.dev)
+        iou = torch.empty((n, K), dtype=torch.float32, device=self.dev) if want_iou else None
+        low = torch.empty((n, K, Ls, Ls), dtype=torch.float32, device=self.dev) if want_lowres else None
+        if n:
+            ws = workspace if workspace is not None else self.prompt_workspace(n, P, boxes is not None, mask_inputs is not None)
+            ptr = lambda t: t.data_ptr() if t is not None else None                                     # noqa: E731
+            self._chk(self.L.ovm_sam_predict(self._h, ptr(coords), ptr(labels), P, ptr(boxes), ptr(mask_inputs), n, int(bool(multimask)), int(mask_index),
+                                             masks.data_ptr(), ptr(iou), ptr(low), ws.data_ptr(), ws.numel(), self._stream()), "ovm_sam_predict")
+        return masks, iou, low
+
+    def mask_boxes(self, masks: torch.Tensor):
+        """masks: device uint8 [n, H, W]. (boxes fp32 [n, 4] = (xmin, ymin, xmax + 1, ymax + 1), pixel counts int32 [n]); zeros for an empty mask."""
+        n, H, W = (int(v) for v in masks.shape)
+        boxes = torch.empty((n, 4), dtype=torch.float32, device=self.dev)
+        counts = torch.empty((n,), dtype=torch.int32, device=self.dev)
+        if n:
+            self._chk(self.L.ovm_sam_mask_boxes(masks.data_ptr(), n, H, W, boxes.data_ptr(), counts.data_ptr(), self._stream()), "ovm_sam_mask_boxes")
+        return boxes, counts
+
     def debug(self, name: str, shape) -> torch.Tensor:
         out = torch.empty(shape, dtype=torch.float32, device=self.dev)
         n = self.L.ovm_sam_debug_copy(self._h, name.encode(), out.data_ptr(), out.numel(), self._stream())
@@ -122,7 +202,7 @@ class SamEngine:
 
 
 class SamPredictor:
-    """segment_anything's ``SamPredictor`` for box prompts."""
+    """segment_anything's ``SamPredictor``: box, point and mask prompts, multimask or single-mask output."""
 
     def __init__(self, engine: SamEngine):
         self.engine = engine
@@ -152,18 +232,62 @@ class SamPredictor:
         b = self._boxes(boxes)
         return self.engine.predict_boxes(b, *self.original_size, mask_index, workspace=workspace)[0]
 
-    def predict(self, box=None, multimask_output: bool = True):
-        """The reference's call shape: one xyxy box -> (masks [3, H, W] bool, iou [3], low_res [3, 4G, 4G]), device tensors."""
-        if box is None or not multimask_output:
-            raise NotImplementedError("box prompts with multimask_output=True only")
-        b = self._boxes(box)
-        if b.shape[0] != 1:
-            raise ValueError("predict takes one box; use predict_boxes for several")
-        H, W = self.original_size
+    def predict_prompts(self, point_coords=None, point_labels=None, boxes=None, mask_inputs=None, multimask_output: bool = True,
+                        mask_index: int = 2, want_iou: bool = False, want_lowres: bool = False, workspace: Optional[torch.Tensor] = None):
+        """n prompts of one shape in one call: point_coords [n, P, 2] (original pixels, P <= 8) with point_labels [n, P] (1 foreground,
+        0 background, -1 padding), boxes [n, 4] xyxy, mask_inputs [n, L, L] (low-resolution logits of an earlier call, L = 4 x grid);
+        at least points or boxes. (masks uint8 [n, H, W]: plane ``mask_index`` of the three multimask outputs, or the single mask with
+        ``multimask_output=False`` (mask_index 0); iou [n, K] | None; low-res logits [n, K, L, L] | None), K = 3 or 1. Device tensors."""
+        if self.original_size is None:
+            raise RuntimeError("An image must be set with .set_image(...) before mask prediction.")
+        if not multimask_output:
+            mask_index = 0
+        if not 0 <= int(mask_index) <= 2:
+            raise ValueError(f"mask_index must be 0, 1 or 2, is {mask_index}")
+        eng = self.engine
+        _, _, coords, labels, bx = check_prompts(point_coords, point_labels, boxes, mask_inputs, 4 * eng.grid)
+        up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(eng.dev)      # noqa: E731
+        mi = None
+        if mask_inputs is not None:
+            mi = torch.as_tensor(mask_inputs).to(eng.dev, torch.float32).contiguous()
+        return eng.predict_prompts(up(coords), up(labels), up(bx), mi, *self.original_size, multimask=multimask_output, mask_index=int(mask_index),
+                                   want_iou=want_iou, want_lowres=want_lowres, workspace=workspace)
+
+    def mask_boxes(self, masks: torch.Tensor):
+        """The tight xyxy box (xmin, ymin, xmax + 1, ymax + 1) and the pixel count of each uint8 / bool mask plane [n, H, W], on the device."""
+        m = masks.to(torch.uint8) if masks.dtype != torch.uint8 else masks
+        return self.engine.mask_boxes(m.contiguous())
+
+    def predict(self, point_coords=None, point_labels=None, box=None, mask_input=None, multimask_output: bool = True, return_logits: bool = False):
+        """segment_anything's call for one prompt: point_coords [P, 2] with point_labels [P], box [4] xyxy, mask_input [1, L, L] ->
+        (masks [C, H, W] bool, iou [C], low_res [C, L, L]), C = 3 or 1, device tensors. The reference's call shape is ``predict(box=b)``."""
+        if return_logits:
+            raise NotImplementedError("return_logits: the masks are thresholded on the device")
+        if point_coords is None and point_labels is None and box is None:
+            raise ValueError("a prompt needs points or a box")
+        if point_coords is None and mask_input is None and multimask_output:                  # the reference's call, as it always ran
+            b = self._boxes(box)
+            if b.shape[0] != 1:
+                raise ValueError("predict takes one box; use predict_boxes for several")
+            H, W = self.original_size
+            planes = []
+            iou = low = None
+            for k in range(3):
+                m, i, l = self.engine.predict_boxes(b, H, W, k, want_iou=k == 0, want_lowres=k == 0)
+                planes.append(m[0])
+                if k == 0:
+                    iou, low = i[0], l[0]
+            return torch.stack(planes).bool(), iou, low
+        as_np = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)      # noqa: E731
+        pc = None if point_coords is None else as_np(point_coords).reshape(1, -1, 2)
+        pl = None if point_labels is None else as_np(point_labels).reshape(1, -1)
+        bx = None if box is None else as_np(box).reshape(-1, 4)
+        if bx is not None and bx.shape[0] != 1:
+            raise ValueError("predict takes one box; use predict_prompts for several")
         planes = []
         iou = low = None
-        for k in range(3):
-            m, i, l = self.engine.predict_boxes(b, H, W, k, want_iou=k == 0, want_lowres=k == 0)
+        for k in range(3 if multimask_output else 1):
+            m, i, l = self.predict_prompts(pc, pl, bx, mask_input, multimask_output, k, want_iou=k == 0, want_lowres=k == 0)
             planes.append(m[0])
             if k == 0:
                 iou, low = i[0], l[0]
@@ -172,8 +296,7 @@ class SamPredictor:
 
 def build_sam(arch: str, checkpoint: Union[str, Dict[str, torch.Tensor], None], device: Optional[torch.device] = None,
               image_size: Optional[int] = None, precision: int = 3, max_boxes: int = 16) -> SamPredictor:
-    """checkpoint: a segment_anything ``.pth`` (or its state dict). The prompt encoder's mask-input convolutions are loaded by the
-    checkpoint reader like every other tensor and not used (box prompts only)."""
+    """checkpoint: a segment_anything ``.pth`` (or its state dict)."""
     cfg = sam_config(arch, image_size, precision, max_boxes)
     if isinstance(checkpoint, str):
         checkpoint = torch.load(checkpoint, map_location="cpu")

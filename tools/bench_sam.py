@@ -4,6 +4,11 @@ synthetic weights, per stage: set_image (resize, encoder, neck) and predict_boxe
 heads, postprocess_masks to uint8 planes at the image's own resolution).
 
     python tools/bench_sam.py [--arch vit_b] [--boxes 20] [--runs 7] [--warmup 2] [--precision 3] [--yardstick]
+                              [--prompts box|points|box+mask] [--points 1]
+
+``--prompts points`` also times ovm_sam_predict with ``--points`` clicks per prompt (the box centres first, labels 1, no box: one padding
+token); ``--prompts box+mask`` the refinement pass (the same boxes with the box pass's plane-2 logits as mask input). Both beside the box
+run, same image, same prompt count, inputs resident.
 
 Device times are HIP event times around the calls alone (inputs resident, no read inside), warm, median of the runs. With
 ``--yardstick`` the same network - Hugging Face SamModel (tests/sam_oracle.py) with the same weights, fp32, eager torch on the same
@@ -59,6 +64,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--precision", type=int, default=3, choices=(1, 3))
     ap.add_argument("--max-boxes", type=int, default=32)
+    ap.add_argument("--prompts", choices=("box", "points", "box+mask"), default="box", help="a second prompt kind to time beside the boxes")
+    ap.add_argument("--points", type=int, default=1, help="--prompts points: clicks per prompt (1..8)")
     ap.add_argument("--yardstick", action="store_true", help="also time Hugging Face SamModel, fp32, eager torch on this card")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "the SAM predictor needs the GPU"
@@ -77,6 +84,21 @@ def main():
     out["predict_per_box_ms"] = round(out["predict_boxes_ms"] / a.boxes, 4)
     masks = pred.predict_boxes(bt, 2, workspace=ws)
     out["mask_fill"] = round(float(masks.float().mean()), 4)
+    eng = pred.engine
+    if a.prompts == "points":
+        g = np.random.RandomState(1)
+        pts = np.concatenate([(boxes[:, None, :2] + boxes[:, None, 2:]) / 2, g.uniform(0, 1, (a.boxes, a.points - 1, 2)) * np.array([W, H])], 1)
+        pt, lt = torch.from_numpy(pts.astype(np.float32)).to(dev), torch.ones((a.boxes, a.points), dtype=torch.int32, device=dev)
+        ws2 = eng.prompt_workspace(a.boxes, a.points, False, False)
+        out["points_per_prompt"] = a.points
+        out["predict_points_ms"] = round(event_ms(lambda: eng.predict_prompts(pt, lt, None, None, H, W, mask_index=2, workspace=ws2), a.runs, a.warmup), 3)
+        out["predict_per_point_prompt_ms"] = round(out["predict_points_ms"] / a.boxes, 4)
+    elif a.prompts == "box+mask":
+        low = eng.predict_boxes(bt, H, W, 2, want_lowres=True)[2]
+        mi = low[:, 2].contiguous()
+        ws2 = eng.prompt_workspace(a.boxes, 0, True, True)
+        out["predict_box_mask_ms"] = round(event_ms(lambda: eng.predict_prompts(None, None, bt, mi, H, W, mask_index=2, workspace=ws2), a.runs, a.warmup), 3)
+        out["predict_per_box_mask_prompt_ms"] = round(out["predict_box_mask_ms"] / a.boxes, 4)
     if a.yardstick:
         import torch.nn.functional as F
         model = so.build_model(a.arch, sd, 1024, torch.float32).to(dev)

@@ -14,7 +14,9 @@ Masks, one of:
                    or above the score threshold; the planes go straight to the lifting without leaving the device. Images are read
                    from ``<image-root>/<file_path>`` by the device JPEG decoder (the host reader for files outside its scope) in
                    cv2.imread's BGR order and handed over as the reference does (``set_image(im, image_format="BGR")``). vit_b
-                   and vit_l checkpoints; vit_h (head dimension 80) is refused by the library.
+                   and vit_l checkpoints; vit_h (head dimension 80) is refused by the library. ``--sam-refine N`` adds
+                   segment_anything's refinement pass N times: the same box again with the previous pass's low-resolution logits
+                   of plane [2] as ``mask_input``.
   ``--mask-dir``   masks some other program wrote: ``<mask-dir>/<image_id>.npz`` with ``masks`` uint8 [n, H, W] (nonzero = inside)
                    and ``index`` int [n], the positions of the masked instances in the image's instance list. ``--dump-masks DIR``
                    writes exactly these files from a ``--mask sam`` run.
@@ -80,11 +82,24 @@ def read_bgr(image_root, file_path, height, width, dev):
     return bgr
 
 
-def sam_masks(predictor, image_root, file_path, height, width, boxes_xyxy, bgr=None):
-    """Device uint8 [n, H, W]: SAM's plane [2] for every box of one image (one set_image, one predict_boxes)."""
+def refined_masks(predictor, refine, mask_index=2, **prompts):
+    """Device uint8 [n, H, W]: plane ``mask_index`` of ``predict_prompts(**prompts)``, then ``refine`` more passes of the same prompts
+    with the previous pass's low-resolution logits of that plane as ``mask_inputs``."""
+    masks, _, low = predictor.predict_prompts(mask_index=mask_index, want_lowres=refine > 0, **prompts)
+    for k in range(refine):
+        masks, _, low = predictor.predict_prompts(mask_inputs=low[:, mask_index].contiguous(), mask_index=mask_index, want_lowres=k + 1 < refine,
+                                                  **prompts)
+    return masks
+
+
+def sam_masks(predictor, image_root, file_path, height, width, boxes_xyxy, bgr=None, refine=0):
+    """Device uint8 [n, H, W]: SAM's plane [2] for every box of one image (one set_image, one predict_boxes; ``refine`` > 0: that many
+    refinement passes behind it, ``refined_masks``)."""
     if bgr is None:
         bgr = read_bgr(image_root, file_path, height, width, predictor.engine.dev)
     predictor.set_image(bgr, image_format="BGR")   # the reference's call (run_seg_anything): a cv2 BGR array, declared as such
+    if refine > 0 and len(boxes_xyxy):
+        return refined_masks(predictor, refine, boxes=boxes_xyxy)
     return predictor.predict_boxes(boxes_xyxy, mask_index=2)
 
 
@@ -155,7 +170,7 @@ def run(args):
             planes = None
             if use_sam:
                 boxes = np.asarray([xywh_to_xyxy(ins["bbox"]) for _, ins in cand], np.float64)
-                planes = list(sam_masks(predictor, args.image_root, im["file_path"], H, W, boxes, bgr=bgr))
+                planes = list(sam_masks(predictor, args.image_root, im["file_path"], H, W, boxes, bgr=bgr, refine=args.sam_refine))
             elif not use_box:
                 have = load_masks(args.mask_dir, rec["image_id"], H, W)
                 missing = [pos for pos, _ in cand if pos not in have]
@@ -216,6 +231,8 @@ def argument_parser():
     ap.add_argument("--sam-weights", default=None, help="segment_anything checkpoint (.pth: image_encoder.*, prompt_encoder.*, mask_decoder.*)")
     ap.add_argument("--sam-arch", default="vit_l", help="vit_b or vit_l (vit_h has head dimension 80: refused)")
     ap.add_argument("--sam-image-size", type=int, default=None, help=argparse.SUPPRESS)      # tests: a small encoder input
+    ap.add_argument("--sam-refine", type=int, default=0, metavar="N",
+                    help="--mask sam: N more passes per box with the previous pass's low-resolution logits as mask_input (default 0: the reference's single pass)")
     ap.add_argument("--image-root", default=None, help="directory the dataset's file_path entries are relative to (--mask sam)")
     ap.add_argument("--dump-masks", default=None, metavar="DIR", help="write the masks used as <DIR>/<image_id>.npz, the files --mask-dir reads")
     ap.add_argument("--score-threshold", type=float, default=0.30)
@@ -227,6 +244,11 @@ def check_args(args, parser=None):
     """What argparse's ``required`` cannot say: --depth-dir is required unless Depth Pro supplies the depth."""
     if args.depth == "files" and not args.depth_dir:
         msg = "the following arguments are required: --depth-dir (or --depth depthpro)"
+        if parser is not None:
+            parser.error(msg)
+        raise SystemExit(msg)
+    if getattr(args, "sam_refine", 0) < 0 or (getattr(args, "sam_refine", 0) > 0 and args.mask != "sam"):
+        msg = "--sam-refine N needs N >= 0 and --mask sam"
         if parser is not None:
             parser.error(msg)
         raise SystemExit(msg)
