@@ -149,8 +149,9 @@ int ovm_create(const OvmConfig* cfg, const OvmTensor* weights, int32_t n_weights
 int ovm_destroy(OvmHandle* h);
 const char* ovm_last_error(const OvmHandle* h);
 const char* ovm_version(void);
-/* sizeof() of a struct of this header as the library was compiled ("OvmConfig", "OvmTensor", "OvmImage", "OvmDet3D",
- * "OvmGdinoConfig", "OvmJpegInfo", "OvmJpegEncInfo", "OvmJpegDecPlan", "OvmSceneInput", "OvmSceneLayout", "OvmSceneSegment", "OvmPanelBox", "OvmPanelsInput", "OvmPanelPrim", "OvmPanelsLayout", "OvmEvalCell", "OvmSamConfig", "OvmDepthProConfig"), -1 for an unknown name: lets a binding check its mirror of the layout before the first call. */
+/* sizeof() of a struct of this header as the library was compiled: every `typedef struct X { ... } X;` here answers to "X", the
+ * nested ones (OvmSceneBox, OvmChainLin, ...) included; -1 for an unknown name. Lets a binding check its view of the layout before
+ * the first call. */
 int ovm_abi_sizeof(const char* struct_name);
 
 /* --- backbone: build_dino_backbone(...).forward(x, prompt_depth) -> {p2,p3,p4}

@@ -109,37 +109,20 @@ extern "C" {
 
 const char* ovm_version(void) { return "libovm3d 0.2 (gfx950)"; }
 
+// every struct include/ovm3d.h defines, in its order (the host binding asks for each of them by name when it loads the library)
+#define OVM_ABI_STRUCTS(X)                                                                                                         \
+  X(OvmConfig) X(OvmTensor) X(OvmImage) X(OvmDet3D) X(OvmGemmEpiOp) X(OvmGdinoConfig) X(OvmAttnF32Op) X(OvmMsDeformOp) X(OvmRowOp) \
+  X(OvmSwinQkvAttnOp) X(OvmChainLin) X(OvmChainLn) X(OvmDecChainOp) X(OvmEvalCell) X(OvmJpegInfo) X(OvmJpegDecPlan)               \
+  X(OvmJpegEncInfo) X(OvmSceneInput) X(OvmSceneBox) X(OvmSceneView) X(OvmSceneLayout) X(OvmSceneSegment) X(OvmPanelBox)            \
+  X(OvmPanelsInput) X(OvmPanelPrim) X(OvmPanelsLayout) X(OvmGeoParams) X(OvmGeoInstance) X(OvmGeoResult) X(OvmGeoBox)              \
+  X(OvmSamConfig) X(OvmDepthProConfig)
+
 int ovm_abi_sizeof(const char* name) {
   if (!name) return -1;
   const std::string n(name);
-  if (n == "OvmConfig") return (int)sizeof(OvmConfig);
-  if (n == "OvmTensor") return (int)sizeof(OvmTensor);
-  if (n == "OvmImage") return (int)sizeof(OvmImage);
-  if (n == "OvmDet3D") return (int)sizeof(OvmDet3D);
-  if (n == "OvmGdinoConfig") return (int)sizeof(OvmGdinoConfig);
-  if (n == "OvmJpegInfo") return (int)sizeof(OvmJpegInfo);
-  if (n == "OvmJpegEncInfo") return (int)sizeof(OvmJpegEncInfo);
-  if (n == "OvmJpegDecPlan") return (int)sizeof(OvmJpegDecPlan);
-  if (n == "OvmSceneInput") return (int)sizeof(OvmSceneInput);
-  if (n == "OvmSceneLayout") return (int)sizeof(OvmSceneLayout);
-  if (n == "OvmSceneSegment") return (int)sizeof(OvmSceneSegment);
-  if (n == "OvmPanelBox") return (int)sizeof(OvmPanelBox);
-  if (n == "OvmPanelsInput") return (int)sizeof(OvmPanelsInput);
-  if (n == "OvmPanelPrim") return (int)sizeof(OvmPanelPrim);
-  if (n == "OvmPanelsLayout") return (int)sizeof(OvmPanelsLayout);
-  if (n == "OvmEvalCell") return (int)sizeof(OvmEvalCell);
-  if (n == "OvmGeoParams") return (int)sizeof(OvmGeoParams);
-  if (n == "OvmGeoInstance") return (int)sizeof(OvmGeoInstance);
-  if (n == "OvmGeoResult") return (int)sizeof(OvmGeoResult);
-  if (n == "OvmGeoBox") return (int)sizeof(OvmGeoBox);
-  if (n == "OvmSamConfig") return (int)sizeof(OvmSamConfig);
-  if (n == "OvmDepthProConfig") return (int)sizeof(OvmDepthProConfig);
-  if (n == "OvmGemmEpiOp") return (int)sizeof(OvmGemmEpiOp);
-  if (n == "OvmAttnF32Op") return (int)sizeof(OvmAttnF32Op);
-  if (n == "OvmMsDeformOp") return (int)sizeof(OvmMsDeformOp);
-  if (n == "OvmRowOp") return (int)sizeof(OvmRowOp);
-  if (n == "OvmSwinQkvAttnOp") return (int)sizeof(OvmSwinQkvAttnOp);
-  if (n == "OvmDecChainOp") return (int)sizeof(OvmDecChainOp);
+#define OVM_ABI_SIZEOF(T) if (n == #T) return (int)sizeof(T);
+  OVM_ABI_STRUCTS(OVM_ABI_SIZEOF)
+#undef OVM_ABI_SIZEOF
   return -1;
 }
 

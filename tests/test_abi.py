@@ -3,6 +3,8 @@ import ctypes as C
 import os
 import re
 
+import pytest
+
 from common import ROOT
 
 
@@ -42,6 +44,83 @@ def test_struct_layouts_match_header():
         assert L.ovm_abi_sizeof(name.encode()) == C.sizeof(mirror), name
     assert L.ovm_abi_sizeof(b"OvmDecChainOp") == C.sizeof(lib.OvmDecChainOp) == 4 * 6 + 8 * 8 + (8 * 3 + 4 * 2) + 4 * 26 + 32 * 14 + 16 * 4 + (4 * 2 + 8 * 2)
     assert L.ovm_abi_sizeof(b"OvmDet3D") == 192 and L.ovm_abi_sizeof(b"nope") == -1
+
+
+def test_parsed_layouts_match_a_c_compiler(tmp_path):
+    """sizeof and every offsetof / field size of every struct the binding derives from include/ovm3d.h, against what a C compiler
+    makes of the same header."""
+    import shutil
+    import subprocess
+    from ovmono3d_amd import lib
+    assert len(lib.STRUCTS) >= 32
+    prints = []
+    for name, s in lib.STRUCTS.items():
+        prints.append(f'  printf("{name} - %zu 0\\n", sizeof({name}));')
+        prints += [f'  printf("{name} {f} %zu %zu\\n", sizeof((({name}*)0)->{f}), offsetof({name}, {f}));' for f, *_ in s._fields_]
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stdio.h>\n#include "ovm3d.h"\nint main(void) {\n' + "\n".join(prints) + "\n  return 0;\n}\n")
+    cc = next((c for c in ("cc", "gcc", "clang", "/opt/rocm/lib/llvm/bin/clang") if shutil.which(c)), None)
+    assert cc, "no C compiler (cc, gcc, clang, ROCm's clang) to check the layouts with"
+    subprocess.run([cc, "-I", os.path.join(ROOT, "include"), "-o", str(tmp_path / "layout"), str(src)], check=True)
+    compiled = [tuple(line.split()) for line in subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True,
+                                                               text=True).stdout.splitlines()]
+    derived = []
+    for name, s in lib.STRUCTS.items():
+        derived.append((name, "-", str(C.sizeof(s)), "0"))
+        derived += [(name, f, str(getattr(s, f).size), str(getattr(s, f).offset)) for f, *_ in s._fields_]
+    assert len(compiled) > 300 and compiled == derived, [x for x in zip(compiled, derived) if x[0] != x[1]][:5]
+
+
+_GOOD = "#define OVM_N 2\ntypedef struct OvmA { int32_t x[OVM_N]; const float* p; } OvmA;\nint ovm_f(const OvmA* a, int64_t n);\n"
+
+
+def test_parser_takes_a_plain_header():
+    """the control for the strictness cases below: the same kind of text without the offending line is bound"""
+    from ovmono3d_amd import lib
+    abi = lib.parse_header(_GOOD)
+    assert abi.constants == {"OVM_N": 2} and list(abi.structs) == ["OvmA"] and C.sizeof(abi.structs["OvmA"]) == 16
+    assert abi.functions["ovm_f"][0] is C.c_int and abi.functions["ovm_f"][1][1] is C.c_int64
+
+
+@pytest.mark.parametrize("what,bad", [
+    ("unknown type", "typedef struct OvmB { foo_t x; } OvmB;"),
+    ("unknown type behind a pointer", "int ovm_g(const OvmNope* p);"),
+    ("union member", "typedef struct OvmB { union { int32_t i; float f; } u; } OvmB;"),
+    ("union", "typedef union OvmU { int32_t i; float f; } OvmU;"),
+    ("bit-field", "typedef struct OvmB { uint32_t a : 3; uint32_t b : 29; } OvmB;"),
+    ("function-pointer parameter", "int ovm_g(void (*done)(int32_t), int32_t n);"),
+    ("function-pointer field", "typedef struct OvmB { void (*done)(int32_t); } OvmB;"),
+    ("struct used before its definition", "typedef struct OvmB { OvmC c[2]; } OvmB;\ntypedef struct OvmC { int32_t x; } OvmC;"),
+    ("unknown array dimension", "typedef struct OvmB { int32_t x[OVM_M]; } OvmB;"),
+    ("unknown directive", "#define OVM_F 1.5f"),
+    ("unknown return type", "float ovm_g(int32_t n);"),
+    ("declaration without an end", "int ovm_g(int32_t n)"),
+])
+def test_parser_refuses_what_it_does_not_understand(what, bad):
+    from ovmono3d_amd import lib
+    with pytest.raises(lib.HeaderError, match=r"ovm3d\.h:4: "):           # _GOOD has three lines: the error names the fourth
+        lib.parse_header(_GOOD + bad + "\n")
+
+
+def test_struct_pointer_parameters_take_addresses_and_only_their_own_struct():
+    """from_param alone, no library call: the one rule for `T*` parameters, on a parameter the callers hand a device address
+    (OvmDet3D* out of ovm_cube_forward) and on one they hand a host struct (OvmConfig* of ovm_create)."""
+    from ovmono3d_amd import lib
+    out, cfg = lib.FUNCTIONS["ovm_cube_forward"][1][9], lib.FUNCTIONS["ovm_create"][1][0]
+    assert out.struct is lib.OvmDet3D and cfg.struct is lib.OvmConfig
+    for p, right, wrong in ((out, lib.OvmDet3D, lib.OvmEvalCell), (cfg, lib.OvmConfig, lib.OvmSamConfig)):
+        for ok in (None, 0, 0x7F0000001000, C.c_void_p(4096), right(), C.byref(right()), C.pointer(right()), (right * 3)()):
+            p.from_param(ok)
+        for bad in (wrong(), C.byref(wrong()), C.pointer(wrong()), (wrong * 3)(), C.c_int32(1), C.byref(C.c_int32(1)), 1.0, b"x", "x"):
+            with pytest.raises((TypeError, C.ArgumentError)):
+                p.from_param(bad)
+    # the other kinds of parameter and result
+    rt, at = lib.FUNCTIONS["ovm_debug_copy"]            # int64_t (OvmHandle*, const char*, float*, int64_t, ovm_stream_t)
+    assert rt is C.c_int64 and at == [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p]
+    assert lib.FUNCTIONS["ovm_last_error"] == (C.c_char_p, [C.c_void_p]) and lib.FUNCTIONS["ovm_version"] == (C.c_char_p, [])
+    assert lib.FUNCTIONS["ovm_host_jpeg_info"][1][:2] == [C.c_void_p, C.c_size_t]
+    assert lib.FUNCTIONS["ovm_create"][1][1:] == [lib.FUNCTIONS["ovm_sam_create"][1][1], C.c_int32, C.c_int32, C.c_void_p]      # OvmHandle**
+    assert lib.FUNCTIONS["ovm_eval_iou2d"][1][5] is C.c_double and lib.FUNCTIONS["ovm_op_nms"][1][3] is C.c_float
 
 
 def test_version_and_error_strings():

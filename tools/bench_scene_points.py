@@ -44,13 +44,9 @@ front, novel = both[:, :W], both[:, W:]
 Rn = (C.c_double * 9)(*so.euler2mat([np.pi / 3, 0, 0]).reshape(-1).tolist())
 stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
-L = _lib.load()
-T = L
+T = _lib.load()
 if args.lib:
-    T = C.CDLL(os.path.abspath(args.lib))
-    for name in ("ovm_render_scene_workspace", "ovm_render_scene", "ovm_render_scene_points_workspace", "ovm_render_scene_points"):
-        if hasattr(T, name):
-            getattr(T, name).argtypes = getattr(L, name).argtypes
+    T = _lib.bind(C.CDLL(os.path.abspath(args.lib)), partial=True)
 has_points = hasattr(T, "ovm_render_scene_points")
 wsb = C.c_int64()
 _lib.check((T.ovm_render_scene_points_workspace if has_points else T.ovm_render_scene_workspace)(C.byref(lay), glyphs.size, C.byref(wsb)))
