@@ -23,6 +23,12 @@ boxes; a "bbox" joins the clicks as a box prompt) and the mask is lifted. The re
 of its mask; its score the entry's, else 1.0. ``--sam-refine N`` runs N refinement passes behind the first (the same prompt with the
 previous low-resolution logits as ``mask_input``), for boxes and for clicks.
 
+``--everything`` needs neither names nor boxes nor clicks: Segment Anything's automatic mask generator (a ``--points-per-side`` grid of
+clicks, ``--pred-iou-thresh``, ``--stability-score-thresh``, ``--box-nms-thresh``; ``ovmono3d_amd.sam.SamAutomaticMaskGenerator``) proposes
+the masks of the whole image and every one is lifted. The record's 2D box is the tight box of its mask, its score the predicted IoU,
+its category "object"; ``--threshold`` is not applied (the generator has its own thresholds). It needs ``--mask sam`` and is refused
+together with ``--points-file`` or ``--boxes-file``.
+
 The LIFT model is not built: ``MODEL.WEIGHTS`` is not needed, the config supplies the detector's settings and ``OUTPUT_DIR``.
 """
 import argparse
@@ -110,7 +116,7 @@ def do_test(args, cfg):
     if args.points_file:
         with open(args.points_file) as f:
             points_per_img = json.load(f)
-    else:
+    elif not args.everything:                                                # --everything reads neither names nor clicks
         with open(args.labels_file) as f:
             cats_per_img = json.load(f)
     boxes_per_img = None
@@ -118,7 +124,7 @@ def do_test(args, cfg):
         with open(args.boxes_file) as f:
             boxes_per_img = json.load(f)
     detector = resize = None
-    if boxes_per_img is None and points_per_img is None:
+    if boxes_per_img is None and points_per_img is None and not args.everything:
         detector = build_detector(cfg, dev)
         resize = ResizeShortestEdgeGPU(cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST)
     depth_source = None
@@ -128,6 +134,11 @@ def do_test(args, cfg):
     if args.mask == "sam":
         from ovmono3d_amd.sam import build_sam
         predictor = build_sam(args.sam_arch, args.sam_weights, device=dev, image_size=args.sam_image_size)
+    generator = None
+    if args.everything:
+        from ovmono3d_amd.sam import SamAutomaticMaskGenerator
+        generator = SamAutomaticMaskGenerator(predictor, points_per_side=args.points_per_side, pred_iou_thresh=args.pred_iou_thresh,
+                                              stability_score_thresh=args.stability_score_thresh, box_nms_thresh=args.box_nms_thresh)
     params = GeoParams()
     focal_length, principal_point = args.focal_length, args.principal_point
     os.makedirs(cfg.OUTPUT_DIR, exist_ok=True)
@@ -135,6 +146,8 @@ def do_test(args, cfg):
         im_name = os.path.splitext(name)[0]
         entries = points_per_img.get(im_name, []) if points_per_img is not None else None
         cats = cats_per_img.get(im_name, []) if entries is None else [e["category_name"] for e in entries]
+        if generator is not None:
+            cats = ["object"]
         if cats == []:
             continue
         stages, t0 = {}, time.perf_counter()
@@ -154,7 +167,12 @@ def do_test(args, cfg):
         px, py = (w / 2, h / 2) if len(principal_point) == 0 else principal_point
         K = np.array([[focal_length, 0.0, px], [0.0, focal_length, py], [0.0, 0.0, 1.0]])
         lap("read")
-        if entries is not None:                                              # the 2D boxes come with the masks, below
+        auto = None
+        if generator is not None:                                            # masks first: their tight boxes are the 2D boxes
+            auto = generator.generate_device(im, "BGR")
+            boxes = auto["boxes"].cpu().numpy().astype(np.float64).reshape(-1, 4)
+            scores, classes = [float(s) for s in auto["scores"].cpu().tolist()], [0] * len(boxes)
+        elif entries is not None:                                            # the 2D boxes come with the masks, below
             boxes = np.zeros((len(entries), 4), np.float64)
             scores, classes = [float(e.get("score", 1.0)) for e in entries], list(range(len(entries)))
         elif boxes_per_img is not None:
@@ -163,7 +181,7 @@ def do_test(args, cfg):
             scores, classes = [float(b.get("score", 1.0)) for b in inst], [int(b["category_id"]) for b in inst]
         else:
             boxes, scores, classes = detect_boxes(detector, resize, im, cats, cfg.INPUT.FORMAT)
-        cand = [i for i, s in enumerate(scores) if not s < args.threshold]
+        cand = [i for i, s in enumerate(scores) if auto is not None or not s < args.threshold]
         lap("boxes")
         out, kept_idx, labels, depth = [], [], None, None
         if cand:
@@ -175,7 +193,9 @@ def do_test(args, cfg):
             if entries is not None:
                 planes, boxes[cand] = point_masks(predictor, im, [entries[i] for i in cand], args.sam_refine)
             cboxes = boxes[cand]
-            if entries is None:
+            if auto is not None:
+                planes = auto["masks"]
+            elif entries is None:
                 planes = sam_masks(predictor, None, None, h, w, cboxes, bgr=im, refine=args.sam_refine) if predictor is not None else None
             lap("masks")
             lifted = lift_boxes(depth, K, boxes_xyxy=cboxes, masks=list(planes) if planes is not None else None, params=params)
@@ -210,6 +230,12 @@ def argument_parser():
     parser.add_argument("--points-file", type=str, default="",
                         help="click prompts per image ({image name: [{points [[x, y]], labels [1 | 0], category_name, optional bbox xywh, optional score}]}) "
                              "instead of the detector: Segment Anything masks what was clicked")
+    parser.add_argument("--everything", action="store_true",
+                        help="no names, boxes or clicks: Segment Anything's automatic mask generator proposes the masks and each is lifted (needs --mask sam)")
+    parser.add_argument("--points-per-side", type=int, default=32, help="--everything: the click grid's side (at most 36)")
+    parser.add_argument("--pred-iou-thresh", type=float, default=0.88, help="--everything: keep masks whose predicted IoU is above it")
+    parser.add_argument("--stability-score-thresh", type=float, default=0.95, help="--everything: keep masks whose stability score is at least it")
+    parser.add_argument("--box-nms-thresh", type=float, default=0.7, help="--everything: box IoU above which the lower-scored mask is dropped")
     parser.add_argument("--sam-refine", type=int, default=0, metavar="N",
                         help="--mask sam: N more passes per prompt with the previous pass's low-resolution logits as mask_input (default 0)")
     parser.add_argument("--boxes-file", type=str, default="", help="2D boxes per image ({image name: [{bbox xywh, category_id, score}]}) instead of the detector")
@@ -235,11 +261,18 @@ def argument_parser():
 def check_arguments(args, parser):
     """Exit status 2 for what cannot work, before any device call."""
     check_args(args, parser)                                                 # --depth-dir with --depth files only, --sam-refine (tools/ovmono3d_geo.py)
+    if args.everything:
+        if args.points_file or args.boxes_file:
+            parser.error("--everything proposes its own masks: it takes neither --points-file nor --boxes-file")
+        if args.mask != "sam":
+            parser.error("--everything runs Segment Anything's automatic mask generator: it needs --mask sam, not --mask box")
+        if not 1 <= args.points_per_side <= 36:
+            parser.error("--points-per-side must be 1 .. 36 (3 candidates per point, 4096 rows in the NMS)")
     if args.points_file and args.mask != "sam":
         parser.error("--points-file prompts Segment Anything with the clicks: it needs --mask sam, not --mask box")
     if args.points_file and args.boxes_file:
         parser.error("--points-file and --boxes-file both replace the detector: give one")
-    if not args.points_file and not args.labels_file:
+    if not args.points_file and not args.labels_file and not args.everything:
         parser.error("the following arguments are required: --labels-file (or --points-file)")
     if args.depth == "depthpro" and not args.depthpro_weights:
         parser.error("--depth depthpro needs --depthpro-weights FILE")

@@ -1185,6 +1185,50 @@ int ovm_sam_predict(OvmSam* sam, const float* points_xy, const int32_t* labels, 
  * atomicMin / atomicMax / atomicAdd into the outputs): exact. boxes_xyxy_out 16-byte aligned. Stream-ordered. */
 int ovm_sam_mask_boxes(const uint8_t* masks_u8, int32_t n, int32_t H, int32_t W, float* boxes_xyxy_out, int32_t* counts_out, ovm_stream_t stream);
 
+/* ---- Segment Anything, automatic mask generation -----------------------------------------------------------------------------
+ * segment_anything's SamAutomaticMaskGenerator for the full-image crop (crop_n_layers = 0), "binary_mask" output, no small-region
+ * clean-up: one foreground click per grid point, multimask outputs, 3 candidates per point in point-major order (candidate
+ * 3 p + k = plane k of point p). The rules (restated from segment_anything's automatic_mask_generator.py / utils/amg.py; the
+ * package is not a dependency, parity with it is not pinned by a test):
+ *   filter 1    only when pred_iou_thresh > 0: keep iou > pred_iou_thresh (strict)
+ *   stability   over the postprocess_masks logits v at H x W: float32(count(v > +offset)) / float32(count(v > -offset)); 0 / 0 = NaN
+ *   filter 2    only when stability_thresh > 0: keep stability >= stability_thresh (NaN fails)
+ *   mask        v > 0; box = inclusive (xmin, ymin, xmax, ymax) of the mask, (0, 0, 0, 0) for an empty one; area = its pixel count
+ *   NMS         torchvision.ops.nms on the inclusive boxes as floats (area (xmax - xmin) (ymax - ymin)), score = iou, suppression at
+ *               IoU > nms_thresh (strict): the rule of ovm_op_nms (decreasing score, ties to the lower index); output in keep order
+ * The crop-edge filter of the generator never removes a mask of the full-image crop and is not built.
+ *
+ * One candidate. flags bit 0 (OVM_SAM_CAND_SKIPPED): the row failed filter 1 inside ovm_sam_auto_candidates and its mask was never
+ * counted: stability 0, area 0, box and counts 0. 64 bytes. */
+#define OVM_SAM_CAND_SKIPPED 1
+typedef struct OvmSamCandidate {
+  float iou;                 /* the decoder's IoU prediction of the plane */
+  float stability;           /* float32(cnt_hi) / float32(cnt_lo) */
+  int32_t area;              /* count(v > 0) */
+  int32_t box[4];            /* inclusive xmin, ymin, xmax, ymax of v > 0; zeros for an empty mask */
+  int32_t cnt_hi, cnt_lo;    /* count(v > +offset), count(v > -offset) */
+  int32_t flags;
+  int32_t reserved[6];
+} OvmSamCandidate;
+/* The candidates of n foreground clicks on the image of the last ovm_sam_set_image. points_xy: device fp32 [n][2], original pixels
+ * (x, y). out: device OvmSamCandidate [3 n]. Per chunk of at most max_boxes points: ovm_sam_predict's own launches for one point of
+ * label 1, multimask, low-resolution logits into the workspace and no mask written; then the mask statistics of the chunk's planes
+ * (ovm_op_sam_mask_stats: nothing of image size is written); then the rows. With pred_iou_thresh > 0 the planes with
+ * !(iou > pred_iou_thresh) are not counted (decided on the device; OVM_SAM_CAND_SKIPPED); with pred_iou_thresh <= 0 every plane is.
+ * The workspace (256-byte aligned) may be smaller than ovm_sam_auto_candidates_workspace says as long as it holds one point: smaller
+ * chunks. Stream-ordered, no synchronisation, no allocation. */
+int ovm_sam_auto_candidates_workspace(const OvmSam* sam, int32_t n, int64_t* bytes);
+int ovm_sam_auto_candidates(OvmSam* sam, const float* points_xy, int32_t n, float pred_iou_thresh, float offset, OvmSamCandidate* out,
+                            void* workspace, int64_t workspace_bytes, ovm_stream_t stream);
+/* Filters 1 and 2 and the NMS over m candidates (device). A row is valid when it was not skipped, its iou is a number, and it
+ * passes the filters that are switched on; pred_iou_thresh here must not be lower than the one the table was computed with (a
+ * skipped row stays out). keep_idx: device int32 [m], the kept candidate indices in NMS keep order; n_keep: one device word.
+ * m > 4096: OVM_ERR_CAPACITY before any device work (points_per_side <= 36). workspace: ovm_sam_auto_select_workspace bytes,
+ * 16-byte aligned. Stream-ordered; the NMS is ovm_op_nms's and, as there, allocates its scratch and waits for the stream. */
+int ovm_sam_auto_select_workspace(int32_t m, int64_t* bytes);
+int ovm_sam_auto_select(const OvmSamCandidate* cands, int32_t m, float pred_iou_thresh, float stability_thresh, float nms_thresh,
+                        int32_t* keep_idx, int32_t* n_keep, void* workspace, int64_t workspace_bytes, ovm_stream_t stream);
+
 /* ---- Depth Pro, metric depth ------------------------------------------------------------------------------------------------
  * The depth source of OVMono3D-GEO (reference tools/ovmono3d_geo.py:267,290-295: depth_pro's model.infer(image, f_px)). The
  * arithmetic is Hugging Face transformers' DepthProForDepthEstimation + DepthProImageProcessor (preprocess and
@@ -1285,6 +1329,16 @@ int ovm_op_sam_mask_prod(const float* up, const float* hyper, int32_t ld_hyper, 
  * -> H x W) > 0, plane n at logits + n * box_stride. newh or neww outside 1 .. S: OVM_ERR_SHAPE. */
 int ovm_op_sam_mask_out(const float* logits, int64_t box_stride, int32_t L, int32_t S, int32_t newh, int32_t neww, int32_t H, int32_t W, int32_t nb,
                         uint8_t* out, ovm_stream_t stream);
+/* The statistics of the same value v = bilinear(bilinear(logits L x L -> S x S)[:newh, :neww] -> H x W) without writing it: per plane
+ * n (logits + n * plane_stride) seven int32 words out[n][7] = count(v > +offset), count(v > 0), count(v > -offset), then the inclusive
+ * xmin, ymin, xmax, ymax of v > 0 (zeros for an empty plane). v is the value ovm_op_sam_mask_out thresholds, by the same device
+ * functions: the middle count is that mask's byte sum and the box its tight box, to the bit. skip: device int32 [planes] or NULL; a
+ * plane whose word is nonzero is not evaluated and its seven words stay as the caller left them. Integer reductions (thread, wave,
+ * one atomic per wave and value): independent of execution order. OVM_ERR_SHAPE, before any device work, for L < 1, S < L, newh or
+ * neww outside 1 .. S, neww > 4096 (two rows of the S-plane must fit the kernel's 32 KiB of LDS), H, W < 1, H * W >= 2^31,
+ * plane_stride < L * L or planes > 65535. */
+int ovm_op_sam_mask_stats(const float* logits, int64_t plane_stride, int32_t planes, int32_t L, int32_t S, int32_t newh, int32_t neww, int32_t H,
+                          int32_t W, float offset, const int32_t* skip, int32_t* out, ovm_stream_t stream);
 /* Patch rows hi (+ lo, may be NULL) [G*G][ld], column (py * P + px) * 3 + c -> out fp32 [3][G P][G P]. ld < 3 P^2: OVM_ERR_SHAPE. */
 int ovm_op_sam_unpatch(const uint16_t* hi, const uint16_t* lo, int32_t ld, int32_t G, int32_t P, float* out, ovm_stream_t stream);
 /* iou [n][3] = head [n][ldh] columns 1 .. 3. ldh < 4: OVM_ERR_SHAPE. */

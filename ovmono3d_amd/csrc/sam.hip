@@ -11,6 +11,8 @@
 //   sam_mask_boxes_kernel tight box and pixel count of a mask plane
 //   sam_mask_out_kernel   postprocess_masks + threshold: both bilinear resamplings (4G -> S, crop, -> H x W) evaluated per output
 //                         pixel from the low-resolution logits, uint8 written at (H, W); the S x S plane never exists in HBM
+//   sam_mask_stats_kernel the same value counted instead of written (automatic mask generation): per plane the pixel counts above
+//                         +offset, 0 and -offset and the tight box, S-plane rows cached in LDS; nothing of image size is written
 //   sam_mask_prod_kernel  hypernetwork product over the requested mask tokens
 //   small element-wise ones (box embedding, dense positional encoding, LayerNorm + GELU of the upscaling, broadcast add)
 // Layouts: every activation is fp32 row-major [rows][channels]; image-side rows are (box, y * G + x). The two transposed
@@ -25,6 +27,7 @@
 #include <vector>
 
 #include "../../include/ovm3d.h"
+#include "det2d.hpp"
 #include "kernels.hpp"
 #include "tower.hpp"
 
@@ -336,11 +339,17 @@ __device__ __forceinline__ float up_sample(const float* __restrict__ lg, int L, 
   return (1.f - ly) * ((1.f - lx) * a + lx * b) + ly * ((1.f - lx) * c + lx * d);
 }
 
+// the second resampling's blend of four S-plane samples: the value of postprocess_masks at an output pixel. sam_mask_out_kernel
+// thresholds it, sam_mask_stats_kernel counts it; both go through this one function (and through up_sample for a, b, c, d)
+__device__ __forceinline__ float mask_blend(float a, float b, float c, float d, float ly, float lx) {
+  return (1.f - ly) * ((1.f - lx) * a + lx * b) + ly * ((1.f - lx) * c + lx * d);
+}
+
 __device__ __forceinline__ uint8_t mask_pixel(const float* __restrict__ lg, int L, float sc1, int newh, int neww, float sch, float scw, int y, int x) {
   int y0, y1, x0, x1; float ly, lx;
   bil_tap(y, sch, newh, &y0, &y1, &ly); bil_tap(x, scw, neww, &x0, &x1, &lx);
   const float a = up_sample(lg, L, sc1, y0, x0), b = up_sample(lg, L, sc1, y0, x1), c = up_sample(lg, L, sc1, y1, x0), d = up_sample(lg, L, sc1, y1, x1);
-  const float vv = (1.f - ly) * ((1.f - lx) * a + lx * b) + ly * ((1.f - lx) * c + lx * d);
+  const float vv = mask_blend(a, b, c, d, ly, lx);
   return vv > 0.f ? 1 : 0;
 }
 
@@ -417,6 +426,122 @@ __global__ void sam_mask_boxes_final_kernel(int* __restrict__ box, const int* __
   const int4 v = reinterpret_cast<const int4*>(box)[i];
   const bool any = cnt[i] > 0;
   reinterpret_cast<float4*>(box)[i] = any ? make_float4((float)v.x, (float)v.y, (float)(v.z + 1), (float)(v.w + 1)) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// ---- automatic mask generation: the statistics of a mask plane without the plane -------------------------------------------------
+// stats [n][7] int32: count(v > +off), count(v > 0), count(v > -off), xmin, ymin, xmax, ymax of v > 0; v = the value mask_pixel
+// thresholds. A plane whose skip word is set is left alone by all three kernels.
+constexpr int kStatsWords = 7;
+constexpr int kStatsLdsFloats = 8192;   // 32 KiB of S-plane samples per workgroup: five workgroups share a CU's 160 KiB
+constexpr int kStatsMaxRows = 16;       // S-plane rows a workgroup caches at most
+constexpr int kStatsMaxBand = 64;       // output rows per workgroup at most
+
+__global__ void sam_mask_stats_init_kernel(int* __restrict__ st, const int* __restrict__ skip, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n || (skip && skip[i])) return;
+  int* o = st + (size_t)i * kStatsWords;
+  o[0] = 0; o[1] = 0; o[2] = 0; o[3] = 0x7fffffff; o[4] = 0x7fffffff; o[5] = -1; o[6] = -1;      // sam_mask_boxes_init_kernel's sentinels
+}
+
+// Workgroup (band, plane): output rows [band * R, band * R + R) of one plane. The S-plane rows those rows blend (from the first
+// row's upper tap to the last row's lower tap, at most NR of them) are evaluated once, by up_sample, into LDS [row][neww]; each
+// output pixel is then mask_blend of four cached samples - the arithmetic of mask_pixel, value for value - or of up_sample itself for
+// a row beyond the cache. A thread owns columns (x taps once per column) and walks the band's rows; counts and extremes go per
+// thread, then per wave (shuffles), then one atomic per wave and value.
+__global__ __launch_bounds__(256) void sam_mask_stats_kernel(const float* __restrict__ logits, long plane_stride, const int* __restrict__ skip, int L, int S,
+                                                             int newh, int neww, int H, int W, int R, int NR, int txw_log2, float off,
+                                                             int* __restrict__ st) {
+  extern __shared__ float smp[];
+  const int p = blockIdx.y;
+  if (skip && skip[p]) return;
+  const float* lg = logits + (size_t)p * plane_stride;
+  const float sc1 = (float)L / (float)S, sch = (float)newh / (float)H, scw = (float)neww / (float)W;
+  const int ya = blockIdx.x * R, yb = min(H, ya + R);
+  int Ylo, Yhi, ti; float tl;
+  bil_tap(ya, sch, newh, &Ylo, &ti, &tl); bil_tap(yb - 1, sch, newh, &ti, &Yhi, &tl);
+  const int nrows = min(Yhi - Ylo + 1, NR);
+  for (int i = threadIdx.x; i < nrows * neww; i += 256) {
+    const int r = i / neww, X = i - r * neww;
+    smp[i] = up_sample(lg, L, sc1, Ylo + r, X);
+  }
+  __syncthreads();
+  auto sample = [&](int Y, int X) -> float { const int r = Y - Ylo; return r < nrows ? smp[r * neww + X] : up_sample(lg, L, sc1, Y, X); };
+  const int txw = 1 << txw_log2, tx = threadIdx.x & (txw - 1), ty = threadIdx.x >> txw_log2, nty = 256 >> txw_log2;
+  int chi = 0, cmid = 0, clo = 0, bx0 = 0x7fffffff, by0 = 0x7fffffff, bx1 = -1, by1 = -1;
+  for (int x = tx; x < W; x += txw) {
+    int x0, x1; float lx;
+    bil_tap(x, scw, neww, &x0, &x1, &lx);
+    bool any = false;
+    for (int y = ya + ty; y < yb; y += nty) {
+      int y0, y1; float ly;
+      bil_tap(y, sch, newh, &y0, &y1, &ly);
+      const float v = mask_blend(sample(y0, x0), sample(y0, x1), sample(y1, x0), sample(y1, x1), ly, lx);
+      chi += v > off ? 1 : 0; clo += v > -off ? 1 : 0;
+      if (v > 0.f) { ++cmid; any = true; by0 = min(by0, y); by1 = max(by1, y); }
+    }
+    if (any) { bx0 = min(bx0, x); bx1 = max(bx1, x); }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    chi += __shfl_xor(chi, o, 64); cmid += __shfl_xor(cmid, o, 64); clo += __shfl_xor(clo, o, 64);
+    bx0 = min(bx0, __shfl_xor(bx0, o, 64)); by0 = min(by0, __shfl_xor(by0, o, 64));
+    bx1 = max(bx1, __shfl_xor(bx1, o, 64)); by1 = max(by1, __shfl_xor(by1, o, 64));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    int* o = st + (size_t)p * kStatsWords;
+    if (chi > 0) atomicAdd(&o[0], chi);
+    if (clo > 0) atomicAdd(&o[2], clo);
+    if (cmid > 0) { atomicAdd(&o[1], cmid); atomicMin(&o[3], bx0); atomicMin(&o[4], by0); atomicMax(&o[5], bx1); atomicMax(&o[6], by1); }
+  }
+}
+
+// an empty plane's box: the sentinels -> zeros
+__global__ void sam_mask_stats_final_kernel(int* __restrict__ st, const int* __restrict__ skip, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n || (skip && skip[i])) return;
+  int* o = st + (size_t)i * kStatsWords;
+  if (o[1] == 0) { o[3] = 0; o[4] = 0; o[5] = 0; o[6] = 0; }
+}
+
+__global__ void sam_fill_int_kernel(int* __restrict__ x, int v, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) x[i] = v;
+}
+
+// filter 1 ahead of the statistics: skip[i] = the plane fails iou > thr (thr > 0; a NaN fails)
+__global__ void sam_auto_skip_kernel(const float* __restrict__ iou, float thr, int n, int* __restrict__ skip) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) skip[i] = (thr > 0.f && !(iou[i] > thr)) ? 1 : 0;
+}
+
+__global__ void sam_auto_rows_kernel(const float* __restrict__ iou, const int* __restrict__ st, const int* __restrict__ skip, int n,
+                                     OvmSamCandidate* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  OvmSamCandidate c; memset(&c, 0, sizeof(c));
+  c.iou = iou[i];
+  if (skip[i]) c.flags = OVM_SAM_CAND_SKIPPED;
+  else {
+    const int* o = st + (size_t)i * kStatsWords;
+    c.cnt_hi = o[0]; c.area = o[1]; c.cnt_lo = o[2];
+    c.stability = (float)o[0] / (float)o[2];                       // 0 / 0: NaN, which fails filter 2
+    c.box[0] = o[3]; c.box[1] = o[4]; c.box[2] = o[5]; c.box[3] = o[6];
+  }
+  out[i] = c;
+}
+
+// the valid mask of filters 1 and 2 and the NMS operands: the inclusive box as floats, the IoU prediction as the score
+__global__ void sam_auto_valid_kernel(const OvmSamCandidate* __restrict__ cands, int m, float pthr, float sthr, float* __restrict__ boxes,
+                                      float* __restrict__ scores, int* __restrict__ valid) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  const OvmSamCandidate c = cands[i];
+  bool ok = !(c.flags & OVM_SAM_CAND_SKIPPED) && c.iou == c.iou;
+  if (pthr > 0.f) ok = ok && c.iou > pthr;
+  if (sthr > 0.f) ok = ok && c.stability >= sthr;
+  valid[i] = ok ? 1 : 0; scores[i] = c.iou;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) boxes[4 * i + k] = (float)c.box[k];
 }
 
 int lin(OvmSam* m, const PackedLin& w, const float* x, int ldx, long M, int act, const float* res, int ldr, float* y, int ldy, hipStream_t s) {
@@ -524,6 +649,32 @@ int launch_mask_boxes(const uint8_t* masks, int n, int H, int W, float* box, int
   hipLaunchKernelGGL(sam_mask_boxes_init_kernel, g1(n), dim3(256), 0, s, (int*)box, cnt, n);
   hipLaunchKernelGGL(sam_mask_boxes_kernel, dim3((unsigned)gx, (unsigned)n), dim3(256), 0, s, masks, H, W, (int*)box, cnt);
   hipLaunchKernelGGL(sam_mask_boxes_final_kernel, g1(n), dim3(256), 0, s, (int*)box, (const int*)cnt, n);
+  return last_launch();
+}
+
+// The geometry rules of ovm_op_sam_mask_stats, without a launch (the engine checks them before its first chunk)
+int mask_stats_geometry(long plane_stride, int planes, int L, int S, int newh, int neww, int H, int W) {
+  if (L < 1 || S < L || newh < 1 || neww < 1 || newh > S || neww > S || 2 * neww > kStatsLdsFloats || H < 1 || W < 1) return OVM_ERR_SHAPE;
+  if ((long)H * W >= (1L << 31) || plane_stride < (long)L * L || planes > 65535) return OVM_ERR_SHAPE;
+  return OVM_OK;
+}
+
+// st int32 [planes][7]. NR = the S-plane rows the LDS budget holds (>= 2: an output row blends two); a band of R output rows spans
+// about R * newh / H + 2 of them, so R = (NR - 2) * H / newh keeps a band inside the cache (the kernel evaluates a row beyond it directly).
+int launch_mask_stats(const float* logits, long plane_stride, int planes, int L, int S, int newh, int neww, int H, int W, float off, const int* skip, int* st,
+                      hipStream_t s) {
+  const int g = mask_stats_geometry(plane_stride, planes, L, S, newh, neww, H, W);
+  if (g) return g;
+  int NR = kStatsLdsFloats / neww; if (NR > kStatsMaxRows) NR = kStatsMaxRows;
+  long R = (long)((double)(NR - 2) * (double)H / (double)newh);
+  if (R < 1) R = 1;
+  if (R > kStatsMaxBand) R = kStatsMaxBand;
+  if (R > H) R = H;
+  const int bands = (int)((H + R - 1) / R), txw_log2 = W > 128 ? 8 : W > 32 ? 6 : 4;
+  hipLaunchKernelGGL(sam_mask_stats_init_kernel, g1(planes), dim3(256), 0, s, st, skip, planes);
+  hipLaunchKernelGGL(sam_mask_stats_kernel, dim3((unsigned)bands, (unsigned)planes), dim3(256), (size_t)NR * neww * sizeof(float), s, logits, plane_stride, skip, L, S,
+                     newh, neww, H, W, (int)R, NR, txw_log2, off, st);
+  hipLaunchKernelGGL(sam_mask_stats_final_kernel, g1(planes), dim3(256), 0, s, st, skip, planes);
   return last_launch();
 }
 
@@ -659,7 +810,8 @@ int decode_chunk(OvmSam* m, const Prompt& pr, int nb, int mask_index, uint8_t* m
   const long LL = (long)m->L * m->L;
   float* planes = lowres ? lowres : w.low; const long stride = lowres ? K * LL : LL;
   OVM_TRY(m, launch_mask_prod(w.up2, w.hyp, c.num_mask_tokens * C8, lowres ? tk0 : tk0 + mask_index, lowres ? K : 1, C8, m->G, nb, planes, stride, s));
-  // 5. postprocess_masks + threshold
+  // 5. postprocess_masks + threshold (not for the candidates of the automatic generator: they are counted, not written)
+  if (!masks) return OVM_OK;
   return launch_mask_out(planes + (lowres ? (size_t)mask_index * LL : 0), stride, m->L, m->S, m->newh, m->neww, m->H, m->W, nb, masks, s);
 }
 
@@ -965,6 +1117,86 @@ int ovm_sam_mask_boxes(const uint8_t* masks, int32_t n, int32_t H, int32_t W, fl
   return launch_mask_boxes(masks, n, H, W, boxes_out, counts_out, (hipStream_t)stream);
 }
 
+// ---- automatic mask generation (include/ovm3d.h, "Segment Anything, automatic mask generation")
+namespace {
+struct AutoWork { float* low; float* iou; int* labels; int* stats; int* skip; };
+
+// the prompt workspace of a chunk of nb one-point prompts, then the chunk's low-res logits, IoU rows, labels, statistics, skip words
+size_t carve_auto(Work* w, AutoWork* a, char* base, const OvmSam* m, long nb) {
+  size_t off = carve(w, base, m, nb, 1 + m->cfg.num_mask_tokens + 2, false);
+  auto take = [&](void** p, size_t bytes) { if (a) *p = base + off; off += (bytes + 255) / 256 * 256; };
+  AutoWork dummy; AutoWork* x = a ? a : &dummy;
+  take((void**)&x->low, (size_t)nb * 3 * m->L * m->L * 4); take((void**)&x->iou, (size_t)nb * 3 * 4); take((void**)&x->labels, (size_t)nb * 4);
+  take((void**)&x->stats, (size_t)nb * 3 * kStatsWords * 4); take((void**)&x->skip, (size_t)nb * 3 * 4);
+  return off;
+}
+}  // namespace
+
+int ovm_sam_auto_candidates_workspace(const OvmSam* m, int32_t n, int64_t* bytes) {
+  if (!m || !bytes || n < 0 || !m->tower.fam) return OVM_ERR_INVALID;
+  const int nb = n < m->cfg.max_boxes ? n : m->cfg.max_boxes;
+  *bytes = (int64_t)carve_auto(nullptr, nullptr, nullptr, m, nb < 1 ? 1 : nb);
+  return OVM_OK;
+}
+
+int ovm_sam_auto_candidates(OvmSam* m, const float* points_xy, int32_t n, float pred_iou_thresh, float offset, OvmSamCandidate* out, void* workspace,
+                            int64_t workspace_bytes, ovm_stream_t stream) {
+  if (!m) return OVM_ERR_INVALID;
+  m->err.clear();
+  if (!m->tower.fam) { m->err = "handle was not created"; return OVM_ERR_INVALID; }
+  if (!m->has_image) { m->err = "ovm_sam_set_image has not been called"; return OVM_ERR_INVALID; }
+  if (n < 0) { m->err = "invalid arguments (n >= 0)"; return OVM_ERR_INVALID; }
+  if (n == 0) return OVM_OK;
+  if (!points_xy || !out || !workspace) { m->err = "null points, candidates or workspace"; return OVM_ERR_INVALID; }
+  if ((uintptr_t)workspace & 255) { m->err = "the workspace must be 256-byte aligned"; return OVM_ERR_INVALID; }
+  const long LL = (long)m->L * m->L;
+  if (mask_stats_geometry(LL, 3, m->L, m->S, m->newh, m->neww, m->H, m->W)) { m->err = "image or model size outside the mask statistics kernel's range (ovm_op_sam_mask_stats)"; return OVM_ERR_SHAPE; }
+  hipStream_t s = (hipStream_t)stream;
+  int nb = n < m->cfg.max_boxes ? n : m->cfg.max_boxes;
+  while (nb > 1 && (int64_t)carve_auto(nullptr, nullptr, nullptr, m, nb) > workspace_bytes) nb = (nb + 1) / 2;
+  if ((int64_t)carve_auto(nullptr, nullptr, nullptr, m, nb) > workspace_bytes) { m->err = "workspace too small for one point (ovm_sam_auto_candidates_workspace)"; return OVM_ERR_CAPACITY; }
+  OVM_HIP(m, hipSetDevice(m->device));
+  Work w; AutoWork a; carve_auto(&w, &a, (char*)workspace, m, nb);
+  hipLaunchKernelGGL(sam_fill_int_kernel, g1(nb), dim3(256), 0, s, a.labels, 1, nb);
+  OVM_TRY(m, last_launch());
+  for (int b0 = 0; b0 < n; b0 += nb) {
+    const int cnt = n - b0 < nb ? n - b0 : nb, planes = 3 * cnt;
+    Prompt pr; pr.points = points_xy + (size_t)b0 * 2; pr.labels = a.labels; pr.P = 1; pr.multimask = true;
+    OVM_TRY(m, decode_chunk(m, pr, cnt, 0, nullptr, a.iou, a.low, w, s));
+    hipLaunchKernelGGL(sam_auto_skip_kernel, g1(planes), dim3(256), 0, s, (const float*)a.iou, pred_iou_thresh, planes, a.skip);
+    OVM_TRY(m, launch_mask_stats(a.low, LL, planes, m->L, m->S, m->newh, m->neww, m->H, m->W, offset, a.skip, a.stats, s));
+    hipLaunchKernelGGL(sam_auto_rows_kernel, g1(planes), dim3(256), 0, s, (const float*)a.iou, (const int*)a.stats, (const int*)a.skip, planes, out + (size_t)b0 * 3);
+    OVM_TRY(m, last_launch());
+  }
+  return OVM_OK;
+}
+
+int ovm_sam_auto_select_workspace(int32_t m, int64_t* bytes) {
+  if (!bytes || m < 0) return OVM_ERR_INVALID;
+  const size_t rows = m < 1 ? 1 : (size_t)m;
+  *bytes = (int64_t)((rows * 16 + 255) / 256 * 256 + 2 * ((rows * 4 + 255) / 256 * 256));
+  return OVM_OK;
+}
+
+int ovm_sam_auto_select(const OvmSamCandidate* cands, int32_t m, float pred_iou_thresh, float stability_thresh, float nms_thresh, int32_t* keep_idx,
+                        int32_t* n_keep, void* workspace, int64_t workspace_bytes, ovm_stream_t stream) {
+  if (m < 0 || !n_keep) return OVM_ERR_INVALID;
+  if (m > 4096) return OVM_ERR_CAPACITY;
+  hipStream_t s = (hipStream_t)stream;
+  if (m == 0) return hipMemsetAsync(n_keep, 0, sizeof(int), s) == hipSuccess ? OVM_OK : OVM_ERR_HIP;
+  int64_t need = 0;
+  ovm_sam_auto_select_workspace(m, &need);
+  if (!cands || !keep_idx || !workspace || ((uintptr_t)workspace & 15)) return OVM_ERR_INVALID;
+  if (workspace_bytes < need) return OVM_ERR_CAPACITY;
+  char* base = (char*)workspace;
+  float* boxes = (float*)base; base += ((size_t)m * 16 + 255) / 256 * 256;
+  float* scores = (float*)base; base += ((size_t)m * 4 + 255) / 256 * 256;
+  int* valid = (int*)base;
+  hipLaunchKernelGGL(sam_auto_valid_kernel, g1(m), dim3(256), 0, s, cands, m, pred_iou_thresh, stability_thresh, boxes, scores, valid);
+  if (last_launch()) return OVM_ERR_HIP;
+  return launch_nms_single(boxes, scores, valid, m, nms_thresh, keep_idx, n_keep, s);
+}
+
 int64_t ovm_sam_debug_copy(OvmSam* m, const char* name, float* dst, int64_t capacity, ovm_stream_t stream) {
   if (!m || !name || !dst || !m->tower.fam) return OVM_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
@@ -1057,6 +1289,12 @@ int ovm_op_sam_mask_out(const float* logits, int64_t box_stride, int32_t L, int3
   if (!logits || !out || nb < 1 || L < 1 || H < 1 || W < 1) return OVM_ERR_INVALID;
   if (newh < 1 || neww < 1 || newh > S || neww > S) return OVM_ERR_SHAPE;
   return launch_mask_out(logits, (long)box_stride, L, S, newh, neww, H, W, nb, out, (hipStream_t)stream);
+}
+
+int ovm_op_sam_mask_stats(const float* logits, int64_t plane_stride, int32_t planes, int32_t L, int32_t S, int32_t newh, int32_t neww, int32_t H, int32_t W,
+                          float offset, const int32_t* skip, int32_t* out, ovm_stream_t stream) {
+  if (!logits || !out || planes < 1) return OVM_ERR_INVALID;
+  return launch_mask_stats(logits, (long)plane_stride, planes, L, S, newh, neww, H, W, offset, skip, out, (hipStream_t)stream);
 }
 
 int ovm_op_sam_unpatch(const uint16_t* hi, const uint16_t* lo, int32_t ld, int32_t G, int32_t P, float* out, ovm_stream_t stream) {

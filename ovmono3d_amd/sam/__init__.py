@@ -27,6 +27,16 @@ VIT_H = (1280, 32, 16, 16, 64, 14, (7, 15, 23, 31))
 PIXEL_MEAN = (123.675, 116.28, 103.53)
 PIXEL_STD = (58.395, 57.12, 57.375)
 MAX_POINTS = 8                       # points per prompt (csrc/sam.hip: 5 + 8 + 2 = 15 of the 16 tokens its second attention kernel holds)
+CAND_WORDS = C.sizeof(_lib.OvmSamCandidate) // 4          # an OvmSamCandidate as int32 words
+MAX_AUTO_POINTS = 4096 // 3          # 3 candidates per point must fit the 4,096 rows the NMS takes: points_per_side <= 36
+
+
+def candidate_fields(table) -> Dict[str, np.ndarray]:
+    """A candidate table (int32 [m, 16], device or host) as named host arrays: the fields of ``OvmSamCandidate``."""
+    t = table.detach().cpu().numpy() if isinstance(table, torch.Tensor) else np.asarray(table)
+    t = np.ascontiguousarray(t, np.int32).reshape(-1, CAND_WORDS)
+    return {"iou": t[:, 0].copy().view(np.float32), "stability": t[:, 1].copy().view(np.float32), "area": t[:, 2].copy(), "box": t[:, 3:7].copy(),
+            "cnt_hi": t[:, 7].copy(), "cnt_lo": t[:, 8].copy(), "flags": t[:, 9].copy()}
 
 
 def check_prompts(point_coords=None, point_labels=None, boxes=None, mask_inputs=None, low_side: Optional[int] = None):
@@ -192,6 +202,40 @@ class SamEngine:
             self._chk(self.L.ovm_sam_mask_boxes(masks.data_ptr(), n, H, W, boxes.data_ptr(), counts.data_ptr(), self._stream()), "ovm_sam_mask_boxes")
         return boxes, counts
 
+    def auto_candidates(self, points: torch.Tensor, pred_iou_thresh: float, offset: float, out: Optional[torch.Tensor] = None,
+                        workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """ovm_sam_auto_candidates: points device fp32 [n, 2] (x, y) -> the candidate table, device int32 [3 n, 16] (the words of
+        ``OvmSamCandidate``; ``candidate_fields`` names them). ``out``: a slice of a larger table to fill."""
+        n = int(points.shape[0])
+        if out is None:
+            out = torch.empty((3 * n, CAND_WORDS), dtype=torch.int32, device=self.dev)
+        if n:
+            ws = workspace
+            if ws is None:
+                nbytes = C.c_int64()
+                self._chk(self.L.ovm_sam_auto_candidates_workspace(self._h, n, C.byref(nbytes)), "ovm_sam_auto_candidates_workspace")
+                if self._ws is None or self._ws.numel() < nbytes.value:
+                    self._ws = None
+                    self._ws = torch.empty(int(nbytes.value), dtype=torch.uint8, device=self.dev)
+                ws = self._ws
+            self._chk(self.L.ovm_sam_auto_candidates(self._h, points.data_ptr(), n, float(pred_iou_thresh), float(offset), out.data_ptr(), ws.data_ptr(),
+                                                     ws.numel(), self._stream()), "ovm_sam_auto_candidates")
+        return out
+
+    def auto_select(self, cands: torch.Tensor, pred_iou_thresh: float, stability_score_thresh: float, box_nms_thresh: float):
+        """ovm_sam_auto_select on a table of ``auto_candidates``: (keep_idx int32 [m], n_keep int32 [1]), device tensors."""
+        m = int(cands.shape[0])
+        keep = torch.empty((max(m, 1),), dtype=torch.int32, device=self.dev)
+        n_keep = torch.zeros((1,), dtype=torch.int32, device=self.dev)
+        nbytes = C.c_int64()
+        rc = self.L.ovm_sam_auto_select_workspace(m, C.byref(nbytes))
+        ws = torch.empty(int(nbytes.value) if rc == 0 else 256, dtype=torch.uint8, device=self.dev)
+        rc = self.L.ovm_sam_auto_select(cands.data_ptr(), m, float(pred_iou_thresh), float(stability_score_thresh), float(box_nms_thresh),
+                                        keep.data_ptr(), n_keep.data_ptr(), ws.data_ptr(), ws.numel(), self._stream())
+        if rc != 0:
+            raise _lib.OvmError(f"ovm_sam_auto_select failed with code {rc} (m = {m}; at most 4096 candidates)")
+        return keep, n_keep
+
     def debug(self, name: str, shape) -> torch.Tensor:
         out = torch.empty(shape, dtype=torch.float32, device=self.dev)
         n = self.L.ovm_sam_debug_copy(self._h, name.encode(), out.data_ptr(), out.numel(), self._stream())
@@ -292,6 +336,119 @@ class SamPredictor:
             if k == 0:
                 iou, low = i[0], l[0]
         return torch.stack(planes).bool(), iou, low
+
+
+def build_point_grid(n_per_side: int) -> np.ndarray:
+    """segment_anything's grid: n x n points in [0, 1]^2 at the cell centres, float64 [n * n, 2] as (x, y), row-major in y."""
+    n = int(n_per_side)
+    offset = 1 / (2 * n)
+    g = np.linspace(offset, 1 - offset, n)
+    return np.stack([np.tile(g[None, :], (n, 1)), np.tile(g[:, None], (1, n))], axis=-1).reshape(-1, 2)
+
+
+class SamAutomaticMaskGenerator:
+    """segment_anything's ``SamAutomaticMaskGenerator`` for the full image: a grid of foreground clicks, three candidates per click,
+    the predicted-IoU filter, the stability filter and box NMS, all on the device (``ovm_sam_auto_candidates`` /
+    ``ovm_sam_auto_select``, include/ovm3d.h states the rules). The emitted masks are ``SamPredictor.predict_prompts``'s own planes.
+
+    Not built and refused with ValueError: crops (``crop_n_layers > 0``), the small-region clean-up (``min_mask_region_area > 0``: it
+    needs connected components), RLE output modes. The crop-edge filter never removes a mask of the full-image crop. Parity with the
+    segment_anything package is not pinned by a test (the package is not a dependency); DESIGN.md section 4.4."""
+
+    def __init__(self, predictor: SamPredictor, points_per_side: Optional[int] = 32, points_per_batch: int = 64, pred_iou_thresh: float = 0.88,
+                 stability_score_thresh: float = 0.95, stability_score_offset: float = 1.0, box_nms_thresh: float = 0.7, crop_n_layers: int = 0,
+                 crop_nms_thresh: float = 0.7, crop_overlap_ratio: float = 512 / 1500, crop_n_points_downscale_factor: int = 1,
+                 point_grids=None, min_mask_region_area: int = 0, output_mode: str = "binary_mask"):
+        if crop_n_layers > 0:
+            raise ValueError(f"crop_n_layers = {crop_n_layers}: crops are not built (the full image only)")
+        if min_mask_region_area > 0:
+            raise ValueError(f"min_mask_region_area = {min_mask_region_area}: the small-region clean-up (connected components) is not built")
+        if output_mode != "binary_mask":
+            raise ValueError(f"output_mode = {output_mode!r}: only 'binary_mask' (RLE modes are not built)")
+        if (points_per_side is None) == (point_grids is None):
+            raise ValueError("exactly one of points_per_side and point_grids must be given")
+        if points_per_side is not None:
+            if int(points_per_side) < 1:
+                raise ValueError(f"points_per_side must be at least 1, is {points_per_side}")
+            grid = build_point_grid(points_per_side) if int(points_per_side) ** 2 <= MAX_AUTO_POINTS else None
+            npts = int(points_per_side) ** 2
+            what = f"points_per_side = {points_per_side}"
+        else:
+            grids = point_grids if isinstance(point_grids, (list, tuple)) else [point_grids]
+            if len(grids) != 1:
+                raise ValueError(f"point_grids must hold one grid (crop_n_layers = 0), holds {len(grids)}")
+            grid = np.asarray(grids[0], np.float64).reshape(-1, 2)
+            npts = grid.shape[0]
+            what = f"point_grids with {npts} points"
+        if npts > MAX_AUTO_POINTS:
+            raise ValueError(f"{what}: at most {MAX_AUTO_POINTS} points (3 candidates each, 4096 rows in the NMS: points_per_side <= 36)")
+        if int(points_per_batch) < 1:
+            raise ValueError(f"points_per_batch must be at least 1, is {points_per_batch}")
+        self.predictor, self.point_grid = predictor, grid
+        self.points_per_batch = int(points_per_batch)
+        self.pred_iou_thresh, self.stability_score_thresh = float(pred_iou_thresh), float(stability_score_thresh)
+        self.stability_score_offset, self.box_nms_thresh = float(stability_score_offset), float(box_nms_thresh)
+        self._cands = self._points = None
+
+    def grid_points(self, H: int, W: int) -> np.ndarray:
+        """The grid in the pixels of an H x W image: float32 [n, 2] (x, y), scaled in float64 as segment_anything does."""
+        return (self.point_grid * np.array([W, H], np.float64)[None]).astype(np.float32)
+
+    def candidates(self):
+        """(fields of the last image's candidate table as host arrays (``candidate_fields``), its points float32 [n, 2])."""
+        if self._cands is None:
+            raise RuntimeError("generate() has not been called")
+        return candidate_fields(self._cands), self._points.copy()
+
+    @torch.no_grad()
+    def generate_device(self, image, image_format: str = "RGB"):
+        """dict of device tensors for the kept masks, in NMS keep order: masks uint8 [m, H, W], boxes fp32 [m, 4] (xmin, ymin,
+        xmax + 1, ymax + 1: ``SamPredictor.mask_boxes``), scores fp32 [m] (predicted IoU), stability fp32 [m], points fp32 [m, 2],
+        areas int32 [m]; and ``index`` int64 [m]: the candidate (3 * point + plane) each mask came from."""
+        pred = self.predictor
+        eng = pred.engine
+        pred.set_image(image, image_format)
+        H, W = pred.original_size
+        pts_host = self.grid_points(H, W)
+        pts = torch.from_numpy(pts_host).to(eng.dev)
+        n = pts.shape[0]
+        table = torch.empty((3 * n, CAND_WORDS), dtype=torch.int32, device=eng.dev)
+        for b0 in range(0, n, self.points_per_batch):
+            b1 = min(n, b0 + self.points_per_batch)
+            eng.auto_candidates(pts[b0:b1], self.pred_iou_thresh, self.stability_score_offset, out=table[3 * b0:3 * b1])
+        keep, n_keep = eng.auto_select(table, self.pred_iou_thresh, self.stability_score_thresh, self.box_nms_thresh)
+        m = int(n_keep.item())                                     # the one read the flow needs before it can size its outputs
+        keep = keep[:m].to(torch.int64)
+        self._cands, self._points = table, pts_host
+        masks = torch.empty((m, H, W), dtype=torch.uint8, device=eng.dev)
+        if m:
+            idx = keep.cpu().numpy()
+            ones = torch.ones((m, 1), dtype=torch.int32, device=eng.dev)
+            for k in range(3):                                     # the predictor's own planes, one call per plane
+                rows = np.nonzero(idx % 3 == k)[0]
+                if len(rows):
+                    sel = torch.from_numpy(rows).to(eng.dev)
+                    coords = pts[keep[sel] // 3].reshape(-1, 1, 2).contiguous()
+                    masks[sel] = eng.predict_prompts(coords, ones[:len(rows)], None, None, H, W, multimask=True, mask_index=k)[0]
+        boxes, areas = eng.mask_boxes(masks)
+        kept = table[keep]
+        return {"masks": masks, "boxes": boxes, "scores": kept[:, 0].contiguous().view(torch.float32), "stability": kept[:, 1].contiguous().view(torch.float32),
+                "points": pts[keep // 3], "areas": areas, "index": keep}
+
+    def generate(self, image, image_format: str = "RGB"):
+        """segment_anything's records, one dict per kept mask in NMS keep order: segmentation (bool [H, W], a device tensor), area,
+        bbox (XYWH of the inclusive box: w = xmax - xmin), predicted_iou, point_coords [[x, y]], stability_score, crop_box [0, 0, W, H]."""
+        out = self.generate_device(image, image_format)
+        H, W = self.predictor.original_size
+        f, pts = self.candidates()
+        seg = out["masks"].bool()
+        records = []
+        for i, c in enumerate(out["index"].cpu().numpy().tolist()):
+            x0, y0, x1, y1 = (int(v) for v in f["box"][c])
+            records.append({"segmentation": seg[i], "area": int(f["area"][c]), "bbox": [x0, y0, x1 - x0, y1 - y0], "predicted_iou": float(f["iou"][c]),
+                            "point_coords": [[float(pts[c // 3][0]), float(pts[c // 3][1])]], "stability_score": float(f["stability"][c]),
+                            "crop_box": [0, 0, W, H]})
+        return records
 
 
 def build_sam(arch: str, checkpoint: Union[str, Dict[str, torch.Tensor], None], device: Optional[torch.device] = None,
