@@ -29,6 +29,12 @@ the masks of the whole image and every one is lifted. The record's 2D box is the
 its category "object"; ``--threshold`` is not applied (the generator has its own thresholds). It needs ``--mask sam`` and is refused
 together with ``--points-file`` or ``--boxes-file``.
 
+Masks as outputs, both off by default (the files above are then unchanged): ``--segmentation rle`` adds ``"segmentation": {"size": [H, W],
+"counts": str}`` to every record of ``<name>_dets.json``, the instance's mask as a COCO RLE string, whatever the mask came from (boxes,
+clicks, ``--everything``, ``--mask box``); ``--show-masks`` writes ``<name>_masks.jpg``, the image with the kept instances' masks
+overlaid in the boxes' colours (alpha 0.5, contours). Both are computed on the device (``ovmono3d_amd.masks``); no plane is copied to
+the host.
+
 The LIFT model is not built: ``MODEL.WEIGHTS`` is not needed, the config supplies the detector's settings and ``OUTPUT_DIR``.
 """
 import argparse
@@ -49,10 +55,11 @@ from make_oracle2d import build_caption, build_detector, gdino_postprocess, phra
 from ovmono3d_geo import check_args, refined_masks, sam_masks, xywh_to_xyxy  # noqa: E402
 
 from ovmono3d_amd.data.depth_prompt import add_depth_arguments, build_depth_prompt, load_depth  # noqa: E402
-from ovmono3d_amd.data.gpu_jpeg import read_image_device  # noqa: E402
+from ovmono3d_amd.data.gpu_jpeg import read_image_device, write_jpeg  # noqa: E402
 from ovmono3d_amd.data.gpu_resize import ResizeShortestEdgeGPU  # noqa: E402
 from ovmono3d_amd.defaults import make_cfg  # noqa: E402
 from ovmono3d_amd.geo import GeoParams, box_to_rect, lift_boxes  # noqa: E402
+from ovmono3d_amd.masks import encode_rle, overlay_masks  # noqa: E402
 
 BOX_THRESHOLD, NMS_THRESHOLD = 0.001, 0.5                            # tools/make_oracle2d.py's defaults
 
@@ -208,15 +215,23 @@ def do_test(args, cfg):
                 out.append({"category": cats[ci] if 0 <= ci < len(cats) else ci, "score": float(scores[i]),
                             "bbox3D": list(box["center_cam"]) + list(box["dimensions"]), "pose": box["pose"], "corners3D": box["bbox3D"],
                             "center_2D": list(box["center_2D"]), "bbox2D": [float(v) for v in boxes[i]]})
+            if out and planes is None and (args.show_points or args.segmentation == "rle" or args.show_masks):
+                planes = box_masks(cboxes, h, w, dev)
             if out and args.show_points:
-                if planes is None:
-                    planes = box_masks(cboxes, h, w, dev)
                 labels = vis.labels_from_masks(planes[kept_idx])
+            if out and args.segmentation == "rle":                               # encoded on the device: only the strings are read back
+                for rec, rle in zip(out, encode_rle(planes[kept_idx])):
+                    rec["segmentation"] = rle
         print("File: {} with {} dets ({} boxes at or above the threshold, {} not lifted)".format(im_name, len(out), len(cand), len(cand) - len(out)))
         with open(os.path.join(cfg.OUTPUT_DIR, im_name + "_dets.json"), "w") as f:
             json.dump({"K": K.tolist(), "detections": out}, f)
         write_views(im, K, out, kept_idx, cfg.OUTPUT_DIR, im_name, gpu_jpeg=bool(cfg.MODEL.AMD.get("GPU_JPEG_WRITE", True)),
                     depth=depth if out and args.show_points else None, labels=labels)
+        if args.show_masks:                                                      # the image under the kept instances' masks, in the boxes' colours
+            shown = overlay_masks(im, planes[kept_idx] if out else torch.zeros((0, h, w), dtype=torch.uint8, device=dev),
+                                  [vis.get_color(i) for i in kept_idx], alpha=0.5)
+            write_jpeg(os.path.join(cfg.OUTPUT_DIR, im_name + "_masks.jpg"), shown, quality=95, channel_order="BGR",
+                       use_device=bool(cfg.MODEL.AMD.get("GPU_JPEG_WRITE", True)))
         lap("views")
         if args.stage_times:
             print("stage_ms " + json.dumps({"image": im_name, **stages}))
@@ -253,6 +268,11 @@ def argument_parser():
     parser.add_argument("--stage-times", action="store_true", help=argparse.SUPPRESS)            # measurements: synchronise and print per-stage ms
     parser.add_argument("--show-points", default=True, action=argparse.BooleanOptionalAction,
                         help="draw the depth map as a point cloud under the boxes of the novel view, tinted per box")
+    parser.add_argument("--segmentation", choices=("none", "rle"), default="none",
+                        help="rle: each record of <name>_dets.json gets \"segmentation\": {size, counts}, its mask as a COCO RLE string "
+                             "(every mask source; encoded on the device)")
+    parser.add_argument("--show-masks", action="store_true",
+                        help="also write <name>_masks.jpg: the image with the kept instances' masks overlaid in the boxes' colours (alpha 0.5, contours)")
     parser.add_argument("opts", default=None, nargs=argparse.REMAINDER,
                         help="Modify config options by adding 'KEY VALUE' pairs at the end of the command.")
     return parser

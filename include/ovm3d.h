@@ -1012,6 +1012,84 @@ int ovm_render_panels(const OvmPanelsLayout* layout, const OvmPanelPrim* prims, 
                       const uint8_t* image, int64_t image_pitch, uint8_t* mosaic, int64_t mosaic_pitch, void* workspace,
                       int64_t workspace_bytes, ovm_stream_t stream);
 
+/* ---- Mask run-length encoding -----------------------------------------------------------------------------------------------
+ * COCO's RLE of binary masks, produced and consumed in HBM: only the strings cross PCIe. The rules are restated from pycocotools'
+ * maskApi.c (rleEncode, rleToString, rleFrString); pycocotools is not a dependency, the numpy restatement is
+ * tests/mask_rle_oracle.py.
+ *
+ * Counts. A plane is uint8 [H][W], row-major, nonzero = inside, and is scanned column-major: position p = x * H + y. counts are
+ * the lengths of the alternating runs along p, the first one a run of zeros: a plane whose first pixel is set starts with count
+ * 0, an all-zero plane is [H * W], an all-one plane [0, H * W]. A run continues across a column boundary (pixel (H - 1, x) and
+ * pixel (0, x + 1) are neighbours). A plane with T value changes along p (the change from the implied 0 in front of p = 0
+ * included) has T + 1 counts.
+ * String. For count i: x = cnts[i], x -= cnts[i - 2] when i > 2 (signed 64-bit); then repeat { c = x & 0x1f; x >>= 5
+ * (arithmetic); more = (c & 0x10) ? x != -1 : x != 0; if (more) c |= 0x20; emit the byte c + 48 } while more.
+ * The inverse (rleFrString) reads groups of 5 bits until one without 0x20, sign-extends when that last group has 0x10 set, and
+ * adds cnts[m - 2] when m > 2; it is host code of the Python layer (ovmono3d_amd.masks), the device takes and gives counts.
+ * H * W <= 2^31 - 1 (counts are uint32, as in COCO), so a difference of two counts lies within +-(2^31 - 1), which is 32 bits with
+ * its sign: OVM_MASK_RLE_MAX_CHARS = ceil(32 / 5) = 7 bytes per count at the most. max_bytes = 7 * max_runs always suffices.
+ *
+ * ovm_mask_rle_encode: masks device uint8, plane i at masks + i * plane_stride, row y at + y * row_pitch (bytes; any alignment,
+ * so a crop of a larger tensor is taken as it is). run_offsets / str_offsets: device int64 [n + 1], the first run / first string
+ * byte of each plane in counts_out (device uint32 [max_runs]) / string_out (device uint8 [max_bytes]); entry n is the total.
+ * counts_out may be null (no counts wanted), string_out and str_offsets may be null (no strings wanted; string_out without
+ * str_offsets is OVM_ERR_INVALID). status: device int32 [4] = code, total runs, total bytes, reserved (totals saturate at
+ * 2^31 - 1; run_offsets[n] and str_offsets[n] hold them in 64 bits).
+ * The runs and (when strings are wanted) the string bytes of every plane are always counted exactly, and run_offsets and
+ * str_offsets are always written. Runs and bytes are written only if the totals fit: total runs <= max_runs, else code =
+ * OVM_ERR_CAPACITY and nothing is written to counts_out or string_out (the string lengths then come from two more walks over the
+ * planes instead of the stored runs); total bytes <= max_bytes, else code = OVM_ERR_CAPACITY, counts_out written and string_out
+ * untouched. A caller reads status once and on OVM_ERR_CAPACITY calls once more with the stated totals: that call fits.
+ * Launches go on the caller's stream only; no read back, no allocation, no synchronisation. Workgroups of 64 columns x 4 bands
+ * of 64 rows read a plane coalesced in its own order (the value in front of pixel (y, x) is (y - 1, x), or (H - 1, x - 1) for
+ * y = 0: no transpose): pass 1 counts the value changes per (plane, column, band), one exclusive scan in column-major order ranks
+ * them, pass 2 stores the positions at their ranks; then per count its length, one 64-bit scan, the scatter. Integer arithmetic
+ * throughout: the output does not depend on scheduling.
+ *
+ * ovm_mask_rle_decode: counts device uint32 [total_runs] (16-byte aligned), run_offsets device int64 [n + 1] as above; plane i is
+ * written as 0 / 1 bytes into masks_out (same addressing as the encoder's input). A prefix sum of the counts, then each (column,
+ * band) finds the run of its first pixel by bisection and walks on; the value is run & 1. status: device int32 [4] = code, number
+ * of bad planes, index of the first bad plane or -1, reserved. A plane is bad when its counts do not sum to H * W or its offsets
+ * are not within 0 <= run_offsets[i] <= run_offsets[i + 1] <= total_runs (they are clamped to that before use): code =
+ * OVM_ERR_INVALID; pixels past the sum of a short plane are 0. Like ovm_jpeg_encode's out_len the word is device memory and the
+ * call does not wait for it.
+ *
+ * Refused before any device work: a null pointer (other than the optional ones), n < 1, H < 1, W < 1, H * W > 2^31 - 1,
+ * row_pitch < W, max_runs < 1, max_bytes < 1 with a string wanted, total_runs < 1, a workspace that is not 16-byte aligned
+ * (OVM_ERR_INVALID); a workspace below what the _workspace call states, or more than 2^24 - 1 workgroups of 64 columns x 256 rows (OVM_ERR_CAPACITY: split
+ * the planes over several calls).
+ * Scope: 8-bit planes. Not built: toBbox, merge and iou on RLEs (ovm_sam_mask_boxes and the evaluator cover boxes and IoU),
+ * polygons. */
+#define OVM_MASK_RLE_MAX_CHARS 7
+int ovm_mask_rle_encode_workspace(int32_t n, int32_t H, int32_t W, int64_t max_runs, int64_t max_bytes, int64_t* bytes);
+int ovm_mask_rle_encode(const uint8_t* masks, int64_t plane_stride, int64_t row_pitch, int32_t n, int32_t H, int32_t W,
+                        uint32_t* counts_out, int64_t max_runs, int64_t* run_offsets, uint8_t* string_out, int64_t max_bytes,
+                        int64_t* str_offsets, int32_t* status, void* workspace, int64_t workspace_bytes, ovm_stream_t stream);
+int ovm_mask_rle_decode_workspace(int32_t n, int32_t H, int32_t W, int64_t total_runs, int64_t* bytes);
+int ovm_mask_rle_decode(const uint32_t* counts, const int64_t* run_offsets, int64_t total_runs, int32_t n, int32_t H, int32_t W,
+                        uint8_t* masks_out, int64_t plane_stride, int64_t row_pitch, int32_t* status, void* workspace,
+                        int64_t workspace_bytes, ovm_stream_t stream);
+
+/* ---- Mask label map and mask picture ----------------------------------------------------------------------------------------
+ * A layer of this project (declared deviation: the reference draws no masks). Integer arithmetic only: the output is defined to
+ * the byte; the numpy restatement is tests/mask_overlay_oracle.py.
+ *
+ * ovm_mask_labels: labels_out[y][x] (device int32, row pitch label_pitch in elements) = the lowest plane index i with
+ * masks[i][y][x] != 0, or -1: what vis.labels_from_masks computes, without an n x H x W temporary (a lane stops at its first
+ * covering plane). masks as ovm_mask_rle_encode takes them; n = 0 (masks may then be null) gives -1 everywhere.
+ * ovm_render_mask_overlay: image and out are device uint8 [H][W][3] with row pitches in bytes (out may be image itself), colors
+ * device uint8 [n][3] in the image's channel order, alpha 0..255. With b = labels[y][x]:
+ *   b < 0 or b >= n                       out = image
+ *   contour: one of the 4-neighbours that lie inside the image has a label other than b (-1 included): out = colors[b]
+ *   otherwise                             out = (image * (255 - alpha) + colors[b] * alpha + 127) / 255 per channel, integer division
+ * The image border is not contour by itself. OVM_ERR_INVALID, nothing launched: a null pointer (colors may be null when n = 0),
+ * n < 0, H < 1, W < 1, a pitch below one row, alpha outside 0..255; OVM_ERR_CAPACITY: H > 262140. Stream-ordered. */
+int ovm_mask_labels(const uint8_t* masks, int64_t plane_stride, int64_t row_pitch, int32_t n, int32_t H, int32_t W,
+                    int32_t* labels_out, int64_t label_pitch, ovm_stream_t stream);
+int ovm_render_mask_overlay(const uint8_t* image, int64_t image_pitch, const int32_t* labels, int64_t label_pitch,
+                            const uint8_t* colors, int32_t n, int32_t alpha, uint8_t* out, int64_t out_pitch, int32_t H, int32_t W,
+                            ovm_stream_t stream);
+
 /* ---- OVMono3D-GEO -----------------------------------------------------------------------------------------------------------
  * The training-free baseline of the reference (tools/ovmono3d_geo.py:127-258): a 2D box's mask pixels are un-projected with a
  * metric depth map, the cloud is yaw-aligned by the first principal direction of its (x, z) columns, outliers are removed with

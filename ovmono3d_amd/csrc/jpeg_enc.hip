@@ -24,13 +24,13 @@
 // Kernels, all on the caller's stream, no read back to the host in between:
 //   1 jenc_color_kernel   colour, padding and downsampling: the three padded planes (16 / 8 byte stores per lane)
 //   2 jenc_fdct_kernel    one lane per block: FDCT, quantisation, dummy-block rule -> int16 planes in the decoder's layout
-//   3 jenc_bitlen_kernel  one lane per block in scan order: its bit length; jenc_scan_* : exclusive prefix sum (64-bit offsets)
+//   3 jenc_bitlen_kernel  one lane per block in scan order: its bit length; scan.hpp: exclusive prefix sum (64-bit offsets)
 //   4 jenc_pack_kernel    one lane per block: its codes at its bit offset. A lane owns every word strictly inside its bit range and
 //                         stores it; the first and the last word it shares with its neighbours, so those (zeroed by
 //                         jenc_zero_edges_kernel) are merged with atomicOr - integer OR is order-independent: deterministic.
 //                         (No LDS staging of a workgroup's run of blocks: the whole call is 0.10 ms of device time on a 1080 x 3000
 //                         picture, bound by its thirteen launches - profiles/jpeg_encode/README.md.)
-//   5 jenc_ffcount_kernel / jenc_scan_* / jenc_stuff_kernel: 0xFF bytes per 16-byte chunk, prefix sum, scatter with the stuffed
+//   5 jenc_ffcount_kernel / scan.hpp / jenc_stuff_kernel: 0xFF bytes per 16-byte chunk, prefix sum, scatter with the stuffed
 //                         zeros behind the header; padding bits, EOI and the file length (a device word)
 // Scope: 8-bit baseline (SOF0), three components YCbCr, luma sampling 2x2 or 1x1, quality 1..100, sizes 1..65535. Out of scope
 // (OVM_ERR_UNSUPPORTED / not offered): greyscale, 4:2:2 and 4:4:0, progressive and optimised-Huffman files, restart markers, custom
@@ -41,8 +41,12 @@
 
 #include "../../include/ovm3d.h"
 #include "jpeg_enc_host.hpp"
+#include "scan.hpp"
 
 namespace {
+
+using ovm_scan::kScanTile;
+using ovm_scan::launch_scan;
 
 struct EncDev {
   int width, height, hs;            // hs: luma sampling on both axes (1 or 2)
@@ -341,82 +345,6 @@ __global__ __launch_bounds__(64) void jenc_pack_kernel(const int16_t* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------
-// exclusive prefix sum: uint32 in[n] -> uint64 out[n + 1] (out[n] = the total), 2048 items per workgroup
-// ------------------------------------------------------------------------------------------------
-constexpr int kScanThreads = 256, kScanItems = 8, kScanTile = kScanThreads * kScanItems;
-
-// exclusive scan of one value per lane over the workgroup; *total = the sum
-__device__ __forceinline__ uint64_t wg_exclusive_scan(uint64_t v, uint64_t* total) {
-  __shared__ __attribute__((aligned(16))) uint64_t sh[kScanThreads];
-  const int t = threadIdx.x;
-  __syncthreads();
-  sh[t] = v;
-  __syncthreads();
-  for (int d = 1; d < kScanThreads; d <<= 1) {
-    const uint64_t add = t >= d ? sh[t - d] : 0;
-    __syncthreads();
-    sh[t] += add;
-    __syncthreads();
-  }
-  const uint64_t incl = sh[t];
-  *total = sh[kScanThreads - 1];
-  return incl - v;
-}
-
-__device__ __forceinline__ void scan_load(const uint32_t* __restrict__ in, int64_t n, int64_t i0, unsigned* v) {
-  if (i0 + kScanItems <= n) {
-    const uint4 a = *(const uint4*)(in + i0), b = *(const uint4*)(in + i0 + 4);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-  } else {
-#pragma unroll
-    for (int j = 0; j < kScanItems; ++j) v[j] = i0 + j < n ? in[i0 + j] : 0u;
-  }
-}
-
-__global__ __launch_bounds__(kScanThreads) void jenc_scan_reduce_kernel(const uint32_t* __restrict__ in, int64_t n, uint64_t* __restrict__ partial) {
-  const int64_t i0 = ((int64_t)blockIdx.x * kScanThreads + threadIdx.x) * kScanItems;
-  unsigned v[kScanItems];
-  scan_load(in, n, i0, v);
-  uint64_t sum = 0;
-#pragma unroll
-  for (int j = 0; j < kScanItems; ++j) sum += v[j];
-  uint64_t total;
-  wg_exclusive_scan(sum, &total);
-  if (threadIdx.x == 0) partial[blockIdx.x] = total;
-}
-
-// one workgroup: the partial sums become exclusive offsets in place; out_total = the grand total
-__global__ __launch_bounds__(kScanThreads) void jenc_scan_partials_kernel(uint64_t* __restrict__ partial, int np, uint64_t* __restrict__ out_total) {
-  uint64_t carry = 0;
-  for (int base = 0; base < np; base += kScanThreads) {
-    const int i = base + threadIdx.x;
-    const uint64_t v = i < np ? partial[i] : 0;
-    uint64_t total;
-    const uint64_t ex = wg_exclusive_scan(v, &total);
-    if (i < np) partial[i] = carry + ex;
-    carry += total;
-  }
-  if (threadIdx.x == 0) *out_total = carry;
-}
-
-__global__ __launch_bounds__(kScanThreads) void jenc_scan_apply_kernel(const uint32_t* __restrict__ in, int64_t n, const uint64_t* __restrict__ partial,
-                                                                       uint64_t* __restrict__ out) {
-  const int64_t i0 = ((int64_t)blockIdx.x * kScanThreads + threadIdx.x) * kScanItems;
-  unsigned v[kScanItems];
-  scan_load(in, n, i0, v);
-  uint64_t sum = 0;
-#pragma unroll
-  for (int j = 0; j < kScanItems; ++j) sum += v[j];
-  uint64_t total;
-  uint64_t run = partial[blockIdx.x] + wg_exclusive_scan(sum, &total);
-#pragma unroll
-  for (int j = 0; j < kScanItems; ++j) {
-    if (i0 + j < n) out[i0 + j] = run;
-    run += v[j];
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
 // 5: byte stuffing, header, EOI, length
 // ------------------------------------------------------------------------------------------------
 // chunk i of the unstuffed stream (16 bytes) with the 1-padding of the last byte applied; returns how many of its bytes exist
@@ -518,13 +446,6 @@ void fill_dev(const OvmJpegEncInfo& I, EncDev* J) {
 void launch_forward(const uint8_t* img, int64_t sy, int64_t sx, int64_t sc, const EncDev& J, uint8_t* planes, int16_t* coef, hipStream_t s) {
   hipLaunchKernelGGL(jenc_color_kernel, dim3((J.mcus_x + 63) / 64, J.mcus_y * 8), dim3(64), 0, s, img, sy, sx, sc, J, planes);
   hipLaunchKernelGGL(jenc_fdct_kernel, dim3((J.nblocks + 63) / 64), dim3(64), 0, s, (const uint8_t*)planes, J, coef);
-}
-
-void launch_scan(const uint32_t* in, int64_t n, uint64_t* partial, uint64_t* out, hipStream_t s) {
-  const int np = (int)((n + kScanTile - 1) / kScanTile);
-  hipLaunchKernelGGL(jenc_scan_reduce_kernel, dim3(np), dim3(kScanThreads), 0, s, in, n, partial);
-  hipLaunchKernelGGL(jenc_scan_partials_kernel, dim3(1), dim3(kScanThreads), 0, s, partial, np, out + n);
-  hipLaunchKernelGGL(jenc_scan_apply_kernel, dim3(np), dim3(kScanThreads), 0, s, in, n, (const uint64_t*)partial, out);
 }
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }

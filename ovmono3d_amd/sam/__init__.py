@@ -352,7 +352,8 @@ class SamAutomaticMaskGenerator:
     ``ovm_sam_auto_select``, include/ovm3d.h states the rules). The emitted masks are ``SamPredictor.predict_prompts``'s own planes.
 
     Not built and refused with ValueError: crops (``crop_n_layers > 0``), the small-region clean-up (``min_mask_region_area > 0``: it
-    needs connected components), RLE output modes. The crop-edge filter never removes a mask of the full-image crop. Parity with the
+    needs connected components), ``output_mode`` other than "binary_mask" (RLE records come from ``generate_rle``). The crop-edge filter
+    never removes a mask of the full-image crop. Parity with the
     segment_anything package is not pinned by a test (the package is not a dependency); DESIGN.md section 4.4."""
 
     def __init__(self, predictor: SamPredictor, points_per_side: Optional[int] = 32, points_per_batch: int = 64, pred_iou_thresh: float = 0.88,
@@ -435,20 +436,32 @@ class SamAutomaticMaskGenerator:
         return {"masks": masks, "boxes": boxes, "scores": kept[:, 0].contiguous().view(torch.float32), "stability": kept[:, 1].contiguous().view(torch.float32),
                 "points": pts[keep // 3], "areas": areas, "index": keep}
 
-    def generate(self, image, image_format: str = "RGB"):
-        """segment_anything's records, one dict per kept mask in NMS keep order: segmentation (bool [H, W], a device tensor), area,
-        bbox (XYWH of the inclusive box: w = xmax - xmin), predicted_iou, point_coords [[x, y]], stability_score, crop_box [0, 0, W, H]."""
-        out = self.generate_device(image, image_format)
+    def _records(self, out, segmentations):
         H, W = self.predictor.original_size
         f, pts = self.candidates()
-        seg = out["masks"].bool()
         records = []
         for i, c in enumerate(out["index"].cpu().numpy().tolist()):
             x0, y0, x1, y1 = (int(v) for v in f["box"][c])
-            records.append({"segmentation": seg[i], "area": int(f["area"][c]), "bbox": [x0, y0, x1 - x0, y1 - y0], "predicted_iou": float(f["iou"][c]),
+            records.append({"segmentation": segmentations[i], "area": int(f["area"][c]), "bbox": [x0, y0, x1 - x0, y1 - y0], "predicted_iou": float(f["iou"][c]),
                             "point_coords": [[float(pts[c // 3][0]), float(pts[c // 3][1])]], "stability_score": float(f["stability"][c]),
                             "crop_box": [0, 0, W, H]})
         return records
+
+    def generate(self, image, image_format: str = "RGB"):
+        """segment_anything's records, one dict per kept mask in NMS keep order: segmentation (bool [H, W], a device tensor), area,
+        bbox (XYWH of the inclusive box: w = xmax - xmin), predicted_iou, point_coords [[x, y]], stability_score, crop_box [0, 0, W, H].
+        (The constructor's ``output_mode`` takes "binary_mask" only; RLE records come from :meth:`generate_rle`.)"""
+        out = self.generate_device(image, image_format)
+        return self._records(out, out["masks"].bool())
+
+    def generate_rle(self, image, image_format: str = "RGB", compressed: bool = True):
+        """The records of :meth:`generate` with ``segmentation`` as the COCO RLE dict ``{"size": [H, W], "counts": str}`` (segment_anything's
+        "coco_rle"; ``compressed=False``: ``counts`` the list of run lengths, its "uncompressed_rle"). The masks are encoded on the
+        device (``ovmono3d_amd.masks.encode_rle``): no plane is copied to the host. The constructor's ``output_mode`` argument still
+        refuses everything but "binary_mask"; this method is the RLE route."""
+        from ..masks import encode_rle
+        out = self.generate_device(image, image_format)
+        return self._records(out, encode_rle(out["masks"], compressed=compressed))
 
 
 def build_sam(arch: str, checkpoint: Union[str, Dict[str, torch.Tensor], None], device: Optional[torch.device] = None,

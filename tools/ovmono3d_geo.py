@@ -19,7 +19,10 @@ Masks, one of:
                    of plane [2] as ``mask_input``.
   ``--mask-dir``   masks some other program wrote: ``<mask-dir>/<image_id>.npz`` with ``masks`` uint8 [n, H, W] (nonzero = inside)
                    and ``index`` int [n], the positions of the masked instances in the image's instance list. ``--dump-masks DIR``
-                   writes exactly these files from a ``--mask sam`` run.
+                   writes exactly these files from a ``--mask sam`` run. With ``--mask-format rle`` it writes
+                   ``<image_id>.rle.json`` = ``{"index": [...], "masks": [{"size": [H, W], "counts": str}, ...]}`` instead: COCO RLE,
+                   encoded on the device, so no plane is copied to the host. ``--mask-dir`` reads the ``.npz`` when it exists, else
+                   the ``.rle.json`` (decoded on the device); the 3D records are the same either way.
   ``--mask box``   the 2D box itself is the mask: the pixels ceil(x0) <= x < ceil(x1), ceil(y0) <= y < ceil(y1) of the xyxy box,
                    clipped to the image (the reference has no such mode; the rule is this project's).
 
@@ -103,9 +106,17 @@ def sam_masks(predictor, image_root, file_path, height, width, boxes_xyxy, bgr=N
     return predictor.predict_boxes(boxes_xyxy, mask_index=2)
 
 
-def dump_masks(mask_dir, image_id, positions, planes):
-    """The <image_id>.npz file load_masks reads."""
+def dump_masks(mask_dir, image_id, positions, planes, fmt="npz"):
+    """The <image_id>.npz file load_masks reads; fmt "rle": <image_id>.rle.json = {"index": [...], "masks": [COCO RLE, ...]} instead,
+    encoded on the device (ovmono3d_amd.masks.encode_rle): the planes stay there and only the strings are read back."""
     os.makedirs(mask_dir, exist_ok=True)
+    if fmt == "rle":
+        from ovmono3d_amd.masks import encode_rle
+        dev = torch.device("cuda", torch.cuda.current_device())
+        stack = torch.stack([p.to(dev) if isinstance(p, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(p)).to(dev) for p in planes])
+        with open(os.path.join(mask_dir, f"{image_id}.rle.json"), "w") as f:
+            json.dump({"index": [int(i) for i in positions], "masks": encode_rle(stack)}, f)
+        return
     planes = [p.cpu().numpy() if isinstance(p, torch.Tensor) else np.asarray(p) for p in planes]
     H, W = planes[0].shape
     np.savez_compressed(os.path.join(mask_dir, f"{image_id}.npz"), masks=np.stack(planes).astype(np.uint8).reshape(-1, H, W),
@@ -113,10 +124,23 @@ def dump_masks(mask_dir, image_id, positions, planes):
 
 
 def load_masks(mask_dir, image_id, height, width):
-    """{position in the instance list: uint8 [H, W]} of one image; empty when the image has no mask file."""
+    """{position in the instance list: uint8 [H, W]} of one image; empty when the image has no mask file. <image_id>.npz when it
+    exists (host arrays), else <image_id>.rle.json, decoded on the device (device tensors of 0 / 1)."""
     path = os.path.join(mask_dir, f"{image_id}.npz")
     if not os.path.exists(path):
-        return {}
+        path = os.path.join(mask_dir, f"{image_id}.rle.json")
+        if not os.path.exists(path):
+            return {}
+        from ovmono3d_amd.masks import decode_rle
+        with open(path) as f:
+            z = json.load(f)
+        index, records = z["index"], z["masks"]
+        if len(index) != len(records) or any(list(r["size"]) != [height, width] for r in records):
+            raise SystemExit(f"{path}: {len(records)} masks / {len(index)} index entries do not fit a {height} x {width} image")
+        if not records:
+            return {}
+        planes = decode_rle(records, torch.device("cuda", torch.cuda.current_device()))
+        return {int(i): planes[k] for k, i in enumerate(index)}
     z = np.load(path)
     masks, index = z["masks"], z["index"]
     if masks.ndim != 3 or tuple(masks.shape[1:]) != (height, width) or len(index) != len(masks):
@@ -183,7 +207,7 @@ def run(args):
                 boxes = np.asarray([xywh_to_xyxy(ins["bbox"]) for _, ins in cand], np.float64)
                 lifted = lift_image(depth, K, boxes, planes, params)
                 if args.dump_masks and planes is not None:
-                    dump_masks(args.dump_masks, rec["image_id"], [pos for pos, _ in cand], planes)
+                    dump_masks(args.dump_masks, rec["image_id"], [pos for pos, _ in cand], planes, args.mask_format)
                 for (pos, ins), box in zip(cand, lifted):
                     if box is None:
                         logger.warning("image %s: instance %d has no 3D box (empty mask, < 2 points, non-finite depth or a box outside "
@@ -235,6 +259,9 @@ def argument_parser():
                     help="--mask sam: N more passes per box with the previous pass's low-resolution logits as mask_input (default 0: the reference's single pass)")
     ap.add_argument("--image-root", default=None, help="directory the dataset's file_path entries are relative to (--mask sam)")
     ap.add_argument("--dump-masks", default=None, metavar="DIR", help="write the masks used as <DIR>/<image_id>.npz, the files --mask-dir reads")
+    ap.add_argument("--mask-format", choices=("npz", "rle"), default="npz",
+                    help="--dump-masks: npz (planes copied to the host and deflated) or rle (<image_id>.rle.json, COCO RLE encoded on the device); "
+                         "--mask-dir reads either")
     ap.add_argument("--score-threshold", type=float, default=0.30)
     ap.add_argument("--output", required=True, help=".pth (torch.save, as the reference) or .json")
     return ap
