@@ -429,7 +429,9 @@ int ovm_gdino_last_outputs(OvmGdino* g, const float** pred_logits, const float**
 /* tests: pin the two-stage top-k selection to the given device int32 [num_queries] (NULL: the network's own) */
 int ovm_gdino_set_force_topk(OvmGdino* g, const int32_t* idx_device);
 /* tests: copy an intermediate of the last forward ("bert_out", "text_features", "swin_stage1..3", "enc_vision", "enc_text",
- * "topk" (int32), "init_ref") into dst; returns the element count. name "launches": returns the kernel launches per forward. */
+ * "topk" (int32), "init_ref") into dst; returns the element count. name "launches": returns the kernel launches per forward
+ * (per image: with the caption cache, tune key gdino_text_cache, the caption's encoding is not among them); "text_launches": the
+ * launches the last forward call spent on encoding its caption, 0 when it was held; "text_entries": captions the handle holds. */
 int64_t ovm_gdino_debug_copy(OvmGdino* g, const char* name, void* dst, int64_t capacity_elems, ovm_stream_t stream);
 
 /* --- the whole path for one image as ONE call (SURVEY.md 8b `ovm_infer`): RCNN3D.inference with the text-prompted head, reference
@@ -621,6 +623,10 @@ int ovm_host_dec_chain_supported(int32_t D, int32_t heads, int32_t ffn, int32_t 
  *   gdino_enc_tap 0|1 (tests: plans built afterwards keep copies of encoder layer 0's out-projection rows, their split and the value |
  *   offsets projections' outputs for ovm_gdino_debug_copy "enc_pos|enc_vis0|enc_vis0_hi|enc_vis0_lo|enc_voff0|enc_P0", with gdino_enc_fold 0
  *   "enc_val0|enc_ow0" for the last two; default 0),
+ *   gdino_text_cache n (the detector's caption cache: what depends on the caption and the weights alone - BERT, the text projection and
+ *   encoder layer 0's text norm and text projection - is computed once per (token ids, position ids), outside the per-image graph, and the
+ *   handle keeps the n most recently used captions' results, which all plans of a caption share; every ovm_tune_set call retires the
+ *   results made before it; 0 = inside every forward as before, the same bits; default 16; read when a plan is built),
  *   attn_tail_split 0|1 (attention's leftover queries split over 16 key slices + combine kernel; default 1), attn_prio n (experiment:
  *   s_setprio inside the two-wave-group attention kernel; default 0), gemm256_ksplit n (experiment: split-K hint of the 256 x 256 kernel for
  *   proj / fc2; default 0 = off, measured slower), glin_wpe 2|4 (experiment: workgroups per CU the small fp32-A GEMM is compiled for; default 2),

@@ -10,8 +10,13 @@
 // merging, shift masks, sine position embeddings, reference grids, text masks - is built on the host once per *plan* and uploaded
 // (gdino_plan.hip). A plan also owns the activation arena (sized by a dry pass over the same code) and every scratch buffer, so nothing
 // is allocated, freed or re-sized on the hot path, and the whole forward is captured into ONE HIP graph per plan, replayed afterwards.
+// What depends on the caption and the weights alone - BERT, the text projection, encoder layer 0's text norm and text projection - is
+// computed once per caption, outside the graph (encode_caption -> a TextEntry the handle keeps and the caption's plans co-own,
+// gdino_model.hpp); the per-image forward starts at the Swin backbone and reads the entry. ovm_tune_set gdino_text_cache 0 puts
+// these ops back into every forward (text_encoder, fusion_layer), the same kernels on the same operands in the same order.
 // This file: forward_impl, one stage function per part of the network, and the extern "C" entry points (types: gdino_model.hpp;
 // weights: gdino_load.hip).
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -23,7 +28,10 @@ using namespace ovm;
 using namespace ovm::gdino;
 
 namespace ovm {
-GdinoTune g_gdino_tune = {1, 1, 0, 1, 1, 1, 0, 0, 0}; // branches, dec_chain, ffn_split, swin_fused, gemm256, mlp_fused, swin_tap, enc_fold, enc_tap
+GdinoTune g_gdino_tune = {1, 1, 0, 1, 1, 1, 0, 0, 0, 16}; // branches, dec_chain, ffn_split, swin_fused, gemm256, mlp_fused, swin_tap, enc_fold, enc_tap, text_cache
+namespace { std::atomic<unsigned long> g_tune_generation{0}; }
+unsigned long tune_generation() { return g_tune_generation.load(); }
+void bump_tune_generation() { ++g_tune_generation; }
 void set_gdino_branches(int v) { g_gdino_tune.branches = v ? 1 : 0; }       // engines created afterwards
 void set_gdino_dec_chain(int v) { g_gdino_tune.dec_chain = v ? 1 : 0; }     // this and the ones below: plans built afterwards
 void set_gdino_ffn_split(int v) { g_gdino_tune.ffn_split = v ? 1 : 0; }
@@ -33,6 +41,7 @@ void set_gdino_gemm256(int v) { g_gdino_tune.gemm256 = v ? 1 : 0; }
 void set_gdino_mlp_fused(int v) { g_gdino_tune.mlp_fused = v < 0 ? 0 : (v > 2 ? 2 : v); }
 void set_gdino_enc_fold(int v) { g_gdino_tune.enc_fold = (v < 0 || v > 3) ? 0 : v; }
 void set_gdino_enc_tap(int v) { g_gdino_tune.enc_tap = v ? 1 : 0; }
+void set_gdino_text_cache(int v) { g_gdino_tune.text_cache = v < 0 ? 0 : (v > 4096 ? 4096 : v); }
 }  // namespace ovm
 
 namespace ovm {
@@ -86,12 +95,11 @@ void deform(Run& r, const float* value, int ldv, const float* ow, int ldow, cons
 }
 
 // =============================== text: BERT + projection ===============================
-// (text branch: runs beside the Swin backbone and the neck, joined before the encoder)
-void text_encoder(Run& r, State& st) {
+// BERT over the caption into tx [T][bertD], then the text projection into text0 [T][d_model] (null: taken from the arena, after
+// BERT's scratch); returns text0. Scratch comes from the run's arena and stays allocated.
+float* bert_chain(Run& r, float* tx, float* text0) {
   OvmGdino* g = r.g; Plan* pl = r.pl;
   const int T = pl->T, D = g->cfg.d_model, BD = g->bertD, BH = g->cfg.bert_heads;
-  float* tx = st.tx = r.f32((size_t)T * BD);
-  r.fork(); r.on_text();
   if (r.go()) r.chk(launch_bert_embed(g->word, g->posemb, g->typemb, pl->d_ids, pl->d_pids, T, BD, g->emb_ln.g, g->emb_ln.b, 1e-12f, tx, r.s), "bert_embed");
   float* qkv = r.f32((size_t)T * 3 * BD);
   float* ctx = r.f32((size_t)T * BD);
@@ -106,9 +114,25 @@ void text_encoder(Run& r, State& st) {
     r.lin(hbuf, nullptr, ly.fi.N, T, ly.fo, 0, nullptr, 0, a, BD);
     r.ln(a, T, BD, ly.oln, 1e-12f, tx, tx);
   }
-  r.tap("bert_out", tx, (int64_t)T * BD);
-  st.text0 = r.f32((size_t)T * D);
-  r.lin(tx, nullptr, BD, T, g->text_proj, 0, nullptr, 0, st.text0, D);
+  if (!text0) text0 = r.f32((size_t)T * D);
+  r.lin(tx, nullptr, BD, T, g->text_proj, 0, nullptr, 0, text0, D);
+  return text0;
+}
+
+// With a caption entry (tune.text_cache): nothing is launched, the forward reads the entry. Otherwise the text branch: BERT and the
+// projection run beside the Swin backbone and the neck, joined before the encoder.
+void text_encoder(Run& r, State& st) {
+  OvmGdino* g = r.g; Plan* pl = r.pl;
+  const int T = pl->T, D = g->cfg.d_model, BD = g->bertD;
+  if (pl->tune.text_cache) {
+    if (!pl->text && !r.dry) { r.fail(OVM_ERR_INVALID, "text_encoder: the plan has no caption entry"); return; }
+    st.tx = pl->text ? pl->text->tx : nullptr; st.text0 = pl->text ? pl->text->text0 : nullptr;
+  } else {
+    st.tx = r.f32((size_t)T * BD);
+    r.fork(); r.on_text();
+    st.text0 = bert_chain(r, st.tx, nullptr);
+  }
+  r.tap("bert_out", st.tx, (int64_t)T * BD);
   r.tap("text_features", st.text0, (int64_t)T * D);
   st.text = r.f32((size_t)T * D);                         // encoder output (the input above stays intact for the debug tap)
   r.on_image();
@@ -278,17 +302,19 @@ struct EncBufs {
   bool ffn_fused;                                          // the layers' FFN on the fused route (ff is not allocated then)
 };
 
-// bi-directional image <-> text attention; leaves the two contexts (cv, ct) and the normalised inputs (v, t) for the halves below
-void fusion_layer(Run& r, const EncLayer& ly, EncBufs& b, const float* vis_in, const float* text_in) {
+// bi-directional image <-> text attention; leaves the two contexts (cv, ct) and the normalised inputs (v, t) for the halves below.
+// `te`: layer 0 with a caption entry - its normalised text rows and their projection are the entry's (text_in is text0), not computed here
+void fusion_layer(Run& r, const EncLayer& ly, EncBufs& b, const float* vis_in, const float* text_in, const TextEntry* te) {
   const OvmGdinoConfig& c = r.g->cfg;
   const int D = c.d_model, T = r.pl->T, S = r.pl->S, HF = c.heads / 2, E = c.ffn_dim / 2, dhf = E / HF;
   r.ln(vis_in, S, D, ly.lnv, c.eps, nullptr, b.v, &b.vsp);
-  r.ln(text_in, T, D, ly.lnt, c.eps, nullptr, b.t);
+  if (!te) r.ln(text_in, T, D, ly.lnt, c.eps, nullptr, b.t);
   { GemmParams q = r.gp(b.vsp, S, ly.vqv); q.C = b.qvv; q.ldc = 2 * E; r.gemm(q, EPI_STORE); }
-  r.lin(b.t, nullptr, D, T, ly.tkv, 0, nullptr, 0, b.tkv, 2 * E);
+  if (!te) r.lin(b.t, nullptr, D, T, ly.tkv, 0, nullptr, 0, b.tkv, 2 * E);
   if (!r.go()) return;
+  const float* tkv = te ? te->tkv0 : b.tkv;
   BiAttnParams a; memset(&a, 0, sizeof(a));
-  a.qv = b.qvv; a.ldq = 2 * E; a.kt = b.tkv; a.ldk = 2 * E; a.vv = b.qvv + E; a.ldvv = 2 * E; a.vt = b.tkv + E; a.ldvt = 2 * E;
+  a.qv = b.qvv; a.ldq = 2 * E; a.kt = tkv; a.ldk = 2 * E; a.vv = b.qvv + E; a.ldvv = 2 * E; a.vt = tkv + E; a.ldvt = 2 * E;
   a.S = S; a.T = T; a.H = HF; a.dh = dhf; a.scale = 1.0f / sqrtf((float)dhf);
   a.cv_hi = b.cv.hi; a.cv_lo = b.cv.lo; a.ldcv = b.cv.ld; a.ct = b.ct; a.sc = b.sc; a.stat = b.stat; a.part = b.part; a.chunk = b.bw.chunk; a.nchunk = b.bw.nchunk;
   if (b.bml) { a.bm = b.bml; a.bl = b.bml + b.bw.ml; }
@@ -296,11 +322,13 @@ void fusion_layer(Run& r, const EncLayer& ly, EncBufs& b, const float* vis_in, c
 }
 
 // text half of a layer, on the text branch: the fusion's gated text output, then the text enhancer -> text
-void text_enhancer(Run& r, const EncLayer& ly, EncBufs& b, float* text) {
+// `t_in`: the layer's normalised text input, the shortcut of the gated output (b.t, or the caption entry's rows for layer 0; b.t is
+// rewritten further down, the entry never is)
+void text_enhancer(Run& r, const EncLayer& ly, EncBufs& b, float* text, const float* t_in) {
   const OvmGdinoConfig& c = r.g->cfg;
   const int D = c.d_model, T = r.pl->T, E = c.ffn_dim / 2;
   r.fork(); r.on_text();
-  r.lin(b.ct, nullptr, E, T, ly.ot, 0, b.t, D, b.text2, D);
+  r.lin(b.ct, nullptr, E, T, ly.ot, 0, t_in, D, b.text2, D);
   r.lin(b.text2, r.pl->text_pos, D, T, ly.te.qk, 0, nullptr, 0, b.tqk, 2 * D);
   r.lin(b.text2, nullptr, D, T, ly.te.v, 0, nullptr, 0, b.tv, D);
   mha_core(r, b.tqk, 2 * D, b.tqk + D, 2 * D, b.tv, D, T, T, ly.te.heads, D, r.pl->text_bias, T, b.tctx, D);
@@ -366,7 +394,7 @@ void encoder(Run& r, State& st) {
   const OvmGdinoConfig& c = r.g->cfg;
   const int D = c.d_model, T = r.pl->T, S = r.pl->S, HF = c.heads / 2, E = c.ffn_dim / 2, dhf = E / HF;
   const int NOW = now_cols(c), NE = (int)r.g->enc.size();
-  r.join();                                               // text features and image features meet in the fusion layers
+  if (!r.pl->tune.text_cache) r.join();                   // text features and image features meet in the fusion layers (a caption entry: no text branch was forked so far)
   EncBufs b;
   // what outlives the encoder's scratch: the rows the last layer's final norm writes for the decoder's value projection, test copies
   if (r.pl->tune.prod_split() && NE > 0) st.dec_vsp = r.split_for256((size_t)S, D);
@@ -408,11 +436,13 @@ void encoder(Run& r, State& st) {
   const float* vis_in = st.vis0; const float* text_in = st.text0;
   for (int li = 0; li < NE; ++li) {
     const EncLayer& ly = r.g->enc[li];
-    fusion_layer(r, ly, b, vis_in, text_in);
+    const TextEntry* te = (li == 0 && r.pl->tune.text_cache) ? r.pl->text.get() : nullptr;
+    if (li == 0 && r.pl->tune.text_cache && !te && !r.dry) { r.fail(OVM_ERR_INVALID, "encoder: the plan has no caption entry"); return; }
+    fusion_layer(r, ly, b, vis_in, text_in, te);
     vis_in = st.vis; text_in = st.text;
     // the two halves of the layer from here on touch disjoint buffers: text side (ot, text enhancer -> text) on the text
     // branch, image side (ov, deformable self-attention, FFN -> vis) on the main one; joined at the end of the layer
-    text_enhancer(r, ly, b, st.text);
+    text_enhancer(r, ly, b, st.text, te ? te->t0 : b.t);
     deformable_layer(r, ly, b, st.vis, li, (li == NE - 1 && st.dec_vsp.hi) ? &st.dec_vsp : nullptr);
     r.join();
   }
@@ -645,7 +675,69 @@ void heads(Run& r, State& st) {
   if (r.go()) r.chk(launch_box_refine(d.delta, 4, st.last_ref, 1e-5f, pl->out_boxes, Q, s), "box_refine");
 }
 
+// what a caption entry holds, into its buffers: the text branch's BERT and projection, then layer 0's text norm and projection of
+// the main branch - the kernels, operands, order and workspace slices they have inside a forward without the cache
+void caption_ops(Run& r, TextEntry& e) {
+  OvmGdino* g = r.g;
+  const OvmGdinoConfig& c = g->cfg;
+  r.ws_text();
+  bert_chain(r, e.tx, e.text0);
+  r.ws_image();
+  if (g->enc.empty()) return;
+  const EncLayer& ly = g->enc[0];
+  r.ln(e.text0, e.T, c.d_model, ly.lnt, c.eps, nullptr, e.t0);
+  r.lin(e.t0, nullptr, c.d_model, e.T, ly.tkv, 0, nullptr, 0, e.tkv0, ly.tkv.N);
+}
+
+// Encodes the plan's caption into a new entry: eagerly on `s`, outside any graph, scratch in a temporary arena. The stream is drained
+// before the entry is returned, so every later forward, on whichever stream, reads finished buffers (a plan build synchronises the
+// device several times already: once more per new caption costs nothing that matters).
+int encode_caption(OvmGdino* g, Plan* pl, hipStream_t s, std::shared_ptr<TextEntry>* out) {
+  const OvmGdinoConfig& c = g->cfg;
+  auto e = std::make_shared<TextEntry>();
+  e->ids = pl->ids; e->pids = pl->pids; e->gen = tune_generation(); e->T = pl->T;
+  const size_t T = (size_t)pl->T;
+  const size_t n[4] = {T * g->bertD, T * c.d_model, T * c.d_model, T * c.ffn_dim};
+  float** dst[4] = {&e->tx, &e->text0, &e->t0, &e->tkv0};
+  for (int i = 0; i < 4; ++i) {
+    OVM_HIP(g, hipMalloc((void**)dst[i], n[i] * sizeof(float)));
+    e->bytes += n[i] * sizeof(float);
+  }
+  Run dry{g, pl, s, true};
+  dry.init_streams();
+  caption_ops(dry, *e);
+  if (dry.rc) return dry.rc;
+  void* tmp = nullptr;
+  OVM_HIP(g, hipMalloc(&tmp, dry.peak + 4096));
+  Run run{g, pl, s, false};
+  run.abase = (char*)tmp; run.acap = dry.peak + 4096;
+  run.s_main = s;                                        // one stream: no init_streams(), no fork
+  caption_ops(run, *e);
+  const hipError_t he = hipStreamSynchronize(s);
+  (void)hipFree(tmp);
+  if (run.rc) return run.rc;
+  OVM_HIP(g, he);
+  e->launches = run.launches;
+  *out = e;
+  return OVM_OK;
+}
+
 }  // namespace
+
+int acquire_text(OvmGdino* g, Plan* pl, hipStream_t s, long* launches) {
+  *launches = 0;
+  if (!pl->tune.text_cache) return OVM_OK;
+  const unsigned long gen = tune_generation();
+  if (pl->text && pl->text->gen == gen) return OVM_OK;
+  std::shared_ptr<TextEntry> e = find_text(g, pl->ids, pl->pids, gen);
+  if (!e) {
+    OVM_TRY(g, encode_caption(g, pl, s, &e));
+    *launches = e->launches;
+    keep_text(g, e, pl->tune.text_cache);
+  }
+  pl->text = e;
+  return OVM_OK;
+}
 
 // One pass over a plan, run three ways over the same code: dry (sizes the arena), eager, under stream capture. Which kernels a pass
 // launches and what it allocates depends on the handle, the plan and the plan's tune knobs alone.
@@ -708,6 +800,7 @@ int ovm_gdino_destroy(OvmGdino* g) {
   (void)hipSetDevice(g->device);
   (void)hipDeviceSynchronize();
   for (Plan* p : g->plans) delete p;
+  g->texts.clear();
   g->free_all();
   if (g->aux) (void)hipStreamDestroy(g->aux);
   if (g->ev_fork) (void)hipEventDestroy(g->ev_fork);
@@ -738,10 +831,13 @@ int ovm_gdino_forward(OvmGdino* g, const OvmImage* image, const int32_t* token_i
   std::vector<int> ids(token_ids, token_ids + ntok), pids;
   if (position_ids) pids.assign(position_ids, position_ids + ntok);
   Plan* pl = find_plan(g, H, W, ids, pids);
+  long text_launches = 0;
   if (!pl) {
     OVM_TRY(g, build_plan(g, H, W, ids, pids, &pl));
+    int r = acquire_text(g, pl, s, &text_launches);       // the caption's entry: held already, or encoded here (its scratch is not the arena's)
+    if (r) { delete pl; return r; }
     Run dry{g, pl, s, true};
-    int r = forward_impl(dry);
+    r = forward_impl(dry);
     if (r) { delete pl; return r; }
     pl->arena_cap = dry.peak + 4096;
     void* q = nullptr;
@@ -756,12 +852,17 @@ int ovm_gdino_forward(OvmGdino* g, const OvmImage* image, const int32_t* token_i
   if (pl->exec) {
     OVM_HIP(g, hipGraphLaunch(pl->exec, s));
   } else {
+    // an eager pass launches under the tune settings of now: so must the caption entry it reads have been (a graph keeps both as captured)
+    long again = 0;
+    OVM_TRY(g, acquire_text(g, pl, s, &again));
+    text_launches += again;
     Run run{g, pl, s, false};
     OVM_TRY(g, forward_impl(run));
     pl->launches = run.launches; pl->mlp_fused_sites = run.mlp_sites;
     if (g->graphs_enabled) capture_plan(g, pl, s);
   }
   g->launches_last = pl->launches;
+  g->text_launches_last = text_launches;
   const size_t nl = (size_t)g->cfg.num_queries * g->cfg.max_text_len;
   if (pred_logits) OVM_HIP(g, hipMemcpyAsync(pred_logits, pl->out_logits, nl * sizeof(float), hipMemcpyDeviceToDevice, s));
   if (pred_boxes) OVM_HIP(g, hipMemcpyAsync(pred_boxes, pl->out_boxes, (size_t)g->cfg.num_queries * 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -795,7 +896,9 @@ int64_t ovm_gdino_debug_copy(OvmGdino* g, const char* name, void* dst, int64_t c
   if (std::string(name) == "launches") return g->launches_last;
   if (std::string(name) == "mlp_fused_sites") return g->last->mlp_fused_sites;            // MLPs of the last plan's forward on the fused route
   if (std::string(name) == "plans") return (int64_t)g->plans.size();                      // plan-cache occupancy (tests, bench)
-  if (std::string(name) == "plan_bytes") { int64_t b = 0; for (Plan* q : g->plans) b += (int64_t)q->bytes; return b; }
+  if (std::string(name) == "plan_bytes") { int64_t b = (int64_t)text_bytes(g, nullptr); for (Plan* q : g->plans) b += (int64_t)q->bytes; return b; }   // caption entries once, not per plan
+  if (std::string(name) == "text_launches") return g->text_launches_last;                 // op launches the last forward call spent encoding its caption (0: held)
+  if (std::string(name) == "text_entries") return (int64_t)g->texts.size();               // caption-cache occupancy
   auto it = g->last->taps.find(name);
   if (it == g->last->taps.end()) { g->err = std::string("unknown debug tensor ") + name; return OVM_ERR_INVALID; }
   if (it->second.second > capacity_elems) return OVM_ERR_CAPACITY;

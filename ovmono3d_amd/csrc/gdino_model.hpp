@@ -8,6 +8,7 @@
 #include <cstring>
 #include <list>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 #include "../../include/ovm3d.h"
@@ -41,10 +42,16 @@ struct GdinoTune {
   int enc_tap;         // tests: keeps copies of encoder layer 0's out-projection rows, their split and the value | offsets projections'
                        // outputs for ovm_gdino_debug_copy "enc_pos|enc_vis0|enc_vis0_hi|enc_vis0_lo|enc_voff0|enc_P0" (enc_fold 0: "enc_val0|enc_ow0"
                        // for the last two); costs arena and four copies per forward, so 0 outside tests
+  int text_cache;      // caption cache (TextEntry below): n > 0 = the handle keeps the n most recently used captions' encodings and a plan's
+                       // forward reads them; 0 = BERT, the text projection and layer 0's text norm / projection inside every forward
   bool fold() const { return enc_fold == 1 || enc_fold == 2; }
   bool prod_split() const { return enc_fold == 1 || enc_fold == 3; }
 };
 extern GdinoTune g_gdino_tune;
+// Advanced by every ovm_tune_set call. The glin_* and split-K knobs change the summation order of the small GEMMs, so what was
+// computed under one setting (a TextEntry) never serves a forward issued under another.
+unsigned long tune_generation();
+void bump_tune_generation();
 
 namespace gdino {
 
@@ -68,6 +75,25 @@ struct EncLayer {
 struct DecLayer { Mha sa, ca; MsdaW msda; Ln ln1, ln2, ln3, ln4; Lin fc1, fc2; };
 
 struct Plan;
+
+// Everything of a forward that depends on the caption and the weights alone, computed once (encode_caption, gdino.hip) and read by
+// every plan of that caption: BERT's output, the projected text features, and encoder layer 0's normalised text rows and their
+// [text_proj | values_text_proj] projection. Key: (token ids, position ids as the caller gave them, tune generation).
+// Lifetime: the handle's list (Model::texts, most recently used first, at most GdinoTune::text_cache entries) and every plan whose
+// forward - and captured graph - points into the buffers hold a shared_ptr each, so eviction from the list or of a plan never frees
+// memory a live graph reads. Written by encode_caption alone, which drains its stream before the entry is handed out: read-only
+// afterwards, on any stream.
+struct TextEntry {
+  std::vector<int> ids, pids;
+  unsigned long gen = 0;
+  int T = 0;
+  float *tx = nullptr, *text0 = nullptr, *t0 = nullptr, *tkv0 = nullptr;   // [T][bertD], [T][d_model], [T][d_model], [T][ffn_dim]
+  size_t bytes = 0;
+  long launches = 0;                          // op launches the encoding took (ovm_gdino_debug_copy "text_launches" of the call that encoded)
+  ~TextEntry() {
+    for (float* p : {tx, text0, t0, tkv0}) if (p) (void)hipFree(p);
+  }
+};
 
 struct Model : Loader {
   OvmGdinoConfig cfg;
@@ -93,6 +119,9 @@ struct Model : Loader {
   const int* force_topk = nullptr;            // device int32 [num_queries] (tests: pin the two-stage selection)
   int graphs_enabled = 1;
   long launches_last = 0;
+  // ---- caption cache
+  std::list<std::shared_ptr<TextEntry>> texts;  // most recently used first
+  long text_launches_last = 0;                // op launches the last forward call spent on encoding its caption (0: it was held)
   // ---- second branch of the forward: the text side (BERT, the text enhancers) has no data dependence on the image side (Swin,
   // deformable attention) between their joins, so it runs on a stream of its own - in a captured plan two branches of the graph
   int branches = 1;                           // GdinoTune::branches when the handle was created
@@ -129,6 +158,7 @@ struct Plan {
   std::vector<void*> allocs; size_t bytes = 0;      // device memory this plan holds (the plan cache's budget counts it)
   // text
   int* d_ids = nullptr; int* d_pids = nullptr; float* text_bias = nullptr; float* text_pos = nullptr;
+  std::shared_ptr<TextEntry> text;                  // tune.text_cache > 0: the caption's encoding this plan's forward and graph read (co-owned)
   // swin
   int Hp = 0, Wp = 0; int* pe_map = nullptr;
   std::vector<StageGeo> geo;
@@ -162,6 +192,11 @@ struct Plan {
 int build_plan(OvmGdino* g, int H, int W, const std::vector<int>& ids, const std::vector<int>& pids, Plan** out);
 Plan* find_plan(OvmGdino* g, int H, int W, const std::vector<int>& ids, const std::vector<int>& pids);   // taken out of the cache, or null
 void evict_plans(OvmGdino* g, const Plan* incoming);
+// caption cache: the held entry of this key (moved to the front of the handle's list) or null; keep_text puts a freshly encoded one
+// in front and drops the least recently used ones beyond `cap`; text_bytes = device memory of every live entry, each counted once
+std::shared_ptr<TextEntry> find_text(OvmGdino* g, const std::vector<int>& ids, const std::vector<int>& pids, unsigned long gen);
+void keep_text(OvmGdino* g, const std::shared_ptr<TextEntry>& e, int cap);
+size_t text_bytes(const OvmGdino* g, const Plan* incoming);
 void capture_plan(OvmGdino* g, Plan* pl, hipStream_t s);
 
 // split-K workspace of the text branch (tail of the plan's workspace): its largest user is BERT's output projection at the
@@ -174,6 +209,7 @@ constexpr size_t kAuxWs = (size_t)16 << 20;
 struct Run {
   OvmGdino* g; Plan* pl; hipStream_t s; bool dry;
   size_t off = 0, peak = 0;
+  char* abase = nullptr; size_t acap = 0;        // an arena of the caller's in place of the plan's (encode_caption's temporary)
   long launches = 0;
   int mlp_sites = 0;                             // MLPs on the fused route so far
   int rc = OVM_OK;
@@ -190,6 +226,14 @@ struct Run {
   }
   void on_text() { if (two()) { s = g->aux; ws = (float*)((char*)pl->gemm_ws + (pl->gemm_ws_cap - kAuxWs)); ws_cap = kAuxWs; } }
   void on_image() { if (two()) { s = s_main; ws = pl->gemm_ws; ws_cap = pl->gemm_ws_cap - kAuxWs; } }
+  // the branches' workspace slices without their streams: encode_caption issues both branches' caption ops on one stream and gives
+  // each the slice - hence the split-K choice - it has inside a forward
+  bool sliced() const { return g->branches && g->aux; }
+  void ws_text() {
+    if (sliced()) { ws = (float*)((char*)pl->gemm_ws + (pl->gemm_ws_cap - kAuxWs)); ws_cap = kAuxWs; }
+    else ws_image();
+  }
+  void ws_image() { ws = pl->gemm_ws; ws_cap = sliced() ? pl->gemm_ws_cap - kAuxWs : pl->gemm_ws_cap; }
   void join() {
     if (!two()) return;
     on_image();
@@ -199,10 +243,11 @@ struct Run {
 
   void* alloc(size_t bytes) {
     off = (off + 255) & ~(size_t)255;
-    void* p = dry ? (void*)(uintptr_t)(0x1000 + off) : (void*)(pl->arena + off);
+    char* base = abase ? abase : pl->arena;
+    void* p = dry ? (void*)(uintptr_t)(0x1000 + off) : (void*)(base + off);
     off += bytes;
     if (off > peak) peak = off;
-    if (!dry && off > pl->arena_cap) { fail(OVM_ERR_CAPACITY, "arena overflow"); return pl->arena; }
+    if (!dry && off > (abase ? acap : pl->arena_cap)) { fail(OVM_ERR_CAPACITY, "arena overflow"); return base; }
     return p;
   }
   float* f32(size_t n) { return (float*)alloc(n * sizeof(float)); }
@@ -309,6 +354,9 @@ struct Run {
 
 // gdino.hip
 int forward_impl(Run& r);
+// tune.text_cache > 0: gives the plan the entry of its caption under the current tune generation - the held one, or a new one encoded
+// here, eagerly on `s` (drained before it returns) and outside any graph. *launches: what this call spent on encoding (0: held).
+int acquire_text(OvmGdino* g, Plan* pl, hipStream_t s, long* launches);
 
 }  // namespace gdino
 }  // namespace ovm

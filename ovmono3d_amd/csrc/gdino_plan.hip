@@ -2,8 +2,11 @@
 // patch merging, shift masks, sine position embeddings, reference grids, text masks - is built on the host once per plan and uploaded
 // (build_plan), with the scratch a forward needs and the tune knobs it will run under. The handle keeps its plans in a least recently
 // used cache (find_plan, evict_plans); a plan's forward is captured into one HIP graph after its first run (capture_plan).
+// What depends on the caption and the weights alone - the text encoder's output - is not a plan's but a TextEntry's, shared by
+// all plans of that caption (find_text, keep_text).
 #include <cmath>
 #include <memory>
+#include <set>
 #include "gdino_model.hpp"
 
 namespace ovm {
@@ -293,12 +296,39 @@ Plan* find_plan(OvmGdino* g, int H, int W, const std::vector<int>& ids, const st
   return nullptr;
 }
 
+std::shared_ptr<TextEntry> find_text(OvmGdino* g, const std::vector<int>& ids, const std::vector<int>& pids, unsigned long gen) {
+  for (auto it = g->texts.begin(); it != g->texts.end(); ++it) {
+    if ((*it)->gen == gen && (*it)->ids == ids && (*it)->pids == pids) {
+      std::shared_ptr<TextEntry> e = *it;
+      g->texts.erase(it); g->texts.push_front(e);
+      return e;
+    }
+  }
+  return nullptr;
+}
+
+// Entries that leave the list live on while a plan holds them; the last owner's release frees the buffers (hipFree waits for the device).
+void keep_text(OvmGdino* g, const std::shared_ptr<TextEntry>& e, int cap) {
+  g->texts.push_front(e);
+  while ((int)g->texts.size() > (cap > 1 ? cap : 1)) g->texts.pop_back();
+}
+
+size_t text_bytes(const OvmGdino* g, const Plan* incoming) {
+  std::set<const TextEntry*> seen;
+  size_t b = 0;
+  auto add = [&](const std::shared_ptr<TextEntry>& e) { if (e && seen.insert(e.get()).second) b += e->bytes; };
+  for (const auto& e : g->texts) add(e);
+  for (const Plan* q : g->plans) add(q->text);
+  if (incoming) add(incoming->text);
+  return b;
+}
+
 // Least recently used plans go when the count or - what matters on a dataset with many aspect ratios - the bytes they hold
 // together with the incoming plan exceed the configured bounds (defaults: 128 plans, 32 GiB of the 288 GB).
 void evict_plans(OvmGdino* g, const Plan* incoming) {
   const int maxp = g->cfg.max_plans > 0 ? g->cfg.max_plans : 128;
   const size_t budget = (size_t)(g->cfg.plan_budget_mb > 0 ? g->cfg.plan_budget_mb : 32768) << 20;
-  size_t held = incoming->bytes;
+  size_t held = incoming->bytes + text_bytes(g, incoming);      // caption entries once (they are small; an evicted plan's may stay held by the handle)
   for (Plan* q : g->plans) held += q->bytes;
   while (!g->plans.empty() && ((int)g->plans.size() >= maxp || held > budget)) {
     (void)hipDeviceSynchronize();

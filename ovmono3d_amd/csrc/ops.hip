@@ -58,7 +58,7 @@ struct Tmp {
 };
 }  // namespace
 
-namespace ovm { void set_use_gemm256(int v); void set_gdino_branches(int v); void msdeform_set_vec(int v); void set_gdino_dec_chain(int v); void set_gdino_gemm256(int v); void set_gdino_swin_fused(int v); void set_gdino_swin_tap(int v); void set_gdino_ffn_split(int v); void set_gdino_mlp_fused(int v); void set_gdino_enc_fold(int v); void set_gdino_enc_tap(int v); void gemm256_set_n192(int v); void set_gemm256_ksplit(int v); }
+namespace ovm { void set_use_gemm256(int v); void set_gdino_branches(int v); void msdeform_set_vec(int v); void set_gdino_dec_chain(int v); void set_gdino_gemm256(int v); void set_gdino_swin_fused(int v); void set_gdino_swin_tap(int v); void set_gdino_ffn_split(int v); void set_gdino_mlp_fused(int v); void set_gdino_enc_fold(int v); void set_gdino_enc_tap(int v); void set_gdino_text_cache(int v); void bump_tune_generation(); void gemm256_set_n192(int v); void set_gemm256_ksplit(int v); }
 
 extern "C" {
 
@@ -406,6 +406,7 @@ int ovm_op_maxpool2(const uint16_t* in_hi, const uint16_t* in_lo, int32_t B, int
 // Tuning knobs for experiments (not part of the stable surface): "gemm_bm" = 0 (heuristic) | 128 | 256.
 int ovm_tune_set(const char* key, int32_t value) {
   if (!key) return OVM_ERR_INVALID;
+  ovm::bump_tune_generation();                    // caption entries of the detector made so far serve no forward issued from here on (gdino_model.hpp)
   if (!strcmp(key, "gemm_bm")) { gemm_set_force_bm(value); return OVM_OK; }
   if (!strcmp(key, "gemm_stages")) { gemm_set_stages(value); return OVM_OK; }
   if (!strcmp(key, "gemm_splitk")) { gemm_set_splitk(value); return OVM_OK; }
@@ -421,6 +422,7 @@ int ovm_tune_set(const char* key, int32_t value) {
   if (!strcmp(key, "gdino_mlp_fused")) { ovm::set_gdino_mlp_fused(value); return OVM_OK; }   // plans built afterwards: 0 = fc1 and fc2 as two GEMMs, 1 = Swin blocks fused, 2 = and the encoder's FFN
   if (!strcmp(key, "gdino_enc_fold")) { ovm::set_gdino_enc_fold(value); return OVM_OK; }     // plans built afterwards: 0 = off, 1 = offsets term folded + no split passes, 2 / 3 = either half
   if (!strcmp(key, "gdino_enc_tap")) { ovm::set_gdino_enc_tap(value); return OVM_OK; }        // tests; plans built afterwards
+  if (!strcmp(key, "gdino_text_cache")) { ovm::set_gdino_text_cache(value); return OVM_OK; }  // plans built afterwards: n > 0 = captions encoded once, the handle keeps n; 0 = inside every forward
   if (!strcmp(key, "gdino_ffn_split")) { ovm::set_gdino_ffn_split(value); return OVM_OK; }   // plans built afterwards: 0 = one workgroup per row block runs the whole FFN
   if (!strcmp(key, "gdino_swin_tap")) { ovm::set_gdino_swin_tap(value); return OVM_OK; }      // tests; plans built afterwards
   if (!strcmp(key, "gdino_swin_fused")) { ovm::set_gdino_swin_fused(value); return OVM_OK; }  // plans built afterwards: 0 = qkv GEMM + window attention as two launches
