@@ -26,6 +26,12 @@ evaluation's mapper, into ``model([d], prompt_depth=...)``.
 run's metric depth map - the raw map at image size, before ``prepare_prompt_depth`` - as a point cloud under the boxes
 (``draw_scene_view(depth=...)``, ``ovm_render_scene_points``). ``<name>_dets.json`` does not depend on it. ``demo/demo_geo.py`` is the
 training-free OVMono3D-GEO method on the same kind of input.
+
+``--scene-ply`` (native build, off by default): also writes ``<name>_scene.ply``, the kept boxes as vertices, faces and edges of a binary
+PLY file (``ovmono3d_amd.vis.scene_ply``) and, with ``--depth depthpro|files``, the run's metric depth map un-projected as coloured
+points in front of them (packed on the device; ``--ply-stride N`` keeps every N-th row and column, ``--ply-max-depth M`` drops points
+farther than M metres). ``--ply-frame camera`` (default) is the frame of ``<name>_dets.json``; ``opengl`` negates y and z. With
+``--depth none`` the file holds the boxes only. The other files do not depend on it.
 """
 import argparse
 import json
@@ -106,7 +112,7 @@ def do_test(args, cfg, model):
             prompt_depth = depth_source(im, "BGR", K, file_name=name)
         elif args.depth == "files":
             prompt_depth = load_depth(args.depth_dir, name)
-        raw_depth = scene_depth(prompt_depth, h, w, im_name) if args.show_points else None   # the map as computed or read, for the picture
+        raw_depth = scene_depth(prompt_depth, h, w, im_name) if args.show_points or args.scene_ply else None   # the map as computed or read
         if prompt_depth is not None:
             prompt_depth = prepare_prompt_depth(prompt_depth, (h, w), depth_resize)[None]
         dets = model([d], prompt_depth=prompt_depth)[0]["instances"]
@@ -128,7 +134,9 @@ def do_test(args, cfg, model):
             json.dump({"K": K.tolist(), "detections": out}, f)
         if vis_on:
             write_views(im, K, out, kept_idx, cfg.OUTPUT_DIR, im_name, gpu_jpeg=bool(cfg.MODEL.AMD.get("GPU_JPEG_WRITE", True)),
-                        depth=raw_depth)
+                        depth=raw_depth if args.show_points else None)
+        if args.scene_ply:
+            write_scene(args, im, K, out, kept_idx, cfg.OUTPUT_DIR, im_name, depth=raw_depth)
 
 
 def scene_depth(depth, h, w, im_name):
@@ -142,7 +150,7 @@ def scene_depth(depth, h, w, im_name):
     if depth.ndim == 3 and depth.shape[0] == 1:
         depth = depth[0]
     if tuple(depth.shape) != (h, w):
-        raise SystemExit(f"--show-points: the depth map of {im_name} is {tuple(depth.shape)} but the image is {(h, w)}")
+        raise SystemExit(f"--show-points / --scene-ply: the depth map of {im_name} is {tuple(depth.shape)} but the image is {(h, w)}")
     return depth
 
 
@@ -164,6 +172,36 @@ def write_views(im, K, dets, kept_idx, output_dir, im_name, gpu_jpeg=True, depth
     else:
         bgr, name = im, im_name + "_boxes.jpg"
     write_jpeg(os.path.join(output_dir, name), bgr, quality=95, channel_order="BGR", use_device=gpu_jpeg)
+
+
+def write_scene(args, im, K, dets, kept_idx, output_dir, im_name, depth=None, labels=None):
+    """--scene-ply: <name>_scene.ply, the boxes of ``dets`` in the colours of <name>_combine.jpg over the un-projected depth map (fp32
+    [H, W] or None: boxes only), its points tinted by ``labels`` as in the picture. Only the point records leave the device."""
+    from ovmono3d_amd import vis
+    corners = np.asarray([d["corners3D"] for d in dets], np.float64).reshape(-1, 8, 3)
+    colors = np.asarray([[c / 255.0 for c in vis.get_color(i)] for i in kept_idx], np.float32).reshape(-1, 3)
+    vis.write_scene_ply(os.path.join(output_dir, im_name + "_scene.ply"), im, K, depth=depth, corners=corners, colors=colors,
+                        point_labels=labels if depth is not None else None, stride=args.ply_stride, max_depth=args.ply_max_depth,
+                        frame=args.ply_frame)
+
+
+def _positive_float(text):
+    v = float(text)
+    if not (v > 0 and v != float("inf")):
+        raise argparse.ArgumentTypeError(f"{text!r} is not a positive finite number")
+    return v
+
+
+def add_ply_arguments(parser):
+    """--scene-ply and its settings; a value out of range is an argparse error (exit status 2)."""
+    parser.add_argument("--scene-ply", default=False, action=argparse.BooleanOptionalAction,
+                        help="(native build) also write <name>_scene.ply: the kept boxes and, where the run has a depth map, its un-projected "
+                             "points as a binary PLY file")
+    parser.add_argument("--ply-stride", type=int, default=1, choices=range(1, 17), metavar="N",
+                        help="--scene-ply: keep every N-th row and column of the depth map (1..16, default 1)")
+    parser.add_argument("--ply-max-depth", type=_positive_float, default=None, metavar="M", help="--scene-ply: drop points farther than M metres")
+    parser.add_argument("--ply-frame", choices=("camera", "opengl"), default="camera",
+                        help="--scene-ply: camera (x right, y down, z forward, as <name>_dets.json) or opengl (y and z negated)")
 
 
 def setup(args):
@@ -191,6 +229,7 @@ if __name__ == "__main__":
                         focal_help="the K[0][0] of this run: --focal-length, or without it the reference's convention 4.0 * h / 2 of the first image")
     parser.add_argument("--show-points", default=False, action="store_true",
                         help="(native build) draw the depth map of --depth depthpro|files as a point cloud under the boxes of the novel view")
+    add_ply_arguments(parser)
     parser.add_argument("--display", default=False, action="store_true", help="no-op: there is no GUI on the target (the views are written to <name>_combine.jpg)")
     parser.add_argument("--eval-only", default=True, action="store_true", help="perform evaluation only")
     parser.add_argument("--num-gpus", type=int, default=1, help="number of gpus *per machine*")

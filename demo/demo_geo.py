@@ -35,6 +35,11 @@ clicks, ``--everything``, ``--mask box``); ``--show-masks`` writes ``<name>_mask
 overlaid in the boxes' colours (alpha 0.5, contours). Both are computed on the device (``ovmono3d_amd.masks``); no plane is copied to
 the host.
 
+``--scene-ply`` (off by default; the files above are then unchanged) writes ``<name>_scene.ply``: the depth map un-projected as coloured
+points - tinted per box as in the novel view - and the kept boxes as vertices, faces and edges, one binary PLY file to orbit in any
+viewer. The points are compacted and packed on the device (``ovmono3d_amd.vis.scene_ply``); ``--ply-stride N``, ``--ply-max-depth M`` and
+``--ply-frame camera|opengl`` as in demo/demo.py.
+
 The LIFT model is not built: ``MODEL.WEIGHTS`` is not needed, the config supplies the detector's settings and ``OUTPUT_DIR``.
 """
 import argparse
@@ -50,7 +55,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (os.path.join(ROOT, "tools"), os.path.join(ROOT, "demo"), ROOT):
     sys.path.insert(0, p)
 
-from demo import write_views  # noqa: E402
+from demo import add_ply_arguments, write_scene, write_views  # noqa: E402
 from make_oracle2d import build_caption, build_detector, gdino_postprocess, phrase_spans  # noqa: E402
 from ovmono3d_geo import check_args, refined_masks, sam_masks, xywh_to_xyxy  # noqa: E402
 
@@ -215,9 +220,9 @@ def do_test(args, cfg):
                 out.append({"category": cats[ci] if 0 <= ci < len(cats) else ci, "score": float(scores[i]),
                             "bbox3D": list(box["center_cam"]) + list(box["dimensions"]), "pose": box["pose"], "corners3D": box["bbox3D"],
                             "center_2D": list(box["center_2D"]), "bbox2D": [float(v) for v in boxes[i]]})
-            if out and planes is None and (args.show_points or args.segmentation == "rle" or args.show_masks):
+            if out and planes is None and (args.show_points or args.segmentation == "rle" or args.show_masks or args.scene_ply):
                 planes = box_masks(cboxes, h, w, dev)
-            if out and args.show_points:
+            if out and (args.show_points or args.scene_ply):
                 labels = vis.labels_from_masks(planes[kept_idx])
             if out and args.segmentation == "rle":                               # encoded on the device: only the strings are read back
                 for rec, rle in zip(out, encode_rle(planes[kept_idx])):
@@ -226,7 +231,9 @@ def do_test(args, cfg):
         with open(os.path.join(cfg.OUTPUT_DIR, im_name + "_dets.json"), "w") as f:
             json.dump({"K": K.tolist(), "detections": out}, f)
         write_views(im, K, out, kept_idx, cfg.OUTPUT_DIR, im_name, gpu_jpeg=bool(cfg.MODEL.AMD.get("GPU_JPEG_WRITE", True)),
-                    depth=depth if out and args.show_points else None, labels=labels)
+                    depth=depth if out and args.show_points else None, labels=labels if args.show_points else None)
+        if args.scene_ply:
+            write_scene(args, im, K, out, kept_idx, cfg.OUTPUT_DIR, im_name, depth=depth, labels=labels)
         if args.show_masks:                                                      # the image under the kept instances' masks, in the boxes' colours
             shown = overlay_masks(im, planes[kept_idx] if out else torch.zeros((0, h, w), dtype=torch.uint8, device=dev),
                                   [vis.get_color(i) for i in kept_idx], alpha=0.5)
@@ -273,6 +280,7 @@ def argument_parser():
                              "(every mask source; encoded on the device)")
     parser.add_argument("--show-masks", action="store_true",
                         help="also write <name>_masks.jpg: the image with the kept instances' masks overlaid in the boxes' colours (alpha 0.5, contours)")
+    add_ply_arguments(parser)
     parser.add_argument("opts", default=None, nargs=argparse.REMAINDER,
                         help="Modify config options by adding 'KEY VALUE' pairs at the end of the command.")
     return parser

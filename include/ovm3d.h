@@ -1096,6 +1096,50 @@ int ovm_render_mask_overlay(const uint8_t* image, int64_t image_pitch, const int
                             const uint8_t* colors, int32_t n, int32_t alpha, uint8_t* out, int64_t out_pitch, int32_t H, int32_t W,
                             ovm_stream_t stream);
 
+/* ---- Scene as a PLY file ----------------------------------------------------------------------------------------------------
+ * <name>_scene.ply: the un-projected depth map and the boxes as one binary little-endian PLY 1.0 file, the 3D counterpart of the
+ * novel view (a layer of this project; the reference's GEO script shows Open3D line sets over the cloud, tools/ovmono3d_geo.py:
+ * 89-104, 209). The device packs the point records; the header, the box part and the file are host work of the Python layer
+ * (ovmono3d_amd.vis.scene_ply). The numpy restatement is tests/scene_ply_oracle.py; the file is defined to the byte.
+ *
+ *   ply / format binary_little_endian 1.0 / comment ovmono3d_amd scene, frame <camera|opengl>, metres
+ *   element vertex <P + 8 n>   property float x, y, z; property uchar red, green, blue          15 bytes per vertex
+ *   element face <12 n>        property list uchar int vertex_indices                           13 bytes per face (3, a, b, c)
+ *   element edge <12 n>        property int vertex1; property int vertex2                       8 bytes per edge
+ *   end_header
+ *
+ * Points, P records in row-major pixel order. Pixel (i, j) with i % stride == 0 and j % stride == 0 is kept when d = depth[i][j]
+ * is finite, d > 0 and, with max_depth > 0, d <= max_depth (compared as floats). Its position is Pass A's camera point above, in
+ * fp64 with contraction off, X = ((j + 0.5) - K[2]) / K[0] * d, Y = ((i + 0.5) - K[5]) / K[4] * d, Z = d, each rounded once to
+ * float32: the file and the picture show the same points. Its colour is Pass B's base colour: the image's BGR there, with labels
+ * given and 0 <= labels[i][j] < n_boxes each channel tinted (c + tint[b][ch] + 1) >> 1; written red = channel 2, green = channel
+ * 1, blue = channel 0.
+ * Boxes (host): 8 vertices per box, the fp64 corners in pred_bbox3D order rounded to float32, in the box's edge_u8 colour with the
+ * same channel swap; the 12 triangles of the renderer's face table (per face (a, b, c, d) of front 0 1 2 3, right 1 5 6 2, left
+ * 4 0 3 7, back 5 4 7 6, top 4 5 1 0, bottom 3 2 6 7: a b c, then c d a); the 12 edges in the panels' order above; indices
+ * offset by P + 8 b.
+ * flip = 1 (frame "opengl") negates y and z of every vertex, the reference's flip_matrix: exact. flip = 0 ("camera") agrees with
+ * <name>_dets.json.
+ *
+ * ovm_scene_ply_points: image device BGR uint8 [H][W][3], depth device fp32 [H][W], labels device int32 [H][W] or null, row pitches
+ * in bytes (depth and labels: multiples of 4; each at least one row). tint: host uint8 [n_boxes][4] ([3] unused), required with
+ * labels. K: host, row-major [9]. out: device, out_bytes >= ceil(H / stride) * ceil(W / stride) * 15 (the worst case), receives
+ * exactly 15 P bytes; no byte at or past 15 P is written. count: device uint64, receives P. Launches go on the caller's stream only:
+ * no allocation, no read back, no synchronisation (the tint rows are copied to the workspace stream-ordered). One workgroup per
+ * tile of 2,048 kept pixels counts its valid ones, ovm_scan ranks the tiles, and the same workgroup packs its records in LDS and
+ * stores its own byte range [15 r0, 15 r1) - bytes up to the first 16-byte boundary, 16-byte stores, bytes - so no store covers a
+ * byte of another workgroup's range. Integer ranks: the bytes do not depend on scheduling.
+ * OVM_ERR_INVALID: a null pointer (labels and tint may be null), H < 1, W < 1, H * W > 2^31 - 1, stride outside 1..16, n_boxes
+ * outside 0..OVM_SCENE_MAX_BOXES, a pitch below one row or (depth, labels) not a multiple of 4, labels without tint, flip other than
+ * 0 / 1, a NaN max_depth, a non-finite K or a zero focal length, a workspace not 16-byte or a count not 8-byte aligned.
+ * OVM_ERR_CAPACITY: out_bytes below the worst case or a workspace below ovm_scene_ply_points_workspace. Both before any device
+ * work; nothing is written then. */
+int ovm_scene_ply_points_workspace(int32_t H, int32_t W, int32_t stride, int32_t n_boxes, int64_t* bytes);
+int ovm_scene_ply_points(const uint8_t* image, int64_t image_pitch, const float* depth, int64_t depth_pitch, const int32_t* labels,
+                         int64_t labels_pitch, const uint8_t* tint, int32_t n_boxes, int32_t H, int32_t W, const double* K,
+                         int32_t stride, float max_depth, int32_t flip, uint8_t* out, int64_t out_bytes, uint64_t* count,
+                         void* workspace, int64_t workspace_bytes, ovm_stream_t stream);
+
 /* ---- OVMono3D-GEO -----------------------------------------------------------------------------------------------------------
  * The training-free baseline of the reference (tools/ovmono3d_geo.py:127-258): a 2D box's mask pixels are un-projected with a
  * metric depth map, the cloud is yaw-aligned by the first principal direction of its (x, z) columns, outliers are removed with

@@ -1,7 +1,7 @@
 // Exclusive prefix sum on the device: uint32 in[n] -> uint64 out[n + 1] (out[n] = the total), 2048 items per workgroup, three
 // launches on the caller's stream (reduce per tile, scan the tile sums in one workgroup, apply). Integer sums: exact and
-// order-independent. Shared by the JPEG encoder (bit and stuffed-byte offsets) and the mask run-length coder (run ranks, string
-// offsets); each translation unit gets its own copy of the kernels.
+// order-independent. Shared by the JPEG encoder (bit and stuffed-byte offsets), the mask run-length coder (run ranks, string
+// offsets) and the scene PLY packer (the first record of each tile); each translation unit gets its own copy of the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

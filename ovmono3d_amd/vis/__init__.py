@@ -5,7 +5,8 @@ blending, the ground grid, box edges and label compositing - is made by ``ovm_re
 Label glyphs are coverage masks drawn here with Pillow's built-in font (the reference uses cv2's Hershey font); the rules and
 every declared deviation are listed in include/ovm3d.h and restated in numpy by tests/scene_oracle.py.
 
-``visualize_from_instances`` and ``render_panels`` (the evaluation's six-panel samples and 3D error line) live in ``panels.py``.
+``visualize_from_instances`` and ``render_panels`` (the evaluation's six-panel samples and 3D error line) live in ``panels.py``;
+``scene_ply`` and ``write_scene_ply`` (the scene as a binary PLY file of points and boxes) in ``ply.py``.
 """
 from __future__ import annotations
 
@@ -258,3 +259,4 @@ def concat_views(front: torch.Tensor, novel: torch.Tensor) -> torch.Tensor:
 
 
 from .panels import SampleDataset, match_errors, panel_boxes, panels_layout, render_panels, visualize_from_instances  # noqa: E402,F401
+from .ply import scene_ply, write_scene_ply  # noqa: E402,F401
