@@ -601,6 +601,38 @@ int ovm_g_dec_chain(const OvmDecChainOp* op, int32_t part, ovm_stream_t stream);
 /* 1 when the decoder row chains take this geometry (what the engine asks before it picks that route; split-fp16 weights, i.e.
  * precision 3, only), else 0. Host only. */
 int ovm_host_dec_chain_supported(int32_t D, int32_t heads, int32_t ffn, int32_t L, int32_t P, int32_t T, int32_t precision);
+/* The small kernels between the fused ones, one at a time (tests): each call checks for null pointers and non-positive sizes
+ * (OVM_ERR_INVALID, nothing launched) and is then the launcher the engine calls (csrc/gdino.hpp), nothing else - no scratch, no
+ * synchronisation; all pointers are device memory the caller owns.
+ *
+ * launch_topk_keys (single_keys_kernel, the bitonic sort, topk_emit_kernel): out_idx[0:k] = the indices of the k largest of scores[0:n]
+ * by decreasing score, the lower index first among equal scores, -0.0 equal to +0.0; NaN scores are outside the contract. keys: N
+ * 64-bit words of caller-owned workspace, N >= max(2048, the next power of two >= n); only the first max(2048, pow2 >= n) words are
+ * written (every real key, then the padding keys, which sort after all of them). n <= 2^24. k > n or N too small: OVM_ERR_INVALID. */
+int ovm_g_topk_keys(const float* scores, int32_t n, int32_t k, int32_t* out_idx, uint64_t* keys, int32_t N, ovm_stream_t stream);
+/* select_ref_kernel: out[i][c] = sigmoid(coord[idx[i]][c] + prop_logit[idx[i]][c]), c < 4, i < n; coord rows have stride ldc,
+ * prop_logit is [rows][4] dense, out [n][4] dense. An infinite proposal logit (an invalid proposal) gives
+ * exactly 1. The indices are trusted. */
+int ovm_g_select_ref(const float* coord, int32_t ldc, const float* prop_logit, const int32_t* idx, int32_t n, float* out,
+                     ovm_stream_t stream);
+/* box_refine_kernel: out[i][c] = sigmoid(delta[i][c] + logit(clamp(ref[i][c], eps, 1 - eps))), c < 4, i < n (torch.special.logit(ref,
+ * eps)); delta rows have stride ldd, ref and out are [n][4] dense. */
+int ovm_g_box_refine(const float* delta, int32_t ldd, const float* ref, float eps, float* out, int32_t n, ovm_stream_t stream);
+/* pad_logits_kernel: out[q][0:T] = x[q][0:T] (row stride ldx >= T), out[q][T:ld] = -inf, q < Q; out rows have stride ld >= T and are
+ * written whole (T = ld: no -inf). */
+int ovm_g_pad_logits(const float* x, int32_t ldx, int32_t Q, int32_t T, float* out, int32_t ld, ovm_stream_t stream);
+/* bert_embed_kernel: out[t][0:D] = LayerNorm((word[ids[t]] + pos[pids[t]]) + type[0:D]; gamma, beta, eps) over D, two-pass variance,
+ * one wave per row t < T; word / pos [rows][D] dense, type the one row of token type 0, out [T][D] dense. The ids are trusted. */
+int ovm_g_bert_embed(const float* word, const float* pos, const float* type, const int32_t* ids, const int32_t* pids, int32_t T, int32_t D,
+                     const float* gamma, const float* beta, float eps, float* out, ovm_stream_t stream);
+/* relpos_tables_kernel (the SAM tower's decomposed relative positions, the rel_h / rel_w operands of OvmAttnF32Op): for the rows m < M
+ * of q (row stride ldq, head h at columns h * DH ..), whose position on the gh x gw attention grid is (qh, qw) = divmod(m mod (gh gw),
+ * gw): rel_h[(m * H + h) * ldrel + kh] = q[m][h] . Rh[qh - kh + gh - 1], kh < gh; rel_w[(m * H + h) * ldrel + kw] = q[m][h] .
+ * Rw[qw - kw + gw - 1], kw < gw. Rh [2 gh - 1][DH], Rw [2 gw - 1][DH] dense; columns past gh (gw) of a table row are not written.
+ * DH % 4, ldq % 4 (the rows are read 16 bytes at a time; q, Rh, Rw 16-byte aligned) or ldrel < max(gh, gw): OVM_ERR_SHAPE, nothing
+ * launched. M = 0: OVM_OK, nothing launched. */
+int ovm_g_relpos_tables(const float* q, int32_t ldq, int32_t M, int32_t H, int32_t DH, int32_t gh, int32_t gw, const float* Rh,
+                        const float* Rw, float* rel_h, float* rel_w, int32_t ldrel, ovm_stream_t stream);
 
 /* Process-global tuning knobs for experiments and tests (also settable as OVM_TUNE="key=value,..." when the host loads the
  * library). Defaults are the measured best; none changes results beyond fp32 summation order.

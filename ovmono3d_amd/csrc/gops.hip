@@ -679,4 +679,39 @@ int ovm_host_dec_chain_supported(int32_t D, int32_t heads, int32_t ffn, int32_t 
   return dec_chain_supported(D, heads, ffn, L, P, T, precision) ? 1 : 0;
 }
 
+// The small kernels between the fused ones, one at a time (tests): null pointers and non-positive sizes are refused, then the
+// launcher the engine calls runs. None synchronises.
+int ovm_g_topk_keys(const float* scores, int32_t n, int32_t k, int32_t* out_idx, uint64_t* keys, int32_t N, ovm_stream_t stream) {
+  if (!scores || !out_idx || !keys || n <= 0 || k <= 0 || N <= 0) return OVM_ERR_INVALID;
+  return launch_topk_keys(scores, n, k, out_idx, (unsigned long long*)keys, N, (hipStream_t)stream);
+}
+
+int ovm_g_select_ref(const float* coord, int32_t ldc, const float* prop_logit, const int32_t* idx, int32_t n, float* out, ovm_stream_t stream) {
+  if (!coord || !prop_logit || !idx || !out || ldc <= 0 || n <= 0) return OVM_ERR_INVALID;
+  return launch_select_ref(coord, ldc, prop_logit, idx, n, out, (hipStream_t)stream);
+}
+
+int ovm_g_box_refine(const float* delta, int32_t ldd, const float* ref, float eps, float* out, int32_t n, ovm_stream_t stream) {
+  if (!delta || !ref || !out || ldd <= 0 || n <= 0) return OVM_ERR_INVALID;
+  return launch_box_refine(delta, ldd, ref, eps, out, n, (hipStream_t)stream);
+}
+
+int ovm_g_pad_logits(const float* x, int32_t ldx, int32_t Q, int32_t T, float* out, int32_t ld, ovm_stream_t stream) {
+  if (!x || !out || ldx <= 0 || Q <= 0 || T <= 0 || ld <= 0) return OVM_ERR_INVALID;
+  return launch_pad_logits(x, ldx, Q, T, out, ld, (hipStream_t)stream);
+}
+
+int ovm_g_bert_embed(const float* word, const float* pos, const float* type, const int32_t* ids, const int32_t* pids, int32_t T, int32_t D,
+                     const float* gamma, const float* beta, float eps, float* out, ovm_stream_t stream) {
+  if (!word || !pos || !type || !ids || !pids || !gamma || !beta || !out || T <= 0 || D <= 0) return OVM_ERR_INVALID;
+  return launch_bert_embed(word, pos, type, ids, pids, T, D, gamma, beta, eps, out, (hipStream_t)stream);
+}
+
+int ovm_g_relpos_tables(const float* q, int32_t ldq, int32_t M, int32_t H, int32_t DH, int32_t gh, int32_t gw, const float* Rh,
+                        const float* Rw, float* rel_h, float* rel_w, int32_t ldrel, ovm_stream_t stream) {
+  // M = 0 is the launcher's own "nothing to do"
+  if (!q || !Rh || !Rw || !rel_h || !rel_w || ldq <= 0 || M < 0 || H <= 0 || DH <= 0 || gh <= 0 || gw <= 0 || ldrel <= 0) return OVM_ERR_INVALID;
+  return launch_relpos_tables(q, ldq, M, H, DH, gh, gw, Rh, Rw, rel_h, rel_w, ldrel, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -233,3 +233,216 @@ def test_gpu_bounds_reject_row_operator_slips():
         assert err <= tol, name
         err, tol = run(name, M, **override)
         assert err > 100 * tol, f"{name}: {what}"
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# The references of tests/test_gpu_gdino_select.py (the small kernels between the fused ones), each against an independent
+# implementation, and - on that file's own case inputs - the slips those kernels could make, each of which must land outside the
+# case's bound (float ops) or change at least one index / word (exact ops).
+def test_topk_ref_matches_torch_stable_sort():
+    import test_gpu_gdino_select as S
+    for family, n, k in S.TOPK_CASES + [("seven", 100, 37), ("mix", 100, 37)]:
+        s = S._topk_scores(family, n)
+        want = torch.sort(s, stable=True, descending=True)[1][:k]
+        assert torch.equal(R.topk_ref(s, k), want), f"{family} n {n}"
+        assert torch.equal(R.topk_ref(s, k, dtype=torch.float32), want)
+    s = torch.tensor([0.0, -0.0, 1.0, -0.0, 0.0, float("-inf"), 1.0])
+    assert R.topk_ref(s, 7).tolist() == [2, 6, 0, 1, 3, 4, 5]
+    with pytest.raises(AssertionError):
+        R.topk_ref(torch.tensor([1.0, float("nan")]), 1)
+
+
+def _ord_key(s, fold_zero):
+    """the kernel's key order restated: the bits of a float as an unsigned integer that ascends with the value"""
+    u = s.numpy().view("uint32").astype("int64")
+    if fold_zero:
+        u[u == 0x80000000] = 0
+    return torch.from_numpy(((u ^ 0xFFFFFFFF) * (u >> 31) + (u | 0x80000000) * (1 - (u >> 31))) & 0xFFFFFFFF)
+
+
+def test_topk_cases_reject_tie_and_signed_zero_slips():
+    import test_gpu_gdino_select as S
+    seen = {"tie": 0, "zero": 0}
+    for family, n, k in S.TOPK_CASES:
+        s = S._topk_scores(family, n)
+        ref = R.topk_ref(s, k)
+        # the key order itself, with -0.0 folded onto +0.0, is the reference's order
+        assert torch.equal(torch.sort(_ord_key(s, True), stable=True, descending=True)[1][:k], ref), f"{family} n {n}"
+        if family != "distinct" and n > 1:                        # ties resolved to the higher index
+            wrong = (n - 1 - torch.sort(s.flip(0), stable=True, descending=True)[1])[:k]
+            assert not torch.equal(wrong, ref), f"{family} n {n}: the case does not see the higher index winning"
+            seen["tie"] += 1
+        if family == "mix" and n > 1:                             # -0.0 sorted below +0.0
+            wrong = torch.sort(_ord_key(s, False), stable=True, descending=True)[1][:k]
+            assert not torch.equal(wrong, ref), f"mix n {n}: the case does not see -0.0 sorted below +0.0"
+            seen["zero"] += 1
+    assert seen["tie"] >= 12 and seen["zero"] == 4
+
+
+def test_box_refine_ref_matches_special_logit_and_rejects_a_missing_clamp():
+    import test_gpu_gdino_select as S
+    for n in S.BOX_N:
+        for ldd in S.BOX_LDD:
+            for eps in S.BOX_EPS:
+                c = S._box_case(n, ldd, eps)
+                e = float(torch.tensor(eps, dtype=torch.float32))
+                want = torch.sigmoid(c["delta"][:, :4].double() + torch.special.logit(c["ref"].double(), eps=e))
+                assert R.rel_err(c["ref64"], want) < TIGHT
+                assert torch.isfinite(c["ref64"]).all() and bool(((c["ref64"] >= 0) & (c["ref64"] <= 1)).all())
+                tol = R.bound(c["ref32"], c["ref64"])
+                x = c["ref"]                                      # eps not applied
+                wrong = torch.sigmoid(c["delta"][:, :4] + torch.log(x / (1 - x)))
+                err = R.rel_err(torch.nan_to_num(wrong, nan=2.0), c["ref64"])
+                assert err > 100 * tol, f"n {n} ldd {ldd} eps {eps}: {err} against {tol}"
+                other = R.box_refine_ref(c["delta"], c["ref"], 1e-4, dtype=torch.float32)            # another eps is outside the bound too
+                assert R.rel_err(other, c["ref64"]) > 10 * tol
+
+
+def test_select_ref_and_pad_logits_refs():
+    import test_gpu_gdino_select as S
+    for ldc in (4, 8):
+        c = S._select_case(ldc)
+        for i, s in enumerate(c["idx"].tolist()):
+            want = 1 / (1 + torch.exp(-(c["coord"][s, :4].double() + c["prop"][s].double())))
+            assert R.rel_err(c["ref64"][i], want) < TIGHT
+        assert bool((c["ref64"][c["invalid"]] == 1.0).all()) and bool((c["ref32"][c["invalid"]] == 1.0).all())
+        wrong = torch.sigmoid(c["coord"].view(-1)[c["idx"].long()[:, None] * 4 + torch.arange(4)] + c["prop"][c["idx"].long()])
+        if ldc != 4:                                              # the row stride taken for 4
+            assert R.rel_err(wrong, c["ref64"]) > 100 * R.bound(c["ref32"], c["ref64"])
+    for Q in S.PAD_Q:
+        for T in S.PAD_T:
+            for extra in (0, 3):
+                x = S._pad_case(Q, T, extra)
+                want = R.pad_logits_ref(x, T, S.PAD_LD)
+                assert want.shape == (Q, S.PAD_LD) and torch.equal(want[:, :T], x[:, :T]) and bool((want[:, T:] == float("-inf")).all())
+                if T < S.PAD_LD:                                  # -inf written from column T + 1
+                    wrong = want.clone()
+                    wrong[:, T] = S.SENT
+                    assert not torch.equal(wrong.view(torch.int32), want.view(torch.int32))
+    for rows in S.ROWMAX_ROWS:
+        for cols in S.ROWMAX_COLS:
+            x = S._rowmax_case(rows, cols)
+            want = R.rowmax_ref(x[:, :cols])
+            assert want.tolist() == [max(r) for r in x[:, :cols].tolist()]
+            assert bool(torch.isinf(want).any()) and bool((want < 0).all())
+            assert bool((x[:, cols:] > 0).all())                  # a read past the width would win every maximum
+
+
+def test_bert_embed_ref_matches_hf_bert_embeddings():
+    from transformers import BertConfig
+    from transformers.models.bert.modeling_bert import BertEmbeddings
+    import test_gpu_gdino_select as S
+    c = S._bert_case(22, 64, "normal")
+    cfg = BertConfig(vocab_size=S.BERT_VOCAB, hidden_size=64, max_position_embeddings=S.BERT_POS, type_vocab_size=2, layer_norm_eps=S.BERT_EPS,
+                     hidden_dropout_prob=0.0, pad_token_id=0)
+    emb = BertEmbeddings(cfg).double().eval()
+    with torch.no_grad():
+        emb.word_embeddings.weight.copy_(c["word"])
+        emb.position_embeddings.weight.copy_(c["pos"])
+        emb.token_type_embeddings.weight[0].copy_(c["typ"])
+        emb.token_type_embeddings.weight[1].fill_(1e3)            # token type 1 is never used
+        emb.LayerNorm.weight.copy_(c["gamma"])
+        emb.LayerNorm.bias.copy_(c["beta"])
+        want = emb(input_ids=c["ids"].long()[None], token_type_ids=torch.zeros(1, 22, dtype=torch.long), position_ids=c["pids"].long()[None])[0]
+    assert R.rel_err(c["ref64"], want) < TIGHT
+    assert c["pids"].tolist()[:9] == [0, 0, 1, 2, 3, 4, 0, 1, 2] and int(c["pids"].max()) < S.BERT_POS
+    assert c["ids"][0] == 0 and c["ids"][-1] == 49 and c["ids"][1] == c["ids"][2]
+
+
+def test_bert_embed_cases_reject_layernorm_slips():
+    import test_gpu_gdino_select as S
+
+    def one_pass(c, dtype):
+        rows = (c["word"].to(dtype)[c["ids"].long()] + c["pos"].to(dtype)[c["pids"].long()]) + c["typ"].to(dtype)
+        mean = rows.mean(-1, keepdim=True)
+        var = (rows * rows).mean(-1, keepdim=True) - mean * mean
+        return (rows - mean) / torch.sqrt(var.clamp_min(0) + S.BERT_EPS) * c["gamma"].to(dtype) + c["beta"].to(dtype)
+
+    c = S._bert_case(22, 768, "offset")
+    tol = R.bound(c["ref32"], c["ref64"])
+    rows = c["word"][c["ids"].long()]
+    assert 99 < float(rows.mean()) < 101 and 0.005 < float(rows.std(-1).mean()) < 0.02
+    assert R.rel_err(one_pass(c, torch.float64), c["ref64"]) < 1e-6          # the same function where the precision suffices
+    err = R.rel_err(torch.nan_to_num(one_pass(c, torch.float32), nan=1e3, posinf=1e3, neginf=-1e3), c["ref64"])
+    assert err > 100 * tol, f"one-pass variance: {err} against {tol}"
+    for T, D, kind in S.BERT_CASES:
+        c = S._bert_case(T, D, kind)
+        tol = R.bound(c["ref32"], c["ref64"])
+        args = (c["word"], c["pos"], c["typ"], c["ids"], c["pids"], c["gamma"], c["beta"])
+        err = R.rel_err(R.bert_embed_ref(*args, 1e-5, dtype=torch.float32), c["ref64"])         # the engine's other LayerNorms' eps
+        print(f"bert_embed T {T} D {D} {kind}: bound {tol:.2e}, eps 1e-5 instead of 1e-12: {err:.2e}")
+        assert err > 10 * tol, f"T {T} D {D} {kind}: eps"
+        if T > 1:                                                 # the position ids taken for 0 .. T - 1
+            wrong = R.bert_embed_ref(c["word"], c["pos"], c["typ"], c["ids"], torch.arange(T) % S.BERT_POS, c["gamma"], c["beta"], S.BERT_EPS,
+                                     dtype=torch.float32)
+            assert R.rel_err(wrong, c["ref64"]) > 100 * tol, f"T {T} D {D} {kind}: position ids"
+
+
+def test_normalize_image_ref_and_the_channel_flip():
+    import test_gpu_gdino_select as S
+    for H, W in S.NORM_SIZES:
+        for layout in S.NORM_LAYOUTS:
+            for flip in (0, 1):
+                c = S._norm_case(H, W, layout, flip)
+                img = c["img"]
+                assert img[0, 0, 0] == 0 and img[2, 0, 0] == 255
+                for y, x, ch in ((0, 0, 0), (H - 1, W - 1, 2), (H // 2, W // 3, 1)):
+                    cs = 2 - ch if flip else ch
+                    px = int(c["buf"][cs * c["strides"][0] + y * c["strides"][1] + x * c["strides"][2]])
+                    want = (px - float(torch.tensor(S.NORM_MEAN[cs]).float())) / float(torch.tensor(S.NORM_STD[cs]).float())
+                    assert abs(float(c["ref64"][y, x, ch]) - want) < 1e-13
+                tol = R.bound(c["ref32"], c["ref64"])
+                assert R.rel_err(c["np32"], c["ref64"]) <= tol
+                wrong = R.normalize_image_ref(img, S.NORM_MEAN, S.NORM_STD, 1 - flip, dtype=torch.float32)       # the flip ignored (or forced)
+                assert R.rel_err(wrong, c["ref64"]) > 100 * tol, f"{H} x {W} {layout} flip {flip}"
+                m = [S.NORM_MEAN[i] for i in (2, 1, 0)]                                                         # the pixel flipped, not its mean
+                assert R.rel_err(R.normalize_image_ref(img, m, S.NORM_STD, flip, dtype=torch.float32), c["ref64"]) > 100 * tol
+
+
+def test_relpos_tables_ref_matches_decomposed_rel_pos_and_rejects_index_slips():
+    from oracle.sam_vit import get_rel_pos
+    import test_gpu_gdino_select as S
+    for name in sorted(S.RELPOS):
+        c = S._relpos_case(name)
+        gh, gw, H, DH, nseq = S.RELPOS[name]
+        q, Rh, Rw = c["q"].double(), c["Rh"].double(), c["Rw"].double()
+        # add_decomposed_rel_pos: r_q [B][h][w][C], tables [h][k_h][C] and [w][k_w][C]
+        rq = q.reshape(nseq, gh, gw, H, DH).permute(0, 3, 1, 2, 4).reshape(nseq * H, gh, gw, DH)
+        want_h = torch.einsum("bhwc,hkc->bhwk", rq, get_rel_pos(gh, gh, Rh))
+        want_w = torch.einsum("bhwc,wkc->bhwk", rq, get_rel_pos(gw, gw, Rw))
+        back = lambda t, k: t.reshape(nseq, H, gh, gw, k).permute(0, 2, 3, 1, 4).reshape(c["M"], H, k)
+        assert R.rel_err(c["ref64"][0], back(want_h, gh)) < TIGHT and R.rel_err(c["ref64"][1], back(want_w, gw)) < TIGHT
+        if name == "g1x1":
+            continue                                              # one table row: no index to get wrong
+        tol = [R.bound(c["ref32"][k], c["ref64"][k]) for k in (0, 1)]
+        # the index qh - kh + gh - 1 off by one: the table read one row further down
+        off = R.relpos_tables_ref(c["q"], torch.roll(c["Rh"], 1, 0), torch.roll(c["Rw"], 1, 0), gh, gw, dtype=torch.float32)
+        assert R.rel_err(off[0], c["ref64"][0]) > 100 * tol[0] and R.rel_err(off[1], c["ref64"][1]) > 100 * tol[1], name
+        # the sign of the offset: kh - qh
+        neg = R.relpos_tables_ref(c["q"], c["Rh"].flip(0), c["Rw"].flip(0), gh, gw, dtype=torch.float32)
+        assert R.rel_err(neg[0], c["ref64"][0]) > 100 * tol[0] and R.rel_err(neg[1], c["ref64"][1]) > 100 * tol[1], name
+    # gh and gw swapped inside the kernel: the row's position taken as divmod(t, gh); only a non-square grid can tell
+    c = S._relpos_case("g3x5")
+    gh, gw = c["gh"], c["gw"]
+    t = torch.arange(c["M"]) % (gh * gw)
+    qh, qw = t // gh, t % gh
+    q32 = c["q"].float()
+    wrong_h = torch.stack([q32[m] @ c["Rh"][(int(qh[m]) - torch.arange(gh) + gh - 1).clamp(0, 2 * gh - 2)].T for m in range(c["M"])])
+    wrong_w = torch.stack([q32[m] @ c["Rw"][(int(qw[m]) - torch.arange(gw) + gw - 1).clamp(0, 2 * gw - 2)].T for m in range(c["M"])])
+    assert R.rel_err(wrong_h, c["ref64"][0]) > 100 * R.bound(c["ref32"][0], c["ref64"][0])
+    assert R.rel_err(wrong_w, c["ref64"][1]) > 100 * R.bound(c["ref32"][1], c["ref64"][1])
+    # and the composition case: attention from tables with gh and gw swapped is outside its bound
+    a = S._relpos_attn_case()
+    nseq, T, H, DH = a["nseq"], gh * gw, a["H"], a["DH"]
+    heads = lambda x: x[:, :, :H * DH].reshape(nseq, T, H, DH).permute(0, 2, 1, 3)
+    qv = a["q"].reshape(nseq, T, H, DH).permute(0, 2, 1, 3)
+    rh, rw = (x.reshape(nseq, T, H, -1) for x in R.relpos_tables_ref(a["q"], a["Rh"], a["Rw"], gh, gw, dtype=torch.float32))
+    tol = R.bound(a["attn32"], a["attn64"])
+    assert R.rel_err(R.attn_ref(qv, heads(a["k"]), heads(a["v"]), a["scale"], None, None, rh, rw, gw, dtype=torch.float32), a["attn64"]) <= tol
+    wrong = R.attn_ref(qv, heads(a["k"]), heads(a["v"]), a["scale"], None, None, wrong_h.reshape(nseq, T, H, gh), wrong_w.reshape(nseq, T, H, gw),
+                       gw, dtype=torch.float32)
+    assert R.rel_err(wrong, a["attn64"]) > 100 * tol
+    # the tables read with the key split the other way round (key = kw * gh + kh)
+    key = torch.arange(T)
+    s = torch.einsum("abqd,abkd->abqk", qv, heads(a["k"])) * a["scale"] + rh.permute(0, 2, 1, 3)[..., key % gh] + rw.permute(0, 2, 1, 3)[..., key // gh]
+    assert R.rel_err(torch.softmax(s, -1) @ heads(a["v"]), a["attn64"]) > 100 * tol
