@@ -35,6 +35,14 @@ clicks, ``--everything``, ``--mask box``); ``--show-masks`` writes ``<name>_mask
 overlaid in the boxes' colours (alpha 0.5, contours). Both are computed on the device (``ovmono3d_amd.masks``); no plane is copied to
 the host.
 
+``--min-mask-region-area N`` (default 0: off, every file as without it) cleans the masks before they are lifted: segment_anything's
+``remove_small_regions``, holes below N pixels filled and then islands below N pixels cleared (8-connected), on the device
+(``ovmono3d_amd.masks.remove_small_regions``). With ``--everything`` it is the generator's ``min_mask_region_area`` (cleaned masks, their
+boxes and areas, and the second NMS); for box and click prompts the planes are cleaned before ``lift_boxes``, and a click prompt without a
+"bbox" takes the tight box of its cleaned mask. The cleaned planes are what ``--segmentation rle``, ``--show-masks`` and the cloud tint
+see. A declared deviation: the reference lifts the raw plane [2], specks included. ``--mask box`` is a rectangle: the flag is accepted
+and does nothing.
+
 ``--scene-ply`` (off by default; the files above are then unchanged) writes ``<name>_scene.ply``: the depth map un-projected as coloured
 points - tinted per box as in the novel view - and the kept boxes as vertices, faces and edges, one binary PLY file to orbit in any
 viewer. The points are compacted and packed on the device (``ovmono3d_amd.vis.scene_ply``); ``--ply-stride N``, ``--ply-max-depth M`` and
@@ -57,7 +65,7 @@ for p in (os.path.join(ROOT, "tools"), os.path.join(ROOT, "demo"), ROOT):
 
 from demo import add_ply_arguments, write_scene, write_views  # noqa: E402
 from make_oracle2d import build_caption, build_detector, gdino_postprocess, phrase_spans  # noqa: E402
-from ovmono3d_geo import check_args, refined_masks, sam_masks, xywh_to_xyxy  # noqa: E402
+from ovmono3d_geo import check_args, clean_planes, refined_masks, sam_masks, xywh_to_xyxy  # noqa: E402
 
 from ovmono3d_amd.data.depth_prompt import add_depth_arguments, build_depth_prompt, load_depth  # noqa: E402
 from ovmono3d_amd.data.gpu_jpeg import read_image_device, write_jpeg  # noqa: E402
@@ -102,9 +110,10 @@ def group_point_prompts(entries):
     return groups
 
 
-def point_masks(predictor, bgr, entries, refine=0):
+def point_masks(predictor, bgr, entries, refine=0, min_area=0):
     """SAM's plane [2] for the click prompts ``entries`` of one image: (device uint8 [n, H, W] in the entries' order, xyxy boxes float64
-    [n, 4]: the entry's own "bbox", else the tight box of its mask - zeros for an empty one)."""
+    [n, 4]: the entry's own "bbox", else the tight box of its mask - zeros for an empty one). ``min_area`` > 0: the planes are
+    cleaned (``clean_planes``) and the tight boxes are the cleaned masks'."""
     h, w = int(bgr.shape[0]), int(bgr.shape[1])
     planes = torch.zeros((len(entries), h, w), dtype=torch.uint8, device=bgr.device)
     boxes = np.zeros((len(entries), 4), np.float64)
@@ -115,6 +124,7 @@ def point_masks(predictor, bgr, entries, refine=0):
         given = np.asarray([xywh_to_xyxy(entries[i]["bbox"]) for i in idx], np.float64) if has_box else None
         masks = refined_masks(predictor, refine, point_coords=np.asarray([entries[i]["points"] for i in idx], np.float32),
                               point_labels=np.asarray([entries[i]["labels"] for i in idx], np.int32), boxes=given)
+        masks = clean_planes(masks, min_area)
         planes[idx] = masks
         boxes[idx] = given if has_box else predictor.mask_boxes(masks)[0].cpu().numpy().astype(np.float64)
     return planes, boxes
@@ -181,7 +191,7 @@ def do_test(args, cfg):
         lap("read")
         auto = None
         if generator is not None:                                            # masks first: their tight boxes are the 2D boxes
-            auto = generator.generate_device(im, "BGR")
+            auto = generator.generate_device(im, "BGR", min_mask_region_area=args.min_mask_region_area)
             boxes = auto["boxes"].cpu().numpy().astype(np.float64).reshape(-1, 4)
             scores, classes = [float(s) for s in auto["scores"].cpu().tolist()], [0] * len(boxes)
         elif entries is not None:                                            # the 2D boxes come with the masks, below
@@ -203,12 +213,13 @@ def do_test(args, cfg):
                 depth = torch.from_numpy(load_depth(args.depth_dir, name, h, w)).to(dev)
             lap("depth")
             if entries is not None:
-                planes, boxes[cand] = point_masks(predictor, im, [entries[i] for i in cand], args.sam_refine)
+                planes, boxes[cand] = point_masks(predictor, im, [entries[i] for i in cand], args.sam_refine, args.min_mask_region_area)
             cboxes = boxes[cand]
             if auto is not None:
                 planes = auto["masks"]
             elif entries is None:
                 planes = sam_masks(predictor, None, None, h, w, cboxes, bgr=im, refine=args.sam_refine) if predictor is not None else None
+                planes = clean_planes(planes, args.min_mask_region_area)
             lap("masks")
             lifted = lift_boxes(depth, K, boxes_xyxy=cboxes, masks=list(planes) if planes is not None else None, params=params)
             lap("lift")
@@ -280,6 +291,11 @@ def argument_parser():
                              "(every mask source; encoded on the device)")
     parser.add_argument("--show-masks", action="store_true",
                         help="also write <name>_masks.jpg: the image with the kept instances' masks overlaid in the boxes' colours (alpha 0.5, contours)")
+    parser.add_argument("--min-mask-region-area", type=int, default=0, metavar="N",
+                        help="clean the masks before they are lifted: holes, then islands, of fewer than N pixels are removed (segment_anything's "
+                             "remove_small_regions, on the device). --everything: the generator's min_mask_region_area; box and click prompts: the "
+                             "planes before the lift. A deviation from the reference, which lifts the raw plane. 0 (default): off. Accepted and "
+                             "without effect with --mask box")
     add_ply_arguments(parser)
     parser.add_argument("opts", default=None, nargs=argparse.REMAINDER,
                         help="Modify config options by adding 'KEY VALUE' pairs at the end of the command.")

@@ -1128,6 +1128,56 @@ int ovm_render_mask_overlay(const uint8_t* image, int64_t image_pitch, const int
                             const uint8_t* colors, int32_t n, int32_t alpha, uint8_t* out, int64_t out_pitch, int32_t H, int32_t W,
                             ovm_stream_t stream);
 
+/* ---- Mask connected components ----------------------------------------------------------------------------------------------
+ * Connected-component labelling of binary planes in HBM, and segment_anything's small-region clean-up (utils/amg.py
+ * remove_small_regions, restated) on top of it. Everything is integer arithmetic and defined exactly; the reference for the labels is
+ * scipy.ndimage.label, the numpy restatement of the clean-up is tests/mask_cc_oracle.py.
+ *
+ * Planes are addressed as ovm_mask_rle_encode takes them (plane i at masks + i * plane_stride, row y at + y * row_pitch, bytes, any
+ * alignment). Foreground is a byte != 0, or == 0 with invert != 0. connectivity is 4 (edge neighbours) or 8 (edge and corner).
+ *
+ * ovm_mask_cc_label: labels_out device int32, pixel (y, x) of plane i at labels_out + i * label_plane_stride + y * label_pitch + x
+ * (elements); background is 0. counts_out device int32 [n]: the number of components of each plane.
+ * Label rule. The components of a plane are numbered 1, 2, ... in row-major order of their first pixel: scipy.ndimage.label's
+ * numbering (structure: the cross for 4, ones((3, 3)) for 8). The unions always hook the larger root under the smaller, so a
+ * component's root is its first pixel, and its label is the rank of that root among the plane's roots (one prefix sum).
+ *
+ * ovm_mask_remove_small_regions: mode 1 = holes, 2 = islands, 3 = holes, then islands on the result. masks_out device uint8 planes of
+ * 0 / 1 (out_plane_stride, out_row_pitch in bytes) that must overlap neither the input nor each other (n > 1:
+ * |out_plane_stride| >= (H - 1) * out_row_pitch + W); changed_out device int32 [n].
+ * Clean-up rule, per plane and step. The working plane is the mask for islands and its complement for holes; connectivity is 8 in
+ * both; the outer background is a region like any other. A region is small when area < min_area (strict). No small region: the
+ * plane is copied (as 0 / 1) and changed = 0. Otherwise changed = 1 and: holes - the small regions of the complement are filled;
+ * islands - the small regions are cleared, and when every region is small the largest one is kept, on a tie the one that comes first
+ * in label order (argmax's first). Mode 3: changed is the OR of the two steps.
+ *
+ * status: device int32 [4] = code, number of threads that gave up, reserved, reserved. Every walk through the union-find forest
+ * counts its steps against a bound derived from H * W (a walk only ever moves to smaller indices, so the bound cannot be reached);
+ * a thread that reaches it, or meets an index that cannot be a parent, sets code = OVM_ERR_HIP and ends: a defect comes back as a
+ * code, not as a hang. The outputs are then undefined. Like ovm_mask_rle_encode's status it is device memory and the call does
+ * not wait for it.
+ * Launches go on the caller's stream only: no read back, no allocation, no synchronisation. Their number is fixed (7 for labels, 5
+ * per clean-up step) and does not depend on what the planes hold. One wave owns 64 consecutive pixels of a row; the unions
+ * within those cost a ballot, the others are atomicMin hooks on roots in global memory, made only where a contact between two rows
+ * begins. No decision relies on a plain load seeing what another workgroup wrote in the same launch: a union takes its decisions
+ * from the atomics' return values and treats a plain read of a parent as a hint (parents only move to smaller indices of the same
+ * component, so an old parent is still an ancestor). Region areas are summed within the wave first: one atomicAdd per distinct
+ * root among its lanes. Outputs do not depend on scheduling; two calls give equal bytes.
+ *
+ * Refused before any device work: a null pointer, n < 1, H < 1, W < 1, H * W > 2^31 - 1, row_pitch, label_pitch or out_row_pitch
+ * below W, connectivity outside {4, 8}, mode outside 1..3, min_area < 1, masks_out overlapping masks or its own planes, a workspace that is not
+ * 16-byte aligned (OVM_ERR_INVALID); a workspace below what the _workspace call states, or more than 2^24 - 1 workgroups of 4
+ * row segments of 64 pixels (OVM_ERR_CAPACITY: split the planes over several calls).
+ * Scope: 8-bit planes. Not built: component statistics tables (boxes, centroids). */
+int ovm_mask_cc_label_workspace(int32_t n, int32_t H, int32_t W, int64_t* bytes);
+int ovm_mask_cc_label(const uint8_t* masks, int64_t plane_stride, int64_t row_pitch, int32_t n, int32_t H, int32_t W, int32_t connectivity,
+                      int32_t invert, int32_t* labels_out, int64_t label_plane_stride, int64_t label_pitch, int32_t* counts_out, int32_t* status,
+                      void* workspace, int64_t workspace_bytes, ovm_stream_t stream);
+int ovm_mask_remove_small_regions_workspace(int32_t n, int32_t H, int32_t W, int64_t* bytes);
+int ovm_mask_remove_small_regions(const uint8_t* masks, int64_t plane_stride, int64_t row_pitch, int32_t n, int32_t H, int32_t W, int64_t min_area,
+                                  int32_t mode, uint8_t* masks_out, int64_t out_plane_stride, int64_t out_row_pitch, int32_t* changed_out,
+                                  int32_t* status, void* workspace, int64_t workspace_bytes, ovm_stream_t stream);
+
 /* ---- Scene as a PLY file ----------------------------------------------------------------------------------------------------
  * <name>_scene.ply: the un-projected depth map and the boxes as one binary little-endian PLY 1.0 file, the 3D counterpart of the
  * novel view (a layer of this project; the reference's GEO script shows Open3D line sets over the cloud, tools/ovmono3d_geo.py:

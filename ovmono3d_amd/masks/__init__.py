@@ -2,6 +2,9 @@
 (``ovm_mask_rle_encode`` / ``ovm_mask_rle_decode`` / ``ovm_mask_labels`` / ``ovm_render_mask_overlay``; the rules are stated in
 include/ovm3d.h). Only the RLE strings cross PCIe; there is no CPU fallback. The one piece of host arithmetic is the string ->
 counts conversion of :func:`decode_rle` and :func:`rle_area`, a few bytes per run.
+
+And their topology: :func:`connected_components` (``ovm_mask_cc_label``) and segment_anything's small-region clean-up
+:func:`remove_small_regions` (``ovm_mask_remove_small_regions``), also on the device: the planes never leave HBM.
 """
 from __future__ import annotations
 
@@ -217,3 +220,103 @@ def overlay_masks(im: torch.Tensor, masks_or_labels: torch.Tensor, colors, alpha
                                                  H, W, _stream(dev))
         _lib.check(rc, what="ovm_render_mask_overlay")
     return out
+
+
+# ---- connected components and the small-region clean-up (include/ovm3d.h, "Mask connected components") ---------------------------
+MAX_CC_WORKSPACE = 1 << 30           # bytes of workspace one call may take: the planes are walked in chunks that stay below it
+_CC_MODES = {"holes": 1, "islands": 2, "both": 3}
+
+
+def _cc_chunks(n: int, H: int, W: int, workspace_fn):
+    """(planes per call, workspace bytes of such a call): the largest chunk whose workspace stays within MAX_CC_WORKSPACE and which
+    one call takes (one plane when even that is above the constant). The workspace grows with n by at most need(2) - need(1) per plane
+    (the offsets are rounded up to 16 bytes), which gives the start; the call's own limit on n is found by halving."""
+    def need(k):
+        b = C.c_int64()
+        return b.value if workspace_fn(k, H, W, C.byref(b)) == _lib.OVM_OK else None
+
+    one = need(1)
+    if one is None:
+        raise ValueError(f"a plane of {H} x {W} is more than one call takes")
+    per = 1
+    if n > 1 and need(2) is not None:
+        per = max(1, min(n, 1 + (MAX_CC_WORKSPACE - one) // max(need(2) - one, 1)))
+    while per > 1:
+        got = need(per)
+        if got is not None and got <= MAX_CC_WORKSPACE:
+            return per, got
+        # more segments than a launch takes: halve; over the constant (the 16-byte rounding): scale down, one fewer at the least
+        per = per // 2 if got is None else min(per - 1, per * MAX_CC_WORKSPACE // got)
+    return 1, one
+
+
+def _cc_status(status: torch.Tensor, what: str) -> None:
+    st = status.cpu().tolist()                                # the one 16-byte read
+    if st[0] != _lib.OVM_OK:
+        raise _lib.OvmError(f"{what}: status {st} ({st[1]} thread(s) reached the bound of a union-find walk)")
+
+
+def connected_components(masks: torch.Tensor, connectivity: int = 8, invert: bool = False):
+    """Device uint8 / bool [n, H, W] (nonzero = foreground, zero with ``invert``; any plane and row strides) -> (labels int32
+    [n, H, W], counts int32 [n]), device tensors. The components of each plane are numbered 1, 2, ... in row-major order of their
+    first pixel, background 0: ``scipy.ndimage.label`` with the cross (``connectivity=4``) or ``ones((3, 3))`` (8). Labelled on
+    the device (``ovm_mask_cc_label``: union-find, a fixed number of launches); what is read back is the 16-byte status."""
+    m = _planes(masks, "connected_components")
+    if connectivity not in (4, 8):
+        raise ValueError(f"connected_components: connectivity must be 4 or 8, is {connectivity}")
+    n, H, W = (int(v) for v in m.shape)
+    dev = m.device
+    with torch.cuda.device(dev):
+        labels = torch.empty((n, H, W), dtype=torch.int32, device=dev)
+        counts = torch.empty((n,), dtype=torch.int32, device=dev)
+        if n == 0:
+            return labels, counts
+        if H < 1 or W < 1 or H * W > _I32_MAX:
+            raise ValueError(f"connected_components: a plane of {H} x {W} (1 <= H * W <= 2^31 - 1)")
+        L = _lib.load()
+        per, ws_bytes = _cc_chunks(n, H, W, L.ovm_mask_cc_label_workspace)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        status = torch.empty(4, dtype=torch.int32, device=dev)
+        for i in range(0, n, per):
+            c, lab = m[i:i + per], labels[i:i + per]
+            rc = L.ovm_mask_cc_label(c.data_ptr(), c.stride(0), c.stride(1), int(c.shape[0]), H, W, int(connectivity), int(bool(invert)),
+                                     lab.data_ptr(), lab.stride(0), lab.stride(1), counts[i:i + per].data_ptr(), status.data_ptr(),
+                                     ws.data_ptr(), ws.numel(), _stream(dev))
+            _lib.check(rc, what="ovm_mask_cc_label")
+            _cc_status(status, "ovm_mask_cc_label")
+    return labels, counts
+
+
+def remove_small_regions(masks: torch.Tensor, area_thresh: int, mode: str):
+    """segment_anything's ``remove_small_regions`` on device planes: uint8 / bool [n, H, W] -> (masks uint8 [n, H, W] of 0 / 1,
+    changed bool [n]), device tensors. ``mode``: "holes" fills the regions of the complement (8-connected, the outer background
+    included) whose area is below ``area_thresh``; "islands" clears such regions of the mask, keeping the largest (the first of equal
+    ones) when all are that small; "both" is holes, then islands on the result, as the automatic mask generator applies them.
+    ``changed`` is whether the plane had a small region. ``remove_small_regions(m, H * W + 1, "islands")`` is "keep the largest
+    component". Runs on the device (``ovm_mask_remove_small_regions``); what is read back is the 16-byte status."""
+    m = _planes(masks, "remove_small_regions")
+    if mode not in _CC_MODES:
+        raise ValueError(f"remove_small_regions: mode must be one of {sorted(_CC_MODES)}, is {mode!r}")
+    if int(area_thresh) < 1:
+        raise ValueError(f"remove_small_regions: area_thresh must be at least 1, is {area_thresh}")
+    n, H, W = (int(v) for v in m.shape)
+    dev = m.device
+    with torch.cuda.device(dev):
+        out = torch.empty((n, H, W), dtype=torch.uint8, device=dev)
+        changed = torch.empty((n,), dtype=torch.int32, device=dev)
+        if n == 0:
+            return out, changed.bool()
+        if H < 1 or W < 1 or H * W > _I32_MAX:
+            raise ValueError(f"remove_small_regions: a plane of {H} x {W} (1 <= H * W <= 2^31 - 1)")
+        L = _lib.load()
+        per, ws_bytes = _cc_chunks(n, H, W, L.ovm_mask_remove_small_regions_workspace)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        status = torch.empty(4, dtype=torch.int32, device=dev)
+        for i in range(0, n, per):
+            c, o = m[i:i + per], out[i:i + per]
+            rc = L.ovm_mask_remove_small_regions(c.data_ptr(), c.stride(0), c.stride(1), int(c.shape[0]), H, W, int(area_thresh), _CC_MODES[mode],
+                                                 o.data_ptr(), o.stride(0), o.stride(1), changed[i:i + per].data_ptr(), status.data_ptr(),
+                                                 ws.data_ptr(), ws.numel(), _stream(dev))
+            _lib.check(rc, what="ovm_mask_remove_small_regions")
+            _cc_status(status, "ovm_mask_remove_small_regions")
+    return out, changed.bool()

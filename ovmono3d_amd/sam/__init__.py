@@ -351,9 +351,10 @@ class SamAutomaticMaskGenerator:
     the predicted-IoU filter, the stability filter and box NMS, all on the device (``ovm_sam_auto_candidates`` /
     ``ovm_sam_auto_select``, include/ovm3d.h states the rules). The emitted masks are ``SamPredictor.predict_prompts``'s own planes.
 
-    Not built and refused with ValueError: crops (``crop_n_layers > 0``), the small-region clean-up (``min_mask_region_area > 0``: it
-    needs connected components), ``output_mode`` other than "binary_mask" (RLE records come from ``generate_rle``). The crop-edge filter
-    never removes a mask of the full-image crop. Parity with the
+    Not built and refused with ValueError: crops (``crop_n_layers > 0``), ``output_mode`` other than "binary_mask" (RLE records come
+    from ``generate_rle``). The small-region clean-up is a keyword of the ``generate*`` calls (``min_mask_region_area=A``:
+    :meth:`postprocess_small_regions` on the device); the constructor argument of that name keeps refusing a value above 0, as
+    ``output_mode`` does. The crop-edge filter never removes a mask of the full-image crop. Parity with the
     segment_anything package is not pinned by a test (the package is not a dependency); DESIGN.md section 4.4."""
 
     def __init__(self, predictor: SamPredictor, points_per_side: Optional[int] = 32, points_per_batch: int = 64, pred_iou_thresh: float = 0.88,
@@ -363,7 +364,8 @@ class SamAutomaticMaskGenerator:
         if crop_n_layers > 0:
             raise ValueError(f"crop_n_layers = {crop_n_layers}: crops are not built (the full image only)")
         if min_mask_region_area > 0:
-            raise ValueError(f"min_mask_region_area = {min_mask_region_area}: the small-region clean-up (connected components) is not built")
+            raise ValueError(f"min_mask_region_area = {min_mask_region_area}: not a constructor argument here; the small-region clean-up is the "
+                             "keyword min_mask_region_area of generate_device / generate / generate_rle")
         if output_mode != "binary_mask":
             raise ValueError(f"output_mode = {output_mode!r}: only 'binary_mask' (RLE modes are not built)")
         if (points_per_side is None) == (point_grids is None):
@@ -401,11 +403,57 @@ class SamAutomaticMaskGenerator:
             raise RuntimeError("generate() has not been called")
         return candidate_fields(self._cands), self._points.copy()
 
+    @staticmethod
     @torch.no_grad()
-    def generate_device(self, image, image_format: str = "RGB"):
+    def postprocess_small_regions(out, min_area: int, nms_thresh: float):
+        """segment_anything's method of this name on the dict of :meth:`generate_device`: every mask is cleaned with
+        ``masks.remove_small_regions(m, min_area, "both")``; boxes and areas of the cleaned masks are recomputed; NMS by ``ovm_op_nms``'s
+        rule runs over the inclusive boxes as floats with score 1.0 for an unchanged mask and 0.0 for a changed one (ties to the lower
+        index), so a mask is dropped when cleaning made its box overlap a kept one's above ``nms_thresh``. The result is in keep order:
+        a kept changed mask carries its cleaned plane, box and area, an unchanged one what it had; ``scores``, ``stability``,
+        ``points`` and ``index`` are carried through. All on the device; the number kept is the one word read back."""
+        from ..masks import remove_small_regions
+        masks = out["masks"]
+        m = int(masks.shape[0])
+        if m == 0:
+            return dict(out)
+        L = _lib.load()
+        dev = masks.device
+        H, W = int(masks.shape[1]), int(masks.shape[2])
+        with torch.cuda.device(dev):
+            cleaned, changed = remove_small_regions(masks, int(min_area), "both")
+            boxes = torch.empty((m, 4), dtype=torch.float32, device=dev)
+            areas = torch.empty((m,), dtype=torch.int32, device=dev)
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(L.ovm_sam_mask_boxes(cleaned.data_ptr(), m, H, W, boxes.data_ptr(), areas.data_ptr(), stream), what="ovm_sam_mask_boxes")
+            incl = boxes.clone()
+            incl[:, 2:] -= (areas > 0).to(torch.float32)[:, None]          # (xmin, ymin, xmax, ymax); zeros for an empty mask
+            scores = (~changed).to(torch.float32).contiguous()
+            keep = torch.empty((m,), dtype=torch.int32, device=dev)
+            n_keep = torch.zeros((1,), dtype=torch.int32, device=dev)
+            rc = L.ovm_op_nms(incl.data_ptr(), scores.data_ptr(), m, float(nms_thresh), keep.data_ptr(), n_keep.data_ptr(), stream)
+            if rc != 0:
+                raise _lib.OvmError(f"ovm_op_nms failed with code {rc} (m = {m}; at most 4096 masks)")
+            keep = keep[:int(n_keep.item())].to(torch.int64)
+            ch = changed[keep]
+            res = {k: v[keep] for k, v in out.items()}
+            res["masks"] = torch.where(ch[:, None, None], cleaned[keep], out["masks"][keep])
+            res["boxes"] = torch.where(ch[:, None], boxes[keep], out["boxes"][keep])
+            res["areas"] = torch.where(ch, areas[keep], out["areas"][keep])
+        return res
+
+    @torch.no_grad()
+    def generate_device(self, image, image_format: str = "RGB", min_mask_region_area: int = 0):
         """dict of device tensors for the kept masks, in NMS keep order: masks uint8 [m, H, W], boxes fp32 [m, 4] (xmin, ymin,
         xmax + 1, ymax + 1: ``SamPredictor.mask_boxes``), scores fp32 [m] (predicted IoU), stability fp32 [m], points fp32 [m, 2],
-        areas int32 [m]; and ``index`` int64 [m]: the candidate (3 * point + plane) each mask came from."""
+        areas int32 [m]; and ``index`` int64 [m]: the candidate (3 * point + plane) each mask came from.
+        ``min_mask_region_area`` > 0: :meth:`postprocess_small_regions` with that area and ``nms_thresh = box_nms_thresh`` is applied to
+        the result (segment_anything takes the larger of the box and crop thresholds; there are no crops here). This keyword is the
+        route to the clean-up: the constructor argument of the same name keeps refusing a value above 0. 0 is the path without it."""
+        if int(min_mask_region_area) < 0:
+            raise ValueError(f"min_mask_region_area must not be negative, is {min_mask_region_area}")
+        if int(min_mask_region_area) > 0:
+            return self.postprocess_small_regions(self.generate_device(image, image_format), int(min_mask_region_area), self.box_nms_thresh)
         pred = self.predictor
         eng = pred.engine
         pred.set_image(image, image_format)
@@ -436,32 +484,40 @@ class SamAutomaticMaskGenerator:
         return {"masks": masks, "boxes": boxes, "scores": kept[:, 0].contiguous().view(torch.float32), "stability": kept[:, 1].contiguous().view(torch.float32),
                 "points": pts[keep // 3], "areas": areas, "index": keep}
 
-    def _records(self, out, segmentations):
+    def _records(self, out, segmentations, cleaned: bool = False):
+        """cleaned: area and bbox come from the outputs (the cleaned masks' own), not from the candidate table."""
         H, W = self.predictor.original_size
         f, pts = self.candidates()
         records = []
+        if cleaned:
+            areas, boxes = out["areas"].cpu().numpy(), out["boxes"].cpu().numpy().astype(np.int64)
         for i, c in enumerate(out["index"].cpu().numpy().tolist()):
             x0, y0, x1, y1 = (int(v) for v in f["box"][c])
-            records.append({"segmentation": segmentations[i], "area": int(f["area"][c]), "bbox": [x0, y0, x1 - x0, y1 - y0], "predicted_iou": float(f["iou"][c]),
+            area = int(f["area"][c])
+            if cleaned:
+                area = int(areas[i])
+                x0, y0, x1, y1 = (int(boxes[i][0]), int(boxes[i][1]), int(boxes[i][2]) - 1, int(boxes[i][3]) - 1) if area else (0, 0, 0, 0)
+            records.append({"segmentation": segmentations[i], "area": area, "bbox": [x0, y0, x1 - x0, y1 - y0], "predicted_iou": float(f["iou"][c]),
                             "point_coords": [[float(pts[c // 3][0]), float(pts[c // 3][1])]], "stability_score": float(f["stability"][c]),
                             "crop_box": [0, 0, W, H]})
         return records
 
-    def generate(self, image, image_format: str = "RGB"):
+    def generate(self, image, image_format: str = "RGB", min_mask_region_area: int = 0):
         """segment_anything's records, one dict per kept mask in NMS keep order: segmentation (bool [H, W], a device tensor), area,
         bbox (XYWH of the inclusive box: w = xmax - xmin), predicted_iou, point_coords [[x, y]], stability_score, crop_box [0, 0, W, H].
-        (The constructor's ``output_mode`` takes "binary_mask" only; RLE records come from :meth:`generate_rle`.)"""
-        out = self.generate_device(image, image_format)
-        return self._records(out, out["masks"].bool())
+        (The constructor's ``output_mode`` takes "binary_mask" only; RLE records come from :meth:`generate_rle`.)
+        ``min_mask_region_area`` > 0: the masks of :meth:`postprocess_small_regions`, with ``area`` and ``bbox`` of the cleaned masks."""
+        out = self.generate_device(image, image_format, min_mask_region_area)
+        return self._records(out, out["masks"].bool(), cleaned=int(min_mask_region_area) > 0)
 
-    def generate_rle(self, image, image_format: str = "RGB", compressed: bool = True):
+    def generate_rle(self, image, image_format: str = "RGB", compressed: bool = True, min_mask_region_area: int = 0):
         """The records of :meth:`generate` with ``segmentation`` as the COCO RLE dict ``{"size": [H, W], "counts": str}`` (segment_anything's
         "coco_rle"; ``compressed=False``: ``counts`` the list of run lengths, its "uncompressed_rle"). The masks are encoded on the
         device (``ovmono3d_amd.masks.encode_rle``): no plane is copied to the host. The constructor's ``output_mode`` argument still
-        refuses everything but "binary_mask"; this method is the RLE route."""
+        refuses everything but "binary_mask"; this method is the RLE route. ``min_mask_region_area``: as in :meth:`generate`."""
         from ..masks import encode_rle
-        out = self.generate_device(image, image_format)
-        return self._records(out, encode_rle(out["masks"], compressed=compressed))
+        out = self.generate_device(image, image_format, min_mask_region_area)
+        return self._records(out, encode_rle(out["masks"], compressed=compressed), cleaned=int(min_mask_region_area) > 0)
 
 
 def build_sam(arch: str, checkpoint: Union[str, Dict[str, torch.Tensor], None], device: Optional[torch.device] = None,

@@ -26,6 +26,12 @@ Masks, one of:
   ``--mask box``   the 2D box itself is the mask: the pixels ceil(x0) <= x < ceil(x1), ceil(y0) <= y < ceil(y1) of the xyxy box,
                    clipped to the image (the reference has no such mode; the rule is this project's).
 
+``--min-mask-region-area N`` (default 0: off, the same bytes as without it) cleans every ``--mask sam`` and ``--mask-dir`` plane before
+it is lifted: segment_anything's ``remove_small_regions`` on the device (``ovmono3d_amd.masks.remove_small_regions(planes, N, "both")``:
+holes below N pixels filled, then islands below N pixels cleared, 8-connected). A declared deviation: the reference lifts the raw
+plane [2], specks included. ``--dump-masks`` writes the cleaned planes. With ``--mask box`` the mask is a rectangle: the flag is accepted
+and does nothing.
+
 Depth, one of:
   ``--depth files``     (default) read from ``<depth-dir>/test/<image base name>.npz`` (or ``<depth-dir>/<image base name>.npz``), key
                         ``depth``, metres, at the image's own resolution - a map of another shape is refused, the reference never
@@ -104,6 +110,18 @@ def sam_masks(predictor, image_root, file_path, height, width, boxes_xyxy, bgr=N
     if refine > 0 and len(boxes_xyxy):
         return refined_masks(predictor, refine, boxes=boxes_xyxy)
     return predictor.predict_boxes(boxes_xyxy, mask_index=2)
+
+
+def clean_planes(planes, min_area):
+    """``remove_small_regions(planes, min_area, "both")`` on a list of [H, W] planes (numpy arrays or device tensors) or a device
+    [n, H, W] tensor: device uint8 [n, H, W] of 0 / 1. ``min_area`` 0, or no plane: what was given."""
+    if not min_area or planes is None or len(planes) == 0:
+        return planes
+    from ovmono3d_amd.masks import remove_small_regions
+    dev = torch.device("cuda", torch.cuda.current_device())
+    if not isinstance(planes, torch.Tensor):
+        planes = torch.stack([p.to(dev) if isinstance(p, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(p)).to(dev) for p in planes])
+    return remove_small_regions(planes, int(min_area), "both")[0]
 
 
 def dump_masks(mask_dir, image_id, positions, planes, fmt="npz"):
@@ -205,6 +223,8 @@ def run(args):
                 planes = [have[pos] for pos, _ in cand]
             if cand:
                 boxes = np.asarray([xywh_to_xyxy(ins["bbox"]) for _, ins in cand], np.float64)
+                if args.min_mask_region_area > 0 and planes is not None:
+                    planes = list(clean_planes(planes, args.min_mask_region_area))
                 lifted = lift_image(depth, K, boxes, planes, params)
                 if args.dump_masks and planes is not None:
                     dump_masks(args.dump_masks, rec["image_id"], [pos for pos, _ in cand], planes, args.mask_format)
@@ -262,6 +282,10 @@ def argument_parser():
     ap.add_argument("--mask-format", choices=("npz", "rle"), default="npz",
                     help="--dump-masks: npz (planes copied to the host and deflated) or rle (<image_id>.rle.json, COCO RLE encoded on the device); "
                          "--mask-dir reads either")
+    ap.add_argument("--min-mask-region-area", type=int, default=0, metavar="N",
+                    help="clean every --mask sam / --mask-dir plane before it is lifted: holes, then islands, of fewer than N pixels are removed "
+                         "(segment_anything's remove_small_regions, on the device; a deviation from the reference, which lifts the raw plane). "
+                         "--dump-masks writes the cleaned planes. 0 (default): off. Accepted and without effect with --mask box")
     ap.add_argument("--score-threshold", type=float, default=0.30)
     ap.add_argument("--output", required=True, help=".pth (torch.save, as the reference) or .json")
     return ap
@@ -276,6 +300,11 @@ def check_args(args, parser=None):
         raise SystemExit(msg)
     if getattr(args, "sam_refine", 0) < 0 or (getattr(args, "sam_refine", 0) > 0 and args.mask != "sam"):
         msg = "--sam-refine N needs N >= 0 and --mask sam"
+        if parser is not None:
+            parser.error(msg)
+        raise SystemExit(msg)
+    if getattr(args, "min_mask_region_area", 0) < 0:
+        msg = "--min-mask-region-area N needs N >= 0"
         if parser is not None:
             parser.error(msg)
         raise SystemExit(msg)
