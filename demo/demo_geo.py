@@ -55,121 +55,158 @@ import json
 import os
 import sys
 import time
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (os.path.join(ROOT, "tools"), os.path.join(ROOT, "demo"), ROOT):
-    sys.path.insert(0, p)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from demo import add_ply_arguments, write_scene, write_views  # noqa: E402
-from make_oracle2d import build_caption, build_detector, gdino_postprocess, phrase_spans  # noqa: E402
-from ovmono3d_geo import check_args, clean_planes, refined_masks, sam_masks, xywh_to_xyxy  # noqa: E402
-
-from ovmono3d_amd.data.depth_prompt import add_depth_arguments, build_depth_prompt, load_depth  # noqa: E402
+from ovmono3d_amd import vis  # noqa: E402
+from ovmono3d_amd.data.depth_prompt import add_depth_arguments, build_depth_prompt, check_depth_arguments, load_depth  # noqa: E402
 from ovmono3d_amd.data.gpu_jpeg import read_image_device, write_jpeg  # noqa: E402
 from ovmono3d_amd.data.gpu_resize import ResizeShortestEdgeGPU  # noqa: E402
 from ovmono3d_amd.defaults import make_cfg  # noqa: E402
-from ovmono3d_amd.geo import GeoParams, box_to_rect, lift_boxes  # noqa: E402
+from ovmono3d_amd.gdino.detector import build_detector  # noqa: E402
+from ovmono3d_amd.geo import GeoParams, lift_boxes  # noqa: E402
+from ovmono3d_amd.geo.sources import (add_mask_arguments, box_masks, check_mask_arguments, clean_planes, detect_boxes, point_masks,  # noqa: E402
+                                      sam_masks, xywh_to_xyxy)
 from ovmono3d_amd.masks import encode_rle, overlay_masks  # noqa: E402
-
-BOX_THRESHOLD, NMS_THRESHOLD = 0.001, 0.5                            # tools/make_oracle2d.py's defaults
-
-
-def detect_boxes(det, resize, bgr, cats, input_format="BGR"):
-    """The native detector on one device image: (boxes xyxy [n, 4] at the image's resolution - float32 values, as tools/make_oracle2d.py
-    writes them -, scores [n], class index [n])."""
-    caption, _ = build_caption(cats)
-    net = resize(bgr if input_format == "BGR" else bgr.flip(-1))
-    r = det(net.permute(2, 0, 1).contiguous(), caption)
-    boxes, scores, cls = gdino_postprocess(r["pred_logits"], r["pred_boxes"], phrase_spans(r["input_ids"], r["phrase_ids"]), tuple(net.shape[:2]),
-                                           box_threshold=BOX_THRESHOLD, nms_threshold=NMS_THRESHOLD)
-    sy, sx = bgr.shape[0] / net.shape[0], bgr.shape[1] / net.shape[1]                      # network resolution -> original resolution
-    b = boxes.cpu().numpy() * np.array([sx, sy, sx, sy], np.float32)
-    return b.astype(np.float64).reshape(-1, 4), scores.cpu().tolist(), cls.cpu().tolist()
+from ovmono3d_amd.vis.outputs import add_ply_arguments, write_scene, write_views  # noqa: E402
 
 
-def box_masks(boxes_xyxy, h, w, device):
-    """uint8 [n, h, w]: the pixels ``--mask box`` lifts (geo.box_to_rect, clipped to the image)."""
-    planes = torch.zeros((len(boxes_xyxy), h, w), dtype=torch.uint8, device=device)
-    for i, b in enumerate(boxes_xyxy):
-        x0, y0, x1, y1 = box_to_rect(b)
-        planes[i, max(y0, 0):max(min(y1, h), 0), max(x0, 0):max(min(x1, w), 0)] = 1
-    return planes
+# ---- step 1: the 2D instances of one image. One of the four below is chosen per run (build_run); each returns (boxes xyxy float64
+# [n, 4], scores [n], class index [n], the positions that go on to the lift, masks) where masks(boxes of those positions) is step 2:
+# (device uint8 planes [m, H, W] or None: the box is the mask, the positions' boxes)
+def candidates(scores, threshold):
+    return [i for i, s in enumerate(scores) if not s < threshold]
 
 
-def group_point_prompts(entries):
-    """{(point count, has box): [positions in ``entries``]}, in order of first appearance. One predict_prompts call takes prompts of one
-    shape; no prompt is padded with label -1 points to fit another's, so each sees exactly its own tokens."""
-    groups = {}
-    for i, e in enumerate(entries):
-        if len(e["points"]) != len(e["labels"]):
-            raise SystemExit(f"--points-file: entry {i} has {len(e['points'])} points and {len(e['labels'])} labels")
-        groups.setdefault((len(e["points"]), "bbox" in e), []).append(i)
-    return groups
+def box_prompt_masks(args, run, im):
+    """Step 2 for boxes from a file or the detector: Segment Anything prompted with them (None with --mask box), cleaned."""
+    def masks(cboxes):
+        planes = None
+        if run.predictor is not None:
+            planes = sam_masks(run.predictor, None, None, int(im.shape[0]), int(im.shape[1]), cboxes, bgr=im, refine=args.sam_refine)
+        return clean_planes(planes, args.min_mask_region_area), cboxes
+    return masks
 
 
-def point_masks(predictor, bgr, entries, refine=0, min_area=0):
-    """SAM's plane [2] for the click prompts ``entries`` of one image: (device uint8 [n, H, W] in the entries' order, xyxy boxes float64
-    [n, 4]: the entry's own "bbox", else the tight box of its mask - zeros for an empty one). ``min_area`` > 0: the planes are
-    cleaned (``clean_planes``) and the tight boxes are the cleaned masks'."""
-    h, w = int(bgr.shape[0]), int(bgr.shape[1])
-    planes = torch.zeros((len(entries), h, w), dtype=torch.uint8, device=bgr.device)
-    boxes = np.zeros((len(entries), 4), np.float64)
-    if not entries:
-        return planes, boxes
-    predictor.set_image(bgr, image_format="BGR")
-    for (_, has_box), idx in group_point_prompts(entries).items():
-        given = np.asarray([xywh_to_xyxy(entries[i]["bbox"]) for i in idx], np.float64) if has_box else None
-        masks = refined_masks(predictor, refine, point_coords=np.asarray([entries[i]["points"] for i in idx], np.float32),
-                              point_labels=np.asarray([entries[i]["labels"] for i in idx], np.int32), boxes=given)
-        masks = clean_planes(masks, min_area)
-        planes[idx] = masks
-        boxes[idx] = given if has_box else predictor.mask_boxes(masks)[0].cpu().numpy().astype(np.float64)
-    return planes, boxes
+def everything_instances(args, cfg, run, im, im_name, cats):
+    """--everything: the masks come first, their tight boxes are the 2D boxes; --threshold is not applied."""
+    auto = run.generator.generate_device(im, "BGR", min_mask_region_area=args.min_mask_region_area)
+    boxes = auto["boxes"].cpu().numpy().astype(np.float64).reshape(-1, 4)
+    scores = [float(s) for s in auto["scores"].cpu().tolist()]
+    return boxes, scores, [0] * len(boxes), list(range(len(boxes))), lambda cboxes: (auto["masks"], cboxes)
+
+
+def click_instances(args, cfg, run, im, im_name, cats):
+    """--points-file: the 2D boxes come with the masks (the entry's "bbox", else the tight box of its mask)."""
+    entries = run.points.get(im_name, [])
+    scores = [float(e.get("score", 1.0)) for e in entries]
+    cand = candidates(scores, args.threshold)
+
+    def masks(cboxes):
+        return point_masks(run.predictor, im, [entries[i] for i in cand], args.sam_refine, args.min_mask_region_area)
+    return np.zeros((len(entries), 4), np.float64), scores, list(range(len(entries))), cand, masks
+
+
+def file_instances(args, cfg, run, im, im_name, cats):
+    inst = run.boxes.get(im_name, [])
+    boxes = np.asarray([xywh_to_xyxy(b["bbox"]) for b in inst], np.float64).reshape(-1, 4)
+    scores, classes = [float(b.get("score", 1.0)) for b in inst], [int(b["category_id"]) for b in inst]
+    return boxes, scores, classes, candidates(scores, args.threshold), box_prompt_masks(args, run, im)
+
+
+def detector_instances(args, cfg, run, im, im_name, cats):
+    boxes, scores, classes = detect_boxes(run.detector, run.resize, im, cats, cfg.INPUT.FORMAT)
+    return boxes, scores, classes, candidates(scores, args.threshold), box_prompt_masks(args, run, im)
+
+
+def build_run(args, cfg, dev):
+    """What a run builds once: the source of the 2D instances and its files or networks, the names per image (None: every image has
+    the one name "object"), the depth source (None: files) and the SAM predictor (None: --mask box)."""
+    run = SimpleNamespace(names=None, points=None, boxes=None, detector=None, resize=None, depth_source=None, predictor=None, generator=None)
+    if args.everything:                                                      # reads neither names nor boxes nor clicks
+        run.instances = everything_instances
+    elif args.points_file:
+        run.instances = click_instances
+        with open(args.points_file) as f:
+            run.points = json.load(f)
+        run.names = {n: [e["category_name"] for e in entries] for n, entries in run.points.items()}
+    else:
+        with open(args.labels_file) as f:
+            run.names = json.load(f)
+        if args.boxes_file:
+            run.instances = file_instances
+            with open(args.boxes_file) as f:
+                run.boxes = json.load(f)
+        else:
+            run.instances = detector_instances
+            run.detector = build_detector(cfg, dev)
+            run.resize = ResizeShortestEdgeGPU(cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST)
+    if args.depth == "depthpro":
+        run.depth_source = build_depth_prompt(args.depthpro_weights, args.depthpro_focal, args.depthpro_config, args.dump_depth, dev)
+    if args.mask == "sam":
+        from ovmono3d_amd.sam import build_sam
+        run.predictor = build_sam(args.sam_arch, args.sam_weights, device=dev, image_size=args.sam_image_size)
+    if args.everything:
+        from ovmono3d_amd.sam import SamAutomaticMaskGenerator
+        run.generator = SamAutomaticMaskGenerator(run.predictor, points_per_side=args.points_per_side, pred_iou_thresh=args.pred_iou_thresh,
+                                                  stability_score_thresh=args.stability_score_thresh, box_nms_thresh=args.box_nms_thresh)
+    return run
+
+
+# ---- step 3
+def lift_records(depth, K, params, cats, boxes, scores, classes, cand, planes):
+    """lift_boxes on the candidates: (demo.py's records of the lifted ones, their positions among the candidates)."""
+    lifted = lift_boxes(depth, K, boxes_xyxy=boxes[cand], masks=list(planes) if planes is not None else None, params=params)
+    out, kept_idx = [], []
+    for k, (i, box) in enumerate(zip(cand, lifted)):
+        if box is None:
+            continue
+        kept_idx.append(k)
+        ci = classes[i]
+        out.append({"category": cats[ci] if 0 <= ci < len(cats) else ci, "score": float(scores[i]),
+                    "bbox3D": list(box["center_cam"]) + list(box["dimensions"]), "pose": box["pose"], "corners3D": box["bbox3D"],
+                    "center_2D": list(box["center_2D"]), "bbox2D": [float(v) for v in boxes[i]]})
+    return out, kept_idx
+
+
+# ---- step 4
+def write_outputs(args, cfg, im, K, im_name, out, kept_idx, cboxes, planes, depth):
+    """<name>_dets.json, the picture and, where asked for, the scene file and the mask picture; ``planes`` None: the boxes are the masks."""
+    h, w, dev = int(im.shape[0]), int(im.shape[1]), im.device
+    gpu_jpeg, labels = bool(cfg.MODEL.AMD.get("GPU_JPEG_WRITE", True)), None
+    if out and planes is None and (args.show_points or args.segmentation == "rle" or args.show_masks or args.scene_ply):
+        planes = box_masks(cboxes, h, w, dev)
+    if out and (args.show_points or args.scene_ply):
+        labels = vis.labels_from_masks(planes[kept_idx])
+    if out and args.segmentation == "rle":                                   # encoded on the device: only the strings are read back
+        for rec, rle in zip(out, encode_rle(planes[kept_idx])):
+            rec["segmentation"] = rle
+    with open(os.path.join(cfg.OUTPUT_DIR, im_name + "_dets.json"), "w") as f:
+        json.dump({"K": K.tolist(), "detections": out}, f)
+    write_views(im, K, out, kept_idx, cfg.OUTPUT_DIR, im_name, gpu_jpeg=gpu_jpeg, depth=depth if out and args.show_points else None,
+                labels=labels if args.show_points else None)
+    if args.scene_ply:
+        write_scene(args, im, K, out, kept_idx, cfg.OUTPUT_DIR, im_name, depth=depth, labels=labels)
+    if args.show_masks:                                                      # the image under the kept instances' masks, in the boxes' colours
+        shown = overlay_masks(im, planes[kept_idx] if out else torch.zeros((0, h, w), dtype=torch.uint8, device=dev),
+                              [vis.get_color(i) for i in kept_idx], alpha=0.5)
+        write_jpeg(os.path.join(cfg.OUTPUT_DIR, im_name + "_masks.jpg"), shown, quality=95, channel_order="BGR", use_device=gpu_jpeg)
 
 
 def do_test(args, cfg):
-    from ovmono3d_amd import vis
     dev = torch.device("cuda", torch.cuda.current_device())
     ims = sorted(f for f in os.listdir(args.input_folder) if not f.endswith(".json"))
-    cats_per_img, points_per_img = {}, None
-    if args.points_file:
-        with open(args.points_file) as f:
-            points_per_img = json.load(f)
-    elif not args.everything:                                                # --everything reads neither names nor clicks
-        with open(args.labels_file) as f:
-            cats_per_img = json.load(f)
-    boxes_per_img = None
-    if args.boxes_file:
-        with open(args.boxes_file) as f:
-            boxes_per_img = json.load(f)
-    detector = resize = None
-    if boxes_per_img is None and points_per_img is None and not args.everything:
-        detector = build_detector(cfg, dev)
-        resize = ResizeShortestEdgeGPU(cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST)
-    depth_source = None
-    if args.depth == "depthpro":
-        depth_source = build_depth_prompt(args.depthpro_weights, args.depthpro_focal, args.depthpro_config, args.dump_depth, dev)
-    predictor = None
-    if args.mask == "sam":
-        from ovmono3d_amd.sam import build_sam
-        predictor = build_sam(args.sam_arch, args.sam_weights, device=dev, image_size=args.sam_image_size)
-    generator = None
-    if args.everything:
-        from ovmono3d_amd.sam import SamAutomaticMaskGenerator
-        generator = SamAutomaticMaskGenerator(predictor, points_per_side=args.points_per_side, pred_iou_thresh=args.pred_iou_thresh,
-                                              stability_score_thresh=args.stability_score_thresh, box_nms_thresh=args.box_nms_thresh)
+    run = build_run(args, cfg, dev)
     params = GeoParams()
     focal_length, principal_point = args.focal_length, args.principal_point
     os.makedirs(cfg.OUTPUT_DIR, exist_ok=True)
     for name in ims:
         im_name = os.path.splitext(name)[0]
-        entries = points_per_img.get(im_name, []) if points_per_img is not None else None
-        cats = cats_per_img.get(im_name, []) if entries is None else [e["category_name"] for e in entries]
-        if generator is not None:
-            cats = ["object"]
+        cats = ["object"] if run.names is None else run.names.get(im_name, [])
         if cats == []:
             continue
         stages, t0 = {}, time.perf_counter()
@@ -189,67 +226,21 @@ def do_test(args, cfg):
         px, py = (w / 2, h / 2) if len(principal_point) == 0 else principal_point
         K = np.array([[focal_length, 0.0, px], [0.0, focal_length, py], [0.0, 0.0, 1.0]])
         lap("read")
-        auto = None
-        if generator is not None:                                            # masks first: their tight boxes are the 2D boxes
-            auto = generator.generate_device(im, "BGR", min_mask_region_area=args.min_mask_region_area)
-            boxes = auto["boxes"].cpu().numpy().astype(np.float64).reshape(-1, 4)
-            scores, classes = [float(s) for s in auto["scores"].cpu().tolist()], [0] * len(boxes)
-        elif entries is not None:                                            # the 2D boxes come with the masks, below
-            boxes = np.zeros((len(entries), 4), np.float64)
-            scores, classes = [float(e.get("score", 1.0)) for e in entries], list(range(len(entries)))
-        elif boxes_per_img is not None:
-            inst = boxes_per_img.get(im_name, [])
-            boxes = np.asarray([xywh_to_xyxy(b["bbox"]) for b in inst], np.float64).reshape(-1, 4)
-            scores, classes = [float(b.get("score", 1.0)) for b in inst], [int(b["category_id"]) for b in inst]
-        else:
-            boxes, scores, classes = detect_boxes(detector, resize, im, cats, cfg.INPUT.FORMAT)
-        cand = [i for i, s in enumerate(scores) if auto is not None or not s < args.threshold]
+        boxes, scores, classes, cand, masks = run.instances(args, cfg, run, im, im_name, cats)
         lap("boxes")
-        out, kept_idx, labels, depth = [], [], None, None
+        out, kept_idx, planes, depth = [], [], None, None
         if cand:
-            if depth_source is not None:
-                depth = depth_source(im, "BGR", K, file_name=name)
+            if run.depth_source is not None:
+                depth = run.depth_source(im, "BGR", K, file_name=name)
             else:
                 depth = torch.from_numpy(load_depth(args.depth_dir, name, h, w)).to(dev)
             lap("depth")
-            if entries is not None:
-                planes, boxes[cand] = point_masks(predictor, im, [entries[i] for i in cand], args.sam_refine, args.min_mask_region_area)
-            cboxes = boxes[cand]
-            if auto is not None:
-                planes = auto["masks"]
-            elif entries is None:
-                planes = sam_masks(predictor, None, None, h, w, cboxes, bgr=im, refine=args.sam_refine) if predictor is not None else None
-                planes = clean_planes(planes, args.min_mask_region_area)
+            planes, boxes[cand] = masks(boxes[cand])
             lap("masks")
-            lifted = lift_boxes(depth, K, boxes_xyxy=cboxes, masks=list(planes) if planes is not None else None, params=params)
+            out, kept_idx = lift_records(depth, K, params, cats, boxes, scores, classes, cand, planes)
             lap("lift")
-            for k, (i, box) in enumerate(zip(cand, lifted)):
-                if box is None:
-                    continue
-                kept_idx.append(k)
-                ci = classes[i]
-                out.append({"category": cats[ci] if 0 <= ci < len(cats) else ci, "score": float(scores[i]),
-                            "bbox3D": list(box["center_cam"]) + list(box["dimensions"]), "pose": box["pose"], "corners3D": box["bbox3D"],
-                            "center_2D": list(box["center_2D"]), "bbox2D": [float(v) for v in boxes[i]]})
-            if out and planes is None and (args.show_points or args.segmentation == "rle" or args.show_masks or args.scene_ply):
-                planes = box_masks(cboxes, h, w, dev)
-            if out and (args.show_points or args.scene_ply):
-                labels = vis.labels_from_masks(planes[kept_idx])
-            if out and args.segmentation == "rle":                               # encoded on the device: only the strings are read back
-                for rec, rle in zip(out, encode_rle(planes[kept_idx])):
-                    rec["segmentation"] = rle
         print("File: {} with {} dets ({} boxes at or above the threshold, {} not lifted)".format(im_name, len(out), len(cand), len(cand) - len(out)))
-        with open(os.path.join(cfg.OUTPUT_DIR, im_name + "_dets.json"), "w") as f:
-            json.dump({"K": K.tolist(), "detections": out}, f)
-        write_views(im, K, out, kept_idx, cfg.OUTPUT_DIR, im_name, gpu_jpeg=bool(cfg.MODEL.AMD.get("GPU_JPEG_WRITE", True)),
-                    depth=depth if out and args.show_points else None, labels=labels if args.show_points else None)
-        if args.scene_ply:
-            write_scene(args, im, K, out, kept_idx, cfg.OUTPUT_DIR, im_name, depth=depth, labels=labels)
-        if args.show_masks:                                                      # the image under the kept instances' masks, in the boxes' colours
-            shown = overlay_masks(im, planes[kept_idx] if out else torch.zeros((0, h, w), dtype=torch.uint8, device=dev),
-                                  [vis.get_color(i) for i in kept_idx], alpha=0.5)
-            write_jpeg(os.path.join(cfg.OUTPUT_DIR, im_name + "_masks.jpg"), shown, quality=95, channel_order="BGR",
-                       use_device=bool(cfg.MODEL.AMD.get("GPU_JPEG_WRITE", True)))
+        write_outputs(args, cfg, im, K, im_name, out, kept_idx, boxes[cand], planes, depth)
         lap("views")
         if args.stage_times:
             print("stage_ms " + json.dumps({"image": im_name, **stages}))
@@ -269,20 +260,13 @@ def argument_parser():
     parser.add_argument("--pred-iou-thresh", type=float, default=0.88, help="--everything: keep masks whose predicted IoU is above it")
     parser.add_argument("--stability-score-thresh", type=float, default=0.95, help="--everything: keep masks whose stability score is at least it")
     parser.add_argument("--box-nms-thresh", type=float, default=0.7, help="--everything: box IoU above which the lower-scored mask is dropped")
-    parser.add_argument("--sam-refine", type=int, default=0, metavar="N",
-                        help="--mask sam: N more passes per prompt with the previous pass's low-resolution logits as mask_input (default 0)")
     parser.add_argument("--boxes-file", type=str, default="", help="2D boxes per image ({image name: [{bbox xywh, category_id, score}]}) instead of the detector")
     parser.add_argument("--focal-length", type=float, default=0, help="focal length for image inputs (in px)")
     parser.add_argument("--principal-point", type=float, default=[], nargs=2, help="principal point for image inputs (in px)")
     parser.add_argument("--threshold", type=float, default=0.30, help="2D boxes scoring below it are dropped (the reference GEO's cut)")
     add_depth_arguments(parser, choices=("depthpro", "files"), default="depthpro",
                         focal_help="the K[0][0] of this run: --focal-length, or without it the reference's convention 4.0 * h / 2 of the first image")
-    parser.add_argument("--mask", choices=("sam", "box"), default="sam",
-                        help="sam: Segment Anything prompted with the box, plane [2] of its multimask outputs (the reference's rule); "
-                             "box: the 2D box is the mask")
-    parser.add_argument("--sam-weights", default=None, help="segment_anything checkpoint (.pth)")
-    parser.add_argument("--sam-arch", default="vit_l", help="vit_b or vit_l (vit_h has head dimension 80: refused)")
-    parser.add_argument("--sam-image-size", type=int, default=None, help=argparse.SUPPRESS)      # tests: a small encoder input
+    add_mask_arguments(parser, choices=("sam", "box"), default="sam")
     parser.add_argument("--stage-times", action="store_true", help=argparse.SUPPRESS)            # measurements: synchronise and print per-stage ms
     parser.add_argument("--show-points", default=True, action=argparse.BooleanOptionalAction,
                         help="draw the depth map as a point cloud under the boxes of the novel view, tinted per box")
@@ -291,11 +275,6 @@ def argument_parser():
                              "(every mask source; encoded on the device)")
     parser.add_argument("--show-masks", action="store_true",
                         help="also write <name>_masks.jpg: the image with the kept instances' masks overlaid in the boxes' colours (alpha 0.5, contours)")
-    parser.add_argument("--min-mask-region-area", type=int, default=0, metavar="N",
-                        help="clean the masks before they are lifted: holes, then islands, of fewer than N pixels are removed (segment_anything's "
-                             "remove_small_regions, on the device). --everything: the generator's min_mask_region_area; box and click prompts: the "
-                             "planes before the lift. A deviation from the reference, which lifts the raw plane. 0 (default): off. Accepted and "
-                             "without effect with --mask box")
     add_ply_arguments(parser)
     parser.add_argument("opts", default=None, nargs=argparse.REMAINDER,
                         help="Modify config options by adding 'KEY VALUE' pairs at the end of the command.")
@@ -304,7 +283,8 @@ def argument_parser():
 
 def check_arguments(args, parser):
     """Exit status 2 for what cannot work, before any device call."""
-    check_args(args, parser)                                                 # --depth-dir with --depth files only, --sam-refine (tools/ovmono3d_geo.py)
+    check_depth_arguments(args, parser, None, files_need_dir=True)
+    check_mask_arguments(args, parser)
     if args.everything:
         if args.points_file or args.boxes_file:
             parser.error("--everything proposes its own masks: it takes neither --points-file nor --boxes-file")
@@ -318,10 +298,6 @@ def check_arguments(args, parser):
         parser.error("--points-file and --boxes-file both replace the detector: give one")
     if not args.points_file and not args.labels_file and not args.everything:
         parser.error("the following arguments are required: --labels-file (or --points-file)")
-    if args.depth == "depthpro" and not args.depthpro_weights:
-        parser.error("--depth depthpro needs --depthpro-weights FILE")
-    if args.depth != "depthpro" and args.dump_depth:
-        parser.error("--dump-depth writes the depth that --depth depthpro computes")
     if args.mask == "sam" and not args.sam_weights:
         parser.error("--mask sam needs --sam-weights FILE")
     return args

@@ -8,8 +8,9 @@ Sources: ``.npz`` files made elsewhere (``load_depth``: ``<dir>/test/<image base
 (to the image's size, dataset_mapper.py:45-52, then ResizeShortestEdge's, :70-72). ``DatasetMapper3D`` and ``demo/demo.py`` both call
 it, so one image gets one prompt on either entry point, and the inline route gives the bits of the file route.
 
-``add_depth_arguments`` / ``check_depth_arguments`` are the command-line flags of this choice for ``demo/demo.py`` and
-``tools/train_net.py`` (the ones ``tools/ovmono3d_geo.py`` has); the checks run on the host, before any device call.
+``add_depth_arguments`` / ``check_depth_arguments`` are the command-line flags of this choice, declared here alone, for
+``demo/demo.py``, ``tools/train_net.py`` and the two OVMono3D-GEO front ends (``tools/ovmono3d_geo.py``, ``demo/demo_geo.py``, which
+lift the map instead of prompting a model with it); the checks run on the host, before any device call.
 """
 from __future__ import annotations
 
@@ -153,10 +154,11 @@ def depth_prompt_unread(cfg) -> Optional[str]:
 
 
 def add_depth_arguments(parser, choices=("files", "depthpro"), default="files", focal_help="the dataset's K[0][0]") -> None:
-    """The depth flags of tools/ovmono3d_geo.py, for an entry point of the model that owns a depth branch."""
+    """The depth flags of every entry point: the depth prompt of a model that owns a depth branch, or the map OVMono3D-GEO lifts."""
     what = {"none": "none: no depth prompt", "files": "files: read --depth-dir", "depthpro": "depthpro: run Depth Pro on the device on the image itself"}
     parser.add_argument("--depth", choices=tuple(choices), default=default,
-                        help="(native build) where the depth prompt of a depth-fusion checkpoint comes from; " + "; ".join(what[c] for c in choices))
+                        help="(native build) where the metric depth comes from - the depth prompt of a depth-fusion checkpoint, or the map "
+                             "OVMono3D-GEO lifts; " + "; ".join(what[c] for c in choices))
     parser.add_argument("--depth-dir", default=None, help="(native build) folder of depth-prompt .npz files (key 'depth', metres): "
                         "<dir>/test/<image base name>.npz; refused with --depth depthpro, which would not read it")
     parser.add_argument("--depthpro-weights", default=None, help="(native build) Depth Pro checkpoint in Hugging Face key names (torch file or "
@@ -169,9 +171,10 @@ def add_depth_arguments(parser, choices=("files", "depthpro"), default="files", 
                         "<DIR>/<image base name>.npz, the files --depth-dir reads (from <DIR> or <DIR>/test)")
 
 
-def check_depth_arguments(args, parser, make_cfg, files_need_dir: bool = False):
+def check_depth_arguments(args, parser, make_cfg=None, files_need_dir: bool = False):
     """argparse errors (exit status 2) for the combinations that cannot work; host only. ``make_cfg()`` builds the configuration and is
-    called only when a depth was asked for."""
+    called only when a depth was asked for; None for an entry point without a model (OVMono3D-GEO lifts the depth itself): nothing
+    is asked of a configuration."""
     if args.depth == "depthpro":
         if not args.depthpro_weights:
             parser.error("--depth depthpro needs --depthpro-weights FILE")
@@ -194,7 +197,7 @@ def check_depth_arguments(args, parser, make_cfg, files_need_dir: bool = False):
         parser.error("--depth files needs --depth-dir DIR")
     if args.depth == "none" and args.depth_dir:
         parser.error("--depth-dir is read with --depth files")
-    if args.depth == "depthpro" or (args.depth == "files" and files_need_dir):
+    if make_cfg is not None and (args.depth == "depthpro" or (args.depth == "files" and files_need_dir)):
         why = depth_prompt_unread(make_cfg())
         if why:
             parser.error(f"--depth {args.depth}: nothing would read the depth ({why})")

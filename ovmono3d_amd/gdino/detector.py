@@ -179,3 +179,20 @@ class NativeGroundingDino:
         ids, phrase_ids, _ = self._tokens(caption)
         logits, boxes = self.engine.forward(im, ids)
         return {"pred_logits": logits, "pred_boxes": boxes, "input_ids": ids, "phrase_ids": phrase_ids}
+
+
+def build_detector(cfg, device) -> NativeGroundingDino:
+    """The detector of a configuration: ``MODEL.AMD.GDINO_WEIGHTS`` (a checkpoint file, tokenised with ``MODEL.AMD.BERT_VOCAB``, or
+    ``synthetic://gdino?arch=swinb|swint&seed=N``: seeded random weights and the hash tokenizer)."""
+    from ..checkpoint import load_state_dict_file
+    from ..modeling.roi_heads.gdino_glue import WordPieceTokenizer
+    path = cfg.MODEL.AMD.GDINO_WEIGHTS
+    if path.startswith("synthetic://"):
+        from ..util.synth_gdino_weights import synth_gdino_state_dict
+        arch, seed = synthetic_spec(path)
+        sd, tok = synth_gdino_state_dict(seed, arch), HashTokenizer()
+    else:
+        sd, tok = load_state_dict_file(path), WordPieceTokenizer(cfg.MODEL.AMD.BERT_VOCAB)
+    # no architecture record is passed: the checkpoint's shapes decide (Swin-B or Swin-T)
+    return NativeGroundingDino(device, sd, tok, cfg.MODEL.PIXEL_MEAN, cfg.MODEL.PIXEL_STD,
+                               precision=3 if cfg.MODEL.AMD.GEMM_PRECISION == "f16x3" else 1)

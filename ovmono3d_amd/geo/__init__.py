@@ -4,7 +4,8 @@
 one image in one call of ``ovm_geo_lift`` (ovmono3d_amd/csrc/geo.hip), then builds the reference's record fields on the host with
 ``ovm_host_geo_box``. Of the two networks the reference runs in front of it, SAM is ``ovmono3d_amd.sam`` (its ``predict_boxes``
 planes are device tensors ``masks`` takes as they are); Depth Pro is not here: the depth map arrives as an array. Masks may also
-come from files, or the 2D box itself is the mask.
+come from files, or the 2D box itself is the mask: ``geo.sources`` holds every source of boxes and masks the two front ends
+(tools/ovmono3d_geo.py, demo/demo_geo.py) put in front of ``lift_boxes``, and their command-line flags.
 """
 from __future__ import annotations
 

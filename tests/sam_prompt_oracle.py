@@ -197,7 +197,7 @@ def mask_weights(sd):
 
 # ---- demo/demo_geo.py --points-file: the entries of one image as the tool groups them --------------------------------------------
 def group_reference(entries):
-    """{(P, has_box): [entry index, ...]} in first-appearance order: the rule of demo_geo.group_point_prompts restated."""
+    """{(P, has_box): [entry index, ...]} in first-appearance order: the rule of ovmono3d_amd.geo.sources.group_point_prompts restated."""
     out = {}
     for i, e in enumerate(entries):
         out.setdefault((len(e["points"]), "bbox" in e), []).append(i)

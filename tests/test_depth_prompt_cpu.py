@@ -70,16 +70,17 @@ def test_synthetic_depthpro_spec():
 
 
 def test_geo_tool_keeps_its_depth_file_helpers(tmp_path):
-    """dump_depth / load_depth moved into the package; tools/ovmono3d_geo.py imports them and a dumped map is found again, under
-    <dir> and under <dir>/test, with GEO's shape check only when a size is given."""
+    """dump_depth / load_depth live in the package; tools/ovmono3d_geo.py reads with that load_depth (Depth Pro's maps are dumped by
+    DepthProPrompt, with that dump_depth) and a dumped map is found again, under <dir> and under <dir>/test, with GEO's shape check only
+    when a size is given."""
     import importlib.util
     from ovmono3d_amd.data import depth_prompt
     spec = importlib.util.spec_from_file_location("geo_for_depth_prompt", os.path.join(ROOT, "tools", "ovmono3d_geo.py"))
     geo = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(geo)
-    assert geo.dump_depth is depth_prompt.dump_depth and geo.load_depth is depth_prompt.load_depth
+    assert geo.load_depth is depth_prompt.load_depth
     ramp = torch.arange(12, dtype=torch.float32).reshape(3, 4) / 7
-    geo.dump_depth(str(tmp_path / "test"), "some/where/a.b.jpg", ramp)
+    depth_prompt.dump_depth(str(tmp_path / "test"), "some/where/a.b.jpg", ramp)
     assert (tmp_path / "test" / "a.b.npz").exists()
     got = geo.load_depth(str(tmp_path), "other/a.b.png", 3, 4)
     assert got.dtype == np.float32 and np.array_equal(got, ramp.numpy())

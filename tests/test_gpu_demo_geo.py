@@ -1,6 +1,7 @@
 """GPU: demo/demo_geo.py - OVMono3D-GEO on a folder of images - writes what its parts give in-process: every field of
 <name>_dets.json is geo.lift_boxes' on the same depth, K, boxes and masks (exact after the JSON round trip), the 2D boxes of the
-detector route are build_detector + gdino_postprocess', and the picture is demo.py's."""
+detector route are build_detector + gdino_postprocess', the picture is demo.py's, and tools/ovmono3d_geo.py on the same boxes gives the same
+records."""
 import importlib.util
 import json
 import os
@@ -121,9 +122,9 @@ def test_boxes_file_box_masks(device, tmp_path):
 
 def test_boxes_file_sam_masks(device, tmp_path):
     from ovmono3d_amd.geo import lift_boxes
+    from ovmono3d_amd.geo.sources import sam_masks
     from ovmono3d_amd.sam import build_sam
     from ovmono3d_amd.util.synth_sam_weights import synth_sam_predictor_state_dict
-    tool = _tool("ovmono3d_geo")
     inp, maps, names = _setup(tmp_path)
     weights = str(tmp_path / "sam_vit_test.pth")
     torch.save(synth_sam_predictor_state_dict("vit_test", seed=3, image_size=128), weights)
@@ -136,7 +137,7 @@ def test_boxes_file_sam_masks(device, tmp_path):
         H, W = SIZES[k]
         inst = _boxes(H, W)
         boxes = _cand_boxes(inst)
-        planes = tool.sam_masks(predictor, str(inp), n + ".jpg", H, W, boxes)
+        planes = sam_masks(predictor, str(inp), n + ".jpg", H, W, boxes)
         lifted = lift_boxes(torch.from_numpy(_depth(H, W)).to(device), _K(k), boxes_xyxy=boxes, masks=list(planes))
         expected.append(_expected(inst, lifted))
     _check_outputs(out, names, expected, r.stdout)
@@ -145,12 +146,13 @@ def test_boxes_file_sam_masks(device, tmp_path):
 def test_detector_route(device, tmp_path):
     from ovmono3d_amd.data.feeding import ResizeShortestEdge, read_image
     from ovmono3d_amd.defaults import make_cfg
+    from ovmono3d_amd.gdino.detector import build_detector
     from ovmono3d_amd.geo import lift_boxes
-    oracle2d = _tool("make_oracle2d")
+    from ovmono3d_amd.modeling.roi_heads import gdino_glue as oracle2d
     inp, maps, names = _setup(tmp_path, n=1)
     opts = ["MODEL.AMD.GDINO_WEIGHTS", "synthetic://gdino?arch=swint&seed=1", "INPUT.MIN_SIZE_TEST", "210", "INPUT.MAX_SIZE_TEST", "280"]
     cfg = make_cfg(CONFIG, opts)
-    det = oracle2d.build_detector(cfg, device)
+    det = build_detector(cfg, device)
     H, W = SIZES[0]
     net = ResizeShortestEdge(cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST)(read_image(str(inp / "img000.jpg"), cfg.INPUT.FORMAT))
     r = det(torch.as_tensor(np.ascontiguousarray(net.transpose(2, 0, 1))).to(device), oracle2d.build_caption(CATS)[0])
@@ -174,6 +176,50 @@ def test_detector_route(device, tmp_path):
     assert [x["bbox2D"] for x in d] == [want[i] for i in keep]
     assert [x["category"] for x in d] == [want_cat[i] for i in keep]
     assert [x["corners3D"] for x in d] == json.loads(json.dumps([lifted[i]["bbox3D"] for i in keep]))
+
+
+@pytest.mark.parametrize("mask", ["box", "sam"])
+def test_tool_and_demo_are_the_same_pipeline(device, tmp_path, mask):
+    """tools/ovmono3d_geo.py and demo/demo_geo.py --boxes-file on the same images, depth files, boxes and K: every lifted instance's
+    record fields are equal, value for value, and the two leave out the same instances."""
+    inp, maps, names = _setup(tmp_path)
+    f, px, py = 110.0, 60.5, 50.25                                   # one K for both images: the demo's flags hold for the whole folder
+    Kmat = [[f, 0.0, px], [0.0, f, py], [0.0, 0.0, 1.0]]
+    images = [{"id": 10 + k, "file_path": n + ".jpg", "height": H, "width": W, "K": Kmat, "dataset_id": 0} for k, (n, (H, W)) in enumerate(zip(names, SIZES))]
+    oracle = [{"image_id": 10 + k, "K": Kmat, "instances": _boxes(*hw)} for k, hw in enumerate(SIZES)]
+    (tmp_path / "synth.json").write_text(json.dumps({"info": {"name": "synth"}, "images": images, "annotations": [], "categories": []}))
+    (tmp_path / "oracle_2d.json").write_text(json.dumps(oracle))
+    sam = []
+    if mask == "sam":
+        from ovmono3d_amd.util.synth_sam_weights import synth_sam_predictor_state_dict
+        weights = str(tmp_path / "sam_vit_test.pth")
+        torch.save(synth_sam_predictor_state_dict("vit_test", seed=3, image_size=128), weights)
+        sam = ["--sam-weights", weights, "--sam-arch", "vit_test", "--sam-image-size", "128"]
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "ovmono3d_geo.py"), "--oracle2d", str(tmp_path / "oracle_2d.json"), "--dataset",
+                        str(tmp_path / "synth.json"), "--depth", "files", "--depth-dir", str(maps), "--image-root", str(inp), "--mask", mask, *sam,
+                        "--output", str(tmp_path / "tool.json")], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-1000:] + r.stderr[-3000:]
+    stats = json.loads(r.stdout.strip().splitlines()[-1])
+    out = tmp_path / "out"
+    run = _run(tmp_path, inp, out, "--boxes-file", str(tmp_path / "boxes.json"), "--depth", "files", "--depth-dir", str(maps), "--mask", mask, *sam,
+               "--focal-length", repr(f), "--principal-point", repr(px), repr(py))
+    tool = json.loads((tmp_path / "tool.json").read_text())
+    n_lifted = 0
+    for rec, n in zip(tool, names):
+        d = json.loads((out / f"{n}_dets.json").read_text())
+        assert d["K"] == Kmat
+        ins, dets = rec["instances"], d["detections"]
+        # the same instances are lifted, in the same order: the tool keeps the xywh box it was given, the demo writes it as xyxy
+        assert [[b[0], b[1], b[0] + b[2], b[1] + b[3]] for b in (i["bbox"] for i in ins)] == [x["bbox2D"] for x in dets], n
+        assert len(ins) >= 1
+        for i, x in zip(ins, dets):
+            assert i["center_cam"] == x["bbox3D"][:3] and i["dimensions"] == x["bbox3D"][3:], n
+            assert i["pose"] == x["pose"] and i["bbox3D"] == x["corners3D"] and i["center_2D"] == x["center_2D"], n
+        assert f"File: {n} with {len(ins)} dets (3 boxes at or above the threshold, {3 - len(ins)} not lifted)" in run.stdout
+        n_lifted += len(ins)
+    assert stats["lifted"] == n_lifted and stats["skipped"] == 3 * len(names) - n_lifted
+    if mask == "box":
+        assert stats["skipped"] == len(names)                        # the box outside the image, in both
 
 
 def test_threshold_above_every_score_writes_boxes_jpg(device, tmp_path):

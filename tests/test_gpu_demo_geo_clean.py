@@ -27,7 +27,7 @@ def test_demo_geo_lifts_the_cleaned_planes(device, tmp_path):
     from ovmono3d_amd.geo import lift_boxes
     from ovmono3d_amd.sam import build_sam
     from ovmono3d_amd.util.synth_sam_weights import synth_sam_predictor_state_dict
-    tool = _tool("ovmono3d_geo")
+    from ovmono3d_amd.geo import sources as tool
     inp, maps, names = _setup(tmp_path, n=1)
     weights = str(tmp_path / "sam_vit_test.pth")
     torch.save(synth_sam_predictor_state_dict("vit_test", seed=3, image_size=128), weights)

@@ -2,7 +2,6 @@
 field of <name>_dets.json is geo.lift_boxes' on the masks predict_prompts returns for the same clicks (exact after the JSON round
 trip), the 2D box the entry's own or mask_boxes' of its mask; --sam-refine 1 is the in-process two-pass result and --sam-refine 0 the
 run without the flag, byte for byte."""
-import importlib.util
 import json
 import os
 import subprocess
@@ -27,16 +26,6 @@ ENTRIES = [{"points": [[40.0, 30.0]], "labels": [1], "category_name": "chair"},
            {"points": [[64.0, 48.0]], "labels": [1], "category_name": "lamp", "bbox": [30.0, 20.0, 70.0, 50.0], "score": 0.6},
            {"points": [[100.0, 20.0]], "labels": [1], "category_name": "chair"},
            {"points": [[10.0, 10.0]], "labels": [1], "category_name": "sofa", "score": 0.1}]
-
-
-def _tool(folder, name):
-    for p in (os.path.join(ROOT, "tools"), os.path.join(ROOT, "demo")):
-        if p not in sys.path:
-            sys.path.insert(0, p)
-    spec = importlib.util.spec_from_file_location("tool_" + name, os.path.join(ROOT, folder, name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 def _depth():
@@ -141,7 +130,7 @@ def test_sam_refine_on_boxes_and_refine_0_is_the_run_without_the_flag(device, sc
     plain = (tmp_path / "plain" / f"{NAME}_dets.json").read_bytes()
     assert plain == (tmp_path / "zero" / f"{NAME}_dets.json").read_bytes()
     # in-process: the box pass, then the same boxes with plane 2's logits as mask input
-    geo = _tool("tools", "ovmono3d_geo")
+    from ovmono3d_amd.geo import sources as geo
     pred = build_sam("vit_test", scene[3], device=device, image_size=128)
     inst = json.loads((root / "boxes.json").read_text())[NAME]
     boxes = np.asarray([geo.xywh_to_xyxy(b["bbox"]) for b in inst], np.float64)

@@ -218,8 +218,6 @@ def test_generate_signatures_carry_the_keyword_and_the_constructor_keeps_refusin
 
 
 def _tool(folder, name):
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    sys.path.insert(0, os.path.join(ROOT, "demo"))
     spec = importlib.util.spec_from_file_location("cc_tool_" + name, os.path.join(ROOT, folder, name + ".py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
@@ -238,6 +236,7 @@ def test_both_argument_parsers_know_the_flag():
     assert a.min_mask_region_area == 9 and geo.check_args(a) is a
     with pytest.raises(SystemExit):
         geo.check_args(geo.argument_parser().parse_args(base + ["--min-mask-region-area", "-1"]))
-    assert geo.clean_planes(None, 5) is None and geo.clean_planes([], 5) == []
+    from ovmono3d_amd.geo.sources import clean_planes
+    assert clean_planes(None, 5) is None and clean_planes([], 5) == []
     planes = [np.zeros((2, 2), np.uint8)]
-    assert geo.clean_planes(planes, 0) is planes                         # off: what was given, untouched, no device
+    assert clean_planes(planes, 0) is planes                         # off: what was given, untouched, no device

@@ -1,7 +1,6 @@
 """SAM's point, box + point and mask-input prompts, checks that need no GPU: the condition of every mask the GPU tests threshold (on
 the reference alone), the token order and padding rule of the restatement against Hugging Face's prompt encoder, the mask-embedding
 restatement against HF's, the argument refusals of ``ovmono3d_amd.sam`` and of demo/demo_geo.py, and the tool's grouping rule."""
-import importlib.util
 import os
 import subprocess
 import sys
@@ -167,15 +166,6 @@ def test_library_refuses_bad_prompt_shapes_without_a_handle():
     assert L.ovm_sam_mask_boxes(None, 0, 4, 5, None, None, None) == 0         # no masks: nothing to do
 
 
-def _demo_geo():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    sys.path.insert(0, os.path.join(ROOT, "demo"))
-    spec = importlib.util.spec_from_file_location("demo_geo_under_test", os.path.join(ROOT, "demo", "demo_geo.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 @pytest.mark.parametrize("extra,msg", [(["--mask", "box"], "needs --mask sam"), (["--boxes-file", "b.json", "--sam-weights", "w"], "give one"),
                                        (["--sam-weights", "w", "--sam-refine", "-1"], "--sam-refine")])
 def test_points_file_refusals_of_demo_geo(extra, msg):
@@ -186,7 +176,7 @@ def test_points_file_refusals_of_demo_geo(extra, msg):
 
 
 def test_points_file_grouping_rule():
-    g = _demo_geo()
+    from ovmono3d_amd.geo import sources as g
     entries = [{"points": [[1, 2]], "labels": [1]},
                {"points": [[1, 2], [3, 4]], "labels": [1, 0]},
                {"points": [[5, 6]], "labels": [1], "bbox": [0, 0, 9, 9]},

@@ -28,23 +28,8 @@ import torch  # noqa: E402
 
 from ovmono3d_amd.data.feeding import ResizeShortestEdge, load_omni3d_json, read_image  # noqa: E402
 from ovmono3d_amd.defaults import make_cfg  # noqa: E402
+from ovmono3d_amd.gdino.detector import build_detector  # noqa: E402
 from ovmono3d_amd.modeling.roi_heads.gdino_glue import build_caption, gdino_postprocess, phrase_spans  # noqa: E402
-
-
-def build_detector(cfg, device):
-    from ovmono3d_amd.checkpoint import load_state_dict_file
-    from ovmono3d_amd.gdino.detector import HashTokenizer, NativeGroundingDino, synthetic_spec
-    from ovmono3d_amd.modeling.roi_heads.gdino_glue import WordPieceTokenizer
-    path = cfg.MODEL.AMD.GDINO_WEIGHTS
-    if path.startswith("synthetic://"):
-        from ovmono3d_amd.util.synth_gdino_weights import synth_gdino_state_dict
-        arch, seed = synthetic_spec(path)             # synthetic://gdino?arch=swinb|swint&seed=N
-        sd, tok = synth_gdino_state_dict(seed, arch), HashTokenizer()
-    else:
-        sd, tok = load_state_dict_file(path), WordPieceTokenizer(cfg.MODEL.AMD.BERT_VOCAB)
-    # no architecture record is passed: the checkpoint's shapes decide (Swin-B or Swin-T)
-    return NativeGroundingDino(device, sd, tok, cfg.MODEL.PIXEL_MEAN, cfg.MODEL.PIXEL_STD,
-                               precision=3 if cfg.MODEL.AMD.GEMM_PRECISION == "f16x3" else 1)
 
 
 def main():

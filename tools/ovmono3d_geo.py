@@ -58,112 +58,21 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from ovmono3d_amd.data.depth_prompt import dump_depth, load_depth  # noqa: E402,F401
+from ovmono3d_amd.data.depth_prompt import add_depth_arguments, build_depth_prompt, check_depth_arguments, load_depth  # noqa: E402
 from ovmono3d_amd.geo import GeoParams, lift_boxes  # noqa: E402
+from ovmono3d_amd.geo.sources import (add_mask_arguments, check_mask_arguments, clean_planes, dump_masks, load_masks, planes_on_device,  # noqa: E402
+                                      read_bgr, sam_masks, xywh_to_xyxy)
 
 logger = logging.getLogger("ovmono3d_geo")
 KEPT_KEYS = ("category_id", "bbox", "score", "category_name")
 
 
-def xywh_to_xyxy(b):
-    x, y, w, h = b
-    return [x, y, x + w, y + h]
-
-
 def lift_image(depth, K, boxes_xyxy, masks, params):
-    """depth: float32 [H, W], numpy or a device tensor; masks: a list of uint8 [H, W] planes (numpy arrays or device tensors) or None (the box is the
-    mask). One device call."""
+    """depth: float32 [H, W], numpy or a device tensor; masks: uint8 [H, W] planes (a list of numpy arrays or device tensors, or a device
+    [n, H, W] tensor) or None (the box is the mask). One device call."""
     dev = torch.device("cuda", torch.cuda.current_device())
     d = depth.to(dev) if isinstance(depth, torch.Tensor) else torch.from_numpy(depth).to(dev)
-    m = None if masks is None else [x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in masks]
-    return lift_boxes(d, K, boxes_xyxy=boxes_xyxy, masks=m, params=params)
-
-
-def read_bgr(image_root, file_path, height, width, dev):
-    """The image as cv2.imread gives it, on the device: uint8 [H, W, 3], BGR."""
-    from ovmono3d_amd.data.gpu_jpeg import read_image_device
-    path = os.path.join(image_root, file_path)
-    if not os.path.exists(path):
-        raise SystemExit(f"no image {path} (--image-root)")
-    bgr = read_image_device(path, "BGR", dev)
-    if tuple(bgr.shape[:2]) != (height, width):
-        raise SystemExit(f"{path}: image is {tuple(bgr.shape[:2])} but the dataset says {(height, width)}")
-    return bgr
-
-
-def refined_masks(predictor, refine, mask_index=2, **prompts):
-    """Device uint8 [n, H, W]: plane ``mask_index`` of ``predict_prompts(**prompts)``, then ``refine`` more passes of the same prompts
-    with the previous pass's low-resolution logits of that plane as ``mask_inputs``."""
-    masks, _, low = predictor.predict_prompts(mask_index=mask_index, want_lowres=refine > 0, **prompts)
-    for k in range(refine):
-        masks, _, low = predictor.predict_prompts(mask_inputs=low[:, mask_index].contiguous(), mask_index=mask_index, want_lowres=k + 1 < refine,
-                                                  **prompts)
-    return masks
-
-
-def sam_masks(predictor, image_root, file_path, height, width, boxes_xyxy, bgr=None, refine=0):
-    """Device uint8 [n, H, W]: SAM's plane [2] for every box of one image (one set_image, one predict_boxes; ``refine`` > 0: that many
-    refinement passes behind it, ``refined_masks``)."""
-    if bgr is None:
-        bgr = read_bgr(image_root, file_path, height, width, predictor.engine.dev)
-    predictor.set_image(bgr, image_format="BGR")   # the reference's call (run_seg_anything): a cv2 BGR array, declared as such
-    if refine > 0 and len(boxes_xyxy):
-        return refined_masks(predictor, refine, boxes=boxes_xyxy)
-    return predictor.predict_boxes(boxes_xyxy, mask_index=2)
-
-
-def clean_planes(planes, min_area):
-    """``remove_small_regions(planes, min_area, "both")`` on a list of [H, W] planes (numpy arrays or device tensors) or a device
-    [n, H, W] tensor: device uint8 [n, H, W] of 0 / 1. ``min_area`` 0, or no plane: what was given."""
-    if not min_area or planes is None or len(planes) == 0:
-        return planes
-    from ovmono3d_amd.masks import remove_small_regions
-    dev = torch.device("cuda", torch.cuda.current_device())
-    if not isinstance(planes, torch.Tensor):
-        planes = torch.stack([p.to(dev) if isinstance(p, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(p)).to(dev) for p in planes])
-    return remove_small_regions(planes, int(min_area), "both")[0]
-
-
-def dump_masks(mask_dir, image_id, positions, planes, fmt="npz"):
-    """The <image_id>.npz file load_masks reads; fmt "rle": <image_id>.rle.json = {"index": [...], "masks": [COCO RLE, ...]} instead,
-    encoded on the device (ovmono3d_amd.masks.encode_rle): the planes stay there and only the strings are read back."""
-    os.makedirs(mask_dir, exist_ok=True)
-    if fmt == "rle":
-        from ovmono3d_amd.masks import encode_rle
-        dev = torch.device("cuda", torch.cuda.current_device())
-        stack = torch.stack([p.to(dev) if isinstance(p, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(p)).to(dev) for p in planes])
-        with open(os.path.join(mask_dir, f"{image_id}.rle.json"), "w") as f:
-            json.dump({"index": [int(i) for i in positions], "masks": encode_rle(stack)}, f)
-        return
-    planes = [p.cpu().numpy() if isinstance(p, torch.Tensor) else np.asarray(p) for p in planes]
-    H, W = planes[0].shape
-    np.savez_compressed(os.path.join(mask_dir, f"{image_id}.npz"), masks=np.stack(planes).astype(np.uint8).reshape(-1, H, W),
-                        index=np.asarray(positions, np.int64))
-
-
-def load_masks(mask_dir, image_id, height, width):
-    """{position in the instance list: uint8 [H, W]} of one image; empty when the image has no mask file. <image_id>.npz when it
-    exists (host arrays), else <image_id>.rle.json, decoded on the device (device tensors of 0 / 1)."""
-    path = os.path.join(mask_dir, f"{image_id}.npz")
-    if not os.path.exists(path):
-        path = os.path.join(mask_dir, f"{image_id}.rle.json")
-        if not os.path.exists(path):
-            return {}
-        from ovmono3d_amd.masks import decode_rle
-        with open(path) as f:
-            z = json.load(f)
-        index, records = z["index"], z["masks"]
-        if len(index) != len(records) or any(list(r["size"]) != [height, width] for r in records):
-            raise SystemExit(f"{path}: {len(records)} masks / {len(index)} index entries do not fit a {height} x {width} image")
-        if not records:
-            return {}
-        planes = decode_rle(records, torch.device("cuda", torch.cuda.current_device()))
-        return {int(i): planes[k] for k, i in enumerate(index)}
-    z = np.load(path)
-    masks, index = z["masks"], z["index"]
-    if masks.ndim != 3 or tuple(masks.shape[1:]) != (height, width) or len(index) != len(masks):
-        raise SystemExit(f"{path}: masks {tuple(masks.shape)} / index {tuple(index.shape)} do not fit a {height} x {width} image")
-    return {int(i): (masks[k] != 0).astype(np.uint8) for k, i in enumerate(index)}
+    return lift_boxes(d, K, boxes_xyxy=boxes_xyxy, masks=None if masks is None else planes_on_device(masks, dev), params=params)
 
 
 def run(args):
@@ -181,13 +90,11 @@ def run(args):
             raise SystemExit("--mask sam needs --sam-weights FILE and --image-root DIR")
         from ovmono3d_amd.sam import build_sam
         predictor = build_sam(args.sam_arch, args.sam_weights, image_size=args.sam_image_size)
-    depthpro = None
+    depth_source = None
     if args.depth == "depthpro":
         if not args.depthpro_weights or not args.image_root:
             raise SystemExit("--depth depthpro needs --depthpro-weights FILE and --image-root DIR")
-        from ovmono3d_amd.depthpro import build_depthpro
-        dp_config = json.loads(args.depthpro_config) if args.depthpro_config else None
-        depthpro = build_depthpro(args.depthpro_weights, config=dp_config)
+        depth_source = build_depth_prompt(args.depthpro_weights, args.depthpro_focal, args.depthpro_config, args.dump_depth)
     out, n_in, n_low, n_skip, n_lifted = [], 0, 0, 0, 0
     for rec in oracle:
         im = images.get(rec["image_id"])
@@ -201,18 +108,15 @@ def run(args):
         new_instances = []
         if cand:
             bgr = None
-            if depthpro is not None:
-                bgr = read_bgr(args.image_root, im["file_path"], H, W, depthpro.dev)
-                f_px = float(K[0][0]) if args.depthpro_focal == "K" else None
-                depth = depthpro.infer(bgr, f_px=f_px, image_format="BGR")["depth"]
-                if args.dump_depth:
-                    dump_depth(args.dump_depth, im["file_path"], depth)
+            if depth_source is not None:
+                bgr = read_bgr(args.image_root, im["file_path"], H, W, depth_source.depthpro.dev)
+                depth = depth_source(bgr, "BGR", K, file_name=im["file_path"])
             else:
                 depth = load_depth(args.depth_dir, im["file_path"], H, W)
             planes = None
             if use_sam:
                 boxes = np.asarray([xywh_to_xyxy(ins["bbox"]) for _, ins in cand], np.float64)
-                planes = list(sam_masks(predictor, args.image_root, im["file_path"], H, W, boxes, bgr=bgr, refine=args.sam_refine))
+                planes = sam_masks(predictor, args.image_root, im["file_path"], H, W, boxes, bgr=bgr, refine=args.sam_refine)
             elif not use_box:
                 have = load_masks(args.mask_dir, rec["image_id"], H, W)
                 missing = [pos for pos, _ in cand if pos not in have]
@@ -223,8 +127,7 @@ def run(args):
                 planes = [have[pos] for pos, _ in cand]
             if cand:
                 boxes = np.asarray([xywh_to_xyxy(ins["bbox"]) for _, ins in cand], np.float64)
-                if args.min_mask_region_area > 0 and planes is not None:
-                    planes = list(clean_planes(planes, args.min_mask_region_area))
+                planes = clean_planes(planes, args.min_mask_region_area)
                 lifted = lift_image(depth, K, boxes, planes, params)
                 if args.dump_masks and planes is not None:
                     dump_masks(args.dump_masks, rec["image_id"], [pos for pos, _ in cand], planes, args.mask_format)
@@ -258,62 +161,25 @@ def argument_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--oracle2d", required=True, help="oracle-2D file (tools/make_oracle2d.py): [{image_id, instances[{bbox xywh, category_id, score}]}]")
     ap.add_argument("--dataset", required=True, help="Omni3D annotation json of the same images (file_path, height, width, K)")
-    ap.add_argument("--depth", choices=("files", "depthpro"), default="files", help="files: read --depth-dir; depthpro: run Depth Pro on the device")
-    ap.add_argument("--depth-dir", default=None, help="metric depth .npz files (key 'depth'), the ones DatasetMapper3D reads (required with --depth files; "
-                                                        "refused with --depth depthpro, which would not read it)")
-    ap.add_argument("--depthpro-weights", default=None, help="Depth Pro checkpoint in Hugging Face key names (torch file or .safetensors)")
-    ap.add_argument("--depthpro-focal", choices=("estimate", "K"), default="estimate",
-                    help="estimate: the field-of-view head chooses the focal length; K: the dataset's K[0][0]")
-    ap.add_argument("--depthpro-config", default=None, metavar="JSON",
-                    help="fields of ovmono3d_amd.depthpro.DEFAULT_CONFIG to override, as a JSON object: a checkpoint of another size than "
-                         "apple/DepthPro-hf (e.g. '{\"embed_dim\": 128, \"depth\": 4, \"heads\": 2, \"crop\": 128}')")
-    ap.add_argument("--dump-depth", default=None, metavar="DIR", help="write the depth used as <DIR>/<image base name>.npz, the files --depth-dir reads")
+    add_depth_arguments(ap)
     ap.add_argument("--mask-dir", default=None, help="<image_id>.npz with 'masks' uint8 [n, H, W] and 'index' int [n]")
-    ap.add_argument("--mask", choices=("box", "sam"), default=None,
-                    help="box: the 2D box is the mask - pixels ceil(x0) <= x < ceil(x1), ceil(y0) <= y < ceil(y1), clipped to the image; "
-                         "sam: Segment Anything prompted with the box, plane [2] of its multimask outputs (the reference's rule)")
-    ap.add_argument("--sam-weights", default=None, help="segment_anything checkpoint (.pth: image_encoder.*, prompt_encoder.*, mask_decoder.*)")
-    ap.add_argument("--sam-arch", default="vit_l", help="vit_b or vit_l (vit_h has head dimension 80: refused)")
-    ap.add_argument("--sam-image-size", type=int, default=None, help=argparse.SUPPRESS)      # tests: a small encoder input
-    ap.add_argument("--sam-refine", type=int, default=0, metavar="N",
-                    help="--mask sam: N more passes per box with the previous pass's low-resolution logits as mask_input (default 0: the reference's single pass)")
+    add_mask_arguments(ap)
     ap.add_argument("--image-root", default=None, help="directory the dataset's file_path entries are relative to (--mask sam)")
     ap.add_argument("--dump-masks", default=None, metavar="DIR", help="write the masks used as <DIR>/<image_id>.npz, the files --mask-dir reads")
     ap.add_argument("--mask-format", choices=("npz", "rle"), default="npz",
                     help="--dump-masks: npz (planes copied to the host and deflated) or rle (<image_id>.rle.json, COCO RLE encoded on the device); "
                          "--mask-dir reads either")
-    ap.add_argument("--min-mask-region-area", type=int, default=0, metavar="N",
-                    help="clean every --mask sam / --mask-dir plane before it is lifted: holes, then islands, of fewer than N pixels are removed "
-                         "(segment_anything's remove_small_regions, on the device; a deviation from the reference, which lifts the raw plane). "
-                         "--dump-masks writes the cleaned planes. 0 (default): off. Accepted and without effect with --mask box")
     ap.add_argument("--score-threshold", type=float, default=0.30)
     ap.add_argument("--output", required=True, help=".pth (torch.save, as the reference) or .json")
     return ap
 
 
 def check_args(args, parser=None):
-    """What argparse's ``required`` cannot say: --depth-dir is required unless Depth Pro supplies the depth."""
-    if args.depth == "files" and not args.depth_dir:
-        msg = "the following arguments are required: --depth-dir (or --depth depthpro)"
-        if parser is not None:
-            parser.error(msg)
-        raise SystemExit(msg)
-    if getattr(args, "sam_refine", 0) < 0 or (getattr(args, "sam_refine", 0) > 0 and args.mask != "sam"):
-        msg = "--sam-refine N needs N >= 0 and --mask sam"
-        if parser is not None:
-            parser.error(msg)
-        raise SystemExit(msg)
-    if getattr(args, "min_mask_region_area", 0) < 0:
-        msg = "--min-mask-region-area N needs N >= 0"
-        if parser is not None:
-            parser.error(msg)
-        raise SystemExit(msg)
-    if args.depth == "depthpro" and args.depth_dir:
-        msg = "--depth depthpro computes the depth: --depth-dir would not be read (to write depth files use --dump-depth DIR)"
-        if parser is not None:
-            parser.error(msg)
-        raise SystemExit(msg)
-    return args
+    """Exit status 2 for what cannot work, before any device call: the shared depth and mask checks; --depth-dir is required unless
+    Depth Pro supplies the depth."""
+    parser = parser if parser is not None else argument_parser()
+    check_depth_arguments(args, parser, None, files_need_dir=True)
+    return check_mask_arguments(args, parser)
 
 
 def main():
