@@ -48,6 +48,16 @@ points - tinted per box as in the novel view - and the kept boxes as vertices, f
 viewer. The points are compacted and packed on the device (``ovmono3d_amd.vis.scene_ply``); ``--ply-stride N``, ``--ply-max-depth M`` and
 ``--ply-frame camera|opengl`` as in demo/demo.py.
 
+``MODEL.AMD.GEO_UPRIGHT True`` among the trailing options (default False: every file as without it, no new file) stands the boxes
+upright on the floor: the plane is fitted once per image to its depth map on the device (``ovmono3d_amd.geo.ground_plane``: RANSAC over
+plane hypotheses, then a least-squares refinement) and every instance is lifted in the frame in which the floor's normal is the vertical
+axis, so a pitched or rolled camera no longer tilts the boxes. A declared deviation: the reference takes the camera for level.
+``<name>_ground.json`` holds ``status``, ``upright``, ``normal`` and ``offset`` of the plane in the camera's frame (x right, y down, z
+forward: the points with normal . p + offset = 0; offset is the camera's height above the floor), ``n_points``, ``n_inliers`` and
+``share``; every record of ``<name>_dets.json`` gets ``height_above_ground`` (metres, the lowest corner; negative: below the floor).
+Where no plane is found the image is lifted level, the file says so and ``<name>_dets.json`` is that of a run without the key. The
+fit's settings (``ovmono3d_amd.geo.GroundParams``) are defaults nobody has tuned on real depth maps.
+
 The LIFT model is not built: ``MODEL.WEIGHTS`` is not needed, the config supplies the detector's settings and ``OUTPUT_DIR``.
 """
 import argparse
@@ -68,7 +78,7 @@ from ovmono3d_amd.data.gpu_jpeg import read_image_device, write_jpeg  # noqa: E4
 from ovmono3d_amd.data.gpu_resize import ResizeShortestEdgeGPU  # noqa: E402
 from ovmono3d_amd.defaults import make_cfg  # noqa: E402
 from ovmono3d_amd.gdino.detector import build_detector  # noqa: E402
-from ovmono3d_amd.geo import GeoParams, lift_boxes  # noqa: E402
+from ovmono3d_amd.geo import GROUND_STATUS_NAMES, GeoParams, ground_plane, lift_boxes  # noqa: E402
 from ovmono3d_amd.geo.sources import (add_mask_arguments, box_masks, check_mask_arguments, clean_planes, detect_boxes, point_masks,  # noqa: E402
                                       sam_masks, xywh_to_xyxy)
 from ovmono3d_amd.masks import encode_rle, overlay_masks  # noqa: E402
@@ -158,9 +168,10 @@ def build_run(args, cfg, dev):
 
 
 # ---- step 3
-def lift_records(depth, K, params, cats, boxes, scores, classes, cand, planes):
-    """lift_boxes on the candidates: (demo.py's records of the lifted ones, their positions among the candidates)."""
-    lifted = lift_boxes(depth, K, boxes_xyxy=boxes[cand], masks=list(planes) if planes is not None else None, params=params)
+def lift_records(depth, K, params, cats, boxes, scores, classes, cand, planes, ground=None):
+    """lift_boxes on the candidates: (demo.py's records of the lifted ones, their positions among the candidates). ground: the image's
+    GroundCall (MODEL.AMD.GEO_UPRIGHT) or None."""
+    lifted = lift_boxes(depth, K, boxes_xyxy=boxes[cand], masks=list(planes) if planes is not None else None, params=params, frame=ground)
     out, kept_idx = [], []
     for k, (i, box) in enumerate(zip(cand, lifted)):
         if box is None:
@@ -170,7 +181,18 @@ def lift_records(depth, K, params, cats, boxes, scores, classes, cand, planes):
         out.append({"category": cats[ci] if 0 <= ci < len(cats) else ci, "score": float(scores[i]),
                     "bbox3D": list(box["center_cam"]) + list(box["dimensions"]), "pose": box["pose"], "corners3D": box["bbox3D"],
                     "center_2D": list(box["center_2D"]), "bbox2D": [float(v) for v in boxes[i]]})
+        if "height_above_ground" in box:
+            out[-1]["height_above_ground"] = box["height_above_ground"]
     return out, kept_idx
+
+
+def write_ground(output_dir, im_name, g):
+    """<name>_ground.json of a fitted plane (OvmGroundResult), in the camera's frame: the lift's frame with y and z flipped."""
+    found = g.status == 0
+    with open(os.path.join(output_dir, im_name + "_ground.json"), "w") as f:
+        json.dump({"status": GROUND_STATUS_NAMES[g.status], "upright": found, "normal": [g.normal[0], -g.normal[1], -g.normal[2]] if found else None,
+                   "offset": g.offset if found else None, "n_points": g.n_points, "n_inliers": g.n_inliers,
+                   "share": g.n_inliers / g.n_points if g.n_points else 0.0}, f)
 
 
 # ---- step 4
@@ -228,17 +250,22 @@ def do_test(args, cfg):
         lap("read")
         boxes, scores, classes, cand, masks = run.instances(args, cfg, run, im, im_name, cats)
         lap("boxes")
-        out, kept_idx, planes, depth = [], [], None, None
+        out, kept_idx, planes, depth, ground = [], [], None, None, None
         if cand:
             if run.depth_source is not None:
                 depth = run.depth_source(im, "BGR", K, file_name=name)
             else:
                 depth = torch.from_numpy(load_depth(args.depth_dir, name, h, w)).to(dev)
             lap("depth")
+            if cfg.MODEL.AMD.get("GEO_UPRIGHT", False):                      # enqueued here, read with the lift's results
+                ground = ground_plane(depth, K)
+                lap("ground")
             planes, boxes[cand] = masks(boxes[cand])
             lap("masks")
-            out, kept_idx = lift_records(depth, K, params, cats, boxes, scores, classes, cand, planes)
+            out, kept_idx = lift_records(depth, K, params, cats, boxes, scores, classes, cand, planes, ground)
             lap("lift")
+            if ground is not None:
+                write_ground(cfg.OUTPUT_DIR, im_name, ground.read())
         print("File: {} with {} dets ({} boxes at or above the threshold, {} not lifted)".format(im_name, len(out), len(cand), len(cand) - len(out)))
         write_outputs(args, cfg, im, K, im_name, out, kept_idx, boxes[cand], planes, depth)
         lap("views")

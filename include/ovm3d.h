@@ -1319,6 +1319,81 @@ int ovm_geo_dbscan(const double* points, int32_t n, double eps, int32_t min_samp
  * get_cuboid_verts_faces of the float32-rounded center, dimensions and pose, computed in float32 as the reference does. */
 int ovm_host_geo_box(const OvmGeoResult* result, const double* K, OvmGeoBox* box);
 
+/* ---- OVMono3D-GEO: the ground plane, and boxes upright to it (ours; off by default everywhere) ------------------------------------
+ * The lift above takes the camera for level: yaw is fitted in the camera's (x, z) plane and the box's vertical axis is the camera's
+ * y axis, so under a pitched or rolled camera the boxes lean with it. The reference has the same defect. A declared deviation,
+ * used only where a caller asks for it: the floor is fitted to the depth map (RANSAC over plane hypotheses, then a least-squares
+ * refinement), and the lift runs in the frame in which the floor's normal is +y.
+ *
+ * All arithmetic is fp64 (no fused multiply-adds); all points are in the lift's frame, step 1 above:
+ * p = (z (x - cx) / fx, -(z (y - cy) / fy), -z), in which "up" is +y. A plane is (n, d), |n| = 1: the points with n . p + d = 0;
+ * the camera, at the origin, is d above it. The numpy restatement is tests/ground_oracle.py.
+ *
+ * Steps:
+ *  1. points: the pixels (y, x) with y % stride == 0 and x % stride == 0 in row-major order whose depth is finite, > 0 and, with
+ *     max_depth > 0, <= max_depth, compacted in that order and un-projected; n_points = n is their number. n < 3: OVM_GROUND_TOO_FEW.
+ *  2. hypothesis h = 0 .. hypotheses-1: the points i_j = mix(seed * 0x9E3779B9 + 3 h + j) % n, j = 0, 1, 2, in 32-bit unsigned
+ *     arithmetic, mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16.
+ *     c = (p1 - p0) x (p2 - p0); invalid when two indices coincide or |c|^2 <= 1e-12 |p1 - p0|^2 |p2 - p0|^2.
+ *     n = c / |c|, negated when n_y < 0; d = -n . p0. Invalid too when n_y < cos(max_tilt_deg) (a wall) or d <= 0 (the camera is
+ *     not above the plane: a ceiling).
+ *  3. count[h] = the number of points with |n . p + d| <= thresh + thresh_rel * |p_z|, n . p = (n_x p_x + n_y p_y) + n_z p_z;
+ *     -1 for an invalid hypothesis. Integer sums: the counts do not depend on any order.
+ *  4. best_hyp = the largest count, the lowest h on ties; hyp_inliers its count. No valid hypothesis, or
+ *     hyp_inliers < min_share * n: OVM_GROUND_NO_PLANE.
+ *  5. with refine: centroid and 3 x 3 scatter matrix of the best hypothesis' inliers (two passes, partial sums over 1024 points
+ *     added in a fixed tree: the same bits run to run), the eigenvector of its smallest eigenvalue (cyclic Jacobi, 12 sweeps),
+ *     negated when n_y < 0, d = -n . centroid; its inliers are counted as in step 3. It replaces the hypothesis when it passes the
+ *     tilt and d > 0 tests of step 2 and its count is >= hyp_inliers; n_inliers is the count of the plane kept.
+ *  6. frame = U, the shortest-arc rotation with U n = (0, 1, 0), row-major: U = I + [a]x + [a]x^2 / (1 + n_y), a = n x e_y.
+ * status != OVM_GROUND_OK: frame is the identity, normal / offset / n_inliers are zero; best_hyp is -1 and the hyp_ fields zero when
+ * no hypothesis was valid, else they describe the best one (which min_share then refused).
+ *
+ * Not measured: the defaults of thresh, thresh_rel and min_share are settings chosen from the noise model of the synthetic scenes
+ * of the tests; nobody has tuned them on real Depth Pro maps. */
+enum { OVM_GROUND_OK = 0, OVM_GROUND_TOO_FEW = 1, OVM_GROUND_NO_PLANE = 2 };
+
+typedef struct OvmGroundParams {    /* defaults: 0.02, 0.01, 45, 0.10, 0, 512, 4, 0, 1 */
+  double thresh;                    /* inlier band, metres ... */
+  double thresh_rel;                /* ... plus this per metre of |p_z| (depth noise grows with depth) */
+  double max_tilt_deg;              /* largest angle between the plane's normal and the camera's up axis; in (0, 90) */
+  double min_share;                 /* the best hypothesis needs this share of the points; in [0, 1] */
+  double max_depth;                 /* points beyond it are not taken; 0: no cut */
+  int32_t hypotheses;               /* 1 .. 4096 */
+  int32_t stride;                   /* >= 1: every stride-th pixel of every stride-th row */
+  uint32_t seed;
+  int32_t refine;                   /* 0 / 1: step 5 */
+  int32_t reserved[2];
+} OvmGroundParams;
+
+typedef struct OvmGroundResult {
+  double normal[3], offset;         /* the plane kept: n and d */
+  double frame[9];                  /* U, row-major */
+  double hyp_normal[3], hyp_offset; /* the best hypothesis */
+  int32_t n_points, n_valid_hyp, best_hyp, hyp_inliers, n_inliers;
+  int32_t status;                   /* OVM_GROUND_* */
+} OvmGroundResult;
+
+int ovm_geo_ground_default_params(OvmGroundParams* params);
+/* Workspace bytes of ovm_geo_ground_plane for an H x W map; nothing touches the device. */
+int ovm_geo_ground_workspace(int32_t H, int32_t W, const OvmGroundParams* params, int64_t* bytes);
+/* Steps 1 to 6: one stream-ordered launch sequence, no device-to-host read, no wait for the device. depth: device fp32 [H][W]; K:
+ * host, row-major 3 x 3; result: device, one OvmGroundResult; hyp_counts: device int32 [hypotheses] (step 3's counts) or NULL.
+ * OVM_ERR_INVALID for null / inconsistent arguments, OVM_ERR_CAPACITY for too small a workspace - before any device work, with
+ * nothing written; the message is ovm_geo_last_error's. */
+int ovm_geo_ground_plane(const float* depth, int32_t H, int32_t W, const double* K, const OvmGroundParams* params,
+                         OvmGroundResult* result, int32_t* hyp_counts, void* workspace, int64_t workspace_bytes, ovm_stream_t stream);
+/* ovm_geo_lift in a turned frame: step 1 writes U p instead of p, U = frame (device, 9 doubles, row-major; e.g. the frame field of a
+ * device OvmGroundResult), steps 2 to 7 run unchanged on those points. frame == NULL is ovm_geo_lift, which is this call. */
+int ovm_geo_lift_frame(const float* depth, int32_t H, int32_t W, const double* K, const OvmGeoInstance* inst, int32_t n_inst,
+                       const OvmGeoParams* params, const double* frame, OvmGeoResult* results, int32_t* labels, void* workspace,
+                       int64_t workspace_bytes, ovm_stream_t stream);
+/* Host, fp64: ovm_host_geo_box for a result of ovm_geo_lift_frame. frame: host, 9 doubles (NULL: ovm_host_geo_box). The box is
+ * built as for a level camera and turned back into the camera's frame by V = F U^T F, F = diag(1, -1, -1): center_cam = V c',
+ * pose = V P', dimensions unchanged, bbox3D the float32 cuboid of the float32-rounded center, dimensions and pose, depth the
+ * center's z, center_2D its projection with K. */
+int ovm_host_geo_box_frame(const OvmGeoResult* result, const double* K, const double* frame, OvmGeoBox* box);
+
 /* ---- Segment Anything, box-prompted ------------------------------------------------------------------------------------------
  * The mask source of OVMono3D-GEO (reference tools/ovmono3d_geo.py:213-217,270-272,308-309): segment_anything's
  * SamPredictor.set_image(image) once, then predict(box=xyxy) per instance, of which the reference keeps plane [2] of the three

@@ -315,6 +315,10 @@ def get_cfg_defaults(cfg: CfgNode) -> CfgNode:
                                  # GPU_JPEG_WRITE: <name>_combine.jpg and the --vis-every samples are JPEG-encoded on the device
                                  # (data/gpu_jpeg.py write_jpeg, the same bytes as Pillow's Image.save); False: host copy + Pillow
                                  GPU_JPEG_WRITE=True,
+                                 # GEO_UPRIGHT: demo/demo_geo.py fits the floor to the image's depth map (geo.ground_plane) and lifts every
+                                 # instance upright on it, writing <name>_ground.json; a declared deviation from the reference, which takes
+                                 # the camera for level. False: the reference's lift, no new file
+                                 GEO_UPRIGHT=False,
                                  # demo.py draws <name>_combine.jpg on the device (ovmono3d_amd/vis); False: detections JSON only
                                  VIS=True))
     return cfg

@@ -115,7 +115,7 @@ const char* ovm_version(void) { return "libovm3d 0.2 (gfx950)"; }
   X(OvmSwinQkvAttnOp) X(OvmChainLin) X(OvmChainLn) X(OvmDecChainOp) X(OvmEvalCell) X(OvmJpegInfo) X(OvmJpegDecPlan)               \
   X(OvmJpegEncInfo) X(OvmSceneInput) X(OvmSceneBox) X(OvmSceneView) X(OvmSceneLayout) X(OvmSceneSegment) X(OvmPanelBox)            \
   X(OvmPanelsInput) X(OvmPanelPrim) X(OvmPanelsLayout) X(OvmGeoParams) X(OvmGeoInstance) X(OvmGeoResult) X(OvmGeoBox)              \
-  X(OvmSamConfig) X(OvmSamCandidate) X(OvmDepthProConfig)
+  X(OvmGroundParams) X(OvmGroundResult) X(OvmSamConfig) X(OvmSamCandidate) X(OvmDepthProConfig)
 
 int ovm_abi_sizeof(const char* name) {
   if (!name) return -1;

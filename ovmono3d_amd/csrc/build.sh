@@ -8,7 +8,7 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result"
 # OVM_DIAG=1: diagnostic build (in-kernel s_memtime stamps and the timing-only attention ablations of scratch/; never shipped) - delete build/ when switching
 if [ -n "$OVM_DIAG" ]; then FLAGS="$FLAGS -DOVM_DIAG"; fi
 pids=()
-OBJS="gemm gemm256 mlp_fused gemm_small elementwise attn attn64 roi_cube det2d ops gops gdino_kernels dec_chain gdino gdino_load gdino_plan box3d eval_match eval3d geo resize jpeg jpeg_enc jpeg_dec mask_rle mask_cc mask_overlay scene_ply render panels loader tower sam depthpro api"
+OBJS="gemm gemm256 mlp_fused gemm_small elementwise attn attn64 roi_cube det2d ops gops gdino_kernels dec_chain gdino gdino_load gdino_plan box3d eval_match eval3d geo ground resize jpeg jpeg_enc jpeg_dec mask_rle mask_cc mask_overlay scene_ply render panels loader tower sam depthpro api"
 for f in $OBJS; do
   if [ ! -f build/$f.o ] || [ $f.hip -nt build/$f.o ] || [ -n "$(find . -maxdepth 1 -name '*.hpp' -newer build/$f.o)" ] || [ ../../include/ovm3d.h -nt build/$f.o ]; then
     # at most 16 compiles at once

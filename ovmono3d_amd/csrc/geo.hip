@@ -23,6 +23,7 @@
 #include <mutex>
 #include <vector>
 #include "../../include/ovm3d.h"
+#include "geo_point.hpp"
 
 // The restatement is numpy: no fused multiply-adds except where a function opts in.
 #pragma clang fp contract(off)
@@ -150,7 +151,7 @@ __global__ __launch_bounds__(1024) void k_row_scan(const GeoDesc* desc, GeoState
 
 // row-major compaction of the mask pixels and un-projection in one pass
 __global__ __launch_bounds__(256) void k_scatter(const GeoDesc* desc, GeoState* state, const float* __restrict__ depth, int H, int W, double fx,
-                                                 double fy, double cx, double cy, const int32_t* rowoff, double* pts) {
+                                                 double fy, double cx, double cy, const double* __restrict__ frame, const int32_t* rowoff, double* pts) {
   const int inst = blockIdx.y, y = blockIdx.x;
   const GeoDesc d = desc[inst];
   if (d.status0 != 0 || y < d.y0 || y >= d.y1) return;
@@ -171,11 +172,8 @@ __global__ __launch_bounds__(256) void k_scatter(const GeoDesc* desc, GeoState* 
     const long idx = run + before;
     if (in && idx < d.n_decl) {
       const float zf = depth[(long)y * W + x];
-      const double z = (double)zf;
       if (!isfinite(zf)) bad = true;
-      out[3 * idx] = z * ((double)x - cx) / fx;
-      out[3 * idx + 1] = -(z * ((double)y - cy) / fy);
-      out[3 * idx + 2] = -z;
+      geo_unproject(zf, x, y, fx, fy, cx, cy, frame, out + 3 * idx);
     }
     run += all;
     __syncthreads();
@@ -644,6 +642,8 @@ hipEvent_t g_stage_ev = nullptr;
 
 }  // namespace
 
+int geo_fail(int code, const char* msg) { return fail(code, msg); }
+
 extern "C" {
 
 const char* ovm_geo_last_error(void) { return g_err; }
@@ -673,6 +673,12 @@ int ovm_geo_lift_workspace(const OvmGeoInstance* inst, int32_t n_inst, int32_t H
 int ovm_geo_lift(const float* depth, int32_t H, int32_t W, const double* K, const OvmGeoInstance* inst, int32_t n_inst,
                  const OvmGeoParams* params, OvmGeoResult* results, int32_t* labels, void* workspace, int64_t workspace_bytes,
                  ovm_stream_t stream) {
+  return ovm_geo_lift_frame(depth, H, W, K, inst, n_inst, params, nullptr, results, labels, workspace, workspace_bytes, stream);
+}
+
+int ovm_geo_lift_frame(const float* depth, int32_t H, int32_t W, const double* K, const OvmGeoInstance* inst, int32_t n_inst,
+                       const OvmGeoParams* params, const double* frame, OvmGeoResult* results, int32_t* labels, void* workspace,
+                       int64_t workspace_bytes, ovm_stream_t stream) {
   if (!depth || !K || !results || !workspace) return fail(OVM_ERR_INVALID, "geo: null depth / K / results / workspace");
   const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
   if (!std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy) || fx == 0.0 || fy == 0.0)
@@ -721,7 +727,7 @@ int ovm_geo_lift(const float* depth, int32_t H, int32_t W, const double* K, cons
   hipLaunchKernelGGL(k_init, ig, dim3(64), 0, s, desc, state, results, n_inst);
   hipLaunchKernelGGL(k_row_count, rg, dim3(256), 0, s, desc, H, W, rowcnt);
   hipLaunchKernelGGL(k_row_scan, dim3((unsigned)n_inst), dim3(1024), 0, s, desc, state, results, H, rowcnt, rowoff);
-  hipLaunchKernelGGL(k_scatter, rg, dim3(256), 0, s, desc, state, depth, H, W, fx, fy, cx, cy, rowoff, pts);
+  hipLaunchKernelGGL(k_scatter, rg, dim3(256), 0, s, desc, state, depth, H, W, fx, fy, cx, cy, frame, rowoff, pts);
   if (stage >= 2) {
     const dim3 cg((unsigned)P.max_chunks, (unsigned)n_inst);
     hipLaunchKernelGGL(k_partial<0>, cg, dim3(256), 0, s, desc, state, pts, P.max_chunks, partial);
@@ -773,7 +779,9 @@ int ovm_geo_dbscan(const double* points, int32_t n, double eps, int32_t min_samp
   return hipGetLastError() == hipSuccess ? OVM_OK : fail(OVM_ERR_HIP, "geo: kernel launch failed");
 }
 
-int ovm_host_geo_box(const OvmGeoResult* r, const double* K, OvmGeoBox* box) {
+int ovm_host_geo_box(const OvmGeoResult* r, const double* K, OvmGeoBox* box) { return ovm_host_geo_box_frame(r, K, nullptr, box); }
+
+int ovm_host_geo_box_frame(const OvmGeoResult* r, const double* K, const double* frame, OvmGeoBox* box) {
   if (!r || !K || !box) return fail(OVM_ERR_INVALID, "geo: null argument");
   if (r->status != OVM_GEO_OK) return fail(OVM_ERR_INVALID, "geo: the instance was not lifted (status != OVM_GEO_OK)");
   // gen_8corners with the reference's swapped names: y_min = max y, z_min = max z, so dy and dz are negative
@@ -804,7 +812,20 @@ int ovm_host_geo_box(const OvmGeoResult* r, const double* K, OvmGeoBox* box) {
   box->dimensions[0] = dist(0, 4);
   box->dimensions[1] = dist(0, 3);
   box->dimensions[2] = dist(0, 1);
-  const double R[9] = {c, 0.0, s, 0.0, 1.0, 0.0, -s, 0.0, c};
+  double R[9] = {c, 0.0, s, 0.0, 1.0, 0.0, -s, 0.0, c};
+  if (frame) {
+    // back into the camera's frame: V = F U^T F, F = diag(1, -1, -1), so V[i][j] = f_i f_j U[j][i]
+    static const double f[3] = {1.0, -1.0, -1.0};
+    double V[9], cc[3], P[9];
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) V[3 * i + j] = f[i] * f[j] * frame[3 * j + i];
+    for (int i = 0; i < 3; ++i) {
+      cc[i] = (V[3 * i] * box->center_cam[0] + V[3 * i + 1] * box->center_cam[1]) + V[3 * i + 2] * box->center_cam[2];
+      for (int j = 0; j < 3; ++j) P[3 * i + j] = (V[3 * i] * R[j] + V[3 * i + 1] * R[3 + j]) + V[3 * i + 2] * R[6 + j];
+    }
+    std::memcpy(box->center_cam, cc, sizeof(cc));
+    std::memcpy(R, P, sizeof(P));
+  }
   std::memcpy(box->pose, R, sizeof(R));
   box->depth = box->center_cam[2];
   box->center_2D[0] = (K[0] * box->center_cam[0]) / box->center_cam[2] + K[2];
